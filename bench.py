@@ -12,8 +12,15 @@ the batch (independent items, no data-path collective): weak scaling.  The RCCL 
 the result shards to rank 0 is timed separately and reported beside the main number.
 
 Prints ONE JSON line (rank 0).  `roofline` describes the dominant kernel, timed with HIP
-events on the launch stream inside the timed region; `cpu_baseline` is the CPU oracle (the C
-restatement of the reference's src/eval.rs loop) timed on this host on a bounded sample.
+events on the launch stream inside the timed region.  A plain run does only what that line
+needs: set-up, warm-up, the timed steps.  --full adds the side measurements: `cpu_baseline`
+(the CPU oracle, the C restatement of the reference's src/eval.rs loop, timed on this host on a
+bounded sample), `matrix_representation`, `single_item_latency`, the other single-GPU
+configurations of the default workload (`configs`) and, with N > 1, the gather.
+
+--dump-outputs DIR writes the result rows of the last timed step to DIR/result.npy (rank 0's
+shard; a fixed, seeded sample of the rows when they exceed DUMP_BYTES).  The inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -29,13 +36,14 @@ PEAK_FP32_TFLOPS = 157.3   # MI355X_MICROARCH.md: FP32 vector == FP32 MFMA peak
 PEAK_FP64_TFLOPS = 78.6     # datasheet (64 cycles per v_mfma_f64_16x16x4_f64 at 2.4 GHz); not in the local guide
 MEASURED_FP64_MFMA_TFLOPS = 74.3   # tools/microbench/mfma_f64_rate.hip on this pool (profiles/r03_microbench_mfma_f64_rate.txt)
 POWER_CAP_W, POWER_IDLE_W, POWER_W_PER_TFLOPS, POWER_W_PER_TBPS = 1400.0, 250.0, 7.2, 129.0   # measured, round 3 (DESIGN.md 4.1 "A power roofline")
-# the other single-GPU BASELINE configurations the default line also times, then (round 4) one workload per kernel family added
-# this round: n = 6 on the matrix cores, the projected rotor sandwich (two lists, one launch), the versor inverse and
-# d = (a + b * c).g(2) beyond R^3 (whole-AST programs in one launch)
+# the other single-GPU BASELINE configurations the default workload's --full line also times, then (round 4) one workload
+# per kernel family added this round: n = 6 on the matrix cores, the projected rotor sandwich (two lists, one launch), the
+# versor inverse and d = (a + b * c).g(2) beyond R^3 (whole-AST programs in one launch)
 SIDE_CONFIGS = ("r8", "cl41", "r12d", "gp6f32", "sand9g1", "vinv12", "cfg1_8")
 PEAK_HBM_GBPS = 8000.0     # spec; 6290 measured float4 copy
 GATHER_WATCHDOG_S = 240     # the multi-GPU gather legs give up after this long (the throughput line is printed regardless)
 GATHER_FAILED_EXIT = 3      # ... and the job then ends with this status: a hung or failed exchange is a FAILED run
+DUMP_BYTES = 32 << 20       # --dump-outputs writes at most this much: every result row, or a seeded sample of the rows
 
 
 def workload_spec(name):
@@ -426,6 +434,21 @@ def side_config(name, dev, stream, steps, warmup):
     return res
 
 
+def dump_outputs(out_t, directory):
+    """DIR/result.npy: the result rows of the last timed step in the workload's value type -- all of them when they fit in
+    DUMP_BYTES, else a sample of rows drawn by a fixed seed from the batch size alone, in ascending order (the same rows in
+    every run with the same arguments)."""
+    import numpy as np
+    import torch
+    batch = out_t.shape[0]
+    rows = min(batch, max(1, DUMP_BYTES // (out_t.shape[1] * out_t.element_size())))
+    if rows < batch:
+        idx = np.sort(np.random.default_rng(0).choice(batch, rows, replace=False))
+        out_t = out_t.index_select(0, torch.from_numpy(idx).to(out_t.device))
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "result.npy"), out_t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -434,13 +457,16 @@ def main():
     ap.add_argument("--workload", default="r12")
     ap.add_argument("--batch", type=int, default=0, help="input sets per GPU (default: the workload's; with --gpus N > 1 "
                     "and the default workload: BASELINE configs[3], 1,048,576 input sets over all GPUs)")
+    ap.add_argument("--full", action="store_true", help="also run the side measurements: CPU baseline, matrix representation, "
+                    "single-item latency, the other configurations of the default workload, the N > 1 gather")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the result rows of the last timed step to DIR/result.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--gather-chunks", type=int, default=4)
     ap.add_argument("--no-alt", action="store_true", help="skip the opt-in matrix-representation side measurement")
     ap.add_argument("--no-latency", action="store_true", help="skip the single-item latency side measurement")
     ap.add_argument("--no-configs", action="store_true", help="skip the other single-GPU BASELINE configurations (r8, cl41, r12d) "
-                    "the default line also times")
+                    "the default line also times with --full")
     ap.add_argument("--flags", type=lambda x: int(x, 0), default=0, help="extra GAAST_FLAG_* bits for the program (A/B measurements)")
     args = ap.parse_args()
 
@@ -464,7 +490,7 @@ def main():
     # CPU baseline first (rank 0, N = 1 only): its all-cores leg forks workers, which must happen before
     # this process initialises the GPU
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(workload_spec(args.workload))
 
     import torch
@@ -483,6 +509,7 @@ def main():
     rccl_ranks = None
     lib_comm = False
     lib_comm_error = None
+    want_gather = world > 1 and args.full and not args.no_gather
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         if rehearsal:
@@ -503,7 +530,7 @@ def main():
         transport = os.environ.get("GAAST_BENCH_REHEARSAL_TRANSPORT") if rehearsal else None
         if transport:
             ga._lib.check(L.gaast_hip_comm_set_library(transport.encode()))
-        if not rehearsal or transport:
+        if want_gather and (not rehearsal or transport):
             # the library's own communicator (what a Rust host would use: include/gaast_hip.h, multi-GPU): the
             # 128-byte id travels over the rendezvous torch.distributed already provides
             # (a failure here is reported in the JSON and the gather falls back to torch.distributed: the throughput
@@ -587,7 +614,6 @@ def main():
         ins.append(ga.DeviceMV.wrap_tensor(t, n, g))
     # the root's result rows live inside the gathered buffer (no local copy at gather time)
     gathered_t = gathered = None
-    want_gather = world > 1 and not args.no_gather
     if want_gather and rank == 0 and lib_comm:
         gathered_t = torch.empty((global_batch, out_len), device=dev, dtype=tdt)
         gathered = ga.DeviceMV.wrap_tensor(gathered_t, n, ga.GradeSet(out_mask))
@@ -632,11 +658,13 @@ def main():
         wall = max_over_ranks(wall, device=None if rehearsal else dev)
     step_ms = [e0.elapsed_time(e1) for e0, e1 in evs]
     kernel_ms = sum(step_ms) / len(step_ms)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out_t, args.dump_outputs)
 
     # the same products through the opt-in matrix-representation kernel (not the reference's summation
     # order, so never `value`): reported beside the headline, with its distance from the default path
     alt = None
-    if args.workload in ("r12", "r12d", "r8", "r8d") and rank == 0 and world == 1 and not args.no_alt:
+    if args.workload in ("r12", "r12d", "r8", "r8d") and rank == 0 and world == 1 and args.full and not args.no_alt:
         spec_alt = wl["build"](*exprs).specialize(ga.MetricAlgebra(wl["metric"]), dtype=dtype, flags=ga.FLAG_SPINOR_GEMM)
         out_alt_t = torch.empty_like(out_t)
         out_alt = ga.DeviceMV.wrap_tensor(out_alt_t, n, ga.GradeSet(out_mask))
@@ -672,7 +700,7 @@ def main():
     # what the reference actually does -- ONE input set per eval(): latency of a batch-1 evaluation through the
     # C ABI (program built once; launch + kernel + synchronize), beside the batched throughput
     latency = None
-    if rank == 0 and world == 1 and not args.no_latency:
+    if rank == 0 and world == 1 and args.full and not args.no_latency:
         one_in = [ga.DeviceMV.wrap_tensor(t[:1], n, g) for t, g in zip(in_t, wl["inputs"])]
         one_out_t = torch.empty((1, out_len), device=dev, dtype=tdt)
         one_out = ga.DeviceMV.wrap_tensor(one_out_t, n, ga.GradeSet(out_mask))
@@ -691,7 +719,7 @@ def main():
     # the other single-GPU BASELINE configurations (configs[1] R^8 f32, configs[4] R^{4,1} sandwich f64, and R^12 in the
     # reference's value type), each with its own roofline object: a few steps each, after the headline's buffers are idle
     side = []
-    if args.workload == "r12" and rank == 0 and world == 1 and not args.no_configs and not args.batch and not args.flags:
+    if args.workload == "r12" and rank == 0 and world == 1 and args.full and not args.no_configs and not args.batch and not args.flags:
         for name in SIDE_CONFIGS:
             try:
                 side.append(side_config(name, dev, stream, steps=20, warmup=5))

@@ -30,6 +30,25 @@ def test_cpu_baseline_fields():
     json.dumps(base)   # must be serialisable into the one JSON line
 
 
+def test_dump_outputs_writes_every_row_or_a_fixed_sample(monkeypatch, tmp_path):
+    """--dump-outputs: all result rows when they fit in DUMP_BYTES; beyond that the same seeded rows, in ascending order, in
+    every run -- so that two builds can be compared row for row."""
+    import numpy as np
+    import torch
+    out = torch.arange(100 * 8, dtype=torch.float64).reshape(100, 8)
+    bench.dump_outputs(out, str(tmp_path / "all"))
+    assert np.array_equal(np.load(tmp_path / "all" / "result.npy"), out.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 10 * 8 * 8)
+    bench.dump_outputs(out, str(tmp_path / "a"))
+    bench.dump_outputs(out.float(), str(tmp_path / "b"))
+    a, b = np.load(tmp_path / "a" / "result.npy"), np.load(tmp_path / "b" / "result.npy")
+    assert a.shape == (10, 8) and a.dtype == np.float64 and b.shape == (20, 8) and b.dtype == np.float32
+    rows = a[:, 0] // 8
+    assert np.array_equal(a, out.numpy()[rows.astype(int)]) and np.all(np.diff(rows) > 0)
+    bench.dump_outputs(out, str(tmp_path / "c"))
+    assert np.array_equal(np.load(tmp_path / "c" / "result.npy"), a)
+
+
 def test_traffic_is_reported_only_for_the_kernel_and_library_it_was_measured_with(monkeypatch, tmp_path):
     """roofline.traffic comes from profiles/traffic.json (tools/pmc_traffic.py); a figure recorded for another kernel, or
     with other kernel sources than the loaded library's, is withheld and flagged stale."""

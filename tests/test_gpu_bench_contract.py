@@ -14,9 +14,13 @@ KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "
 
 @pytest.mark.parametrize("args,bound", [(["--workload", "r12", "--batch", "512"], "mfma"),
                                         (["--workload", "cl41", "--batch", "65536"], "hbm")])
-def test_bench_prints_one_json_line(args, bound):
+def test_bench_prints_one_json_line(args, bound, tmp_path):
+    """A plain run (no --full) prints the headline line and nothing of the side measurements; --dump-outputs writes the
+    result rows of the last timed step (all of them at these batch sizes) in the workload's value type."""
+    import numpy as np
     run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
-                          "--no-cpu-baseline"] + args, capture_output=True, text=True, cwd=ROOT, timeout=600)
+                          "--no-cpu-baseline", "--dump-outputs", str(tmp_path)] + args, capture_output=True, text=True, cwd=ROOT,
+                         timeout=600)
     assert run.returncode == 0, run.stderr[-2000:]
     lines = [l for l in run.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, run.stdout[-2000:]
@@ -28,6 +32,10 @@ def test_bench_prints_one_json_line(args, bound):
     r = d["roofline"]
     assert r["bound"] == bound and r["unit"] == ("TFLOP/s" if bound == "mfma" else "GB/s")
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9 and set(r) >= {"bound", "achieved", "peak", "unit", "frac", "traffic"}
+    assert not {"cpu_baseline", "configs", "matrix_representation", "single_item_latency", "gather"} & set(d), sorted(d)
+    res = np.load(tmp_path / "result.npy")
+    assert res.shape[0] == d["config"]["batch_per_gpu"] and res.dtype == {"f32": np.float32, "f64": np.float64}[d["dtype"]]
+    assert np.isfinite(res).all() and np.abs(res).max() > 0
 
 
 @pytest.mark.parametrize("with_transport", [True, False])
@@ -43,7 +51,7 @@ def test_bench_self_launches_two_ranks_and_gathers(tmp_path, with_transport):
     if with_transport:
         env["GAAST_BENCH_REHEARSAL_TRANSPORT"] = build_rccl_stub(tmp_path)
     run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--batch", "300"], capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
+                          "--batch", "300", "--full"], capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
     assert run.returncode == 0, run.stderr[-3000:]
     lines = [l for l in run.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, run.stdout[-2000:]
@@ -68,18 +76,18 @@ def test_a_failed_gather_ends_the_job_non_zero(tmp_path):
     env["GAAST_BENCH_REHEARSAL"] = "1"
     env["GAAST_BENCH_FAIL_GATHER"] = "1"
     run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-                          "--batch", "64"], capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
+                          "--batch", "64", "--full"], capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
     assert run.returncode == 3, (run.returncode, run.stderr[-2000:])
     d = json.loads([l for l in run.stdout.splitlines() if l.strip()][0])
     assert d["value"] > 0 and "error" in d["gather"]
 
 
 def test_default_line_carries_the_other_single_gpu_configs():
-    """The DEFAULT run (no --workload, no --batch) also times BASELINE configs[1] (R^8 f32), configs[4] (R^{4,1} sandwich,
+    """The default workload's --full run (no --workload, no --batch) also times BASELINE configs[1] (R^8 f32), configs[4] (R^{4,1} sandwich,
     f64) and R^12 in f64, each with its own roofline object, so that they stop resting on builder-run profiles -- and, since
     round 4, one workload per kernel family added that round (n = 6 on the matrix cores, the projected sandwich as one launch of
     two lists, the versor inverse and d = (a + b * c).g(2) beyond R^3 as one launch each)."""
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                           "--no-alt", "--no-latency"], capture_output=True, text=True, cwd=ROOT, timeout=900)
     assert run.returncode == 0, run.stderr[-2000:]
     d = json.loads([l for l in run.stdout.splitlines() if l.strip()][0])

@@ -44,7 +44,7 @@ def main():
         except (OSError, ValueError, KeyError):
             note = "bench line unavailable"
         with open(os.path.join(dst, f"{tag}_bench_{name}_kernel_stats.csv"), "w", newline="") as f:
-            f.write(f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-latency --workload {name}   ({tag}; {rev})\n")
+            f.write(f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 40 --warmup 5 --full --no-cpu-baseline --no-latency --workload {name}   ({tag}; {rev})\n")
             f.write(f"# {note}\n")
             w = csv.writer(f)
             for r in rows[:9]:

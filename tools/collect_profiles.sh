@@ -15,7 +15,7 @@ stats() { # name, bench args...
   name=$1; shift
   d=$out/stats_$name
   rm -rf $d; mkdir -p $d
-  rocprofv3 --kernel-trace --stats --output-format csv -d $d -- python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-latency "$@" > $d/bench.json 2> $d/log.txt || echo "stats $name failed"
+  rocprofv3 --kernel-trace --stats --output-format csv -d $d -- python3 bench.py --steps 40 --warmup 5 --full --no-cpu-baseline --no-latency "$@" > $d/bench.json 2> $d/log.txt || echo "stats $name failed"
 }
 if [ $phase != pmc ]; then
 stats r12 --workload r12
@@ -39,14 +39,14 @@ stats sand10g1 --workload sand10g1 --no-alt
 stats sand8 --workload sand8 --no-alt
 stats sand9 --workload sand9 --no-alt
 stats sand10 --workload sand10 --no-alt
-python3 bench.py > $out/bench_default.json 2> $out/bench_default.err
+python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 # the N > 1 control flow with the LIBRARY's gather over the test transport (ranks share this box's GPU)
 gcc -std=gnu11 -shared -fPIC -O1 -fvisibility=hidden -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include tests/cpp/rccl_stub.c -L/opt/rocm/lib -lamdhip64 -lpthread -Wl,-Bsymbolic -Wl,-rpath,/opt/rocm/lib -o $out/librccl_stub.so
-GAAST_BENCH_REHEARSAL=1 GAAST_BENCH_REHEARSAL_TRANSPORT=$PWD/$out/librccl_stub.so python3 bench.py --gpus 2 --steps 3 --warmup 1 --batch 4096 > $out/bench_rehearsal_2ranks.json 2> $out/bench_rehearsal.err
-GAAST_BENCH_REHEARSAL=1 GAAST_BENCH_REHEARSAL_TRANSPORT=$PWD/$out/librccl_stub.so python3 bench.py --gpus 3 --steps 2 --warmup 1 --batch 1000 > $out/bench_rehearsal_3ranks.json 2>> $out/bench_rehearsal.err
+GAAST_BENCH_REHEARSAL=1 GAAST_BENCH_REHEARSAL_TRANSPORT=$PWD/$out/librccl_stub.so python3 bench.py --gpus 2 --steps 3 --warmup 1 --batch 4096 --full > $out/bench_rehearsal_2ranks.json 2> $out/bench_rehearsal.err
+GAAST_BENCH_REHEARSAL=1 GAAST_BENCH_REHEARSAL_TRANSPORT=$PWD/$out/librccl_stub.so python3 bench.py --gpus 3 --steps 2 --warmup 1 --batch 1000 --full > $out/bench_rehearsal_3ranks.json 2>> $out/bench_rehearsal.err
 rm -f $out/librccl_stub.so
-python3 bench.py --workload r8 > $out/bench_r8.json 2>/dev/null
-python3 bench.py --workload cl41 > $out/bench_cl41.json 2>/dev/null
+python3 bench.py --workload r8 --full > $out/bench_r8.json 2>/dev/null
+python3 bench.py --workload cl41 --full > $out/bench_cl41.json 2>/dev/null
 fi
 if [ $phase != stats ]; then
 for spec in "r12:k_gp_mfma32:--workload r12" "r8:k_gp_mfma16:--workload r8" "cl41:gaast_jit:--workload cl41" "cl41g1:gaast_jit:--workload cl41g1" "r12s:k_gp_spinor12s:--workload r12s" "r12d:k_gp_mfma16:--workload r12d" "r8d:k_gp_mfma16:--workload r8d" "gp7f32:k_gp_mfma7:--workload gp7f32" "sand8:k_gp_mfma7:--workload sand8" "sand9g1:k_product_ell_chain:--workload sand9g1" "sand9:k_gp_mfma16:--workload sand9" "sand10:k_gp_mfma16:--workload sand10" "gp12f32ee:k_gp_mfma32:--workload gp12f32ee"; do

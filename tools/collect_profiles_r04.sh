@@ -32,7 +32,7 @@ stats1)
   stats sand9g1 --workload sand9g1
   stats sand10g1 --workload sand10g1
   stats sand9g1x --workload sand9g1x
-  python3 bench.py > $out/bench_default.json 2> $out/bench_default.err
+  python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err
   ;;
 stats2)
   stats vinv8 --workload vinv8
