@@ -108,6 +108,10 @@ SIGNATURES = {
     "gaast_hip_comm_count_ranks": (_ci, [C.POINTER(_ci)]),
     "gaast_hip_gather_rows": (_ci, [_vp, _vp, C.POINTER(_i64), _ci]),
     "gaast_hip_eval_gather": (_ci, [_vp, C.POINTER(_vp), _ci, _vp, _vp, C.POINTER(_i64), _ci, _ci]),
+    "gaast_hip_linmap_create": (_ci, [_ci, _pd, _ci, C.POINTER(_vp)]),
+    "gaast_hip_linmap_apply": (_ci, [_vp, _vp, _vp]),
+    "gaast_hip_linmap_destroy": (_ci, [_vp]),
+    "gaast_hip_program_create_in_basis": (_ci, [C.POINTER(ProgramDesc), _pd, C.POINTER(_vp)]),
     # ---- include/gaast_expr.h ----
     "gaast_expr_last_error": (C.c_char_p, []),
     "gaast_gs_single": (_u64, [_i64]),
@@ -119,6 +123,8 @@ SIGNATURES = {
     "gaast_component_to_blade": (_u64, [_ci, _ci, _u64]),
     "gaast_blade_to_component": (_u64, [_ci, _u64, C.POINTER(_ci)]),
     "gaast_blades_gp": (_dbl, [_ci, _pd, _u64, _u64, C.POINTER(_u64)]),
+    "gaast_metric_diagonalize": (_ci, [_ci, _pd, _pd, _pd]),
+    "gaast_compound_matrix": (_ci, [_ci, _pd, _ci, _pd]),
     "gaast_expr_retain": (_vp, [_vp]),
     "gaast_expr_release": (None, [_vp]),
     "gaast_expr_input": (_vp, [_ci, _u64, _ci]),

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .algebra import as_algebra
+from .algebra import GramAlgebra, as_algebra
 from .grade_set import GradeSet
 from .graded import DeviceMV, GradeMapMV, _mask_of
 
@@ -222,8 +222,16 @@ class SpecializedAst:
         _lib.check(_lib.lib().gaast_spec_program_desc(self._p, self.dtype, self.flags, C.byref(d)))
         return d
 
+    def _basis(self):
+        """Q of a GramAlgebra whose basis is not the identity (the program runs in the orthogonal basis f), else None."""
+        if isinstance(self.alg, GramAlgebra) and not self.alg.identity_basis():
+            return self.alg.basis
+        return None
+
     def serialize(self):
         """The flat program as bytes (program wire format, include/gaast_expr.h)."""
+        if self._basis() is not None:
+            raise ValueError("a program in a non-diagonal Gram metric cannot be serialized: the wire format carries no basis")
         d = self.program_desc()
         n = _lib.lib().gaast_program_serialize(C.byref(d), None, 0)
         buf = (C.c_ubyte * n)()
@@ -237,7 +245,12 @@ class SpecializedAst:
             _lib.init_device()
             d = self.program_desc()
             h = C.c_void_p()
-            _lib.check(_lib.lib().gaast_hip_program_create(C.byref(d), C.byref(h)))
+            q = self._basis()
+            if q is None:
+                _lib.check(_lib.lib().gaast_hip_program_create(C.byref(d), C.byref(h)))
+            else:
+                q = np.ascontiguousarray(q, dtype=np.float64)
+                _lib.check(_lib.lib().gaast_hip_program_create_in_basis(C.byref(d), q.ctypes.data_as(_lib._pd), C.byref(h)))
             self._prog = h
         return self._prog
 

@@ -1,0 +1,125 @@
+// Non-diagonal metrics (Gram matrices) and changes of basis, host side.
+//
+//   metric_diagonalize  G = Q diag(L) Q^T with Q orthogonal (cyclic Jacobi in double: no LAPACK, deterministic).  Programs are then
+//                       specialised for the orthogonal basis f_j = sum_i Q_ij e_i, whose metric diag(L) the kernels already handle.
+//   compound_matrix     the k-th compound C_k(M) of an n x n matrix: the outermorphism of M on grade k, rows and columns in the
+//                       library's component order (colex rank of the blade), entry [I][J] = det M[I, J].  Built grade by grade by
+//                       Laplace expansion along the first row of each minor, from the (k - 1)-minors.
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+#include "algebra.hpp"
+
+namespace gaast {
+
+inline bool gram_is_diagonal(int n, const double* g) {
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j)
+            if (i != j && g[i * n + j] != 0.0) return false;
+    return true;
+}
+
+// false: gram not finite / not exactly symmetric / n out of range.  basis[i * n + j] = coordinate i of f_j.
+inline bool metric_diagonalize(int n, const double* gram, double* diag, double* basis) {
+    if (n < 1 || n > 16 || !gram) return false;
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j)
+            if (!std::isfinite(gram[i * n + j]) || gram[i * n + j] != gram[j * n + i]) return false;
+    if (gram_is_diagonal(n, gram)) {   // exactly diagonal: Q = I, L = diag(G) bit for bit, original order
+        for (int i = 0; i < n; ++i) {
+            diag[i] = gram[i * n + i];
+            for (int j = 0; j < n; ++j) basis[i * n + j] = i == j ? 1.0 : 0.0;
+        }
+        return true;
+    }
+    std::vector<double> a(gram, gram + n * n), v(size_t(n * n), 0.0);
+    for (int i = 0; i < n; ++i) v[size_t(i * n + i)] = 1.0;
+    auto A = [&](int i, int j) -> double& { return a[size_t(i * n + j)]; };
+    for (int sweep = 0; sweep < 100; ++sweep) {
+        double off = 0.0;
+        for (int p = 0; p < n; ++p)
+            for (int q = p + 1; q < n; ++q) off += std::fabs(A(p, q));
+        if (off == 0.0) break;
+        for (int p = 0; p < n; ++p) {
+            for (int q = p + 1; q < n; ++q) {
+                const double apq = A(p, q);
+                if (apq == 0.0) continue;
+                // after a few sweeps an element below the last bit of both diagonal entries is dropped (it no longer moves them)
+                if (sweep > 3 && std::fabs(A(p, p)) + 100.0 * std::fabs(apq) == std::fabs(A(p, p)) &&
+                    std::fabs(A(q, q)) + 100.0 * std::fabs(apq) == std::fabs(A(q, q))) {
+                    A(p, q) = A(q, p) = 0.0;
+                    continue;
+                }
+                const double theta = (A(q, q) - A(p, p)) / (2.0 * apq);
+                double t = 1.0 / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                if (theta < 0.0) t = -t;
+                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < n; ++k) {   // A <- J^T A J, J the rotation in the (p, q) plane
+                    const double akp = A(k, p), akq = A(k, q);
+                    A(k, p) = c * akp - s * akq;
+                    A(k, q) = s * akp + c * akq;
+                }
+                for (int k = 0; k < n; ++k) {
+                    const double apk = A(p, k), aqk = A(q, k);
+                    A(p, k) = c * apk - s * aqk;
+                    A(q, k) = s * apk + c * aqk;
+                }
+                A(p, q) = A(q, p) = 0.0;
+                for (int k = 0; k < n; ++k) {
+                    double& vkp = v[size_t(k * n + p)];
+                    double& vkq = v[size_t(k * n + q)];
+                    const double x = vkp, y = vkq;
+                    vkp = c * x - s * y;
+                    vkq = s * x + c * y;
+                }
+            }
+        }
+    }
+    double lmax = 0.0;
+    for (int i = 0; i < n; ++i) lmax = std::fmax(lmax, std::fabs(A(i, i)));
+    const double tiny = 64.0 * 2.220446049250313e-16 * lmax;   // a degenerate metric stays degenerate
+    for (int j = 0; j < n; ++j) {
+        diag[j] = std::fabs(A(j, j)) <= tiny ? 0.0 : A(j, j);
+        int big = 0;   // sign of column j: its largest-magnitude entry (the first of equals) positive
+        for (int i = 1; i < n; ++i)
+            if (std::fabs(v[size_t(i * n + j)]) > std::fabs(v[size_t(big * n + j)])) big = i;
+        const double sg = v[size_t(big * n + j)] < 0.0 ? -1.0 : 1.0;
+        for (int i = 0; i < n; ++i) basis[i * n + j] = sg * v[size_t(i * n + j)] + 0.0;
+    }
+    return true;
+}
+
+// C_0 ... C_kmax of m (n x n, row-major): out[k] is C(n,k) x C(n,k), row-major, component order of grade k
+// (keep_all = false: only out[kmax] is kept, each lower grade is released once the next one is built)
+inline void compound_matrices(int n, const double* m, int kmax, std::vector<std::vector<double>>& out, bool keep_all = true) {
+    const BladeTable t(n);
+    out.assign(size_t(kmax + 1), {});
+    out[0].assign(1, 1.0);
+    for (int k = 1; k <= kmax; ++k) {
+        const size_t d = t.grade_dim[size_t(k)], dp = t.grade_dim[size_t(k - 1)];
+        const std::vector<double>& prev = out[size_t(k - 1)];
+        std::vector<double>& cur = out[size_t(k)];
+        cur.assign(d * d, 0.0);
+        for (size_t I = 0; I < d; ++I) {
+            const uint32_t bi = t.blade_of[size_t(k)][I];
+            const int i0 = __builtin_ctz(bi);              // first row of the minor
+            const size_t Ir = t.index_of[bi & (bi - 1)];   // the other rows: a (k - 1)-minor's row
+            for (size_t J = 0; J < d; ++J) {
+                uint32_t bj = t.blade_of[size_t(k)][J];
+                double acc = 0.0;
+                int tpos = 0;
+                for (uint32_t rest = bj; rest; rest &= rest - 1, ++tpos) {   // expansion along row i0: column j_t, sign (-1)^t
+                    const int jt = __builtin_ctz(rest);
+                    const double term = m[i0 * n + jt] * prev[Ir * dp + t.index_of[bj & ~(1u << jt)]];
+                    acc += (tpos & 1) ? -term : term;
+                }
+                cur[I * d + J] = acc;
+            }
+        }
+        if (!keep_all) std::vector<double>().swap(out[size_t(k - 1)]);
+    }
+}
+
+}  // namespace gaast

@@ -39,7 +39,7 @@ inline Layout make_layout(int dim, uint64_t mask) {
 }
 
 struct Step {
-    enum Kind { ZERO, AXPY, FLIP, SUNARY, PRODUCT_CSR, PRODUCT_DENSE, FUSED, EXPLOG, REDUCE_SCALE, ELEMENTWISE } kind = ZERO;
+    enum Kind { ZERO, AXPY, FLIP, SUNARY, PRODUCT_CSR, PRODUCT_DENSE, FUSED, EXPLOG, REDUCE_SCALE, ELEMENTWISE, LINMAP } kind = ZERO;
     BufRef res, a, b;
     std::string name;
     std::string hip_kernel;        // the HIP kernel (template and arguments) prepare_step picked: appended to the launch label
@@ -151,6 +151,9 @@ struct Step {
     int spinor_lam_bit = -1, spinor_has_alpha = 0;  // index basis of the matrix-representation kernels: spinor_basis.hpp
     int use_spinor = 0;  // opt-in matrix-representation kernel (GAAST_FLAG_SPINOR_GEMM): log2 of the matrix size, or 0
     uint64_t n_entries = 0;  // comp-mul count this step stands for
+    // LINMAP (gaast_hip_program_create_in_basis): res = the outermorphism of a change of basis applied to row buffer `a` -- an input
+    // slot into the orthogonal basis of the program, or the root's result back into the caller's basis (kernels_linmap.hip.hpp)
+    const void* linmap = nullptr;   // the program's map (runtime.hip: LinmapDev), borrowed
     // FUSED: the whole plan as one micro-op stream over per-item LDS slabs (u32_a = the stream)
     struct FusedInput {
         int slot, base, canon;
@@ -216,6 +219,11 @@ struct Plan {
     std::string unsupported;           // non-empty: valid in the reference, beyond this back end (program_create fails)
     std::vector<char> slot_used;       // input slots some launch reads (the others may stay unbound)
     std::string jit_source_kept;       // GAAST_FLAG_DEBUG_KEEP_JIT_SOURCE
+    // program in a non-orthonormal basis (gaast_hip_program_create_in_basis): the steps other than LINMAP read input slot i from
+    // node buffer basis_slot_buf[i] (>= 0: its rows moved into the orthogonal basis) and write the root to node buffer basis_out_buf
+    // (>= 0), which the last LINMAP step moves back into `out`
+    std::vector<int> basis_slot_buf;
+    int basis_out_buf = -1;
 };
 
 // Throws std::runtime_error (-> GAAST_ERR_INVALID_PROGRAM) on malformed input.

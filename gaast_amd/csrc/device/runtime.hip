@@ -13,6 +13,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "../common/metric_basis.hpp"
 #include "comm.hpp"
 #include "gaast_hip.h"
 #include "kernels.hip.hpp"
@@ -70,6 +71,28 @@ struct gaast_hip_mv_s {
     bool owns = false;
 };
 
+namespace {
+// The compounds C_0(M) ... C_n(M) of a linear map on the device, in the dtype they are applied in (kernels_linmap.hip.hpp)
+struct LinmapDev {
+    int n = 0;
+    int dtype = GAAST_F64;
+    void* d_mats = nullptr;
+    std::vector<int> moff;            // grade k's matrix at element moff[k]
+    int mat_total = 0;
+    int small_blocks_per_cu = 1;      // k_linmap_small: resident workgroups per CU (persistent grid)
+    LinmapDev() = default;
+    LinmapDev(const LinmapDev&) = delete;
+    LinmapDev& operator=(const LinmapDev&) = delete;
+    ~LinmapDev() {
+        if (d_mats) (void)hipFree(d_mats);
+    }
+};
+}  // namespace
+
+struct gaast_hip_linmap_s {
+    LinmapDev dev;
+};
+
 struct gaast_hip_program_s;
 
 namespace {
@@ -84,6 +107,7 @@ struct gaast_hip_program_s {
     int64_t scratch_batch = 0;
     std::vector<std::string> launch_names;
     void* d_domain = nullptr;               // exp / log extension: items refused by the domain check (unsigned long long)
+    std::unique_ptr<LinmapDev> basis_in, basis_out;   // program in a non-orthonormal basis: C_k(Q^T) and C_k(Q) (LINMAP steps)
     gaast_hip_program_s() = default;
     gaast_hip_program_s(const gaast_hip_program_s&) = delete;
     gaast_hip_program_s& operator=(const gaast_hip_program_s&) = delete;
@@ -208,6 +232,98 @@ auto pick_variant(bool scaled, bool chained, F&& f) {
     if (scaled) return f(std::true_type{}, std::false_type{});
     if (chained) return f(std::false_type{}, std::true_type{});
     return f(std::false_type{}, std::false_type{});
+}
+
+// ------------------------------------------------------------------------------------------
+// Outermorphisms (kernels_linmap.hip.hpp): rows of layout `l` (dimension m.n) -> the same layout, `batch` items
+// ------------------------------------------------------------------------------------------
+constexpr int kLinmapSmallMaxDim = 6;
+constexpr int kLinmapMaxDim = 14;   // the compounds at n = 14: C(28,14) ~ 40 M entries
+
+size_t linmap_small_lds(const LinmapDev& m, int64_t row_len, size_t elem) {
+    return (size_t((m.mat_total + 3) & ~3) + size_t(2 * kLinmapItems) * size_t(row_len + 1)) * elem;
+}
+
+template <typename T>
+int launch_linmap(const LinmapDev& m, const Layout& l, const Bound& in, const Bound& out, int64_t batch) {
+    if (batch <= 0 || l.row_len == 0) return GAAST_OK;
+    LinmapArgs<T> p;
+    std::memset(&p, 0, sizeof(p));
+    p.in = static_cast<const T*>(in.ptr);
+    p.out = static_cast<T*>(out.ptr);
+    p.mats = static_cast<const T*>(m.d_mats);
+    p.in_stride = in.stride;
+    p.out_stride = out.stride;
+    p.batch = batch;
+    p.row_len = int(l.row_len);
+    p.mat_total = m.mat_total;
+    for (int k = 0; k <= m.n; ++k) {
+        if (!((l.mask >> k) & 1ULL)) continue;
+        const int len = int(n_choose_k(uint64_t(m.n), uint64_t(k)));
+        const int g = p.n_grades++;
+        p.goff[g] = int(l.offset(k));
+        p.glen[g] = len;
+        p.moff[g] = m.moff[size_t(k)];
+        p.job0[g + 1] = p.job0[g] + (len + kLinmapBN - 1) / kLinmapBN;
+        if (m.n <= kLinmapSmallMaxDim)
+            for (int r = 0; r < len; ++r)
+                p.comp[p.goff[g] + r] = uint32_t(p.goff[g]) | uint32_t(r) << 7 | uint32_t(len) << 13 | uint32_t(p.moff[g]) << 19;
+    }
+    p.n_jobs = p.job0[p.n_grades];
+    if (m.n <= kLinmapSmallMaxDim) {
+        auto vec_ok = [&](const Bound& b) {
+            return b.stride == l.row_len && reinterpret_cast<uintptr_t>(b.ptr) % 16 == 0 && (size_t(l.row_len) * sizeof(T)) % 16 == 0;
+        };
+        p.in_vec = vec_ok(in);
+        p.out_vec = vec_ok(out);
+        const int64_t blocks = std::min<int64_t>((batch + kLinmapItems - 1) / kLinmapItems, int64_t(g_num_cu) * m.small_blocks_per_cu);
+        hipLaunchKernelGGL(k_linmap_small<T>, dim3(unsigned(blocks)), dim3(256), linmap_small_lds(m, l.row_len, sizeof(T)), g_stream, p);
+    } else {
+        const int64_t tiles = std::min<int64_t>((batch + kLinmapBM - 1) / kLinmapBM, 65535);
+        hipLaunchKernelGGL(k_linmap_mfma<T>, dim3(unsigned(p.n_jobs), unsigned(tiles)), dim3(256), 0, g_stream, p);
+    }
+    HIP_TRY(hipGetLastError());
+    return GAAST_OK;
+}
+
+const char* linmap_kernel_name(int n, int dtype) {
+    if (n <= kLinmapSmallMaxDim) return dtype == GAAST_F32 ? "k_linmap_small<float>" : "k_linmap_small<double>";
+    return dtype == GAAST_F32 ? "k_linmap_mfma<float>" : "k_linmap_mfma<double>";
+}
+
+// the compounds of `mat` (n x n, row-major) rounded to dtype, on the device.  n <= kLinmapMaxDim.
+int linmap_build(int n, const double* mat, int dtype, LinmapDev& dev, std::vector<std::vector<double>>* host = nullptr) {
+    std::vector<std::vector<double>> c;
+    compound_matrices(n, mat, n, c);
+    dev.n = n;
+    dev.dtype = dtype;
+    dev.moff.assign(size_t(n + 1), 0);
+    size_t total = 0;
+    for (int k = 0; k <= n; ++k) {
+        dev.moff[size_t(k)] = int(total);
+        total += c[size_t(k)].size();
+    }
+    dev.mat_total = int(total);
+    const size_t esz = dtype_size(dtype);
+    HIP_TRY(hipMalloc(&dev.d_mats, total * esz));
+    for (int k = 0; k <= n; ++k) {
+        const std::vector<double>& ck = c[size_t(k)];
+        char* dst = static_cast<char*>(dev.d_mats) + size_t(dev.moff[size_t(k)]) * esz;
+        if (dtype == GAAST_F32) {
+            std::vector<float> f(ck.begin(), ck.end());
+            HIP_TRY(hipMemcpy(dst, f.data(), f.size() * 4, hipMemcpyHostToDevice));
+        } else {
+            HIP_TRY(hipMemcpy(dst, ck.data(), ck.size() * 8, hipMemcpyHostToDevice));
+        }
+    }
+    if (n <= kLinmapSmallMaxDim) {
+        const void* kern = dtype == GAAST_F32 ? reinterpret_cast<const void*>(&k_linmap_small<float>) : reinterpret_cast<const void*>(&k_linmap_small<double>);
+        const size_t lds = linmap_small_lds(dev, kLinmapSmallComps, esz);   // the longest row
+        if (int st = allow_lds(kern, lds)) return st;
+        if (int st = resident_blocks(kern, 256, lds, &dev.small_blocks_per_cu)) return st;
+    }
+    if (host) *host = std::move(c);
+    return GAAST_OK;
 }
 
 template <typename T>
@@ -454,6 +570,9 @@ int prepare_step(Step& s, const Layout& la, const Layout& lb, int n) {
         const size_t lds = (size_t(s.fused_slab) * FUSED_ITEMS + 8) * sizeof(T);
         return allow_lds(reinterpret_cast<const void*>(&k_ast_fused<T>), lds);
     }
+    case Step::LINMAP:
+        s.hip_kernel = linmap_kernel_name(static_cast<const LinmapDev*>(s.linmap)->n, is_f64 ? GAAST_F64 : GAAST_F32);
+        return GAAST_OK;
     default: return GAAST_OK;
     }
 }
@@ -656,6 +775,8 @@ int run_step(const Step& s, const Bound& res, const Bound& a, const Bound& b, co
         break;
     }
     case Step::FUSED: return GAAST_OK;  // launched by run_fused (needs every bound buffer)
+    case Step::ELEMENTWISE: return GAAST_OK;  // launched by run_elementwise (needs every source buffer)
+    case Step::LINMAP: return launch_linmap<T>(*static_cast<const LinmapDev*>(s.linmap), la, a, res, batch);
     case Step::PRODUCT_DENSE: {
         if (s.use_spinor) {
             SpinorArgs q;
@@ -762,6 +883,7 @@ int run_step(const Step& s, const Bound& res, const Bound& a, const Bound& b, co
                            dim3(unsigned(s.threads)), s.lds, g_stream, p);
         break;
     }
+    default: return set_err(GAAST_ERR_INVALID_PROGRAM, "run_step: unknown step kind " + std::to_string(int(s.kind)) + " (" + s.name + ")");
     }
     HIP_TRY(hipGetLastError());
     return GAAST_OK;
@@ -1029,6 +1151,168 @@ int gaast_hip_program_create(const gaast_program_desc* desc, gaast_hip_program_t
         return program_create_impl(&d2, out);
     }
     return st;
+}
+
+// ---- linear maps of the vector space on graded rows (outermorphisms) --------------------------------------------------
+int gaast_hip_linmap_create(int n, const double* matrix, int dtype, gaast_hip_linmap_t* out) {
+    if (!matrix || !out) return set_err(GAAST_ERR_INVALID_ARGUMENT, "null argument");
+    if (n < 1 || n > GAAST_MAX_DIM) return set_err(GAAST_ERR_INVALID_ARGUMENT, "linmap: dimension out of range");
+    if (dtype != GAAST_F32 && dtype != GAAST_F64) return set_err(GAAST_ERR_INVALID_ARGUMENT, "linmap: unknown dtype");
+    if (n > kLinmapMaxDim) return set_err(GAAST_ERR_UNIMPLEMENTED, "linmap: dimension above " + std::to_string(kLinmapMaxDim));
+    for (int i = 0; i < n * n; ++i)
+        if (!std::isfinite(matrix[i])) return set_err(GAAST_ERR_INVALID_ARGUMENT, "linmap: matrix entry not finite");
+    if (int st = ensure_init()) return st;
+    auto m = std::make_unique<gaast_hip_linmap_s>();
+    if (int st = linmap_build(n, matrix, dtype, m->dev)) return st;
+    *out = m.release();
+    return GAAST_OK;
+}
+
+int gaast_hip_linmap_destroy(gaast_hip_linmap_t map) {
+    if (!map) return GAAST_OK;
+    if (g_init) (void)hipSetDevice(g_device);
+    delete map;
+    return GAAST_OK;
+}
+
+int gaast_hip_linmap_apply(gaast_hip_linmap_t map, gaast_hip_mv_t in, gaast_hip_mv_t out) {
+    if (!map || !in || !out) return set_err(GAAST_ERR_INVALID_ARGUMENT, "null argument");
+    if (int st = ensure_init()) return st;
+    const LinmapDev& m = map->dev;
+    if (in->layout.dim != m.n || out->layout.dim != m.n)
+        return set_err(GAAST_ERR_INVALID_ARGUMENT, "linmap_apply: the rows' dimension differs from the map's");
+    if (in->layout.mask != out->layout.mask) return set_err(GAAST_ERR_INVALID_ARGUMENT, "linmap_apply: in and out grade sets differ");
+    if (in->batch != out->batch) return set_err(GAAST_ERR_INVALID_ARGUMENT, "linmap_apply: in and out batches differ");
+    if (in->dtype != m.dtype || out->dtype != m.dtype) return set_err(GAAST_ERR_INVALID_ARGUMENT, "linmap_apply: dtype differs from the map's");
+    const size_t sz = dtype_size(m.dtype);
+    auto span = [&](gaast_hip_mv_t v, uintptr_t* lo, uintptr_t* hi) {
+        *lo = reinterpret_cast<uintptr_t>(v->ptr);
+        *hi = *lo + (v->batch > 0 ? size_t((v->batch - 1) * v->row_stride + v->layout.row_len) * sz : 0);
+    };
+    uintptr_t a0, a1, b0, b1;
+    span(in, &a0, &a1);
+    span(out, &b0, &b1);
+    if (a0 < b1 && b0 < a1) return set_err(GAAST_ERR_INVALID_ARGUMENT, "linmap_apply: in and out overlap");
+    const Bound src{in->ptr, in->row_stride}, dst{out->ptr, out->row_stride};
+    return m.dtype == GAAST_F32 ? launch_linmap<float>(m, in->layout, src, dst, in->batch)
+                                : launch_linmap<double>(m, in->layout, src, dst, in->batch);
+}
+
+// A program specialised for the orthogonal basis f_j = sum_i Q_ij e_i, evaluated on rows in the caller's basis e: inputs move into f
+// through C_k(Q^T), the result back through C_k(Q) (LINMAP steps around the program's own plan).  Q == I exactly: the plain program.
+int gaast_hip_program_create_in_basis(const gaast_program_desc* desc, const double* basis, gaast_hip_program_t* out) {
+    if (!desc || !basis || !out) return set_err(GAAST_ERR_INVALID_ARGUMENT, "null argument");
+    const int n = desc->vec_space_dim;
+    if (n < 1 || n > GAAST_MAX_DIM) return set_err(GAAST_ERR_INVALID_ARGUMENT, "program_create_in_basis: dimension out of range");
+    bool identity = true;
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            const double q = basis[i * n + j];
+            if (!std::isfinite(q)) return set_err(GAAST_ERR_INVALID_ARGUMENT, "program_create_in_basis: basis entry not finite");
+            identity = identity && q == (i == j ? 1.0 : 0.0);
+            double qtq = 0.0;   // (Q^T Q)_ij
+            for (int k = 0; k < n; ++k) qtq += basis[k * n + i] * basis[k * n + j];
+            if (std::fabs(qtq - (i == j ? 1.0 : 0.0)) > 1e-12)
+                return set_err(GAAST_ERR_INVALID_ARGUMENT, "program_create_in_basis: the basis is not orthogonal (|Q^T Q - I| > 1e-12)");
+        }
+    if (identity) return gaast_hip_program_create(desc, out);
+    if (int st = ensure_init()) return st;
+    if (n > kLinmapMaxDim)
+        return set_err(GAAST_ERR_UNIMPLEMENTED, "program_create_in_basis: dimension above " + std::to_string(kLinmapMaxDim));
+    std::vector<double> qt(size_t(n * n));
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) qt[size_t(i * n + j)] = basis[j * n + i];
+    auto to_f = std::make_unique<LinmapDev>(), to_e = std::make_unique<LinmapDev>();
+    std::vector<std::vector<double>> c_in;   // C_k(Q^T) in double: the constant inputs move on the host
+    if (int st = linmap_build(n, qt.data(), desc->dtype, *to_f, &c_in)) return st;
+    if (int st = linmap_build(n, basis, desc->dtype, *to_e)) return st;
+    // constant rows into f; a row of another dimension can only be a scalar
+    gaast_program_desc d2 = *desc;
+    std::vector<gaast_input_desc> ins(desc->inputs, desc->inputs + (desc->n_inputs > 0 ? desc->n_inputs : 0));
+    std::vector<std::vector<double>> rows(ins.size());
+    for (size_t i = 0; i < ins.size(); ++i) {
+        const gaast_input_desc& in = ins[i];
+        if (!(in.grade_mask & ~1ULL)) continue;
+        if (in.storage_dim != n)
+            return set_err(GAAST_ERR_UNIMPLEMENTED, "program_create_in_basis: input slot " + std::to_string(i) + " has grades above 0 in another dimension");
+        if (!in.is_const || !in.const_row) continue;
+        const Layout l = make_layout(n, in.grade_mask);
+        rows[i].assign(in.const_row, in.const_row + l.row_len);
+        for (int k = 1; k <= n; ++k) {
+            const int64_t off = l.offset(k);
+            if (off < 0) continue;
+            const int64_t d = l.grade_len(k);
+            for (int64_t r = 0; r < d; ++r) {
+                double acc = 0.0;
+                for (int64_t c = 0; c < d; ++c) acc += c_in[size_t(k)][size_t(r * d + c)] * in.const_row[off + c];
+                rows[i][size_t(off + r)] = acc;
+            }
+        }
+        ins[i].const_row = rows[i].data();
+    }
+    d2.inputs = ins.empty() ? nullptr : ins.data();
+    gaast_hip_program_t prog = nullptr;
+    if (int st = gaast_hip_program_create(&d2, &prog)) return st;
+    std::unique_ptr<gaast_hip_program_s> owner(prog);
+    Plan& plan = prog->plan;
+    if (plan.out_layout.dim != n && (plan.out_layout.mask & ~1ULL))
+        return set_err(GAAST_ERR_UNIMPLEMENTED, "program_create_in_basis: the result has grades above 0 in another dimension");
+    // LINMAP steps: every batched input a launch reads, with grades above 0, into a node buffer of its own; the root back into out
+    std::vector<Step> pre;
+    std::vector<std::string> pre_names;
+    plan.basis_slot_buf.assign(plan.inputs.size(), -1);
+    auto make_step = [&](const LinmapDev* m, BufRef res, BufRef a, const std::string& name) -> int {
+        Step s;
+        s.kind = Step::LINMAP;
+        s.linmap = m;
+        s.res = res;
+        s.a = a;
+        s.name = name;
+        const Layout none;
+        if (int st = plan.dtype == GAAST_F32 ? prepare_step<float>(s, none, none, n) : prepare_step<double>(s, none, none, n)) return st;
+        pre_names.push_back(s.name + " :: " + s.hip_kernel);
+        pre.push_back(std::move(s));
+        return GAAST_OK;
+    };
+    for (size_t i = 0; i < plan.inputs.size(); ++i) {
+        if (plan.inputs[i].is_const || !plan.slot_used[i] || !(plan.inputs[i].grade_mask & ~1ULL)) continue;
+        const int buf = int(plan.node_buffers.size());
+        plan.node_buffers.push_back(plan.input_layouts[i]);
+        if (!plan.node_dead.empty()) plan.node_dead.push_back(0);
+        plan.basis_slot_buf[i] = buf;
+        if (int st = make_step(to_f.get(), BufRef{BufKind::NODE, buf}, BufRef{BufKind::INPUT, int(i)},
+                               "linmap[input " + std::to_string(i) + " -> orthogonal basis]"))
+            return st;
+    }
+    const size_t n_pre = pre.size();
+    if (plan.out_layout.mask & ~1ULL) {
+        plan.basis_out_buf = int(plan.node_buffers.size());
+        plan.node_buffers.push_back(plan.out_layout);
+        if (!plan.node_dead.empty()) plan.node_dead.push_back(0);
+        if (int st = make_step(to_e.get(), BufRef{BufKind::OUT, -1}, BufRef{BufKind::NODE, plan.basis_out_buf}, "linmap[result -> caller's basis]"))
+            return st;
+    }
+    std::vector<Step> steps;
+    std::vector<std::string> names;
+    for (size_t i = 0; i < n_pre; ++i) {
+        steps.push_back(std::move(pre[i]));
+        names.push_back(pre_names[i]);
+    }
+    for (size_t i = 0; i < plan.steps.size(); ++i) {
+        steps.push_back(std::move(plan.steps[i]));
+        names.push_back(prog->launch_names[i]);
+    }
+    for (size_t i = n_pre; i < pre.size(); ++i) {
+        steps.push_back(std::move(pre[i]));
+        names.push_back(pre_names[i]);
+    }
+    plan.steps = std::move(steps);
+    prog->launch_names = std::move(names);
+    prog->basis_in = std::move(to_f);
+    prog->basis_out = std::move(to_e);
+    prog->scratch_batch = 0;   // the node buffers are re-allocated at the next eval
+    *out = owner.release();
+    return GAAST_OK;
 }
 
 static int program_create_impl(const gaast_program_desc* desc, gaast_hip_program_t* out) {
@@ -1456,6 +1740,19 @@ int eval_range(gaast_hip_program_t prog, const std::vector<Bound>& in_bound0, ga
         prog->scratch_batch = count;
     }
 
+    // a program in a non-orthonormal basis: every step but LINMAP reads the inputs' rows moved into the orthogonal basis (a shared
+    // input: one row, broadcast) and writes the root into a node buffer that the last LINMAP step moves back into `out`
+    std::vector<Bound> inner_bound = in_bound;
+    Bound out_inner = out_b;
+    for (size_t i = 0; i < plan.basis_slot_buf.size(); ++i) {
+        if (plan.basis_slot_buf[i] < 0 || !in_bound[i].ptr) continue;
+        gaast_hip_mv_t m = prog->scratch[size_t(plan.basis_slot_buf[i])];
+        inner_bound[i] = Bound{m->ptr, in_bound[i].stride == 0 ? 0 : m->row_stride};
+    }
+    if (plan.basis_out_buf >= 0) {
+        gaast_hip_mv_t m = prog->scratch[size_t(plan.basis_out_buf)];
+        out_inner = Bound{m->ptr, m->row_stride};
+    }
     auto resolve = [&](BufRef r, Layout* lay) -> Bound {
         switch (r.kind) {
         case BufKind::NODE: {
@@ -1463,16 +1760,37 @@ int eval_range(gaast_hip_program_t prog, const std::vector<Bound>& in_bound0, ga
             *lay = m->layout;
             return Bound{m->ptr, m->row_stride};
         }
-        case BufKind::INPUT: *lay = plan.input_layouts[size_t(r.idx)]; return in_bound[size_t(r.idx)];
-        default: *lay = out->layout; return out_b;
+        case BufKind::INPUT: *lay = plan.input_layouts[size_t(r.idx)]; return inner_bound[size_t(r.idx)];
+        default: *lay = out->layout; return out_inner;
         }
     };
     for (const Step& s : plan.steps) {
         Layout lres, la, lb;
+        if (s.kind == Step::LINMAP) {   // the caller's rows in, the caller's rows out
+            Bound src, dst;
+            int64_t items = count;
+            if (s.a.kind == BufKind::INPUT) {
+                la = plan.input_layouts[size_t(s.a.idx)];
+                src = in_bound[size_t(s.a.idx)];
+                if (src.stride == 0) items = 1;   // shared by every item: moved once
+            } else {
+                src = resolve(s.a, &la);
+            }
+            if (s.res.kind == BufKind::OUT) {
+                lres = out->layout;
+                dst = out_b;
+            } else {
+                dst = resolve(s.res, &lres);
+            }
+            const int st = plan.dtype == GAAST_F32 ? run_step<float>(s, dst, src, Bound{nullptr, 0}, la, lb, items, plan.n)
+                                                   : run_step<double>(s, dst, src, Bound{nullptr, 0}, la, lb, items, plan.n);
+            if (st != GAAST_OK) return st;
+            continue;
+        }
         const Bound res = resolve(s.res, &lres);
         if (s.kind == Step::FUSED) {
-            const int st = plan.dtype == GAAST_F32 ? run_fused<float>(s, plan, in_bound, res, count)
-                                                   : run_fused<double>(s, plan, in_bound, res, count);
+            const int st = plan.dtype == GAAST_F32 ? run_fused<float>(s, plan, inner_bound, res, count)
+                                                   : run_fused<double>(s, plan, inner_bound, res, count);
             if (st != GAAST_OK) return st;
             continue;
         }

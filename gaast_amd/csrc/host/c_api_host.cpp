@@ -6,6 +6,7 @@
 
 #include "../common/algebra.hpp"
 #include "../common/grade_set.hpp"
+#include "../common/metric_basis.hpp"
 #include "expr.hpp"
 
 using namespace gaast;
@@ -70,6 +71,25 @@ uint64_t gaast_blade_to_component(int n, uint64_t blade, int* grade) {
 double gaast_blades_gp(int n, const double* metric_diag, uint64_t b1, uint64_t b2, uint64_t* res) {
     if (res) *res = b1 ^ b2;
     return blades_gp_coeff(n, metric_diag, b1, b2);
+}
+
+int gaast_metric_diagonalize(int n, const double* gram, double* diag_out, double* basis_out) {
+    if (!diag_out || !basis_out || !metric_diagonalize(n, gram, diag_out, basis_out)) {
+        g_err = "gaast_metric_diagonalize: the Gram matrix must be finite and exactly symmetric, 1 <= n <= GAAST_MAX_DIM";
+        return GAAST_ERR_INVALID_ARGUMENT;
+    }
+    return GAAST_OK;
+}
+
+int gaast_compound_matrix(int n, const double* m, int k, double* out) {
+    if (n < 1 || n > GAAST_MAX_DIM || k < 0 || k > n || !m || !out) {
+        g_err = "gaast_compound_matrix: need 1 <= n <= GAAST_MAX_DIM and 0 <= k <= n";
+        return GAAST_ERR_INVALID_ARGUMENT;
+    }
+    std::vector<std::vector<double>> c;
+    compound_matrices(n, m, k, c, false);
+    std::memcpy(out, c[size_t(k)].data(), c[size_t(k)].size() * sizeof(double));
+    return GAAST_OK;
 }
 
 gaast_expr_t gaast_expr_retain(gaast_expr_t e) {

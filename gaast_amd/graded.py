@@ -167,3 +167,33 @@ class DeviceMV:
                 out[k] = row[pos:pos + g]
                 pos += g
         return GradeMapMV(out, dim=self.dim)
+
+
+class Outermorphism:
+    """A linear map M of the vector space (n x n, row-major) extended to every grade: on grade k of a row, the k-th compound
+    C_k(M) (gaast_compound_matrix), shared by every item.  `apply` runs on the GPU (gaast_hip_linmap_apply, asynchronous)."""
+
+    def __init__(self, matrix, dtype=_lib.F64):
+        m = np.ascontiguousarray(np.asarray(matrix, dtype=np.float64))
+        if m.ndim != 2 or m.shape[0] != m.shape[1]:
+            raise ValueError(f"a linear map is an n x n matrix, got shape {m.shape}")
+        _lib.init_device()
+        self.n, self.dtype = m.shape[0], dtype
+        h = C.c_void_p()
+        _lib.check(_lib.lib().gaast_hip_linmap_create(self.n, m.ctypes.data_as(C.POINTER(C.c_double)), dtype, C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().gaast_hip_linmap_destroy(self._h)
+        except Exception:
+            pass
+
+    def apply(self, mv, out=None):
+        """out(item)_k = C_k(M) mv(item)_k; out: a DeviceMV of mv's dimension, grades and batch (allocated when None)."""
+        if out is None:
+            out = DeviceMV.alloc(mv.dim, GradeSet(mv.mask), mv.batch, self.dtype)
+        _lib.check(_lib.lib().gaast_hip_linmap_apply(self._h, mv._h, out._h))
+        out._keep_inputs = mv
+        return out

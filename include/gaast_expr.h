@@ -47,6 +47,17 @@ uint64_t gaast_component_to_blade(int n, int grade, uint64_t index);     /* alge
 uint64_t gaast_blade_to_component(int n, uint64_t blade, int *grade);    /* algebra.rs:41-45 */
 /* ortho_basis_blades_gp, algebra.rs:73-83: returns the coefficient, *res = b1 ^ b2 */
 double gaast_blades_gp(int n, const double *metric_diag, uint64_t b1, uint64_t b2, uint64_t *res);
+/* Non-diagonal metrics: the reference's MetricAlgebra::base_vec_dot(i, j) as a full Gram matrix (algebra.rs:57-66, whose
+ * TODO is its diagonalisation, algebra.rs:68-83).  gram: row-major n x n, finite and exactly symmetric, 1 <= n <= GAAST_MAX_DIM
+ * (else GAAST_ERR_INVALID_ARGUMENT).  G = Q diag(L) Q^T by cyclic Jacobi in double: diag_out[j] = L_j, basis_out[i*n + j] = Q_ij,
+ * coordinate i of the orthogonal basis vector f_j = sum_i Q_ij e_i.  Deterministic (same input, same bits): every column's
+ * largest-magnitude entry is positive; |L_j| <= 64 eps max|L| becomes exactly 0 (a degenerate metric stays degenerate).  An
+ * exactly diagonal G gives Q = I and L = diag(G) bit for bit, in the original order (no sorting). */
+int gaast_metric_diagonalize(int n, const double *gram, double *diag_out, double *basis_out);
+/* k-th compound of an n x n matrix (row-major): out is C(n,k) x C(n,k), row-major, out[I*C(n,k) + J] = det m[rows of blade I,
+ * columns of blade J], I and J in the component order of grade k (gaast_component_to_blade).  C_k(M) is the outermorphism of M
+ * on grade k: the coordinates of M e_J = (M e_j1) ^ ... ^ (M e_jk) are column J. */
+int gaast_compound_matrix(int n, const double *m, int k, double *out);
 
 /* ---- Expr construction (phase 1) -------------------------------------------------------------- */
 gaast_expr_t gaast_expr_retain(gaast_expr_t e);  /* Expr::clone, expr.rs:47-53: same node identity */

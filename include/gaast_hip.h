@@ -224,6 +224,36 @@ int gaast_hip_mv_zero(gaast_hip_mv_t mv);
 int gaast_hip_eval(gaast_hip_program_t prog, const gaast_hip_mv_t *inputs, int n_inputs,
                    int64_t batch, gaast_hip_mv_t out);
 
+/* ---- non-diagonal metrics and linear maps of the vector space ------------------------------ */
+/*
+ * The reference's MetricAlgebra is a full Gram matrix (algebra.rs:57-66); its product rule assumes it diagonal (algebra.rs:68-83).
+ * A Gram metric G = Q diag(L) Q^T (gaast_metric_diagonalize, include/gaast_expr.h) is evaluated in the orthogonal basis
+ * f_j = sum_i Q_ij e_i, whose metric diag(L) every kernel handles: specialise the program for diag(L), then create it with
+ * gaast_hip_program_create_in_basis.  Rows cross the boundary in the caller's basis e.
+ *
+ * The change of basis is the outermorphism of a linear map M of the vector space: on grade k of a row, the k-th compound C_k(M)
+ * (gaast_compound_matrix), shared by every item -- also public, as a linear map applied to a batch of multivectors.
+ * Linear maps and in-basis programs accept n <= 14 (the compounds at n = 14 total C(28,14) ~ 40 M entries); beyond that they
+ * return GAAST_ERR_UNIMPLEMENTED and nothing is created.
+ */
+typedef struct gaast_hip_linmap_s *gaast_hip_linmap_t;
+/* matrix: n x n, row-major, finite.  The compounds of every grade are built once on the host (f64, rounded to dtype) and
+ * uploaded.  Synchronous. */
+int gaast_hip_linmap_create(int n, const double *matrix, int dtype, gaast_hip_linmap_t *out);
+/* out(item)_k = C_k(M) in(item)_k for every grade k of the rows.  in and out: dimension n, the map's dtype, the same grade mask
+ * and batch, no overlap (rows may be strided: gaast_hip_mv_wrap).  Asynchronous on the library stream. */
+int gaast_hip_linmap_apply(gaast_hip_linmap_t map, gaast_hip_mv_t in, gaast_hip_mv_t out);
+int gaast_hip_linmap_destroy(gaast_hip_linmap_t map);
+/* desc: a program specialised for the orthogonal basis f (its metric_diag is L; explicit comp-mul lists computed in f are fine).
+ * basis: Q as gaast_metric_diagonalize returns it, refused (GAAST_ERR_INVALID_ARGUMENT) unless |Q^T Q - I| <= 1e-12 elementwise.
+ * Inputs are bound and the result written in the caller's basis e: every batched input slot with grades above 0 goes through
+ * C_k(Q^T) into library scratch first (one scratch row per item per such slot, grown with the batch; an input shared by all items
+ * is moved once per evaluation), constant inputs are moved on the host here, and the result comes back through C_k(Q) -- launches
+ * "linmap[...]" in gaast_hip_program_launch_name.  Q == I exactly: the very program (plan, launches, bits) of
+ * gaast_hip_program_create.  GAAST_FLAG_EXACT_ORDER applies to the program inside the basis change: there are no reference bits
+ * in a non-diagonal metric. */
+int gaast_hip_program_create_in_basis(const gaast_program_desc *desc, const double *basis, gaast_hip_program_t *out);
+
 /* ---- multi-GPU: one rank per GPU, batch sharded by item ------------------------------------ */
 /*
  * The reference evaluates one input set per eval() and keeps no cross-item state (eval.rs:16), so a batch
