@@ -1036,7 +1036,7 @@ struct Lowering {
 // the steps become one micro-op stream (k_ast_fused).  Exact: same operations, same order.
 // ---------------------------------------------------------------------------------------------
 // slab_probe != nullptr: only report the slab size a fused plan would have (0: cannot be fused) and change nothing
-bool try_fuse(Plan& plan, int* slab_probe = nullptr) {
+bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
     if (slab_probe) *slab_probe = 0;
     if (plan.flags & GAAST_FLAG_NO_FUSION) return false;
     if (plan.error != GAAST_OK || plan.steps.empty()) return false;
@@ -1096,9 +1096,9 @@ bool try_fuse(Plan& plan, int* slab_probe = nullptr) {
     // compiler keeps only the LIVE values in registers, the projection (v & bv) & bv.vinv() at n = 12 (slab 171) compiles to 222
     // registers and runs at 0.75 of the HBM roof against 0.44 with its slabs in LDS, the versor inverse at n = 8 (slab 259: the
     // whole row is live until it is scaled) to 310 with one wave per SIMD and 0.46 against 0.67.  The runtime measures the compiled
-    // kernel's occupancy and rebuilds the plan with GAAST_FLAG_INTERNAL_SMALL_REG_SLAB when the trial fails.
+    // kernel's occupancy and rebuilds the plan with small_reg_slab when the trial fails.
     const int jit_slab_small = plan.dtype == GAAST_F32 ? 200 : 160;
-    const int jit_slab_limit = (plan.flags & GAAST_FLAG_INTERNAL_SMALL_REG_SLAB) ? jit_slab_small : (plan.dtype == GAAST_F32 ? 320 : 256);
+    const int jit_slab_limit = small_reg_slab ? jit_slab_small : (plan.dtype == GAAST_F32 ? 320 : 256);
     const bool jit_allowed = !(plan.flags & GAAST_FLAG_NO_JIT) && slab <= jit_slab_limit;
     if (!interp_ok && !jit_allowed) return false;
     if (slab_probe) {
@@ -3060,7 +3060,7 @@ static void jit_long_row_lists(Plan& plan) {
     }
 }
 
-void build_plan(const gaast_program_desc& desc, Plan& plan) {
+void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab) {
     if (desc.vec_space_dim < 0 || desc.vec_space_dim > GAAST_MAX_DIM) throw std::runtime_error("vec_space_dim out of range");
     if (desc.n_nodes <= 0 || desc.root < 0 || desc.root >= desc.n_nodes) throw std::runtime_error("bad node count / root");
     if (desc.dtype != GAAST_F64 && desc.dtype != GAAST_F32) throw std::runtime_error("bad dtype");
@@ -3119,7 +3119,7 @@ void build_plan(const gaast_program_desc& desc, Plan& plan) {
     // A program that would only fit the LDS interpreter (its slab is beyond the registers of the hiprtc-specialised kernel) but is
     // exactly one list chain -- (R X ~R).g(1) at n = 8 -- runs on k_product_ell_chain instead (same box: 1.43 against 1.59 ms per 1 M items)
     int slab = 0;
-    try_fuse(plan, &slab);
+    try_fuse(plan, small_reg_slab, &slab);
     if (slab > (plan.dtype == GAAST_F32 ? 200 : 160) && !(plan.flags & (GAAST_FLAG_NO_FUSION | GAAST_FLAG_DEBUG_NO_CHAIN | GAAST_FLAG_NO_JIT))) {
         Plan trial = plan;
         uniform_csr_to_ell(trial);
@@ -3129,7 +3129,7 @@ void build_plan(const gaast_program_desc& desc, Plan& plan) {
             return;
         }
     }
-    if (!try_fuse(plan)) {
+    if (!try_fuse(plan, small_reg_slab)) {
         fuse_elementwise_runs(plan);
         fuse_reduce_scale(plan);
         chain_sparse_into_dense(plan);

@@ -9,10 +9,6 @@
 #include "../common/comp_mul_table.hpp"
 #include "gaast_hip.h"
 
-// internal (not in include/gaast_hip.h): the one-item-per-thread specialised kernel is limited to slabs of 160 / 200 elements -- set by
-// program_create_impl when a bigger slab's trial compilation needs more than half of a SIMD's registers
-#define GAAST_FLAG_INTERNAL_SMALL_REG_SLAB 0x40000000u
-
 namespace gaast {
 
 enum class BufKind : int { NODE = 0, INPUT = 1, OUT = 2 };
@@ -42,13 +38,11 @@ struct Step {
     enum Kind { ZERO, AXPY, FLIP, SUNARY, PRODUCT_CSR, PRODUCT_DENSE, FUSED, EXPLOG, REDUCE_SCALE, ELEMENTWISE, LINMAP } kind = ZERO;
     BufRef res, a, b;
     std::string name;
-    std::string hip_kernel;        // the HIP kernel (template and arguments) prepare_step picked: appended to the launch label
     // host images of the tables (uploaded once at program_create)
     std::vector<uint32_t> u32_a;   // AXPY map | FLIP offsets | CSR row_start | DENSE left_map
     std::vector<uint32_t> u32_b;   // CSR row_out | DENSE right_map
     std::vector<uint32_t> u32_c;   // CSR entries
-    std::vector<double> coeff;     // CSR coefficients (converted to the program dtype on upload)
-    std::vector<double> coeff_host; // FUSED: the general coefficients, passed by value at launch
+    std::vector<double> coeff;     // CSR coefficients (converted to the program dtype on upload) | FUSED: the general coefficients
     std::vector<int32_t> i32_a;    // DENSE out_map
     int sunary_op = 0, sunary_off = 0;
     // EXPLOG (GAAST_FLAG_EXP_LOG extension): res += exp(arg) / log(arg), arg = buffer `a` holding a k-vector (log: + grade 0).
@@ -59,14 +53,11 @@ struct Step {
     int explog_arg_k = 0, explog_arg_0 = -1; // offsets in the operand row (grade k; grade 0 for log, -1 = absent)
     int explog_res_k = -1, explog_res_0 = -1;// offsets in the result row, -1 = not produced
     std::vector<double> coeff_b;
-    void* d_coeff_b = nullptr;
     // DENSE with a general diagonal metric (entries other than +-1 / 0): the kernels run in the rescaled basis
     // f_i = e_i / sqrt|g_i|: coeff = w_S per loaded left component, coeff_b = per loaded right component, coeff_c = 1 / w_T per
     // blade of the permuted basis (the index of i32_a)
     std::vector<double> coeff_c;
-    void* d_coeff_c = nullptr;
     int scaled = 0;
-    void* d_domain = nullptr;                // the program's domain-error counter (device, not owned by the step)
     int ell_bytes = 0;             // ... and the offsets of its entries are byte offsets
     int ell_width = 0;             // PRODUCT_CSR with rows of one length and +-1 coefficients: u32_c is [term][row], sign in bit 31
     int canon_a = 0, canon_b = 0;
@@ -92,12 +83,6 @@ struct Step {
     std::vector<double> pre_row_scale;   // per row (rescaled basis), else empty
     int pre_left_len = 0, pre_right_len = 0;
     int pre_width = 0;                   // > 0: rows of one length with +-1 coefficients: pre_entries is [term][row], sign in bit 31
-    size_t pre_scratch_off = 0;          // bytes: where the list's operand rows sit in the kernel's LDS (after its images)
-    void* d_pre_row_start = nullptr;
-    void* d_pre_entries = nullptr;
-    void* d_pre_coeff = nullptr;
-    void* d_pre_row_map = nullptr;
-    void* d_pre_row_scale = nullptr;
     // PRODUCT_CSR (ELL form), list chain (plan.cpp: chain_list_into_list): one operand of this list is the result of ANOTHER list that
     // nothing else reads -- (R X) ~R projected on a grade.  Both lists run in one k_product_ell_chain launch, the mid row stays in
     // LDS.  Reuses pre_a / pre_b / pre_canon_* / pre_left_len / pre_right_len / pre_entries ([term][row] words of the first list) /
@@ -110,13 +95,9 @@ struct Step {
     // of a workgroup fastest, so that the 32 lanes of an LDS access read one row's operand of 32 different items (odd item stride:
     // no bank conflict); entries carry byte offsets from the item's base (list 1: the sign is folded into a negated image of the
     // smaller operand); compile-time widths, lengths and strides.  The generic k_product_ell_chain stays as the fallback.
-    int chain_jit = 0;                   // 1: chain_jit_source is to be compiled (runtime.hip), 2: compiled and in charge
+    int chain_jit = 0;                   // 1: chain_jit_source was generated (runtime.hip compiles it)
     std::string chain_jit_source;
     std::vector<uint32_t> cj_ent1, cj_pos1, cj_ent2, cj_out2;
-    void* d_cj_ent1 = nullptr;
-    void* d_cj_pos1 = nullptr;
-    void* d_cj_ent2 = nullptr;
-    void* d_cj_out2 = nullptr;
     int list_jit = 0;                    // the specialised kernel runs a SINGLE list (few long rows): plan.cpp: jit_long_row_lists
     int fold_prev = 0;                   // ... and, once compiled, also the covering copy_grades_from step right before it (pre_a = its source)
     int cj_ipb = 0, cj_threads = 0;
@@ -153,7 +134,6 @@ struct Step {
     uint64_t n_entries = 0;  // comp-mul count this step stands for
     // LINMAP (gaast_hip_program_create_in_basis): res = the outermorphism of a change of basis applied to row buffer `a` -- an input
     // slot into the orthogonal basis of the program, or the root's result back into the caller's basis (kernels_linmap.hip.hpp)
-    const void* linmap = nullptr;   // the program's map (runtime.hip: LinmapDev), borrowed
     // FUSED: the whole plan as one micro-op stream over per-item LDS slabs (u32_a = the stream)
     struct FusedInput {
         int slot, base, canon;
@@ -167,29 +147,6 @@ struct Step {
     int jit_reg_trial = 0;    // one item per thread with a slab beyond 160 / 200 elements: kept only if the compiled kernel leaves two
                               // waves per SIMD (runtime.hip: program_create_impl); else the plan is rebuilt with the slabs in LDS
     std::string jit_source;   // FUSED: the plan as straight-line HIP (compiled with hiprtc at program_create)
-    void* jit_module = nullptr;
-    void* jit_function = nullptr;
-    std::vector<char> jit_code;   // the hiprtc code object jit_module was loaded from: kept until the module is unloaded
-    // the same source compiled with floating-point contraction (l * r + acc as ONE fused multiply-add: fewer roundings than the
-    // reference, so within the tolerance contract but not its bits): built only without GAAST_FLAG_EXACT_ORDER, launched only when
-    // an item's arithmetic outweighs its bytes (runtime.hip: run_jit -- in practice: operands shared by all items)
-    void* jit_module_fma = nullptr;
-    void* jit_function_fma = nullptr;
-    std::vector<char> jit_code_fma;
-    // launch configuration, fixed once at gaast_hip_program_create (runtime.hip: prepare_step): kernel, block
-    // size, dynamic LDS, persistent-grid size.  ELL products pick kern[log2(items per pass)] by batch.
-    const void* kern[4] = {nullptr, nullptr, nullptr, nullptr};
-    int threads = 0;
-    size_t lds = 0;            // bytes per launch (ELL / CSR: per staged item)
-    int max_items = 0;         // ELL / CSR: items per workgroup when the batch allows
-    int items_per_block = 0;   // dense kernels
-    int blocks_per_cu = 0;     // persistent kernels: resident workgroups per CU
-    // device copies
-    void* d_a = nullptr;
-    void* d_b = nullptr;
-    void* d_c = nullptr;
-    void* d_coeff = nullptr;
-    void* d_i32 = nullptr;
 };
 
 // limits of this back end (gfx950): a product whose staged operands exceed the LDS of a CU, or whose comp-mul list
@@ -226,8 +183,10 @@ struct Plan {
     int basis_out_buf = -1;
 };
 
-// Throws std::runtime_error (-> GAAST_ERR_INVALID_PROGRAM) on malformed input.
-void build_plan(const gaast_program_desc& desc, Plan& plan);
+// Throws std::runtime_error (-> GAAST_ERR_INVALID_PROGRAM) on malformed input.  small_reg_slab: the one-item-per-thread
+// specialised kernel is limited to slabs of 160 / 200 elements (runtime.hip rebuilds a plan so when a bigger slab's trial
+// compilation needs more than half of a SIMD's registers)
+void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab = false);
 
 // Micro-op encoding shared by the plan builder and k_ast_fused (see kernels.hip.hpp).
 namespace uop {

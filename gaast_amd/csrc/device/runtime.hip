@@ -31,7 +31,6 @@ bool g_init = false;
 int g_device = -1;
 hipStream_t g_stream = nullptr;
 int g_num_cu = 256;
-bool g_chain_too_big = false;      // program_create: a chained step went beyond the LDS the plan builder had budgeted
 size_t g_max_lds = 160 * 1024;
 Comm g_comm;                       // the gather communicator (gaast_hip_comm_init), if any
 std::vector<hipEvent_t> g_events;  // chunk-done events of gaast_hip_eval_gather, created on demand
@@ -60,6 +59,74 @@ int ensure_init() {
 
 size_t dtype_size(int dtype) { return dtype == GAAST_F32 ? 4 : 8; }
 
+// internal status of program creation: a chained step went beyond the LDS the plan builder had budgeted (reported as
+// GAAST_ERR_UNIMPLEMENTED once gaast_hip_program_create has tried the program without chains)
+constexpr int kChainTooBig = -1000;
+
+// One device allocation of `count` elements, freed with its owner
+struct DevTable {
+    void* ptr = nullptr;
+    size_t count = 0;
+    DevTable() = default;
+    DevTable(DevTable&& o) noexcept : ptr(o.ptr), count(o.count) {
+        o.ptr = nullptr;
+        o.count = 0;
+    }
+    DevTable& operator=(DevTable&& o) noexcept {
+        std::swap(ptr, o.ptr);
+        std::swap(count, o.count);
+        return *this;
+    }
+    ~DevTable() {
+        if (ptr) (void)hipFree(ptr);
+    }
+    template <typename T>
+    const T* as() const { return static_cast<const T*>(ptr); }
+    // an index table, as it is (the host image goes with the argument)
+    template <typename I>
+    int upload(std::vector<I> v) {
+        return upload_bytes(v.data(), v.size(), sizeof(I));
+    }
+    // a value table, converted to the program's dtype
+    int upload(std::vector<double> v, int dtype) {
+        if (dtype != GAAST_F32) return upload_bytes(v.data(), v.size(), sizeof(double));
+        const std::vector<float> f(v.begin(), v.end());
+        return upload_bytes(f.data(), f.size(), sizeof(float));
+    }
+
+private:
+    int upload_bytes(const void* src, size_t n, size_t elem) {
+        *this = DevTable();
+        if (!n) return GAAST_OK;
+        HIP_TRY(hipMalloc(&ptr, n * elem));
+        count = n;
+        HIP_TRY(hipMemcpy(ptr, src, n * elem, hipMemcpyHostToDevice));
+        return GAAST_OK;
+    }
+};
+
+// A kernel compiled through hiprtc: the code image, the module loaded from it and its entry point
+struct JitKernel {
+    // HIP's header does not say that hipModuleLoadData copies the image: it stays alive for as long as the module does.
+    // (Members are destroyed after the destructor's body: the module is unloaded before the image is freed.  A move of
+    // the vector keeps code.data() where it is.)
+    std::vector<char> code;
+    hipModule_t module = nullptr;
+    hipFunction_t fn = nullptr;
+    JitKernel() = default;
+    JitKernel(JitKernel&& o) noexcept : code(std::move(o.code)), module(o.module), fn(o.fn) { o.module = nullptr; }
+    JitKernel& operator=(JitKernel&& o) noexcept {
+        std::swap(code, o.code);
+        std::swap(module, o.module);
+        std::swap(fn, o.fn);
+        return *this;
+    }
+    ~JitKernel() {
+        if (module) (void)hipModuleUnload(module);
+    }
+    explicit operator bool() const { return fn != nullptr; }
+};
+
 }  // namespace
 
 struct gaast_hip_mv_s {
@@ -76,17 +143,44 @@ namespace {
 struct LinmapDev {
     int n = 0;
     int dtype = GAAST_F64;
-    void* d_mats = nullptr;
+    DevTable mats;
     std::vector<int> moff;            // grade k's matrix at element moff[k]
     int mat_total = 0;
     int small_blocks_per_cu = 1;      // k_linmap_small: resident workgroups per CU (persistent grid)
-    LinmapDev() = default;
-    LinmapDev(const LinmapDev&) = delete;
-    LinmapDev& operator=(const LinmapDev&) = delete;
-    ~LinmapDev() {
-        if (d_mats) (void)hipFree(d_mats);
-    }
 };
+
+// One launch of a program: the plan's step it runs and what gaast_hip_program_create made of it on the device
+struct Launch {
+    Step s;
+    // launch configuration, fixed once (prepare_step): kernel, block size, dynamic LDS, persistent-grid size.  ELL products
+    // pick kern[log2(items per pass)] by batch.
+    const void* kern[4] = {nullptr, nullptr, nullptr, nullptr};
+    int n = 0;                 // dimension of the algebra the kernel runs in (parity-pure dense products: n - 1)
+    int threads = 0;
+    size_t lds = 0;            // bytes per launch (ELL / CSR: per staged item)
+    int max_items = 0;         // ELL / CSR: items per workgroup when the batch allows
+    int items_per_block = 0;   // dense kernels
+    int blocks_per_cu = 0;     // persistent kernels: resident workgroups per CU
+    size_t pre_scratch_off = 0;   // chained: bytes, where the list's operand rows sit in the kernel's LDS (after its images)
+    // the step's tables on the device (their host images are dropped after the upload)
+    DevTable u32_a, u32_b, u32_c, i32_a, coeff, coeff_b, coeff_c;
+    DevTable pre_row_start, pre_entries, pre_coeff, pre_row_map, pre_row_scale;
+    DevTable cj_ent1, cj_pos1, cj_ent2, cj_out2;
+    std::vector<double> fused_coeff;   // FUSED: the general coefficients, passed by value
+    void* domain = nullptr;            // the program's domain-error counter (borrowed)
+    const LinmapDev* linmap = nullptr; // LINMAP: the program's map (borrowed)
+    // FUSED: the plan specialised through hiprtc, or a list chain (Step::chain_jit); a FUSED step also gets the same source
+    // compiled with floating-point contraction (l * r + acc as ONE fused multiply-add: fewer roundings than the reference, so
+    // within the tolerance contract but not its bits): built only without GAAST_FLAG_EXACT_ORDER, launched only when an item's
+    // arithmetic outweighs its bytes (run_jit -- in practice: operands shared by all items)
+    JitKernel jit, jit_fma;
+    std::string label;   // what the step is, then WHICH HIP kernel runs it (the name rocprofv3 reports)
+};
+
+struct MvFree {
+    void operator()(gaast_hip_mv_t m) const;
+};
+using MvPtr = std::unique_ptr<gaast_hip_mv_s, MvFree>;
 }  // namespace
 
 struct gaast_hip_linmap_s {
@@ -95,57 +189,18 @@ struct gaast_hip_linmap_s {
 
 struct gaast_hip_program_s;
 
-namespace {
-void mv_free_impl(gaast_hip_mv_t m);
-void release_plan_resources(Plan& plan);
-}  // namespace
-
+// Everything a program owns is freed through its members: gaast_hip_program_destroy synchronises the stream first
 struct gaast_hip_program_s {
-    Plan plan;
-    std::vector<gaast_hip_mv_t> const_mvs;  // per input slot (nullptr for bound slots)
-    std::vector<gaast_hip_mv_t> scratch;    // per node buffer, sized for scratch_batch
+    Plan plan;                              // the shared data (layouts, inputs, buffers); its steps live on in `launches`
+    std::vector<Launch> launches;
+    std::vector<DevTable> const_rows;       // per input slot (empty for bound slots)
+    std::vector<MvPtr> scratch;             // per node buffer, sized for scratch_batch
     int64_t scratch_batch = 0;
-    std::vector<std::string> launch_names;
-    void* d_domain = nullptr;               // exp / log extension: items refused by the domain check (unsigned long long)
+    DevTable domain;                        // exp / log extension: items refused by the domain check (unsigned long long)
     std::unique_ptr<LinmapDev> basis_in, basis_out;   // program in a non-orthonormal basis: C_k(Q^T) and C_k(Q) (LINMAP steps)
-    gaast_hip_program_s() = default;
-    gaast_hip_program_s(const gaast_hip_program_s&) = delete;
-    gaast_hip_program_s& operator=(const gaast_hip_program_s&) = delete;
-    ~gaast_hip_program_s() {  // every failure path of program_create and program_destroy end here
-        release_plan_resources(plan);
-        if (d_domain) (void)hipFree(d_domain);
-        for (gaast_hip_mv_t m : const_mvs) mv_free_impl(m);
-        for (gaast_hip_mv_t m : scratch) mv_free_impl(m);
-    }
 };
 
 namespace {
-
-// device tables and hiprtc modules of a plan (also called before a plan is rebuilt)
-void release_plan_resources(Plan& plan) {
-    for (Step& s : plan.steps) {
-        for (void** p : {&s.d_a, &s.d_b, &s.d_c, &s.d_coeff, &s.d_i32, &s.d_coeff_b, &s.d_coeff_c, &s.d_pre_row_start, &s.d_pre_entries,
-                         &s.d_pre_coeff, &s.d_pre_row_map, &s.d_pre_row_scale, &s.d_cj_ent1, &s.d_cj_pos1, &s.d_cj_ent2, &s.d_cj_out2}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-        }
-        if (s.jit_module) (void)hipModuleUnload(static_cast<hipModule_t>(s.jit_module));
-        if (s.jit_module_fma) (void)hipModuleUnload(static_cast<hipModule_t>(s.jit_module_fma));
-        s.jit_module = s.jit_module_fma = nullptr;
-        s.jit_function = s.jit_function_fma = nullptr;
-        std::vector<char>().swap(s.jit_code);   // only after the unload: the image outlives the module built from it
-        std::vector<char>().swap(s.jit_code_fma);
-    }
-}
-
-template <typename T>
-int upload_vec(const std::vector<T>& v, void** dptr) {
-    *dptr = nullptr;
-    if (v.empty()) return GAAST_OK;
-    HIP_TRY(hipMalloc(dptr, v.size() * sizeof(T)));
-    HIP_TRY(hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return GAAST_OK;
-}
 
 int mv_alloc_impl(int dim, uint64_t mask, int64_t batch, int dtype, gaast_hip_mv_t* out) {
     auto* m = new gaast_hip_mv_s;
@@ -173,6 +228,7 @@ void mv_free_impl(gaast_hip_mv_t m) {
     if (m->owns && m->ptr) (void)hipFree(m->ptr);
     delete m;
 }
+void MvFree::operator()(gaast_hip_mv_t m) const { mv_free_impl(m); }
 
 int grid_for(int64_t total, int block) {
     int64_t g = (total + block - 1) / block;
@@ -251,7 +307,7 @@ int launch_linmap(const LinmapDev& m, const Layout& l, const Bound& in, const Bo
     std::memset(&p, 0, sizeof(p));
     p.in = static_cast<const T*>(in.ptr);
     p.out = static_cast<T*>(out.ptr);
-    p.mats = static_cast<const T*>(m.d_mats);
+    p.mats = m.mats.as<T>();
     p.in_stride = in.stride;
     p.out_stride = out.stride;
     p.batch = batch;
@@ -291,43 +347,37 @@ const char* linmap_kernel_name(int n, int dtype) {
     return dtype == GAAST_F32 ? "k_linmap_mfma<float>" : "k_linmap_mfma<double>";
 }
 
-// the compounds of `mat` (n x n, row-major) rounded to dtype, on the device.  n <= kLinmapMaxDim.
-int linmap_build(int n, const double* mat, int dtype, LinmapDev& dev, std::vector<std::vector<double>>* host = nullptr) {
+// the compounds of `mat` (n x n, row-major) rounded to dtype, on the device (and in double, grade k at dev.moff[k], in *host).
+// n <= kLinmapMaxDim.
+int linmap_build(int n, const double* mat, int dtype, LinmapDev& dev, std::vector<double>* host = nullptr) {
     std::vector<std::vector<double>> c;
     compound_matrices(n, mat, n, c);
     dev.n = n;
     dev.dtype = dtype;
     dev.moff.assign(size_t(n + 1), 0);
-    size_t total = 0;
+    std::vector<double> all;
     for (int k = 0; k <= n; ++k) {
-        dev.moff[size_t(k)] = int(total);
-        total += c[size_t(k)].size();
+        dev.moff[size_t(k)] = int(all.size());
+        all.insert(all.end(), c[size_t(k)].begin(), c[size_t(k)].end());
+        std::vector<double>().swap(c[size_t(k)]);
     }
-    dev.mat_total = int(total);
+    dev.mat_total = int(all.size());
+    if (host) *host = all;
+    if (int st = dev.mats.upload(std::move(all), dtype)) return st;
     const size_t esz = dtype_size(dtype);
-    HIP_TRY(hipMalloc(&dev.d_mats, total * esz));
-    for (int k = 0; k <= n; ++k) {
-        const std::vector<double>& ck = c[size_t(k)];
-        char* dst = static_cast<char*>(dev.d_mats) + size_t(dev.moff[size_t(k)]) * esz;
-        if (dtype == GAAST_F32) {
-            std::vector<float> f(ck.begin(), ck.end());
-            HIP_TRY(hipMemcpy(dst, f.data(), f.size() * 4, hipMemcpyHostToDevice));
-        } else {
-            HIP_TRY(hipMemcpy(dst, ck.data(), ck.size() * 8, hipMemcpyHostToDevice));
-        }
-    }
     if (n <= kLinmapSmallMaxDim) {
         const void* kern = dtype == GAAST_F32 ? reinterpret_cast<const void*>(&k_linmap_small<float>) : reinterpret_cast<const void*>(&k_linmap_small<double>);
         const size_t lds = linmap_small_lds(dev, kLinmapSmallComps, esz);   // the longest row
         if (int st = allow_lds(kern, lds)) return st;
         if (int st = resident_blocks(kern, 256, lds, &dev.small_blocks_per_cu)) return st;
     }
-    if (host) *host = std::move(c);
     return GAAST_OK;
 }
 
 template <typename T>
-int prepare_step(Step& s, const Layout& la, const Layout& lb, int n) {
+int prepare_step(Launch& L, const Layout& la, const Layout& lb, std::string& kernel) {
+    Step& s = L.s;
+    const int n = L.n;
     constexpr bool is_f64 = std::is_same<T, double>::value;
     const std::string tn = is_f64 ? "double" : "float";
     const std::string dg = s.degenerate ? "true" : "false";
@@ -340,46 +390,43 @@ int prepare_step(Step& s, const Layout& la, const Layout& lb, int n) {
             return set_err(GAAST_ERR_UNIMPLEMENTED,
                            "product operands of " + std::to_string(per_item) + " bytes per item do not fit the " +
                                std::to_string(g_max_lds) + "-byte LDS of the list kernels (" + s.name + ")");
-        if (s.chain_jit == 2) {
+        if (L.jit) {
             // the chain (or single long-row list) specialised through hiprtc (plan.cpp: make_chain_jit): static LDS, persistent workgroups
-            s.threads = s.cj_threads;
-            s.lds = s.cj_lds;
-            s.hip_kernel = "gaast_chain<" + tn + ">[" + (s.list_jit ? "one list, " : "") + std::to_string(s.cj_ipb) + " items, " + std::to_string(s.cj_threads) + " threads" +
-                           (s.cj_split > 1 ? ", rows in " + std::to_string(s.cj_split) + " slices: re-ordered sums" : "") +
-                           (s.cj_fmt[1] >= 3 ? ", sign-sorted terms" : "") + "]";
+            L.threads = s.cj_threads;
+            L.lds = s.cj_lds;
+            kernel = "gaast_chain<" + tn + ">[" + (s.list_jit ? "one list, " : "") + std::to_string(s.cj_ipb) + " items, " + std::to_string(s.cj_threads) + " threads" +
+                      (s.cj_split > 1 ? ", rows in " + std::to_string(s.cj_split) + " slices: re-ordered sums" : "") +
+                      (s.cj_fmt[1] >= 3 ? ", sign-sorted terms" : "") + "]";
             int per_cu = 0;
-            HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, static_cast<hipFunction_t>(s.jit_function), s.threads, 0));
-            s.blocks_per_cu = per_cu < 1 ? 1 : per_cu;
+            HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, L.jit.fn, L.threads, 0));
+            L.blocks_per_cu = per_cu < 1 ? 1 : per_cu;
             return GAAST_OK;
         }
         if (s.list_chain) {
             // two lists in one launch, the mid row in LDS (plan.cpp: chain_list_into_list): IPB items per workgroup
-            s.lds = size_t(s.chain_ent2_lds) + size_t(s.chain_item_stride) * size_t(s.chain_ipb) * sizeof(T);
-            if (s.lds > g_max_lds) {
-                g_chain_too_big = true;
-                return set_err(GAAST_ERR_UNIMPLEMENTED, "list chain does not fit in LDS (" + s.name + ")");
-            }
+            L.lds = size_t(s.chain_ent2_lds) + size_t(s.chain_item_stride) * size_t(s.chain_ipb) * sizeof(T);
+            if (L.lds > g_max_lds) return set_err(kChainTooBig, "list chain does not fit in LDS (" + s.name + ")");
             const int64_t pairs2 = int64_t(s.u32_b.size()) * s.chain_ipb;
-            s.threads = int(std::min<int64_t>(512, std::max<int64_t>(256, (pairs2 + 63) / 64 * 64)));
-            s.kern[0] = reinterpret_cast<const void*>(&k_product_ell_chain<T>);
-            s.hip_kernel = "k_product_ell_chain<" + tn + ">";
-            if (int st = allow_lds(s.kern[0], s.lds)) return st;
-            return resident_blocks(s.kern[0], s.threads, s.lds, &s.blocks_per_cu);   // persistent workgroups
+            L.threads = int(std::min<int64_t>(512, std::max<int64_t>(256, (pairs2 + 63) / 64 * 64)));
+            L.kern[0] = reinterpret_cast<const void*>(&k_product_ell_chain<T>);
+            kernel = "k_product_ell_chain<" + tn + ">";
+            if (int st = allow_lds(L.kern[0], L.lds)) return st;
+            return resident_blocks(L.kern[0], L.threads, L.lds, &L.blocks_per_cu);   // persistent workgroups
         }
-        s.lds = per_item;
-        s.threads = 256;
+        L.lds = per_item;
+        L.threads = 256;
         if (s.ell_width > 0) {
             // items per pass over the list: as many as a 64 KiB share of LDS holds (at least one), at most 8
             int items = int((64 * 1024) / per_item);
             items = items >= 8 ? 8 : items >= 4 ? 4 : items >= 2 ? 2 : 1;
-            s.max_items = items;
+            L.max_items = items;
             using KernE = void (*)(EllArgs<T>);
             const KernE tab[2][4] = {{&k_product_ell<T, 1, false>, &k_product_ell<T, 2, false>, &k_product_ell<T, 4, false>, &k_product_ell<T, 8, false>},
                                      {&k_product_ell<T, 1, true>, &k_product_ell<T, 2, true>, &k_product_ell<T, 4, true>, &k_product_ell<T, 8, true>}};
-            s.hip_kernel = "k_product_ell<" + tn + ",1.." + std::to_string(items) + "," + (s.ell_bytes ? "true" : "false") + ">";
+            kernel = "k_product_ell<" + tn + ",1.." + std::to_string(items) + "," + (s.ell_bytes ? "true" : "false") + ">";
             for (int l2 = 0; (1 << l2) <= items; ++l2) {
-                s.kern[l2] = reinterpret_cast<const void*>(tab[s.ell_bytes ? 1 : 0][l2]);
-                if (int st = allow_lds(s.kern[l2], per_item << l2)) return st;
+                L.kern[l2] = reinterpret_cast<const void*>(tab[s.ell_bytes ? 1 : 0][l2]);
+                if (int st = allow_lds(L.kern[l2], per_item << l2)) return st;
             }
             return GAAST_OK;
         }
@@ -389,17 +436,17 @@ int prepare_step(Step& s, const Layout& la, const Layout& lb, int n) {
         const size_t budget = 64 * 1024;
         if (per_item * size_t(items) > budget) items = int(budget / per_item);
         if (items < 1) items = 1;
-        s.max_items = items;
-        s.kern[0] = reinterpret_cast<const void*>(&k_product_csr<T>);
-        s.hip_kernel = "k_product_csr<" + tn + ">";
-        return allow_lds(s.kern[0], per_item * size_t(items));
+        L.max_items = items;
+        L.kern[0] = reinterpret_cast<const void*>(&k_product_csr<T>);
+        kernel = "k_product_csr<" + tn + ">";
+        return allow_lds(L.kern[0], per_item * size_t(items));
     }
     case Step::PRODUCT_DENSE: {
         if (s.use_spinor) {
             using KernS = void (*)(SpinorArgs);
             const int m = s.use_spinor;
             const size_t D = size_t(1) << m, plane = (D * (D + 1) + 63) / 64 * 64;
-            s.lds = (m == 6 ? 2 * plane + (is_f64 ? 0 : 16) : 2 * D * (D + 1)) * sizeof(T);   // k_gp_spinor12s: second plane 16 words further
+            L.lds = (m == 6 ? 2 * plane + (is_f64 ? 0 : 16) : 2 * D * (D + 1)) * sizeof(T);   // k_gp_spinor12s: second plane 16 words further
             const int lb5 = s.spinor_lam_bit;
             KernS kern = nullptr;
             if (is_f64 && m == 6) kern = lb5 == 5 ? &k_gp_spinor12d<5> : lb5 == 4 ? &k_gp_spinor12d<4> : &k_gp_spinor12d<-1>;
@@ -408,26 +455,26 @@ int prepare_step(Step& s, const Layout& la, const Layout& lb, int n) {
             else if (m == 6) {
                 kern = lb5 == 5 ? &k_gp_spinor12s<5, false> : lb5 == 4 ? &k_gp_spinor12s<4, false> : &k_gp_spinor12s<-1, false>;
                 const KernS fast = lb5 == 5 ? &k_gp_spinor12s<5, true> : lb5 == 4 ? &k_gp_spinor12s<4, true> : &k_gp_spinor12s<-1, true>;
-                s.kern[1] = reinterpret_cast<const void*>(fast);   // full, aligned rows on both sides and in the result
-                if (int st = allow_lds(s.kern[1], s.lds)) return st;
+                L.kern[1] = reinterpret_cast<const void*>(fast);   // full, aligned rows on both sides and in the result
+                if (int st = allow_lds(L.kern[1], L.lds)) return st;
             }
             else if (m == 5) kern = lb5 == 4 ? &k_gp_spinor_wave1<5, 4> : lb5 == 3 ? &k_gp_spinor_wave1<5, 3> : &k_gp_spinor_wave1<5, -1>;
             else kern = lb5 == 3 ? &k_gp_spinor_wave1<4, 3> : lb5 == 2 ? &k_gp_spinor_wave1<4, 2> : &k_gp_spinor_wave1<4, -1>;
-            s.kern[0] = reinterpret_cast<const void*>(kern);
-            s.hip_kernel = (m == 6 ? (is_f64 ? "k_gp_spinor12d<" : "k_gp_spinor12s<") : (is_f64 ? "k_gp_spinor_wave1d<" : "k_gp_spinor_wave1<") + std::to_string(m) + ",") +
-                           std::to_string(lb5) + ">";
-            s.threads = m == 6 ? 256 : 64;
-            if (int st = allow_lds(s.kern[0], s.lds)) return st;
-            return resident_blocks(s.kern[0], s.threads, s.lds, &s.blocks_per_cu);
+            L.kern[0] = reinterpret_cast<const void*>(kern);
+            kernel = (m == 6 ? (is_f64 ? "k_gp_spinor12d<" : "k_gp_spinor12s<") : (is_f64 ? "k_gp_spinor_wave1d<" : "k_gp_spinor_wave1<") + std::to_string(m) + ",") +
+                      std::to_string(lb5) + ">";
+            L.threads = m == 6 ? 256 : 64;
+            if (int st = allow_lds(L.kern[0], L.lds)) return st;
+            return resident_blocks(L.kern[0], L.threads, L.lds, &L.blocks_per_cu);
         }
         if (s.use_mfma) {
             if constexpr (!is_f64) {
                 const int wpi = 1 << (n - 10);                 // waves per item
-                s.threads = wpi > 4 ? wpi * 64 : 256;
-                s.items_per_block = (s.threads / 64) / wpi;
+                L.threads = wpi > 4 ? wpi * 64 : 256;
+                L.items_per_block = (L.threads / 64) / wpi;
                 if (s.mfma32_pairs) {
-                    s.lds = (size_t(s.items_per_block) * size_t(4 << n) + 16) * sizeof(float);
-                    if (s.lds > g_max_lds) return set_err(GAAST_ERR_UNIMPLEMENTED, "dense product does not fit in LDS");
+                    L.lds = (size_t(L.items_per_block) * size_t(4 << n) + 16) * sizeof(float);
+                    if (L.lds > g_max_lds) return set_err(GAAST_ERR_UNIMPLEMENTED, "dense product does not fit in LDS");
                     using KernD = void (*)(DenseArgs<float>);
                     const KernD kernp = pick_variant(s.scaled, s.chained, [&](auto sc, auto ch) -> KernD {
                         constexpr bool SC = decltype(sc)::value, CH = decltype(ch)::value;
@@ -436,31 +483,31 @@ int prepare_step(Step& s, const Layout& la, const Layout& lb, int n) {
                                : n == 12 ? (s.degenerate ? &k_gp_mfma32p<true, 12, SC, CH> : &k_gp_mfma32p<false, 12, SC, CH>)
                                          : (s.degenerate ? &k_gp_mfma32p<true, 13, SC, CH> : &k_gp_mfma32p<false, 13, SC, CH>);
                     });
-                    s.kern[0] = reinterpret_cast<const void*>(kernp);
-                    s.hip_kernel = "k_gp_mfma32p<" + dg + "," + std::to_string(n) + vs + ">";
-                    if (int st = allow_lds(s.kern[0], s.lds)) return st;
-                    return resident_blocks(s.kern[0], s.threads, s.lds, &s.blocks_per_cu);   // persistent workgroups
+                    L.kern[0] = reinterpret_cast<const void*>(kernp);
+                    kernel = "k_gp_mfma32p<" + dg + "," + std::to_string(n) + vs + ">";
+                    if (int st = allow_lds(L.kern[0], L.lds)) return st;
+                    return resident_blocks(L.kern[0], L.threads, L.lds, &L.blocks_per_cu);   // persistent workgroups
                 }
-                s.lds = size_t(s.items_per_block) * size_t(2 << n) * sizeof(float);
-                if (s.lds > g_max_lds) return set_err(GAAST_ERR_UNIMPLEMENTED, "dense product does not fit in LDS");
+                L.lds = size_t(L.items_per_block) * size_t(2 << n) * sizeof(float);
+                if (L.lds > g_max_lds) return set_err(GAAST_ERR_UNIMPLEMENTED, "dense product does not fit in LDS");
                 using KernD = void (*)(DenseArgs<float>);
                 // (k_gp_mfma32 serves n = 14 only -- 16 waves and 128 KiB of LDS per item; n = 10 ... 13 run on k_gp_mfma32p)
-                if (s.threads != 1024) return set_err(GAAST_ERR_UNIMPLEMENTED, "k_gp_mfma32 is built for n = 14 only");
+                if (L.threads != 1024) return set_err(GAAST_ERR_UNIMPLEMENTED, "k_gp_mfma32 is built for n = 14 only");
                 const KernD kern = pick_variant(s.scaled, s.chained, [&](auto sc, auto ch) -> KernD {
                     constexpr bool SC = decltype(sc)::value, CH = decltype(ch)::value;
                     return s.degenerate ? &k_gp_mfma32<true, 1024, SC, CH> : &k_gp_mfma32<false, 1024, SC, CH>;
                 });
-                s.kern[0] = reinterpret_cast<const void*>(kern);
-                s.hip_kernel = "k_gp_mfma32<" + dg + "," + std::to_string(s.threads) + vs + ">";
-                return allow_lds(s.kern[0], s.lds);
+                L.kern[0] = reinterpret_cast<const void*>(kern);
+                kernel = "k_gp_mfma32<" + dg + "," + std::to_string(L.threads) + vs + ">";
+                return allow_lds(L.kern[0], L.lds);
             }
         }
         if (s.use_mfma16 && s.use_mfma16d) {
             // k_gp_mfma16x4<T>: one wave per 16 result columns, one item per workgroup (f64: n = 8 ... 12; f32: build switch)
-            s.threads = 64 << (n - 8);
-            s.items_per_block = 1;
-            s.lds = size_t(4 * (size_t(1) << n) + 32) * sizeof(T);   // +B, -B, +A, 16 spare, -A images, 16 zeros
-            if (s.lds > g_max_lds) return set_err(GAAST_ERR_UNIMPLEMENTED, "dense product does not fit in LDS");
+            L.threads = 64 << (n - 8);
+            L.items_per_block = 1;
+            L.lds = size_t(4 * (size_t(1) << n) + 32) * sizeof(T);   // +B, -B, +A, 16 spare, -A images, 16 zeros
+            if (L.lds > g_max_lds) return set_err(GAAST_ERR_UNIMPLEMENTED, "dense product does not fit in LDS");
             using KernD = void (*)(DenseArgs<T>);
             // [0]: general staging; [1]: register prefetch (full, contiguous, 16-byte aligned rows at launch); [2]: ... and
             // every blade produced, nothing accumulated: straight-line result stores
@@ -474,34 +521,34 @@ int prepare_step(Step& s, const Layout& la, const Layout& lb, int n) {
             const KernD kf = chained_fast ? pick_chained(std::integral_constant<int, 1>{}) : pick(std::integral_constant<int, 1>{}),
                         kw = chained_fast ? pick_chained(std::integral_constant<int, 2>{}) : pick(std::integral_constant<int, 2>{});
             if (!kd || !kf || !kw) return set_err(GAAST_ERR_UNIMPLEMENTED, "no k_gp_mfma16x4 instantiation for this dimension and value type");
-            s.kern[0] = reinterpret_cast<const void*>(kd);
-            s.kern[1] = reinterpret_cast<const void*>(kf);
-            s.kern[2] = reinterpret_cast<const void*>(kw);
-            s.hip_kernel = "k_gp_mfma16x4<" + tn + "," + dg + "," + std::to_string(n) + (s.scaled ? ",0" + vs + ">" : ",0|1|2" + vs + ">");   // staging / store mode: by alignment at launch
+            L.kern[0] = reinterpret_cast<const void*>(kd);
+            L.kern[1] = reinterpret_cast<const void*>(kf);
+            L.kern[2] = reinterpret_cast<const void*>(kw);
+            kernel = "k_gp_mfma16x4<" + tn + "," + dg + "," + std::to_string(n) + (s.scaled ? ",0" + vs + ">" : ",0|1|2" + vs + ">");   // staging / store mode: by alignment at launch
             for (int v = 0; v < 3; ++v)
-                if (int st = allow_lds(s.kern[v], s.lds)) return st;
-            return resident_blocks(s.kern[1], s.threads, s.lds, &s.blocks_per_cu);   // persistent workgroups
+                if (int st = allow_lds(L.kern[v], L.lds)) return st;
+            return resident_blocks(L.kern[1], L.threads, L.lds, &L.blocks_per_cu);   // persistent workgroups
         }
         if (s.use_mfma6) {
             // k_gp_mfma6<T>: one wave per item, persistent single-wave workgroups, 2 KiB (f32) / 4 KiB (f64) of operand images
-            s.threads = 64 * GAAST_MFMA6_WAVES;
-            s.items_per_block = GAAST_MFMA6_WAVES;
-            s.lds = (size_t(is_f64 ? 4096 : 2048) + 64 * sizeof(T)) * GAAST_MFMA6_WAVES;   // + a dummy element per lane (stores of vanishing slots)
+            L.threads = 64 * GAAST_MFMA6_WAVES;
+            L.items_per_block = GAAST_MFMA6_WAVES;
+            L.lds = (size_t(is_f64 ? 4096 : 2048) + 64 * sizeof(T)) * GAAST_MFMA6_WAVES;   // + a dummy element per lane (stores of vanishing slots)
             using KernD = void (*)(DenseArgs<T>);
             // [0]: any operands (partial grade sets, projected or accumulated results); [1]: full operands, every blade produced, nothing
             // accumulated -- straight-line item loop with counted waits
             const KernD k6 = s.scaled ? &k_gp_mfma6<T, true, false> : &k_gp_mfma6<T, false, false>;
             const KernD k6f = s.scaled ? &k_gp_mfma6<T, true, true> : &k_gp_mfma6<T, false, true>;
-            s.kern[0] = reinterpret_cast<const void*>(k6);
-            s.kern[1] = reinterpret_cast<const void*>(k6f);
-            s.hip_kernel = "k_gp_mfma6<" + tn + (s.scaled ? ",true,0|1>" : ",false,0|1>");
-            return resident_blocks(s.kern[1], s.threads, s.lds, &s.blocks_per_cu);
+            L.kern[0] = reinterpret_cast<const void*>(k6);
+            L.kern[1] = reinterpret_cast<const void*>(k6f);
+            kernel = "k_gp_mfma6<" + tn + (s.scaled ? ",true,0|1>" : ",false,0|1>");
+            return resident_blocks(L.kern[1], L.threads, L.lds, &L.blocks_per_cu);
         }
         if (s.use_mfma7) {
             // k_gp_mfma7<T>: one wave per item, single-wave workgroups
-            s.threads = 64;
-            s.items_per_block = 1;
-            s.lds = size_t(560) * sizeof(T);   // +B, -B, +A (u = 1 half 72 further), -A 144 further, 16 zeros
+            L.threads = 64;
+            L.items_per_block = 1;
+            L.lds = size_t(560) * sizeof(T);   // +B, -B, +A (u = 1 half 72 further), -A 144 further, 16 zeros
             using KernD = void (*)(DenseArgs<T>);
             const KernD kd = pick_variant(s.scaled, s.chained, [&](auto sc, auto ch) -> KernD {
                 return &k_gp_mfma7<T, 0, decltype(sc)::value, decltype(ch)::value>;
@@ -509,43 +556,43 @@ int prepare_step(Step& s, const Layout& la, const Layout& lb, int n) {
             const bool chained_fast = s.chained && !s.scaled;
             const KernD kf = chained_fast ? &k_gp_mfma7<T, 1, false, true> : &k_gp_mfma7<T, 1>;
             const KernD kw = chained_fast ? &k_gp_mfma7<T, 2, false, true> : &k_gp_mfma7<T, 2>;
-            s.kern[0] = reinterpret_cast<const void*>(kd);
-            s.kern[1] = reinterpret_cast<const void*>(kf);
-            s.kern[2] = reinterpret_cast<const void*>(kw);
-            s.hip_kernel = "k_gp_mfma7<" + tn + (s.scaled ? ",0" + vs + ">" : ",0|1|2" + vs + ">");   // (null vectors: run-time, no instantiation of their own)
-            return resident_blocks(s.kern[1], s.threads, s.lds, &s.blocks_per_cu);   // persistent single-wave workgroups
+            L.kern[0] = reinterpret_cast<const void*>(kd);
+            L.kern[1] = reinterpret_cast<const void*>(kf);
+            L.kern[2] = reinterpret_cast<const void*>(kw);
+            kernel = "k_gp_mfma7<" + tn + (s.scaled ? ",0" + vs + ">" : ",0|1|2" + vs + ">");   // (null vectors: run-time, no instantiation of their own)
+            return resident_blocks(L.kern[1], L.threads, L.lds, &L.blocks_per_cu);   // persistent single-wave workgroups
         }
         const int lpi = 1 << (n - 4);
-        s.threads = lpi > 256 ? lpi : 256;
-        s.items_per_block = s.threads / lpi;
-        s.lds = size_t(s.items_per_block) * size_t(2 * (1 << n) + (s.items_per_block > 1 ? 4 : 0)) * sizeof(T);
-        if (s.lds > g_max_lds)
+        L.threads = lpi > 256 ? lpi : 256;
+        L.items_per_block = L.threads / lpi;
+        L.lds = size_t(L.items_per_block) * size_t(2 * (1 << n) + (L.items_per_block > 1 ? 4 : 0)) * sizeof(T);
+        if (L.lds > g_max_lds)
             return set_err(GAAST_ERR_UNIMPLEMENTED, "dense product of dimension " + std::to_string(n) + " does not fit in LDS");
         using KernD = void (*)(DenseArgs<T>);
         const KernD kern = pick_variant(s.scaled, s.chained, [&](auto sc, auto ch) -> KernD {
             constexpr bool SC = decltype(sc)::value, CH = decltype(ch)::value;
             if (s.neg_lo_all)
-                return s.threads == 256 ? (s.degenerate ? &k_gp_dense<T, true, 256, true, SC, CH> : &k_gp_dense<T, false, 256, true, SC, CH>)
+                return L.threads == 256 ? (s.degenerate ? &k_gp_dense<T, true, 256, true, SC, CH> : &k_gp_dense<T, false, 256, true, SC, CH>)
                                         : (s.degenerate ? &k_gp_dense<T, true, 512, true, SC, CH> : &k_gp_dense<T, false, 512, true, SC, CH>);
-            return s.threads == 256 ? (s.degenerate ? &k_gp_dense<T, true, 256, false, SC, CH> : &k_gp_dense<T, false, 256, false, SC, CH>)
+            return L.threads == 256 ? (s.degenerate ? &k_gp_dense<T, true, 256, false, SC, CH> : &k_gp_dense<T, false, 256, false, SC, CH>)
                                     : (s.degenerate ? &k_gp_dense<T, true, 512, false, SC, CH> : &k_gp_dense<T, false, 512, false, SC, CH>);
         });
-        s.kern[0] = reinterpret_cast<const void*>(kern);
-        s.hip_kernel = "k_gp_dense<" + tn + "," + dg + "," + std::to_string(s.threads) + "," + (s.neg_lo_all ? "true" : "false") + vs + ">";
-        if (int st = allow_lds(s.kern[0], s.lds)) return st;
+        L.kern[0] = reinterpret_cast<const void*>(kern);
+        kernel = "k_gp_dense<" + tn + "," + dg + "," + std::to_string(L.threads) + "," + (s.neg_lo_all ? "true" : "false") + vs + ">";
+        if (int st = allow_lds(L.kern[0], L.lds)) return st;
         // persistent workgroups: as many as are resident at once (register- and LDS-limited)
-        return resident_blocks(s.kern[0], s.threads, s.lds, &s.blocks_per_cu);
+        return resident_blocks(L.kern[0], L.threads, L.lds, &L.blocks_per_cu);
     }
     case Step::ELEMENTWISE:
-        s.hip_kernel = "k_elementwise<" + tn + (s.ew_ops <= 4 ? ",4>" : ",8>");
+        kernel = "k_elementwise<" + tn + (s.ew_ops <= 4 ? ",4>" : ",8>");
         return GAAST_OK;
-    case Step::AXPY: s.hip_kernel = "k_axpy_map<" + tn + ">"; return GAAST_OK;
-    case Step::FLIP: s.hip_kernel = "k_flip<" + tn + ">"; return GAAST_OK;
-    case Step::SUNARY: s.hip_kernel = "k_scalar_unary<" + tn + ">"; return GAAST_OK;
+    case Step::AXPY: kernel = "k_axpy_map<" + tn + ">"; return GAAST_OK;
+    case Step::FLIP: kernel = "k_flip<" + tn + ">"; return GAAST_OK;
+    case Step::SUNARY: kernel = "k_scalar_unary<" + tn + ">"; return GAAST_OK;
     case Step::REDUCE_SCALE: {
-        s.threads = 256;
-        s.kern[0] = reinterpret_cast<const void*>(&k_reduce_scale<T>);
-        s.hip_kernel = "k_reduce_scale<" + tn + ">";
+        L.threads = 256;
+        L.kern[0] = reinterpret_cast<const void*>(&k_reduce_scale<T>);
+        kernel = "k_reduce_scale<" + tn + ">";
         if (s.rs_wave) {   // tolerance mode: one wave per item, the row read once -- taken at launch when the three rows are one (run_step)
             using KernW = void (*)(ReduceScaleArgs<T>, const uint32_t*);
             KernW kw = nullptr;
@@ -559,40 +606,42 @@ int prepare_step(Step& s, const Layout& la, const Layout& lb, int n) {
                 break;
             default: break;
             }
-            s.kern[1] = reinterpret_cast<const void*>(kw);
-            if (kw) s.hip_kernel += " | k_reduce_scale_wave<" + tn + "," + std::to_string(s.rs_wave) + "> (lane-parallel sums) when the rows are one";
+            L.kern[1] = reinterpret_cast<const void*>(kw);
+            if (kw) kernel += " | k_reduce_scale_wave<" + tn + "," + std::to_string(s.rs_wave) + "> (lane-parallel sums) when the rows are one";
             else s.rs_wave = 0;
         }
-        return resident_blocks(s.kern[0], s.threads, 0, &s.blocks_per_cu);
+        return resident_blocks(L.kern[0], L.threads, 0, &L.blocks_per_cu);
     }
     case Step::FUSED: {
-        if (s.jit_function) return GAAST_OK;
+        if (L.jit) return GAAST_OK;
         const size_t lds = (size_t(s.fused_slab) * FUSED_ITEMS + 8) * sizeof(T);
         return allow_lds(reinterpret_cast<const void*>(&k_ast_fused<T>), lds);
     }
     case Step::LINMAP:
-        s.hip_kernel = linmap_kernel_name(static_cast<const LinmapDev*>(s.linmap)->n, is_f64 ? GAAST_F64 : GAAST_F32);
+        kernel = linmap_kernel_name(L.linmap->n, is_f64 ? GAAST_F64 : GAAST_F32);
         return GAAST_OK;
     default: return GAAST_OK;
     }
 }
 
 template <typename T>
-int run_step(const Step& s, const Bound& res, const Bound& a, const Bound& b, const Layout& la,
-             const Layout& lb, int64_t batch, int n, const Bound& pre_a = Bound{nullptr, 0}, const Bound& pre_b = Bound{nullptr, 0}) {
+int run_step(const Launch& L, const Bound& res, const Bound& a, const Bound& b, const Layout& la, const Layout& lb, int64_t batch,
+             const Bound& pre_a = Bound{nullptr, 0}, const Bound& pre_b = Bound{nullptr, 0}) {
+    const Step& s = L.s;
+    const int n = L.n;
     switch (s.kind) {
     case Step::ZERO: return GAAST_OK;  // handled by the caller (needs the row length)
     case Step::AXPY: {
-        const int nm = int(s.u32_a.size());
+        const int nm = int(L.u32_a.count);
         hipLaunchKernelGGL(k_axpy_map<T>, dim3(grid_for(batch * nm, 256)), dim3(256), 0, g_stream,
                            static_cast<T*>(res.ptr), res.stride, static_cast<const T*>(a.ptr), a.stride,
-                           static_cast<const uint32_t*>(s.d_a), nm, batch, s.beta);
+                           L.u32_a.as<uint32_t>(), nm, batch, s.beta);
         break;
     }
     case Step::FLIP: {
-        const int nm = int(s.u32_a.size());
+        const int nm = int(L.u32_a.count);
         hipLaunchKernelGGL(k_flip<T>, dim3(grid_for(batch * nm, 256)), dim3(256), 0, g_stream,
-                           static_cast<T*>(res.ptr), res.stride, static_cast<const uint32_t*>(s.d_a), nm, batch);
+                           static_cast<T*>(res.ptr), res.stride, L.u32_a.as<uint32_t>(), nm, batch);
         break;
     }
     case Step::SUNARY:
@@ -609,12 +658,12 @@ int run_step(const Step& s, const Bound& res, const Bound& a, const Bound& b, co
         q.r1_stride = b.stride;
         q.x_stride = pre_a.stride;
         q.out_stride = res.stride;
-        q.ent1 = static_cast<const uint32_t*>(s.d_a);
-        q.coeff1 = static_cast<const T*>(s.d_coeff);
-        q.ent2 = static_cast<const uint32_t*>(s.d_b);
-        q.coeff2 = static_cast<const T*>(s.d_coeff_b);
-        q.n1 = int(s.u32_a.size());
-        q.n2 = int(s.u32_b.size());
+        q.ent1 = L.u32_a.as<uint32_t>();
+        q.coeff1 = L.coeff.as<T>();
+        q.ent2 = L.u32_b.as<uint32_t>();
+        q.coeff2 = L.coeff_b.as<T>();
+        q.n1 = int(L.u32_a.count);
+        q.n2 = int(L.u32_b.count);
         q.canon_l1 = s.canon_a;
         q.canon_r1 = s.canon_b;
         q.canon_x = s.pre_canon_a;
@@ -622,20 +671,20 @@ int run_step(const Step& s, const Bound& res, const Bound& a, const Bound& b, co
         q.s_is_left = s.list_chain == 1;
         q.op = s.rs_op;
         q.batch = batch;
-        if (s.rs_wave && s.kern[1] && a.ptr == b.ptr && a.ptr == pre_a.ptr && a.stride == b.stride && a.stride == pre_a.stride &&
+        if (s.rs_wave && L.kern[1] && a.ptr == b.ptr && a.ptr == pre_a.ptr && a.stride == b.stride && a.stride == pre_a.stride &&
             (reinterpret_cast<uintptr_t>(a.ptr) & 15u) == 0 && (size_t(a.stride) * sizeof(T)) % 16 == 0 &&
             (reinterpret_cast<uintptr_t>(res.ptr) & 15u) == 0 && (size_t(res.stride) * sizeof(T)) % 16 == 0 && res.ptr != a.ptr) {
             // one wave per item, four per workgroup, persistent
             using KernW = void (*)(ReduceScaleArgs<T>, const uint32_t*);
             int64_t blocks = (batch + 3) / 4;
             blocks = std::min<int64_t>(blocks, int64_t(g_num_cu) * 8);
-            hipLaunchKernelGGL(reinterpret_cast<KernW>(const_cast<void*>(s.kern[1])), dim3(unsigned(blocks)), dim3(256), 0, g_stream, q,
-                               static_cast<const uint32_t*>(s.d_c));
+            hipLaunchKernelGGL(reinterpret_cast<KernW>(const_cast<void*>(L.kern[1])), dim3(unsigned(blocks)), dim3(256), 0, g_stream, q,
+                               L.u32_c.as<uint32_t>());
             break;
         }
         // sixteen items per wave, four waves per workgroup, persistent: as many workgroups as are resident at once
         int64_t blocks = (batch + 63) / 64;
-        blocks = std::min<int64_t>(blocks, int64_t(g_num_cu) * (s.blocks_per_cu > 0 ? s.blocks_per_cu : 8));
+        blocks = std::min<int64_t>(blocks, int64_t(g_num_cu) * (L.blocks_per_cu > 0 ? L.blocks_per_cu : 8));
         hipLaunchKernelGGL(k_reduce_scale<T>, dim3(unsigned(blocks)), dim3(256), 0, g_stream, q);
         break;
     }
@@ -652,32 +701,32 @@ int run_step(const Step& s, const Bound& res, const Bound& a, const Bound& b, co
         q.arg_0 = s.explog_arg_0;
         q.res_k = s.explog_res_k;
         q.res_0 = s.explog_res_0;
-        q.sq = static_cast<const T*>(s.d_coeff);
-        q.row_start = static_cast<const uint32_t*>(s.d_a);
-        q.pairs = static_cast<const uint32_t*>(s.d_c);
-        q.pair_coeff = static_cast<const T*>(s.d_coeff_b);
-        q.n_rows = int(s.u32_a.size()) - 1;
-        q.dom = static_cast<unsigned long long*>(s.d_domain);
+        q.sq = L.coeff.as<T>();
+        q.row_start = L.u32_a.as<uint32_t>();
+        q.pairs = L.u32_c.as<uint32_t>();
+        q.pair_coeff = L.coeff_b.as<T>();
+        q.n_rows = int(L.u32_a.count) - 1;
+        q.dom = static_cast<unsigned long long*>(L.domain);
         q.batch = batch;
         hipLaunchKernelGGL(k_exp_log<T>, dim3(grid_for(batch, 256)), dim3(256), 0, g_stream, q);
         break;
     }
     case Step::PRODUCT_CSR: {
-        if (s.chain_jit == 2) {
+        if (L.jit) {
             const bool mid_left = s.list_chain == 1;
             const Bound& other = s.list_jit ? b : s.chain_alias ? pre_a : (mid_left ? b : a);
             // a single list: its left operand is staged as the "mid" row (pointer l1), its right one is list 2's own operand (r2)
             const void *l1 = s.list_jit ? a.ptr : pre_a.ptr, *r1 = s.list_jit ? nullptr : pre_b.ptr, *r2 = other.ptr;
             long long s_l1 = s.list_jit ? a.stride : pre_a.stride, s_r1 = s.list_jit ? 0 : pre_b.stride, s_r2 = other.stride, s_out = res.stride, nb = batch;
             void* optr = res.ptr;
-            const void *e1 = s.d_cj_ent1, *p1 = s.d_cj_pos1, *e2 = s.d_cj_ent2, *o2 = s.d_cj_out2;
+            const void *e1 = L.cj_ent1.ptr, *p1 = L.cj_pos1.ptr, *e2 = L.cj_ent2.ptr, *o2 = L.cj_out2.ptr;
             const void* init = (s.list_jit && s.fold_prev) ? pre_a.ptr : nullptr;
             long long s_init = (s.list_jit && s.fold_prev) ? pre_a.stride : 0;
             void* args[] = {&l1, &s_l1, &r1, &s_r1, &r2, &s_r2, &optr, &s_out, &e1, &p1, &e2, &o2, &nb, &init, &s_init};
             int64_t blocks = (batch + s.cj_ipb - 1) / s.cj_ipb;
-            blocks = std::min<int64_t>(blocks, int64_t(g_num_cu) * s.blocks_per_cu);
+            blocks = std::min<int64_t>(blocks, int64_t(g_num_cu) * L.blocks_per_cu);
             // (the argument block is copied into the dispatch packet at call time, like run_jit's)
-            HIP_TRY(hipModuleLaunchKernel(static_cast<hipFunction_t>(s.jit_function), unsigned(blocks), 1, 1, unsigned(s.threads), 1, 1, 0, g_stream,
+            HIP_TRY(hipModuleLaunchKernel(L.jit.fn, unsigned(blocks), 1, 1, unsigned(L.threads), 1, 1, 0, g_stream,
                                           args, nullptr));
             break;
         }
@@ -702,13 +751,13 @@ int run_step(const Step& s, const Bound& res, const Bound& a, const Bound& b, co
             q.canon_r1 = s.pre_canon_b;
             q.canon_r2 = mid_left ? s.canon_b : s.canon_a;
             q.canon_mid = s.chain_canon_mid;
-            q.ent1 = static_cast<const uint32_t*>(s.d_pre_entries);
-            q.pos1 = static_cast<const uint32_t*>(s.d_pre_row_map);
-            q.rows1 = int(s.pre_row_map.size());
+            q.ent1 = L.pre_entries.as<uint32_t>();
+            q.pos1 = L.pre_row_map.as<uint32_t>();
+            q.rows1 = int(L.pre_row_map.count);
             q.width1 = s.pre_width;
-            q.ent2 = static_cast<const uint32_t*>(s.d_c);
-            q.out2 = static_cast<const uint32_t*>(s.d_b);
-            q.rows2 = int(s.u32_b.size());
+            q.ent2 = L.u32_c.as<uint32_t>();
+            q.out2 = L.u32_b.as<uint32_t>();
+            q.rows2 = int(L.u32_b.count);
             q.width2 = s.ell_width;
             q.mid_is_left = mid_left ? 1 : 0;
             q.r2_alias = s.chain_alias;
@@ -719,8 +768,8 @@ int run_step(const Step& s, const Bound& res, const Bound& a, const Bound& b, co
             q.batch = batch;
             q.ent2_lds_bytes = s.chain_ent2_lds;
             int64_t blocks = (batch + s.chain_ipb - 1) / s.chain_ipb;
-            if (s.blocks_per_cu > 0) blocks = std::min<int64_t>(blocks, int64_t(g_num_cu) * s.blocks_per_cu);
-            hipLaunchKernelGGL(k_product_ell_chain<T>, dim3(unsigned(blocks)), dim3(unsigned(s.threads)), s.lds, g_stream, q);
+            if (L.blocks_per_cu > 0) blocks = std::min<int64_t>(blocks, int64_t(g_num_cu) * L.blocks_per_cu);
+            hipLaunchKernelGGL(k_product_ell_chain<T>, dim3(unsigned(blocks)), dim3(unsigned(L.threads)), L.lds, g_stream, q);
             break;
         }
         if (s.ell_width > 0) {
@@ -735,18 +784,18 @@ int run_step(const Step& s, const Bound& res, const Bound& a, const Bound& b, co
             q.right_len = int(lb.row_len);
             q.canon_left = s.canon_a;
             q.canon_right = s.canon_b;
-            q.row_out = static_cast<const uint32_t*>(s.d_b);
-            q.entries = static_cast<const uint32_t*>(s.d_c);
-            q.n_rows = int(s.u32_b.size());
+            q.row_out = L.u32_b.as<uint32_t>();
+            q.entries = L.u32_c.as<uint32_t>();
+            q.n_rows = int(L.u32_b.count);
             q.width = s.ell_width;
             q.beta = s.beta;
             q.batch = batch;
-            int l2 = s.max_items >= 8 ? 3 : s.max_items >= 4 ? 2 : s.max_items >= 2 ? 1 : 0;
+            int l2 = L.max_items >= 8 ? 3 : L.max_items >= 4 ? 2 : L.max_items >= 2 ? 1 : 0;
             while (l2 > 0 && (int64_t(1) << l2) > batch) --l2;
             using KernE = void (*)(EllArgs<T>);
             const int64_t blocks = (batch + (int64_t(1) << l2) - 1) >> l2;
-            hipLaunchKernelGGL(reinterpret_cast<KernE>(const_cast<void*>(s.kern[l2])), dim3(unsigned(blocks)), dim3(256),
-                               s.lds << l2, g_stream, q);
+            hipLaunchKernelGGL(reinterpret_cast<KernE>(const_cast<void*>(L.kern[l2])), dim3(unsigned(blocks)), dim3(256),
+                               L.lds << l2, g_stream, q);
             break;
         }
         CsrArgs<T> p;
@@ -760,23 +809,23 @@ int run_step(const Step& s, const Bound& res, const Bound& a, const Bound& b, co
         p.right_len = int(lb.row_len);
         p.canon_left = s.canon_a;
         p.canon_right = s.canon_b;
-        p.row_start = static_cast<const uint32_t*>(s.d_a);
-        p.row_out = static_cast<const uint32_t*>(s.d_b);
-        p.entries = static_cast<const uint32_t*>(s.d_c);
-        p.coeff = static_cast<const T*>(s.d_coeff);
-        p.n_rows = int(s.u32_b.size());
+        p.row_start = L.u32_a.as<uint32_t>();
+        p.row_out = L.u32_b.as<uint32_t>();
+        p.entries = L.u32_c.as<uint32_t>();
+        p.coeff = L.coeff.as<T>();
+        p.n_rows = int(L.u32_b.count);
         p.beta = s.beta;
         p.batch = batch;
-        int items = s.max_items;
+        int items = L.max_items;
         if (int64_t(items) > batch) items = int(batch);
         p.items = items;
         const int64_t blocks = (batch + items - 1) / items;
-        hipLaunchKernelGGL(k_product_csr<T>, dim3(unsigned(blocks)), dim3(256), s.lds * size_t(items), g_stream, p);
+        hipLaunchKernelGGL(k_product_csr<T>, dim3(unsigned(blocks)), dim3(256), L.lds * size_t(items), g_stream, p);
         break;
     }
     case Step::FUSED: return GAAST_OK;  // launched by run_fused (needs every bound buffer)
     case Step::ELEMENTWISE: return GAAST_OK;  // launched by run_elementwise (needs every source buffer)
-    case Step::LINMAP: return launch_linmap<T>(*static_cast<const LinmapDev*>(s.linmap), la, a, res, batch);
+    case Step::LINMAP: return launch_linmap<T>(*L.linmap, la, a, res, batch);
     case Step::PRODUCT_DENSE: {
         if (s.use_spinor) {
             SpinorArgs q;
@@ -786,11 +835,11 @@ int run_step(const Step& s, const Bound& res, const Bound& a, const Bound& b, co
             q.left_stride = a.stride;
             q.right_stride = b.stride;
             q.out_stride = res.stride;
-            q.left_map = static_cast<const uint16_t*>(s.d_a);
-            q.right_map = static_cast<const uint16_t*>(s.d_b);
+            q.left_map = L.u32_a.as<uint16_t>();
+            q.right_map = L.u32_b.as<uint16_t>();
             q.left_full = s.left_full;
             q.right_full = s.right_full;
-            q.out_map = static_cast<const uint16_t*>(s.d_c);
+            q.out_map = L.u32_c.as<uint16_t>();
             q.out_full = s.out_full;
             q.left_len = int(la.row_len);
             q.right_len = int(lb.row_len);
@@ -800,15 +849,15 @@ int run_step(const Step& s, const Bound& res, const Bound& a, const Bound& b, co
             q.batch = batch;
             q.has_alpha = s.spinor_has_alpha;
             using KernS = void (*)(SpinorArgs);
-            int64_t blocks = int64_t(g_num_cu) * s.blocks_per_cu;
+            int64_t blocks = int64_t(g_num_cu) * L.blocks_per_cu;
             if (blocks > batch) blocks = batch;
             auto aligned16 = [](const void* ptr, int64_t stride) {
                 return (reinterpret_cast<uintptr_t>(ptr) % 16 == 0) && ((size_t(stride) * sizeof(T)) % 16 == 0);
             };
-            const bool fast = s.kern[1] && s.left_full && s.right_full && s.out_full && !s.beta && q.left_len == 4096 && q.right_len == 4096 &&
+            const bool fast = L.kern[1] && s.left_full && s.right_full && s.out_full && !s.beta && q.left_len == 4096 && q.right_len == 4096 &&
                               aligned16(a.ptr, a.stride) && aligned16(b.ptr, b.stride) && aligned16(res.ptr, res.stride);
-            hipLaunchKernelGGL(reinterpret_cast<KernS>(const_cast<void*>(s.kern[fast ? 1 : 0])), dim3(unsigned(blocks)),
-                               dim3(unsigned(s.threads)), s.lds, g_stream, q);
+            hipLaunchKernelGGL(reinterpret_cast<KernS>(const_cast<void*>(L.kern[fast ? 1 : 0])), dim3(unsigned(blocks)),
+                               dim3(unsigned(L.threads)), L.lds, g_stream, q);
             break;
         }
         DenseArgs<T> p;
@@ -818,10 +867,10 @@ int run_step(const Step& s, const Bound& res, const Bound& a, const Bound& b, co
         p.left_stride = a.stride;
         p.right_stride = b.stride;
         p.out_stride = res.stride;
-        p.left_map = static_cast<const uint32_t*>(s.d_a);
-        p.right_map = static_cast<const uint32_t*>(s.d_b);
-        p.left_count = int(s.u32_a.size());
-        p.right_count = int(s.u32_b.size());
+        p.left_map = L.u32_a.as<uint32_t>();
+        p.right_map = L.u32_b.as<uint32_t>();
+        p.left_count = int(L.u32_a.count);
+        p.right_count = int(L.u32_b.count);
         p.left_full = s.left_full;
         p.right_full = s.right_full;
         // vector loads need 16-byte aligned rows: base pointer and row stride
@@ -830,7 +879,7 @@ int run_step(const Step& s, const Bound& res, const Bound& a, const Bound& b, co
         };
         p.left_contig = s.left_contig && aligned(a.ptr, a.stride);
         p.right_contig = s.right_contig && aligned(b.ptr, b.stride);
-        p.out_map = static_cast<const int32_t*>(s.d_i32);
+        p.out_map = L.i32_a.as<int32_t>();
         p.canon_left = s.canon_a;
         p.canon_right = s.canon_b;
         p.n = n;
@@ -840,10 +889,10 @@ int run_step(const Step& s, const Bound& res, const Bound& a, const Bound& b, co
         p.beta = s.beta;
         p.batch = batch;
         using KernD = void (*)(DenseArgs<T>);
-        const int64_t groups = (batch + s.items_per_block - 1) / s.items_per_block;
+        const int64_t groups = (batch + L.items_per_block - 1) / L.items_per_block;
         int64_t blocks = groups;
-        if (s.blocks_per_cu > 0) {  // persistent workgroups (vector-FMA form)
-            blocks = int64_t(g_num_cu) * s.blocks_per_cu;
+        if (L.blocks_per_cu > 0) {  // persistent workgroups (vector-FMA form)
+            blocks = int64_t(g_num_cu) * L.blocks_per_cu;
             if (blocks > groups) blocks = groups;
         }
         p.left_signs = s.left_signs;
@@ -859,28 +908,28 @@ int run_step(const Step& s, const Bound& res, const Bound& a, const Bound& b, co
             p.pre_right_len = s.pre_right_len;
             p.pre_canon_left = s.pre_canon_a;
             p.pre_canon_right = s.pre_canon_b;
-            p.pre_row_start = static_cast<const uint32_t*>(s.d_pre_row_start);
-            p.pre_entries = static_cast<const uint32_t*>(s.d_pre_entries);
-            p.pre_coeff = static_cast<const T*>(s.d_pre_coeff);
-            p.pre_row_map = static_cast<const uint32_t*>(s.d_pre_row_map);
-            p.pre_row_scale = static_cast<const T*>(s.d_pre_row_scale);
-            p.pre_rows = int(s.pre_row_map.size());
+            p.pre_row_start = L.pre_row_start.as<uint32_t>();
+            p.pre_entries = L.pre_entries.as<uint32_t>();
+            p.pre_coeff = L.pre_coeff.as<T>();
+            p.pre_row_map = L.pre_row_map.as<uint32_t>();
+            p.pre_row_scale = L.pre_row_scale.as<T>();
+            p.pre_rows = int(L.pre_row_map.count);
             p.pre_width = s.pre_width;
-            p.pre_scratch = int(s.pre_scratch_off / sizeof(T));
+            p.pre_scratch = int(L.pre_scratch_off / sizeof(T));
             p.left_count = 0;
         }
-        p.left_scale = s.scaled ? static_cast<const T*>(s.d_coeff) : nullptr;
-        p.right_scale = s.scaled ? static_cast<const T*>(s.d_coeff_b) : nullptr;
-        p.out_scale = s.scaled ? static_cast<const T*>(s.d_coeff_c) : nullptr;
+        p.left_scale = s.scaled ? L.coeff.as<T>() : nullptr;
+        p.right_scale = s.scaled ? L.coeff_b.as<T>() : nullptr;
+        p.out_scale = s.scaled ? L.coeff_c.as<T>() : nullptr;
         // register-prefetch staging: full, contiguous, aligned operand rows; a chained step computes its left operand from a list
         // (then only the right row is prefetched)
         const bool prefetch = s.use_mfma6 ? (p.left_full && p.right_full && s.out_full && !s.beta)   // k_gp_mfma6's straight-line instantiation
-                              : s.use_mfma7 ? (s.kern[1] && p.right_full && !s.scaled && (s.chained || p.left_full))   // one component per lane and load: no alignment needed
-                                          : (s.use_mfma16 && s.kern[1] && p.right_contig && p.right_full && !s.scaled &&
+                              : s.use_mfma7 ? (L.kern[1] && p.right_full && !s.scaled && (s.chained || p.left_full))   // one component per lane and load: no alignment needed
+                                          : (s.use_mfma16 && L.kern[1] && p.right_contig && p.right_full && !s.scaled &&
                                              (s.chained ? true : (p.left_contig && p.left_full)));
-        const bool whole_rows = prefetch && s.kern[2] && s.out_full && !s.beta;   // k_gp_mfma16x4: straight-line result stores
-        hipLaunchKernelGGL(reinterpret_cast<KernD>(const_cast<void*>(s.kern[whole_rows ? 2 : prefetch ? 1 : 0])), dim3(unsigned(blocks)),
-                           dim3(unsigned(s.threads)), s.lds, g_stream, p);
+        const bool whole_rows = prefetch && L.kern[2] && s.out_full && !s.beta;   // k_gp_mfma16x4: straight-line result stores
+        hipLaunchKernelGGL(reinterpret_cast<KernD>(const_cast<void*>(L.kern[whole_rows ? 2 : prefetch ? 1 : 0])), dim3(unsigned(blocks)),
+                           dim3(unsigned(L.threads)), L.lds, g_stream, p);
         break;
     }
     default: return set_err(GAAST_ERR_INVALID_PROGRAM, "run_step: unknown step kind " + std::to_string(int(s.kind)) + " (" + s.name + ")");
@@ -889,11 +938,11 @@ int run_step(const Step& s, const Bound& res, const Bound& a, const Bound& b, co
     return GAAST_OK;
 }
 
-// hiprtc specialisation of a fused plan; on any failure the LDS interpreter kernel stays in charge
-// (contract: the variant with fused multiply-adds, kept beside the exact one -- Step::jit_function_fma)
-bool jit_compile(Step& s, const std::string& source, const char* entry, std::string* log, bool contract = false) {
+// hiprtc specialisation of a fused plan or a list chain: an empty kernel on any failure (then the generic kernel stays in charge)
+// (contract: the variant with fused multiply-adds, kept beside the exact one -- Launch::jit_fma)
+JitKernel jit_compile(const std::string& source, const char* entry, std::string* log, bool contract = false) {
     hiprtcProgram prog = nullptr;
-    if (hiprtcCreateProgram(&prog, source.c_str(), "gaast_jit.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) return false;
+    if (hiprtcCreateProgram(&prog, source.c_str(), "gaast_jit.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) return {};
     const char* opts[] = {"--offload-arch=gfx950", "-O3", contract ? "-ffp-contract=fast" : "-ffp-contract=off"};
     const hiprtcResult res = hiprtcCompileProgram(prog, 3, opts);
     if (res != HIPRTC_SUCCESS) {
@@ -902,39 +951,24 @@ bool jit_compile(Step& s, const std::string& source, const char* entry, std::str
         log->assign(n, 0);
         if (n) hiprtcGetProgramLog(prog, &(*log)[0]);
         hiprtcDestroyProgram(&prog);
-        return false;
+        return {};
     }
     size_t cs = 0;
-    std::vector<char> code;
+    JitKernel k;
     bool got = hiprtcGetCodeSize(prog, &cs) == HIPRTC_SUCCESS && cs > 0;
     if (got) {
-        code.resize(cs);
-        got = hiprtcGetCode(prog, code.data()) == HIPRTC_SUCCESS;
+        k.code.resize(cs);
+        got = hiprtcGetCode(prog, k.code.data()) == HIPRTC_SUCCESS;
     }
     hiprtcDestroyProgram(&prog);
     if (!got) {
         *log = "hiprtcGetCodeSize / hiprtcGetCode failed";
-        return false;
+        return {};
     }
-    hipModule_t mod = nullptr;
     hipFunction_t fn = nullptr;
-    // HIP's header does not say that hipModuleLoadData copies the image: it stays alive, in the step, for as long as the
-    // module does (release_plan_resources frees it after hipModuleUnload).  std::move keeps code.data() where it is.
-    if (hipModuleLoadData(&mod, code.data()) != hipSuccess) return false;
-    if (hipModuleGetFunction(&fn, mod, entry) != hipSuccess) {
-        (void)hipModuleUnload(mod);
-        return false;
-    }
-    if (contract) {
-        s.jit_code_fma = std::move(code);
-        s.jit_module_fma = mod;
-        s.jit_function_fma = fn;
-    } else {
-        s.jit_code = std::move(code);
-        s.jit_module = mod;
-        s.jit_function = fn;
-    }
-    return true;
+    if (hipModuleLoadData(&k.module, k.code.data()) != hipSuccess || hipModuleGetFunction(&fn, k.module, entry) != hipSuccess) return {};
+    k.fn = fn;
+    return k;
 }
 
 // When does the contracted variant of a specialised kernel pay?  An item costs ~2 vector instructions per comp-mul (4 cycles per
@@ -947,7 +981,8 @@ bool arithmetic_bound(uint64_t comp_muls, double bytes) {
 }
 
 template <typename T>
-int run_jit(const Step& s, const Plan& plan, const std::vector<Bound>& in_bound, const Bound& out, int64_t batch) {
+int run_jit(const Launch& L, const Plan& plan, const std::vector<Bound>& in_bound, const Bound& out, int64_t batch) {
+    const Step& s = L.s;
     // argument block: (ptr, stride) per staged input image, then out, out stride, batch
     std::vector<void*> args;
     std::vector<const void*> ptrs(s.fused_inputs.size());
@@ -965,7 +1000,7 @@ int run_jit(const Step& s, const Plan& plan, const std::vector<Bound>& in_bound,
     args.push_back(&optr);
     args.push_back(&ostride);
     args.push_back(&b);
-    void* dom = s.d_domain;
+    void* dom = L.domain;
     if (plan.has_explog) args.push_back(&dom);
     const unsigned threads = unsigned(s.jit_threads);
     const unsigned per_block = unsigned(s.jit_items > 0 ? s.jit_items : s.jit_threads);   // (the slab-in-LDS form: 64 items per 512 threads)
@@ -973,8 +1008,8 @@ int run_jit(const Step& s, const Plan& plan, const std::vector<Bound>& in_bound,
     if (s.jit_persistent > 0) blocks = unsigned(std::min<int64_t>(blocks, int64_t(g_num_cu) * std::min(s.jit_persistent, 4)));   // persistent workgroups
     // (the argument block -- args, ptrs, strides and the locals they point at -- only has to live until this call returns:
     //  hipModuleLaunchKernel copies the kernel arguments into the dispatch packet's kernarg segment at call time)
-    void* fn = s.jit_function;
-    if (s.jit_function_fma) {
+    hipFunction_t fn = L.jit.fn;
+    if (L.jit_fma) {
         // tolerance mode: the rows this launch really moves -- an operand shared by all items moves none, and only then does the
         // contracted variant run (a program over batched operands only keeps the reference's bits by default, as before)
         double bytes = double(plan.out_layout.row_len) * sizeof(T);
@@ -983,21 +1018,22 @@ int run_jit(const Step& s, const Plan& plan, const std::vector<Bound>& in_bound,
             if (strides[i] != 0) bytes += double(plan.input_layouts[size_t(s.fused_inputs[i].slot)].row_len) * sizeof(T);
             else shared = true;
         }
-        if (shared && arithmetic_bound(s.n_entries, bytes)) fn = s.jit_function_fma;
+        if (shared && arithmetic_bound(s.n_entries, bytes)) fn = L.jit_fma.fn;
     }
-    HIP_TRY(hipModuleLaunchKernel(static_cast<hipFunction_t>(fn), blocks, 1, 1, threads, 1, 1, 0, g_stream, args.data(), nullptr));
+    HIP_TRY(hipModuleLaunchKernel(fn, blocks, 1, 1, threads, 1, 1, 0, g_stream, args.data(), nullptr));
     return GAAST_OK;
 }
 
 template <typename T>
-int run_fused(const Step& s, const Plan& plan, const std::vector<Bound>& in_bound, const Bound& out, int64_t batch) {
-    if (s.jit_function) return run_jit<T>(s, plan, in_bound, out, batch);
+int run_fused(const Launch& L, const Plan& plan, const std::vector<Bound>& in_bound, const Bound& out, int64_t batch) {
+    if (L.jit) return run_jit<T>(L, plan, in_bound, out, batch);
+    const Step& s = L.s;
     FusedArgs<T> p;
     std::memset(&p, 0, sizeof(p));
-    p.prog = static_cast<const uint32_t*>(s.d_a);
-    p.phase_tab = static_cast<const uint32_t*>(s.d_b);
-    p.n_phases = int(s.u32_b.size() / (2 * FUSED_GROUPS));
-    for (size_t i = 0; i < s.coeff_host.size() && i < 6; ++i) p.coeff[i] = T(s.coeff_host[i]);
+    p.prog = L.u32_a.as<uint32_t>();
+    p.phase_tab = L.u32_b.as<uint32_t>();
+    p.n_phases = int(L.u32_b.count / (2 * FUSED_GROUPS));
+    for (size_t i = 0; i < L.fused_coeff.size() && i < 6; ++i) p.coeff[i] = T(L.fused_coeff[i]);
     p.slab = s.fused_slab;
     p.zero_slot = s.fused_zero_slot;
     p.n_in = int(s.fused_inputs.size());
@@ -1023,7 +1059,8 @@ int run_fused(const Step& s, const Plan& plan, const std::vector<Bound>& in_boun
 
 // a run of element-wise arms (and the scaling product after it) in one pass: plan.cpp: fuse_elementwise_runs
 template <typename T, typename Resolve>
-int run_elementwise(const Step& s, const Bound& res, Resolve&& resolve, int64_t batch) {
+int run_elementwise(const Launch& L, const Bound& res, Resolve&& resolve, int64_t batch) {
+    const Step& s = L.s;
     ElementwiseArgs<T> q;
     std::memset(&q, 0, sizeof(q));
     Layout unused;
@@ -1032,18 +1069,18 @@ int run_elementwise(const Step& s, const Bound& res, Resolve&& resolve, int64_t 
         q.src[i] = static_cast<const T*>(b.ptr);
         q.src_stride[i] = b.stride;
     }
-    q.ops = static_cast<const uint32_t*>(s.d_a);
-    q.comp_off = static_cast<const uint32_t*>(s.d_b);
+    q.ops = L.u32_a.as<uint32_t>();
+    q.comp_off = L.u32_b.as<uint32_t>();
     q.n_ops = s.ew_ops;
-    q.n_comp = int(s.u32_b.size());
+    q.n_comp = int(L.u32_b.count);
     q.load_first = s.ew_load_first;
     q.batch = batch;
     if (s.ew_scale) {
         const Bound sc = resolve(s.b, &unused);
         q.out = static_cast<T*>(res.ptr);
         q.out_stride = res.stride;
-        q.out_off = static_cast<const uint32_t*>(s.d_c);
-        q.coeff = static_cast<const T*>(s.d_coeff);
+        q.out_off = L.u32_c.as<uint32_t>();
+        q.coeff = L.coeff.as<T>();
         q.scalar = static_cast<const T*>(sc.ptr);
         q.scalar_stride = sc.stride;
         q.scalar_off = s.ew_scalar_off;
@@ -1061,6 +1098,210 @@ int run_elementwise(const Step& s, const Bound& res, Resolve&& resolve, int64_t 
     if (q.n_ops <= 4) hipLaunchKernelGGL((k_elementwise<T, 4>), dim3(gx, gy), dim3(256), 0, g_stream, q);
     else hipLaunchKernelGGL((k_elementwise<T, ELEMENTWISE_MAX_OPS>), dim3(gx, gy), dim3(256), 0, g_stream, q);
     HIP_TRY(hipGetLastError());
+    return GAAST_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Program creation (program_create_impl), phase by phase
+// ------------------------------------------------------------------------------------------
+// the plan of `desc` and one launch per step (plan.steps is left empty); a rebuild discards the launches made so far
+int make_launches(const gaast_program_desc& desc, bool small_reg_slab, gaast_hip_program_s& prog) {
+    prog.launches.clear();
+    prog.plan = Plan();
+    try {
+        build_plan(desc, prog.plan, small_reg_slab);
+    } catch (const std::exception& ex) {
+        return set_err(GAAST_ERR_INVALID_PROGRAM, ex.what());
+    }
+    // valid in the reference, beyond this back end: refused whole, here, never half-evaluated
+    if (!prog.plan.unsupported.empty()) return set_err(GAAST_ERR_UNIMPLEMENTED, prog.plan.unsupported);
+    prog.launches.resize(prog.plan.steps.size());
+    for (size_t i = 0; i < prog.launches.size(); ++i) prog.launches[i].s = std::move(prog.plan.steps[i]);
+    prog.plan.steps.clear();
+    return GAAST_OK;
+}
+
+// hiprtc specialisation of fused plans, before anything is uploaded.  True: the plan has to be rebuilt with *rebuild_flags /
+// *small_reg_slab -- it can only run as the specialised kernel and the compiler is not available, or a register trial failed.
+bool compile_fused(gaast_hip_program_s& prog, uint32_t flags, uint32_t* rebuild_flags, bool* small_reg_slab) {
+    bool rebuild = false;
+    for (Launch& L : prog.launches) {
+        Step& s = L.s;
+        if (s.kind != Step::FUSED || s.jit_source.empty()) continue;
+        if (flags & GAAST_FLAG_DEBUG_KEEP_JIT_SOURCE) prog.plan.jit_source_kept += s.jit_source;
+        std::string log;
+        if (!(flags & GAAST_FLAG_DEBUG_JIT_FAILS)) L.jit = jit_compile(s.jit_source, "gaast_jit", &log);
+        if (L.jit)
+            s.name = "ast_jit" + s.name.substr(s.name.find('[')) + (s.jit_items ? " slab in LDS" : "");
+        else if (!log.empty())
+            g_err = "hiprtc: " + log;  // informational: the interpreter kernel (or an unfused plan) runs instead
+        bool trial_failed = false;
+        if (L.jit && s.jit_reg_trial) {
+            // a slab beyond 160 / 200 elements in registers, on trial (plan.cpp: try_fuse): the compiled kernel has to leave two
+            // waves per SIMD (eight single-wave workgroups per CU), else the plan is rebuilt with the slabs in LDS
+            int per_cu = 0;
+            trial_failed = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, L.jit.fn, s.jit_threads, 0) != hipSuccess ||
+                           per_cu * (s.jit_threads / 64) < 8;
+            if (trial_failed) rebuild = *small_reg_slab = true;
+        }
+        // tolerance mode, one item per thread, and arithmetic-bound at least when every operand is shared by all items: the
+        // contracted variant too (run_jit picks per launch, by the operands bound)
+        if (L.jit && !trial_failed && !(flags & GAAST_FLAG_EXACT_ORDER) && !s.jit_items && !prog.plan.has_explog &&
+            arithmetic_bound(s.n_entries, double(prog.plan.out_layout.row_len) * dtype_size(prog.plan.dtype))) {
+            std::string log2;
+            L.jit_fma = jit_compile(s.jit_source, "gaast_jit", &log2, true);
+            if (L.jit_fma) s.name += " | fused multiply-adds under shared operands";
+        }
+        std::string().swap(s.jit_source);
+        if (!L.jit && s.fused_jit_only) {
+            rebuild = true;
+            *rebuild_flags |= GAAST_FLAG_NO_JIT;
+        }
+    }
+    return rebuild;
+}
+
+// list chains specialised per program; on any failure the generic k_product_ell_chain stays in charge
+void compile_chains(gaast_hip_program_s& prog, uint32_t flags) {
+    std::vector<Launch>& ls = prog.launches;
+    std::vector<char> drop(ls.size(), 0);
+    for (size_t i = 0; i < ls.size(); ++i) {
+        Step& s = ls[i].s;
+        if (!s.chain_jit) continue;
+        if (flags & GAAST_FLAG_DEBUG_KEEP_JIT_SOURCE) prog.plan.jit_source_kept += s.chain_jit_source;
+        std::string log;
+        ls[i].jit = jit_compile(s.chain_jit_source, "gaast_chain", &log);
+        if (!ls[i].jit && !log.empty()) g_err = "hiprtc: " + log;
+        std::string().swap(s.chain_jit_source);
+        if (!ls[i].jit) {
+            s.list_jit = s.fold_prev = 0;
+        } else if (s.fold_prev && i > 0) {   // the copy_grades_from step before a single list is evaluated by the specialised kernel
+            drop[i - 1] = 1;
+            s.name += " <- " + ls[i - 1].s.name;
+        }
+    }
+    std::vector<Launch> kept;
+    for (size_t i = 0; i < ls.size(); ++i)
+        if (!drop[i]) kept.push_back(std::move(ls[i]));
+    ls = std::move(kept);
+}
+
+// Kernel choice, LDS budget, persistent grid, device tables and label of one launch: fixed here, and a program no kernel can
+// run is refused whole (an eval then either runs every launch or none)
+int prepare_launch(Launch& L, const gaast_hip_program_s& prog) {
+    const Plan& plan = prog.plan;
+    Step& s = L.s;
+    auto layout_of = [&](BufRef r) -> Layout {
+        if (r.idx < 0) return Layout();
+        switch (r.kind) {
+        case BufKind::NODE: return plan.node_buffers[size_t(r.idx)];
+        case BufKind::INPUT: return plan.input_layouts[size_t(r.idx)];
+        default: return plan.out_layout;
+        }
+    };
+    L.n = (s.kind == Step::PRODUCT_DENSE && s.dense_n) ? s.dense_n : plan.n;   // parity-pure products run in Cl(n - 1)
+    L.domain = prog.domain.ptr;
+    std::string kernel;
+    const Layout la = layout_of(s.a), lb = layout_of(s.b);
+    if (int st = plan.dtype == GAAST_F32 ? prepare_step<float>(L, la, lb, kernel) : prepare_step<double>(L, la, lb, kernel)) return st;
+    if (s.chained) {
+        // the list's operand rows of every item a workgroup stages at once, after the kernel's own images
+        L.pre_scratch_off = (L.lds + 15) / 16 * 16;
+        const size_t items = size_t(L.items_per_block > 0 ? L.items_per_block : 1);
+        // + the zero pair; the one-item matrix kernels keep the list's right row twice (+x, -x: a term's sign is an address)
+        L.lds = L.pre_scratch_off + (items * size_t(s.pre_left_len + s.pre_right_len + 1) + (items == 1 ? size_t(s.pre_right_len) : 0)) * dtype_size(plan.dtype);
+        // The plan builder sizes a chain's LDS with its own estimate of the kernel's images; this is the real figure, checked
+        // against the device.  On a mismatch gaast_hip_program_create rebuilds the program without chains.
+        if (L.lds > g_max_lds) return set_err(kChainTooBig, "chained product does not fit in LDS (" + s.name + ")");
+        for (int v = 0; v < 3; ++v)
+            if (L.kern[v])
+                if (int st = allow_lds(L.kern[v], L.lds)) return st;
+        if (L.blocks_per_cu > 0)
+            if (int st = resident_blocks(L.kern[0], L.threads, L.lds, &L.blocks_per_cu)) return st;
+        if (int st = L.pre_row_start.upload(std::move(s.pre_row_start))) return st;
+        if (int st = L.pre_entries.upload(std::move(s.pre_entries))) return st;
+        if (int st = L.pre_row_map.upload(std::move(s.pre_row_map))) return st;
+        if (int st = L.pre_coeff.upload(std::move(s.pre_coeff), plan.dtype)) return st;
+        if (int st = L.pre_row_scale.upload(std::move(s.pre_row_scale), plan.dtype)) return st;
+    }
+    if (s.kind == Step::PRODUCT_CSR && (s.list_chain || s.list_jit)) {
+        if (L.jit) {
+            if (int st = L.cj_ent1.upload(std::move(s.cj_ent1))) return st;
+            if (int st = L.cj_pos1.upload(std::move(s.cj_pos1))) return st;
+            if (int st = L.cj_ent2.upload(std::move(s.cj_ent2))) return st;
+            if (int st = L.cj_out2.upload(std::move(s.cj_out2))) return st;
+        } else {
+            if (int st = L.pre_entries.upload(std::move(s.pre_entries))) return st;
+            if (int st = L.pre_row_map.upload(std::move(s.pre_row_map))) return st;
+        }
+    }
+    if (int st = L.u32_a.upload(std::move(s.u32_a))) return st;
+    if (int st = L.u32_b.upload(std::move(s.u32_b))) return st;
+    if (int st = L.u32_c.upload(std::move(s.u32_c))) return st;
+    if (int st = L.i32_a.upload(std::move(s.i32_a))) return st;
+    if (s.kind == Step::FUSED) L.fused_coeff = std::move(s.coeff);
+    else if (int st = L.coeff.upload(std::move(s.coeff), plan.dtype)) return st;
+    if (int st = L.coeff_b.upload(std::move(s.coeff_b), plan.dtype)) return st;
+    if (int st = L.coeff_c.upload(std::move(s.coeff_c), plan.dtype)) return st;
+    L.label = kernel.empty() ? s.name : s.name + " :: " + kernel;
+    return GAAST_OK;
+}
+
+// input slots some launch reads (the others may stay unbound)
+void mark_used_slots(gaast_hip_program_s& prog) {
+    Plan& plan = prog.plan;
+    plan.slot_used.assign(plan.inputs.size(), 0);
+    auto use = [&](BufRef r) {
+        if (r.idx >= 0 && r.kind == BufKind::INPUT) plan.slot_used[size_t(r.idx)] = 1;
+    };
+    for (const Launch& L : prog.launches) {
+        const Step& s = L.s;
+        if (s.chained) {
+            use(s.pre_a);
+            use(s.pre_b);
+        }
+        if (s.kind == Step::ELEMENTWISE) {
+            for (const BufRef& b : s.ew_src) use(b);
+        } else if (s.kind == Step::REDUCE_SCALE) {
+            use(s.pre_a);
+        } else if (s.list_chain || s.list_jit) {
+            use(s.pre_a);
+            if (s.list_chain) use(s.pre_b);
+        }
+        use(s.a);
+        use(s.b);
+        for (const Step::FusedInput& fi : s.fused_inputs) plan.slot_used[size_t(fi.slot)] = 1;
+    }
+}
+
+int upload_const_rows(gaast_hip_program_s& prog) {
+    const Plan& plan = prog.plan;
+    prog.const_rows.resize(plan.inputs.size());
+    for (size_t i = 0; i < plan.inputs.size(); ++i)
+        if (plan.inputs[i].is_const)
+            if (int st = prog.const_rows[i].upload(plan.const_rows[i], plan.dtype)) return st;
+    return GAAST_OK;
+}
+
+int program_create_impl(const gaast_program_desc* desc, gaast_hip_program_t* out) {
+    auto prog = std::make_unique<gaast_hip_program_s>();  // its destructor releases whatever a failure leaves behind
+    if (int st = make_launches(*desc, false, *prog)) return st;
+    // a plan that can only run as the specialised kernel is rebuilt without run-time compilation if the compiler is not available
+    uint32_t rebuild_flags = 0;
+    bool small_reg_slab = false;
+    for (int attempt = 0; attempt < 3 && compile_fused(*prog, desc->flags, &rebuild_flags, &small_reg_slab); ++attempt) {
+        gaast_program_desc d2 = *desc;
+        d2.flags |= rebuild_flags;
+        if (int st = make_launches(d2, small_reg_slab, *prog)) return st;
+    }
+    compile_chains(*prog, desc->flags);
+    if (prog->plan.has_explog)
+        if (int st = prog->domain.upload(std::vector<unsigned long long>(1, 0))) return st;
+    for (Launch& L : prog->launches)
+        if (int st = prepare_launch(L, *prog)) return st;
+    mark_used_slots(*prog);
+    if (int st = upload_const_rows(*prog)) return st;
+    *out = prog.release();
     return GAAST_OK;
 }
 
@@ -1135,22 +1376,18 @@ int gaast_hip_synchronize(void) {
     return GAAST_OK;
 }
 
-static int program_create_impl(const gaast_program_desc* desc, gaast_hip_program_t* out);
-
 int gaast_hip_program_create(const gaast_program_desc* desc, gaast_hip_program_t* out) {
     if (!desc || !out) return set_err(GAAST_ERR_INVALID_ARGUMENT, "null argument");
     if (int st = ensure_init()) return st;
-    g_chain_too_big = false;
-    const int st = program_create_impl(desc, out);
-    // The plan builder sizes a chain's LDS with its own estimate of the kernel's images; prepare_step checks the real figure
-    // against the device.  On a mismatch the unchained plan of the same program still runs: rebuild without chains
-    // (as the hiprtc-failure fallback does) instead of refusing the program.
-    if (st == GAAST_ERR_UNIMPLEMENTED && g_chain_too_big && !(desc->flags & GAAST_FLAG_DEBUG_NO_CHAIN)) {
+    int st = program_create_impl(desc, out);
+    // a chain beyond the device's LDS: the unchained plan of the same program still runs -- rebuild without chains (as the
+    // hiprtc-failure fallback does) instead of refusing the program
+    if (st == kChainTooBig && !(desc->flags & GAAST_FLAG_DEBUG_NO_CHAIN)) {
         gaast_program_desc d2 = *desc;
         d2.flags |= GAAST_FLAG_DEBUG_NO_CHAIN;
-        return program_create_impl(&d2, out);
+        st = program_create_impl(&d2, out);
     }
-    return st;
+    return st == kChainTooBig ? GAAST_ERR_UNIMPLEMENTED : st;
 }
 
 // ---- linear maps of the vector space on graded rows (outermorphisms) --------------------------------------------------
@@ -1223,7 +1460,7 @@ int gaast_hip_program_create_in_basis(const gaast_program_desc* desc, const doub
     for (int i = 0; i < n; ++i)
         for (int j = 0; j < n; ++j) qt[size_t(i * n + j)] = basis[j * n + i];
     auto to_f = std::make_unique<LinmapDev>(), to_e = std::make_unique<LinmapDev>();
-    std::vector<std::vector<double>> c_in;   // C_k(Q^T) in double: the constant inputs move on the host
+    std::vector<double> c_in;   // C_k(Q^T) in double: the constant inputs move on the host
     if (int st = linmap_build(n, qt.data(), desc->dtype, *to_f, &c_in)) return st;
     if (int st = linmap_build(n, basis, desc->dtype, *to_e)) return st;
     // constant rows into f; a row of another dimension can only be a scalar
@@ -1244,7 +1481,7 @@ int gaast_hip_program_create_in_basis(const gaast_program_desc* desc, const doub
             const int64_t d = l.grade_len(k);
             for (int64_t r = 0; r < d; ++r) {
                 double acc = 0.0;
-                for (int64_t c = 0; c < d; ++c) acc += c_in[size_t(k)][size_t(r * d + c)] * in.const_row[off + c];
+                for (int64_t c = 0; c < d; ++c) acc += c_in[size_t(to_f->moff[size_t(k)] + r * d + c)] * in.const_row[off + c];
                 rows[i][size_t(off + r)] = acc;
             }
         }
@@ -1257,21 +1494,18 @@ int gaast_hip_program_create_in_basis(const gaast_program_desc* desc, const doub
     Plan& plan = prog->plan;
     if (plan.out_layout.dim != n && (plan.out_layout.mask & ~1ULL))
         return set_err(GAAST_ERR_UNIMPLEMENTED, "program_create_in_basis: the result has grades above 0 in another dimension");
-    // LINMAP steps: every batched input a launch reads, with grades above 0, into a node buffer of its own; the root back into out
-    std::vector<Step> pre;
-    std::vector<std::string> pre_names;
+    // LINMAP launches: every batched input a launch reads, with grades above 0, into a node buffer of its own; the root back into out
+    std::vector<Launch> launches;
     plan.basis_slot_buf.assign(plan.inputs.size(), -1);
-    auto make_step = [&](const LinmapDev* m, BufRef res, BufRef a, const std::string& name) -> int {
-        Step s;
-        s.kind = Step::LINMAP;
-        s.linmap = m;
-        s.res = res;
-        s.a = a;
-        s.name = name;
-        const Layout none;
-        if (int st = plan.dtype == GAAST_F32 ? prepare_step<float>(s, none, none, n) : prepare_step<double>(s, none, none, n)) return st;
-        pre_names.push_back(s.name + " :: " + s.hip_kernel);
-        pre.push_back(std::move(s));
+    auto add_linmap = [&](const LinmapDev* m, BufRef res, BufRef a, const std::string& name) -> int {
+        Launch L;
+        L.s.kind = Step::LINMAP;
+        L.s.res = res;
+        L.s.a = a;
+        L.s.name = name;
+        L.linmap = m;
+        if (int st = prepare_launch(L, *prog)) return st;
+        launches.push_back(std::move(L));
         return GAAST_OK;
     };
     for (size_t i = 0; i < plan.inputs.size(); ++i) {
@@ -1280,251 +1514,23 @@ int gaast_hip_program_create_in_basis(const gaast_program_desc* desc, const doub
         plan.node_buffers.push_back(plan.input_layouts[i]);
         if (!plan.node_dead.empty()) plan.node_dead.push_back(0);
         plan.basis_slot_buf[i] = buf;
-        if (int st = make_step(to_f.get(), BufRef{BufKind::NODE, buf}, BufRef{BufKind::INPUT, int(i)},
-                               "linmap[input " + std::to_string(i) + " -> orthogonal basis]"))
+        if (int st = add_linmap(to_f.get(), BufRef{BufKind::NODE, buf}, BufRef{BufKind::INPUT, int(i)},
+                                "linmap[input " + std::to_string(i) + " -> orthogonal basis]"))
             return st;
     }
-    const size_t n_pre = pre.size();
+    for (Launch& L : prog->launches) launches.push_back(std::move(L));
     if (plan.out_layout.mask & ~1ULL) {
         plan.basis_out_buf = int(plan.node_buffers.size());
         plan.node_buffers.push_back(plan.out_layout);
         if (!plan.node_dead.empty()) plan.node_dead.push_back(0);
-        if (int st = make_step(to_e.get(), BufRef{BufKind::OUT, -1}, BufRef{BufKind::NODE, plan.basis_out_buf}, "linmap[result -> caller's basis]"))
+        if (int st = add_linmap(to_e.get(), BufRef{BufKind::OUT, -1}, BufRef{BufKind::NODE, plan.basis_out_buf}, "linmap[result -> caller's basis]"))
             return st;
     }
-    std::vector<Step> steps;
-    std::vector<std::string> names;
-    for (size_t i = 0; i < n_pre; ++i) {
-        steps.push_back(std::move(pre[i]));
-        names.push_back(pre_names[i]);
-    }
-    for (size_t i = 0; i < plan.steps.size(); ++i) {
-        steps.push_back(std::move(plan.steps[i]));
-        names.push_back(prog->launch_names[i]);
-    }
-    for (size_t i = n_pre; i < pre.size(); ++i) {
-        steps.push_back(std::move(pre[i]));
-        names.push_back(pre_names[i]);
-    }
-    plan.steps = std::move(steps);
-    prog->launch_names = std::move(names);
+    prog->launches = std::move(launches);
     prog->basis_in = std::move(to_f);
     prog->basis_out = std::move(to_e);
     prog->scratch_batch = 0;   // the node buffers are re-allocated at the next eval
     *out = owner.release();
-    return GAAST_OK;
-}
-
-static int program_create_impl(const gaast_program_desc* desc, gaast_hip_program_t* out) {
-    auto prog = std::make_unique<gaast_hip_program_s>();  // its destructor releases whatever a failure leaves behind
-    try {
-        build_plan(*desc, prog->plan);
-    } catch (const std::exception& ex) {
-        return set_err(GAAST_ERR_INVALID_PROGRAM, ex.what());
-    }
-    // valid in the reference, beyond this back end: refused whole, here, never half-evaluated
-    if (!prog->plan.unsupported.empty()) return set_err(GAAST_ERR_UNIMPLEMENTED, prog->plan.unsupported);
-    // hiprtc specialisation of fused plans, before anything is uploaded: a plan that can only run as the
-    // specialised kernel is rebuilt without run-time compilation if the compiler is not available
-    uint32_t rebuild_flags = 0;
-    for (int attempt = 0; attempt < 3; ++attempt) {
-        bool rebuild = false;
-        for (Step& s : prog->plan.steps) {
-            if (s.kind != Step::FUSED || s.jit_source.empty()) continue;
-            if (desc->flags & GAAST_FLAG_DEBUG_KEEP_JIT_SOURCE) prog->plan.jit_source_kept += s.jit_source;
-            std::string log;
-            const bool ok = (desc->flags & GAAST_FLAG_DEBUG_JIT_FAILS) ? false : jit_compile(s, s.jit_source, "gaast_jit", &log);
-            if (ok)
-                s.name = "ast_jit" + s.name.substr(s.name.find('[')) + (s.jit_items ? " slab in LDS" : "");
-            else if (!log.empty())
-                g_err = "hiprtc: " + log;  // informational: the interpreter kernel (or an unfused plan) runs instead
-            bool trial_failed = false;
-            if (ok && s.jit_reg_trial) {
-                // a slab beyond 160 / 200 elements in registers, on trial (plan.cpp: try_fuse): the compiled kernel has to leave two
-                // waves per SIMD (eight single-wave workgroups per CU), else the plan is rebuilt with the slabs in LDS
-                int per_cu = 0;
-                trial_failed = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, static_cast<hipFunction_t>(s.jit_function), s.jit_threads, 0) != hipSuccess ||
-                               per_cu * (s.jit_threads / 64) < 8;
-                if (trial_failed) {
-                    rebuild = true;
-                    rebuild_flags |= GAAST_FLAG_INTERNAL_SMALL_REG_SLAB;
-                }
-            }
-            // tolerance mode, one item per thread, and arithmetic-bound at least when every operand is shared by all items: the
-            // contracted variant too (run_jit picks per launch, by the operands bound)
-            if (ok && !trial_failed && !(desc->flags & GAAST_FLAG_EXACT_ORDER) && !s.jit_items && !prog->plan.has_explog &&
-                arithmetic_bound(s.n_entries, double(prog->plan.out_layout.row_len) * dtype_size(prog->plan.dtype))) {
-                std::string log2;
-                if (jit_compile(s, s.jit_source, "gaast_jit", &log2, true)) s.name += " | fused multiply-adds under shared operands";
-            }
-            std::string().swap(s.jit_source);
-            if (!ok && s.fused_jit_only) {
-                rebuild = true;
-                rebuild_flags |= GAAST_FLAG_NO_JIT;
-            }
-        }
-        if (!rebuild) break;
-        gaast_program_desc d2 = *desc;
-        d2.flags |= rebuild_flags;
-        release_plan_resources(prog->plan);  // modules already loaded for other fused steps
-        prog->plan = Plan();
-        try {
-            build_plan(d2, prog->plan);
-        } catch (const std::exception& ex) {
-            return set_err(GAAST_ERR_INVALID_PROGRAM, ex.what());
-        }
-        if (!prog->plan.unsupported.empty()) return set_err(GAAST_ERR_UNIMPLEMENTED, prog->plan.unsupported);
-    }
-    // list chains specialised per program; on any failure the generic k_product_ell_chain stays in charge
-    {
-        std::vector<char> drop(prog->plan.steps.size(), 0);
-        for (size_t i = 0; i < prog->plan.steps.size(); ++i) {
-            Step& s = prog->plan.steps[i];
-            if (s.chain_jit != 1) continue;
-            if (desc->flags & GAAST_FLAG_DEBUG_KEEP_JIT_SOURCE) prog->plan.jit_source_kept += s.chain_jit_source;
-            std::string log;
-            const bool ok = jit_compile(s, s.chain_jit_source, "gaast_chain", &log);
-            if (!ok && !log.empty()) g_err = "hiprtc: " + log;
-            s.chain_jit = ok ? 2 : 0;
-            std::string().swap(s.chain_jit_source);
-            if (ok && s.fold_prev && i > 0) {   // the copy_grades_from step before a single list is evaluated by the specialised kernel
-                drop[i - 1] = 1;
-                s.name += " <- " + prog->plan.steps[i - 1].name;
-            }
-            if (!ok) s.list_jit = s.fold_prev = 0;
-        }
-        std::vector<Step> kept;
-        for (size_t i = 0; i < prog->plan.steps.size(); ++i)
-            if (!drop[i]) kept.push_back(std::move(prog->plan.steps[i]));
-        prog->plan.steps = std::move(kept);
-    }
-    Plan& plan = prog->plan;
-    auto layout_of = [&](BufRef r) -> Layout {
-        if (r.idx < 0) return Layout();
-        switch (r.kind) {
-        case BufKind::NODE: return plan.node_buffers[size_t(r.idx)];
-        case BufKind::INPUT: return plan.input_layouts[size_t(r.idx)];
-        default: return plan.out_layout;
-        }
-    };
-    plan.slot_used.assign(plan.inputs.size(), 0);
-    if (plan.has_explog) {
-        HIP_TRY(hipMalloc(&prog->d_domain, sizeof(unsigned long long)));
-        HIP_TRY(hipMemset(prog->d_domain, 0, sizeof(unsigned long long)));
-    }
-    for (Step& s : plan.steps) {
-        s.d_domain = prog->d_domain;
-        // kernel choice, LDS budget, persistent grid: fixed here, and a program no kernel can run is refused whole
-        const Layout la = layout_of(s.a), lb = layout_of(s.b);
-        const int step_n = (s.kind == Step::PRODUCT_DENSE && s.dense_n) ? s.dense_n : plan.n;   // parity-pure products run in Cl(n - 1)
-        if (int st = plan.dtype == GAAST_F32 ? prepare_step<float>(s, la, lb, step_n) : prepare_step<double>(s, la, lb, step_n))
-            return st;
-        if (s.chained) {
-            // the list's operand rows of every item a workgroup stages at once, after the kernel's own images
-            s.pre_scratch_off = (s.lds + 15) / 16 * 16;
-            const size_t items = size_t(s.items_per_block > 0 ? s.items_per_block : 1);
-            // + the zero pair; the one-item matrix kernels keep the list's right row twice (+x, -x: a term's sign is an address)
-            s.lds = s.pre_scratch_off + (items * size_t(s.pre_left_len + s.pre_right_len + 1) + (items == 1 ? size_t(s.pre_right_len) : 0)) * dtype_size(plan.dtype);
-            if (s.lds > g_max_lds) {
-                g_chain_too_big = true;
-                return set_err(GAAST_ERR_UNIMPLEMENTED, "chained product does not fit in LDS (" + s.name + ")");
-            }
-            for (int v = 0; v < 3; ++v)
-                if (s.kern[v])
-                    if (int st = allow_lds(s.kern[v], s.lds)) return st;
-            if (s.blocks_per_cu > 0)
-                if (int st = resident_blocks(s.kern[0], s.threads, s.lds, &s.blocks_per_cu)) return st;
-            if (s.pre_a.kind == BufKind::INPUT) plan.slot_used[size_t(s.pre_a.idx)] = 1;
-            if (s.pre_b.kind == BufKind::INPUT) plan.slot_used[size_t(s.pre_b.idx)] = 1;
-            if (int st = upload_vec(s.pre_row_start, &s.d_pre_row_start)) return st;
-            if (int st = upload_vec(s.pre_entries, &s.d_pre_entries)) return st;
-            if (int st = upload_vec(s.pre_row_map, &s.d_pre_row_map)) return st;
-            auto upload_t = [&](const std::vector<double>& v, void** dptr) -> int {
-                if (plan.dtype == GAAST_F32) {
-                    std::vector<float> cf(v.begin(), v.end());
-                    return upload_vec(cf, dptr);
-                }
-                return upload_vec(v, dptr);
-            };
-            if (int st = upload_t(s.pre_coeff, &s.d_pre_coeff)) return st;
-            if (int st = upload_t(s.pre_row_scale, &s.d_pre_row_scale)) return st;
-        }
-        if (s.kind == Step::ELEMENTWISE) {
-            for (const BufRef& b : s.ew_src)
-                if (b.kind == BufKind::INPUT) plan.slot_used[size_t(b.idx)] = 1;
-        } else if (s.kind == Step::REDUCE_SCALE) {
-            if (s.pre_a.idx >= 0 && s.pre_a.kind == BufKind::INPUT) plan.slot_used[size_t(s.pre_a.idx)] = 1;
-        } else if (s.list_chain || s.list_jit) {
-            if (s.pre_a.idx >= 0 && s.pre_a.kind == BufKind::INPUT) plan.slot_used[size_t(s.pre_a.idx)] = 1;
-            if (s.list_chain && s.pre_b.kind == BufKind::INPUT) plan.slot_used[size_t(s.pre_b.idx)] = 1;
-            if (s.chain_jit == 2) {
-                if (int st = upload_vec(s.cj_ent1, &s.d_cj_ent1)) return st;
-                if (int st = upload_vec(s.cj_pos1, &s.d_cj_pos1)) return st;
-                if (int st = upload_vec(s.cj_ent2, &s.d_cj_ent2)) return st;
-                if (int st = upload_vec(s.cj_out2, &s.d_cj_out2)) return st;
-            } else {
-                if (int st = upload_vec(s.pre_entries, &s.d_pre_entries)) return st;
-                if (int st = upload_vec(s.pre_row_map, &s.d_pre_row_map)) return st;
-            }
-            std::vector<uint32_t>().swap(s.cj_ent1);
-            std::vector<uint32_t>().swap(s.cj_ent2);
-        }
-        if (s.a.idx >= 0 && s.a.kind == BufKind::INPUT) plan.slot_used[size_t(s.a.idx)] = 1;
-        if (s.b.idx >= 0 && s.b.kind == BufKind::INPUT) plan.slot_used[size_t(s.b.idx)] = 1;
-        for (const Step::FusedInput& fi : s.fused_inputs) plan.slot_used[size_t(fi.slot)] = 1;
-        if (int st = upload_vec(s.u32_a, &s.d_a)) return st;
-        if (int st = upload_vec(s.u32_b, &s.d_b)) return st;
-        if (int st = upload_vec(s.u32_c, &s.d_c)) return st;
-        if (int st = upload_vec(s.i32_a, &s.d_i32)) return st;
-        if (!s.coeff.empty() && s.kind != Step::FUSED) {
-            if (plan.dtype == GAAST_F32) {
-                std::vector<float> cf(s.coeff.begin(), s.coeff.end());
-                if (int st = upload_vec(cf, &s.d_coeff)) return st;
-            } else {
-                if (int st = upload_vec(s.coeff, &s.d_coeff)) return st;
-            }
-        }
-        if (!s.coeff_b.empty()) {
-            if (plan.dtype == GAAST_F32) {
-                std::vector<float> cf(s.coeff_b.begin(), s.coeff_b.end());
-                if (int st = upload_vec(cf, &s.d_coeff_b)) return st;
-            } else {
-                if (int st = upload_vec(s.coeff_b, &s.d_coeff_b)) return st;
-            }
-        }
-        if (!s.coeff_c.empty()) {
-            if (plan.dtype == GAAST_F32) {
-                std::vector<float> cf(s.coeff_c.begin(), s.coeff_c.end());
-                if (int st = upload_vec(cf, &s.d_coeff_c)) return st;
-            } else {
-                if (int st = upload_vec(s.coeff_c, &s.d_coeff_c)) return st;
-            }
-        }
-        // the host images of the big tables are no longer needed
-        s.coeff_host = s.kind == Step::FUSED ? s.coeff : std::vector<double>();
-        std::vector<uint32_t>().swap(s.u32_c);
-        std::vector<double>().swap(s.coeff);
-        // launch label: what the step is, then WHICH HIP kernel runs it (the name rocprofv3 reports)
-        prog->launch_names.push_back(s.hip_kernel.empty() ? s.name : s.name + " :: " + s.hip_kernel);
-    }
-    prog->const_mvs.assign(plan.inputs.size(), nullptr);
-    for (size_t i = 0; i < plan.inputs.size(); ++i) {
-        if (!plan.inputs[i].is_const) continue;
-        const Layout& l = plan.input_layouts[i];
-        gaast_hip_mv_t m = nullptr;
-        if (int st = mv_alloc_impl(l.dim, l.mask, 1, plan.dtype, &m)) return st;
-        prog->const_mvs[i] = m;
-        if (l.row_len) {
-            if (plan.dtype == GAAST_F32) {
-                std::vector<float> r(plan.const_rows[i].begin(), plan.const_rows[i].end());
-                HIP_TRY(hipMemcpy(m->ptr, r.data(), r.size() * 4, hipMemcpyHostToDevice));
-            } else {
-                HIP_TRY(hipMemcpy(m->ptr, plan.const_rows[i].data(), plan.const_rows[i].size() * 8,
-                                  hipMemcpyHostToDevice));
-            }
-        }
-    }
-    *out = prog.release();
     return GAAST_OK;
 }
 
@@ -1543,11 +1549,11 @@ int gaast_hip_program_domain_errors(gaast_hip_program_t prog, int64_t* count) {
     if (!prog || !count) return set_err(GAAST_ERR_INVALID_ARGUMENT, "null argument");
     if (int st = ensure_init()) return st;
     *count = 0;
-    if (!prog->d_domain) return GAAST_OK;
+    if (!prog->domain.ptr) return GAAST_OK;
     HIP_TRY(hipStreamSynchronize(g_stream));
     unsigned long long v = 0;
-    HIP_TRY(hipMemcpy(&v, prog->d_domain, sizeof(v), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset(prog->d_domain, 0, sizeof(v)));
+    HIP_TRY(hipMemcpy(&v, prog->domain.ptr, sizeof(v), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemset(prog->domain.ptr, 0, sizeof(v)));
     *count = int64_t(v);
     return GAAST_OK;
 }
@@ -1563,10 +1569,10 @@ int gaast_hip_program_output_info(gaast_hip_program_t prog, uint64_t* grade_mask
     return GAAST_OK;
 }
 
-int gaast_hip_program_num_launches(gaast_hip_program_t prog) { return prog ? int(prog->launch_names.size()) : 0; }
+int gaast_hip_program_num_launches(gaast_hip_program_t prog) { return prog ? int(prog->launches.size()) : 0; }
 const char* gaast_hip_program_launch_name(gaast_hip_program_t prog, int i) {
-    if (!prog || i < 0 || i >= int(prog->launch_names.size())) return "";
-    return prog->launch_names[size_t(i)].c_str();
+    if (!prog || i < 0 || i >= int(prog->launches.size())) return "";
+    return prog->launches[size_t(i)].label.c_str();
 }
 
 int gaast_hip_mv_alloc(int dim, uint64_t grade_mask, int64_t batch, int dtype, gaast_hip_mv_t* out) {
@@ -1689,8 +1695,12 @@ int bind_eval(gaast_hip_program_t prog, const gaast_hip_mv_t* inputs, int n_inpu
     if (n_inputs < 0 || (n_inputs && !inputs)) return set_err(GAAST_ERR_INVALID_ARGUMENT, "bad inputs");
     in_bound.assign(plan.inputs.size(), Bound{nullptr, 0});
     for (size_t i = 0; i < plan.inputs.size(); ++i) {
-        gaast_hip_mv_t m = plan.inputs[i].is_const ? prog->const_mvs[i] : (int(i) < n_inputs ? inputs[i] : nullptr);
         const Layout& want = plan.input_layouts[i];
+        if (plan.inputs[i].is_const) {   // one row, shared by every item
+            in_bound[i] = Bound{prog->const_rows[i].ptr, batch != 1 ? 0 : want.row_len};
+            continue;
+        }
+        gaast_hip_mv_t m = int(i) < n_inputs ? inputs[i] : nullptr;
         if (!m) {
             // slots no launch reads may stay unbound
             if (plan.slot_used[i]) return set_err(GAAST_ERR_INVALID_ARGUMENT, "input slot " + std::to_string(i) + " is not bound");
@@ -1710,12 +1720,10 @@ int bind_eval(gaast_hip_program_t prog, const gaast_hip_mv_t* inputs, int n_inpu
     return GAAST_OK;
 }
 
-// the launches of one evaluation over items [first, first + count) of the bound buffers
-int eval_range(gaast_hip_program_t prog, const std::vector<Bound>& in_bound0, gaast_hip_mv_t out, int64_t first, int64_t count) {
-    Plan& plan = prog->plan;
-    if (plan.flags & GAAST_FLAG_DEBUG_FAIL_EVAL) return set_err(GAAST_ERR_HIP, "injected evaluation failure (GAAST_FLAG_DEBUG_FAIL_EVAL)");
-    if (count == 0) return GAAST_OK;
-    const size_t sz = dtype_size(plan.dtype);
+template <typename T>
+int run_launches(gaast_hip_program_t prog, const std::vector<Bound>& in_bound0, gaast_hip_mv_t out, int64_t first, int64_t count) {
+    const Plan& plan = prog->plan;
+    const size_t sz = sizeof(T);
     auto shifted = [&](Bound b) {
         if (b.ptr && first) b.ptr = static_cast<char*>(b.ptr) + size_t(first) * size_t(b.stride) * sz;
         return b;
@@ -1727,7 +1735,6 @@ int eval_range(gaast_hip_program_t prog, const std::vector<Bound>& in_bound0, ga
     // cache buffers of the product operands (the per-eval HashMap<NodeId, R> of eval.rs:16)
     if (prog->scratch_batch < count || prog->scratch.size() != plan.node_buffers.size()) {
         if (!prog->scratch.empty()) HIP_TRY(hipStreamSynchronize(g_stream));  // launches may still read the old ones
-        for (gaast_hip_mv_t m : prog->scratch) mv_free_impl(m);
         prog->scratch.clear();
         for (size_t bi = 0; bi < plan.node_buffers.size(); ++bi) {
             const Layout& l = plan.node_buffers[bi];
@@ -1735,7 +1742,7 @@ int eval_range(gaast_hip_program_t prog, const std::vector<Bound>& in_bound0, ga
             // a cache buffer a chained product made unnecessary is never allocated
             const bool dead = bi < plan.node_dead.size() && plan.node_dead[bi];
             if (int st = mv_alloc_impl(l.dim, l.mask, dead ? 0 : count, plan.dtype, &m)) return st;
-            prog->scratch.push_back(m);
+            prog->scratch.emplace_back(m);
         }
         prog->scratch_batch = count;
     }
@@ -1746,17 +1753,17 @@ int eval_range(gaast_hip_program_t prog, const std::vector<Bound>& in_bound0, ga
     Bound out_inner = out_b;
     for (size_t i = 0; i < plan.basis_slot_buf.size(); ++i) {
         if (plan.basis_slot_buf[i] < 0 || !in_bound[i].ptr) continue;
-        gaast_hip_mv_t m = prog->scratch[size_t(plan.basis_slot_buf[i])];
+        gaast_hip_mv_t m = prog->scratch[size_t(plan.basis_slot_buf[i])].get();
         inner_bound[i] = Bound{m->ptr, in_bound[i].stride == 0 ? 0 : m->row_stride};
     }
     if (plan.basis_out_buf >= 0) {
-        gaast_hip_mv_t m = prog->scratch[size_t(plan.basis_out_buf)];
+        gaast_hip_mv_t m = prog->scratch[size_t(plan.basis_out_buf)].get();
         out_inner = Bound{m->ptr, m->row_stride};
     }
     auto resolve = [&](BufRef r, Layout* lay) -> Bound {
         switch (r.kind) {
         case BufKind::NODE: {
-            gaast_hip_mv_t m = prog->scratch[size_t(r.idx)];
+            gaast_hip_mv_t m = prog->scratch[size_t(r.idx)].get();
             *lay = m->layout;
             return Bound{m->ptr, m->row_stride};
         }
@@ -1764,7 +1771,8 @@ int eval_range(gaast_hip_program_t prog, const std::vector<Bound>& in_bound0, ga
         default: *lay = out->layout; return out_inner;
         }
     };
-    for (const Step& s : plan.steps) {
+    for (const Launch& L : prog->launches) {
+        const Step& s = L.s;
         Layout lres, la, lb;
         if (s.kind == Step::LINMAP) {   // the caller's rows in, the caller's rows out
             Bound src, dst;
@@ -1782,21 +1790,16 @@ int eval_range(gaast_hip_program_t prog, const std::vector<Bound>& in_bound0, ga
             } else {
                 dst = resolve(s.res, &lres);
             }
-            const int st = plan.dtype == GAAST_F32 ? run_step<float>(s, dst, src, Bound{nullptr, 0}, la, lb, items, plan.n)
-                                                   : run_step<double>(s, dst, src, Bound{nullptr, 0}, la, lb, items, plan.n);
-            if (st != GAAST_OK) return st;
+            if (int st = run_step<T>(L, dst, src, Bound{nullptr, 0}, la, lb, items)) return st;
             continue;
         }
         const Bound res = resolve(s.res, &lres);
         if (s.kind == Step::FUSED) {
-            const int st = plan.dtype == GAAST_F32 ? run_fused<float>(s, plan, inner_bound, res, count)
-                                                   : run_fused<double>(s, plan, inner_bound, res, count);
-            if (st != GAAST_OK) return st;
+            if (int st = run_fused<T>(L, plan, inner_bound, res, count)) return st;
             continue;
         }
         if (s.kind == Step::ELEMENTWISE) {
-            const int st = plan.dtype == GAAST_F32 ? run_elementwise<float>(s, res, resolve, count) : run_elementwise<double>(s, res, resolve, count);
-            if (st != GAAST_OK) return st;
+            if (int st = run_elementwise<T>(L, res, resolve, count)) return st;
             continue;
         }
         if (s.kind == Step::ZERO) {
@@ -1808,7 +1811,6 @@ int eval_range(gaast_hip_program_t prog, const std::vector<Bound>& in_bound0, ga
         Bound a{nullptr, 0}, b{nullptr, 0};
         if (s.a.idx >= 0) a = resolve(s.a, &la);
         if (s.b.idx >= 0) b = resolve(s.b, &lb);
-        const int step_n = (s.kind == Step::PRODUCT_DENSE && s.dense_n) ? s.dense_n : plan.n;
         Bound pa{nullptr, 0}, pb{nullptr, 0};
         if (s.kind == Step::REDUCE_SCALE) {
             Layout unused;
@@ -1821,11 +1823,17 @@ int eval_range(gaast_hip_program_t prog, const std::vector<Bound>& in_bound0, ga
             Layout unused;
             pa = resolve(s.pre_a, &unused);   // the folded copy's source
         }
-        const int st = plan.dtype == GAAST_F32 ? run_step<float>(s, res, a, b, la, lb, count, step_n, pa, pb)
-                                               : run_step<double>(s, res, a, b, la, lb, count, step_n, pa, pb);
-        if (st != GAAST_OK) return st;
+        if (int st = run_step<T>(L, res, a, b, la, lb, count, pa, pb)) return st;
     }
     return GAAST_OK;
+}
+
+// the launches of one evaluation over items [first, first + count) of the bound buffers
+int eval_range(gaast_hip_program_t prog, const std::vector<Bound>& in_bound, gaast_hip_mv_t out, int64_t first, int64_t count) {
+    const Plan& plan = prog->plan;
+    if (plan.flags & GAAST_FLAG_DEBUG_FAIL_EVAL) return set_err(GAAST_ERR_HIP, "injected evaluation failure (GAAST_FLAG_DEBUG_FAIL_EVAL)");
+    if (count == 0) return GAAST_OK;
+    return plan.dtype == GAAST_F32 ? run_launches<float>(prog, in_bound, out, first, count) : run_launches<double>(prog, in_bound, out, first, count);
 }
 
 int rccl_err(const std::string& msg) { return set_err(GAAST_ERR_RCCL, msg); }

@@ -470,6 +470,35 @@ static void single_list_tables_agree(int n, int dtype, const char* dump_dir, uin
     gaast_spec_free(spec);
 }
 
+// Bits 30 and 31 of the caller's flags are reserved and ignored: only the runtime's register-trial rebuild asks for small slabs
+// (build_plan's small_reg_slab).  A program whose fused slab lies above the small-slab limit (160 elements in f64, 200 in f32)
+// must lower the same with and without bit 30 set.
+static void reserved_flag_bits_are_ignored(gaast_expr_t e, int n, const double* metric, int dtype, const char* what) {
+    gaast_spec_t spec = gaast_expr_specialize(e, n, metric, 1 << 16);
+    CHECK(spec != nullptr);
+    if (!spec) return;
+    gaast_program_desc desc;
+    CHECK(gaast_spec_program_desc(spec, dtype, 0, &desc) == 0);
+    gaast::Plan plain, reserved;
+    gaast::build_plan(desc, plain);
+    desc.flags |= 0x40000000u;
+    gaast::build_plan(desc, reserved);
+    bool big_slab = false;
+    for (const gaast::Step& s : plain.steps)
+        if (s.kind == gaast::Step::FUSED && s.fused_slab > (dtype == GAAST_F32 ? 200 : 160)) big_slab = true;
+    if (!big_slab) std::printf("%s: no fused slab above the small-slab limit\n", what);
+    CHECK(big_slab);
+    bool same = plain.steps.size() == reserved.steps.size();
+    for (size_t i = 0; same && i < plain.steps.size(); ++i) {
+        const gaast::Step &a = plain.steps[i], &b = reserved.steps[i];
+        same = a.kind == b.kind && a.fused_slab == b.fused_slab && a.jit_items == b.jit_items && a.jit_reg_trial == b.jit_reg_trial;
+    }
+    if (!same) std::printf("%s: bit 30 of the flags changed the plan\n", what);
+    CHECK(same);
+    gaast_spec_free(spec);
+    std::printf("ok  %s\n", what);
+}
+
 int main(int argc, char** argv) {
     const char* dump_dir = argc > 1 ? argv[1] : nullptr;
     single_list_tables_agree(8, GAAST_F64, dump_dir);
@@ -670,6 +699,8 @@ int main(int argc, char** argv) {
             }
         }
     }
+    // the versor inverse of an even multivector at n = 8 in f32 (plan.cpp, beside jit_slab_small: a slab of 259 elements, on register trial)
+    reserved_flag_bits_are_ignored(gaast_expr_vinv(gaast_expr_input(0, 0x155, 8)), 8, euclid, GAAST_F32, "flag bit 30 ignored: versor inverse n=8 f32");
     for (gaast_expr_t h : handles) gaast_expr_release(h);
     if (failures) {
         std::printf("%d failures\n", failures);
