@@ -22,6 +22,7 @@ F64, F32 = 0, 1
 OP_NAMES = ["GradedObj", "Addition", "Product", "Negation", "Exponential", "Logarithm",
             "GradeProjection", "Reverse", "GradeInvolution", "ScalarInversion", "ScalarSqrt"]
 PROD_EXPLICIT, PROD_GEOMETRIC, PROD_OUTER, PROD_INNER, PROD_LCONTRACT, PROD_RCONTRACT = -1, 0, 1, 2, 3, 4
+PROD_ADJ_LEFT, PROD_ADJ_RIGHT = 8, 16   # added to a forward kind: compact adjoint products (reverse mode)
 FLAG_DEBUG_OVERFLOW, FLAG_NO_FUSION, FLAG_EXACT_ORDER, FLAG_NO_MFMA, FLAG_NO_JIT, FLAG_SPINOR_GEMM = 1, 2, 4, 8, 16, 32
 FLAG_DEBUG_JIT_FAILS, FLAG_DEBUG_KEEP_JIT_SOURCE, FLAG_EXP_LOG, FLAG_NO_COALESCE, FLAG_DEBUG_LDS_12K = 0x40, 0x80, 0x100, 0x200, 0x400
 FLAG_DEBUG_NO_CHAIN = 0x800
@@ -112,6 +113,8 @@ SIGNATURES = {
     "gaast_hip_linmap_apply": (_ci, [_vp, _vp, _vp]),
     "gaast_hip_linmap_destroy": (_ci, [_vp]),
     "gaast_hip_program_create_in_basis": (_ci, [C.POINTER(ProgramDesc), _pd, C.POINTER(_vp)]),
+    "gaast_hip_program_create_vjp": (_ci, [C.POINTER(ProgramDesc), C.c_int32, C.POINTER(_vp)]),
+    "gaast_hip_mv_sum_rows": (_ci, [_vp, _vp]),
     # ---- include/gaast_expr.h ----
     "gaast_expr_last_error": (C.c_char_p, []),
     "gaast_gs_single": (_u64, [_i64]),
@@ -161,6 +164,7 @@ SIGNATURES = {
     "gaast_program_deserialize": (_vp, [_vp, _sz]),
     "gaast_program_image_desc": (C.POINTER(ProgramDesc), [_vp]),
     "gaast_program_image_free": (None, [_vp]),
+    "gaast_program_vjp": (_ci, [C.POINTER(ProgramDesc), C.c_int32, C.POINTER(_vp)]),
     "gaast_spec_num_inputs": (_ci, [_vp]),
     "gaast_spec_num_user_inputs": (_ci, [_vp]),
 }

@@ -321,11 +321,92 @@ class SpecializedAst:
         out._keep_inputs = keep
         return out
 
+    # -- reverse mode ---------------------------------------------------------------------------
+    def vjp(self, slot):
+        """The vector-Jacobian product with respect to input `slot` (gaast_program_vjp), built once per slot."""
+        if self._basis() is not None:
+            raise _lib.GaastError(3, "programs in a non-diagonal Gram metric have no VJP")
+        cache = self.__dict__.setdefault("_vjps", {})
+        if slot not in cache:
+            cache[slot] = Vjp(self, int(slot))
+        return cache[slot]
+
+    def torch_fn(self):
+        """A callable on torch tensors [B or 1, row_len] backed by a torch.autograd.Function (gaast_amd.autograd)."""
+        from .autograd import torch_fn
+        return torch_fn(self)
+
     def eval(self):
         """eval::<GradeMapMV>() (eval.rs:12-19) for an AST whose inputs are all fixed values."""
         out = self.eval_batch((), 1)
         _lib.check(_lib.lib().gaast_hip_synchronize())
         return out.item(0)
+
+
+class Vjp:
+    """Reverse mode of a SpecializedAst with respect to one input slot: a program whose inputs are the forward inputs and the
+    cotangent (slot = number of forward slots), and whose output is the gradient in the layout of input `slot`."""
+
+    def __init__(self, spec, slot):
+        L = _lib.lib()
+        self.spec, self.slot, self.dtype = spec, slot, spec.dtype
+        d = spec.program_desc()
+        img = C.c_void_p()
+        st = L.gaast_program_vjp(C.byref(d), slot, C.byref(img))
+        if st:
+            raise _lib.GaastError(st, L.gaast_expr_last_error().decode())
+        self._img = img
+        self.desc = L.gaast_program_image_desc(img).contents
+        self.n_fwd = d.n_inputs
+        self.wrt_dim, self.wrt_mask = d.inputs[slot].storage_dim, d.inputs[slot].grade_mask
+        self._prog = None
+
+    def __del__(self):
+        try:
+            if self._prog:
+                _lib.lib().gaast_hip_program_destroy(self._prog)
+            if self._img:
+                _lib.lib().gaast_program_image_free(self._img)
+        except Exception:
+            pass
+
+    def program(self):
+        if self._prog is None:
+            _lib.init_device()
+            h = C.c_void_p()
+            _lib.check(_lib.lib().gaast_hip_program_create(C.byref(self.desc), C.byref(h)))
+            self._prog = h
+        return self._prog
+
+    def launches(self):
+        p = self.program()
+        return [_lib.lib().gaast_hip_program_launch_name(p, i).decode()
+                for i in range(_lib.lib().gaast_hip_program_num_launches(p))]
+
+    def eval_batch(self, inputs, cotangent, batch, reduce=False, out=None):
+        """Gradient rows of input `slot` for each item (inputs as for SpecializedAst.eval_batch, cotangent: [batch, root row]
+        or a DeviceMV).  reduce=True: their sum over the batch (gaast_hip_mv_sum_rows), one row."""
+        prog = self.program()
+        n_slots = self.desc.n_inputs
+        handles = (C.c_void_p * n_slots)()
+        keep = []
+        for s, x in enumerate(list(inputs)[:self.n_fwd] + [None] * (self.n_fwd - min(len(inputs), self.n_fwd)) + [cotangent]):
+            if x is None:
+                continue
+            if not isinstance(x, DeviceMV):
+                ind = self.desc.inputs[s]
+                x = DeviceMV.from_rows(ind.storage_dim, GradeSet(ind.grade_mask), x, self.dtype)
+            keep.append(x)
+            handles[s] = x._h
+        if out is None or reduce:
+            grad = DeviceMV.alloc(self.wrt_dim, GradeSet(self.wrt_mask), batch, self.dtype)
+        else:
+            grad = out
+        _lib.check(_lib.lib().gaast_hip_eval(prog, handles, n_slots, batch, grad._h))
+        grad._keep_inputs = keep
+        if reduce:
+            return grad.sum_rows(out)
+        return grad
 
 
 class ProgramImage:

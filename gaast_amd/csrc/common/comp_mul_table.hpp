@@ -2,6 +2,7 @@
 // needs), in the reference's order T4: (k_left asc, k_right asc, left index asc, right index
 // asc), filtered by grade(result) in contribs  (specialize.rs:132-183).
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <vector>
 
@@ -53,6 +54,34 @@ inline void for_each_comp_mul(const BladeTable& bt, const double* metric_diag,
             }
         }
     }
+}
+
+// Adjoint (transposed) list of a product list (l, r -> o, c).  The operand that is differentiated becomes the result and
+// the cotangent o takes its place: right = false gives (o, r -> l, c); right = true gives (l, o -> r, c), or (o, l -> r, c)
+// with cotangent_first (the operand order of a GAAST_PROD_ADJ_RIGHT node: cotangent, then the other forward operand).
+// Forward order is kept, then the entries are ordered stably by result component.
+inline std::vector<gaast_comp_mul> transpose_comp_muls(const gaast_comp_mul* fwd, uint64_t n, bool right, bool cotangent_first) {
+    std::vector<gaast_comp_mul> out(static_cast<size_t>(n));
+    for (uint64_t e = 0; e < n; ++e) {
+        const gaast_comp_mul& f = fwd[e];
+        gaast_comp_mul& m = out[size_t(e)];
+        m.coeff = f.coeff;
+        if (!right) {
+            m.left_grade = f.result_grade, m.left_index = f.result_index;
+            m.right_grade = f.right_grade, m.right_index = f.right_index;
+            m.result_grade = f.left_grade, m.result_index = f.left_index;
+        } else {
+            const uint32_t ag = cotangent_first ? f.result_grade : f.left_grade, ai = cotangent_first ? f.result_index : f.left_index;
+            const uint32_t bg = cotangent_first ? f.left_grade : f.result_grade, bi = cotangent_first ? f.left_index : f.result_index;
+            m.left_grade = ag, m.left_index = ai;
+            m.right_grade = bg, m.right_index = bi;
+            m.result_grade = f.right_grade, m.result_index = f.right_index;
+        }
+    }
+    std::stable_sort(out.begin(), out.end(), [](const gaast_comp_mul& a, const gaast_comp_mul& b) {
+        return a.result_grade != b.result_grade ? a.result_grade < b.result_grade : a.result_index < b.result_index;
+    });
+    return out;
 }
 
 }  // namespace gaast

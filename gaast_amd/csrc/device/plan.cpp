@@ -526,6 +526,17 @@ struct Lowering {
         const int n = d.vec_space_dim;
         if (n < 6 || n > 15) return 0;
         if (layout(res).dim != n || layout(l).dim != n || layout(r).dim != n) return 0;
+        if (nd.product_kind >= GAAST_PROD_ADJ_LEFT) {
+            // adjoint of a geometric product: a forward product in the metric m' (1 / m off the null
+            // vectors, 0 on them) of relabelled / re-signed / rescaled operands, always in the full frame
+            if ((nd.product_kind & 7) != GAAST_PROD_GEOMETRIC || n > 14) return 0;
+            DenseFrame f;
+            f.n = n;
+            for (int i = 0; i < n; ++i) f.metric.push_back(d.metric_diag[i] == 0.0 ? 0.0 : 1.0 / d.metric_diag[i]);
+            const int kind = dense_kind_for(f, nd.n_comp_muls, perm);
+            if (kind) frame = f;
+            return kind;
+        }
         const uint64_t lmask = node(nd.child0).minimal_grade_mask & layout(l).mask, rmask = node(nd.child1).minimal_grade_mask & layout(r).mask;
         int kind = 0;
         bool geometric_known = false, geometric = false;
@@ -688,11 +699,37 @@ struct Lowering {
             if (beta0) {
                 removed[size_t(fr->second)] = 1;
             }
+            // adjoint products (GAAST_PROD_ADJ_*): ADJ_LEFT multiplies (cotangent, B), ADJ_RIGHT (A, cotangent), so the kernel's
+            // operands are (child0, child1) or (child1, child0); the cotangent's blades and the result's are relabelled k -> k ^ Z
+            // (Z: the null vectors), the other operand's component j is scaled by rev(j) mn(j) (-1)^R(Z, j) (left adjoint) or
+            // (-1)^R(j, Z) (right adjoint), mn the product of the non-null squares (tools/proto/adjoint_dense.py)
+            const int adj = nd.product_kind >= GAAST_PROD_ADJ_LEFT ? (nd.product_kind & ~7) : 0;
+            uint32_t adj_z = 0;
+            for (int i = 0; adj && i < n; ++i)
+                if (d.metric_diag[i] == 0.0) adj_z |= 1u << i;
+            const bool swap_ops = adj == GAAST_PROD_ADJ_RIGHT;
+            const BufRef ka = swap_ops ? r : l, kb = swap_ops ? l : r;
+            const Layout &kla = swap_ops ? lrr : ll, &klb = swap_ops ? ll : lrr;
+            const uint64_t kfa = swap_ops ? flip_r : flip_l, kfb = swap_ops ? flip_l : flip_r;
+            const uint64_t kwa = swap_ops ? (rmin & lrr.mask) : (lmin & ll.mask), kwb = swap_ops ? (lmin & ll.mask) : (rmin & lrr.mask);
+            auto adj_operand = [&](uint32_t S, bool right, long double* f) -> uint32_t {
+                *f = 1.0L;
+                if (!adj) return S;
+                if ((adj == GAAST_PROD_ADJ_LEFT) != right) return S ^ adj_z;   // the cotangent
+                const int k = __builtin_popcount(S);
+                int sign = (k * (k - 1) / 2) & 1;
+                sign ^= adj == GAAST_PROD_ADJ_LEFT ? reorder_parity(adj_z, S) : reorder_parity(S, adj_z);
+                long double m = 1.0L;
+                for (int i = 0; i < n; ++i)
+                    if (((S >> i) & 1u) && d.metric_diag[i] != 0.0) m *= (long double)d.metric_diag[i];
+                *f = sign ? -m : m;
+                return S;
+            };
             Step& s = emit(Step::PRODUCT_DENSE, res, "product_dense[gp n=" + std::to_string(n) + "]");
-            s.a = l;
-            s.b = r;
-            s.canon_a = canon_l;
-            s.canon_b = canon_r;
+            s.a = ka;
+            s.b = kb;
+            s.canon_a = swap_ops ? canon_r : canon_l;
+            s.canon_b = swap_ops ? canon_l : canon_r;
             s.beta = beta0 ? 0 : 1;
             s.n_entries = nd.n_comp_muls;
             s.dense_n = n2;
@@ -810,11 +847,12 @@ struct Lowering {
                 for (int k = 0; k <= n; ++k) {
                     if (!((want >> k) & 1ULL)) continue;
                     for (uint32_t i = 0; i < bt.grade_dim[size_t(k)]; ++i) {
-                        const uint32_t orig = bt.blade_of[size_t(k)][i];
+                        long double fa;
+                        const uint32_t orig = adj_operand(bt.blade_of[size_t(k)][i], right, &fa);
                         long double f1;
                         const uint32_t R = operand_to_frame(orig, right, &f1);
                         const uint32_t blade = new_blade[R];
-                        const long double factor = f1 * blade_scale(frame, R);
+                        const long double factor = fa * f1 * blade_scale(frame, R);
                         uint32_t neg = uint32_t((flip >> k) & 1ULL) ^ blade_sign[R] ^ (factor < 0.0L ? 1u : 0u);
                         // image-pair kernels: the b_hi part of (-1)^(|a_hi| |b_lo|), |a_hi| = |b_hi| + |c_hi| (mod 2), lives in the B image
                         if (s.use_mfma16 && right) neg ^= uint32_t(__builtin_popcount(blade >> 4) & __builtin_popcount(blade & 15u) & 1);
@@ -887,9 +925,8 @@ struct Lowering {
                     }
                 }
             };
-            uint64_t lwant = lmin & ll.mask, rwant = rmin & lrr.mask;
-            build_map(ll, lwant, flip_l, false, s.u32_a, s.coeff, &s.left_full, &s.left_contig);
-            build_map(lrr, rwant, flip_r, true, s.u32_b, s.coeff_b, &s.right_full, &s.right_contig);
+            build_map(kla, kwa, kfa, false, s.u32_a, s.coeff, &s.left_full, &s.left_contig);
+            build_map(klb, kwb, kfb, true, s.u32_b, s.coeff_b, &s.right_full, &s.right_contig);
             // out_map: indexed by the blade of the frame's permuted basis; offset | sign << 30, or -1; coeff_c: |factor|
             s.i32_a.assign(size_t(1) << n2, -1);
             s.coeff_c.assign(size_t(1) << n2, 1.0);
@@ -897,7 +934,7 @@ struct Lowering {
                 const int g = __builtin_popcount(m);
                 if (!((prod_mask >> g) & 1ULL)) continue;
                 long double f1;
-                const uint32_t R = result_from_frame(m, &f1);
+                const uint32_t R = result_from_frame(adj ? (m ^ adj_z) : m, &f1);
                 const long double factor = f1 / blade_scale(frame, R);
                 const uint32_t sgn = blade_sign[R] ^ (factor < 0.0L ? 1u : 0u);
                 s.i32_a[new_blade[R]] = int32_t(uint32_t(lr.offset(g) + bt.index_of[m]) | (sgn << 30));
@@ -932,7 +969,8 @@ struct Lowering {
             static const char* const par_name[2] = {"even", "odd"};
             s.name = std::string(dense_kind == 1 ? "product_dense" : "product_dense_mfma") + "[gp n=" + std::to_string(n) +
                      (reduced ? std::string(" ") + par_name[frame.lpar] + " x " + par_name[frame.rpar] + " in Cl(" + std::to_string(n2) + ")" : std::string()) +
-                     (identity ? "" : " permuted basis") + (s.scaled ? " rescaled basis" : "") + "]";
+                     (identity ? "" : " permuted basis") + (s.scaled ? " rescaled basis" : "") +
+                     (adj == GAAST_PROD_ADJ_LEFT ? " adjoint left" : adj ? " adjoint right" : "") + "]";
             touch(res);
             return;
         }
@@ -953,6 +991,25 @@ struct Lowering {
             if (n_muls > kMaxListEntries && plan.unsupported.empty())
                 plan.unsupported = "a comp-mul list of " + std::to_string(n_muls) + " entries exceeds this back end's table budget";
             if (!plan.unsupported.empty()) return;
+        }
+        if (!muls && nd.product_kind >= GAAST_PROD_ADJ_LEFT) {
+            // compact adjoint: regenerate the forward list from the node's three grade sets, then transpose it
+            const bool right = (nd.product_kind & GAAST_PROD_ADJ_RIGHT) != 0;
+            const Selection sel{nd.product_kind & 7, nullptr, nullptr};
+            auto contribs = right ? iter_contribs(lmin, sel, rmin, omin) : iter_contribs(lmin, sel, omin, rmin);
+            const uint64_t count = comp_mul_count(d.vec_space_dim, contribs);
+            // no dense kernel took it (EXACT_ORDER, a kind other than geometric, a metric the kernels cannot scale): the list is
+            // regenerated, transposed and sorted on the host -- refused beyond kMaxAdjointListEntries instead of building GBs
+            if (count > kMaxAdjointListEntries && plan.unsupported.empty())
+                plan.unsupported = "a compact adjoint product whose list of " + std::to_string(count) +
+                                   " entries no dense kernel takes exceeds the adjoint list budget";
+            if (!plan.unsupported.empty()) return;
+            std::vector<gaast_comp_mul> fwd;
+            fwd.reserve(size_t(count));
+            for_each_comp_mul(bt, d.metric_diag, contribs, [&](const gaast_comp_mul& m) { fwd.push_back(m); });
+            generated = transpose_comp_muls(fwd.data(), fwd.size(), right, true);
+            muls = generated.data();
+            n_muls = generated.size();
         }
         if (!muls) {
             Selection sel{nd.product_kind, nullptr, nullptr};
@@ -3093,6 +3150,11 @@ void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab)
         case GAAST_OP_ADD:
         case GAAST_OP_PRODUCT:
             if (!child_ok(nd.child0) || !child_ok(nd.child1)) throw std::runtime_error("nodes are not in post-order");
+            if (nd.opcode == GAAST_OP_PRODUCT && nd.product_kind >= GAAST_PROD_ADJ_LEFT) {
+                const int adj = nd.product_kind & ~7, base = nd.product_kind & 7;
+                if ((adj != GAAST_PROD_ADJ_LEFT && adj != GAAST_PROD_ADJ_RIGHT) || base > GAAST_PROD_RCONTRACT)
+                    throw std::runtime_error("unknown product kind");
+            }
             break;
         case GAAST_OP_NEG: case GAAST_OP_EXP: case GAAST_OP_LOG: case GAAST_OP_PROJ:
         case GAAST_OP_REVERSE: case GAAST_OP_GINVOL: case GAAST_OP_SINV: case GAAST_OP_SSQRT:

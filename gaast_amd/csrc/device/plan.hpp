@@ -157,6 +157,7 @@ constexpr size_t kLdsBytes = 160 * 1024;
 #endif
 constexpr size_t kInterpLdsBytes = size_t(GAAST_INTERP_BUDGET_KB) * 1024;   // slabs of the 64 items of a k_ast_fused workgroup
 constexpr uint64_t kMaxListEntries = uint64_t(1) << 27;
+constexpr uint64_t kMaxAdjointListEntries = uint64_t(1) << 22;   // compact adjoints regenerated as lists (n = 11 full: 4 M)
 
 struct Plan {
     int n = 0;

@@ -15,6 +15,7 @@
 
 #include "../common/metric_basis.hpp"
 #include "comm.hpp"
+#include "gaast_expr.h"
 #include "gaast_hip.h"
 #include "kernels.hip.hpp"
 #include "plan.hpp"
@@ -36,6 +37,14 @@ Comm g_comm;                       // the gather communicator (gaast_hip_comm_in
 std::vector<hipEvent_t> g_events;  // chunk-done events of gaast_hip_eval_gather, created on demand
 hipEvent_t g_comm_done = nullptr;
 int64_t* g_comm_flag = nullptr;    // device word of gaast_hip_eval_gather's collective error flag
+// partial rows of gaast_hip_mv_sum_rows, one buffer per stream it ran on (reductions on two streams never share one); grown on
+// demand after a synchronisation of that stream only, freed at shutdown
+struct ReduceScratch {
+    hipStream_t stream;
+    void* ptr;
+    size_t bytes;
+};
+std::vector<ReduceScratch> g_reduce_scratch;
 
 int set_err(int status, const std::string& msg) {
     g_err = msg;
@@ -1359,6 +1368,11 @@ int gaast_hip_shutdown(void) {
         g_comm_done = nullptr;
         if (g_comm_flag) (void)hipFree(g_comm_flag);
         g_comm_flag = nullptr;
+        for (ReduceScratch& r : g_reduce_scratch) {
+            (void)hipStreamSynchronize(r.stream);
+            (void)hipFree(r.ptr);
+        }
+        g_reduce_scratch.clear();
     }
     g_init = false;
     return GAAST_OK;
@@ -1388,6 +1402,75 @@ int gaast_hip_program_create(const gaast_program_desc* desc, gaast_hip_program_t
         st = program_create_impl(&d2, out);
     }
     return st == kChainTooBig ? GAAST_ERR_UNIMPLEMENTED : st;
+}
+
+// ---- reverse mode -------------------------------------------------------------------------------------------------------
+int gaast_hip_program_create_vjp(const gaast_program_desc* desc, int32_t wrt_slot, gaast_hip_program_t* out) {
+    if (!desc || !out) return set_err(GAAST_ERR_INVALID_ARGUMENT, "null argument");
+    gaast_program_image_t img = nullptr;
+    if (int st = gaast_program_vjp(desc, wrt_slot, &img)) return set_err(st, std::string("program_create_vjp: ") + gaast_expr_last_error());
+    const int st = gaast_hip_program_create(gaast_program_image_desc(img), out);
+    gaast_program_image_free(img);
+    return st;
+}
+
+extern "C++" {
+namespace {
+template <typename T>
+int launch_sum_rows(gaast_hip_mv_t in, gaast_hip_mv_t out) {
+    const int64_t B = in->batch, len = in->layout.row_len;
+    if (len == 0) return GAAST_OK;
+    const int64_t chunk = GAAST_SUM_ROWS_CHUNK, chunks = (B + chunk - 1) / chunk;
+    const unsigned tiles = unsigned((len + kSumCols - 1) / kSumCols);
+    T* dst = static_cast<T*>(out->ptr);
+    if (chunks > 1) {
+        const size_t bytes = size_t(chunks * len) * sizeof(T);
+        ReduceScratch* sc = nullptr;
+        for (ReduceScratch& r : g_reduce_scratch)
+            if (r.stream == g_stream) sc = &r;
+        if (!sc) {
+            g_reduce_scratch.push_back(ReduceScratch{g_stream, nullptr, 0});
+            sc = &g_reduce_scratch.back();
+        }
+        if (bytes > sc->bytes) {
+            if (sc->ptr) {
+                HIP_TRY(hipStreamSynchronize(g_stream));   // an earlier reduction on this stream may still read it
+                HIP_TRY(hipFree(sc->ptr));
+                sc->ptr = nullptr;
+                sc->bytes = 0;
+            }
+            HIP_TRY(hipMalloc(&sc->ptr, bytes));
+            sc->bytes = bytes;
+        }
+        T* part = static_cast<T*>(sc->ptr);
+        hipLaunchKernelGGL(k_sum_rows<T>, dim3(unsigned(chunks), tiles), dim3(256), 0, g_stream,
+                           static_cast<const T*>(in->ptr), in->row_stride, B, int(len), chunk, part, len);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_sum_rows<T>, dim3(1u, tiles), dim3(256), 0, g_stream, static_cast<const T*>(part), len, chunks, int(len),
+                           chunks, dst, len);
+    } else {
+        hipLaunchKernelGGL(k_sum_rows<T>, dim3(1u, tiles), dim3(256), 0, g_stream, static_cast<const T*>(in->ptr), in->row_stride, B,
+                           int(len), chunk, dst, len);
+    }
+    HIP_TRY(hipGetLastError());
+    return GAAST_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int gaast_hip_mv_sum_rows(gaast_hip_mv_t in, gaast_hip_mv_t out) {
+    if (!in || !out) return set_err(GAAST_ERR_INVALID_ARGUMENT, "null argument");
+    if (int st = ensure_init()) return st;
+    if (out->batch != 1) return set_err(GAAST_ERR_INVALID_ARGUMENT, "sum_rows: out must hold one row");
+    if (in->batch < 1) return set_err(GAAST_ERR_INVALID_ARGUMENT, "sum_rows: in holds no rows");
+    if (in->layout.dim != out->layout.dim || in->layout.mask != out->layout.mask || in->dtype != out->dtype)
+        return set_err(GAAST_ERR_INVALID_ARGUMENT, "sum_rows: in and out differ in dimension, grade mask or dtype");
+    if (in->layout.row_len > (int64_t(1) << GAAST_MAX_DIM)) return set_err(GAAST_ERR_INVALID_ARGUMENT, "sum_rows: row too long");
+    const size_t sz = dtype_size(in->dtype);
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(in->ptr), b0 = reinterpret_cast<uintptr_t>(out->ptr);
+    const uintptr_t a1 = a0 + size_t((in->batch - 1) * in->row_stride + in->layout.row_len) * sz, b1 = b0 + size_t(out->layout.row_len) * sz;
+    if (a0 < b1 && b0 < a1) return set_err(GAAST_ERR_INVALID_ARGUMENT, "sum_rows: in and out overlap");
+    return in->dtype == GAAST_F32 ? launch_sum_rows<float>(in, out) : launch_sum_rows<double>(in, out);
 }
 
 // ---- linear maps of the vector space on graded rows (outermorphisms) --------------------------------------------------

@@ -26,6 +26,7 @@ static gaast_expr_t wrap(ExprPtr p) {
     h->node = std::move(p);
     return h;
 }
+void gaast_set_expr_error(const std::string& msg) { g_err = msg; }  // also used by vjp.cpp
 static Selection builtin(int kind) { return Selection{kind, nullptr, nullptr}; }
 
 extern "C" {

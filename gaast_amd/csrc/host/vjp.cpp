@@ -1,0 +1,430 @@
+// Reverse mode: the vector-Jacobian product of a flat program as another flat program (gaast_program_vjp, gaast_expr.h).
+//
+// eval.rs evaluates in place: the root and every product operand get a buffer of their own (store_in_cache), and every other
+// node adds into the buffer of the one that contains it (add_to_res).  A buffer is therefore built by a sequence of EVENTS --
+// add an input, add a product, flip the sign of some grades (Negation / Reverse / GradeInvolution), apply a scalar op to grade 0
+// (ScalarUnaryOp) -- and a flip or scalar op acts on everything accumulated before it, not only on its own child.  The adjoint
+// walks each buffer's events backwards with the cotangent of that buffer:
+//   input       the cotangent's grades of that input node go to the gradient (zip of the slice lengths, graded.rs:67-78);
+//   product     transposed list -> cotangent of the operand buffers (explicit stays explicit, compact -> GAAST_PROD_ADJ_*);
+//   flip        the same flip of the cotangent (kept as a per-grade sign and folded into the next list's coefficients);
+//   SINV        t = 1/s: ds = -g t t;  SSQRT r = sqrt(s): ds = 0.5 g sinv(r) -- t and r are the buffer's grade 0 right after
+//               the op, recomputed by a node that replays the buffer's events up to it.
+// Buffers are visited from the root down (decreasing node index: a buffer's users come after it in post-order).  The adjoint
+// program is evaluated in place as well, so every cotangent node it builds is ADDITIVE (input, product, or sums of them): adding
+// it into a buffer adds its value.  Sign changes and projections of a cotangent that cannot be folded into a list are explicit
+// products with a constant scalar 1 (slot n_inputs + 1).
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../common/algebra.hpp"
+#include "../common/comp_mul_table.hpp"
+#include "../common/grade_set.hpp"
+#include "gaast_expr.h"
+
+void gaast_set_expr_error(const std::string& msg);
+
+namespace {
+
+using namespace gaast;
+
+struct VjpError {
+    int status;
+    std::string msg;
+};
+
+enum EventKind { EV_INPUT, EV_PRODUCT, EV_FLIP, EV_SCALAR, EV_OPAQUE };
+struct Event {
+    EventKind kind;
+    int node;
+    std::vector<std::pair<int, int>> path;  // (ancestor, which child) from the buffer's node down to `node`
+};
+
+// cotangent of a buffer = sum over terms of flip_sigma(proj_kappa(value of node))
+struct Term {
+    int node;
+    uint64_t sigma;  // grades whose sign is flipped
+    uint64_t kappa;  // grades kept
+};
+
+struct Builder {
+    const gaast_program_desc& d;
+    const int wrt;
+    const int n;
+    std::vector<gaast_node_desc> nodes;
+    std::vector<std::vector<gaast_comp_mul>> lists;  // owned explicit lists (forward nodes keep their pointers)
+    std::vector<char> dep;                           // forward node depends on input `wrt`
+    int one_node = -1, cot_node = -1;
+    double one_value = 1.0;
+
+    Builder(const gaast_program_desc& desc, int slot) : d(desc), wrt(slot), n(desc.vec_space_dim) {}
+
+    int add(gaast_node_desc nd, std::vector<gaast_comp_mul> list = {}) {
+        nodes.push_back(nd);
+        lists.push_back(std::move(list));
+        return int(nodes.size()) - 1;
+    }
+    gaast_node_desc blank(int opcode, uint64_t mask, int dim) const {
+        gaast_node_desc nd{};
+        nd.opcode = opcode;
+        nd.child0 = nd.child1 = -1;
+        nd.minimal_grade_mask = mask;
+        nd.vec_space_dim = dim;
+        nd.input_slot = -1;
+        nd.product_kind = GAAST_PROD_EXPLICIT;
+        return nd;
+    }
+    int one() {
+        if (one_node < 0) {
+            gaast_node_desc nd = blank(GAAST_OP_INPUT, 1ULL, n);
+            nd.input_slot = d.n_inputs + 1;
+            one_node = add(nd);
+        }
+        return one_node;
+    }
+    int explicit_product(int c0, int c1, std::vector<gaast_comp_mul> list, uint64_t mask, int dim) {
+        gaast_node_desc nd = blank(GAAST_OP_PRODUCT, mask, dim);
+        nd.child0 = c0;
+        nd.child1 = c1;
+        nd.n_comp_muls = list.size();
+        return add(nd, std::move(list));
+    }
+    // sum of additive nodes (ADD chain); -1 for none
+    int sum(const std::vector<int>& parts, uint64_t mask, int dim) {
+        if (parts.empty()) return -1;
+        int acc = parts[0];
+        for (size_t i = 1; i < parts.size(); ++i) {
+            gaast_node_desc nd = blank(GAAST_OP_ADD, mask, dim);
+            nd.child0 = acc;
+            nd.child1 = parts[i];
+            acc = add(nd);
+        }
+        return acc;
+    }
+    uint64_t mask_of(int i) const { return nodes[size_t(i)].minimal_grade_mask; }
+
+    // copy of grades `want` of a term, signs applied, as (component) x 1 -> (component); slices zipped to `dim`
+    std::vector<gaast_comp_mul> copy_list(const Term& t, uint64_t want, int dim) const {
+        std::vector<gaast_comp_mul> list;
+        const int tn = nodes[size_t(t.node)].vec_space_dim;
+        for (int k = 0; k < 64; ++k) {
+            if (!((want >> k) & 1ULL)) continue;
+            const uint64_t len = std::min(n_choose_k(uint64_t(tn), uint64_t(k)), n_choose_k(uint64_t(dim), uint64_t(k)));
+            for (uint64_t i = 0; i < len; ++i)
+                list.push_back(gaast_comp_mul{uint32_t(k), uint32_t(i), 0, 0, uint32_t(k), uint32_t(i),
+                                              ((t.sigma >> k) & 1ULL) ? -1.0 : 1.0});
+        }
+        return list;
+    }
+    // the value of a cotangent restricted to `mask`, as one additive node whose minimal mask is within `mask`; -1 when zero
+    int materialize(const std::vector<Term>& terms, uint64_t mask) {
+        if (terms.size() == 1) {
+            const Term& t = terms[0];
+            const uint64_t m = mask_of(t.node);
+            if ((m & ~mask) == 0 && (m & ~t.kappa) == 0 && (m & t.sigma) == 0 && nodes[size_t(t.node)].vec_space_dim == n)
+                return t.node;
+        }
+        std::vector<int> parts;
+        for (const Term& t : terms) {
+            const uint64_t want = mask_of(t.node) & t.kappa & mask;
+            if (want) parts.push_back(explicit_product(t.node, one(), copy_list(t, want, n), mask, n));
+        }
+        return sum(parts, mask, n);
+    }
+
+    void collect(int x, std::vector<std::pair<int, int>>& path, std::vector<Event>& ev) const {
+        const gaast_node_desc& nd = d.nodes[x];
+        if (nd.minimal_grade_mask == 0) return;  // eval.rs:40-43
+        switch (nd.opcode) {
+        case GAAST_OP_INPUT: ev.push_back({EV_INPUT, x, path}); return;
+        case GAAST_OP_PRODUCT: ev.push_back({EV_PRODUCT, x, path}); return;
+        case GAAST_OP_ADD:
+            path.push_back({x, 0});
+            collect(nd.child0, path, ev);
+            path.back().second = 1;
+            collect(nd.child1, path, ev);
+            path.pop_back();
+            return;
+        case GAAST_OP_NEG:
+        case GAAST_OP_REVERSE:
+        case GAAST_OP_GINVOL:
+        case GAAST_OP_SINV:
+        case GAAST_OP_SSQRT:
+        case GAAST_OP_PROJ:
+            path.push_back({x, 0});
+            collect(nd.child0, path, ev);
+            path.pop_back();
+            if (nd.opcode == GAAST_OP_SINV || nd.opcode == GAAST_OP_SSQRT) ev.push_back({EV_SCALAR, x, path});
+            else if (nd.opcode != GAAST_OP_PROJ) ev.push_back({EV_FLIP, x, path});
+            return;
+        default: ev.push_back({EV_OPAQUE, x, path}); return;  // exp / log
+        }
+    }
+    static uint64_t flip_set(const gaast_node_desc& nd) {
+        const uint64_t gs = nd.minimal_grade_mask;
+        if (nd.opcode == GAAST_OP_NEG) return gs;
+        uint64_t m = 0;
+        for (int k = 0; k < 64; ++k) {
+            if (!((gs >> k) & 1ULL)) continue;
+            if (nd.opcode == GAAST_OP_REVERSE ? (k % 4 == 2 || k % 4 == 3) : (k & 1)) m |= 1ULL << k;
+        }
+        return m;
+    }
+    // a node whose evaluation into a fresh buffer of buffer node s replays s's events up to and including event e
+    int replay(int s, const Event& e) {
+        const uint64_t ms = d.nodes[s].minimal_grade_mask;
+        int prefix = e.node;
+        for (size_t i = e.path.size(); i-- > 0;) {
+            const gaast_node_desc& a = d.nodes[e.path[i].first];
+            if (a.opcode == GAAST_OP_ADD && e.path[i].second == 1) {  // the left sibling's events came first
+                gaast_node_desc nd = blank(GAAST_OP_ADD, ms, n);
+                nd.child0 = a.child0;
+                nd.child1 = prefix;
+                prefix = add(nd);
+            }
+        }
+        gaast_node_desc nd = blank(GAAST_OP_PROJ, ms, n);
+        nd.child0 = prefix;
+        return add(nd);
+    }
+
+    // cotangent of a product's operand buffer, from the cotangent of the buffer the product adds into
+    void product_adjoint(int p, const std::vector<Term>& terms, std::vector<std::vector<Term>>& cot) {
+        const gaast_node_desc& pd = d.nodes[p];
+        for (int side = 0; side < 2; ++side) {
+            const int c = side ? pd.child1 : pd.child0, other = side ? pd.child0 : pd.child1;
+            if (!dep[size_t(c)]) continue;
+            const uint64_t cmask = d.nodes[c].minimal_grade_mask;
+            // a geometric product from n = 6 on keeps its adjoint compact even when the forward list is explicit: the plan can then
+            // run it on the dense kernels (the list it would regenerate is the very same, product_kind names it)
+            if (pd.comp_muls && !(pd.product_kind == GAAST_PROD_GEOMETRIC && n >= 6)) {
+                for (const Term& t : terms) {
+                    const uint64_t avail = mask_of(t.node) & t.kappa;
+                    std::vector<gaast_comp_mul> fwd;
+                    fwd.reserve(size_t(pd.n_comp_muls));
+                    for (uint64_t e = 0; e < pd.n_comp_muls; ++e) {
+                        gaast_comp_mul m = pd.comp_muls[e];
+                        if (m.result_grade >= 64 || !((avail >> m.result_grade) & 1ULL)) continue;
+                        if ((t.sigma >> m.result_grade) & 1ULL) m.coeff = -m.coeff;
+                        fwd.push_back(m);
+                    }
+                    if (fwd.empty()) continue;
+                    auto adj = transpose_comp_muls(fwd.data(), fwd.size(), side == 1, false);
+                    const int node = side ? explicit_product(other, t.node, std::move(adj), cmask, n)
+                                          : explicit_product(t.node, other, std::move(adj), cmask, n);
+                    cot[size_t(c)].push_back(Term{node, 0, ~0ULL});
+                }
+            } else {
+                if (pd.product_kind < 0 || pd.product_kind > GAAST_PROD_RCONTRACT)
+                    throw VjpError{GAAST_ERR_INVALID_PROGRAM, "PRODUCT node has neither a comp-mul list nor a product kind"};
+                const int g = materialize(terms, pd.minimal_grade_mask);
+                if (g < 0) continue;
+                gaast_node_desc nd = blank(GAAST_OP_PRODUCT, cmask, n);
+                nd.child0 = g;
+                nd.child1 = other;
+                nd.product_kind = pd.product_kind + (side ? GAAST_PROD_ADJ_RIGHT : GAAST_PROD_ADJ_LEFT);
+                const Selection sel{pd.product_kind, nullptr, nullptr};
+                const uint64_t lmask = side ? mask_of(other) : cmask, rmask = side ? cmask : mask_of(other);
+                nd.n_comp_muls = comp_mul_count(n, iter_contribs(mask_of(g), sel, lmask, rmask));
+                cot[size_t(c)].push_back(Term{add(nd), 0, ~0ULL});
+            }
+        }
+    }
+
+    void scalar_adjoint(int s, const Event& e, std::vector<Term>& terms) {
+        const gaast_node_desc& x = d.nodes[e.node];
+        const int t = replay(s, e);
+        int factor = t;          // SINV: -g t t
+        double c = -1.0;
+        if (x.opcode == GAAST_OP_SSQRT) {  // 0.5 g sinv(r)
+            gaast_node_desc nd = blank(GAAST_OP_SINV, d.nodes[s].minimal_grade_mask, n);
+            nd.child0 = t;
+            factor = add(nd);
+            c = 0.5;
+        }
+        std::vector<int> parts;
+        for (Term& term : terms) {
+            if ((mask_of(term.node) & term.kappa) & 1ULL) {
+                const double sg = (term.sigma & 1ULL) ? -c : c;
+                parts.push_back(explicit_product(term.node, factor, {gaast_comp_mul{0, 0, 0, 0, 0, 0, sg}}, 1ULL, n));
+            }
+            term.kappa &= ~1ULL;
+        }
+        int ds = sum(parts, 1ULL, n);
+        if (ds < 0) return;
+        if (x.opcode == GAAST_OP_SINV) ds = explicit_product(ds, t, {gaast_comp_mul{0, 0, 0, 0, 0, 0, 1.0}}, 1ULL, n);
+        terms.push_back(Term{ds, 0, ~0ULL});
+    }
+
+    int build() {
+        const int nf = d.n_nodes;
+        const gaast_input_desc& in = d.inputs[wrt];
+        const int sd = in.storage_dim;
+        for (int i = 0; i < nf; ++i) add(d.nodes[i]);
+        dep.assign(size_t(nf), 0);
+        for (int i = 0; i < nf; ++i) {
+            const gaast_node_desc& nd = d.nodes[i];
+            if (nd.opcode == GAAST_OP_INPUT) dep[size_t(i)] = nd.input_slot == wrt;
+            else dep[size_t(i)] = dep[size_t(nd.child0)] || (nd.child1 >= 0 && (nd.opcode == GAAST_OP_ADD || nd.opcode == GAAST_OP_PRODUCT) && dep[size_t(nd.child1)]);
+        }
+        std::vector<std::vector<Term>> cot(static_cast<size_t>(nf));
+        std::vector<int> outs;
+        if (dep[size_t(d.root)] && d.nodes[d.root].minimal_grade_mask) {
+            gaast_node_desc nd = blank(GAAST_OP_INPUT, d.nodes[d.root].minimal_grade_mask, n);
+            nd.input_slot = d.n_inputs;
+            cot_node = add(nd);
+            cot[size_t(d.root)].push_back(Term{cot_node, 0, ~0ULL});
+        }
+        for (int s = d.root; s >= 0; --s) {
+            if (cot[size_t(s)].empty()) continue;
+            std::vector<Term> terms = std::move(cot[size_t(s)]);
+            std::vector<Event> ev;
+            std::vector<std::pair<int, int>> path;
+            collect(s, path, ev);
+            std::vector<char> dep_upto(ev.size(), 0);
+            for (size_t i = 0; i < ev.size(); ++i) {
+                const bool self = (ev[i].kind == EV_INPUT || ev[i].kind == EV_PRODUCT || ev[i].kind == EV_OPAQUE) && dep[size_t(ev[i].node)];
+                dep_upto[i] = char(self || (i > 0 && dep_upto[i - 1]));
+            }
+            for (size_t i = ev.size(); i-- > 0;) {
+                if (!dep_upto[i]) break;  // nothing before this point reaches input `wrt`
+                const Event& e = ev[i];
+                const gaast_node_desc& x = d.nodes[e.node];
+                switch (e.kind) {
+                case EV_INPUT: {
+                    if (x.input_slot != wrt) break;
+                    const uint64_t used = x.minimal_grade_mask & in.grade_mask;
+                    for (const Term& t : terms) {
+                        const uint64_t m = mask_of(t.node), want = m & t.kappa & used;
+                        if (!want) continue;
+                        if ((m & ~want) == 0 && (m & t.sigma) == 0 && sd == n && nodes[size_t(t.node)].vec_space_dim == n)
+                            outs.push_back(t.node);
+                        else
+                            outs.push_back(explicit_product(t.node, one(), copy_list(t, want, sd), in.grade_mask, sd));
+                    }
+                    break;
+                }
+                case EV_PRODUCT: product_adjoint(e.node, terms, cot); break;
+                case EV_FLIP: {
+                    const uint64_t f = flip_set(x);
+                    for (Term& t : terms) t.sigma ^= f;
+                    break;
+                }
+                case EV_SCALAR: scalar_adjoint(s, e, terms); break;
+                case EV_OPAQUE:
+                    throw VjpError{GAAST_ERR_UNIMPLEMENTED, "exp / log on the path to the differentiated input has no adjoint"};
+                }
+            }
+        }
+        int root;
+        if (outs.empty()) {  // the input does not reach the root: zero rows (one product that adds 0 * 1 * 1)
+            int k0 = 0;
+            while (k0 < 63 && !((in.grade_mask >> k0) & 1ULL)) ++k0;
+            const int o = one();
+            gaast_node_desc nd = blank(GAAST_OP_PROJ, 0, sd);
+            nd.child0 = o;
+            root = in.grade_mask ? explicit_product(o, o, {gaast_comp_mul{0, 0, 0, 0, uint32_t(k0), 0, 0.0}}, in.grade_mask, sd) : add(nd);
+        } else if (outs.size() == 1) {
+            gaast_node_desc nd = blank(GAAST_OP_PROJ, in.grade_mask, sd);
+            nd.child0 = outs[0];
+            root = (mask_of(outs[0]) == in.grade_mask && nodes[size_t(outs[0])].vec_space_dim == sd) ? outs[0] : add(nd);
+        } else {
+            root = sum(outs, in.grade_mask, sd);
+        }
+        return root;
+    }
+};
+
+}  // namespace
+
+extern "C" int gaast_program_vjp(const gaast_program_desc* desc, int32_t wrt_slot, gaast_program_image_t* out) {
+    if (!desc || !out) {
+        gaast_set_expr_error("null argument");
+        return GAAST_ERR_INVALID_ARGUMENT;
+    }
+    *out = nullptr;
+    const gaast_program_desc& d = *desc;
+    if (d.n_nodes <= 0 || !d.nodes || d.root < 0 || d.root >= d.n_nodes || d.n_inputs < 0 || d.n_inputs > GAAST_MAX_INPUTS ||
+        (d.n_inputs && !d.inputs) || d.vec_space_dim < 0 || d.vec_space_dim > GAAST_MAX_DIM) {
+        gaast_set_expr_error("malformed program description");
+        return GAAST_ERR_INVALID_PROGRAM;
+    }
+    if (wrt_slot < 0 || wrt_slot >= d.n_inputs || d.inputs[wrt_slot].is_const) {
+        gaast_set_expr_error("wrt_slot is out of range or names a const input");
+        return GAAST_ERR_INVALID_ARGUMENT;
+    }
+    if (d.n_inputs + 1 > GAAST_MAX_INPUTS) {
+        gaast_set_expr_error("no input slot is left for the cotangent");
+        return GAAST_ERR_INVALID_ARGUMENT;
+    }
+    if (d.flags & GAAST_FLAG_SPINOR_GEMM) {
+        gaast_set_expr_error("GAAST_FLAG_SPINOR_GEMM programs have no VJP");
+        return GAAST_ERR_UNIMPLEMENTED;
+    }
+    for (int i = 0; i < d.n_nodes; ++i) {
+        const gaast_node_desc& nd = d.nodes[i];
+        const bool two = nd.opcode == GAAST_OP_ADD || nd.opcode == GAAST_OP_PRODUCT;
+        const bool ok = nd.opcode == GAAST_OP_INPUT ? (nd.input_slot >= 0 && nd.input_slot < d.n_inputs)
+                        : (nd.opcode > GAAST_OP_INPUT && nd.opcode <= GAAST_OP_SSQRT && nd.child0 >= 0 && nd.child0 < i &&
+                           (!two || (nd.child1 >= 0 && nd.child1 < i)));
+        if (!ok || (nd.opcode == GAAST_OP_PRODUCT && nd.product_kind >= GAAST_PROD_ADJ_LEFT)) {
+            gaast_set_expr_error("malformed program description (node " + std::to_string(i) + ")");
+            return GAAST_ERR_INVALID_PROGRAM;
+        }
+    }
+    try {
+        Builder b(d, wrt_slot);
+        const int root = b.build();
+        if (b.one_node >= 0 && d.n_inputs + 2 > GAAST_MAX_INPUTS) {
+            gaast_set_expr_error("no input slot is left for the constant 1 of the adjoint");
+            return GAAST_ERR_INVALID_ARGUMENT;
+        }
+        // keep what the root reaches, in post-order
+        std::vector<int> keep(b.nodes.size(), 0), remap(b.nodes.size(), -1);
+        keep[size_t(root)] = 1;
+        for (size_t i = b.nodes.size(); i-- > 0;) {
+            if (!keep[i]) continue;
+            const gaast_node_desc& nd = b.nodes[i];
+            if (nd.child0 >= 0) keep[size_t(nd.child0)] = 1;
+            if (nd.child1 >= 0 && (nd.opcode == GAAST_OP_ADD || nd.opcode == GAAST_OP_PRODUCT)) keep[size_t(nd.child1)] = 1;
+        }
+        std::vector<gaast_node_desc> nodes;
+        for (size_t i = 0; i < b.nodes.size(); ++i) {
+            if (!keep[i]) continue;
+            gaast_node_desc nd = b.nodes[i];
+            if (nd.child0 >= 0) nd.child0 = remap[size_t(nd.child0)];
+            if (nd.child1 >= 0) nd.child1 = (nd.opcode == GAAST_OP_ADD || nd.opcode == GAAST_OP_PRODUCT) ? remap[size_t(nd.child1)] : -1;
+            if (nd.opcode == GAAST_OP_PRODUCT && i >= size_t(d.n_nodes) && nd.product_kind == GAAST_PROD_EXPLICIT)
+                nd.comp_muls = b.lists[i].data();
+            remap[i] = int(nodes.size());
+            nodes.push_back(nd);
+        }
+        std::vector<gaast_input_desc> inputs(d.inputs, d.inputs + d.n_inputs);
+        inputs.push_back(gaast_input_desc{d.nodes[d.root].minimal_grade_mask, d.vec_space_dim, 0, nullptr});
+        if (b.one_node >= 0 && keep[size_t(b.one_node)]) inputs.push_back(gaast_input_desc{1ULL, 0, 1, &b.one_value});
+        gaast_program_desc a = d;
+        a.n_nodes = int(nodes.size());
+        a.nodes = nodes.data();
+        a.root = remap[size_t(root)];
+        a.n_inputs = int(inputs.size());
+        a.inputs = inputs.data();
+        // the image owns copies of every array: round trip through the wire format
+        const size_t len = gaast_program_serialize(&a, nullptr, 0);
+        std::vector<unsigned char> buf(len);
+        gaast_program_serialize(&a, buf.data(), len);
+        *out = gaast_program_deserialize(buf.data(), len);
+        if (!*out) {
+            gaast_set_expr_error("adjoint program could not be encoded");
+            return GAAST_ERR_INVALID_PROGRAM;
+        }
+        return GAAST_OK;
+    } catch (const VjpError& e) {
+        gaast_set_expr_error(e.msg);
+        return e.status;
+    } catch (const std::exception& e) {
+        gaast_set_expr_error(e.what());
+        return GAAST_ERR_INVALID_PROGRAM;
+    }
+}

@@ -149,6 +149,14 @@ class DeviceMV:
         a = np.ascontiguousarray(rows, dtype=_NP[self.dtype])
         _lib.check(_lib.lib().gaast_hip_mv_upload_rows(self._h, a.ctypes.data_as(C.c_void_p), a.size))
 
+    def sum_rows(self, out=None):
+        """gaast_hip_mv_sum_rows: the sum of the batch's rows as a batch-1 DeviceMV (deterministic two-level tree; asynchronous)."""
+        if out is None:
+            out = DeviceMV.alloc(self.dim, GradeSet(self.mask), 1, self.dtype)
+        _lib.check(_lib.lib().gaast_hip_mv_sum_rows(self._h, out._h))
+        out._keep_inputs = [self]
+        return out
+
     def download_rows(self):
         a = np.empty((self.batch, self.row_len), dtype=_NP[self.dtype])
         _lib.check(_lib.lib().gaast_hip_mv_download_rows(self._h, a.ctypes.data_as(C.c_void_p), a.size))

@@ -134,6 +134,22 @@ gaast_program_image_t gaast_program_deserialize(const void *buf, size_t len);
 const gaast_program_desc *gaast_program_image_desc(gaast_program_image_t img);
 void gaast_program_image_free(gaast_program_image_t img);
 
+/* ---- reverse mode ---------------------------------------------------------------------------------
+ * The vector-Jacobian product of a flat program with respect to input `wrt_slot`, as a new flat program (read it with
+ * gaast_program_image_desc, free it with gaast_program_image_free).  It differentiates the program as eval.rs evaluates it,
+ * including the in-place order of a node's operations (a Negation / Reverse / GradeInvolution / scalar op acts on everything
+ * accumulated so far into the buffer of the product operand or root that contains it).
+ * Inputs: slots 0 .. n_inputs - 1 are desc's, unchanged (const ones included); slot n_inputs is the cotangent (grade mask = the
+ * root's minimal mask, storage dimension n, batched); a const scalar 1 may follow at slot n_inputs + 1 (used by sign changes and
+ * projections of a cotangent).  Output: the gradient rows in input wrt_slot's layout (its grade mask and storage dimension), zero
+ * when the input does not reach the root.  An explicit list gets its explicit transposed list; a compact product, and a geometric
+ * product (product_kind GAAST_PROD_GEOMETRIC) at n >= 6 whatever its form, a compact GAAST_PROD_ADJ_LEFT / GAAST_PROD_ADJ_RIGHT node,
+ * which the dense kernels evaluate where they take the forward product.  The adjoint program inherits desc->flags.
+ * Errors: GAAST_ERR_INVALID_ARGUMENT for a wrt_slot out of range or const, or n_inputs + 1 > GAAST_MAX_INPUTS;
+ * GAAST_ERR_UNIMPLEMENTED for exp / log on the path to wrt_slot, or GAAST_FLAG_SPINOR_GEMM;
+ * GAAST_ERR_INVALID_PROGRAM for a malformed desc.  The message is in gaast_expr_last_error(). */
+int gaast_program_vjp(const gaast_program_desc *desc, int32_t wrt_slot, gaast_program_image_t *out);
+
 /* number of input slots the program expects (caller slots + embedded constants) */
 int gaast_spec_num_inputs(gaast_spec_t s);
 int gaast_spec_num_user_inputs(gaast_spec_t s);

@@ -86,7 +86,14 @@ typedef enum gaast_product_kind {
     GAAST_PROD_OUTER = 1,
     GAAST_PROD_INNER = 2,
     GAAST_PROD_LCONTRACT = 3,
-    GAAST_PROD_RCONTRACT = 4
+    GAAST_PROD_RCONTRACT = 4,
+    /* Compact ADJOINT products (reverse mode, gaast_program_vjp in gaast_expr.h): added to a forward kind 0..4, e.g.
+     * GAAST_PROD_ADJ_LEFT + GAAST_PROD_GEOMETRIC.  child0 is the cotangent of the forward product's result, child1 the
+     * other forward operand, and the node's own minimal grade mask that of the differentiated operand.  These three grade
+     * sets regenerate the forward list (specialize.rs:132-183); the library evaluates its transpose: (l, r -> o, c) becomes
+     * (o, r -> l, c) for ADJ_LEFT and (o, l -> r, c) for ADJ_RIGHT, forward order kept, ordered stably by result. */
+    GAAST_PROD_ADJ_LEFT = 8,
+    GAAST_PROD_ADJ_RIGHT = 16
 } gaast_product_kind;
 
 /* IndividualCompMul (base_types.rs:45-55) with Component{grade,index} (algebra.rs:87-91) */
@@ -135,6 +142,11 @@ typedef struct gaast_input_desc {
  * a fused program (n >= 9) is summed by the 64 lanes of a wave in parallel (the row is then read once).  Small programs over
  * batched operands and element-wise arms keep the reference's bits either way. */
 #define GAAST_FLAG_EXACT_ORDER 0x4u
+/* Reverse-mode programs (gaast_hip_program_create_vjp below) follow the same rule.  Default mode: an adjoint list is summed like
+ * any forward list (slices with fused multiply-adds on long rows, contraction over shared operands), within the bound above of the
+ * exactly rounded sum.  With EXACT_ORDER every adjoint list sums in the transposed table's order (result rows in ascending
+ * component order, entries in forward order) with three roundings per term: the bits are the same on every run.  There are no
+ * reference bits to match: the reference has no gradients. */
 #define GAAST_FLAG_NO_MFMA 0x8u        /* dense products stay on the vector-FMA kernel (A/B testing) */
 #define GAAST_FLAG_NO_JIT 0x10u        /* small programs run on the LDS interpreter kernel, not on hiprtc-specialised code */
 /* OPT-IN, not the reference's algorithm: dense geometric products of a non-degenerate algebra (f32:
@@ -302,6 +314,23 @@ int gaast_hip_gather_rows(gaast_hip_mv_t local, gaast_hip_mv_t gathered, const i
 int gaast_hip_eval_gather(gaast_hip_program_t prog, const gaast_hip_mv_t *inputs, int n_inputs,
                           gaast_hip_mv_t out, gaast_hip_mv_t gathered, const int64_t *counts, int root,
                           int n_chunks);
+
+/* ---- reverse mode ------------------------------------------------------------------------------ */
+/* gaast_program_vjp (gaast_expr.h) followed by gaast_hip_program_create.  Bind slots 0 .. desc->n_inputs - 1 as for the forward
+ * program and the cotangent (root grade mask, dimension n, one row per item) at slot desc->n_inputs; gaast_hip_eval writes the
+ * gradient rows of input `wrt_slot` (its grade mask and storage dimension).  Batch-1 inputs are shared as usual; the gradient of a
+ * shared input is then one row per item, to be summed with gaast_hip_mv_sum_rows.  Programs created with
+ * GAAST_FLAG_SPINOR_GEMM or through gaast_hip_program_create_in_basis have no VJP: GAAST_ERR_UNIMPLEMENTED. */
+int gaast_hip_program_create_vjp(const gaast_program_desc *desc, int32_t wrt_slot, gaast_hip_program_t *out);
+/* out(0) = sum over the B rows of `in` (out: batch 1, same dimension, grade mask and dtype; B >= 1).  Deterministic: rows are
+ * summed in index order within chunks of GAAST_SUM_ROWS_CHUNK rows, then the chunk partials in chunk order, so the bits depend
+ * on B and the data only.  Sums accumulate in the dtype (f32 in f32): |result - exact| <= (GAAST_SUM_ROWS_CHUNK - 1 + ceil(B /
+ * GAAST_SUM_ROWS_CHUNK)) eps sum_i |x_i| per component, to first order.  No atomics; the partials live in library scratch, one
+ * buffer per stream (B > GAAST_SUM_ROWS_CHUNK), grown on first use with a larger row count after synchronising that stream -- so
+ * the first such call on a stream must not be inside a stream capture.  in and out must not overlap.  Asynchronous on the library
+ * stream. */
+#define GAAST_SUM_ROWS_CHUNK 1024
+int gaast_hip_mv_sum_rows(gaast_hip_mv_t in, gaast_hip_mv_t out);
 
 #ifdef __cplusplus
 }

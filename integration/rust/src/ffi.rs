@@ -107,6 +107,9 @@ extern "C" {
     pub fn gaast_hip_mv_upload(m: Mv, grade: c_int, host: *const c_void, count: i64) -> c_int;
     pub fn gaast_hip_mv_download(m: Mv, grade: c_int, host: *mut c_void, count: i64) -> c_int;
     pub fn gaast_hip_eval(p: Program, inputs: *const Mv, n_inputs: c_int, batch: i64, out: Mv) -> c_int;
+    // reverse mode: the VJP of a program w.r.t. one input slot (cotangent at slot n_inputs), and the sum of a batch's rows
+    pub fn gaast_hip_program_create_vjp(desc: *const GaastProgramDesc, wrt_slot: i32, out: *mut Program) -> c_int;
+    pub fn gaast_hip_mv_sum_rows(input: Mv, out: Mv) -> c_int;
     // multi-GPU (one process per GPU): the gather of result rows over RCCL, see include/gaast_hip.h
     /// which shared object provides the nccl* entry points (NULL = the system's librccl); before the first comm call
     pub fn gaast_hip_comm_set_library(path: *const std::os::raw::c_char) -> c_int;
