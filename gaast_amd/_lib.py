@@ -88,6 +88,7 @@ SIGNATURES = {
     "gaast_hip_program_output_info": (_ci, [_vp, C.POINTER(_u64), C.POINTER(_i64)]),
     "gaast_hip_program_num_launches": (_ci, [_vp]),
     "gaast_hip_program_launch_name": (C.c_char_p, [_vp, _ci]),
+    "gaast_hip_program_launch_variant": (_ci, [_vp, _ci]),
     "gaast_hip_mv_alloc": (_ci, [_ci, _u64, _i64, _ci, C.POINTER(_vp)]),
     "gaast_hip_mv_wrap": (_ci, [_vp, _ci, _u64, _i64, _ci, _i64, C.POINTER(_vp)]),
     "gaast_hip_mv_free": (_ci, [_vp]),

@@ -298,6 +298,12 @@ class SpecializedAst:
         return [_lib.lib().gaast_hip_program_launch_name(p, i).decode()
                 for i in range(_lib.lib().gaast_hip_program_num_launches(p))]
 
+    def launch_variants(self):
+        """Per launch, the index into its kernel table that the most recent evaluation took (gaast_hip_program_launch_variant):
+        the "0|1|2" of a launch name, decided from the bound rows' pointers and strides; -1 before any evaluation."""
+        p = self.program()
+        return [_lib.lib().gaast_hip_program_launch_variant(p, i) for i in range(_lib.lib().gaast_hip_program_num_launches(p))]
+
     def eval_batch(self, inputs=(), batch=1, out=None):
         """One evaluation per batch item.  inputs[slot]: DeviceMV (batch items, or 1 = shared),
         a [batch, row_len] array, or None for unused slots.  Returns the output DeviceMV."""
@@ -382,6 +388,11 @@ class Vjp:
         p = self.program()
         return [_lib.lib().gaast_hip_program_launch_name(p, i).decode()
                 for i in range(_lib.lib().gaast_hip_program_num_launches(p))]
+
+    def launch_variants(self):
+        """As SpecializedAst.launch_variants, for the reverse-mode program."""
+        p = self.program()
+        return [_lib.lib().gaast_hip_program_launch_variant(p, i) for i in range(_lib.lib().gaast_hip_program_num_launches(p))]
 
     def eval_batch(self, inputs, cotangent, batch, reduce=False, out=None):
         """Gradient rows of input `slot` for each item (inputs as for SpecializedAst.eval_batch, cotangent: [batch, root row]

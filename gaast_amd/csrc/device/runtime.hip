@@ -184,6 +184,9 @@ struct Launch {
     // arithmetic outweighs its bytes (run_jit -- in practice: operands shared by all items)
     JitKernel jit, jit_fma;
     std::string label;   // what the step is, then WHICH HIP kernel runs it (the name rocprofv3 reports)
+    // index into kern[] (REDUCE_SCALE: 1 = wave kernel; jit: 1 = jit_fma) the most recent evaluation launched: host-side record
+    // for gaast_hip_program_launch_variant, -1 before any evaluation
+    mutable int variant = -1;
 };
 
 struct MvFree {
@@ -687,6 +690,7 @@ int run_step(const Launch& L, const Bound& res, const Bound& a, const Bound& b, 
             using KernW = void (*)(ReduceScaleArgs<T>, const uint32_t*);
             int64_t blocks = (batch + 3) / 4;
             blocks = std::min<int64_t>(blocks, int64_t(g_num_cu) * 8);
+            L.variant = 1;
             hipLaunchKernelGGL(reinterpret_cast<KernW>(const_cast<void*>(L.kern[1])), dim3(unsigned(blocks)), dim3(256), 0, g_stream, q,
                                L.u32_c.as<uint32_t>());
             break;
@@ -803,6 +807,7 @@ int run_step(const Launch& L, const Bound& res, const Bound& a, const Bound& b, 
             while (l2 > 0 && (int64_t(1) << l2) > batch) --l2;
             using KernE = void (*)(EllArgs<T>);
             const int64_t blocks = (batch + (int64_t(1) << l2) - 1) >> l2;
+            L.variant = l2;
             hipLaunchKernelGGL(reinterpret_cast<KernE>(const_cast<void*>(L.kern[l2])), dim3(unsigned(blocks)), dim3(256),
                                L.lds << l2, g_stream, q);
             break;
@@ -865,6 +870,7 @@ int run_step(const Launch& L, const Bound& res, const Bound& a, const Bound& b, 
             };
             const bool fast = L.kern[1] && s.left_full && s.right_full && s.out_full && !s.beta && q.left_len == 4096 && q.right_len == 4096 &&
                               aligned16(a.ptr, a.stride) && aligned16(b.ptr, b.stride) && aligned16(res.ptr, res.stride);
+            L.variant = fast ? 1 : 0;
             hipLaunchKernelGGL(reinterpret_cast<KernS>(const_cast<void*>(L.kern[fast ? 1 : 0])), dim3(unsigned(blocks)),
                                dim3(unsigned(L.threads)), L.lds, g_stream, q);
             break;
@@ -937,7 +943,8 @@ int run_step(const Launch& L, const Bound& res, const Bound& a, const Bound& b, 
                                           : (s.use_mfma16 && L.kern[1] && p.right_contig && p.right_full && !s.scaled &&
                                              (s.chained ? true : (p.left_contig && p.left_full)));
         const bool whole_rows = prefetch && L.kern[2] && s.out_full && !s.beta;   // k_gp_mfma16x4: straight-line result stores
-        hipLaunchKernelGGL(reinterpret_cast<KernD>(const_cast<void*>(L.kern[whole_rows ? 2 : prefetch ? 1 : 0])), dim3(unsigned(blocks)),
+        L.variant = whole_rows ? 2 : prefetch ? 1 : 0;
+        hipLaunchKernelGGL(reinterpret_cast<KernD>(const_cast<void*>(L.kern[L.variant])), dim3(unsigned(blocks)),
                            dim3(unsigned(L.threads)), L.lds, g_stream, p);
         break;
     }
@@ -1029,6 +1036,7 @@ int run_jit(const Launch& L, const Plan& plan, const std::vector<Bound>& in_boun
         }
         if (shared && arithmetic_bound(s.n_entries, bytes)) fn = L.jit_fma.fn;
     }
+    L.variant = fn == L.jit.fn ? 0 : 1;
     HIP_TRY(hipModuleLaunchKernel(fn, blocks, 1, 1, threads, 1, 1, 0, g_stream, args.data(), nullptr));
     return GAAST_OK;
 }
@@ -1657,6 +1665,10 @@ const char* gaast_hip_program_launch_name(gaast_hip_program_t prog, int i) {
     if (!prog || i < 0 || i >= int(prog->launches.size())) return "";
     return prog->launches[size_t(i)].label.c_str();
 }
+int gaast_hip_program_launch_variant(gaast_hip_program_t prog, int i) {
+    if (!prog || i < 0 || i >= int(prog->launches.size())) return -1;
+    return prog->launches[size_t(i)].variant;
+}
 
 int gaast_hip_mv_alloc(int dim, uint64_t grade_mask, int64_t batch, int dtype, gaast_hip_mv_t* out) {
     if (!out || dim < 0 || dim > GAAST_MAX_DIM || batch < 0 || (dtype != GAAST_F64 && dtype != GAAST_F32))
@@ -1669,6 +1681,9 @@ int gaast_hip_mv_wrap(void* device_ptr, int dim, uint64_t grade_mask, int64_t ba
                       int64_t row_stride, gaast_hip_mv_t* out) {
     if (!out || dim < 0 || dim > GAAST_MAX_DIM || batch < 0 || (dtype != GAAST_F64 && dtype != GAAST_F32))
         return set_err(GAAST_ERR_INVALID_ARGUMENT, "bad mv_wrap argument");
+    // every kernel addresses the rows as elements: a base that is not a multiple of the element size cannot be one
+    if (reinterpret_cast<uintptr_t>(device_ptr) % dtype_size(dtype) != 0)
+        return set_err(GAAST_ERR_INVALID_ARGUMENT, "mv_wrap: device_ptr is not aligned to the element size");
     auto* m = new gaast_hip_mv_s;
     m->layout = make_layout(dim, grade_mask);
     if (row_stride < m->layout.row_len && !(batch <= 1)) {
@@ -1857,6 +1872,7 @@ int run_launches(gaast_hip_program_t prog, const std::vector<Bound>& in_bound0, 
     for (const Launch& L : prog->launches) {
         const Step& s = L.s;
         Layout lres, la, lb;
+        L.variant = 0;   // a launch with one kernel; run_step / run_jit record which of several they took
         if (s.kind == Step::LINMAP) {   // the caller's rows in, the caller's rows out
             Bound src, dst;
             int64_t items = count;

@@ -201,6 +201,15 @@ int gaast_hip_program_output_info(gaast_hip_program_t prog, uint64_t *grade_mask
 /* number of kernel launches one eval issues, and a one-line description of launch `i` */
 int gaast_hip_program_num_launches(gaast_hip_program_t prog);
 const char *gaast_hip_program_launch_name(gaast_hip_program_t prog, int i);
+/* Which of launch `i`'s kernels the most recent gaast_hip_eval of `prog` ran: the index into the launch's kernel table (the
+ * alternatives its launch name lists as "0|1|2": picked at launch from the pointers and row strides of the bound rows; a
+ * specialised program: 1 for its contracted build).  REDUCE_SCALE: 1 for k_reduce_scale_wave, 0 for k_reduce_scale.  0 for a
+ * launch with a single kernel; negative before any evaluation and for a bad index.  Written on the host when the launch is
+ * issued: forms chosen inside a kernel (gaast_jit, gaast_chain, k_linmap_small, k_sum_rows) are not visible here.  An
+ * evaluation that is cut into item ranges (gaast_hip_eval_gather's chunks) issues every launch once per range, each with the
+ * rows' base moved by first * stride -- which can change the alignment when the stride is not a multiple of 16 bytes: the value
+ * is that of the LAST range.  Like every call on a program, to be made from the thread that drives it. */
+int gaast_hip_program_launch_variant(gaast_hip_program_t prog, int i);
 /* GAAST_FLAG_EXP_LOG extension: how many items, since the last call, had an exp / log operand outside the domain (a
  * k-vector whose square is not scalar: |<B B>_{not 0}|^2 > 2^-40 (sum B_i^2)^2); their results are the closed form applied
  * to <B B>_0 regardless.  Synchronises the library stream; resets the counter.  0 for programs without exp / log. */
@@ -211,7 +220,9 @@ const char *gaast_hip_program_jit_source(gaast_hip_program_t prog);
 /* ---- GradedDataMut on the device (graded.rs:51-79) ------------------------------------- */
 /* init_null_mv(dim, gs) for `batch` items: zero-filled rows (graded.rs:195-201). */
 int gaast_hip_mv_alloc(int dim, uint64_t grade_mask, int64_t batch, int dtype, gaast_hip_mv_t *out);
-/* Same layout over caller-owned device memory (e.g. a torch tensor); row_stride in elements. */
+/* Same layout over caller-owned device memory (e.g. a torch tensor); row_stride in elements.  device_ptr must be a multiple of
+ * the element size (GAAST_ERR_INVALID_ARGUMENT otherwise, nothing is created); any further alignment only decides which row
+ * I/O form of a kernel runs. */
 int gaast_hip_mv_wrap(void *device_ptr, int dim, uint64_t grade_mask, int64_t batch, int dtype,
                       int64_t row_stride, gaast_hip_mv_t *out);
 int gaast_hip_mv_free(gaast_hip_mv_t mv);

@@ -102,6 +102,8 @@ extern "C" {
     pub fn gaast_hip_program_destroy(p: Program) -> c_int;
     pub fn gaast_hip_program_output_info(p: Program, mask: *mut u64, row_len: *mut i64) -> c_int;
     pub fn gaast_hip_program_domain_errors(p: Program, count: *mut i64) -> c_int;
+    /// index into launch `i`'s kernel table that the most recent evaluation took (negative: none yet / bad index)
+    pub fn gaast_hip_program_launch_variant(p: Program, i: c_int) -> c_int;
     pub fn gaast_hip_mv_alloc(dim: c_int, mask: u64, batch: i64, dtype: c_int, out: *mut Mv) -> c_int;
     pub fn gaast_hip_mv_free(m: Mv) -> c_int;
     pub fn gaast_hip_mv_upload(m: Mv, grade: c_int, host: *const c_void, count: i64) -> c_int;

@@ -203,6 +203,30 @@ def abs_terms_bound(n, A_bits, B_bits, metric=None):
     return np.abs(wht(wht(A_bits * w) * wht(B_bits * w)) / N) / w
 
 
+# ---- outermorphisms on the host (numpy compounds): the reference of the linmap tests -----------------------------------------------
+def linmap_compound(m, k):
+    """C_k(M): the k-th compound of the n x n matrix m (gaast_compound_matrix, host code)"""
+    import ctypes as C
+    PD = C.POINTER(C.c_double)
+    n = m.shape[0]
+    d = n_choose_k(n, k)
+    out = np.zeros((d, d))
+    m = np.ascontiguousarray(m, dtype=np.float64)
+    assert ga.lib().gaast_compound_matrix(n, m.ctypes.data_as(PD), k, out.ctypes.data_as(PD)) == 0
+    return out
+
+
+def linmap_host_apply(m, grades, rows):
+    """every grade slice of every row times its compound, in float64"""
+    n = m.shape[0]
+    out, pos = np.empty_like(rows, dtype=np.float64), 0
+    for k in sorted(grades):
+        d = n_choose_k(n, k)
+        out[:, pos:pos + d] = rows[:, pos:pos + d].astype(np.float64) @ linmap_compound(m, k).T
+        pos += d
+    return out
+
+
 # ---- C hosts and the test transport (tests/cpp) ---------------------------------------------------------------------
 def build_c_host(name, out_dir):
     """gcc a plain C host of the ABI (tests/cpp/<name>.c) against include/gaast_hip.h and libgaast_hip.so"""

@@ -6,29 +6,11 @@ import pytest
 
 import gaast_amd as ga
 from clifford_gram import blades_of_grade
+from helpers import linmap_host_apply as host_apply
 
 pytestmark = pytest.mark.gpu
 PD = C.POINTER(C.c_double)
 NP = {ga.F32: np.float32, ga.F64: np.float64}
-
-
-def compound(m, k):
-    n = m.shape[0]
-    d = len(blades_of_grade(n, k))
-    out = np.zeros((d, d))
-    m = np.ascontiguousarray(m, dtype=np.float64)
-    assert ga.lib().gaast_compound_matrix(n, m.ctypes.data_as(PD), k, out.ctypes.data_as(PD)) == 0
-    return out
-
-
-def host_apply(m, grades, rows):
-    n = m.shape[0]
-    out, pos = np.empty_like(rows, dtype=np.float64), 0
-    for k in sorted(grades):
-        d = len(blades_of_grade(n, k))
-        out[:, pos:pos + d] = rows[:, pos:pos + d].astype(np.float64) @ compound(m, k).T
-        pos += d
-    return out
 
 
 def check(n, grades, batch, dtype, seed, orthogonal=False):
