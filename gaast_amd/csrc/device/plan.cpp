@@ -105,7 +105,7 @@ struct Lowering {
         if (!offsets_of(res, mask, offs)) return;
         if (offs.empty()) return;
         Step& s = emit(Step::FLIP, res, std::string("negate_grades[") + what + "]");
-        s.u32_a = std::move(offs);
+        s.flip_offsets = std::move(offs);
         touch(res);
     }
 
@@ -151,7 +151,7 @@ struct Lowering {
             if (covers) removed[size_t(fr->second)] = 1;
             Step& s = emit(Step::AXPY, res, std::string(covers ? "copy_grades_from" : "add_grades_from") + "[input " + std::to_string(nd.input_slot) + "]");
             s.a = BufRef{BufKind::INPUT, nd.input_slot};
-            s.u32_a = std::move(map);
+            s.axpy_map = std::move(map);
             s.beta = covers ? 0 : 1;
             touch(res);
             return;
@@ -248,17 +248,17 @@ struct Lowering {
         }
         const int64_t m = la.grade_len(k);
         Step st;   // filled before emit(): emit invalidates references into plan.steps
-        st.explog_op = is_exp ? 0 : 1;
-        st.explog_m = int(m);
-        st.explog_arg_k = int(la.offset(k));
-        st.explog_arg_0 = (!is_exp && (la.mask & 1ULL) && la.grade_len(0) > 0) ? int(la.offset(0)) : -1;
+        st.explog.op = is_exp ? 0 : 1;
+        st.explog.m = int(m);
+        st.explog.arg_k = int(la.offset(k));
+        st.explog.arg_0 = (!is_exp && (la.mask & 1ULL) && la.grade_len(0) > 0) ? int(la.offset(0)) : -1;
         const uint64_t mine = nd.minimal_grade_mask;
         if (is_exp && (mine & 1ULL)) {
             if (!(lr.mask & 1ULL)) {
                 fail(GAAST_ERR_MISSING_GRADE, "grade 0 absent from result buffer");
                 return;
             }
-            st.explog_res_0 = int(lr.offset(0));
+            st.explog.res_0 = int(lr.offset(0));
         }
         // (exp of a bare scalar, k = 0: both statements land in grade 0, cosh|a| + (sinh|a| / |a|) a = e^a, as in the oracle)
         if ((mine >> k) & 1ULL) {
@@ -266,15 +266,15 @@ struct Lowering {
                 fail(GAAST_ERR_MISSING_GRADE, "grade " + std::to_string(k) + " absent from result buffer");
                 return;
             }
-            st.explog_res_k = int(lr.offset(k));
-            st.explog_mres = int(std::min<int64_t>(lr.grade_len(k), m));
+            st.explog.res_k = int(lr.offset(k));
+            st.explog.mres = int(std::min<int64_t>(lr.grade_len(k), m));
         }
         // blade squares, and the pairs of commuting blades (the non-scalar part of B B) grouped by product blade
         std::vector<uint32_t> blade(static_cast<size_t>(m));
         for (int64_t i = 0; i < m; ++i) blade[size_t(i)] = bt.blade_of[size_t(k)][size_t(i)];
-        st.coeff.resize(size_t(m));
+        st.explog.sq.resize(size_t(m));
         for (int64_t i = 0; i < m; ++i)
-            st.coeff[size_t(i)] = blades_gp_coeff(d.vec_space_dim, d.metric_diag, blade[size_t(i)], blade[size_t(i)]);
+            st.explog.sq[size_t(i)] = blades_gp_coeff(d.vec_space_dim, d.metric_diag, blade[size_t(i)], blade[size_t(i)]);
         bool structurally_scalar = true;   // every pair of distinct grade-k blades anticommutes
         for (int64_t i = 0; i < m && structurally_scalar; ++i)
             for (int64_t j = i + 1; j < m; ++j)
@@ -282,7 +282,7 @@ struct Lowering {
                     structurally_scalar = false;
                     break;
                 }
-        st.u32_a.assign(1, 0u);
+        st.explog.row_start.assign(1, 0u);
         if (!structurally_scalar) {
             if (m > 512) {
                 if (plan.unsupported.empty())
@@ -298,14 +298,14 @@ struct Lowering {
                 }
             for (auto& kv : rows) {
                 for (auto& e : kv.second) {
-                    st.u32_c.push_back(e.first);
-                    st.coeff_b.push_back(e.second);
+                    st.explog.pairs.push_back(e.first);
+                    st.explog.pair_coeff.push_back(e.second);
                 }
-                st.u32_a.push_back(uint32_t(st.u32_c.size()));
+                st.explog.row_start.push_back(uint32_t(st.explog.pairs.size()));
             }
         }
         Step& s = emit(Step::EXPLOG, res, std::string(is_exp ? "exponential" : "logarithm") + "[grade " + std::to_string(k) + ", " +
-                                              std::to_string(m) + " components, " + std::to_string(st.u32_c.size()) + " domain-check pairs]");
+                                              std::to_string(m) + " components, " + std::to_string(st.explog.pairs.size()) + " domain-check pairs]");
         const BufRef keep_res = s.res;
         const std::string keep_name = s.name;
         s = std::move(st);
@@ -495,50 +495,50 @@ struct Lowering {
         return true;
     }
 
-    // which dense kernel (0 = none, 1 = k_gp_dense, 3 = k_gp_mfma32 / k_gp_mfma32p, 4 = k_gp_mfma16x4<T>, 5 = k_gp_mfma7<T>, 6 = k_gp_mfma6<T>), in which algebra
-    // (frame) and in which basis of it (perm)
-    int dense_kind_for(const DenseFrame& f, uint64_t n_comp_muls, std::vector<int>& perm) const {
+    // which dense kernel family (false: none), in which algebra (frame) and in which basis of it (perm)
+    bool dense_family_for(const DenseFrame& f, uint64_t n_comp_muls, std::vector<int>& perm, DenseFamily& fam) const {
         const int n = f.n;
-        if (n < 6 || n > 14) return 0;  // small algebras: the exact kernel is HBM-bound anyway
+        auto take = [&](DenseFamily x) { fam = x; return true; };
+        if (n < 6 || n > 14) return false;  // small algebras: the exact kernel is HBM-bound anyway
         // A general diagonal metric (algebra.rs:148-165 multiplies by ANY base_vec_dot, :79-81) runs in the rescaled basis
         // f_i = e_i / sqrt|g_i|; it needs finite, well-scaled factors, else the list kernels keep the product
-        if (!dense_scales_ok(f)) return 0;
-        if (double(n_comp_muls) * 8.0 < double(uint64_t(1) << (2 * n))) return 0;  // the tiled kernels always do 4^n multiply-adds
+        if (!dense_scales_ok(f)) return false;
+        if (double(n_comp_muls) * 8.0 < double(uint64_t(1) << (2 * n))) return false;  // the tiled kernels always do 4^n multiply-adds
         const bool mfma_ok = plan.dtype == GAAST_F32 && !(plan.flags & GAAST_FLAG_NO_MFMA);
         // matrix-core variants: f32, n >= 10 (32 result columns per wave, five lo vectors) / n = 8, 9 (lo = 4 bits)
-        if (mfma_ok && n >= 10 && dense_basis_permutation(f, 5, false, perm)) return 3;
-        if (n == 14) return 0;          // both operands of an item (128 KiB in f32) fit the LDS of the matrix-core kernel only
-        if (mfma_ok && (n == 8 || n == 9) && dense_basis_permutation(f, 4, false, perm)) return 4;   // k_gp_mfma16x4<float>
+        // (k_gp_mfma32p: +A, -A, +B, -B images; n = 14 does not fit and runs on k_gp_mfma32)
+        if (mfma_ok && n >= 10 && dense_basis_permutation(f, 5, false, perm)) return take(n <= 13 ? DenseFamily::MFMA32P : DenseFamily::MFMA32);
+        if (n == 14) return false;      // both operands of an item (128 KiB in f32) fit the LDS of the matrix-core kernel only
+        if (mfma_ok && (n == 8 || n == 9) && dense_basis_permutation(f, 4, false, perm)) return take(DenseFamily::MFMA16X4);   // k_gp_mfma16x4<float>
         // f64 (the reference's value type), n = 8 ... 12: v_mfma_f64_16x16x4_f64, one item per workgroup
         if (plan.dtype == GAAST_F64 && !(plan.flags & GAAST_FLAG_NO_MFMA) && n >= 8 && n <= 12 &&
             dense_basis_permutation(f, 4, false, perm))
-            return 4;
+            return take(DenseFamily::MFMA16X4);
         // n = 7, both value types: one wave per item on the 16x16x4 instructions (lo = 3 bits: three non-null vectors)
-        if (n == 7 && !(plan.flags & GAAST_FLAG_NO_MFMA) && dense_basis_permutation(f, 3, false, perm)) return 5;
+        if (n == 7 && !(plan.flags & GAAST_FLAG_NO_MFMA) && dense_basis_permutation(f, 3, false, perm)) return take(DenseFamily::MFMA7);
         // n = 6, both value types: four 16x16x4 instructions per item, ANY +-1 / 0 metric in the basis as it stands (signs and
         // vanishing terms are slots of the operand images and bits of the accumulators: no lo vectors, no permutation)
-        if (n == 6 && !(plan.flags & GAAST_FLAG_NO_MFMA) && dense_basis_permutation(f, 0, false, perm)) return 6;
-        if (dense_basis_permutation(f, 4, true, perm)) return 1;
-        return 0;
+        if (n == 6 && !(plan.flags & GAAST_FLAG_NO_MFMA) && dense_basis_permutation(f, 0, false, perm)) return take(DenseFamily::MFMA6);
+        if (dense_basis_permutation(f, 4, true, perm)) return take(DenseFamily::VECTOR_FMA);
+        return false;
     }
-    int dense_choice(const gaast_node_desc& nd, BufRef res, BufRef l, BufRef r, std::vector<int>& perm, DenseFrame& frame) const {
-        if (plan.flags & (GAAST_FLAG_EXACT_ORDER | GAAST_FLAG_NO_FUSION)) return 0;
+    bool dense_choice(const gaast_node_desc& nd, BufRef res, BufRef l, BufRef r, std::vector<int>& perm, DenseFrame& frame, DenseFamily& fam) const {
+        if (plan.flags & (GAAST_FLAG_EXACT_ORDER | GAAST_FLAG_NO_FUSION)) return false;
         const int n = d.vec_space_dim;
-        if (n < 6 || n > 15) return 0;
-        if (layout(res).dim != n || layout(l).dim != n || layout(r).dim != n) return 0;
+        if (n < 6 || n > 15) return false;
+        if (layout(res).dim != n || layout(l).dim != n || layout(r).dim != n) return false;
         if (nd.product_kind >= GAAST_PROD_ADJ_LEFT) {
             // adjoint of a geometric product: a forward product in the metric m' (1 / m off the null
             // vectors, 0 on them) of relabelled / re-signed / rescaled operands, always in the full frame
-            if ((nd.product_kind & 7) != GAAST_PROD_GEOMETRIC || n > 14) return 0;
+            if ((nd.product_kind & 7) != GAAST_PROD_GEOMETRIC || n > 14) return false;
             DenseFrame f;
             f.n = n;
             for (int i = 0; i < n; ++i) f.metric.push_back(d.metric_diag[i] == 0.0 ? 0.0 : 1.0 / d.metric_diag[i]);
-            const int kind = dense_kind_for(f, nd.n_comp_muls, perm);
-            if (kind) frame = f;
-            return kind;
+            const bool found = dense_family_for(f, nd.n_comp_muls, perm, fam);
+            if (found) frame = f;
+            return found;
         }
         const uint64_t lmask = node(nd.child0).minimal_grade_mask & layout(l).mask, rmask = node(nd.child1).minimal_grade_mask & layout(r).mask;
-        int kind = 0;
         bool geometric_known = false, geometric = false;
         auto is_gp = [&]() {
             if (!geometric_known) {
@@ -548,18 +548,18 @@ struct Lowering {
             return geometric;
         };
         DenseFrame reduced;
-        if (parity_reduced_frame(lmask, rmask, reduced) && (kind = dense_kind_for(reduced, nd.n_comp_muls, perm)) && is_gp()) {
+        if (parity_reduced_frame(lmask, rmask, reduced) && dense_family_for(reduced, nd.n_comp_muls, perm, fam) && is_gp()) {
             frame = reduced;
-            return kind;
+            return true;
         }
         DenseFrame full;
         full.n = n;
         full.metric.assign(d.metric_diag, d.metric_diag + n);
-        if (n <= 14 && (kind = dense_kind_for(full, nd.n_comp_muls, perm)) && is_gp()) {
+        if (n <= 14 && dense_family_for(full, nd.n_comp_muls, perm, fam) && is_gp()) {
             frame = full;
-            return kind;
+            return true;
         }
-        return 0;
+        return false;
     }
 
     // opt-in matrix-representation kernels: f32, n = 7..12 (odd n as the subalgebra of n + 1), every
@@ -635,7 +635,8 @@ struct Lowering {
             s.canon_b = canon_r;
             s.beta = beta0 ? 0 : 1;
             s.n_entries = nd.n_comp_muls;
-            s.use_spinor = m;
+            s.dense.family = DenseFamily::SPINOR;
+            s.dense.spinor_m = m;
             {
                 // D*D 16-bit table entries indexed by row offset, two per word (format: SpinorArgs);
                 // one real plane per operand: indices in the basis of spinor_basis.hpp
@@ -647,8 +648,8 @@ struct Lowering {
                     if (px == 0 && __builtin_popcount(pz) == 1 && (pk & 1u)) lam |= pz;
                 }
                 const SpinorBasis sb = choose_spinor_basis(m, alpha, lam);
-                s.spinor_lam_bit = sb.lam_bit;
-                s.spinor_has_alpha = sb.has_alpha ? 1 : 0;
+                s.dense.spinor_lam_bit = sb.lam_bit;
+                s.dense.spinor_has_alpha = sb.has_alpha ? 1 : 0;
                 auto build1 = [&](const Layout& lay, uint64_t want, uint64_t flip, int role, std::vector<uint32_t>& packed, int* full) {
                     // operands: bit 0 = negate, bits [14:2] = x'*LD + z'; result: bit 0 = negate, bit 1 = nothing
                     // to store, bits [15:2] = x'*LD + z'
@@ -674,9 +675,9 @@ struct Lowering {
                     packed.resize(map.size() / 2);
                     std::memcpy(packed.data(), map.data(), map.size() * sizeof(uint16_t));
                 };
-                build1(ll, lmin & ll.mask, flip_l, 0, s.u32_a, &s.left_full);
-                build1(lrr, rmin & lrr.mask, flip_r, 1, s.u32_b, &s.right_full);
-                build1(lr, omin, 0, 2, s.u32_c, &s.out_full);
+                build1(ll, lmin & ll.mask, flip_l, 0, s.dense.left_map, &s.dense.left_full);
+                build1(lrr, rmin & lrr.mask, flip_r, 1, s.dense.right_map, &s.dense.right_full);
+                build1(lr, omin, 0, 2, s.dense.spinor_out_map, &s.dense.out_full);
                 s.name = "product_spinor_gemm[gp n=" + std::to_string(n) + " lam=" + std::to_string(sb.lam_bit) + "]";
                 touch(res);
                 return;
@@ -684,7 +685,8 @@ struct Lowering {
         }
         std::vector<int> perm;
         DenseFrame frame;
-        if (const int dense_kind = dense_choice(nd, res, l, r, perm, frame)) {
+        DenseFamily fam = DenseFamily::VECTOR_FMA;
+        if (dense_choice(nd, res, l, r, perm, frame, fam)) {
             if ((omin & lr.mask) != omin) {
                 fail(GAAST_ERR_MISSING_GRADE, "product result grade absent from result buffer");
                 return;
@@ -732,14 +734,10 @@ struct Lowering {
             s.canon_b = swap_ops ? canon_l : canon_r;
             s.beta = beta0 ? 0 : 1;
             s.n_entries = nd.n_comp_muls;
-            s.dense_n = n2;
-            s.use_mfma = dense_kind == 3;
-            s.use_mfma16 = dense_kind == 4;
-            s.use_mfma16d = dense_kind == 4;
-            s.use_mfma7 = dense_kind == 5;
-            s.use_mfma6 = dense_kind == 6;
-            s.mfma16_quads = dense_kind == 4 && plan.dtype == GAAST_F32;   // k_gp_mfma16x4<float>: B words in 16-byte quads
-            s.mfma32_pairs = dense_kind == 3 && n2 <= 13;   // k_gp_mfma32p: +A, -A, +B, -B images (n = 14 does not fit)
+            Step::Dense& ds = s.dense;   // (no step is emitted below: the reference stays valid)
+            ds.n = n2;
+            ds.family = fam;
+            ds.mfma16_quads = fam == DenseFamily::MFMA16X4 && plan.dtype == GAAST_F32;   // k_gp_mfma16x4<float>: B words in 16-byte quads
             // blade R of the frame's basis <-> blade R' of its permuted basis, f_R = sign(R) f'_R' (the parity of the
             // inversions of the new positions of R's vectors taken in ascending original order)
             std::vector<int> inv(size_t(n2), 0);
@@ -855,16 +853,25 @@ struct Lowering {
                         const long double factor = fa * f1 * blade_scale(frame, R);
                         uint32_t neg = uint32_t((flip >> k) & 1ULL) ^ blade_sign[R] ^ (factor < 0.0L ? 1u : 0u);
                         // image-pair kernels: the b_hi part of (-1)^(|a_hi| |b_lo|), |a_hi| = |b_hi| + |c_hi| (mod 2), lives in the B image
-                        if (s.use_mfma16 && right) neg ^= uint32_t(__builtin_popcount(blade >> 4) & __builtin_popcount(blade & 15u) & 1);
-                        if (s.mfma32_pairs && right) neg ^= uint32_t(__builtin_popcount(blade >> 5) & __builtin_popcount(blade & 31u) & 1);
-                        if (s.use_mfma7 && right) neg ^= uint32_t(__builtin_popcount((blade >> 3) & 7u) & __builtin_popcount(blade & 7u) & 1);
+                        uint32_t pos = blade;   // the A images of the matrix-core kernels; k_gp_mfma6 derives its image slots from the blade itself
+                        switch (fam) {
+                        case DenseFamily::MFMA16X4:
+                            if (right) neg ^= uint32_t(__builtin_popcount(blade >> 4) & __builtin_popcount(blade & 15u) & 1);
+                            if (right) pos = ds.mfma16_quads ? mfma16q_b_pos(blade) : mfma16d_b_pos(blade);
+                            break;
+                        case DenseFamily::MFMA32P:
+                            if (right) neg ^= uint32_t(__builtin_popcount(blade >> 5) & __builtin_popcount(blade & 31u) & 1);
+                            if (right) pos = mfma32p_b_pos(blade);
+                            break;
+                        case DenseFamily::MFMA32: if (right) pos = mfma_b_pos(blade); break;
+                        case DenseFamily::MFMA7:
+                            if (right) neg ^= uint32_t(__builtin_popcount((blade >> 3) & 7u) & __builtin_popcount(blade & 7u) & 1);
+                            pos = right ? mfma7_b_pos(blade) : mfma7_a_pos(blade);
+                            break;
+                        case DenseFamily::MFMA6: break;
+                        default: pos = vec_pos(blade); break;
+                        }
                         const uint32_t sgn = neg ? 0x80000000u : 0u;
-                        const uint32_t pos = s.use_mfma6 ? blade   // k_gp_mfma6 derives its image slots from the blade itself
-                                             : s.use_mfma7 ? (right ? mfma7_b_pos(blade) : mfma7_a_pos(blade))
-                                             : s.mfma32_pairs ? (right ? mfma32p_b_pos(blade) : blade)
-                                             : s.use_mfma ? (right ? mfma_b_pos(blade) : blade)
-                                             : s.mfma16_quads ? (right ? mfma16q_b_pos(blade) : blade)
-                                             : s.use_mfma16d ? (right ? mfma16d_b_pos(blade) : blade) : vec_pos(blade);
                         const uint32_t off = uint32_t(lay.offset(k) + i);
                         seq = seq && off == map.size();
                         map.push_back(off | (pos << 16) | sgn);
@@ -873,7 +880,7 @@ struct Lowering {
                 }
                 *full = map.size() == (size_t(1) << n2);
                 *contig = seq && map.size() % 4 == 0 && !map.empty();
-                if (s.use_mfma6 && *full) {
+                if (fam == DenseFamily::MFMA6 && *full) {
                     // k_gp_mfma6: lane q moves the component of entry q into its four image slots.  Entries are dealt to lanes so
                     // that the lanes sharing an LDS cycle of a store hit different banks (row order: 73 % of the LDS cycles were
                     // conflicts, profiles/r04_gp6f32_pmc_first_version.csv).  blade = (top2 | hi2 | lo2) = (u, ah, al) / (v, bh, bl):
@@ -900,7 +907,7 @@ struct Lowering {
                     scale.swap(s2);
                     *contig = 0;
                 }
-                if (s.use_mfma7 && *full) {
+                if (fam == DenseFamily::MFMA7 && *full) {
                     // k_gp_mfma7 moves ONE component per lane and load (entry q = load * 64 + lane), so the entries can be dealt
                     // to lanes by LDS bank: the lanes that share an LDS cycle of a store (f32: 32 lanes, bank = position mod 32;
                     // f64: 16 lanes of 8 bytes, position mod 16) get components of different banks -- every residue holds
@@ -925,11 +932,11 @@ struct Lowering {
                     }
                 }
             };
-            build_map(kla, kwa, kfa, false, s.u32_a, s.coeff, &s.left_full, &s.left_contig);
-            build_map(klb, kwb, kfb, true, s.u32_b, s.coeff_b, &s.right_full, &s.right_contig);
-            // out_map: indexed by the blade of the frame's permuted basis; offset | sign << 30, or -1; coeff_c: |factor|
-            s.i32_a.assign(size_t(1) << n2, -1);
-            s.coeff_c.assign(size_t(1) << n2, 1.0);
+            build_map(kla, kwa, kfa, false, ds.left_map, ds.left_scale, &ds.left_full, &ds.left_contig);
+            build_map(klb, kwb, kfb, true, ds.right_map, ds.right_scale, &ds.right_full, &ds.right_contig);
+            // out_map: indexed by the blade of the frame's permuted basis; offset | sign << 30, or -1; out_scale: |factor|
+            ds.out_map.assign(size_t(1) << n2, -1);
+            ds.out_scale.assign(size_t(1) << n2, 1.0);
             for (uint32_t m = 0; m < (1u << n); ++m) {
                 const int g = __builtin_popcount(m);
                 if (!((prod_mask >> g) & 1ULL)) continue;
@@ -937,39 +944,40 @@ struct Lowering {
                 const uint32_t R = result_from_frame(adj ? (m ^ adj_z) : m, &f1);
                 const long double factor = f1 / blade_scale(frame, R);
                 const uint32_t sgn = blade_sign[R] ^ (factor < 0.0L ? 1u : 0u);
-                s.i32_a[new_blade[R]] = int32_t(uint32_t(lr.offset(g) + bt.index_of[m]) | (sgn << 30));
-                s.coeff_c[new_blade[R]] = double(fabsl(factor));
+                ds.out_map[new_blade[R]] = int32_t(uint32_t(lr.offset(g) + bt.index_of[m]) | (sgn << 30));
+                ds.out_scale[new_blade[R]] = double(fabsl(factor));
             }
             // scale tables only when some factor is not 1 (a general metric): +-1 / 0 metrics keep the register-prefetch paths
-            s.scaled = 0;
-            for (const std::vector<double>* v : {&s.coeff, &s.coeff_b, &s.coeff_c})
-                for (double x : *v) s.scaled |= int(x != 1.0);
-            if (!s.scaled) {
-                s.coeff.clear();
-                s.coeff_b.clear();
-                s.coeff_c.clear();
+            ds.scaled = 0;
+            for (const std::vector<double>* v : {&ds.left_scale, &ds.right_scale, &ds.out_scale})
+                for (double x : *v) ds.scaled |= int(x != 1.0);
+            if (!ds.scaled) {
+                ds.left_scale.clear();
+                ds.right_scale.clear();
+                ds.out_scale.clear();
             }
             // every blade produced into a row that holds nothing else: whole rows can be written in 16-byte pieces
-            s.out_full = lr.row_len == (int64_t(1) << n2);
-            for (uint32_t m = 0; m < (1u << n2); ++m) s.out_full = s.out_full && s.i32_a[m] >= 0;
-            for (uint32_t w : s.u32_a) s.left_signs |= int(w >> 31);
-            for (int32_t w : s.i32_a) s.out_signs |= int(w >= 0 && (uint32_t(w) & 0x40000000u));
-            const int lo_bits = s.use_mfma ? 5 : s.use_mfma7 ? 3 : s.use_mfma6 ? 0 : 4;
+            ds.out_full = lr.row_len == (int64_t(1) << n2);
+            for (uint32_t m = 0; m < (1u << n2); ++m) ds.out_full = ds.out_full && ds.out_map[m] >= 0;
+            for (uint32_t w : ds.left_map) ds.left_signs |= int(w >> 31);
+            for (int32_t w : ds.out_map) ds.out_signs |= int(w >= 0 && (uint32_t(w) & 0x40000000u));
+            const bool mfma32 = fam == DenseFamily::MFMA32 || fam == DenseFamily::MFMA32P;
+            const int lo_bits = mfma32 ? 5 : fam == DenseFamily::MFMA7 ? 3 : fam == DenseFamily::MFMA6 ? 0 : 4;
             for (int j = 0; j < n2; ++j) {
                 const double g = frame.metric[size_t(perm[size_t(j)])];   // only its sign matters here: the magnitude is in the scales
                 if (j < lo_bits) {
-                    if (g < 0.0) s.neg_lo |= 1u << j;
+                    if (g < 0.0) ds.neg_lo |= 1u << j;
                 } else {
-                    if (g < 0.0) s.neg_hi |= 1u << (j - lo_bits);
-                    if (g == 0.0) s.zero_hi |= 1u << (j - lo_bits);
+                    if (g < 0.0) ds.neg_hi |= 1u << (j - lo_bits);
+                    if (g == 0.0) ds.zero_hi |= 1u << (j - lo_bits);
                 }
             }
-            s.neg_lo_all = dense_kind == 1 && s.neg_lo == 15u;
-            s.degenerate = s.zero_hi != 0;
+            ds.neg_lo_all = fam == DenseFamily::VECTOR_FMA && ds.neg_lo == 15u;
+            ds.degenerate = ds.zero_hi != 0;
             static const char* const par_name[2] = {"even", "odd"};
-            s.name = std::string(dense_kind == 1 ? "product_dense" : "product_dense_mfma") + "[gp n=" + std::to_string(n) +
+            s.name = std::string(fam == DenseFamily::VECTOR_FMA ? "product_dense" : "product_dense_mfma") + "[gp n=" + std::to_string(n) +
                      (reduced ? std::string(" ") + par_name[frame.lpar] + " x " + par_name[frame.rpar] + " in Cl(" + std::to_string(n2) + ")" : std::string()) +
-                     (identity ? "" : " permuted basis") + (s.scaled ? " rescaled basis" : "") +
+                     (identity ? "" : " permuted basis") + (ds.scaled ? " rescaled basis" : "") +
                      (adj == GAAST_PROD_ADJ_LEFT ? " adjoint left" : adj ? " adjoint right" : "") + "]";
             touch(res);
             return;
@@ -1068,20 +1076,20 @@ struct Lowering {
         s.canon_b = canon_r;
         s.beta = beta0 ? 0 : 1;
         s.n_entries = n_muls;
-        s.u32_a.assign(row_out.size() + 1, 0);
-        for (size_t i = 0; i < counts.size(); ++i) s.u32_a[i + 1] = s.u32_a[i] + counts[i];
-        s.u32_b = row_out;
-        s.u32_c.resize(size_t(n_muls));
-        s.coeff.resize(size_t(n_muls));
-        std::vector<uint32_t> cursor(s.u32_a.begin(), s.u32_a.end() - 1);
+        s.list.row_start.assign(row_out.size() + 1, 0);
+        for (size_t i = 0; i < counts.size(); ++i) s.list.row_start[i + 1] = s.list.row_start[i] + counts[i];
+        s.list.row_out = row_out;
+        s.list.entries.resize(size_t(n_muls));
+        s.list.coeff.resize(size_t(n_muls));
+        std::vector<uint32_t> cursor(s.list.row_start.begin(), s.list.row_start.end() - 1);
         for (uint64_t e = 0; e < n_muls; ++e) {  // stable: keeps the reference order per output
             const gaast_comp_mul& m = muls[e];
             const uint32_t pos = cursor[size_t(row_of[eo[size_t(e)]])]++;
             const uint32_t lo = uint32_t(ll.offset(int(m.left_grade)) + m.left_index);
             const uint32_t ro = uint32_t(lrr.offset(int(m.right_grade)) + m.right_index);
-            s.u32_c[pos] = lo | (ro << 16);
+            s.list.entries[pos] = lo | (ro << 16);
             const bool neg = (((flip_l >> m.left_grade) ^ (flip_r >> m.right_grade)) & 1ULL) != 0;
-            s.coeff[pos] = neg ? -m.coeff : m.coeff;
+            s.list.coeff[pos] = neg ? -m.coeff : m.coeff;
         }
         touch(res);
     }
@@ -1120,16 +1128,16 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
         if (plan.input_layouts[i].row_len == 0) continue;
         if (in_axpy[i]) {
             in_base[i] = cursor;
-            f.fused_inputs.push_back({int(i), cursor, 0});
+            f.fused.inputs.push_back({int(i), cursor, 0});
             cursor += int(plan.input_layouts[i].row_len);
         }
         if (in_direct[i]) {
             in_base_canon[i] = cursor;
-            f.fused_inputs.push_back({int(i), cursor, 1});
+            f.fused.inputs.push_back({int(i), cursor, 1});
             cursor += int(plan.input_layouts[i].row_len);
         }
     }
-    if (f.fused_inputs.size() > size_t(uop::MAX_INPUTS)) return false;
+    if (f.fused.inputs.size() > size_t(uop::MAX_INPUTS)) return false;
     for (size_t i = 0; i < plan.node_buffers.size(); ++i) {
         node_base[i] = cursor;
         cursor += int(plan.node_buffers[i].row_len);
@@ -1176,9 +1184,9 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
     // Product never read what another row of the same Product writes.
     constexpr int G = uop::GROUPS;
     constexpr uint32_t LW = 32;                   // words per line
-    std::vector<uint32_t>& prog = f.u32_a;        // 32-word lines, see kernels.hip.hpp
-    std::vector<uint32_t>& phase_tab = f.u32_b;   // per (phase, wave): first line, line count
-    std::vector<double>& general = f.coeff;
+    std::vector<uint32_t>& prog = f.fused.prog;        // 32-word lines, see kernels.hip.hpp
+    std::vector<uint32_t>& phase_tab = f.fused.phase_tab;   // per (phase, wave): first line, line count
+    std::vector<double>& general = f.fused.general;
     uint64_t entries = 0;
     const uint32_t esz = uint32_t(elem);
     auto mop = [](uint32_t code, uint32_t lo, uint32_t mid = 0) { return (code << 28) | (mid << 12) | lo; };
@@ -1213,11 +1221,11 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
             break;
         }
         case Step::AXPY:
-            for (uint32_t m : s.u32_a) misc.push_back(mop(s.beta ? uop::ADD : uop::COPY, rb + (m & 0xffffu), uint32_t(base_of(s.a)) + (m >> 16)));   // (COPY: the zero fill folded in)
+            for (uint32_t m : s.axpy_map) misc.push_back(mop(s.beta ? uop::ADD : uop::COPY, rb + (m & 0xffffu), uint32_t(base_of(s.a)) + (m >> 16)));   // (COPY: the zero fill folded in)
             push_misc(misc);
             break;
         case Step::FLIP:
-            for (uint32_t o : s.u32_a) misc.push_back(mop(uop::NEG, rb + o));
+            for (uint32_t o : s.flip_offsets) misc.push_back(mop(uop::NEG, rb + o));
             push_misc(misc);
             break;
         case Step::SUNARY:
@@ -1226,14 +1234,14 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
             break;
         case Step::PRODUCT_CSR: {
             const uint32_t lb = uint32_t(base_of(s.a, s.canon_a)), rrb = uint32_t(base_of(s.b, s.canon_b));
-            for (size_t row = 0; row + 1 < s.u32_a.size(); ++row) {
-                const uint32_t dst = rb + s.u32_b[row];
-                const uint32_t e0 = s.u32_a[row], e1 = s.u32_a[row + 1];
+            for (size_t row = 0; row + 1 < s.list.row_start.size(); ++row) {
+                const uint32_t dst = rb + s.list.row_out[row];
+                const uint32_t e0 = s.list.row_start[row], e1 = s.list.row_start[row + 1];
                 const int g = least();
                 std::vector<uint32_t>& out = glines[size_t(g)];
                 load[size_t(g)] += (e1 - e0) + 2;
                 bool row_general = false;
-                for (uint32_t e = e0; e < e1; ++e) row_general |= (s.coeff[e] != 1.0 && s.coeff[e] != -1.0);
+                for (uint32_t e = e0; e < e1; ++e) row_general |= (s.list.coeff[e] != 1.0 && s.list.coeff[e] != -1.0);
                 // split long rows evenly over their lines (16 entries -> 8 + 8, not 10 + 6)
                 const uint32_t n_l = e1 > e0 ? (e1 - e0 + 9) / 10 : 1;
                 const uint32_t per = e1 > e0 ? (e1 - e0 + n_l - 1) / n_l : 0;
@@ -1248,8 +1256,8 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
                     out.resize(line0 + LW, 0u);
                     out[line0] = hdr;
                     for (uint32_t k = 0; k < cnt; ++k) {
-                        const double c = s.coeff[e + k];
-                        const uint32_t lo = lb + (s.u32_c[e + k] & 0xffffu), ro = rrb + (s.u32_c[e + k] >> 16);
+                        const double c = s.list.coeff[e + k];
+                        const uint32_t lo = lb + (s.list.entries[e + k] & 0xffffu), ro = rrb + (s.list.entries[e + k] >> 16);
                         if (!row_general) {
                             out[line0 + 2 + 3 * k] = lo * esz;
                             out[line0 + 3 + 3 * k] = ro * esz;
@@ -1297,7 +1305,7 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
     // constants, the statements are the reference's in the reference's order; the runtime
     // compiles it with -ffp-contract=off so that the roundings stay those of eval.rs:82.
     if (!interp_ok && entries > 8192) return false;
-    f.fused_jit_only = interp_ok ? 0 : 1;
+    f.fused.jit_only = interp_ok ? 0 : 1;
     if (jit_allowed && entries <= 8192) {
         std::string src;
         char buf[256];
@@ -1326,16 +1334,16 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
         // (160 KiB / 16 = 10 KiB per wave); the result rows reuse the operands' space.  Operands left out (and rows
         // too long for the budget) are read by their lanes directly.
         const size_t lds_budget = (plan.flags & GAAST_FLAG_DEBUG_LDS_12K) ? 12 * 1024 + 256 : 10 * 1024;
-        std::vector<int> lds_off(f.fused_inputs.size(), -1);
+        std::vector<int> lds_off(f.fused.inputs.size(), -1);
         size_t lds_in = 0;
         {
-            std::vector<size_t> order(f.fused_inputs.size());
+            std::vector<size_t> order(f.fused.inputs.size());
             for (size_t i = 0; i < order.size(); ++i) order[i] = i;
             std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) {
-                return plan.input_layouts[size_t(f.fused_inputs[x].slot)].row_len > plan.input_layouts[size_t(f.fused_inputs[y].slot)].row_len;
+                return plan.input_layouts[size_t(f.fused.inputs[x].slot)].row_len > plan.input_layouts[size_t(f.fused.inputs[y].slot)].row_len;
             });
             for (size_t i : order) {
-                const size_t need = size_t(64) * size_t(padded_len(int(plan.input_layouts[size_t(f.fused_inputs[i].slot)].row_len))) * esz;
+                const size_t need = size_t(64) * size_t(padded_len(int(plan.input_layouts[size_t(f.fused.inputs[i].slot)].row_len))) * esz;
                 if (lds_in + need > lds_budget) continue;
                 lds_off[i] = int(lds_in);
                 lds_in += need;
@@ -1352,10 +1360,10 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
         // (programs with big slabs are register-bound: the transposition's temporaries would spill -- measured on full R^6
         // f32 products, 193 elements: 1.93 -> 1.30 TB/s -- so they keep the row-per-lane form)
         auto line_ok = [&](int len) { return slab <= 128 && size_t(len) * esz >= 128 && (size_t(len) * esz) % 16 == 0; };
-        std::vector<char> by_line(f.fused_inputs.size(), 0);
+        std::vector<char> by_line(f.fused.inputs.size(), 0);
         bool any_line = false;
-        for (size_t i = 0; i < f.fused_inputs.size(); ++i)
-            if (lds_off[i] < 0 && line_ok(int(plan.input_layouts[size_t(f.fused_inputs[i].slot)].row_len))) by_line[i] = 1, any_line = true;
+        for (size_t i = 0; i < f.fused.inputs.size(); ++i)
+            if (lds_off[i] < 0 && line_ok(int(plan.input_layouts[size_t(f.fused.inputs[i].slot)].row_len))) by_line[i] = 1, any_line = true;
         const bool out_by_line = !out_via_lds && line_ok(out_len);
         any_line = any_line || out_by_line;
         const size_t line_bytes = any_line ? size_t(64) * 144 : 0;
@@ -1371,7 +1379,7 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
         src += std::string("typedef ") + ty + " T;\n";
         src += std::string("typedef ") + ty + " VT __attribute__((ext_vector_type(" + std::to_string(epc) + ")));\n";
         src += "extern \"C\" __global__ __launch_bounds__(" + std::to_string(threads) + ") void gaast_jit(";
-        for (size_t i = 0; i < f.fused_inputs.size(); ++i)
+        for (size_t i = 0; i < f.fused.inputs.size(); ++i)
             src += "const T* __restrict__ in" + std::to_string(i) + ", long long s" + std::to_string(i) + ", ";
         src += std::string("T* __restrict__ out, long long so, long long batch") + (plan.has_explog ? ", unsigned long long* dom" : "") + ") {\n";
         if (coalesce) {
@@ -1382,8 +1390,8 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
             src += "  const long long item = blockIdx.x * 256LL + threadIdx.x;\n  if (item >= batch) return;\n";
         }
         for (int i = 0; i < slab; ++i) src += "  T " + var(uint32_t(i)) + " = 0;\n";
-        for (size_t i = 0; i < f.fused_inputs.size(); ++i) {
-            const Step::FusedInput& fi = f.fused_inputs[i];
+        for (size_t i = 0; i < f.fused.inputs.size(); ++i) {
+            const Step::FusedInput& fi = f.fused.inputs[i];
             const int len = int(plan.input_layouts[size_t(fi.slot)].row_len);
             const std::string I = std::to_string(i);
             auto assign = [&](const std::string& from_prefix, const std::string& indent) {
@@ -1473,13 +1481,13 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
                 for (int64_t o = 0; o < layout_of(s.res).row_len; ++o) src += "  " + var(rb + uint32_t(o)) + " = T(0);\n";
                 break;
             case Step::AXPY:
-                for (uint32_t m : s.u32_a) {
+                for (uint32_t m : s.axpy_map) {
                     const std::string d = var(rb + (m & 0xffffu));
                     src += "  " + d + " = " + (s.beta ? d : std::string("T(0)")) + " + " + var(uint32_t(base_of(s.a)) + (m >> 16)) + ";\n";
                 }
                 break;
             case Step::FLIP:
-                for (uint32_t o : s.u32_a) src += "  " + var(rb + o) + " = -" + var(rb + o) + ";\n";
+                for (uint32_t o : s.flip_offsets) src += "  " + var(rb + o) + " = -" + var(rb + o) + ";\n";
                 break;
             case Step::SUNARY: {
                 const std::string d = var(rb + uint32_t(s.sunary_off));
@@ -1493,38 +1501,38 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
                 const uint32_t ab = uint32_t(base_of(s.a));
                 const bool f32 = plan.dtype == GAAST_F32;
                 auto fn = [&](const char* name) { return std::string(name) + (f32 ? "f" : ""); };
-                auto B = [&](uint32_t i) { return var(ab + uint32_t(s.explog_arg_k) + i); };
+                auto B = [&](uint32_t i) { return var(ab + uint32_t(s.explog.arg_k) + i); };
                 src += "  { T sq = T(0), nrm = T(0), viol = T(0);\n";
-                for (int i = 0; i < s.explog_m; ++i) {
-                    src += "    sq = sq + " + B(uint32_t(i)) + " * " + B(uint32_t(i)) + " * T(" + lit(s.coeff[size_t(i)]) + ");\n";
+                for (int i = 0; i < s.explog.m; ++i) {
+                    src += "    sq = sq + " + B(uint32_t(i)) + " * " + B(uint32_t(i)) + " * T(" + lit(s.explog.sq[size_t(i)]) + ");\n";
                     src += "    nrm = nrm + " + B(uint32_t(i)) + " * " + B(uint32_t(i)) + ";\n";
                 }
-                for (size_t row = 0; row + 1 < s.u32_a.size(); ++row) {
+                for (size_t row = 0; row + 1 < s.explog.row_start.size(); ++row) {
                     src += "    { T acc = T(0);\n";
-                    for (uint32_t e = s.u32_a[row]; e < s.u32_a[row + 1]; ++e)
-                        src += "      acc = acc + " + B(s.u32_c[e] & 0xffffu) + " * " + B(s.u32_c[e] >> 16) + " * T(" + lit(s.coeff_b[e]) + ");\n";
+                    for (uint32_t e = s.explog.row_start[row]; e < s.explog.row_start[row + 1]; ++e)
+                        src += "      acc = acc + " + B(s.explog.pairs[e] & 0xffffu) + " * " + B(s.explog.pairs[e] >> 16) + " * T(" + lit(s.explog.pair_coeff[e]) + ");\n";
                     src += "      viol = viol + acc * acc; }\n";
                 }
-                if (s.u32_a.size() > 1)
+                if (s.explog.row_start.size() > 1)
                     src += std::string("    if (viol > T(") + lit(9.094947017729282e-13) + ") * (nrm * nrm)) atomicAdd(dom, 1ull);\n";
                 src += "    T c0 = T(0), f;\n";
-                if (s.explog_op == 0) {
+                if (s.explog.op == 0) {
                     src += "    if (sq < T(0)) { const T t = " + fn("sqrt") + "(-sq); c0 = " + fn("cos") + "(t); f = " + fn("sin") + "(t) / t; }\n";
                     src += "    else if (sq > T(0)) { const T t = " + fn("sqrt") + "(sq); c0 = " + fn("cosh") + "(t); f = " + fn("sinh") + "(t) / t; }\n";
                     src += "    else if (sq == T(0)) { c0 = T(1); f = T(1); }\n    else { c0 = sq; f = sq; }\n";
                 } else {
-                    const std::string a = s.explog_arg_0 >= 0 ? var(ab + uint32_t(s.explog_arg_0)) : std::string("T(0)");
+                    const std::string a = s.explog.arg_0 >= 0 ? var(ab + uint32_t(s.explog.arg_0)) : std::string("T(0)");
                     src += "    if (sq < T(0)) { const T mm = " + fn("sqrt") + "(-sq); f = " + fn("atan2") + "(mm, " + a + ") / mm; }\n";
                     src += "    else if (sq > T(0)) { const T mm = " + fn("sqrt") + "(sq); f = " + fn("atanh") + "(mm / " + a + ") / mm; }\n";
                     src += "    else if (sq == T(0)) { f = T(1) / " + a + "; }\n    else { f = sq; }\n";
                 }
-                if (s.explog_res_0 >= 0) {
-                    const std::string d = var(rb + uint32_t(s.explog_res_0));
+                if (s.explog.res_0 >= 0) {
+                    const std::string d = var(rb + uint32_t(s.explog.res_0));
                     src += "    " + d + " = " + d + " + c0;\n";
                 }
-                if (s.explog_res_k >= 0)
-                    for (int i = 0; i < s.explog_mres; ++i) {
-                        const std::string d = var(rb + uint32_t(s.explog_res_k) + uint32_t(i));
+                if (s.explog.res_k >= 0)
+                    for (int i = 0; i < s.explog.mres; ++i) {
+                        const std::string d = var(rb + uint32_t(s.explog.res_k) + uint32_t(i));
                         src += "    " + d + " = " + d + " + f * " + B(uint32_t(i)) + ";\n";
                     }
                 src += "  }\n";
@@ -1532,12 +1540,12 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
             }
             case Step::PRODUCT_CSR: {
                 const uint32_t lb = uint32_t(base_of(s.a, s.canon_a)), rrb = uint32_t(base_of(s.b, s.canon_b));
-                for (size_t row = 0; row + 1 < s.u32_a.size(); ++row) {
-                    const std::string d = var(rb + s.u32_b[row]);
+                for (size_t row = 0; row + 1 < s.list.row_start.size(); ++row) {
+                    const std::string d = var(rb + s.list.row_out[row]);
                     src += "  { T acc = " + (s.beta ? d : std::string("T(0)")) + ";\n";
-                    for (uint32_t e = s.u32_a[row]; e < s.u32_a[row + 1]; ++e) {
-                        const std::string prod = "(" + var(lb + (s.u32_c[e] & 0xffffu)) + " * " + var(rrb + (s.u32_c[e] >> 16)) + ")";
-                        const double c = s.coeff[e];
+                    for (uint32_t e = s.list.row_start[row]; e < s.list.row_start[row + 1]; ++e) {
+                        const std::string prod = "(" + var(lb + (s.list.entries[e] & 0xffffu)) + " * " + var(rrb + (s.list.entries[e] >> 16)) + ")";
+                        const double c = s.list.coeff[e];
                         if (c == 1.0)
                             src += "    acc = acc + " + prod + ";\n";
                         else if (c == -1.0)
@@ -1611,9 +1619,9 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
             src += "  }\n";
         }
         src += "}\n";
-        f.jit_threads = threads;
-        f.jit_source = std::move(src);
-        f.jit_reg_trial = slab > jit_slab_small;
+        f.fused.jit_threads = threads;
+        f.fused.jit_source = std::move(src);
+        f.fused.jit_reg_trial = slab > jit_slab_small;
     } else if (!(plan.flags & GAAST_FLAG_NO_JIT) && interp_ok && !plan.has_explog && entries <= 2048 &&
                size_t(slab | 1) * elem * 64 + 64 <= kLdsBytes) {
         // ---- MEDIUM programs (round 4): the slab is beyond the registers of the specialised kernel above (160 / 200 elements) but the
@@ -1635,7 +1643,7 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
         auto at = [&](uint32_t i) { return "my[" + std::to_string(i) + "]"; };
         src += std::string("typedef ") + ty + " T;\n";
         src += "extern \"C\" __global__ __launch_bounds__(512) void gaast_jit(";
-        for (size_t i = 0; i < f.fused_inputs.size(); ++i)
+        for (size_t i = 0; i < f.fused.inputs.size(); ++i)
             src += "const T* __restrict__ in" + std::to_string(i) + ", long long s" + std::to_string(i) + ", ";
         src += "T* __restrict__ out, long long so, long long batch) {\n";
         src += "  __shared__ T slab[" + std::to_string(64 * stride) + "];\n";
@@ -1649,8 +1657,8 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
         src += std::string("  typedef T VT __attribute__((ext_vector_type(") + std::to_string(epc) + ")));\n";
         std::string fast_cond = "true";
         int total_chunks_per_thread = 0;
-        for (size_t i = 0; i < f.fused_inputs.size(); ++i) {
-            const int len = int(plan.input_layouts[size_t(f.fused_inputs[i].slot)].row_len);
+        for (size_t i = 0; i < f.fused.inputs.size(); ++i) {
+            const int len = int(plan.input_layouts[size_t(f.fused.inputs[i].slot)].row_len);
             const std::string I = std::to_string(i);
             fast_cond += " && s" + I + " == " + std::to_string(len) + " && (((unsigned long long)in" + I + ") & 15ull) == 0";
             if ((64 * len) % epc) fast_cond += " && false";
@@ -1659,14 +1667,14 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
         if (total_chunks_per_thread > 24) fast_cond = "false";
         src += "  const bool fast = " + fast_cond + ";\n";
         src += "  const long long groups = (batch + 63) / 64;\n";
-        for (size_t i = 0; i < f.fused_inputs.size(); ++i) {
-            const int len = int(plan.input_layouts[size_t(f.fused_inputs[i].slot)].row_len);
+        for (size_t i = 0; i < f.fused.inputs.size(); ++i) {
+            const int len = int(plan.input_layouts[size_t(f.fused.inputs[i].slot)].row_len);
             const int nch = 64 * len / epc, cpt = std::max(1, (nch + 511) / 512);
             src += "  VT r" + std::to_string(i) + "[" + std::to_string(cpt) + "];\n";
         }
         src += "  auto issue = [&](long long item0) {\n";
-        for (size_t i = 0; i < f.fused_inputs.size(); ++i) {
-            const int len = int(plan.input_layouts[size_t(f.fused_inputs[i].slot)].row_len);
+        for (size_t i = 0; i < f.fused.inputs.size(); ++i) {
+            const int len = int(plan.input_layouts[size_t(f.fused.inputs[i].slot)].row_len);
             const int nch = 64 * len / epc, cpt = (nch + 511) / 512;
             const std::string I = std::to_string(i);
             src += "    { const VT* src = (const VT*)(in" + I + " + item0 * " + std::to_string(len) + ");\n";
@@ -1677,8 +1685,8 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
         }
         src += "  };\n";
         src += "  auto commit = [&]() {\n";
-        for (size_t i = 0; i < f.fused_inputs.size(); ++i) {
-            const Step::FusedInput& fi = f.fused_inputs[i];
+        for (size_t i = 0; i < f.fused.inputs.size(); ++i) {
+            const Step::FusedInput& fi = f.fused.inputs[i];
             const int len = int(plan.input_layouts[size_t(fi.slot)].row_len);
             const int nch = 64 * len / epc, cpt = (nch + 511) / 512;
             const std::string I = std::to_string(i), L = std::to_string(len);
@@ -1693,8 +1701,8 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
         }
         src += "  };\n";
         src += "  auto stage = [&](long long item0, int nitems) {\n";
-        for (size_t i = 0; i < f.fused_inputs.size(); ++i) {
-            const Step::FusedInput& fi = f.fused_inputs[i];
+        for (size_t i = 0; i < f.fused.inputs.size(); ++i) {
+            const Step::FusedInput& fi = f.fused.inputs[i];
             const int len = int(plan.input_layouts[size_t(fi.slot)].row_len);
             const std::string I = std::to_string(i), L = std::to_string(len);
             src += "#pragma unroll 4\n    for (int e = tid; e < " + std::to_string(64 * len) + "; e += 512) { const int i2 = e / " + L + ", c = e - i2 * " + L +
@@ -1731,14 +1739,14 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
                 elementwise(st);
                 break;
             case Step::AXPY:
-                for (uint32_t m : s.u32_a) {
+                for (uint32_t m : s.axpy_map) {
                     const std::string d = at(rb + (m & 0xffffu));
                     st.push_back(d + " = " + (s.beta ? d : std::string("T(0)")) + " + " + at(uint32_t(base_of(s.a)) + (m >> 16)) + ";");
                 }
                 elementwise(st);
                 break;
             case Step::FLIP:
-                for (uint32_t o : s.u32_a) st.push_back(at(rb + o) + " = -" + at(rb + o) + ";");
+                for (uint32_t o : s.flip_offsets) st.push_back(at(rb + o) + " = -" + at(rb + o) + ";");
                 elementwise(st);
                 break;
             case Step::SUNARY: {
@@ -1750,18 +1758,18 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
             }
             case Step::PRODUCT_CSR: {
                 const uint32_t lb = uint32_t(base_of(s.a, s.canon_a)), rrb = uint32_t(base_of(s.b, s.canon_b));
-                for (size_t row = 0; row + 1 < s.u32_a.size(); ++row) {
-                    const std::string d = at(rb + s.u32_b[row]);
+                for (size_t row = 0; row + 1 < s.list.row_start.size(); ++row) {
+                    const std::string d = at(rb + s.list.row_out[row]);
                     std::string blk = "      { T acc = " + (s.beta ? d : std::string("T(0)")) + ";\n";
-                    for (uint32_t e = s.u32_a[row]; e < s.u32_a[row + 1]; ++e) {
-                        const std::string prod = "(" + at(lb + (s.u32_c[e] & 0xffffu)) + " * " + at(rrb + (s.u32_c[e] >> 16)) + ")";
-                        const double c = s.coeff[e];
+                    for (uint32_t e = s.list.row_start[row]; e < s.list.row_start[row + 1]; ++e) {
+                        const std::string prod = "(" + at(lb + (s.list.entries[e] & 0xffffu)) + " * " + at(rrb + (s.list.entries[e] >> 16)) + ")";
+                        const double c = s.list.coeff[e];
                         blk += c == 1.0 ? "        acc = acc + " + prod + ";\n"
                                : c == -1.0 ? "        acc = acc - " + prod + ";\n"
                                            : "        acc = acc + " + prod + " * T(" + lit(c) + ");\n";
                     }
                     blk += "        " + d + " = acc; }\n";
-                    pieces.emplace_back(uint64_t(s.u32_a[row + 1] - s.u32_a[row]) + 2, blk);
+                    pieces.emplace_back(uint64_t(s.list.row_start[row + 1] - s.list.row_start[row]) + 2, blk);
                 }
                 break;
             }
@@ -1803,14 +1811,14 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
         src += "  if (pre_next) commit(); else stage(gn * 64, nnext);\n";
         src += "  }\n";
         src += "}\n";
-        f.jit_threads = 512;
-        f.jit_items = 64;
-        f.jit_persistent = int(std::max<size_t>(1, kLdsBytes / (size_t(64) * size_t(stride) * elem)));   // workgroups resident per CU (LDS)
-        f.jit_source = std::move(src);
+        f.fused.jit_threads = 512;
+        f.fused.jit_items = 64;
+        f.fused.jit_persistent = int(std::max<size_t>(1, kLdsBytes / (size_t(64) * size_t(stride) * elem)));   // workgroups resident per CU (LDS)
+        f.fused.jit_source = std::move(src);
     }
-    f.fused_slab = slab;
-    f.fused_zero_slot = zero_slot;
-    f.fused_out_base = out_base;
+    f.fused.slab = slab;
+    f.fused.zero_slot = zero_slot;
+    f.fused.out_base = out_base;
     f.n_entries = entries;
     f.name = "ast_fused[" + std::to_string(plan.steps.size()) + " arms, " + std::to_string(entries) +
              " comp-muls, slab " + std::to_string(slab) + "]";
@@ -1829,32 +1837,32 @@ bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
 static void uniform_csr_to_ell(Plan& plan) {
     if (plan.flags & GAAST_FLAG_NO_FUSION) return;
     for (Step& s : plan.steps) {
-        if (s.kind != Step::PRODUCT_CSR || s.u32_b.empty()) continue;
-        const size_t n_rows = s.u32_b.size();
-        const uint32_t width = s.u32_a[1] - s.u32_a[0];
+        if (s.kind != Step::PRODUCT_CSR || s.list.row_out.empty()) continue;
+        const size_t n_rows = s.list.row_out.size();
+        const uint32_t width = s.list.row_start[1] - s.list.row_start[0];
         bool uniform = width >= 4;   // (round 3: from 4 terms per row on -- R X has n per row; 16 before: such lists ran on k_product_csr, an entry and a coefficient load per term)
-        for (size_t i = 0; uniform && i < n_rows; ++i) uniform = s.u32_a[i + 1] - s.u32_a[i] == width;
-        for (size_t e = 0; uniform && e < s.coeff.size(); ++e) uniform = s.coeff[e] == 1.0 || s.coeff[e] == -1.0;
-        for (size_t e = 0; uniform && e < s.u32_c.size(); ++e) uniform = !(s.u32_c[e] & 0x80000000u);   // right offset < 2^15
+        for (size_t i = 0; uniform && i < n_rows; ++i) uniform = s.list.row_start[i + 1] - s.list.row_start[i] == width;
+        for (size_t e = 0; uniform && e < s.list.coeff.size(); ++e) uniform = s.list.coeff[e] == 1.0 || s.list.coeff[e] == -1.0;
+        for (size_t e = 0; uniform && e < s.list.entries.size(); ++e) uniform = !(s.list.entries[e] & 0x80000000u);   // right offset < 2^15
         if (!uniform) continue;
         // offsets in BYTES when they fit 15 bits (rows of <= 32 KiB: n <= 12 in f64, n <= 13 in f32): the kernel
         // then adds them to an LDS base without scaling
         const uint32_t elem = plan.dtype == GAAST_F32 ? 4u : 8u;
         bool bytes = true;
-        for (size_t e = 0; bytes && e < s.u32_c.size(); ++e)
-            bytes = (s.u32_c[e] & 0xffffu) * elem < 32768u && (s.u32_c[e] >> 16) * elem < 32768u;
+        for (size_t e = 0; bytes && e < s.list.entries.size(); ++e)
+            bytes = (s.list.entries[e] & 0xffffu) * elem < 32768u && (s.list.entries[e] >> 16) * elem < 32768u;
         std::vector<uint32_t> ell(size_t(width) * n_rows);
         for (size_t row = 0; row < n_rows; ++row)
             for (uint32_t t = 0; t < width; ++t) {
-                const size_t e = size_t(s.u32_a[row]) + t;
-                const uint32_t lo = s.u32_c[e] & 0xffffu, ro = s.u32_c[e] >> 16;
-                const uint32_t word = bytes ? (lo * elem) | ((ro * elem) << 16) : s.u32_c[e];
-                ell[size_t(t) * n_rows + row] = word | (s.coeff[e] < 0.0 ? 0x80000000u : 0u);
+                const size_t e = size_t(s.list.row_start[row]) + t;
+                const uint32_t lo = s.list.entries[e] & 0xffffu, ro = s.list.entries[e] >> 16;
+                const uint32_t word = bytes ? (lo * elem) | ((ro * elem) << 16) : s.list.entries[e];
+                ell[size_t(t) * n_rows + row] = word | (s.list.coeff[e] < 0.0 ? 0x80000000u : 0u);
             }
-        s.ell_bytes = bytes ? 1 : 0;
-        s.u32_c.swap(ell);
-        s.coeff.clear();
-        s.ell_width = int(width);
+        s.list.ell_bytes = bytes ? 1 : 0;
+        s.list.entries.swap(ell);
+        s.list.coeff.clear();
+        s.list.ell_width = int(width);
         s.name = "product_ell" + s.name.substr(s.name.find('['));
     }
 }
@@ -1868,63 +1876,70 @@ static void chain_sparse_into_dense(Plan& plan) {
     if (plan.flags & (GAAST_FLAG_NO_FUSION | GAAST_FLAG_DEBUG_NO_CHAIN)) return;
     plan.node_dead.assign(plan.node_buffers.size(), 0);
     const size_t elem = plan.dtype == GAAST_F32 ? 4 : 8;
-    auto same = [](BufRef x, BufRef y) { return x.kind == y.kind && x.idx == y.idx; };
     for (size_t j = 0; j < plan.steps.size(); ++j) {
         Step& dn = plan.steps[j];
-        if (dn.kind != Step::PRODUCT_DENSE || dn.use_spinor || dn.use_mfma6 || dn.chained || dn.a.kind != BufKind::NODE) continue;   // (k_gp_mfma6 has no chained staging: programs that small are fused whole)
+        const DenseFamily fam = dn.dense.family;   // (k_gp_mfma6 has no chained staging: programs that small are fused whole)
+        if (dn.kind != Step::PRODUCT_DENSE || fam == DenseFamily::SPINOR || fam == DenseFamily::MFMA6 || dn.dense.chained || dn.a.kind != BufKind::NODE) continue;
         const BufRef buf = dn.a;
         // exactly one writer (a list product that starts the buffer: beta = 0), no other reader, nothing else touches it
         int writer = -1;
-        bool ok = !same(dn.b, buf);
+        bool ok = dn.b != buf;
         for (size_t i = 0; i < plan.steps.size() && ok; ++i) {
             const Step& t = plan.steps[i];
             if (i == j) continue;
             if (t.kind == Step::FUSED) ok = false;
-            if (same(t.res, buf)) {
+            if (t.res == buf) {
                 if (writer >= 0 || t.kind != Step::PRODUCT_CSR || t.beta != 0 || i > j) ok = false;
                 writer = int(i);
             }
-            if ((t.a.idx >= 0 && same(t.a, buf)) || (t.b.idx >= 0 && same(t.b, buf))) ok = false;
-            if (t.chained && (same(t.pre_a, buf) || same(t.pre_b, buf))) ok = false;
+            if (reads(t, buf)) ok = false;
         }
         if (!ok || writer < 0) continue;
         Step& w = plan.steps[size_t(writer)];
         // the list's operands must still hold at the dense launch: inputs always do; a cache buffer does unless a later step
         // writes it (cache buffers are written by the steps that fill them, all before their first reader)
         for (size_t i = size_t(writer) + 1; i < j && ok; ++i)
-            if (same(plan.steps[i].res, w.a) || same(plan.steps[i].res, w.b)) ok = false;
+            if (plan.steps[i].res == w.a || plan.steps[i].res == w.b) ok = false;
         if (!ok) continue;
         auto row_len = [&](BufRef r) -> int64_t {
             return r.kind == BufKind::NODE ? plan.node_buffers[size_t(r.idx)].row_len : r.kind == BufKind::INPUT ? plan.input_layouts[size_t(r.idx)].row_len
                                                                                                                : plan.out_layout.row_len;
         };
         const int64_t ll = row_len(w.a), rl = row_len(w.b);
-        const int n2 = dn.dense_n;
+        const int n2 = dn.dense.n;
         // items a workgroup of the dense kernel stages at once (runtime.hip: prepare_step)
-        int ipb = 1;
-        if (dn.use_mfma) ipb = n2 <= 10 ? 4 : n2 == 11 ? 2 : 1;
-        else if (!dn.use_mfma16 && !dn.use_mfma7) ipb = std::max(256, 1 << (n2 - 4)) >> (n2 - 4);
+        int ipb = 1, images_per_item = 4;   // (image counts: +-A, +-B, or A and B)
+        switch (fam) {
+        case DenseFamily::MFMA32:
+        case DenseFamily::MFMA32P:
+            ipb = n2 <= 10 ? 4 : n2 == 11 ? 2 : 1;
+            images_per_item = fam == DenseFamily::MFMA32 ? 2 : 4;
+            break;
+        case DenseFamily::MFMA16X4:
+        case DenseFamily::MFMA7: break;
+        default: ipb = std::max(256, 1 << (n2 - 4)) >> (n2 - 4); images_per_item = 2; break;
+        }
         const size_t scratch = size_t(ipb) * size_t(ll + rl + 1) * elem;
-        const size_t images = size_t(ipb) * (size_t(dn.use_mfma && !dn.mfma32_pairs ? 2 : (dn.use_mfma || dn.use_mfma16 || dn.use_mfma7) ? 4 : 2) << n2) * elem + 256;
-        if (scratch > 48 * 1024 || images + scratch > kLdsBytes - 1024 || w.u32_b.size() > 32768) continue;
+        const size_t images = size_t(ipb) * (size_t(images_per_item) << n2) * elem + 256;
+        if (scratch > 48 * 1024 || images + scratch > kLdsBytes - 1024 || w.list.row_out.size() > 32768) continue;
         // rows of the list -> components of the dense step's left image
         std::vector<int32_t> map_of(size_t(row_len(buf)), -1);
-        for (size_t c = 0; c < dn.u32_a.size(); ++c) map_of[dn.u32_a[c] & 0xffffu] = int32_t(c);
-        dn.pre_row_map.clear();
-        dn.pre_row_scale.clear();
+        for (size_t c = 0; c < dn.dense.left_map.size(); ++c) map_of[dn.dense.left_map[c] & 0xffffu] = int32_t(c);
+        dn.pre.row_map.clear();
+        dn.pre.row_scale.clear();
         bool covered = true;
         std::vector<uint32_t> row_start(1, 0u), entries;
         std::vector<double> coeff;
-        std::vector<char> produced(dn.u32_a.size(), 0);
-        for (size_t row = 0; row < w.u32_b.size(); ++row) {
-            const int32_t c = map_of[w.u32_b[row]];
+        std::vector<char> produced(dn.dense.left_map.size(), 0);
+        for (size_t row = 0; row < w.list.row_out.size(); ++row) {
+            const int32_t c = map_of[w.list.row_out[row]];
             if (c < 0) continue;   // a component the dense product does not read (its grade is not wanted there)
             produced[size_t(c)] = 1;
-            dn.pre_row_map.push_back(dn.u32_a[size_t(c)] & 0xffff0000u);
-            if (dn.scaled) dn.pre_row_scale.push_back(dn.coeff[size_t(c)]);
-            for (uint32_t e = w.u32_a[row]; e < w.u32_a[row + 1]; ++e) {
-                entries.push_back(w.u32_c[e]);
-                coeff.push_back(w.coeff[e]);
+            dn.pre.row_map.push_back(dn.dense.left_map[size_t(c)] & 0xffff0000u);
+            if (dn.dense.scaled) dn.pre.row_scale.push_back(dn.dense.left_scale[size_t(c)]);
+            for (uint32_t e = w.list.row_start[row]; e < w.list.row_start[row + 1]; ++e) {
+                entries.push_back(w.list.entries[e]);
+                coeff.push_back(w.list.coeff[e]);
             }
             row_start.push_back(uint32_t(entries.size()));
         }
@@ -1951,22 +1966,22 @@ static void chain_sparse_into_dense(Plan& plan) {
                     }
                 entries.swap(ell);
                 coeff.clear();
-                dn.pre_width = int(wpad);
+                dn.pre.width = int(wpad);
             }
         }
-        dn.chained = 1;
-        dn.pre_a = w.a;
-        dn.pre_b = w.b;
-        dn.pre_canon_a = w.canon_a;
-        dn.pre_canon_b = w.canon_b;
-        dn.pre_row_start = std::move(row_start);
-        dn.pre_entries = std::move(entries);
-        dn.pre_coeff = std::move(coeff);
-        dn.pre_left_len = int(ll);
-        dn.pre_right_len = int(rl);
+        dn.dense.chained = 1;
+        dn.pre.a = w.a;
+        dn.pre.b = w.b;
+        dn.pre.canon_a = w.canon_a;
+        dn.pre.canon_b = w.canon_b;
+        dn.pre.row_start = std::move(row_start);
+        dn.pre.entries = std::move(entries);
+        dn.pre.coeff = std::move(coeff);
+        dn.pre.left_len = int(ll);
+        dn.pre.right_len = int(rl);
         // components no row produces stay zero: the kernel zero-fills the image first unless every loaded component is covered
-        dn.left_full = dn.left_full && covered;
-        dn.left_contig = 0;   // general staging
+        dn.dense.left_full = dn.dense.left_full && covered;
+        dn.dense.left_contig = 0;   // general staging
         dn.name += " <- " + w.name + " in LDS";
         dn.n_entries += w.n_entries;
         dn.a = BufRef{BufKind::NODE, -1};
@@ -2022,14 +2037,14 @@ static void make_chain_jit(const Plan& plan, Step& c, const Step* wp, int64_t l1
     // sign words; R^{6,3} at n = 9: 64 + 64 of 128, no padding; (a + b c).g(2) at n = 8: 136 + 136 for 256)
     bool sorted = !(plan.flags & GAAST_FLAG_EXACT_ORDER) && (cur + 1) * esz <= 65536;
     if (sorted) {
-        const int64_t rows2e = int64_t(c.u32_b.size()), w2e = c.ell_width;
+        const int64_t rows2e = int64_t(c.list.row_out.size()), w2e = c.list.ell_width;
         int64_t sp = 1;   // (the slice count of the tolerance mode, decided again below with the same rule)
         while (sp < 4 && w2e % (2 * sp) == 0 && w2e / (2 * sp) >= 32 && rows2e * 32 * 2 * sp <= 1024 && rows2e * 2 * sp <= mid) sp *= 2;
         const int64_t gran = plan.dtype == GAAST_F32 ? 16 : 8;
         int64_t wp = 0, wm = 0;
         for (int64_t row = 0; row < rows2e; ++row) {
             int64_t np = 0, nm = 0;
-            for (int64_t t = 0; t < w2e; ++t) ((c.u32_c[size_t(t * rows2e + row)] & 0x80000000u) ? nm : np) += 1;
+            for (int64_t t = 0; t < w2e; ++t) ((c.list.entries[size_t(t * rows2e + row)] & 0x80000000u) ? nm : np) += 1;
             wp = std::max(wp, (np + sp - 1) / sp);
             wm = std::max(wm, (nm + sp - 1) / sp);
         }
@@ -2043,8 +2058,8 @@ static void make_chain_jit(const Plan& plan, Step& c, const Step* wp, int64_t l1
     const int64_t off_other = alias == 0 ? off_r2 : alias == 1 ? off_l1 : off_r1;
     const int64_t other_len = alias == 0 ? r2 : alias == 1 ? l1 : r1;
     if ((off_other + other_len) * esz > 32768 || cur * esz > 65536) return;   // (15-bit / 16-bit byte offsets from the item's base)
-    const int64_t rows1 = int64_t(w.u32_b.size()), rows2 = int64_t(c.u32_b.size());
-    const int64_t w1 = w.ell_width, w2 = c.ell_width;
+    const int64_t rows1 = int64_t(w.list.row_out.size()), rows2 = int64_t(c.list.row_out.size());
+    const int64_t w1 = w.list.ell_width, w2 = c.list.ell_width;
     if (rows2 <= 0 || w2 <= 0) return;
     if (!single && (rows1 <= 0 || w1 <= 0 || w1 > 32)) return;   // (list 1's operands of a row are all in flight at once)
     // items per workgroup: a power of two up to 32 (the lanes of an LDS access group), as many as the LDS holds
@@ -2076,7 +2091,7 @@ static void make_chain_jit(const Plan& plan, Step& c, const Step* wp, int64_t l1
         const int64_t off_other_b = (alias == 0 ? off_r2 : alias == 1 ? off_l1 : off_r1) * esz;
         for (int64_t row = 0; row < rows2; ++row)
             for (int64_t t = 0; t < w2; ++t) {
-                const uint32_t e = c.u32_c[size_t(t * rows2 + row)];
+                const uint32_t e = c.list.entries[size_t(t * rows2 + row)];
                 const int64_t lo = e & 0x7fffu, ro = (e >> 16) & 0x7fffu;
                 const int64_t ma = off_mid * esz + (side == 1 ? lo : ro), oa = off_other_b + (side == 1 ? ro : lo);
                 ((e & 0x80000000u) ? minus_terms : plus_terms)[size_t(row)].push_back(uint32_t(ma) | (uint32_t(oa) << 16));
@@ -2125,59 +2140,59 @@ static void make_chain_jit(const Plan& plan, Step& c, const Step* wp, int64_t l1
     for (int64_t row = 0; row < rows1 && xreg; ++row) {
         uint32_t seen = 0;
         for (int64_t t = 0; t < w1 && xreg; ++t) {
-            const int64_t j = int64_t((w.u32_c[size_t(t * rows1 + row)] >> 16) & 0x7fffu) / esz;
+            const int64_t j = int64_t((w.list.entries[size_t(t * rows1 + row)] >> 16) & 0x7fffu) / esz;
             xreg = j < r1 && !(seen & (1u << j));
             seen |= 1u << j;
         }
     }
-    c.cj_ent1.assign(size_t(rows1 * w1s), 0u);
-    c.cj_pos1.resize(size_t(rows1));
-    if (init_off) c.cj_pos1 = *init_off;   // (a single list has no row positions: the slot carries the offsets of the folded copy)
+    c.cj.ent1.assign(size_t(rows1 * w1s), 0u);
+    c.cj.pos1.resize(size_t(rows1));
+    if (init_off) c.cj.pos1 = *init_off;   // (a single list has no row positions: the slot carries the offsets of the folded copy)
     for (int64_t row = 0; row < rows1; ++row) {
-        c.cj_pos1[size_t(row)] = uint32_t((off_mid + int64_t(w.u32_b[size_t(row)])) * esz);
+        c.cj.pos1[size_t(row)] = uint32_t((off_mid + int64_t(w.list.row_out[size_t(row)])) * esz);
         for (int64_t t = 0; t < w1; ++t) {
-            const uint32_t e = w.u32_c[size_t(t * rows1 + row)];
+            const uint32_t e = w.list.entries[size_t(t * rows1 + row)];
             const bool neg = (e & 0x80000000u) != 0;
             const int64_t lo = e & 0x7fffu, ro = (e >> 16) & 0x7fffu;   // bytes, from the operand rows
             const int64_t la = ((neg && neg_is_left) ? off_neg : off_l1) * esz + lo;
             const int64_t ra = ((neg && !neg_is_left) ? off_neg : off_r1) * esz + ro;
-            if (!xreg) c.cj_ent1[size_t(row * w1s + t)] = uint32_t(la) | (uint32_t(ra) << 16);
+            if (!xreg) c.cj.ent1[size_t(row * w1s + t)] = uint32_t(la) | (uint32_t(ra) << 16);
         }
         if (xreg) {
-            for (int64_t j = 0; j < w1s; ++j) c.cj_ent1[size_t(row * w1s + j)] = uint32_t(off_zero * esz);   // no term for x_j: 0 * x_j
+            for (int64_t j = 0; j < w1s; ++j) c.cj.ent1[size_t(row * w1s + j)] = uint32_t(off_zero * esz);   // no term for x_j: 0 * x_j
             for (int64_t t = 0; t < w1; ++t) {
-                const uint32_t e = w.u32_c[size_t(t * rows1 + row)];
+                const uint32_t e = w.list.entries[size_t(t * rows1 + row)];
                 const int64_t lo = e & 0x7fffu, j = int64_t((e >> 16) & 0x7fffu) / esz;
-                c.cj_ent1[size_t(row * w1s + j)] = uint32_t(off_l1 * esz + lo) | (e & 0x80000000u);
+                c.cj.ent1[size_t(row * w1s + j)] = uint32_t(off_l1 * esz + lo) | (e & 0x80000000u);
             }
         }
     }
     const int64_t wpt2 = ent2_mode == 2 ? 2 : 1;   // words per term
-    c.cj_out2 = c.u32_b;
+    c.cj.out2 = c.list.row_out;
     if (sorted) {
         const uint32_t pad = uint32_t(off_zero * esz) | (uint32_t(off_zero * esz) << 16);
-        c.cj_ent2.assign(size_t(rows2 * split * wss), pad);
+        c.cj.ent2.assign(size_t(rows2 * split * wss), pad);
         for (int64_t row = 0; row < rows2; ++row)
             for (int which = 0; which < 2; ++which) {
                 const std::vector<uint32_t>& tv = which ? minus_terms[size_t(row)] : plus_terms[size_t(row)];
                 const int64_t per = (int64_t(tv.size()) + split - 1) / split;   // consecutive chunks, one per slice
                 for (int64_t i = 0; i < int64_t(tv.size()); ++i) {
                     const int64_t sl = per ? i / per : 0, k = per ? i % per : 0;
-                    c.cj_ent2[size_t((row * split + sl) * wss + (which ? wps : 0) + k)] = tv[size_t(i)];
+                    c.cj.ent2[size_t((row * split + sl) * wss + (which ? wps : 0) + k)] = tv[size_t(i)];
                 }
             }
     } else
-        c.cj_ent2.assign(size_t(rows2 * w2p * wpt2), 0u);
+        c.cj.ent2.assign(size_t(rows2 * w2p * wpt2), 0u);
     for (int64_t row = 0; row < rows2 && !sorted; ++row)
         for (int64_t t = 0; t < w2; ++t) {
-            const uint32_t e = c.u32_c[size_t(t * rows2 + row)];
+            const uint32_t e = c.list.entries[size_t(t * rows2 + row)];
             const int64_t lo = e & 0x7fffu, ro = (e >> 16) & 0x7fffu;
             const int64_t ma = off_mid * esz + (side == 1 ? lo : ro), oa = off_other * esz + (side == 1 ? ro : lo);
             if (ent2_mode == 2) {
-                c.cj_ent2[size_t((row * w2p + t) * 2)] = uint32_t(ma) | (uint32_t(oa) << 16);
-                c.cj_ent2[size_t((row * w2p + t) * 2 + 1)] = e & 0x80000000u;
+                c.cj.ent2[size_t((row * w2p + t) * 2)] = uint32_t(ma) | (uint32_t(oa) << 16);
+                c.cj.ent2[size_t((row * w2p + t) * 2 + 1)] = e & 0x80000000u;
             } else {
-                c.cj_ent2[size_t(row * w2p + t)] = uint32_t(ma) | (uint32_t(oa) << 16) | (e & 0x80000000u);
+                c.cj.ent2[size_t(row * w2p + t)] = uint32_t(ma) | (uint32_t(oa) << 16) | (e & 0x80000000u);
             }
         }
     // source
@@ -2193,7 +2208,7 @@ static void make_chain_jit(const Plan& plan, Step& c, const Step* wp, int64_t l1
     def("CANON_MID", side == 1 ? c.canon_a : c.canon_b); def("COVERED", covered ? 1 : 0); def("BETA", init_off ? 0 : c.beta);
     def("SINGLE", single ? 1 : 0); def("INIT_SRC", init_off ? 1 : 0);
     bool pos1_linear = true;   // row k of list 1 is component k of the mid row (the usual case): no table, no load
-    for (int64_t row = 0; row < rows1; ++row) pos1_linear = pos1_linear && int64_t(w.u32_b[size_t(row)]) == row;
+    for (int64_t row = 0; row < rows1; ++row) pos1_linear = pos1_linear && int64_t(w.list.row_out[size_t(row)]) == row;
     def("POS1_LINEAR", pos1_linear ? 1 : 0);
     // EXACT: every product rounded, then added (eval.rs:82), rows summed whole -- the reference's bits.  Otherwise (the default,
     // the dense products' tolerance contract): rows of list 2 in slices, and l * r + acc as one fused multiply-add
@@ -2682,20 +2697,20 @@ extern "C" __global__ __launch_bounds__(NT) void gaast_chain(const T* __restrict
     }
 }
 )JIT";
-    c.chain_jit = 1;
-    c.chain_jit_source = std::move(src);
+    c.cj.on = 1;
+    c.cj.source = std::move(src);
     const int64_t lay[7] = {off_l1, off_r1, off_neg, off_mid, alias ? -1 : off_r2, stride, neg_is_left ? 1 : 0};
-    for (int i = 0; i < 7; ++i) c.cj_layout[i] = int(lay[i]);
-    c.cj_fmt[0] = int(w1s);
-    c.cj_fmt[1] = ent2_mode;
-    c.cj_sorted[0] = int(wps);
-    c.cj_sorted[1] = int(wms);
-    c.cj_sorted[2] = int(off_zero * esz);
-    c.cj_xreg = xreg ? 1 : 0;
-    c.cj_split = int(split);
-    c.cj_ipb = int(ipb);
-    c.cj_threads = int(threads);
-    c.cj_lds = size_t(used);
+    for (int i = 0; i < 7; ++i) c.cj.layout[i] = int(lay[i]);
+    c.cj.fmt[0] = int(w1s);
+    c.cj.fmt[1] = ent2_mode;
+    c.cj.sorted[0] = int(wps);
+    c.cj.sorted[1] = int(wms);
+    c.cj.sorted[2] = int(off_zero * esz);
+    c.cj.xreg = xreg ? 1 : 0;
+    c.cj.split = int(split);
+    c.cj.ipb = int(ipb);
+    c.cj.threads = int(threads);
+    c.cj.lds = size_t(used);
 }
 
 // A list product whose result is read ONLY by another list product (as either operand): both run in ONE k_product_ell_chain
@@ -2706,7 +2721,6 @@ static void chain_list_into_list(Plan& plan) {
     if (plan.flags & (GAAST_FLAG_NO_FUSION | GAAST_FLAG_DEBUG_NO_CHAIN)) return;
     if (plan.node_dead.size() != plan.node_buffers.size()) plan.node_dead.assign(plan.node_buffers.size(), 0);
     const size_t elem = plan.dtype == GAAST_F32 ? 4 : 8;
-    auto same = [](BufRef x, BufRef y) { return x.kind == y.kind && x.idx == y.idx; };
     auto row_len = [&](BufRef r) -> int64_t {
         return r.kind == BufKind::NODE ? plan.node_buffers[size_t(r.idx)].row_len : r.kind == BufKind::INPUT ? plan.input_layouts[size_t(r.idx)].row_len
                                                                                                            : plan.out_layout.row_len;
@@ -2715,33 +2729,32 @@ static void chain_list_into_list(Plan& plan) {
         if (t.kind == Step::FUSED) return;
     for (size_t j = 0; j < plan.steps.size(); ++j) {
         Step& c = plan.steps[j];
-        if (c.kind != Step::PRODUCT_CSR || c.ell_width <= 0 || !c.ell_bytes || c.list_chain) continue;
-        for (int side = 1; side <= 2 && !c.list_chain; ++side) {
+        if (c.kind != Step::PRODUCT_CSR || c.list.ell_width <= 0 || !c.list.ell_bytes || c.chain.side) continue;
+        for (int side = 1; side <= 2 && !c.chain.side; ++side) {
             const BufRef buf = side == 1 ? c.a : c.b, other = side == 1 ? c.b : c.a;
-            if (buf.kind != BufKind::NODE || buf.idx < 0 || same(buf, other)) continue;
+            if (buf.kind != BufKind::NODE || buf.idx < 0 || buf == other) continue;
             int writer = -1;
             bool ok = true;
             for (size_t i = 0; i < plan.steps.size() && ok; ++i) {
                 const Step& t = plan.steps[i];
                 if (i == j) continue;
-                if (same(t.res, buf)) {
-                    if (writer >= 0 || t.kind != Step::PRODUCT_CSR || t.ell_width <= 0 || !t.ell_bytes || t.beta != 0 || t.list_chain || i > j) ok = false;
+                if (t.res == buf) {
+                    if (writer >= 0 || t.kind != Step::PRODUCT_CSR || t.list.ell_width <= 0 || !t.list.ell_bytes || t.beta != 0 || t.chain.side || i > j) ok = false;
                     writer = int(i);
                 }
-                if ((t.a.idx >= 0 && same(t.a, buf)) || (t.b.idx >= 0 && same(t.b, buf))) ok = false;
-                if ((t.chained || t.list_chain) && (same(t.pre_a, buf) || same(t.pre_b, buf))) ok = false;
+                if (reads(t, buf)) ok = false;
             }
             if (!ok || writer < 0) continue;
             Step& w = plan.steps[size_t(writer)];
-            if (same(w.a, buf) || same(w.b, buf) || same(c.res, w.a) || same(c.res, w.b)) continue;
+            if (w.a == buf || w.b == buf || c.res == w.a || c.res == w.b) continue;
             for (size_t i = size_t(writer) + 1; i < j && ok; ++i)
-                if (same(plan.steps[i].res, w.a) || same(plan.steps[i].res, w.b)) ok = false;
+                if (plan.steps[i].res == w.a || plan.steps[i].res == w.b) ok = false;
             if (!ok) continue;
             const int64_t l1 = row_len(w.a), r1 = row_len(w.b), mid = row_len(buf), r2 = row_len(other);
             const int canon_other = side == 1 ? c.canon_b : c.canon_a;
             int alias = 0;
-            if (same(other, w.a) && canon_other == w.canon_a) alias = 1;
-            else if (same(other, w.b) && canon_other == w.canon_b) alias = 2;
+            if (other == w.a && canon_other == w.canon_a) alias = 1;
+            else if (other == w.b && canon_other == w.canon_b) alias = 2;
             const int64_t per_item = l1 + r1 + mid + (alias ? 0 : r2);
             if (per_item * int64_t(elem) >= 32768 * 3) continue;       // byte offsets of the entries stay below 32 KiB per row anyway
             int64_t stride = per_item;
@@ -2749,11 +2762,11 @@ static void chain_list_into_list(Plan& plan) {
             // items per workgroup: about 36 KiB of LDS (four workgroups per CU: one's staging overlaps another's lists), at least
             // four items when that still fits the CU
             // this list's words ride in LDS when they take at most 48 KiB (n <= 11 for the sandwich)
-            int64_t ent2 = ((int64_t(c.ell_width) + 4) * int64_t(c.u32_b.size()) * 4 + 15) / 16 * 16;   // [row][term], rows 4 words apart; widths are multiples of 4
-            if (ent2 > 48 * 1024 || c.ell_width % 4) ent2 = 0;
+            int64_t ent2 = ((int64_t(c.list.ell_width) + 4) * int64_t(c.list.row_out.size()) * 4 + 15) / 16 * 16;   // [row][term], rows 4 words apart; widths are multiples of 4
+            if (ent2 > 48 * 1024 || c.list.ell_width % 4) ent2 = 0;
             // items per workgroup: as many as make this list's (row, item) pairs just fill a wave (9 rows: 7 items = 63 lanes) -- a
             // second, nearly empty wave would issue the whole list again --, fewer when the LDS does not hold them
-            const int64_t rows2 = int64_t(c.u32_b.size());
+            const int64_t rows2 = int64_t(c.list.row_out.size());
             int64_t ipb = rows2 <= 32 ? 64 / rows2 : 4;
             const int64_t lds_cap = int64_t(kLdsBytes) - 16 * 1024;
             while (ipb > 2 && ent2 + ipb * stride * int64_t(elem) > lds_cap / 2) --ipb;   // two workgroups per CU when that costs at most ...
@@ -2763,28 +2776,28 @@ static void chain_list_into_list(Plan& plan) {
                 while (ipb > 1 && ipb * stride * int64_t(elem) > lds_cap) --ipb;
             }
             if (ipb < 2 || ent2 + ipb * stride * int64_t(elem) > lds_cap) continue;
-            c.chain_ent2_lds = int(ent2);
+            c.chain.ent2_lds = int(ent2);
             // rows of the first list -> their element offsets in the mid row; is every component of the mid row produced?
             std::vector<char> produced(size_t(mid), 0);
-            for (uint32_t off : w.u32_b) produced[off] = 1;
+            for (uint32_t off : w.list.row_out) produced[off] = 1;
             bool covered = true;
             for (char x : produced) covered = covered && x;
-            c.list_chain = side;
-            c.chain_alias = alias;
-            c.chain_mid_len = int(mid);
-            c.chain_canon_mid = side == 1 ? c.canon_a : c.canon_b;
-            c.chain_covered = covered ? 1 : 0;
-            c.chain_ipb = int(ipb);
-            c.chain_item_stride = int(stride);
-            c.pre_a = w.a;
-            c.pre_b = w.b;
-            c.pre_canon_a = w.canon_a;
-            c.pre_canon_b = w.canon_b;
-            c.pre_left_len = int(l1);
-            c.pre_right_len = int(r1);
-            c.pre_entries = w.u32_c;
-            c.pre_row_map = w.u32_b;
-            c.pre_width = w.ell_width;
+            c.chain.side = side;
+            c.chain.alias = alias;
+            c.chain.mid_len = int(mid);
+            c.chain.canon_mid = side == 1 ? c.canon_a : c.canon_b;
+            c.chain.covered = covered ? 1 : 0;
+            c.chain.ipb = int(ipb);
+            c.chain.item_stride = int(stride);
+            c.pre.a = w.a;
+            c.pre.b = w.b;
+            c.pre.canon_a = w.canon_a;
+            c.pre.canon_b = w.canon_b;
+            c.pre.left_len = int(l1);
+            c.pre.right_len = int(r1);
+            c.pre.entries = w.list.entries;
+            c.pre.row_map = w.list.row_out;
+            c.pre.width = w.list.ell_width;
             c.name += " <- " + w.name + " in LDS";
             c.n_entries += w.n_entries;
             make_chain_jit(plan, c, &w, l1, r1, mid, r2, alias, side, covered);
@@ -2808,7 +2821,6 @@ static void chain_list_into_list(Plan& plan) {
 // buffer is never written at all.
 static void fuse_elementwise_runs(Plan& plan) {
     if (plan.flags & (GAAST_FLAG_NO_FUSION | GAAST_FLAG_DEBUG_NO_CHAIN)) return;
-    auto same = [](BufRef x, BufRef y) { return x.kind == y.kind && x.idx == y.idx; };
     auto row_len = [&](BufRef r) -> int64_t {
         return r.kind == BufKind::NODE ? plan.node_buffers[size_t(r.idx)].row_len : r.kind == BufKind::INPUT ? plan.input_layouts[size_t(r.idx)].row_len
                                                                                                            : plan.out_layout.row_len;
@@ -2822,11 +2834,11 @@ static void fuse_elementwise_runs(Plan& plan) {
         bool ok = true;
         while (j < plan.steps.size() && ok) {
             const Step& t = plan.steps[j];
-            if ((t.kind != Step::AXPY && t.kind != Step::FLIP) || !same(t.res, R)) break;
+            if ((t.kind != Step::AXPY && t.kind != Step::FLIP) || t.res != R) break;
             if (t.kind == Step::AXPY) {
                 if (t.a.kind != BufKind::INPUT) break;
                 bool known = false;
-                for (const BufRef& b : srcs) known = known || same(b, t.a);
+                for (const BufRef& b : srcs) known = known || b == t.a;
                 if (!known) {
                     if (srcs.size() == 6) break;
                     srcs.push_back(t.a);
@@ -2841,11 +2853,10 @@ static void fuse_elementwise_runs(Plan& plan) {
         const int64_t rl = row_len(R);
         std::vector<int32_t> comp_of(size_t(rl), -1);
         std::vector<uint32_t> comps;
-        for (size_t k = i; k < j; ++k)
-            for (uint32_t w : plan.steps[k].u32_a) {
-                const uint32_t off = plan.steps[k].kind == Step::AXPY ? (w & 0xffffu) : w;
-                if (comp_of[off] < 0) comp_of[off] = 0;
-            }
+        for (size_t k = i; k < j; ++k) {
+            for (uint32_t w : plan.steps[k].axpy_map) comp_of[w & 0xffffu] = 0;
+            for (uint32_t off : plan.steps[k].flip_offsets) comp_of[off] = 0;
+        }
         for (int64_t o = 0; o < rl; ++o)
             if (comp_of[size_t(o)] == 0) {
                 comp_of[size_t(o)] = int32_t(comps.size());
@@ -2857,12 +2868,12 @@ static void fuse_elementwise_runs(Plan& plan) {
         for (size_t k = i; k < j; ++k) {
             const Step& t = plan.steps[k];
             if (t.kind == Step::FLIP) {
-                for (uint32_t off : t.u32_a) ops[(k - i) * nc + size_t(comp_of[off])] = 2u;
+                for (uint32_t off : t.flip_offsets) ops[(k - i) * nc + size_t(comp_of[off])] = 2u;
             } else {
                 uint32_t slot = 0;
                 for (size_t q = 0; q < srcs.size(); ++q)
-                    if (same(srcs[q], t.a)) slot = uint32_t(q);
-                for (uint32_t w : t.u32_a) ops[(k - i) * nc + size_t(comp_of[w & 0xffffu])] = (t.beta ? 1u : 3u) | (slot << 2) | ((w >> 16) << 16);
+                    if (srcs[q] == t.a) slot = uint32_t(q);
+                for (uint32_t w : t.axpy_map) ops[(k - i) * nc + size_t(comp_of[w & 0xffffu])] = (t.beta ? 1u : 3u) | (slot << 2) | ((w >> 16) << 16);
             }
         }
         // Every component executes ITS OWN statements in order, so each list is compacted on its own: empty statements go, and two
@@ -2896,11 +2907,11 @@ static void fuse_elementwise_runs(Plan& plan) {
         Step f;
         f.kind = Step::ELEMENTWISE;
         f.res = R;
-        f.ew_src = srcs;
-        f.ew_ops = int(n_stmt);
-        f.ew_load_first = load_first ? 1 : 0;
-        f.u32_a = std::move(ops);
-        f.u32_b = comps;
+        f.ew.src = srcs;
+        f.ew.n_ops = int(n_stmt);
+        f.ew.load_first = load_first ? 1 : 0;
+        f.ew.ops = std::move(ops);
+        f.ew.comp_off = comps;
         f.name = "elementwise[" + std::to_string(n_ops) + " arms:";
         for (size_t k = i; k < j; ++k) f.name += " " + plan.steps[k].name.substr(0, plan.steps[k].name.find('[') == std::string::npos ? 8 : plan.steps[k].name.find('['));
         f.name += "]";
@@ -2908,39 +2919,38 @@ static void fuse_elementwise_runs(Plan& plan) {
         size_t drop_to = j;
         if (R.kind == BufKind::NODE && j < plan.steps.size() && !load_first && int64_t(nc) == rl) {
             const Step& p2 = plan.steps[j];
-            const bool r_left = p2.kind == Step::PRODUCT_CSR && same(p2.a, R), r_right = p2.kind == Step::PRODUCT_CSR && same(p2.b, R);
-            if (p2.kind == Step::PRODUCT_CSR && p2.beta == 0 && r_left != r_right && !p2.list_chain && !p2.chained && p2.u32_b.size() == nc) {
+            const bool r_left = p2.kind == Step::PRODUCT_CSR && p2.a == R, r_right = p2.kind == Step::PRODUCT_CSR && p2.b == R;
+            if (p2.kind == Step::PRODUCT_CSR && p2.beta == 0 && r_left != r_right && !p2.chain.side && p2.list.row_out.size() == nc) {
                 const BufRef S = r_left ? p2.b : p2.a;
-                bool fits = row_len(S) == 1 && !same(S, R) && !same(p2.res, R);
-                for (size_t r = 0; r + 1 < p2.u32_a.size() && fits; ++r) fits = p2.u32_a[r + 1] - p2.u32_a[r] == 1;
+                bool fits = row_len(S) == 1 && S != R && p2.res != R;
+                for (size_t r = 0; r + 1 < p2.list.row_start.size() && fits; ++r) fits = p2.list.row_start[r + 1] - p2.list.row_start[r] == 1;
                 for (size_t k = 0; k < plan.steps.size() && fits; ++k) {   // nobody else reads the run's buffer
                     if (k >= i && k <= j) continue;
                     const Step& t = plan.steps[k];
-                    if (same(t.res, R) || (t.a.idx >= 0 && same(t.a, R)) || (t.b.idx >= 0 && same(t.b, R))) fits = false;
-                    if ((t.chained || t.list_chain) && (same(t.pre_a, R) || same(t.pre_b, R))) fits = false;
+                    if (t.res == R || reads(t, R)) fits = false;
                 }
                 std::vector<uint32_t> out_off(nc, 0u);
                 std::vector<double> coeff(nc, 0.0);
                 std::vector<char> seen(nc, 0);
-                for (size_t r = 0; r + 1 < p2.u32_a.size() && fits; ++r) {
-                    const uint32_t e = p2.u32_c[p2.u32_a[r]];
+                for (size_t r = 0; r + 1 < p2.list.row_start.size() && fits; ++r) {
+                    const uint32_t e = p2.list.entries[p2.list.row_start[r]];
                     const uint32_t roff = r_left ? (e & 0xffffu) : (e >> 16);
                     fits = roff < uint32_t(rl) && comp_of[roff] >= 0 && !seen[size_t(comp_of[roff])];
                     if (!fits) break;
                     seen[size_t(comp_of[roff])] = 1;
-                    out_off[size_t(comp_of[roff])] = p2.u32_b[r];
-                    coeff[size_t(comp_of[roff])] = p2.coeff[p2.u32_a[r]];
+                    out_off[size_t(comp_of[roff])] = p2.list.row_out[r];
+                    coeff[size_t(comp_of[roff])] = p2.list.coeff[p2.list.row_start[r]];
                 }
                 if (fits) {
-                    f.ew_scale = 1;
+                    f.ew.scale = 1;
                     f.res = p2.res;
                     f.b = S;
-                    f.u32_c = std::move(out_off);
-                    f.coeff = std::move(coeff);
-                    f.ew_scalar_off = 0;
-                    f.ew_canon_v = r_left ? p2.canon_a : p2.canon_b;
-                    f.ew_canon_s = r_left ? p2.canon_b : p2.canon_a;
-                    f.ew_s_is_left = r_left ? 0 : 1;
+                    f.ew.out_off = std::move(out_off);
+                    f.ew.coeff = std::move(coeff);
+                    f.ew.scalar_off = 0;
+                    f.ew.canon_v = r_left ? p2.canon_a : p2.canon_b;
+                    f.ew.canon_s = r_left ? p2.canon_b : p2.canon_a;
+                    f.ew.s_is_left = r_left ? 0 : 1;
                     f.beta = 0;
                     f.n_entries = p2.n_entries;
                     f.name += " * scalar -> " + p2.name;
@@ -2966,32 +2976,30 @@ static void fuse_elementwise_runs(Plan& plan) {
 // roundings, the scalar never leaves the wave, the row is streamed once from HBM.  Runs on the CSR form, before the ELL pass.
 static void fuse_reduce_scale(Plan& plan) {
     if (plan.flags & (GAAST_FLAG_NO_FUSION | GAAST_FLAG_DEBUG_NO_CHAIN)) return;
-    auto same = [](BufRef x, BufRef y) { return x.kind == y.kind && x.idx == y.idx; };
     for (size_t i = 0; i + 1 < plan.steps.size(); ++i) {
         Step& p1 = plan.steps[i];
-        if (p1.kind != Step::PRODUCT_CSR || p1.u32_b.size() != 1 || p1.beta != 0 || p1.res.kind != BufKind::NODE || p1.list_chain || p1.chained) continue;
-        if (plan.node_buffers[size_t(p1.res.idx)].row_len != 1 || p1.u32_c.size() < 64) continue;
+        if (p1.kind != Step::PRODUCT_CSR || p1.list.row_out.size() != 1 || p1.beta != 0 || p1.res.kind != BufKind::NODE || p1.chain.side) continue;
+        if (plan.node_buffers[size_t(p1.res.idx)].row_len != 1 || p1.list.entries.size() < 64) continue;
         const BufRef S = p1.res;
         size_t j = i + 1;
         int op = 0;
-        if (plan.steps[j].kind == Step::SUNARY && same(plan.steps[j].res, S) && plan.steps[j].sunary_off == 0) {
+        if (plan.steps[j].kind == Step::SUNARY && plan.steps[j].res == S && plan.steps[j].sunary_off == 0) {
             op = plan.steps[j].sunary_op == 0 ? 1 : 2;
             ++j;
         }
         if (j >= plan.steps.size()) continue;
         Step& p2 = plan.steps[j];
-        if (p2.kind != Step::PRODUCT_CSR || p2.beta != 0 || p2.list_chain || p2.chained) continue;
-        const bool s_left = same(p2.a, S), s_right = same(p2.b, S);
+        if (p2.kind != Step::PRODUCT_CSR || p2.beta != 0 || p2.chain.side) continue;
+        const bool s_left = p2.a == S, s_right = p2.b == S;
         if (s_left == s_right) continue;
         const BufRef xop = s_left ? p2.b : p2.a;
-        if (same(xop, S) || same(p2.res, p1.a) || same(p2.res, p1.b) || same(p2.res, xop)) continue;
+        if (xop == S || p2.res == p1.a || p2.res == p1.b || p2.res == xop) continue;
         bool ok = true;
-        for (size_t r = 0; r + 1 < p2.u32_a.size() && ok; ++r) ok = p2.u32_a[r + 1] - p2.u32_a[r] == 1;   // one term per row
+        for (size_t r = 0; r + 1 < p2.list.row_start.size() && ok; ++r) ok = p2.list.row_start[r + 1] - p2.list.row_start[r] == 1;   // one term per row
         for (size_t k = 0; k < plan.steps.size() && ok; ++k) {   // nobody else touches the scalar
             if (k == i || k == j || (op && k == i + 1)) continue;
             const Step& t = plan.steps[k];
-            if (same(t.res, S) || (t.a.idx >= 0 && same(t.a, S)) || (t.b.idx >= 0 && same(t.b, S))) ok = false;
-            if ((t.chained || t.list_chain) && (same(t.pre_a, S) || same(t.pre_b, S))) ok = false;
+            if (t.res == S || reads(t, S)) ok = false;
         }
         if (!ok) continue;
         Step f;
@@ -2999,21 +3007,21 @@ static void fuse_reduce_scale(Plan& plan) {
         f.res = p2.res;
         f.a = p1.a;
         f.b = p1.b;
-        f.pre_a = xop;
+        f.reduce.x = xop;
         f.canon_a = p1.canon_a;
         f.canon_b = p1.canon_b;
-        f.pre_canon_a = s_left ? p2.canon_b : p2.canon_a;
-        f.rs_canon_s = s_left ? p2.canon_a : p2.canon_b;
-        f.rs_op = op;
-        f.list_chain = s_left ? 1 : 2;   // (which side of the scaling the scalar is on; run_step reads it)
-        f.u32_a = p1.u32_c;
-        f.coeff = p1.coeff;
-        f.u32_b.resize(p2.u32_c.size());
-        f.coeff_b = p2.coeff;
-        for (size_t r = 0; r + 1 < p2.u32_a.size(); ++r) {
-            const uint32_t e = p2.u32_c[p2.u32_a[r]];
+        f.reduce.canon_x = s_left ? p2.canon_b : p2.canon_a;
+        f.reduce.canon_s = s_left ? p2.canon_a : p2.canon_b;
+        f.reduce.op = op;
+        f.reduce.s_is_left = s_left ? 1 : 0;
+        f.reduce.ent1 = p1.list.entries;
+        f.reduce.coeff1 = p1.list.coeff;
+        f.reduce.ent2.resize(p2.list.entries.size());
+        f.reduce.coeff2 = p2.list.coeff;
+        for (size_t r = 0; r + 1 < p2.list.row_start.size(); ++r) {
+            const uint32_t e = p2.list.entries[p2.list.row_start[r]];
             const uint32_t xoff = s_left ? (e >> 16) : (e & 0xffffu);
-            f.u32_b[r] = xoff | (p2.u32_b[r] << 16);
+            f.reduce.ent2[r] = xoff | (p2.list.row_out[r] << 16);
         }
         f.beta = 0;
         f.n_entries = p1.n_entries + p2.n_entries;
@@ -3021,10 +3029,11 @@ static void fuse_reduce_scale(Plan& plan) {
         // per component, (i, i), coefficient +-1, in any order; the scaling one row per component in place (x offset = out offset),
         // +-1; the row a whole number of 64 x 16 bytes with at most 32 components per lane.  (Whether the three rows ARE one row is
         // known when they are bound: run_step.)
-        if (!(plan.flags & GAAST_FLAG_EXACT_ORDER) && same(p1.a, p1.b) && same(xop, p1.a)) {
+        if (!(plan.flags & GAAST_FLAG_EXACT_ORDER) && p1.a == p1.b && xop == p1.a) {
             const size_t per_piece = 64 * (plan.dtype == GAAST_F32 ? 4 : 2);   // components a wave moves per 16-byte load
-            const size_t R = f.u32_a.size();
-            bool okw = R == f.u32_b.size() && R % per_piece == 0 && (R / per_piece) * (per_piece / 64) <= 32 && f.coeff.size() == R && f.coeff_b.size() == R;
+            const Step::Reduce& q = f.reduce;
+            const size_t R = q.ent1.size();
+            bool okw = R == q.ent2.size() && R % per_piece == 0 && (R / per_piece) * (per_piece / 64) <= 32 && q.coeff1.size() == R && q.coeff2.size() == R;
             const size_t pieces = okw ? R / per_piece : 0;
             okw = okw && (pieces == 1 || pieces == 2 || pieces == 4 || pieces == 8 || pieces == 16);
             std::vector<uint32_t> sg(128, 0u);
@@ -3035,33 +3044,33 @@ static void fuse_reduce_scale(Plan& plan) {
                 sg[size_t(which) * 64 + lane] |= 1u << (m * ec + e);
             };
             for (size_t t = 0; okw && t < R; ++t) {
-                const uint32_t li = f.u32_a[t] & 0xffffu, ri = f.u32_a[t] >> 16;
-                okw = li == ri && li < R && !seen1[li] && (f.coeff[t] == 1.0 || f.coeff[t] == -1.0);
+                const uint32_t li = q.ent1[t] & 0xffffu, ri = q.ent1[t] >> 16;
+                okw = li == ri && li < R && !seen1[li] && (q.coeff1[t] == 1.0 || q.coeff1[t] == -1.0);
                 if (okw) {
                     seen1[li] = 1;
-                    if (f.coeff[t] < 0) place(li, 0);
+                    if (q.coeff1[t] < 0) place(li, 0);
                 }
             }
             for (size_t r = 0; okw && r < R; ++r) {
-                const uint32_t xo = f.u32_b[r] & 0xffffu, oo = f.u32_b[r] >> 16;
-                okw = xo == oo && xo < R && !seen2[xo] && (f.coeff_b[r] == 1.0 || f.coeff_b[r] == -1.0);
+                const uint32_t xo = q.ent2[r] & 0xffffu, oo = q.ent2[r] >> 16;
+                okw = xo == oo && xo < R && !seen2[xo] && (q.coeff2[r] == 1.0 || q.coeff2[r] == -1.0);
                 if (okw) {
                     seen2[xo] = 1;
-                    if (f.coeff_b[r] < 0) place(xo, 1);
+                    if (q.coeff2[r] < 0) place(xo, 1);
                 }
             }
             if (okw) {
-                f.rs_wave = int(pieces);
-                f.u32_c = std::move(sg);
+                f.reduce.wave = int(pieces);
+                f.reduce.sign_words = std::move(sg);
             }
         }
-        f.name = "reduce_scale[" + std::to_string(p1.u32_c.size()) + " comp-muls -> scalar" + (op == 1 ? ", 1/s" : op == 2 ? ", sqrt(s)" : "") + ", " +
-                 std::to_string(p2.u32_c.size()) + " scaled components]";
+        f.name = "reduce_scale[" + std::to_string(p1.list.entries.size()) + " comp-muls -> scalar" + (op == 1 ? ", 1/s" : op == 2 ? ", sqrt(s)" : "") + ", " +
+                 std::to_string(p2.list.entries.size()) + " scaled components]";
         if (plan.node_dead.size() != plan.node_buffers.size()) plan.node_dead.assign(plan.node_buffers.size(), 0);
         plan.node_dead[size_t(S.idx)] = 1;
         // out offsets need 16 bits
         bool fits = true;
-        for (uint32_t o : p2.u32_b) fits = fits && o < 65536u;
+        for (uint32_t o : p2.list.row_out) fits = fits && o < 65536u;
         if (!fits) continue;
         std::vector<Step> kept;
         for (size_t k = 0; k < plan.steps.size(); ++k) {
@@ -3081,15 +3090,14 @@ static void fuse_reduce_scale(Plan& plan) {
 // Same order, same roundings; k_product_ell (and the copy) stay in charge when hiprtc is not available.
 static void jit_long_row_lists(Plan& plan) {
     if (plan.flags & (GAAST_FLAG_NO_FUSION | GAAST_FLAG_NO_JIT | GAAST_FLAG_DEBUG_JIT_FAILS | GAAST_FLAG_DEBUG_NO_CHAIN)) return;
-    auto same = [](BufRef x, BufRef y) { return x.kind == y.kind && x.idx == y.idx; };
     auto row_len = [&](BufRef r) -> int64_t {
         return r.kind == BufKind::NODE ? plan.node_buffers[size_t(r.idx)].row_len : r.kind == BufKind::INPUT ? plan.input_layouts[size_t(r.idx)].row_len
                                                                                                            : plan.out_layout.row_len;
     };
     for (size_t j = 0; j < plan.steps.size(); ++j) {
         Step& c = plan.steps[j];
-        if (c.kind != Step::PRODUCT_CSR || c.ell_width < 32 || !c.ell_bytes || c.list_chain || c.chain_jit) continue;
-        const int64_t rows = int64_t(c.u32_b.size());
+        if (c.kind != Step::PRODUCT_CSR || c.list.ell_width < 32 || !c.list.ell_bytes || c.chain.side || c.cj.on) continue;
+        const int64_t rows = int64_t(c.list.row_out.size());
         if (rows > 128 || c.a.idx < 0 || c.b.idx < 0) continue;
         const int64_t la = row_len(c.a), lb = row_len(c.b);
         // the covering copy right before it, into the same buffer?
@@ -3097,22 +3105,22 @@ static void jit_long_row_lists(Plan& plan) {
         bool fold = false;
         if (j > 0 && c.beta == 1) {
             const Step& ax = plan.steps[j - 1];
-            if (ax.kind == Step::AXPY && ax.beta == 0 && same(ax.res, c.res) && ax.a.kind == BufKind::INPUT && int64_t(ax.u32_a.size()) == rows) {
+            if (ax.kind == Step::AXPY && ax.beta == 0 && ax.res == c.res && ax.a.kind == BufKind::INPUT && int64_t(ax.axpy_map.size()) == rows) {
                 std::vector<int64_t> src_of(size_t(row_len(c.res)), -1);
-                for (uint32_t m : ax.u32_a) src_of[m & 0xffffu] = int64_t(m >> 16);
+                for (uint32_t m : ax.axpy_map) src_of[m & 0xffffu] = int64_t(m >> 16);
                 fold = true;
                 for (int64_t r = 0; r < rows && fold; ++r) {
-                    fold = src_of[c.u32_b[size_t(r)]] >= 0;
-                    init.push_back(uint32_t(fold ? src_of[c.u32_b[size_t(r)]] : 0));
+                    fold = src_of[c.list.row_out[size_t(r)]] >= 0;
+                    init.push_back(uint32_t(fold ? src_of[c.list.row_out[size_t(r)]] : 0));
                 }
             }
         }
         make_chain_jit(plan, c, nullptr, 0, 0, la, lb, 0, 1, true, fold ? &init : nullptr);
-        if (!c.chain_jit) continue;
-        c.list_jit = 1;
+        if (!c.cj.on) continue;
+        c.cj.single = 1;
         if (fold) {
-            c.fold_prev = 1;
-            c.pre_a = plan.steps[j - 1].a;   // the copy's source: the accumulators' starting values
+            c.cj.fold_prev = 1;
+            c.cj.init_src = plan.steps[j - 1].a;   // the copy's source: the accumulators' starting values
         }
     }
 }
@@ -3186,7 +3194,7 @@ void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab)
         Plan trial = plan;
         uniform_csr_to_ell(trial);
         chain_list_into_list(trial);
-        if (trial.steps.size() == 1 && trial.steps[0].list_chain) {
+        if (trial.steps.size() == 1 && trial.steps[0].chain.side) {
             plan = std::move(trial);
             return;
         }

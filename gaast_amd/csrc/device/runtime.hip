@@ -171,14 +171,19 @@ struct Launch {
     int items_per_block = 0;   // dense kernels
     int blocks_per_cu = 0;     // persistent kernels: resident workgroups per CU
     size_t pre_scratch_off = 0;   // chained: bytes, where the list's operand rows sit in the kernel's LDS (after its images)
-    // the step's tables on the device (their host images are dropped after the upload)
-    DevTable u32_a, u32_b, u32_c, i32_a, coeff, coeff_b, coeff_c;
-    DevTable pre_row_start, pre_entries, pre_coeff, pre_row_map, pre_row_scale;
-    DevTable cj_ent1, cj_pos1, cj_ent2, cj_out2;
-    std::vector<double> fused_coeff;   // FUSED: the general coefficients, passed by value
+    // the step's tables on the device, under the names of their host images in Step (those are dropped after the upload)
+    DevTable axpy_map, flip_offsets;
+    struct { DevTable row_start, row_out, entries, coeff; } list;
+    struct { DevTable left_map, right_map, out_map, spinor_out_map, left_scale, right_scale, out_scale; } dense;
+    struct { DevTable row_start, entries, coeff, row_map, row_scale; } pre;
+    struct { DevTable ent1, pos1, ent2, out2; } cj;
+    struct { DevTable prog, phase_tab; std::vector<double> general; } fused;   // (general: passed by value)
+    struct { DevTable sq, row_start, pairs, pair_coeff; } explog;
+    struct { DevTable ent1, coeff1, ent2, coeff2, sign_words; } reduce;
+    struct { DevTable ops, comp_off, out_off, coeff; } ew;
     void* domain = nullptr;            // the program's domain-error counter (borrowed)
     const LinmapDev* linmap = nullptr; // LINMAP: the program's map (borrowed)
-    // FUSED: the plan specialised through hiprtc, or a list chain (Step::chain_jit); a FUSED step also gets the same source
+    // FUSED: the plan specialised through hiprtc, or a list chain (Step::cj); a FUSED step also gets the same source
     // compiled with floating-point contraction (l * r + acc as ONE fused multiply-add: fewer roundings than the reference, so
     // within the tolerance contract but not its bits): built only without GAAST_FLAG_EXACT_ORDER, launched only when an item's
     // arithmetic outweighs its bytes (run_jit -- in practice: operands shared by all items)
@@ -392,9 +397,9 @@ int prepare_step(Launch& L, const Layout& la, const Layout& lb, std::string& ker
     const int n = L.n;
     constexpr bool is_f64 = std::is_same<T, double>::value;
     const std::string tn = is_f64 ? "double" : "float";
-    const std::string dg = s.degenerate ? "true" : "false";
+    const std::string dg = s.dense.degenerate ? "true" : "false";
     // (SCALED, CHAINED) template arguments as they appear in the kernel's name: ",true" = rescaled basis, ",false,true" = chained
-    const std::string vs = s.chained ? (s.scaled ? ",true,true" : ",false,true") : (s.scaled ? ",true" : "");
+    const std::string vs = s.dense.chained ? (s.dense.scaled ? ",true,true" : ",false,true") : (s.dense.scaled ? ",true" : "");
     switch (s.kind) {
     case Step::PRODUCT_CSR: {
         const size_t per_item = size_t(la.row_len + lb.row_len) * sizeof(T);
@@ -404,21 +409,21 @@ int prepare_step(Launch& L, const Layout& la, const Layout& lb, std::string& ker
                                std::to_string(g_max_lds) + "-byte LDS of the list kernels (" + s.name + ")");
         if (L.jit) {
             // the chain (or single long-row list) specialised through hiprtc (plan.cpp: make_chain_jit): static LDS, persistent workgroups
-            L.threads = s.cj_threads;
-            L.lds = s.cj_lds;
-            kernel = "gaast_chain<" + tn + ">[" + (s.list_jit ? "one list, " : "") + std::to_string(s.cj_ipb) + " items, " + std::to_string(s.cj_threads) + " threads" +
-                      (s.cj_split > 1 ? ", rows in " + std::to_string(s.cj_split) + " slices: re-ordered sums" : "") +
-                      (s.cj_fmt[1] >= 3 ? ", sign-sorted terms" : "") + "]";
+            L.threads = s.cj.threads;
+            L.lds = s.cj.lds;
+            kernel = "gaast_chain<" + tn + ">[" + (s.cj.single ? "one list, " : "") + std::to_string(s.cj.ipb) + " items, " + std::to_string(s.cj.threads) + " threads" +
+                      (s.cj.split > 1 ? ", rows in " + std::to_string(s.cj.split) + " slices: re-ordered sums" : "") +
+                      (s.cj.fmt[1] >= 3 ? ", sign-sorted terms" : "") + "]";
             int per_cu = 0;
             HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, L.jit.fn, L.threads, 0));
             L.blocks_per_cu = per_cu < 1 ? 1 : per_cu;
             return GAAST_OK;
         }
-        if (s.list_chain) {
+        if (s.chain.side) {
             // two lists in one launch, the mid row in LDS (plan.cpp: chain_list_into_list): IPB items per workgroup
-            L.lds = size_t(s.chain_ent2_lds) + size_t(s.chain_item_stride) * size_t(s.chain_ipb) * sizeof(T);
+            L.lds = size_t(s.chain.ent2_lds) + size_t(s.chain.item_stride) * size_t(s.chain.ipb) * sizeof(T);
             if (L.lds > g_max_lds) return set_err(kChainTooBig, "list chain does not fit in LDS (" + s.name + ")");
-            const int64_t pairs2 = int64_t(s.u32_b.size()) * s.chain_ipb;
+            const int64_t pairs2 = int64_t(s.list.row_out.size()) * s.chain.ipb;
             L.threads = int(std::min<int64_t>(512, std::max<int64_t>(256, (pairs2 + 63) / 64 * 64)));
             L.kern[0] = reinterpret_cast<const void*>(&k_product_ell_chain<T>);
             kernel = "k_product_ell_chain<" + tn + ">";
@@ -427,7 +432,7 @@ int prepare_step(Launch& L, const Layout& la, const Layout& lb, std::string& ker
         }
         L.lds = per_item;
         L.threads = 256;
-        if (s.ell_width > 0) {
+        if (s.list.ell_width > 0) {
             // items per pass over the list: as many as a 64 KiB share of LDS holds (at least one), at most 8
             int items = int((64 * 1024) / per_item);
             items = items >= 8 ? 8 : items >= 4 ? 4 : items >= 2 ? 2 : 1;
@@ -435,15 +440,15 @@ int prepare_step(Launch& L, const Layout& la, const Layout& lb, std::string& ker
             using KernE = void (*)(EllArgs<T>);
             const KernE tab[2][4] = {{&k_product_ell<T, 1, false>, &k_product_ell<T, 2, false>, &k_product_ell<T, 4, false>, &k_product_ell<T, 8, false>},
                                      {&k_product_ell<T, 1, true>, &k_product_ell<T, 2, true>, &k_product_ell<T, 4, true>, &k_product_ell<T, 8, true>}};
-            kernel = "k_product_ell<" + tn + ",1.." + std::to_string(items) + "," + (s.ell_bytes ? "true" : "false") + ">";
+            kernel = "k_product_ell<" + tn + ",1.." + std::to_string(items) + "," + (s.list.ell_bytes ? "true" : "false") + ">";
             for (int l2 = 0; (1 << l2) <= items; ++l2) {
-                L.kern[l2] = reinterpret_cast<const void*>(tab[s.ell_bytes ? 1 : 0][l2]);
+                L.kern[l2] = reinterpret_cast<const void*>(tab[s.list.ell_bytes ? 1 : 0][l2]);
                 if (int st = allow_lds(L.kern[l2], per_item << l2)) return st;
             }
             return GAAST_OK;
         }
         // enough items per block to give 256 threads work, within a 64 KiB LDS budget
-        const int n_rows = int(s.u32_b.size());
+        const int n_rows = int(s.list.row_out.size());
         int items = int((256 + n_rows - 1) / (n_rows > 0 ? n_rows : 1));
         const size_t budget = 64 * 1024;
         if (per_item * size_t(items) > budget) items = int(budget / per_item);
@@ -454,12 +459,13 @@ int prepare_step(Launch& L, const Layout& la, const Layout& lb, std::string& ker
         return allow_lds(L.kern[0], per_item * size_t(items));
     }
     case Step::PRODUCT_DENSE: {
-        if (s.use_spinor) {
+        switch (s.dense.family) {
+        case DenseFamily::SPINOR: {
             using KernS = void (*)(SpinorArgs);
-            const int m = s.use_spinor;
+            const int m = s.dense.spinor_m;
             const size_t D = size_t(1) << m, plane = (D * (D + 1) + 63) / 64 * 64;
             L.lds = (m == 6 ? 2 * plane + (is_f64 ? 0 : 16) : 2 * D * (D + 1)) * sizeof(T);   // k_gp_spinor12s: second plane 16 words further
-            const int lb5 = s.spinor_lam_bit;
+            const int lb5 = s.dense.spinor_lam_bit;
             KernS kern = nullptr;
             if (is_f64 && m == 6) kern = lb5 == 5 ? &k_gp_spinor12d<5> : lb5 == 4 ? &k_gp_spinor12d<4> : &k_gp_spinor12d<-1>;
             else if (is_f64 && m == 5) kern = lb5 == 4 ? &k_gp_spinor_wave1d<5, 4> : lb5 == 3 ? &k_gp_spinor_wave1d<5, 3> : &k_gp_spinor_wave1d<5, -1>;
@@ -479,21 +485,22 @@ int prepare_step(Launch& L, const Layout& la, const Layout& lb, std::string& ker
             if (int st = allow_lds(L.kern[0], L.lds)) return st;
             return resident_blocks(L.kern[0], L.threads, L.lds, &L.blocks_per_cu);
         }
-        if (s.use_mfma) {
+        case DenseFamily::MFMA32:
+        case DenseFamily::MFMA32P:
             if constexpr (!is_f64) {
                 const int wpi = 1 << (n - 10);                 // waves per item
                 L.threads = wpi > 4 ? wpi * 64 : 256;
                 L.items_per_block = (L.threads / 64) / wpi;
-                if (s.mfma32_pairs) {
+                if (s.dense.family == DenseFamily::MFMA32P) {
                     L.lds = (size_t(L.items_per_block) * size_t(4 << n) + 16) * sizeof(float);
                     if (L.lds > g_max_lds) return set_err(GAAST_ERR_UNIMPLEMENTED, "dense product does not fit in LDS");
                     using KernD = void (*)(DenseArgs<float>);
-                    const KernD kernp = pick_variant(s.scaled, s.chained, [&](auto sc, auto ch) -> KernD {
+                    const KernD kernp = pick_variant(s.dense.scaled, s.dense.chained, [&](auto sc, auto ch) -> KernD {
                         constexpr bool SC = decltype(sc)::value, CH = decltype(ch)::value;
-                        return n == 10   ? (s.degenerate ? &k_gp_mfma32p<true, 10, SC, CH> : &k_gp_mfma32p<false, 10, SC, CH>)
-                               : n == 11 ? (s.degenerate ? &k_gp_mfma32p<true, 11, SC, CH> : &k_gp_mfma32p<false, 11, SC, CH>)
-                               : n == 12 ? (s.degenerate ? &k_gp_mfma32p<true, 12, SC, CH> : &k_gp_mfma32p<false, 12, SC, CH>)
-                                         : (s.degenerate ? &k_gp_mfma32p<true, 13, SC, CH> : &k_gp_mfma32p<false, 13, SC, CH>);
+                        return n == 10   ? (s.dense.degenerate ? &k_gp_mfma32p<true, 10, SC, CH> : &k_gp_mfma32p<false, 10, SC, CH>)
+                               : n == 11 ? (s.dense.degenerate ? &k_gp_mfma32p<true, 11, SC, CH> : &k_gp_mfma32p<false, 11, SC, CH>)
+                               : n == 12 ? (s.dense.degenerate ? &k_gp_mfma32p<true, 12, SC, CH> : &k_gp_mfma32p<false, 12, SC, CH>)
+                                         : (s.dense.degenerate ? &k_gp_mfma32p<true, 13, SC, CH> : &k_gp_mfma32p<false, 13, SC, CH>);
                     });
                     L.kern[0] = reinterpret_cast<const void*>(kernp);
                     kernel = "k_gp_mfma32p<" + dg + "," + std::to_string(n) + vs + ">";
@@ -505,16 +512,16 @@ int prepare_step(Launch& L, const Layout& la, const Layout& lb, std::string& ker
                 using KernD = void (*)(DenseArgs<float>);
                 // (k_gp_mfma32 serves n = 14 only -- 16 waves and 128 KiB of LDS per item; n = 10 ... 13 run on k_gp_mfma32p)
                 if (L.threads != 1024) return set_err(GAAST_ERR_UNIMPLEMENTED, "k_gp_mfma32 is built for n = 14 only");
-                const KernD kern = pick_variant(s.scaled, s.chained, [&](auto sc, auto ch) -> KernD {
+                const KernD kern = pick_variant(s.dense.scaled, s.dense.chained, [&](auto sc, auto ch) -> KernD {
                     constexpr bool SC = decltype(sc)::value, CH = decltype(ch)::value;
-                    return s.degenerate ? &k_gp_mfma32<true, 1024, SC, CH> : &k_gp_mfma32<false, 1024, SC, CH>;
+                    return s.dense.degenerate ? &k_gp_mfma32<true, 1024, SC, CH> : &k_gp_mfma32<false, 1024, SC, CH>;
                 });
                 L.kern[0] = reinterpret_cast<const void*>(kern);
                 kernel = "k_gp_mfma32<" + dg + "," + std::to_string(L.threads) + vs + ">";
                 return allow_lds(L.kern[0], L.lds);
             }
-        }
-        if (s.use_mfma16 && s.use_mfma16d) {
+            break;
+        case DenseFamily::MFMA16X4: {
             // k_gp_mfma16x4<T>: one wave per 16 result columns, one item per workgroup (f64: n = 8 ... 12; f32: build switch)
             L.threads = 64 << (n - 8);
             L.items_per_block = 1;
@@ -523,25 +530,25 @@ int prepare_step(Launch& L, const Layout& la, const Layout& lb, std::string& ker
             using KernD = void (*)(DenseArgs<T>);
             // [0]: general staging; [1]: register prefetch (full, contiguous, 16-byte aligned rows at launch); [2]: ... and
             // every blade produced, nothing accumulated: straight-line result stores
-            auto pick = [&](auto mode_tag) -> KernD { return mfma16x4_kernel<T, decltype(mode_tag)::value, false, false>(n, s.degenerate != 0); };
+            auto pick = [&](auto mode_tag) -> KernD { return mfma16x4_kernel<T, decltype(mode_tag)::value, false, false>(n, s.dense.degenerate != 0); };
             // a rescaled basis (general diagonal metric): general staging and stores only; a chained product: every mode
-            const KernD kd = pick_variant(s.scaled, s.chained, [&](auto sc, auto ch) -> KernD {
-                return mfma16x4_kernel<T, 0, decltype(sc)::value, decltype(ch)::value>(n, s.degenerate != 0);
+            const KernD kd = pick_variant(s.dense.scaled, s.dense.chained, [&](auto sc, auto ch) -> KernD {
+                return mfma16x4_kernel<T, 0, decltype(sc)::value, decltype(ch)::value>(n, s.dense.degenerate != 0);
             });
-            auto pick_chained = [&](auto mode_tag) -> KernD { return mfma16x4_kernel<T, decltype(mode_tag)::value, false, true>(n, s.degenerate != 0); };
-            const bool chained_fast = s.chained && !s.scaled;
+            auto pick_chained = [&](auto mode_tag) -> KernD { return mfma16x4_kernel<T, decltype(mode_tag)::value, false, true>(n, s.dense.degenerate != 0); };
+            const bool chained_fast = s.dense.chained && !s.dense.scaled;
             const KernD kf = chained_fast ? pick_chained(std::integral_constant<int, 1>{}) : pick(std::integral_constant<int, 1>{}),
                         kw = chained_fast ? pick_chained(std::integral_constant<int, 2>{}) : pick(std::integral_constant<int, 2>{});
             if (!kd || !kf || !kw) return set_err(GAAST_ERR_UNIMPLEMENTED, "no k_gp_mfma16x4 instantiation for this dimension and value type");
             L.kern[0] = reinterpret_cast<const void*>(kd);
             L.kern[1] = reinterpret_cast<const void*>(kf);
             L.kern[2] = reinterpret_cast<const void*>(kw);
-            kernel = "k_gp_mfma16x4<" + tn + "," + dg + "," + std::to_string(n) + (s.scaled ? ",0" + vs + ">" : ",0|1|2" + vs + ">");   // staging / store mode: by alignment at launch
+            kernel = "k_gp_mfma16x4<" + tn + "," + dg + "," + std::to_string(n) + (s.dense.scaled ? ",0" + vs + ">" : ",0|1|2" + vs + ">");   // staging / store mode: by alignment at launch
             for (int v = 0; v < 3; ++v)
                 if (int st = allow_lds(L.kern[v], L.lds)) return st;
             return resident_blocks(L.kern[1], L.threads, L.lds, &L.blocks_per_cu);   // persistent workgroups
         }
-        if (s.use_mfma6) {
+        case DenseFamily::MFMA6: {
             // k_gp_mfma6<T>: one wave per item, persistent single-wave workgroups, 2 KiB (f32) / 4 KiB (f64) of operand images
             L.threads = 64 * GAAST_MFMA6_WAVES;
             L.items_per_block = GAAST_MFMA6_WAVES;
@@ -549,30 +556,32 @@ int prepare_step(Launch& L, const Layout& la, const Layout& lb, std::string& ker
             using KernD = void (*)(DenseArgs<T>);
             // [0]: any operands (partial grade sets, projected or accumulated results); [1]: full operands, every blade produced, nothing
             // accumulated -- straight-line item loop with counted waits
-            const KernD k6 = s.scaled ? &k_gp_mfma6<T, true, false> : &k_gp_mfma6<T, false, false>;
-            const KernD k6f = s.scaled ? &k_gp_mfma6<T, true, true> : &k_gp_mfma6<T, false, true>;
+            const KernD k6 = s.dense.scaled ? &k_gp_mfma6<T, true, false> : &k_gp_mfma6<T, false, false>;
+            const KernD k6f = s.dense.scaled ? &k_gp_mfma6<T, true, true> : &k_gp_mfma6<T, false, true>;
             L.kern[0] = reinterpret_cast<const void*>(k6);
             L.kern[1] = reinterpret_cast<const void*>(k6f);
-            kernel = "k_gp_mfma6<" + tn + (s.scaled ? ",true,0|1>" : ",false,0|1>");
+            kernel = "k_gp_mfma6<" + tn + (s.dense.scaled ? ",true,0|1>" : ",false,0|1>");
             return resident_blocks(L.kern[1], L.threads, L.lds, &L.blocks_per_cu);
         }
-        if (s.use_mfma7) {
+        case DenseFamily::MFMA7: {
             // k_gp_mfma7<T>: one wave per item, single-wave workgroups
             L.threads = 64;
             L.items_per_block = 1;
             L.lds = size_t(560) * sizeof(T);   // +B, -B, +A (u = 1 half 72 further), -A 144 further, 16 zeros
             using KernD = void (*)(DenseArgs<T>);
-            const KernD kd = pick_variant(s.scaled, s.chained, [&](auto sc, auto ch) -> KernD {
+            const KernD kd = pick_variant(s.dense.scaled, s.dense.chained, [&](auto sc, auto ch) -> KernD {
                 return &k_gp_mfma7<T, 0, decltype(sc)::value, decltype(ch)::value>;
             });
-            const bool chained_fast = s.chained && !s.scaled;
+            const bool chained_fast = s.dense.chained && !s.dense.scaled;
             const KernD kf = chained_fast ? &k_gp_mfma7<T, 1, false, true> : &k_gp_mfma7<T, 1>;
             const KernD kw = chained_fast ? &k_gp_mfma7<T, 2, false, true> : &k_gp_mfma7<T, 2>;
             L.kern[0] = reinterpret_cast<const void*>(kd);
             L.kern[1] = reinterpret_cast<const void*>(kf);
             L.kern[2] = reinterpret_cast<const void*>(kw);
-            kernel = "k_gp_mfma7<" + tn + (s.scaled ? ",0" + vs + ">" : ",0|1|2" + vs + ">");   // (null vectors: run-time, no instantiation of their own)
+            kernel = "k_gp_mfma7<" + tn + (s.dense.scaled ? ",0" + vs + ">" : ",0|1|2" + vs + ">");   // (null vectors: run-time, no instantiation of their own)
             return resident_blocks(L.kern[1], L.threads, L.lds, &L.blocks_per_cu);   // persistent single-wave workgroups
+        }
+        case DenseFamily::VECTOR_FMA: break;
         }
         const int lpi = 1 << (n - 4);
         L.threads = lpi > 256 ? lpi : 256;
@@ -581,22 +590,22 @@ int prepare_step(Launch& L, const Layout& la, const Layout& lb, std::string& ker
         if (L.lds > g_max_lds)
             return set_err(GAAST_ERR_UNIMPLEMENTED, "dense product of dimension " + std::to_string(n) + " does not fit in LDS");
         using KernD = void (*)(DenseArgs<T>);
-        const KernD kern = pick_variant(s.scaled, s.chained, [&](auto sc, auto ch) -> KernD {
+        const KernD kern = pick_variant(s.dense.scaled, s.dense.chained, [&](auto sc, auto ch) -> KernD {
             constexpr bool SC = decltype(sc)::value, CH = decltype(ch)::value;
-            if (s.neg_lo_all)
-                return L.threads == 256 ? (s.degenerate ? &k_gp_dense<T, true, 256, true, SC, CH> : &k_gp_dense<T, false, 256, true, SC, CH>)
-                                        : (s.degenerate ? &k_gp_dense<T, true, 512, true, SC, CH> : &k_gp_dense<T, false, 512, true, SC, CH>);
-            return L.threads == 256 ? (s.degenerate ? &k_gp_dense<T, true, 256, false, SC, CH> : &k_gp_dense<T, false, 256, false, SC, CH>)
-                                    : (s.degenerate ? &k_gp_dense<T, true, 512, false, SC, CH> : &k_gp_dense<T, false, 512, false, SC, CH>);
+            if (s.dense.neg_lo_all)
+                return L.threads == 256 ? (s.dense.degenerate ? &k_gp_dense<T, true, 256, true, SC, CH> : &k_gp_dense<T, false, 256, true, SC, CH>)
+                                        : (s.dense.degenerate ? &k_gp_dense<T, true, 512, true, SC, CH> : &k_gp_dense<T, false, 512, true, SC, CH>);
+            return L.threads == 256 ? (s.dense.degenerate ? &k_gp_dense<T, true, 256, false, SC, CH> : &k_gp_dense<T, false, 256, false, SC, CH>)
+                                    : (s.dense.degenerate ? &k_gp_dense<T, true, 512, false, SC, CH> : &k_gp_dense<T, false, 512, false, SC, CH>);
         });
         L.kern[0] = reinterpret_cast<const void*>(kern);
-        kernel = "k_gp_dense<" + tn + "," + dg + "," + std::to_string(L.threads) + "," + (s.neg_lo_all ? "true" : "false") + vs + ">";
+        kernel = "k_gp_dense<" + tn + "," + dg + "," + std::to_string(L.threads) + "," + (s.dense.neg_lo_all ? "true" : "false") + vs + ">";
         if (int st = allow_lds(L.kern[0], L.lds)) return st;
         // persistent workgroups: as many as are resident at once (register- and LDS-limited)
         return resident_blocks(L.kern[0], L.threads, L.lds, &L.blocks_per_cu);
     }
     case Step::ELEMENTWISE:
-        kernel = "k_elementwise<" + tn + (s.ew_ops <= 4 ? ",4>" : ",8>");
+        kernel = "k_elementwise<" + tn + (s.ew.n_ops <= 4 ? ",4>" : ",8>");
         return GAAST_OK;
     case Step::AXPY: kernel = "k_axpy_map<" + tn + ">"; return GAAST_OK;
     case Step::FLIP: kernel = "k_flip<" + tn + ">"; return GAAST_OK;
@@ -605,10 +614,10 @@ int prepare_step(Launch& L, const Layout& la, const Layout& lb, std::string& ker
         L.threads = 256;
         L.kern[0] = reinterpret_cast<const void*>(&k_reduce_scale<T>);
         kernel = "k_reduce_scale<" + tn + ">";
-        if (s.rs_wave) {   // tolerance mode: one wave per item, the row read once -- taken at launch when the three rows are one (run_step)
+        if (s.reduce.wave) {   // tolerance mode: one wave per item, the row read once -- taken at launch when the three rows are one (run_step)
             using KernW = void (*)(ReduceScaleArgs<T>, const uint32_t*);
             KernW kw = nullptr;
-            switch (s.rs_wave) {
+            switch (s.reduce.wave) {
             case 1: kw = &k_reduce_scale_wave<T, 1>; break;
             case 2: kw = &k_reduce_scale_wave<T, 2>; break;
             case 4: kw = &k_reduce_scale_wave<T, 4>; break;
@@ -619,14 +628,14 @@ int prepare_step(Launch& L, const Layout& la, const Layout& lb, std::string& ker
             default: break;
             }
             L.kern[1] = reinterpret_cast<const void*>(kw);
-            if (kw) kernel += " | k_reduce_scale_wave<" + tn + "," + std::to_string(s.rs_wave) + "> (lane-parallel sums) when the rows are one";
-            else s.rs_wave = 0;
+            if (kw) kernel += " | k_reduce_scale_wave<" + tn + "," + std::to_string(s.reduce.wave) + "> (lane-parallel sums) when the rows are one";
+            else s.reduce.wave = 0;
         }
         return resident_blocks(L.kern[0], L.threads, 0, &L.blocks_per_cu);
     }
     case Step::FUSED: {
         if (L.jit) return GAAST_OK;
-        const size_t lds = (size_t(s.fused_slab) * FUSED_ITEMS + 8) * sizeof(T);
+        const size_t lds = (size_t(s.fused.slab) * FUSED_ITEMS + 8) * sizeof(T);
         return allow_lds(reinterpret_cast<const void*>(&k_ast_fused<T>), lds);
     }
     case Step::LINMAP:
@@ -636,24 +645,29 @@ int prepare_step(Launch& L, const Layout& la, const Layout& lb, std::string& ker
     }
 }
 
+// the operands of a launch beyond a and b (Step: pre.a, pre.b, reduce.x, cj.init_src); null where the step has none
+struct Extra {
+    Bound pre_a{nullptr, 0}, pre_b{nullptr, 0}, scaled_row{nullptr, 0}, init{nullptr, 0};
+};
+
 template <typename T>
 int run_step(const Launch& L, const Bound& res, const Bound& a, const Bound& b, const Layout& la, const Layout& lb, int64_t batch,
-             const Bound& pre_a = Bound{nullptr, 0}, const Bound& pre_b = Bound{nullptr, 0}) {
+             const Extra& x = Extra()) {
     const Step& s = L.s;
     const int n = L.n;
     switch (s.kind) {
     case Step::ZERO: return GAAST_OK;  // handled by the caller (needs the row length)
     case Step::AXPY: {
-        const int nm = int(L.u32_a.count);
+        const int nm = int(L.axpy_map.count);
         hipLaunchKernelGGL(k_axpy_map<T>, dim3(grid_for(batch * nm, 256)), dim3(256), 0, g_stream,
                            static_cast<T*>(res.ptr), res.stride, static_cast<const T*>(a.ptr), a.stride,
-                           L.u32_a.as<uint32_t>(), nm, batch, s.beta);
+                           L.axpy_map.as<uint32_t>(), nm, batch, s.beta);
         break;
     }
     case Step::FLIP: {
-        const int nm = int(L.u32_a.count);
+        const int nm = int(L.flip_offsets.count);
         hipLaunchKernelGGL(k_flip<T>, dim3(grid_for(batch * nm, 256)), dim3(256), 0, g_stream,
-                           static_cast<T*>(res.ptr), res.stride, L.u32_a.as<uint32_t>(), nm, batch);
+                           static_cast<T*>(res.ptr), res.stride, L.flip_offsets.as<uint32_t>(), nm, batch);
         break;
     }
     case Step::SUNARY:
@@ -664,26 +678,26 @@ int run_step(const Launch& L, const Bound& res, const Bound& a, const Bound& b, 
         ReduceScaleArgs<T> q;
         q.l1 = static_cast<const T*>(a.ptr);
         q.r1 = static_cast<const T*>(b.ptr);
-        q.x = static_cast<const T*>(pre_a.ptr);
+        q.x = static_cast<const T*>(x.scaled_row.ptr);
         q.out = static_cast<T*>(res.ptr);
         q.l1_stride = a.stride;
         q.r1_stride = b.stride;
-        q.x_stride = pre_a.stride;
+        q.x_stride = x.scaled_row.stride;
         q.out_stride = res.stride;
-        q.ent1 = L.u32_a.as<uint32_t>();
-        q.coeff1 = L.coeff.as<T>();
-        q.ent2 = L.u32_b.as<uint32_t>();
-        q.coeff2 = L.coeff_b.as<T>();
-        q.n1 = int(L.u32_a.count);
-        q.n2 = int(L.u32_b.count);
+        q.ent1 = L.reduce.ent1.as<uint32_t>();
+        q.coeff1 = L.reduce.coeff1.as<T>();
+        q.ent2 = L.reduce.ent2.as<uint32_t>();
+        q.coeff2 = L.reduce.coeff2.as<T>();
+        q.n1 = int(L.reduce.ent1.count);
+        q.n2 = int(L.reduce.ent2.count);
         q.canon_l1 = s.canon_a;
         q.canon_r1 = s.canon_b;
-        q.canon_x = s.pre_canon_a;
-        q.canon_s = s.rs_canon_s;
-        q.s_is_left = s.list_chain == 1;
-        q.op = s.rs_op;
+        q.canon_x = s.reduce.canon_x;
+        q.canon_s = s.reduce.canon_s;
+        q.s_is_left = s.reduce.s_is_left;
+        q.op = s.reduce.op;
         q.batch = batch;
-        if (s.rs_wave && L.kern[1] && a.ptr == b.ptr && a.ptr == pre_a.ptr && a.stride == b.stride && a.stride == pre_a.stride &&
+        if (s.reduce.wave && L.kern[1] && a.ptr == b.ptr && a.ptr == x.scaled_row.ptr && a.stride == b.stride && a.stride == x.scaled_row.stride &&
             (reinterpret_cast<uintptr_t>(a.ptr) & 15u) == 0 && (size_t(a.stride) * sizeof(T)) % 16 == 0 &&
             (reinterpret_cast<uintptr_t>(res.ptr) & 15u) == 0 && (size_t(res.stride) * sizeof(T)) % 16 == 0 && res.ptr != a.ptr) {
             // one wave per item, four per workgroup, persistent
@@ -692,7 +706,7 @@ int run_step(const Launch& L, const Bound& res, const Bound& a, const Bound& b, 
             blocks = std::min<int64_t>(blocks, int64_t(g_num_cu) * 8);
             L.variant = 1;
             hipLaunchKernelGGL(reinterpret_cast<KernW>(const_cast<void*>(L.kern[1])), dim3(unsigned(blocks)), dim3(256), 0, g_stream, q,
-                               L.u32_c.as<uint32_t>());
+                               L.reduce.sign_words.as<uint32_t>());
             break;
         }
         // sixteen items per wave, four waves per workgroup, persistent: as many workgroups as are resident at once
@@ -707,18 +721,18 @@ int run_step(const Launch& L, const Bound& res, const Bound& a, const Bound& b, 
         q.arg = static_cast<const T*>(a.ptr);
         q.res_stride = res.stride;
         q.arg_stride = a.stride;
-        q.op = s.explog_op;
-        q.m = s.explog_m;
-        q.m_res = s.explog_mres;
-        q.arg_k = s.explog_arg_k;
-        q.arg_0 = s.explog_arg_0;
-        q.res_k = s.explog_res_k;
-        q.res_0 = s.explog_res_0;
-        q.sq = L.coeff.as<T>();
-        q.row_start = L.u32_a.as<uint32_t>();
-        q.pairs = L.u32_c.as<uint32_t>();
-        q.pair_coeff = L.coeff_b.as<T>();
-        q.n_rows = int(L.u32_a.count) - 1;
+        q.op = s.explog.op;
+        q.m = s.explog.m;
+        q.m_res = s.explog.mres;
+        q.arg_k = s.explog.arg_k;
+        q.arg_0 = s.explog.arg_0;
+        q.res_k = s.explog.res_k;
+        q.res_0 = s.explog.res_0;
+        q.sq = L.explog.sq.as<T>();
+        q.row_start = L.explog.row_start.as<uint32_t>();
+        q.pairs = L.explog.pairs.as<uint32_t>();
+        q.pair_coeff = L.explog.pair_coeff.as<T>();
+        q.n_rows = int(L.explog.row_start.count) - 1;
         q.dom = static_cast<unsigned long long*>(L.domain);
         q.batch = batch;
         hipLaunchKernelGGL(k_exp_log<T>, dim3(grid_for(batch, 256)), dim3(256), 0, g_stream, q);
@@ -726,66 +740,66 @@ int run_step(const Launch& L, const Bound& res, const Bound& a, const Bound& b, 
     }
     case Step::PRODUCT_CSR: {
         if (L.jit) {
-            const bool mid_left = s.list_chain == 1;
-            const Bound& other = s.list_jit ? b : s.chain_alias ? pre_a : (mid_left ? b : a);
+            const bool mid_left = s.chain.side == 1, single = s.cj.single != 0;
+            const Bound& other = single ? b : s.chain.alias ? x.pre_a : (mid_left ? b : a);
             // a single list: its left operand is staged as the "mid" row (pointer l1), its right one is list 2's own operand (r2)
-            const void *l1 = s.list_jit ? a.ptr : pre_a.ptr, *r1 = s.list_jit ? nullptr : pre_b.ptr, *r2 = other.ptr;
-            long long s_l1 = s.list_jit ? a.stride : pre_a.stride, s_r1 = s.list_jit ? 0 : pre_b.stride, s_r2 = other.stride, s_out = res.stride, nb = batch;
+            const void *l1 = single ? a.ptr : x.pre_a.ptr, *r1 = single ? nullptr : x.pre_b.ptr, *r2 = other.ptr;
+            long long s_l1 = single ? a.stride : x.pre_a.stride, s_r1 = single ? 0 : x.pre_b.stride, s_r2 = other.stride, s_out = res.stride, nb = batch;
             void* optr = res.ptr;
-            const void *e1 = L.cj_ent1.ptr, *p1 = L.cj_pos1.ptr, *e2 = L.cj_ent2.ptr, *o2 = L.cj_out2.ptr;
-            const void* init = (s.list_jit && s.fold_prev) ? pre_a.ptr : nullptr;
-            long long s_init = (s.list_jit && s.fold_prev) ? pre_a.stride : 0;
+            const void *e1 = L.cj.ent1.ptr, *p1 = L.cj.pos1.ptr, *e2 = L.cj.ent2.ptr, *o2 = L.cj.out2.ptr;
+            const void* init = x.init.ptr;   // the folded copy's source, if any
+            long long s_init = x.init.stride;
             void* args[] = {&l1, &s_l1, &r1, &s_r1, &r2, &s_r2, &optr, &s_out, &e1, &p1, &e2, &o2, &nb, &init, &s_init};
-            int64_t blocks = (batch + s.cj_ipb - 1) / s.cj_ipb;
+            int64_t blocks = (batch + s.cj.ipb - 1) / s.cj.ipb;
             blocks = std::min<int64_t>(blocks, int64_t(g_num_cu) * L.blocks_per_cu);
             // (the argument block is copied into the dispatch packet at call time, like run_jit's)
             HIP_TRY(hipModuleLaunchKernel(L.jit.fn, unsigned(blocks), 1, 1, unsigned(L.threads), 1, 1, 0, g_stream,
                                           args, nullptr));
             break;
         }
-        if (s.list_chain) {
+        if (s.chain.side) {
             EllChainArgs<T> q;
-            const bool mid_left = s.list_chain == 1;
+            const bool mid_left = s.chain.side == 1;
             const Bound& other = mid_left ? b : a;
             const Layout& lo = mid_left ? lb : la;
-            q.l1 = static_cast<const T*>(pre_a.ptr);
-            q.r1 = static_cast<const T*>(pre_b.ptr);
+            q.l1 = static_cast<const T*>(x.pre_a.ptr);
+            q.r1 = static_cast<const T*>(x.pre_b.ptr);
             q.r2 = static_cast<const T*>(other.ptr);
             q.out = static_cast<T*>(res.ptr);
-            q.l1_stride = pre_a.stride;
-            q.r1_stride = pre_b.stride;
+            q.l1_stride = x.pre_a.stride;
+            q.r1_stride = x.pre_b.stride;
             q.r2_stride = other.stride;
             q.out_stride = res.stride;
-            q.l1_len = s.pre_left_len;
-            q.r1_len = s.pre_right_len;
+            q.l1_len = s.pre.left_len;
+            q.r1_len = s.pre.right_len;
             q.r2_len = int(lo.row_len);
-            q.mid_len = s.chain_mid_len;
-            q.canon_l1 = s.pre_canon_a;
-            q.canon_r1 = s.pre_canon_b;
+            q.mid_len = s.chain.mid_len;
+            q.canon_l1 = s.pre.canon_a;
+            q.canon_r1 = s.pre.canon_b;
             q.canon_r2 = mid_left ? s.canon_b : s.canon_a;
-            q.canon_mid = s.chain_canon_mid;
-            q.ent1 = L.pre_entries.as<uint32_t>();
-            q.pos1 = L.pre_row_map.as<uint32_t>();
-            q.rows1 = int(L.pre_row_map.count);
-            q.width1 = s.pre_width;
-            q.ent2 = L.u32_c.as<uint32_t>();
-            q.out2 = L.u32_b.as<uint32_t>();
-            q.rows2 = int(L.u32_b.count);
-            q.width2 = s.ell_width;
+            q.canon_mid = s.chain.canon_mid;
+            q.ent1 = L.pre.entries.as<uint32_t>();
+            q.pos1 = L.pre.row_map.as<uint32_t>();
+            q.rows1 = int(L.pre.row_map.count);
+            q.width1 = s.pre.width;
+            q.ent2 = L.list.entries.as<uint32_t>();
+            q.out2 = L.list.row_out.as<uint32_t>();
+            q.rows2 = int(L.list.row_out.count);
+            q.width2 = s.list.ell_width;
             q.mid_is_left = mid_left ? 1 : 0;
-            q.r2_alias = s.chain_alias;
-            q.mid_covered = s.chain_covered;
+            q.r2_alias = s.chain.alias;
+            q.mid_covered = s.chain.covered;
             q.beta = s.beta;
-            q.ipb = s.chain_ipb;
-            q.item_stride = s.chain_item_stride;
+            q.ipb = s.chain.ipb;
+            q.item_stride = s.chain.item_stride;
             q.batch = batch;
-            q.ent2_lds_bytes = s.chain_ent2_lds;
-            int64_t blocks = (batch + s.chain_ipb - 1) / s.chain_ipb;
+            q.ent2_lds_bytes = s.chain.ent2_lds;
+            int64_t blocks = (batch + s.chain.ipb - 1) / s.chain.ipb;
             if (L.blocks_per_cu > 0) blocks = std::min<int64_t>(blocks, int64_t(g_num_cu) * L.blocks_per_cu);
             hipLaunchKernelGGL(k_product_ell_chain<T>, dim3(unsigned(blocks)), dim3(unsigned(L.threads)), L.lds, g_stream, q);
             break;
         }
-        if (s.ell_width > 0) {
+        if (s.list.ell_width > 0) {
             EllArgs<T> q;
             q.left = static_cast<const T*>(a.ptr);
             q.right = static_cast<const T*>(b.ptr);
@@ -797,10 +811,10 @@ int run_step(const Launch& L, const Bound& res, const Bound& a, const Bound& b, 
             q.right_len = int(lb.row_len);
             q.canon_left = s.canon_a;
             q.canon_right = s.canon_b;
-            q.row_out = L.u32_b.as<uint32_t>();
-            q.entries = L.u32_c.as<uint32_t>();
-            q.n_rows = int(L.u32_b.count);
-            q.width = s.ell_width;
+            q.row_out = L.list.row_out.as<uint32_t>();
+            q.entries = L.list.entries.as<uint32_t>();
+            q.n_rows = int(L.list.row_out.count);
+            q.width = s.list.ell_width;
             q.beta = s.beta;
             q.batch = batch;
             int l2 = L.max_items >= 8 ? 3 : L.max_items >= 4 ? 2 : L.max_items >= 2 ? 1 : 0;
@@ -823,11 +837,11 @@ int run_step(const Launch& L, const Bound& res, const Bound& a, const Bound& b, 
         p.right_len = int(lb.row_len);
         p.canon_left = s.canon_a;
         p.canon_right = s.canon_b;
-        p.row_start = L.u32_a.as<uint32_t>();
-        p.row_out = L.u32_b.as<uint32_t>();
-        p.entries = L.u32_c.as<uint32_t>();
-        p.coeff = L.coeff.as<T>();
-        p.n_rows = int(L.u32_b.count);
+        p.row_start = L.list.row_start.as<uint32_t>();
+        p.row_out = L.list.row_out.as<uint32_t>();
+        p.entries = L.list.entries.as<uint32_t>();
+        p.coeff = L.list.coeff.as<T>();
+        p.n_rows = int(L.list.row_out.count);
         p.beta = s.beta;
         p.batch = batch;
         int items = L.max_items;
@@ -841,7 +855,7 @@ int run_step(const Launch& L, const Bound& res, const Bound& a, const Bound& b, 
     case Step::ELEMENTWISE: return GAAST_OK;  // launched by run_elementwise (needs every source buffer)
     case Step::LINMAP: return launch_linmap<T>(*L.linmap, la, a, res, batch);
     case Step::PRODUCT_DENSE: {
-        if (s.use_spinor) {
+        if (s.dense.family == DenseFamily::SPINOR) {
             SpinorArgs q;
             q.left = a.ptr;
             q.right = b.ptr;
@@ -849,26 +863,26 @@ int run_step(const Launch& L, const Bound& res, const Bound& a, const Bound& b, 
             q.left_stride = a.stride;
             q.right_stride = b.stride;
             q.out_stride = res.stride;
-            q.left_map = L.u32_a.as<uint16_t>();
-            q.right_map = L.u32_b.as<uint16_t>();
-            q.left_full = s.left_full;
-            q.right_full = s.right_full;
-            q.out_map = L.u32_c.as<uint16_t>();
-            q.out_full = s.out_full;
+            q.left_map = L.dense.left_map.as<uint16_t>();
+            q.right_map = L.dense.right_map.as<uint16_t>();
+            q.left_full = s.dense.left_full;
+            q.right_full = s.dense.right_full;
+            q.out_map = L.dense.spinor_out_map.as<uint16_t>();
+            q.out_full = s.dense.out_full;
             q.left_len = int(la.row_len);
             q.right_len = int(lb.row_len);
             q.canon_left = s.canon_a;
             q.canon_right = s.canon_b;
             q.beta = s.beta;
             q.batch = batch;
-            q.has_alpha = s.spinor_has_alpha;
+            q.has_alpha = s.dense.spinor_has_alpha;
             using KernS = void (*)(SpinorArgs);
             int64_t blocks = int64_t(g_num_cu) * L.blocks_per_cu;
             if (blocks > batch) blocks = batch;
             auto aligned16 = [](const void* ptr, int64_t stride) {
                 return (reinterpret_cast<uintptr_t>(ptr) % 16 == 0) && ((size_t(stride) * sizeof(T)) % 16 == 0);
             };
-            const bool fast = L.kern[1] && s.left_full && s.right_full && s.out_full && !s.beta && q.left_len == 4096 && q.right_len == 4096 &&
+            const bool fast = L.kern[1] && s.dense.left_full && s.dense.right_full && s.dense.out_full && !s.beta && q.left_len == 4096 && q.right_len == 4096 &&
                               aligned16(a.ptr, a.stride) && aligned16(b.ptr, b.stride) && aligned16(res.ptr, res.stride);
             L.variant = fast ? 1 : 0;
             hipLaunchKernelGGL(reinterpret_cast<KernS>(const_cast<void*>(L.kern[fast ? 1 : 0])), dim3(unsigned(blocks)),
@@ -882,25 +896,25 @@ int run_step(const Launch& L, const Bound& res, const Bound& a, const Bound& b, 
         p.left_stride = a.stride;
         p.right_stride = b.stride;
         p.out_stride = res.stride;
-        p.left_map = L.u32_a.as<uint32_t>();
-        p.right_map = L.u32_b.as<uint32_t>();
-        p.left_count = int(L.u32_a.count);
-        p.right_count = int(L.u32_b.count);
-        p.left_full = s.left_full;
-        p.right_full = s.right_full;
+        p.left_map = L.dense.left_map.as<uint32_t>();
+        p.right_map = L.dense.right_map.as<uint32_t>();
+        p.left_count = int(L.dense.left_map.count);
+        p.right_count = int(L.dense.right_map.count);
+        p.left_full = s.dense.left_full;
+        p.right_full = s.dense.right_full;
         // vector loads need 16-byte aligned rows: base pointer and row stride
         auto aligned = [](const void* ptr, int64_t stride) {
             return (reinterpret_cast<uintptr_t>(ptr) % 16 == 0) && ((size_t(stride) * sizeof(T)) % 16 == 0);
         };
-        p.left_contig = s.left_contig && aligned(a.ptr, a.stride);
-        p.right_contig = s.right_contig && aligned(b.ptr, b.stride);
-        p.out_map = L.i32_a.as<int32_t>();
+        p.left_contig = s.dense.left_contig && aligned(a.ptr, a.stride);
+        p.right_contig = s.dense.right_contig && aligned(b.ptr, b.stride);
+        p.out_map = L.dense.out_map.as<int32_t>();
         p.canon_left = s.canon_a;
         p.canon_right = s.canon_b;
         p.n = n;
-        p.neg_hi = s.neg_hi;
-        p.zero_hi = s.zero_hi;
-        p.neg_lo = s.neg_lo;
+        p.neg_hi = s.dense.neg_hi;
+        p.zero_hi = s.dense.zero_hi;
+        p.neg_lo = s.dense.neg_lo;
         p.beta = s.beta;
         p.batch = batch;
         using KernD = void (*)(DenseArgs<T>);
@@ -910,39 +924,42 @@ int run_step(const Launch& L, const Bound& res, const Bound& a, const Bound& b, 
             blocks = int64_t(g_num_cu) * L.blocks_per_cu;
             if (blocks > groups) blocks = groups;
         }
-        p.left_signs = s.left_signs;
-        p.out_signs = s.out_signs;
+        p.left_signs = s.dense.left_signs;
+        p.out_signs = s.dense.out_signs;
         p.pre_left = p.pre_right = nullptr;
         p.pre_entries = nullptr;
-        if (s.chained) {   // the left operand is a comp-mul list over two other rows, evaluated in LDS while staging
-            p.pre_left = static_cast<const T*>(pre_a.ptr);
-            p.pre_right = static_cast<const T*>(pre_b.ptr);
-            p.pre_left_stride = pre_a.stride;
-            p.pre_right_stride = pre_b.stride;
-            p.pre_left_len = s.pre_left_len;
-            p.pre_right_len = s.pre_right_len;
-            p.pre_canon_left = s.pre_canon_a;
-            p.pre_canon_right = s.pre_canon_b;
-            p.pre_row_start = L.pre_row_start.as<uint32_t>();
-            p.pre_entries = L.pre_entries.as<uint32_t>();
-            p.pre_coeff = L.pre_coeff.as<T>();
-            p.pre_row_map = L.pre_row_map.as<uint32_t>();
-            p.pre_row_scale = L.pre_row_scale.as<T>();
-            p.pre_rows = int(L.pre_row_map.count);
-            p.pre_width = s.pre_width;
+        if (s.dense.chained) {   // the left operand is a comp-mul list over two other rows, evaluated in LDS while staging
+            p.pre_left = static_cast<const T*>(x.pre_a.ptr);
+            p.pre_right = static_cast<const T*>(x.pre_b.ptr);
+            p.pre_left_stride = x.pre_a.stride;
+            p.pre_right_stride = x.pre_b.stride;
+            p.pre_left_len = s.pre.left_len;
+            p.pre_right_len = s.pre.right_len;
+            p.pre_canon_left = s.pre.canon_a;
+            p.pre_canon_right = s.pre.canon_b;
+            p.pre_row_start = L.pre.row_start.as<uint32_t>();
+            p.pre_entries = L.pre.entries.as<uint32_t>();
+            p.pre_coeff = L.pre.coeff.as<T>();
+            p.pre_row_map = L.pre.row_map.as<uint32_t>();
+            p.pre_row_scale = L.pre.row_scale.as<T>();
+            p.pre_rows = int(L.pre.row_map.count);
+            p.pre_width = s.pre.width;
             p.pre_scratch = int(L.pre_scratch_off / sizeof(T));
             p.left_count = 0;
         }
-        p.left_scale = s.scaled ? L.coeff.as<T>() : nullptr;
-        p.right_scale = s.scaled ? L.coeff_b.as<T>() : nullptr;
-        p.out_scale = s.scaled ? L.coeff_c.as<T>() : nullptr;
+        p.left_scale = s.dense.scaled ? L.dense.left_scale.as<T>() : nullptr;
+        p.right_scale = s.dense.scaled ? L.dense.right_scale.as<T>() : nullptr;
+        p.out_scale = s.dense.scaled ? L.dense.out_scale.as<T>() : nullptr;
         // register-prefetch staging: full, contiguous, aligned operand rows; a chained step computes its left operand from a list
         // (then only the right row is prefetched)
-        const bool prefetch = s.use_mfma6 ? (p.left_full && p.right_full && s.out_full && !s.beta)   // k_gp_mfma6's straight-line instantiation
-                              : s.use_mfma7 ? (L.kern[1] && p.right_full && !s.scaled && (s.chained || p.left_full))   // one component per lane and load: no alignment needed
-                                          : (s.use_mfma16 && L.kern[1] && p.right_contig && p.right_full && !s.scaled &&
-                                             (s.chained ? true : (p.left_contig && p.left_full)));
-        const bool whole_rows = prefetch && L.kern[2] && s.out_full && !s.beta;   // k_gp_mfma16x4: straight-line result stores
+        bool prefetch = false;
+        switch (s.dense.family) {
+        case DenseFamily::MFMA6: prefetch = p.left_full && p.right_full && s.dense.out_full && !s.beta; break;   // k_gp_mfma6's straight-line instantiation
+        case DenseFamily::MFMA7: prefetch = L.kern[1] && p.right_full && !s.dense.scaled && (s.dense.chained || p.left_full); break;   // one component per lane and load: no alignment needed
+        case DenseFamily::MFMA16X4: prefetch = L.kern[1] && p.right_contig && p.right_full && !s.dense.scaled && (s.dense.chained || (p.left_contig && p.left_full)); break;
+        default: break;
+        }
+        const bool whole_rows = prefetch && L.kern[2] && s.dense.out_full && !s.beta;   // k_gp_mfma16x4: straight-line result stores
         L.variant = whole_rows ? 2 : prefetch ? 1 : 0;
         hipLaunchKernelGGL(reinterpret_cast<KernD>(const_cast<void*>(L.kern[L.variant])), dim3(unsigned(blocks)),
                            dim3(unsigned(L.threads)), L.lds, g_stream, p);
@@ -1001,13 +1018,13 @@ int run_jit(const Launch& L, const Plan& plan, const std::vector<Bound>& in_boun
     const Step& s = L.s;
     // argument block: (ptr, stride) per staged input image, then out, out stride, batch
     std::vector<void*> args;
-    std::vector<const void*> ptrs(s.fused_inputs.size());
-    std::vector<long long> strides(s.fused_inputs.size());
-    for (size_t i = 0; i < s.fused_inputs.size(); ++i) {
-        ptrs[i] = in_bound[size_t(s.fused_inputs[i].slot)].ptr;
-        strides[i] = in_bound[size_t(s.fused_inputs[i].slot)].stride;
+    std::vector<const void*> ptrs(s.fused.inputs.size());
+    std::vector<long long> strides(s.fused.inputs.size());
+    for (size_t i = 0; i < s.fused.inputs.size(); ++i) {
+        ptrs[i] = in_bound[size_t(s.fused.inputs[i].slot)].ptr;
+        strides[i] = in_bound[size_t(s.fused.inputs[i].slot)].stride;
     }
-    for (size_t i = 0; i < s.fused_inputs.size(); ++i) {
+    for (size_t i = 0; i < s.fused.inputs.size(); ++i) {
         args.push_back(&ptrs[i]);
         args.push_back(&strides[i]);
     }
@@ -1018,10 +1035,10 @@ int run_jit(const Launch& L, const Plan& plan, const std::vector<Bound>& in_boun
     args.push_back(&b);
     void* dom = L.domain;
     if (plan.has_explog) args.push_back(&dom);
-    const unsigned threads = unsigned(s.jit_threads);
-    const unsigned per_block = unsigned(s.jit_items > 0 ? s.jit_items : s.jit_threads);   // (the slab-in-LDS form: 64 items per 512 threads)
+    const unsigned threads = unsigned(s.fused.jit_threads);
+    const unsigned per_block = unsigned(s.fused.jit_items > 0 ? s.fused.jit_items : s.fused.jit_threads);   // (the slab-in-LDS form: 64 items per 512 threads)
     unsigned blocks = unsigned((batch + per_block - 1) / per_block);
-    if (s.jit_persistent > 0) blocks = unsigned(std::min<int64_t>(blocks, int64_t(g_num_cu) * std::min(s.jit_persistent, 4)));   // persistent workgroups
+    if (s.fused.jit_persistent > 0) blocks = unsigned(std::min<int64_t>(blocks, int64_t(g_num_cu) * std::min(s.fused.jit_persistent, 4)));   // persistent workgroups
     // (the argument block -- args, ptrs, strides and the locals they point at -- only has to live until this call returns:
     //  hipModuleLaunchKernel copies the kernel arguments into the dispatch packet's kernarg segment at call time)
     hipFunction_t fn = L.jit.fn;
@@ -1030,8 +1047,8 @@ int run_jit(const Launch& L, const Plan& plan, const std::vector<Bound>& in_boun
         // contracted variant run (a program over batched operands only keeps the reference's bits by default, as before)
         double bytes = double(plan.out_layout.row_len) * sizeof(T);
         bool shared = false;
-        for (size_t i = 0; i < s.fused_inputs.size(); ++i) {
-            if (strides[i] != 0) bytes += double(plan.input_layouts[size_t(s.fused_inputs[i].slot)].row_len) * sizeof(T);
+        for (size_t i = 0; i < s.fused.inputs.size(); ++i) {
+            if (strides[i] != 0) bytes += double(plan.input_layouts[size_t(s.fused.inputs[i].slot)].row_len) * sizeof(T);
             else shared = true;
         }
         if (shared && arithmetic_bound(s.n_entries, bytes)) fn = L.jit_fma.fn;
@@ -1047,15 +1064,15 @@ int run_fused(const Launch& L, const Plan& plan, const std::vector<Bound>& in_bo
     const Step& s = L.s;
     FusedArgs<T> p;
     std::memset(&p, 0, sizeof(p));
-    p.prog = L.u32_a.as<uint32_t>();
-    p.phase_tab = L.u32_b.as<uint32_t>();
-    p.n_phases = int(L.u32_b.count / (2 * FUSED_GROUPS));
-    for (size_t i = 0; i < L.fused_coeff.size() && i < 6; ++i) p.coeff[i] = T(L.fused_coeff[i]);
-    p.slab = s.fused_slab;
-    p.zero_slot = s.fused_zero_slot;
-    p.n_in = int(s.fused_inputs.size());
+    p.prog = L.fused.prog.as<uint32_t>();
+    p.phase_tab = L.fused.phase_tab.as<uint32_t>();
+    p.n_phases = int(L.fused.phase_tab.count / (2 * FUSED_GROUPS));
+    for (size_t i = 0; i < L.fused.general.size() && i < 6; ++i) p.coeff[i] = T(L.fused.general[i]);
+    p.slab = s.fused.slab;
+    p.zero_slot = s.fused.zero_slot;
+    p.n_in = int(s.fused.inputs.size());
     for (int i = 0; i < p.n_in; ++i) {
-        const Step::FusedInput& fi = s.fused_inputs[size_t(i)];
+        const Step::FusedInput& fi = s.fused.inputs[size_t(i)];
         p.in_ptr[i] = static_cast<const T*>(in_bound[size_t(fi.slot)].ptr);
         p.in_stride[i] = in_bound[size_t(fi.slot)].stride;
         p.in_len[i] = int(plan.input_layouts[size_t(fi.slot)].row_len);
@@ -1065,7 +1082,7 @@ int run_fused(const Launch& L, const Plan& plan, const std::vector<Bound>& in_bo
     p.out_ptr = static_cast<T*>(out.ptr);
     p.out_stride = out.stride;
     p.out_len = int(plan.out_layout.row_len);
-    p.out_base = s.fused_out_base;
+    p.out_base = s.fused.out_base;
     p.batch = batch;
     const size_t lds = (size_t(p.slab) * FUSED_ITEMS + 8) * sizeof(T);
     const int64_t blocks = (batch + FUSED_ITEMS - 1) / FUSED_ITEMS;
@@ -1081,29 +1098,29 @@ int run_elementwise(const Launch& L, const Bound& res, Resolve&& resolve, int64_
     ElementwiseArgs<T> q;
     std::memset(&q, 0, sizeof(q));
     Layout unused;
-    for (size_t i = 0; i < s.ew_src.size() && i < size_t(ELEMENTWISE_MAX_SRC); ++i) {
-        const Bound b = resolve(s.ew_src[i], &unused);
+    for (size_t i = 0; i < s.ew.src.size() && i < size_t(ELEMENTWISE_MAX_SRC); ++i) {
+        const Bound b = resolve(s.ew.src[i], &unused);
         q.src[i] = static_cast<const T*>(b.ptr);
         q.src_stride[i] = b.stride;
     }
-    q.ops = L.u32_a.as<uint32_t>();
-    q.comp_off = L.u32_b.as<uint32_t>();
-    q.n_ops = s.ew_ops;
-    q.n_comp = int(L.u32_b.count);
-    q.load_first = s.ew_load_first;
+    q.ops = L.ew.ops.as<uint32_t>();
+    q.comp_off = L.ew.comp_off.as<uint32_t>();
+    q.n_ops = s.ew.n_ops;
+    q.n_comp = int(L.ew.comp_off.count);
+    q.load_first = s.ew.load_first;
     q.batch = batch;
-    if (s.ew_scale) {
+    if (s.ew.scale) {
         const Bound sc = resolve(s.b, &unused);
         q.out = static_cast<T*>(res.ptr);
         q.out_stride = res.stride;
-        q.out_off = L.u32_c.as<uint32_t>();
-        q.coeff = L.coeff.as<T>();
+        q.out_off = L.ew.out_off.as<uint32_t>();
+        q.coeff = L.ew.coeff.as<T>();
         q.scalar = static_cast<const T*>(sc.ptr);
         q.scalar_stride = sc.stride;
-        q.scalar_off = s.ew_scalar_off;
-        q.canon_v = s.ew_canon_v;
-        q.canon_s = s.ew_canon_s;
-        q.s_is_left = s.ew_s_is_left;
+        q.scalar_off = s.ew.scalar_off;
+        q.canon_v = s.ew.canon_v;
+        q.canon_s = s.ew.canon_s;
+        q.s_is_left = s.ew.s_is_left;
     } else {
         q.res = static_cast<T*>(res.ptr);
         q.res_stride = res.stride;
@@ -1144,33 +1161,33 @@ bool compile_fused(gaast_hip_program_s& prog, uint32_t flags, uint32_t* rebuild_
     bool rebuild = false;
     for (Launch& L : prog.launches) {
         Step& s = L.s;
-        if (s.kind != Step::FUSED || s.jit_source.empty()) continue;
-        if (flags & GAAST_FLAG_DEBUG_KEEP_JIT_SOURCE) prog.plan.jit_source_kept += s.jit_source;
+        if (s.kind != Step::FUSED || s.fused.jit_source.empty()) continue;
+        if (flags & GAAST_FLAG_DEBUG_KEEP_JIT_SOURCE) prog.plan.jit_source_kept += s.fused.jit_source;
         std::string log;
-        if (!(flags & GAAST_FLAG_DEBUG_JIT_FAILS)) L.jit = jit_compile(s.jit_source, "gaast_jit", &log);
+        if (!(flags & GAAST_FLAG_DEBUG_JIT_FAILS)) L.jit = jit_compile(s.fused.jit_source, "gaast_jit", &log);
         if (L.jit)
-            s.name = "ast_jit" + s.name.substr(s.name.find('[')) + (s.jit_items ? " slab in LDS" : "");
+            s.name = "ast_jit" + s.name.substr(s.name.find('[')) + (s.fused.jit_items ? " slab in LDS" : "");
         else if (!log.empty())
             g_err = "hiprtc: " + log;  // informational: the interpreter kernel (or an unfused plan) runs instead
         bool trial_failed = false;
-        if (L.jit && s.jit_reg_trial) {
+        if (L.jit && s.fused.jit_reg_trial) {
             // a slab beyond 160 / 200 elements in registers, on trial (plan.cpp: try_fuse): the compiled kernel has to leave two
             // waves per SIMD (eight single-wave workgroups per CU), else the plan is rebuilt with the slabs in LDS
             int per_cu = 0;
-            trial_failed = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, L.jit.fn, s.jit_threads, 0) != hipSuccess ||
-                           per_cu * (s.jit_threads / 64) < 8;
+            trial_failed = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, L.jit.fn, s.fused.jit_threads, 0) != hipSuccess ||
+                           per_cu * (s.fused.jit_threads / 64) < 8;
             if (trial_failed) rebuild = *small_reg_slab = true;
         }
         // tolerance mode, one item per thread, and arithmetic-bound at least when every operand is shared by all items: the
         // contracted variant too (run_jit picks per launch, by the operands bound)
-        if (L.jit && !trial_failed && !(flags & GAAST_FLAG_EXACT_ORDER) && !s.jit_items && !prog.plan.has_explog &&
+        if (L.jit && !trial_failed && !(flags & GAAST_FLAG_EXACT_ORDER) && !s.fused.jit_items && !prog.plan.has_explog &&
             arithmetic_bound(s.n_entries, double(prog.plan.out_layout.row_len) * dtype_size(prog.plan.dtype))) {
             std::string log2;
-            L.jit_fma = jit_compile(s.jit_source, "gaast_jit", &log2, true);
+            L.jit_fma = jit_compile(s.fused.jit_source, "gaast_jit", &log2, true);
             if (L.jit_fma) s.name += " | fused multiply-adds under shared operands";
         }
-        std::string().swap(s.jit_source);
-        if (!L.jit && s.fused_jit_only) {
+        std::string().swap(s.fused.jit_source);
+        if (!L.jit && s.fused.jit_only) {
             rebuild = true;
             *rebuild_flags |= GAAST_FLAG_NO_JIT;
         }
@@ -1184,15 +1201,16 @@ void compile_chains(gaast_hip_program_s& prog, uint32_t flags) {
     std::vector<char> drop(ls.size(), 0);
     for (size_t i = 0; i < ls.size(); ++i) {
         Step& s = ls[i].s;
-        if (!s.chain_jit) continue;
-        if (flags & GAAST_FLAG_DEBUG_KEEP_JIT_SOURCE) prog.plan.jit_source_kept += s.chain_jit_source;
+        if (!s.cj.on) continue;
+        if (flags & GAAST_FLAG_DEBUG_KEEP_JIT_SOURCE) prog.plan.jit_source_kept += s.cj.source;
         std::string log;
-        ls[i].jit = jit_compile(s.chain_jit_source, "gaast_chain", &log);
+        ls[i].jit = jit_compile(s.cj.source, "gaast_chain", &log);
         if (!ls[i].jit && !log.empty()) g_err = "hiprtc: " + log;
-        std::string().swap(s.chain_jit_source);
+        std::string().swap(s.cj.source);
         if (!ls[i].jit) {
-            s.list_jit = s.fold_prev = 0;
-        } else if (s.fold_prev && i > 0) {   // the copy_grades_from step before a single list is evaluated by the specialised kernel
+            s.cj.single = s.cj.fold_prev = 0;
+            s.cj.init_src = BufRef();
+        } else if (s.cj.fold_prev && i > 0) {   // the copy_grades_from step before a single list is evaluated by the specialised kernel
             drop[i - 1] = 1;
             s.name += " <- " + ls[i - 1].s.name;
         }
@@ -1216,17 +1234,17 @@ int prepare_launch(Launch& L, const gaast_hip_program_s& prog) {
         default: return plan.out_layout;
         }
     };
-    L.n = (s.kind == Step::PRODUCT_DENSE && s.dense_n) ? s.dense_n : plan.n;   // parity-pure products run in Cl(n - 1)
+    L.n = (s.kind == Step::PRODUCT_DENSE && s.dense.n) ? s.dense.n : plan.n;   // parity-pure products run in Cl(n - 1)
     L.domain = prog.domain.ptr;
     std::string kernel;
     const Layout la = layout_of(s.a), lb = layout_of(s.b);
     if (int st = plan.dtype == GAAST_F32 ? prepare_step<float>(L, la, lb, kernel) : prepare_step<double>(L, la, lb, kernel)) return st;
-    if (s.chained) {
+    if (s.dense.chained) {
         // the list's operand rows of every item a workgroup stages at once, after the kernel's own images
         L.pre_scratch_off = (L.lds + 15) / 16 * 16;
         const size_t items = size_t(L.items_per_block > 0 ? L.items_per_block : 1);
         // + the zero pair; the one-item matrix kernels keep the list's right row twice (+x, -x: a term's sign is an address)
-        L.lds = L.pre_scratch_off + (items * size_t(s.pre_left_len + s.pre_right_len + 1) + (items == 1 ? size_t(s.pre_right_len) : 0)) * dtype_size(plan.dtype);
+        L.lds = L.pre_scratch_off + (items * size_t(s.pre.left_len + s.pre.right_len + 1) + (items == 1 ? size_t(s.pre.right_len) : 0)) * dtype_size(plan.dtype);
         // The plan builder sizes a chain's LDS with its own estimate of the kernel's images; this is the real figure, checked
         // against the device.  On a mismatch gaast_hip_program_create rebuilds the program without chains.
         if (L.lds > g_max_lds) return set_err(kChainTooBig, "chained product does not fit in LDS (" + s.name + ")");
@@ -1235,31 +1253,31 @@ int prepare_launch(Launch& L, const gaast_hip_program_s& prog) {
                 if (int st = allow_lds(L.kern[v], L.lds)) return st;
         if (L.blocks_per_cu > 0)
             if (int st = resident_blocks(L.kern[0], L.threads, L.lds, &L.blocks_per_cu)) return st;
-        if (int st = L.pre_row_start.upload(std::move(s.pre_row_start))) return st;
-        if (int st = L.pre_entries.upload(std::move(s.pre_entries))) return st;
-        if (int st = L.pre_row_map.upload(std::move(s.pre_row_map))) return st;
-        if (int st = L.pre_coeff.upload(std::move(s.pre_coeff), plan.dtype)) return st;
-        if (int st = L.pre_row_scale.upload(std::move(s.pre_row_scale), plan.dtype)) return st;
     }
-    if (s.kind == Step::PRODUCT_CSR && (s.list_chain || s.list_jit)) {
-        if (L.jit) {
-            if (int st = L.cj_ent1.upload(std::move(s.cj_ent1))) return st;
-            if (int st = L.cj_pos1.upload(std::move(s.cj_pos1))) return st;
-            if (int st = L.cj_ent2.upload(std::move(s.cj_ent2))) return st;
-            if (int st = L.cj_out2.upload(std::move(s.cj_out2))) return st;
-        } else {
-            if (int st = L.pre_entries.upload(std::move(s.pre_entries))) return st;
-            if (int st = L.pre_row_map.upload(std::move(s.pre_row_map))) return st;
-        }
+    // every table of the step under its own name: L.X from s.X (index tables as they are, value tables in the program's dtype; the
+    // tables of the groups this step does not use are empty and cost nothing)
+    int st = GAAST_OK;
+    auto idx = [&](DevTable& dev, auto& host) { if (!st) st = dev.upload(std::move(host)); };
+    auto val = [&](DevTable& dev, std::vector<double>& host) { if (!st) st = dev.upload(std::move(host), plan.dtype); };
+    const bool chain_jit = s.kind == Step::PRODUCT_CSR && bool(L.jit);   // the specialised kernel has tables of its own: cj, not pre
+    if (!chain_jit) {
+        idx(L.pre.row_start, s.pre.row_start); idx(L.pre.entries, s.pre.entries); idx(L.pre.row_map, s.pre.row_map);
+        val(L.pre.coeff, s.pre.coeff); val(L.pre.row_scale, s.pre.row_scale);
+    } else {
+        idx(L.cj.ent1, s.cj.ent1); idx(L.cj.pos1, s.cj.pos1); idx(L.cj.ent2, s.cj.ent2); idx(L.cj.out2, s.cj.out2);
     }
-    if (int st = L.u32_a.upload(std::move(s.u32_a))) return st;
-    if (int st = L.u32_b.upload(std::move(s.u32_b))) return st;
-    if (int st = L.u32_c.upload(std::move(s.u32_c))) return st;
-    if (int st = L.i32_a.upload(std::move(s.i32_a))) return st;
-    if (s.kind == Step::FUSED) L.fused_coeff = std::move(s.coeff);
-    else if (int st = L.coeff.upload(std::move(s.coeff), plan.dtype)) return st;
-    if (int st = L.coeff_b.upload(std::move(s.coeff_b), plan.dtype)) return st;
-    if (int st = L.coeff_c.upload(std::move(s.coeff_c), plan.dtype)) return st;
+    idx(L.axpy_map, s.axpy_map); idx(L.flip_offsets, s.flip_offsets);
+    idx(L.list.row_start, s.list.row_start); idx(L.list.row_out, s.list.row_out); idx(L.list.entries, s.list.entries); val(L.list.coeff, s.list.coeff);
+    idx(L.dense.left_map, s.dense.left_map); idx(L.dense.right_map, s.dense.right_map); idx(L.dense.out_map, s.dense.out_map);
+    idx(L.dense.spinor_out_map, s.dense.spinor_out_map);
+    val(L.dense.left_scale, s.dense.left_scale); val(L.dense.right_scale, s.dense.right_scale); val(L.dense.out_scale, s.dense.out_scale);
+    idx(L.fused.prog, s.fused.prog); idx(L.fused.phase_tab, s.fused.phase_tab);
+    L.fused.general = std::move(s.fused.general);
+    val(L.explog.sq, s.explog.sq); idx(L.explog.row_start, s.explog.row_start); idx(L.explog.pairs, s.explog.pairs); val(L.explog.pair_coeff, s.explog.pair_coeff);
+    idx(L.reduce.ent1, s.reduce.ent1); val(L.reduce.coeff1, s.reduce.coeff1); idx(L.reduce.ent2, s.reduce.ent2); val(L.reduce.coeff2, s.reduce.coeff2);
+    idx(L.reduce.sign_words, s.reduce.sign_words);
+    idx(L.ew.ops, s.ew.ops); idx(L.ew.comp_off, s.ew.comp_off); idx(L.ew.out_off, s.ew.out_off); val(L.ew.coeff, s.ew.coeff);
+    if (st) return st;
     L.label = kernel.empty() ? s.name : s.name + " :: " + kernel;
     return GAAST_OK;
 }
@@ -1269,26 +1287,9 @@ void mark_used_slots(gaast_hip_program_s& prog) {
     Plan& plan = prog.plan;
     plan.slot_used.assign(plan.inputs.size(), 0);
     auto use = [&](BufRef r) {
-        if (r.idx >= 0 && r.kind == BufKind::INPUT) plan.slot_used[size_t(r.idx)] = 1;
+        if (r.kind == BufKind::INPUT) plan.slot_used[size_t(r.idx)] = 1;
     };
-    for (const Launch& L : prog.launches) {
-        const Step& s = L.s;
-        if (s.chained) {
-            use(s.pre_a);
-            use(s.pre_b);
-        }
-        if (s.kind == Step::ELEMENTWISE) {
-            for (const BufRef& b : s.ew_src) use(b);
-        } else if (s.kind == Step::REDUCE_SCALE) {
-            use(s.pre_a);
-        } else if (s.list_chain || s.list_jit) {
-            use(s.pre_a);
-            if (s.list_chain) use(s.pre_b);
-        }
-        use(s.a);
-        use(s.b);
-        for (const Step::FusedInput& fi : s.fused_inputs) plan.slot_used[size_t(fi.slot)] = 1;
-    }
+    for (const Launch& L : prog.launches) for_each_read(L.s, use);
 }
 
 int upload_const_rows(gaast_hip_program_s& prog) {
@@ -1910,19 +1911,12 @@ int run_launches(gaast_hip_program_t prog, const std::vector<Bound>& in_bound0, 
         Bound a{nullptr, 0}, b{nullptr, 0};
         if (s.a.idx >= 0) a = resolve(s.a, &la);
         if (s.b.idx >= 0) b = resolve(s.b, &lb);
-        Bound pa{nullptr, 0}, pb{nullptr, 0};
-        if (s.kind == Step::REDUCE_SCALE) {
+        auto extra = [&](BufRef r) {   // (an operand the step does not have stays null)
             Layout unused;
-            pa = resolve(s.pre_a, &unused);
-        } else if (s.chained || s.list_chain) {
-            Layout unused;
-            pa = resolve(s.pre_a, &unused);
-            pb = resolve(s.pre_b, &unused);
-        } else if (s.list_jit && s.fold_prev) {
-            Layout unused;
-            pa = resolve(s.pre_a, &unused);   // the folded copy's source
-        }
-        if (int st = run_step<T>(L, res, a, b, la, lb, count, pa, pb)) return st;
+            return r.idx >= 0 ? resolve(r, &unused) : Bound{nullptr, 0};
+        };
+        const Extra x{extra(s.pre.a), extra(s.pre.b), extra(s.reduce.x), extra(s.cj.init_src)};
+        if (int st = run_step<T>(L, res, a, b, la, lb, count, x)) return st;
     }
     return GAAST_OK;
 }

@@ -132,7 +132,7 @@ static void dense_tables_agree_with_the_list(int n, const double* metric, int dt
     gaast::build_plan(desc, plan);
     const gaast::Step* st = nullptr;
     for (const gaast::Step& s : plan.steps)
-        if (s.kind == gaast::Step::PRODUCT_DENSE && !s.use_spinor) st = &s;
+        if (s.kind == gaast::Step::PRODUCT_DENSE && s.dense.family != gaast::DenseFamily::SPINOR) st = &s;
     CHECK(st != nullptr);
     if (!st) {
         std::printf("%s: no dense step\n", what);
@@ -140,10 +140,13 @@ static void dense_tables_agree_with_the_list(int n, const double* metric, int dt
         return;
     }
     CHECK(st->name.find(expect_step) != std::string::npos);
-    // the kernel's algebra: the program's, or Cl(n - 1) for parity-pure operands (st->dense_n)
-    const int n2 = st->dense_n ? st->dense_n : n;
+    // the kernel's algebra: the program's, or Cl(n - 1) for parity-pure operands (st->dense.n)
+    const int n2 = st->dense.n ? st->dense.n : n;
+    using gaast::DenseFamily;
+    const DenseFamily fam = st->dense.family;
+    const bool mfma32 = fam == DenseFamily::MFMA32 || fam == DenseFamily::MFMA32P;
     const uint32_t N = 1u << n2, NROW = 1u << n;
-    const int L = st->use_mfma ? 5 : st->use_mfma7 ? 3 : st->use_mfma6 ? 0 : 4;   // (k_gp_mfma6: no lo vectors, the image position is the blade)
+    const int L = mfma32 ? 5 : fam == DenseFamily::MFMA7 ? 3 : fam == DenseFamily::MFMA6 ? 0 : 4;   // (k_gp_mfma6: no lo vectors, the image position is the blade)
     // operands: a fixed pseudo-random row each (exact small integers: every sum below is exact)
     std::vector<double> lrow(NROW), rrow(NROW);
     uint64_t x = 88172645463325252ULL;
@@ -153,37 +156,37 @@ static void dense_tables_agree_with_the_list(int n, const double* metric, int dt
     // images in permuted-blade order
     std::vector<uint32_t> inv_vec(N), inv_b(N), inv_a7(256, 0);
     for (uint32_t m = 0; m < N; ++m) inv_vec[vec_pos(m)] = m;
-    if (st->use_mfma7) for (uint32_t m = 0; m < N; ++m) { inv_b[mfma7_b_pos(m)] = m; inv_a7[mfma7_a_pos(m)] = m; }
-    else if (st->mfma32_pairs) for (uint32_t m = 0; m < N; ++m) inv_b[mfma32p_b_pos(m)] = m;
-    else if (st->use_mfma) for (uint32_t m = 0; m < N; ++m) inv_b[mfma_b_pos(m)] = m;
-    else if (st->mfma16_quads) for (uint32_t m = 0; m < N; ++m) inv_b[mfma16q_b_pos(m)] = m;
-    else if (st->use_mfma16d) for (uint32_t m = 0; m < N; ++m) inv_b[mfma16d_b_pos(m)] = m;
-    // a general diagonal metric: the step carries w_S per loaded component (coeff / coeff_b) and 1 / w_T per permuted blade
-    // (coeff_c); the test metrics have squares of powers of two, so every product below stays exact
-    CHECK(st->scaled == (st->coeff_c.empty() ? 0 : 1));
+    if (fam == DenseFamily::MFMA7) for (uint32_t m = 0; m < N; ++m) { inv_b[mfma7_b_pos(m)] = m; inv_a7[mfma7_a_pos(m)] = m; }
+    else if (fam == DenseFamily::MFMA32P) for (uint32_t m = 0; m < N; ++m) inv_b[mfma32p_b_pos(m)] = m;
+    else if (fam == DenseFamily::MFMA32) for (uint32_t m = 0; m < N; ++m) inv_b[mfma_b_pos(m)] = m;
+    else if (st->dense.mfma16_quads) for (uint32_t m = 0; m < N; ++m) inv_b[mfma16q_b_pos(m)] = m;
+    else if (fam == DenseFamily::MFMA16X4) for (uint32_t m = 0; m < N; ++m) inv_b[mfma16d_b_pos(m)] = m;
+    // a general diagonal metric: the step carries w_S per loaded component (left_scale / right_scale) and 1 / w_T per permuted blade
+    // (out_scale); the test metrics have squares of powers of two, so every product below stays exact
+    CHECK(st->dense.scaled == (st->dense.out_scale.empty() ? 0 : 1));
     auto image = [&](const std::vector<uint32_t>& map, const std::vector<double>& row, bool right) {
         std::vector<double> img(N, 0.0);
-        const std::vector<double>& scale = right ? st->coeff_b : st->coeff;
-        CHECK(!st->scaled || scale.size() == map.size());
+        const std::vector<double>& scale = right ? st->dense.right_scale : st->dense.left_scale;
+        CHECK(!st->dense.scaled || scale.size() == map.size());
         size_t idx = 0;
         for (uint32_t w : map) {
             const uint32_t off = w & 0xffffu, pos = (w >> 16) & 0x7fffu;
-            const uint32_t blade = st->use_mfma6 ? pos
-                                   : st->use_mfma7 ? (right ? inv_b[pos] : inv_a7[pos])
-                                   : (st->use_mfma || st->use_mfma16) ? (right ? inv_b[pos] : pos) : inv_vec[pos];
+            const uint32_t blade = fam == DenseFamily::MFMA6 ? pos
+                                   : fam == DenseFamily::MFMA7 ? (right ? inv_b[pos] : inv_a7[pos])
+                                   : (mfma32 || fam == DenseFamily::MFMA16X4) ? (right ? inv_b[pos] : pos) : inv_vec[pos];
             uint32_t neg = w >> 31;
             // the image-pair kernels keep the b_hi part of (-1)^(|a_hi| |b_lo|) in the B image (the kernel supplies the
             // c_hi part): taken out again here, the plain formula below applies
-            if (right && (st->use_mfma16 || st->mfma32_pairs))
+            if (right && (fam == DenseFamily::MFMA16X4 || fam == DenseFamily::MFMA32P))
                 neg ^= uint32_t(__builtin_popcount(blade >> L) & __builtin_popcount(blade & ((1u << L) - 1u)) & 1);
-            if (right && st->use_mfma7)   // the hi3 part only: the top vector's share is in the kernel's A and result signs
+            if (right && fam == DenseFamily::MFMA7)   // the hi3 part only: the top vector's share is in the kernel's A and result signs
                 neg ^= uint32_t(__builtin_popcount((blade >> 3) & 7u) & __builtin_popcount(blade & 7u) & 1);
-            img[blade] = (neg ? -row[off] : row[off]) * (st->scaled ? scale[idx] : 1.0);
+            img[blade] = (neg ? -row[off] : row[off]) * (st->dense.scaled ? scale[idx] : 1.0);
             ++idx;
         }
         return img;
     };
-    const std::vector<double> A = image(st->u32_a, lrow, false), B = image(st->u32_b, rrow, true);
+    const std::vector<double> A = image(st->dense.left_map, lrow, false), B = image(st->dense.right_map, rrow, true);
     std::vector<double> Cp(N, 0.0);
     const uint32_t lomask = (1u << L) - 1;
     for (uint32_t pa = 0; pa < N; ++pa)
@@ -192,16 +195,16 @@ static void dense_tables_agree_with_the_list(int n, const double* metric, int dt
             for (int p = 1; p < n2; ++p)
                 if ((pa >> p) & 1u) par ^= __builtin_popcount(pb & ((1u << p) - 1u)) & 1;
             const uint32_t sh = pa & pb;
-            par ^= __builtin_popcount((sh & lomask) & st->neg_lo) & 1;
-            par ^= __builtin_popcount((sh >> L) & st->neg_hi) & 1;
-            if ((sh >> L) & st->zero_hi) continue;
+            par ^= __builtin_popcount((sh & lomask) & st->dense.neg_lo) & 1;
+            par ^= __builtin_popcount((sh >> L) & st->dense.neg_hi) & 1;
+            if ((sh >> L) & st->dense.zero_hi) continue;
             Cp[pa ^ pb] += (par ? -1.0 : 1.0) * A[pa] * B[pb];
         }
     std::vector<double> got(NROW, 0.0);
     for (uint32_t m = 0; m < N; ++m) {
-        const int32_t w = st->i32_a[m];
+        const int32_t w = st->dense.out_map[m];
         if (w < 0) continue;
-        got[size_t(w & 0x3fffffff)] = ((w & 0x40000000) ? -Cp[m] : Cp[m]) * (st->scaled ? st->coeff_c[m] : 1.0);
+        got[size_t(w & 0x3fffffff)] = ((w & 0x40000000) ? -Cp[m] : Cp[m]) * (st->dense.scaled ? st->dense.out_scale[m] : 1.0);
     }
     // the reference's list (specialize.rs:162-183), on graded rows (each buffer laid out by its own grade set)
     std::vector<double> want(NROW, 0.0);
@@ -245,8 +248,8 @@ static void chain_tables_agree(int n, const double* metric, int dtype, const cha
     CHECK(gaast_spec_program_desc(spec, dtype, flags, &desc) == 0);
     gaast::Plan plan;
     gaast::build_plan(desc, plan);
-    CHECK(plan.steps.size() == 1 && plan.steps[0].list_chain && plan.steps[0].chain_jit == 1);
-    if (plan.steps.size() != 1 || plan.steps[0].chain_jit != 1) {
+    CHECK(plan.steps.size() == 1 && plan.steps[0].chain.side && plan.steps[0].cj.on == 1);
+    if (plan.steps.size() != 1 || plan.steps[0].cj.on != 1) {
         gaast_spec_free(spec);
         return;
     }
@@ -255,21 +258,21 @@ static void chain_tables_agree(int n, const double* metric, int dtype, const cha
         char path[512];
         std::snprintf(path, sizeof path, "%s/chain_n%d_%s.hip", dump_dir, n, dtype == GAAST_F32 ? "f32" : "f64");
         if (FILE* f = std::fopen(path, "w")) {
-            std::fputs(s.chain_jit_source.c_str(), f);
+            std::fputs(s.cj.source.c_str(), f);
             std::fclose(f);
         }
     }
     const int esz = dtype == GAAST_F32 ? 4 : 8;
-    const int l1 = s.pre_left_len, r1 = s.pre_right_len, mid = s.chain_mid_len;
-    const int rows1 = int(s.pre_row_map.size()), w1 = s.pre_width, rows2 = int(s.u32_b.size()), w2 = s.ell_width;
-    const int w1p = s.cj_fmt[0], w2p = (w2 + 3) & ~3, wide = s.cj_fmt[1] == 2 ? 2 : 1;
-    const bool sorted = s.cj_fmt[1] >= 3;
+    const int l1 = s.pre.left_len, r1 = s.pre.right_len, mid = s.chain.mid_len;
+    const int rows1 = int(s.pre.row_map.size()), w1 = s.pre.width, rows2 = int(s.list.row_out.size()), w2 = s.list.ell_width;
+    const int w1p = s.cj.fmt[0], w2p = (w2 + 3) & ~3, wide = s.cj.fmt[1] == 2 ? 2 : 1;
+    const bool sorted = s.cj.fmt[1] >= 3;
     // (sign-sorted only without the flag, and only when the rows' signs are balanced: R^{6,3} at n = 9 is, the Euclidean n = 8, 10 are not)
     CHECK(!sorted || !(flags & GAAST_FLAG_EXACT_ORDER));
     if (!(flags & GAAST_FLAG_EXACT_ORDER) && n == 9) CHECK(sorted);
-    const int wss = s.cj_sorted[0] + s.cj_sorted[1];
-    CHECK(int(s.cj_ent1.size()) == rows1 * w1p && s.chain_alias == 1 && s.list_chain == 1);
-    CHECK(int(s.cj_ent2.size()) == (sorted ? rows2 * s.cj_split * wss : rows2 * w2p * wide));
+    const int wss = s.cj.sorted[0] + s.cj.sorted[1];
+    CHECK(int(s.cj.ent1.size()) == rows1 * w1p && s.chain.alias == 1 && s.chain.side == 1);
+    CHECK(int(s.cj.ent2.size()) == (sorted ? rows2 * s.cj.split * wss : rows2 * w2p * wide));
     std::vector<double> L(static_cast<size_t>(l1), 0.0), X(static_cast<size_t>(r1), 0.0);
     unsigned long long seed = 88172645463325252ull + unsigned(n);
     auto rnd = [&]() {
@@ -283,23 +286,23 @@ static void chain_tables_agree(int n, const double* metric, int dtype, const cha
     for (int row = 0; row < rows1; ++row) {
         double acc = 0.0;
         for (int t = 0; t < w1; ++t) {
-            const uint32_t w = s.pre_entries[size_t(t) * rows1 + row];
+            const uint32_t w = s.pre.entries[size_t(t) * rows1 + row];
             const double p = L[(w & 0x7fffu) / esz] * X[((w >> 16) & 0x7fffu) / esz];
             acc = acc + ((w & 0x80000000u) ? -p : p);
         }
-        mid_a[s.pre_row_map[size_t(row)]] = acc;
+        mid_a[s.pre.row_map[size_t(row)]] = acc;
     }
     for (int row = 0; row < rows2; ++row) {
         double acc = 0.0;
         for (int t = 0; t < w2; ++t) {
-            const uint32_t w = s.u32_c[size_t(t) * rows2 + row];
+            const uint32_t w = s.list.entries[size_t(t) * rows2 + row];
             const double p = mid_a[(w & 0x7fffu) / esz] * L[((w >> 16) & 0x7fffu) / esz];
             acc = acc + ((w & 0x80000000u) ? -p : p);
         }
         out_a[size_t(row)] = acc;
     }
     // (b) the specialised kernel's tables over its item image
-    const int* lay = s.cj_layout;
+    const int* lay = s.cj.layout;
     std::vector<double> img(size_t(lay[5]), 0.0);
     for (int c = 0; c < l1; ++c) img[size_t(lay[0] + c)] = L[size_t(c)];
     for (int c = 0; c < r1; ++c) img[size_t(lay[1] + c)] = X[size_t(c)];
@@ -310,36 +313,36 @@ static void chain_tables_agree(int n, const double* metric, int dtype, const cha
     };
     for (int row = 0; row < rows1; ++row) {
         double acc = 0.0;
-        if (s.cj_xreg) {   // tolerance mode: term j multiplies the right operand's component j (a register); word = left offset | sign << 31
+        if (s.cj.xreg) {   // tolerance mode: term j multiplies the right operand's component j (a register); word = left offset | sign << 31
             CHECK(!(flags & GAAST_FLAG_EXACT_ORDER) && r1 <= w1p);
             int real_terms = 0;
             for (int j = 0; j < r1; ++j) {
-                const uint32_t w = s.cj_ent1[size_t(row) * w1p + j];
+                const uint32_t w = s.cj.ent1[size_t(row) * w1p + j];
                 const double pr = at(w & 0x7fffffffu) * img[size_t(lay[1] + j)];
                 acc = (w & 0x80000000u) ? acc - pr : acc + pr;
-                real_terms += (w & 0x7fffffffu) == uint32_t(s.cj_sorted[2]) ? 0 : 1;
+                real_terms += (w & 0x7fffffffu) == uint32_t(s.cj.sorted[2]) ? 0 : 1;
             }
             CHECK(real_terms == w1);
-            CHECK(std::fabs(acc - mid_a[s.pre_row_map[size_t(row)]]) <= 1e-12 * (std::fabs(acc) + 1.0));
+            CHECK(std::fabs(acc - mid_a[s.pre.row_map[size_t(row)]]) <= 1e-12 * (std::fabs(acc) + 1.0));
         } else {
             for (int t = 0; t < w1; ++t) {
-                const uint32_t w = s.cj_ent1[size_t(row) * w1p + t];
+                const uint32_t w = s.cj.ent1[size_t(row) * w1p + t];
                 acc = acc + at(w & 0xffffu) * at(w >> 16);
             }
         }
-        at(s.cj_pos1[size_t(row)]) = acc;
+        at(s.cj.pos1[size_t(row)]) = acc;
     }
     bool same = true;
     for (int row = 0; row < rows2 && sorted; ++row) {   // slices in order, each plus terms then minus terms; every real term exactly once
         double acc = 0.0, mag = 0.0;
         int real_terms = 0;
-        for (int sl = 0; sl < s.cj_split; ++sl) {
+        for (int sl = 0; sl < s.cj.split; ++sl) {
             double part = 0.0;
             for (int t = 0; t < wss; ++t) {
-                const uint32_t w = s.cj_ent2[(size_t(row) * s.cj_split + sl) * wss + t];
-                const bool pad = (w & 0xffffu) == uint32_t(s.cj_sorted[2]) && (w >> 16) == uint32_t(s.cj_sorted[2]);
+                const uint32_t w = s.cj.ent2[(size_t(row) * s.cj.split + sl) * wss + t];
+                const bool pad = (w & 0xffffu) == uint32_t(s.cj.sorted[2]) && (w >> 16) == uint32_t(s.cj.sorted[2]);
                 const double pr = at(w & 0xffffu) * at(w >> 16);
-                part = t < s.cj_sorted[0] ? part + pr : part - pr;
+                part = t < s.cj.sorted[0] ? part + pr : part - pr;
                 mag += std::fabs(pr);
                 real_terms += pad ? 0 : 1;
                 CHECK(!pad || pr == 0.0);
@@ -347,21 +350,21 @@ static void chain_tables_agree(int n, const double* metric, int dtype, const cha
             acc = acc + part;
         }
         CHECK(real_terms == w2);
-        same = same && std::fabs(acc - out_a[size_t(row)]) <= 1e-12 * (mag + 1.0) && s.cj_out2[size_t(row)] == s.u32_b[size_t(row)];
+        same = same && std::fabs(acc - out_a[size_t(row)]) <= 1e-12 * (mag + 1.0) && s.cj.out2[size_t(row)] == s.list.row_out[size_t(row)];
     }
     for (int row = 0; row < rows2 && !sorted; ++row) {
         double acc = 0.0;
         for (int t = 0; t < w2; ++t) {
-            const uint32_t w = s.cj_ent2[(size_t(row) * w2p + t) * wide];
-            const uint32_t sign = wide == 2 ? s.cj_ent2[(size_t(row) * w2p + t) * 2 + 1] : (w & 0x80000000u);
+            const uint32_t w = s.cj.ent2[(size_t(row) * w2p + t) * wide];
+            const uint32_t sign = wide == 2 ? s.cj.ent2[(size_t(row) * w2p + t) * 2 + 1] : (w & 0x80000000u);
             CHECK(sign == 0u || sign == 0x80000000u);
             const double p = at(w & 0xffffu) * at(wide == 2 ? (w >> 16) : ((w >> 16) & 0x7fffu));
             acc = acc + (sign ? -p : p);
         }
         // (list 1 re-ordered by right index leaves the mid row within rounding of the reference's: list 2 then agrees within a tolerance)
-        const bool agree = s.cj_xreg ? std::fabs(acc - out_a[size_t(row)]) <= 1e-11 * (std::fabs(acc) + 1.0)
+        const bool agree = s.cj.xreg ? std::fabs(acc - out_a[size_t(row)]) <= 1e-11 * (std::fabs(acc) + 1.0)
                                      : std::memcmp(&acc, &out_a[size_t(row)], sizeof acc) == 0;
-        same = same && agree && s.cj_out2[size_t(row)] == s.u32_b[size_t(row)];
+        same = same && agree && s.cj.out2[size_t(row)] == s.list.row_out[size_t(row)];
     }
     if (!same) std::printf("chain tables n=%d: the specialised tables compute another result\n", n);
     CHECK(same);
@@ -381,9 +384,9 @@ static void single_list_tables_agree(int n, int dtype, const char* dump_dir, uin
     CHECK(gaast_spec_program_desc(spec, dtype, flags, &desc) == 0);
     gaast::Plan plan;
     gaast::build_plan(desc, plan);
-    CHECK(plan.steps.size() == 2 && plan.steps[0].kind == gaast::Step::AXPY && plan.steps[0].beta == 0 && plan.steps[1].list_jit == 1 &&
-          plan.steps[1].fold_prev == 1 && plan.steps[1].chain_jit == 1);
-    if (plan.steps.size() != 2 || !plan.steps[1].list_jit) {
+    CHECK(plan.steps.size() == 2 && plan.steps[0].kind == gaast::Step::AXPY && plan.steps[0].beta == 0 && plan.steps[1].cj.single == 1 &&
+          plan.steps[1].cj.fold_prev == 1 && plan.steps[1].cj.on == 1);
+    if (plan.steps.size() != 2 || !plan.steps[1].cj.single) {
         for (const gaast::Step& st : plan.steps) std::printf("    step %s\n", st.name.c_str());
         gaast_spec_free(spec);
         return;
@@ -394,12 +397,12 @@ static void single_list_tables_agree(int n, int dtype, const char* dump_dir, uin
         char path[512];
         std::snprintf(path, sizeof path, "%s/list_n%d_%s.hip", dump_dir, n, dtype == GAAST_F32 ? "f32" : "f64");
         if (FILE* f = std::fopen(path, "w")) {
-            std::fputs(s.chain_jit_source.c_str(), f);
+            std::fputs(s.cj.source.c_str(), f);
             std::fclose(f);
         }
     }
     const int esz = dtype == GAAST_F32 ? 4 : 8;
-    const int N = 1 << n, rows = int(s.u32_b.size()), w2 = s.ell_width, w2p = (w2 + 3) & ~3, wide = s.cj_fmt[1] == 2 ? 2 : 1;
+    const int N = 1 << n, rows = int(s.list.row_out.size()), w2 = s.list.ell_width, w2p = (w2 + 3) & ~3, wide = s.cj.fmt[1] == 2 ? 2 : 1;
     std::vector<double> A(static_cast<size_t>(N), 0.0), B(static_cast<size_t>(N), 0.0), Cc(static_cast<size_t>(N), 0.0);
     unsigned long long seed = 1234567ull + unsigned(n);
     auto rnd = [&]() {
@@ -411,39 +414,39 @@ static void single_list_tables_agree(int n, int dtype, const char* dump_dir, uin
     for (double& v : Cc) v = rnd();
     // (a) the two-launch plan: copy, then the generic ELL words accumulate onto it
     std::vector<double> out_a(size_t(rows), 0.0);
-    for (uint32_t m : ax.u32_a) out_a[m & 0xffffu] = 0.0 + A[m >> 16];
+    for (uint32_t m : ax.axpy_map) out_a[m & 0xffffu] = 0.0 + A[m >> 16];
     for (int row = 0; row < rows; ++row) {
-        double acc = out_a[s.u32_b[size_t(row)]];
+        double acc = out_a[s.list.row_out[size_t(row)]];
         for (int t = 0; t < w2; ++t) {
-            const uint32_t w = s.u32_c[size_t(t) * rows + row];
+            const uint32_t w = s.list.entries[size_t(t) * rows + row];
             const double p = B[(w & 0x7fffu) / esz] * Cc[((w >> 16) & 0x7fffu) / esz];
             acc = acc + ((w & 0x80000000u) ? -p : p);
         }
-        out_a[s.u32_b[size_t(row)]] = acc;
+        out_a[s.list.row_out[size_t(row)]] = acc;
     }
-    // (b) the specialised tables over the item image: left operand at cj_layout[3] ("mid"), right one at cj_layout[4]
-    const int* lay = s.cj_layout;
+    // (b) the specialised tables over the item image: left operand at cj.layout[3] ("mid"), right one at cj.layout[4]
+    const int* lay = s.cj.layout;
     std::vector<double> img(size_t(lay[5]), 0.0);
     for (int c2 = 0; c2 < N; ++c2) img[size_t(lay[3] + c2)] = B[size_t(c2)];
     for (int c2 = 0; c2 < N; ++c2) img[size_t(lay[4] + c2)] = Cc[size_t(c2)];
-    bool same = int(s.cj_pos1.size()) == rows;
-    const bool sorted = s.cj_fmt[1] >= 3;
+    bool same = int(s.cj.pos1.size()) == rows;
+    const bool sorted = s.cj.fmt[1] >= 3;
     CHECK(!sorted || !(flags & GAAST_FLAG_EXACT_ORDER));
     if (!(flags & GAAST_FLAG_EXACT_ORDER) && n == 8 && dtype == GAAST_F64) CHECK(sorted);   // 136 + 136 terms for 256
     if (n == 12) CHECK(!sorted);                                                              // 2 x 32 KiB of operands leave no room for the zero element
-    const int wss = s.cj_sorted[0] + s.cj_sorted[1];
+    const int wss = s.cj.sorted[0] + s.cj.sorted[1];
     for (int row = 0; row < rows && same && sorted; ++row) {
-        double acc = 0.0 + A[s.cj_pos1[size_t(row)]], mag = 1.0;
+        double acc = 0.0 + A[s.cj.pos1[size_t(row)]], mag = 1.0;
         int real_terms = 0;
-        for (int sl = 0; sl < s.cj_split; ++sl) {
+        for (int sl = 0; sl < s.cj.split; ++sl) {
             double part = 0.0;
             for (int t = 0; t < wss; ++t) {
-                const uint32_t w = s.cj_ent2[(size_t(row) * s.cj_split + sl) * wss + t];
+                const uint32_t w = s.cj.ent2[(size_t(row) * s.cj.split + sl) * wss + t];
                 const uint32_t mo = w & 0xffffu, oo = w >> 16;
                 CHECK(mo % esz == 0 && oo % esz == 0 && mo / esz < uint32_t(lay[5]) && oo / esz < uint32_t(lay[5]));
-                const bool pad = mo == uint32_t(s.cj_sorted[2]) && oo == uint32_t(s.cj_sorted[2]);
+                const bool pad = mo == uint32_t(s.cj.sorted[2]) && oo == uint32_t(s.cj.sorted[2]);
                 const double pr = img[mo / esz] * img[oo / esz];
-                part = t < s.cj_sorted[0] ? part + pr : part - pr;
+                part = t < s.cj.sorted[0] ? part + pr : part - pr;
                 mag += std::fabs(pr);
                 real_terms += pad ? 0 : 1;
                 CHECK(!pad || pr == 0.0);
@@ -451,19 +454,19 @@ static void single_list_tables_agree(int n, int dtype, const char* dump_dir, uin
             acc = acc + part;
         }
         CHECK(real_terms == w2);
-        same = std::fabs(acc - out_a[s.cj_out2[size_t(row)]]) <= 1e-12 * mag;
+        same = std::fabs(acc - out_a[s.cj.out2[size_t(row)]]) <= 1e-12 * mag;
     }
     for (int row = 0; row < rows && same && !sorted; ++row) {
-        double acc = 0.0 + A[s.cj_pos1[size_t(row)]];
+        double acc = 0.0 + A[s.cj.pos1[size_t(row)]];
         for (int t = 0; t < w2; ++t) {
-            const uint32_t w = s.cj_ent2[(size_t(row) * w2p + t) * wide];
-            const uint32_t sign = wide == 2 ? s.cj_ent2[(size_t(row) * w2p + t) * 2 + 1] : (w & 0x80000000u);
+            const uint32_t w = s.cj.ent2[(size_t(row) * w2p + t) * wide];
+            const uint32_t sign = wide == 2 ? s.cj.ent2[(size_t(row) * w2p + t) * 2 + 1] : (w & 0x80000000u);
             const uint32_t mo = w & 0xffffu, oo = wide == 2 ? (w >> 16) : ((w >> 16) & 0x7fffu);
             CHECK(mo % esz == 0 && oo % esz == 0 && mo / esz < uint32_t(lay[5]) && oo / esz < uint32_t(lay[5]));
             const double p = img[mo / esz] * img[oo / esz];
             acc = acc + (sign ? -p : p);
         }
-        same = std::memcmp(&acc, &out_a[s.cj_out2[size_t(row)]], sizeof acc) == 0;
+        same = std::memcmp(&acc, &out_a[s.cj.out2[size_t(row)]], sizeof acc) == 0;
     }
     if (!same) std::printf("single list n=%d: the specialised tables compute another result\n", n);
     CHECK(same);
@@ -485,16 +488,47 @@ static void reserved_flag_bits_are_ignored(gaast_expr_t e, int n, const double* 
     gaast::build_plan(desc, reserved);
     bool big_slab = false;
     for (const gaast::Step& s : plain.steps)
-        if (s.kind == gaast::Step::FUSED && s.fused_slab > (dtype == GAAST_F32 ? 200 : 160)) big_slab = true;
+        if (s.kind == gaast::Step::FUSED && s.fused.slab > (dtype == GAAST_F32 ? 200 : 160)) big_slab = true;
     if (!big_slab) std::printf("%s: no fused slab above the small-slab limit\n", what);
     CHECK(big_slab);
     bool same = plain.steps.size() == reserved.steps.size();
     for (size_t i = 0; same && i < plain.steps.size(); ++i) {
         const gaast::Step &a = plain.steps[i], &b = reserved.steps[i];
-        same = a.kind == b.kind && a.fused_slab == b.fused_slab && a.jit_items == b.jit_items && a.jit_reg_trial == b.jit_reg_trial;
+        same = a.kind == b.kind && a.fused.slab == b.fused.slab && a.fused.jit_items == b.fused.jit_items && a.fused.jit_reg_trial == b.fused.jit_reg_trial;
     }
     if (!same) std::printf("%s: bit 30 of the flags changed the plan\n", what);
     CHECK(same);
+    gaast_spec_free(spec);
+    std::printf("ok  %s\n", what);
+}
+
+// No step may read a cache buffer the plan has declared dead (never allocated), and every cache buffer a step reads has a writer
+// before it: asked through the one definition of a step's reads (plan.hpp: for_each_read).
+static void every_buffer_read_is_live(gaast_expr_t e, int n, const double* metric, int dtype, const char* what, bool expect_reduce_scale) {
+    gaast_spec_t spec = gaast_expr_specialize(e, n, metric, 1 << 16);
+    CHECK(spec != nullptr);
+    if (!spec) return;
+    gaast_program_desc desc;
+    CHECK(gaast_spec_program_desc(spec, dtype, 0, &desc) == 0);
+    gaast::Plan plan;
+    gaast::build_plan(desc, plan);
+    CHECK(plan.error == GAAST_OK && plan.unsupported.empty());
+    bool live = true, reduce_scale = false;
+    for (size_t i = 0; i < plan.steps.size(); ++i) {
+        reduce_scale = reduce_scale || plan.steps[i].kind == gaast::Step::REDUCE_SCALE;
+        gaast::for_each_read(plan.steps[i], [&](gaast::BufRef r) {
+            if (r.kind != gaast::BufKind::NODE) return;
+            bool written = false;
+            for (size_t k = 0; k < i; ++k) written = written || plan.steps[k].res == r;
+            const bool dead = size_t(r.idx) < plan.node_dead.size() && plan.node_dead[size_t(r.idx)];
+            if (dead || !written) {
+                std::printf("%s: step %zu (%s) reads cache buffer %d, %s\n", what, i, plan.steps[i].name.c_str(), r.idx, dead ? "declared dead" : "never written");
+                live = false;
+            }
+        });
+    }
+    CHECK(live);
+    CHECK(reduce_scale == expect_reduce_scale);
     gaast_spec_free(spec);
     std::printf("ok  %s\n", what);
 }
@@ -697,6 +731,24 @@ int main(int argc, char** argv) {
                 gaast_expr_t e2 = gaast_expr_g(gaast_expr_product(b, gaast_expr_product(x, gaast_expr_rev(r), GAAST_PROD_GEOMETRIC), GAAST_PROD_GEOMETRIC), 1);
                 lower(e2, n, euclid, GAAST_F32, 0, "b (x ~r) projected: mid row on the right", " <- product_ell[");
             }
+        }
+    }
+    {   // (R X) * (1 / |R|^2) + (R X) ~R: the sparse product R X is the row a REDUCE_SCALE step scales AND the left operand of a dense
+        // product.  chain_sparse_into_dense used to look only at the a / b of other steps (and at the first list of chained dense
+        // steps): it moved R X into the dense step's staging, declared its buffer dead, and the scaling read a buffer that is
+        // never allocated.  With one definition of a step's reads the product R X stays a launch of its own.
+        for (int n : {8, 9}) {
+            uint64_t even = 0;
+            for (int k = 0; k <= n; k += 2) even |= uint64_t(1) << k;
+            gaast_expr_t r = gaast_expr_input(0, even, n), x = gaast_expr_input(1, 0x2, n);
+            gaast_expr_t p = gaast_expr_product(r, x, GAAST_PROD_GEOMETRIC), s = H(gaast_expr_sinv(H(gaast_expr_norm_sq(r))));
+            gaast_expr_t e = gaast_expr_add(gaast_expr_product(p, s, GAAST_PROD_GEOMETRIC), gaast_expr_product(p, gaast_expr_rev(r), GAAST_PROD_GEOMETRIC));
+            char what[96];
+            std::snprintf(what, sizeof what, "scaled AND dense-multiplied sparse product n=%d: its buffer stays live", n);
+            every_buffer_read_is_live(e, n, euclid, n == 8 ? GAAST_F32 : GAAST_F64, what, true);
+            gaast_expr_t sw = gaast_expr_product(p, gaast_expr_rev(r), GAAST_PROD_GEOMETRIC);
+            std::snprintf(what, sizeof what, "sandwich n=%d: every buffer read is live", n);
+            every_buffer_read_is_live(sw, n, euclid, GAAST_F64, what, false);
         }
     }
     // the versor inverse of an even multivector at n = 8 in f32 (plan.cpp, beside jit_slab_small: a slab of 259 elements, on register trial)
