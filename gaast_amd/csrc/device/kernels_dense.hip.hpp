@@ -714,6 +714,15 @@ __device__ __forceinline__ void lds_barrier() {
 typedef __attribute__((address_space(3))) unsigned char lds_u8;
 typedef uint32_t uint4v __attribute__((ext_vector_type(4)));
 
+// a ^ b ^ c in one vector instruction (v_bitop3_b32, truth table 0x96); c may be a scalar register
+__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+#if __has_builtin(__builtin_amdgcn_bitop3_b32)
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+#else
+    return a ^ b ^ c;
+#endif
+}
+
 // term t of a step multiplies the words k = mfma16_k(t): even |k| first
 __device__ __forceinline__ constexpr int mfma16_k(int t) {
     constexpr int order[16] = {0, 3, 5, 6, 9, 10, 12, 15, 1, 2, 4, 7, 8, 11, 13, 14};
@@ -730,8 +739,13 @@ __device__ __forceinline__ constexpr int mfma16_k(int t) {
 //   * (-1)^(|a_hi| |k|), |a_hi| = |b_hi| + |c_hi| (mod 2): the b_hi part is folded into the B images (host map); for
 //     the c_hi part the lane's 16 words are stored even-|s2| first, so that each 16-byte quad holds words of one |k|
 //     parity, and lanes with odd |c_hi| read the odd-|k| quads from the image of the other sign.
-// Steps run in chunks of eight (immediate offsets for the A reads, the 16 A addresses move once per chunk): per step of
-// 16 MFMAs (1,024 matrix-pipe cycles) 16 ds_read_b32 + 4 ds_read_b128 and ~10 vector instructions.
+// Steps run in chunks (immediate offsets for the A reads, the 16 A addresses move once per chunk): per step of 16 MFMAs
+// (1,024 matrix-pipe cycles) 16 ds_read_b32 + 4 ds_read_b128.  Vector instructions per step: ~10 where the B address is
+// rebuilt from its parts (sign bit extract, v_lshl_or, xor + add per quad, A moves: n = 13, DEGENERATE at n = 12); 4.25 at
+// n = 12 (XOR_STEP below: the four B addresses stay live and move by one three-operand xor with a lane-constant delta,
+// the A addresses move once per 64 steps).  There the per-item phases are lean as well: the canonicalising add of the
+// fast staging is a wave-uniform branch (2-3 instead of 4 instructions per word), and the store phase requests the
+// lane's 16 out_map words together instead of waiting for each in turn.
 // n = 14 does not fit (4 x 64 KiB) and stays on k_gp_mfma32.
 // ------------------------------------------------------------------------------------------
 // Persistent workgroups: a workgroup walks the groups of IPB items blockIdx.x, blockIdx.x + gridDim.x, ...; when both
@@ -804,7 +818,8 @@ __global__ __launch_bounds__(NDIM == 13 ? 512 : 256, NDIM <= 11 ? 2 : 1) void k_
     // n <= 11: the A addresses are LDS ADDRESSES (the allocation's base included) and are used as such -- otherwise the
     // compiler adds the (zero) base to every one of them in every chunk; at n = 12 that form measured slower (the register
     // allocation it leads to: 16.06 against 15.65 ms), so there the base stays a separate term
-    constexpr bool ABS_A = NDIM <= 11;
+    // (n = 12, non-degenerate: LDS addresses again, since the XOR step loop below keeps its B addresses in that form too)
+    constexpr bool ABS_A = NDIM <= 11 || (NDIM == 12 && !DEGENERATE);
     const uint32_t lds0 = ABS_A ? uint32_t(size_t(lds)) : 0u;
     uint32_t ak0[16];
 #pragma unroll
@@ -829,20 +844,59 @@ __global__ __launch_bounds__(NDIM == 13 ? 512 : 256, NDIM <= 11 ? 2 : 1) void k_
     }
     const uint32_t c_hi_u = uint32_t(c_hi) | 0x8000u;
     // block sign of step a_hi for this lane's column: wave-uniform part on the scalar unit, lane part = and + popcount
-    auto block_sign = [&](int a_hi) -> uint32_t {
+    auto sign_terms = [&](int a_hi, uint32_t& M, uint32_t& u) {   // block sign = u(a_hi) ^ parity(c_hi & M(a_hi)): both wave-uniform
         uint32_t sp = uint32_t(a_hi) >> 1;
         sp ^= sp >> 1;
         sp ^= sp >> 2;
         sp ^= sp >> 4;
         sp ^= sp >> 8;
-        const uint32_t M = sp ^ (uint32_t(a_hi) & p.neg_hi);
-        const uint32_t u = (__builtin_popcount(uint32_t(a_hi) & sp) ^ __builtin_popcount(uint32_t(a_hi) & p.neg_hi)) & 1u;
+        M = sp ^ (uint32_t(a_hi) & p.neg_hi);
+        u = (__builtin_popcount(uint32_t(a_hi) & sp) ^ __builtin_popcount(uint32_t(a_hi) & p.neg_hi)) & 1u;
+    };
+    auto block_sign = [&](int a_hi) -> uint32_t {
+        uint32_t M, u;
+        sign_terms(a_hi, M, u);
         return uint32_t(__builtin_popcount(c_hi_u & (M | (u << 15)))) & 1u;
     };
-    // n <= 12: the signs of all H steps as lane-constant bit masks, computed once per launch (a persistent workgroup
-    // reuses them for every group); n = 13 (8 words, an 8-fold unrolled loop) keeps computing them per step, and so does
-    // the DEGENERATE instantiation at n = 12 (with the masks it needs more than the 256 registers of two waves per SIMD)
-    constexpr int SIGN_WORDS = (H <= 64 || (H == 128 && !DEGENERATE)) ? H / 32 : 0;
+    // n <= 11: the signs of all H steps as lane-constant bit masks, computed once per launch (a persistent workgroup
+    // reuses them for every group); n = 13 (8 words, an 8-fold unrolled loop) and the DEGENERATE instantiation at n = 12
+    // (the zero-block select needs the address in two parts) compute them per step
+    constexpr int SIGN_WORDS = H <= 64 ? H / 32 : 0;
+    // n = 12: the four B quad addresses stay LIVE in registers and move from step a_hi to a_hi + 1 by ONE xor each.  The
+    // address is (lane constant) ^ (a_hi << 7) ^ (swizzle bits of a_hi) ^ (block sign on the NEG bit), and all but u(a_hi)
+    // is linear over GF(2) in the bits of a_hi (M is: a suffix parity and an AND): a_hi -> a_hi + 1 flips the bits
+    // P_t = 2^(t+1) - 1, t = the number of trailing ones of a_hi (seven patterns for 128 steps), which moves the address by
+    // the lane constant
+    //     dlt[t] = (P_t << 7) ^ (swizzle bits of P_t) ^ (parity(c_hi & M(P_t)) on the NEG bit),
+    // seven registers computed once per launch.  u is quadratic in a_hi but wave-uniform: ud holds u(a_hi) ^ u(a_hi + 1)
+    // for every step as 128 bits in scalar registers, and joins the xor as its third, scalar operand.
+    // The live addresses are LDS addresses (base included), so the xor must not reach the base: the kernel has no static
+    // LDS, its dynamic segment starts at address 0, and the deltas stay below 2^(n+4) = 64 KiB.
+    constexpr bool XOR_STEP = NDIM == 12 && !DEGENERATE;
+    if (XOR_STEP && (lds0 & ((16u << n) - 1u))) __builtin_trap();
+    uint32_t dlt[XOR_STEP ? 7 : 1] = {0};
+    uint32_t ud[XOR_STEP ? H / 32 : 1] = {0};
+    if constexpr (XOR_STEP) {
+#pragma unroll
+        for (int t = 0; t < 7; ++t) {
+            const uint32_t P = (2u << t) - 1u;
+            uint32_t M, u;
+            sign_terms(int(P), M, u);
+            dlt[t] = (P << 7) ^ (((P >> 1) & 7u) << 4) ^ ((uint32_t(__builtin_popcount(uint32_t(c_hi) & M)) & 1u) << (n + 2));
+        }
+#pragma unroll
+        for (int w = 0; w < H / 32; ++w) {
+            uint32_t bits = 0;
+#pragma unroll 1
+            for (int b = 0; b < 32; ++b) {
+                uint32_t M, u0, u1;
+                sign_terms(32 * w + b, M, u0);
+                sign_terms(32 * w + b + 1, M, u1);
+                bits |= (u0 ^ u1) << b;
+            }
+            ud[w] = __builtin_amdgcn_readfirstlane(bits);
+        }
+    }
     uint32_t sgn[SIGN_WORDS > 0 ? SIGN_WORDS : 1] = {0};
 #pragma unroll
     for (int w = 0; w < SIGN_WORDS; ++w) {
@@ -857,8 +911,7 @@ __global__ __launch_bounds__(NDIM == 13 ? 512 : 256, NDIM <= 11 ? 2 : 1) void k_
         const int nitems = int(p.batch - item0 < IPB ? p.batch - item0 : IPB);
         // ---- both operands of the group's items into their +/- images ----
         if (fast) {
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
+            auto stage_row = [&](int r, bool canon) {
                 const int k = r % IPB, side = r / IPB;
                 if (k < nitems) {
 #pragma unroll
@@ -869,13 +922,23 @@ __global__ __launch_bounds__(NDIM == 13 ? 512 : 256, NDIM <= 11 ? 2 : 1) void k_
                         for (int c = 0; c < 4; ++c) {
                             const uint32_t w = mw[side][4 * m + c];
                             float y = x[c];
-                            if (side ? p.canon_right : p.canon_left) y = 0.f + y;   // the reference's zero-init + add_grades_from copy
+                            if (canon) y = 0.f + y;   // the reference's zero-init + add_grades_from copy
                             const uint32_t yb = __float_as_uint(y) ^ (w & 0x80000000u);
                             const uint32_t at = uint32_t(k) * uint32_t(item_stride * 4) + (side ? 2u * NEG : 0u) + (((w >> 16) & 0x7fffu) << 2);
                             *(__attribute__((address_space(3))) uint32_t*)(lds + at) = yb;
                             *(__attribute__((address_space(3))) uint32_t*)(lds + at + NEG) = yb ^ 0x80000000u;
                         }
                     }
+                }
+            };
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                if constexpr (XOR_STEP) {
+                    // canon is wave-uniform: a branch around two copies instead of an add + a select for every word
+                    if (r / IPB ? p.canon_right : p.canon_left) stage_row(r, true);
+                    else stage_row(r, false);
+                } else {
+                    stage_row(r, r / IPB ? p.canon_right : p.canon_left);
                 }
             }
         } else {
@@ -906,9 +969,13 @@ __global__ __launch_bounds__(NDIM == 13 ? 512 : 256, NDIM <= 11 ? 2 : 1) void k_
             float16v acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-            uint32_t ak[16];
+            // (n = 12: the loop leaves the addresses where it found them and works on ak0 itself)
+            uint32_t akc[XOR_STEP ? 1 : 16];
+            uint32_t (&ak)[16] = *reinterpret_cast<uint32_t (*)[16]>(XOR_STEP ? ak0 : akc);
+            if constexpr (!XOR_STEP) {
 #pragma unroll
-            for (int t = 0; t < 16; ++t) ak[t] = ak0[t];
+                for (int t = 0; t < 16; ++t) ak[t] = ak0[t];
+            }
 
             // one step: the lane's B block a_hi ^ c_hi from the image of its block sign (sxs carries the sign as the NEG
             // address bit), the 16 A words of the step at immediate offsets, 16 MFMAs
@@ -997,30 +1064,42 @@ __global__ __launch_bounds__(NDIM == 13 ? 512 : 256, NDIM <= 11 ? 2 : 1) void k_
                         for (int t = 0; t < 16; ++t) ak[t] += 16u << 7;
                     }
                 }
-            } else if constexpr (SIGN_WORDS > 0) {
-                // n = 12: round 2's loop (every read in its step); the pipelined form measures 1 % SLOWER there (15.65 -> 15.83 ms,
-                // same box, tools/ab_r3a.sh) while n = 10 / 11 gain 6.5 / 3.7 % -- at n = 12 the other wave of the SIMD already
-                // covers the read latency and the extra bookkeeping of the pipeline costs more than it hides
-                // block signs from the per-launch bit masks: two vector instructions per step (bit, address bit) instead
-                // of five; chunks of 16 steps (the A addresses move once per chunk)
+            } else if constexpr (XOR_STEP) {
+                // n = 12: every read in its step (no software pipeline: the other wave of the SIMD covers the read latency),
+                // two chunks of 64 steps: the A words at immediate offsets 128 j, their 16 addresses move once per chunk; the B
+                // quad addresses move by one three-operand xor each per step (dlt[t] with t a compile-time constant inside
+                // the chunk, the step's u bit from the scalar unit) -- 4 vector instructions per step + 16 per chunk (one xor per A
+                // address: bit 13 is clear in every ak0, so the second xor restores them for the next item)
+                uint32_t xb[4];
 #pragma unroll
-                for (int w = 0; w < SIGN_WORDS; ++w) {
-                    uint32_t sw = sgn[w];
+                for (int q = 0; q < 4; ++q) xb[q] = lds0 + (b_base | bq[q]);   // step 0: a_hi = 0, block sign +
 #pragma unroll 1
-                    for (int c = 0; c < 2; ++c) {
-                        const int a0 = 32 * w + 16 * c;
+                for (int c = 0; c < H / 64; ++c) {
+                    const uint32_t udw[2] = {c == 0 ? ud[0] : ud[2], c == 0 ? ud[1] : ud[3]};
 #pragma unroll
-                        for (int j = 0; j < 16; ++j) {
-                            const int a_hi = a0 + j;
-                            // (wave-uniform: kept on the scalar unit, one v_lshl_or_b32 joins it with the lane's sign bit)
-                            uint32_t sx = __builtin_amdgcn_readfirstlane((uint32_t(a_hi) << 7) | (uint32_t((a_hi >> 1) & 7) << 4));
-                            asm("" : "+s"(sx));   // whole, in a scalar register: otherwise its parts are OR-ed in one by one on the vector unit
-                            step(a_hi, j, (((sw >> j) & 1u) << (n + 2)) | sx);
+                    for (int j = 0; j < 64; ++j) {
+                        uint32_t bw[16], aw[16];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const uint4v v = *(__attribute__((address_space(3))) const uint4v*)size_t(xb[q]);
+                            bw[4 * q + 0] = v.x; bw[4 * q + 1] = v.y; bw[4 * q + 2] = v.z; bw[4 * q + 3] = v.w;
                         }
-                        sw >>= 16;
 #pragma unroll
-                        for (int t = 0; t < 16; ++t) ak[t] += 16u << 7;
+                        for (int t = 0; t < 16; ++t)
+                            aw[t] = *(__attribute__((address_space(3))) const uint32_t*)size_t(ak[t] + uint32_t(j << 7));
+#pragma unroll
+                        for (int t = 0; t < 16; ++t)
+                            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(aw[t]), __uint_as_float(bw[t]), acc, 0, 0, 0);
+                        asm volatile("" ::: "memory");   // keep the LDS reads of a step in their step
+                        // on to step a_hi + 1
+                        uint32_t su = __builtin_amdgcn_readfirstlane(((udw[j >> 5] >> (j & 31)) & 1u) << (n + 2));
+                        asm("" : "+s"(su));   // in a scalar register: the third operand of the xor
+                        const uint32_t d = dlt[j < 63 ? __builtin_ctz(~uint32_t(j)) : 6];   // (63 -> 64 flips seven bits)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) xb[q] = xor3(xb[q], d, su);
                     }
+#pragma unroll
+                    for (int t = 0; t < 16; ++t) ak[t] ^= 64u << 7;   // to the second chunk, and back for the next item
                 }
             } else {
                 for (int a0 = 0; a0 < H; a0 += 8) {
@@ -1037,11 +1116,35 @@ __global__ __launch_bounds__(NDIM == 13 ? 512 : 256, NDIM <= 11 ? 2 : 1) void k_
 
             // ---- accumulator (row = c_lo, column = this lane's c_hi) -> graded row ----
             float* orow = p.out + (item0 + it) * p.out_stride;
-            const int32_t* om = p.out_map + (c_hi << 5);
+            if constexpr (XOR_STEP) {
+                // store_result's arithmetic, with the lane's 16 out_map words requested together (one round trip to the
+                // cache instead of sixteen in turn) and the reordering signs behind a wave-uniform branch
+                const int32_t* om = p.out_map + (c_hi << 5);
+                int32_t ow[16];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int c_lo = (r & 3) + 8 * (r >> 2) + 4 * h;
-                store_result<float>(orow, om[c_lo], acc[r], p.beta, out_scale, (c_hi << 5) + c_lo);
+                for (int r = 0; r < 16; ++r) ow[r] = om[(r & 3) + 8 * (r >> 2) + 4 * h];
+                asm volatile("" ::: "memory");
+                auto put = [&](bool signs, bool beta) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int32_t w = ow[r];
+                        if (w < 0) continue;
+                        float v = acc[r];
+                        if (out_scale) v = v * out_scale[(c_hi << 5) + (r & 3) + 8 * (r >> 2) + 4 * h];
+                        if (signs && (w & 0x40000000)) v = beta ? -v : 0.f + (-v);
+                        float* dst = orow + (signs ? w & 0x3fffffff : w);
+                        *dst = beta ? *dst + v : v;
+                    }
+                };
+                if (p.out_signs) put(true, p.beta != 0);
+                else put(false, p.beta != 0);
+            } else {
+                const int32_t* om = p.out_map + (c_hi << 5);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int c_lo = (r & 3) + 8 * (r >> 2) + 4 * h;
+                    store_result<float>(orow, om[c_lo], acc[r], p.beta, out_scale, (c_hi << 5) + c_lo);
+                }
             }
         }
         lds_barrier<THREADS>();   // the images are rewritten by the next group
