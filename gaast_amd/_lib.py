@@ -27,6 +27,8 @@ FLAG_DEBUG_OVERFLOW, FLAG_NO_FUSION, FLAG_EXACT_ORDER, FLAG_NO_MFMA, FLAG_NO_JIT
 FLAG_DEBUG_JIT_FAILS, FLAG_DEBUG_KEEP_JIT_SOURCE, FLAG_EXP_LOG, FLAG_NO_COALESCE, FLAG_DEBUG_LDS_12K = 0x40, 0x80, 0x100, 0x200, 0x400
 FLAG_DEBUG_NO_CHAIN = 0x800
 COMM_ID_BYTES = 128
+# gaast_jit_cache_counter, in order
+JIT_CACHE_COUNTERS = ("compiled", "memory_hits", "disk_hits", "disk_stores", "disk_rejected", "live_modules")
 
 
 class GaastError(RuntimeError):
@@ -116,6 +118,8 @@ SIGNATURES = {
     "gaast_hip_program_create_in_basis": (_ci, [C.POINTER(ProgramDesc), _pd, C.POINTER(_vp)]),
     "gaast_hip_program_create_vjp": (_ci, [C.POINTER(ProgramDesc), C.c_int32, C.POINTER(_vp)]),
     "gaast_hip_mv_sum_rows": (_ci, [_vp, _vp]),
+    "gaast_hip_jit_cache_set_dir": (_ci, [C.c_char_p]),
+    "gaast_hip_jit_cache_stats": (_ci, [C.POINTER(_i64), _ci]),
     # ---- include/gaast_expr.h ----
     "gaast_expr_last_error": (C.c_char_p, []),
     "gaast_gs_single": (_u64, [_i64]),
@@ -205,3 +209,20 @@ def init_device(device_id=None):
     ids = (C.c_int * 1)(device_id)
     check(lib().gaast_hip_init(ids, 1))
     _device_ready = True
+
+
+def jit_cache_dir(path):
+    """Keep compiled program kernels in `path` (created if missing) for later processes; None or "" turns that off.
+
+    Kernels are always shared inside a process; nothing is written to disk unless this has been called.  Works before
+    init_device and without a GPU."""
+    check(lib().gaast_hip_jit_cache_set_dir(os.fsencode(path) if path else None))
+
+
+def jit_cache_stats():
+    """The process's kernel-cache counters (gaast_jit_cache_counter) as a dict: compiled, memory_hits, disk_hits,
+    disk_stores, disk_rejected, live_modules."""
+    n = lib().gaast_hip_jit_cache_stats(None, 0)
+    out = (C.c_int64 * n)()
+    lib().gaast_hip_jit_cache_stats(out, n)
+    return {name: int(out[i]) for i, name in enumerate(JIT_CACHE_COUNTERS[:n])}

@@ -6,8 +6,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <atomic>
 #include <cstring>
+#include <map>
 #include <memory>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -17,10 +20,16 @@
 #include "comm.hpp"
 #include "gaast_expr.h"
 #include "gaast_hip.h"
+#include "jit_cache.hpp"
 #include "kernels.hip.hpp"
 #include "plan.hpp"
 
 using namespace gaast;
+
+// revision of everything that decides which kernel code runs (csrc/Makefile: KREV)
+#ifndef GAAST_KERNELS_REV
+#define GAAST_KERNELS_REV "unknown"
+#endif
 
 // ------------------------------------------------------------------------------------------
 // state
@@ -114,25 +123,56 @@ private:
     }
 };
 
-// A kernel compiled through hiprtc: the code image, the module loaded from it and its entry point
-struct JitKernel {
+// ---- run-time compiled kernels and their cache (include/gaast_hip.h: gaast_hip_jit_cache_*) ------------------------------
+// One compiled kernel of the process: the code image, the module loaded from it and its entry point.  Every program whose
+// generated source, entry point and compile options hash to the same key holds the same entry; the module is unloaded when
+// the last of them is destroyed (gaast_hip_program_destroy has synchronised the stream by then).
+struct JitEntry {
+    jitcache::Digest key{};
     // HIP's header does not say that hipModuleLoadData copies the image: it stays alive for as long as the module does.
-    // (Members are destroyed after the destructor's body: the module is unloaded before the image is freed.  A move of
-    // the vector keeps code.data() where it is.)
+    // (Members are destroyed after the destructor's body: the module is unloaded before the image is freed.)
     std::vector<char> code;
     hipModule_t module = nullptr;
     hipFunction_t fn = nullptr;
+    JitEntry() = default;
+    JitEntry(const JitEntry&) = delete;
+    JitEntry& operator=(const JitEntry&) = delete;
+    ~JitEntry();
+};
+
+enum { JIT_COMPILED, JIT_MEMORY_HITS, JIT_DISK_HITS, JIT_DISK_STORES, JIT_DISK_REJECTED, JIT_LIVE_MODULES, JIT_N_COUNTERS };
+static_assert(JIT_N_COUNTERS == GAAST_JIT_CACHE_N_COUNTERS && JIT_LIVE_MODULES == GAAST_JIT_CACHE_LIVE_MODULES, "counter order of gaast_hip.h");
+
+// Never destroyed: a program may be destroyed (and its entries with it) while the process is on its way out
+struct JitCache {
+    std::mutex mutex;                                               // guards live and dir
+    std::map<jitcache::Digest, std::weak_ptr<JitEntry>> live;       // the in-process level: always on
+    std::string dir;                                                // the directory level: off while empty
+    std::string compiler;                                           // hiprtcVersion, asked once
+    std::atomic<int64_t> counters[JIT_N_COUNTERS] = {};
+};
+JitCache& jit_cache() {
+    static JitCache* c = new JitCache;
+    return *c;
+}
+
+JitEntry::~JitEntry() {
+    if (module) {
+        (void)hipModuleUnload(module);
+        jit_cache().counters[JIT_LIVE_MODULES]--;
+    }
+    JitCache& c = jit_cache();
+    std::lock_guard<std::mutex> lock(c.mutex);
+    auto it = c.live.find(key);
+    if (it != c.live.end() && it->second.expired()) c.live.erase(it);   // (not a newer entry under the same key)
+}
+
+// A program's handle on a compiled kernel
+struct JitKernel {
+    std::shared_ptr<JitEntry> entry;
+    hipFunction_t fn = nullptr;   // entry->fn
     JitKernel() = default;
-    JitKernel(JitKernel&& o) noexcept : code(std::move(o.code)), module(o.module), fn(o.fn) { o.module = nullptr; }
-    JitKernel& operator=(JitKernel&& o) noexcept {
-        std::swap(code, o.code);
-        std::swap(module, o.module);
-        std::swap(fn, o.fn);
-        return *this;
-    }
-    ~JitKernel() {
-        if (module) (void)hipModuleUnload(module);
-    }
+    explicit JitKernel(std::shared_ptr<JitEntry> e) : entry(std::move(e)), fn(entry ? entry->fn : nullptr) {}
     explicit operator bool() const { return fn != nullptr; }
 };
 
@@ -971,13 +1011,27 @@ int run_step(const Launch& L, const Bound& res, const Bound& a, const Bound& b, 
     return GAAST_OK;
 }
 
-// hiprtc specialisation of a fused plan or a list chain: an empty kernel on any failure (then the generic kernel stays in charge)
-// (contract: the variant with fused multiply-adds, kept beside the exact one -- Launch::jit_fma)
-JitKernel jit_compile(const std::string& source, const char* entry, std::string* log, bool contract = false) {
+// Loads a code image as a module of its own; null when HIP refuses it
+std::shared_ptr<JitEntry> jit_load(const jitcache::Digest& key, std::vector<char> code, const char* entry) {
+    auto e = std::make_shared<JitEntry>();
+    e->key = key;
+    e->code = std::move(code);
+    if (hipModuleLoadData(&e->module, e->code.data()) != hipSuccess) {
+        e->module = nullptr;
+        return nullptr;
+    }
+    jit_cache().counters[JIT_LIVE_MODULES]++;
+    if (hipModuleGetFunction(&e->fn, e->module, entry) != hipSuccess) return nullptr;
+    return e;
+}
+
+// hiprtc itself: the code object of `source`, empty on any failure (*log says why)
+std::vector<char> hiprtc_compile(const std::string& source, const std::vector<std::string>& options, std::string* log) {
     hiprtcProgram prog = nullptr;
     if (hiprtcCreateProgram(&prog, source.c_str(), "gaast_jit.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) return {};
-    const char* opts[] = {"--offload-arch=gfx950", "-O3", contract ? "-ffp-contract=fast" : "-ffp-contract=off"};
-    const hiprtcResult res = hiprtcCompileProgram(prog, 3, opts);
+    std::vector<const char*> opts;
+    for (const std::string& o : options) opts.push_back(o.c_str());
+    const hiprtcResult res = hiprtcCompileProgram(prog, int(opts.size()), opts.data());
     if (res != HIPRTC_SUCCESS) {
         size_t n = 0;
         hiprtcGetProgramLogSize(prog, &n);
@@ -987,21 +1041,75 @@ JitKernel jit_compile(const std::string& source, const char* entry, std::string*
         return {};
     }
     size_t cs = 0;
-    JitKernel k;
+    std::vector<char> code;
     bool got = hiprtcGetCodeSize(prog, &cs) == HIPRTC_SUCCESS && cs > 0;
     if (got) {
-        k.code.resize(cs);
-        got = hiprtcGetCode(prog, k.code.data()) == HIPRTC_SUCCESS;
+        code.resize(cs);
+        got = hiprtcGetCode(prog, code.data()) == HIPRTC_SUCCESS;
     }
     hiprtcDestroyProgram(&prog);
     if (!got) {
         *log = "hiprtcGetCodeSize / hiprtcGetCode failed";
         return {};
     }
-    hipFunction_t fn = nullptr;
-    if (hipModuleLoadData(&k.module, k.code.data()) != hipSuccess || hipModuleGetFunction(&fn, k.module, entry) != hipSuccess) return {};
-    k.fn = fn;
-    return k;
+    return code;
+}
+
+// hiprtc specialisation of a fused plan or a list chain: an empty kernel on any failure (then the generic kernel stays in charge)
+// (contract: the variant with fused multiply-adds, kept beside the exact one -- Launch::jit_fma)
+// The ONE lookup point of the kernel cache: the modules alive in this process, then the directory (if one is set), then the
+// compiler; only what the compiler produced is stored.  GAAST_FLAG_DEBUG_JIT_FAILS fails before either level is asked.
+JitKernel jit_compile(const std::string& source, const char* entry, std::string* log, uint32_t flags, bool contract = false) {
+    if (flags & GAAST_FLAG_DEBUG_JIT_FAILS) return {};
+    JitCache& c = jit_cache();
+    jitcache::KeyFields kf;
+    kf.revision = GAAST_KERNELS_REV;
+    kf.target = "gfx950";
+    kf.options = {"--offload-arch=gfx950", "-O3", contract ? "-ffp-contract=fast" : "-ffp-contract=off"};
+    kf.entry = entry;
+    kf.source = source;
+    std::string dir;
+    {
+        std::lock_guard<std::mutex> lock(c.mutex);
+        if (c.compiler.empty()) {
+            int major = 0, minor = 0;
+            if (hiprtcVersion(&major, &minor) != HIPRTC_SUCCESS) return {};
+            c.compiler = std::to_string(major) + "." + std::to_string(minor);
+        }
+        kf.compiler = c.compiler;
+        dir = c.dir;
+    }
+    const jitcache::Digest key = jitcache::make_key(kf);
+    {
+        std::lock_guard<std::mutex> lock(c.mutex);
+        auto it = c.live.find(key);
+        if (it != c.live.end())
+            if (std::shared_ptr<JitEntry> e = it->second.lock()) {
+                c.counters[JIT_MEMORY_HITS]++;
+                return JitKernel(std::move(e));
+            }
+    }
+    std::shared_ptr<JitEntry> e;
+    if (!dir.empty()) {
+        std::vector<char> code;
+        const jitcache::Load got = jitcache::load(dir, kf.revision, key, &code);
+        if (got == jitcache::Load::Ok && (e = jit_load(key, std::move(code), entry)))
+            c.counters[JIT_DISK_HITS]++;
+        else if (got != jitcache::Load::Missing)
+            c.counters[JIT_DISK_REJECTED]++;   // (a checked file HIP still refuses: as good as a bad one; replaced below)
+    }
+    if (!e) {
+        std::vector<char> code = hiprtc_compile(source, kf.options, log);
+        if (code.empty()) return {};
+        c.counters[JIT_COMPILED]++;
+        // a store that fails (no such directory, read-only, full disk) costs the next process a compilation, nothing else
+        if (!dir.empty() && jitcache::store(dir, kf.revision, key, code.data(), code.size())) c.counters[JIT_DISK_STORES]++;
+        e = jit_load(key, std::move(code), entry);
+        if (!e) return {};
+    }
+    std::lock_guard<std::mutex> lock(c.mutex);
+    c.live[key] = e;
+    return JitKernel(std::move(e));
 }
 
 // When does the contracted variant of a specialised kernel pay?  An item costs ~2 vector instructions per comp-mul (4 cycles per
@@ -1164,7 +1272,7 @@ bool compile_fused(gaast_hip_program_s& prog, uint32_t flags, uint32_t* rebuild_
         if (s.kind != Step::FUSED || s.fused.jit_source.empty()) continue;
         if (flags & GAAST_FLAG_DEBUG_KEEP_JIT_SOURCE) prog.plan.jit_source_kept += s.fused.jit_source;
         std::string log;
-        if (!(flags & GAAST_FLAG_DEBUG_JIT_FAILS)) L.jit = jit_compile(s.fused.jit_source, "gaast_jit", &log);
+        L.jit = jit_compile(s.fused.jit_source, "gaast_jit", &log, flags);
         if (L.jit)
             s.name = "ast_jit" + s.name.substr(s.name.find('[')) + (s.fused.jit_items ? " slab in LDS" : "");
         else if (!log.empty())
@@ -1183,7 +1291,7 @@ bool compile_fused(gaast_hip_program_s& prog, uint32_t flags, uint32_t* rebuild_
         if (L.jit && !trial_failed && !(flags & GAAST_FLAG_EXACT_ORDER) && !s.fused.jit_items && !prog.plan.has_explog &&
             arithmetic_bound(s.n_entries, double(prog.plan.out_layout.row_len) * dtype_size(prog.plan.dtype))) {
             std::string log2;
-            L.jit_fma = jit_compile(s.fused.jit_source, "gaast_jit", &log2, true);
+            L.jit_fma = jit_compile(s.fused.jit_source, "gaast_jit", &log2, flags, true);
             if (L.jit_fma) s.name += " | fused multiply-adds under shared operands";
         }
         std::string().swap(s.fused.jit_source);
@@ -1204,7 +1312,7 @@ void compile_chains(gaast_hip_program_s& prog, uint32_t flags) {
         if (!s.cj.on) continue;
         if (flags & GAAST_FLAG_DEBUG_KEEP_JIT_SOURCE) prog.plan.jit_source_kept += s.cj.source;
         std::string log;
-        ls[i].jit = jit_compile(s.cj.source, "gaast_chain", &log);
+        ls[i].jit = jit_compile(s.cj.source, "gaast_chain", &log, flags);
         if (!ls[i].jit && !log.empty()) g_err = "hiprtc: " + log;
         std::string().swap(s.cj.source);
         if (!ls[i].jit) {
@@ -1331,9 +1439,6 @@ int program_create_impl(const gaast_program_desc* desc, gaast_hip_program_t* out
 extern "C" {
 
 const char* gaast_hip_last_error(void) { return g_err.c_str(); }
-#ifndef GAAST_KERNELS_REV
-#define GAAST_KERNELS_REV "unknown"
-#endif
 const char* gaast_hip_version(void) { return "gaast-hip 0.2 (gfx950) kernels " GAAST_KERNELS_REV; }
 
 int gaast_hip_init(const int* device_ids, int n_dev) {
@@ -1635,6 +1740,23 @@ int gaast_hip_program_destroy(gaast_hip_program_t prog) {
     }
     delete prog;
     return GAAST_OK;
+}
+
+int gaast_hip_jit_cache_set_dir(const char* path) {
+    JitCache& c = jit_cache();
+    std::lock_guard<std::mutex> lock(c.mutex);
+    c.dir.clear();
+    if (!path || !*path) return GAAST_OK;
+    if (!jitcache::prepare_dir(path))
+        return set_err(GAAST_ERR_INVALID_ARGUMENT, std::string("jit_cache_set_dir: cannot create or is not a directory: ") + path);
+    c.dir = path;
+    return GAAST_OK;
+}
+
+int gaast_hip_jit_cache_stats(int64_t* out, int n) {
+    JitCache& c = jit_cache();
+    for (int i = 0; out && i < n && i < JIT_N_COUNTERS; ++i) out[i] = c.counters[i].load();
+    return JIT_N_COUNTERS;
 }
 
 int gaast_hip_program_domain_errors(gaast_hip_program_t prog, int64_t* count) {

@@ -217,6 +217,49 @@ int gaast_hip_program_domain_errors(gaast_hip_program_t prog, int64_t *count);
 /* GAAST_FLAG_DEBUG_KEEP_JIT_SOURCE: the HIP source generated for this program ("" if none). */
 const char *gaast_hip_program_jit_source(gaast_hip_program_t prog);
 
+/* ---- cache of compiled program kernels ------------------------------------------------------ */
+/*
+ * Small and medium programs run as kernels generated per program and compiled at gaast_hip_program_create (gaast_jit,
+ * gaast_chain): set-up the reference's eval does not have (eval.rs:12-19 evaluates at once).  Compiled kernels are therefore
+ * reused, on two levels, under one key: SHA-256 over the kernel revision gaast_hip_version() reports, the hiprtc version, the
+ * target, every compile option, the entry point's name and the generated source (each field preceded by its length).
+ *  - In the process, always: programs whose kernels have the same key share ONE loaded module, unloaded when the last of
+ *    them is destroyed.  This changes the time of program creation only -- no launch name, no bit of any result.
+ *  - In a directory, once the caller names one (the library reads no environment variable and writes no file otherwise): the
+ *    code object exactly as the compiler returned it, so a later process loads the very code this one ran.
+ *
+ * File <dir>/<64 lower-case hex digits of the key>.gaastco, integers little-endian, no padding:
+ *     offset   0   8 bytes   magic "GAASTCO\0"
+ *     offset   8   uint32    format version (1)
+ *     offset  12  32 bytes   kernel revision string, NUL-padded (its first 32 bytes if longer)
+ *     offset  44  32 bytes   the key
+ *     offset  76   uint64    payload length L; the file is exactly 116 + L bytes long
+ *     offset  84  32 bytes   SHA-256 of the payload
+ *     offset 116   L bytes   payload: the code object as hiprtcGetCode returned it
+ * A file is written under a temporary name in the same directory (<final name>.tmp.<pid>.<serial>) and renamed onto its
+ * final name, so concurrent writers (the ranks of a launch) leave one complete file.  A file that fails any check on load
+ * (magic, version, revision, key, length against its size, payload hash) is never used: the kernel is compiled and the file
+ * replaced.  Failures to write are ignored; program creation never fails because of the cache.  Only successful compilations
+ * are stored.  Nothing is ever evicted.
+ */
+/* Turns the directory level on (eval.rs:12-19 has no set-up; this keeps ours to the first process).  NULL or "": off.
+ * Otherwise the last component of `path` is created when missing; GAAST_ERR_INVALID_ARGUMENT, and the level off, when it
+ * cannot be created or is not a directory.  Needs neither gaast_hip_init nor a GPU. */
+int gaast_hip_jit_cache_set_dir(const char *path);
+typedef enum gaast_jit_cache_counter {
+    GAAST_JIT_CACHE_COMPILED = 0,      /* kernels compiled by hiprtc (successfully) */
+    GAAST_JIT_CACHE_MEMORY_HITS = 1,   /* kernels taken from a module already loaded in this process */
+    GAAST_JIT_CACHE_DISK_HITS = 2,     /* kernels loaded from a checked file of the directory */
+    GAAST_JIT_CACHE_DISK_STORES = 3,   /* files written (renamed into place) */
+    GAAST_JIT_CACHE_DISK_REJECTED = 4, /* files found and not used: a failed check, or a code object HIP refused */
+    GAAST_JIT_CACHE_LIVE_MODULES = 5,  /* modules loaded now (the one counter that also falls) */
+    GAAST_JIT_CACHE_N_COUNTERS = 6
+} gaast_jit_cache_counter;
+/* How much of program creation's set-up (absent from eval.rs:12-19) was compilation: fills out[0 .. min(n, count)) with the
+ * process's counters in the order of gaast_jit_cache_counter and returns how many counters exist (never an error; out may be
+ * NULL with n = 0).  Needs neither gaast_hip_init nor a GPU. */
+int gaast_hip_jit_cache_stats(int64_t *out, int n);
+
 /* ---- GradedDataMut on the device (graded.rs:51-79) ------------------------------------- */
 /* init_null_mv(dim, gs) for `batch` items: zero-filled rows (graded.rs:195-201). */
 int gaast_hip_mv_alloc(int dim, uint64_t grade_mask, int64_t batch, int dtype, gaast_hip_mv_t *out);

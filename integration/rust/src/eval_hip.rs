@@ -74,6 +74,19 @@ pub fn clear_program_cache() {
     PROGRAM_CACHE.with(|c| c.borrow_mut().clear());
 }
 
+/// The map above is keyed by the address of an AST: it saves nothing for an equal AST built elsewhere, and nothing across
+/// processes.  The library shares compiled kernels between equal programs of a process by itself; this keeps them in `dir`
+/// (created if missing) for later processes as well -- `None` turns that off.  Callable before `gaast_hip_init`.
+pub fn set_cache_dir(dir: Option<&std::path::Path>) -> bool {
+    use std::os::unix::ffi::OsStrExt;
+    let st = match dir.map(|d| std::ffi::CString::new(d.as_os_str().as_bytes())) {
+        None => unsafe { gaast_hip_jit_cache_set_dir(std::ptr::null()) },
+        Some(Ok(c)) => unsafe { gaast_hip_jit_cache_set_dir(c.as_ptr()) },
+        Some(Err(_)) => return false, // a NUL inside the path
+    };
+    st == 0
+}
+
 /// One `SpecializedAst` bound to its device program and to the values its `GradedObj` nodes hold right now.
 pub struct HipProgram<'a, T> {
     prog: Rc<DeviceProgram>,

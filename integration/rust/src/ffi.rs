@@ -112,6 +112,10 @@ extern "C" {
     // reverse mode: the VJP of a program w.r.t. one input slot (cotangent at slot n_inputs), and the sum of a batch's rows
     pub fn gaast_hip_program_create_vjp(desc: *const GaastProgramDesc, wrt_slot: i32, out: *mut Program) -> c_int;
     pub fn gaast_hip_mv_sum_rows(input: Mv, out: Mv) -> c_int;
+    // cache of compiled program kernels (eval.rs:12-19 has no set-up): a directory later processes load from, and the counters
+    // (compiled, memory hits, disk hits, disk stores, disk rejected, live modules -- GAAST_JIT_CACHE_* in gaast_hip.h)
+    pub fn gaast_hip_jit_cache_set_dir(path: *const std::os::raw::c_char) -> c_int;
+    pub fn gaast_hip_jit_cache_stats(out: *mut i64, n: c_int) -> c_int;
     // multi-GPU (one process per GPU): the gather of result rows over RCCL, see include/gaast_hip.h
     /// which shared object provides the nccl* entry points (NULL = the system's librccl); before the first comm call
     pub fn gaast_hip_comm_set_library(path: *const std::os::raw::c_char) -> c_int;
