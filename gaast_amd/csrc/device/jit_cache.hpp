@@ -32,7 +32,7 @@ std::string hex(const Digest& d);   // 64 lower-case digits
 
 // Everything that decides the bytes hiprtc returns for one kernel
 struct KeyFields {
-    std::string revision;               // GAAST_KERNELS_REV: the generators (plan.cpp) and the launcher
+    std::string revision;               // GAAST_KERNELS_REV: the generators (plan_fused.cpp, plan_chain_jit.cpp) and the launcher
     std::string compiler;               // hiprtcVersion, "major.minor"
     std::string target;                 // "gfx950"
     std::vector<std::string> options;   // as passed to hiprtcCompileProgram, in order

@@ -12,7 +12,7 @@
 //   (3) products whose list is a dense slice of the geometric product's table run on the
 //       bitmask-tiled kernel (re-ordered sums: tolerance, not bit-exact; GAAST_FLAG_EXACT_ORDER
 //       keeps them on the exact kernel).
-#include "plan.hpp"
+#include "plan_internal.hpp"
 #include "spinor_basis.hpp"
 
 #include <algorithm>
@@ -23,9 +23,6 @@
 #include <map>
 #include <stdexcept>
 
-#ifndef GAAST_JIT_NT
-#define GAAST_JIT_NT 3   /* bit 0: nontemporal span stores, bit 1: nontemporal span loads in the specialised kernels (A/B switch; both: config 5 0.70 -> 0.78-0.82 of 8 TB/s) */
-#endif
 namespace gaast {
 namespace {
 
@@ -1095,739 +1092,6 @@ struct Lowering {
     }
 };
 
-
-// ---------------------------------------------------------------------------------------------
-// Whole-plan fusion for small programs: every buffer becomes a region of a per-item LDS slab and
-// the steps become one micro-op stream (k_ast_fused).  Exact: same operations, same order.
-// ---------------------------------------------------------------------------------------------
-// slab_probe != nullptr: only report the slab size a fused plan would have (0: cannot be fused) and change nothing
-bool try_fuse(Plan& plan, bool small_reg_slab, int* slab_probe = nullptr) {
-    if (slab_probe) *slab_probe = 0;
-    if (plan.flags & GAAST_FLAG_NO_FUSION) return false;
-    if (plan.error != GAAST_OK || plan.steps.empty()) return false;
-    const size_t elem = plan.dtype == GAAST_F32 ? 4 : 8;
-    // which buffers are touched, and how inputs are read
-    std::vector<int> in_direct(plan.inputs.size(), 0), in_axpy(plan.inputs.size(), 0);
-    for (const Step& s : plan.steps) {
-        if (s.kind == Step::PRODUCT_DENSE || s.kind == Step::FUSED) return false;
-        if (s.kind == Step::AXPY) in_axpy[size_t(s.a.idx)] = 1;
-        if (s.kind == Step::PRODUCT_CSR) {
-            if (s.a.kind == BufKind::INPUT) (s.canon_a ? in_direct : in_axpy)[size_t(s.a.idx)] = 1;
-            if (s.b.kind == BufKind::INPUT) (s.canon_b ? in_direct : in_axpy)[size_t(s.b.idx)] = 1;
-        }
-    }
-    Step f;
-    f.kind = Step::FUSED;
-    f.res = BufRef{BufKind::OUT, 0};
-    int cursor = 0;
-    // an input read both ways gets two images: the raw rows (add_grades_from) and 0.0 + x
-    // (the zero-init + copy the reference makes of a product operand)
-    std::vector<int> in_base(plan.inputs.size(), -1), in_base_canon(plan.inputs.size(), -1);
-    std::vector<int> node_base(plan.node_buffers.size(), -1);
-    for (size_t i = 0; i < plan.inputs.size(); ++i) {
-        if (plan.input_layouts[i].row_len == 0) continue;
-        if (in_axpy[i]) {
-            in_base[i] = cursor;
-            f.fused.inputs.push_back({int(i), cursor, 0});
-            cursor += int(plan.input_layouts[i].row_len);
-        }
-        if (in_direct[i]) {
-            in_base_canon[i] = cursor;
-            f.fused.inputs.push_back({int(i), cursor, 1});
-            cursor += int(plan.input_layouts[i].row_len);
-        }
-    }
-    if (f.fused.inputs.size() > size_t(uop::MAX_INPUTS)) return false;
-    for (size_t i = 0; i < plan.node_buffers.size(); ++i) {
-        node_base[i] = cursor;
-        cursor += int(plan.node_buffers[i].row_len);
-    }
-    const int out_base = cursor;
-    cursor += int(plan.out_layout.row_len);
-    if (plan.out_layout.row_len == 0) return false;
-    const int zero_slot = cursor++;  // one element per item holding +0.0: target of unused MAC slots
-    int slab = cursor | 1;  // odd: 64 lanes at one slab offset hit 64 different banks
-    // the LDS interpreter kernel needs the slabs of 64 items in 48 KiB; the hiprtc-specialised kernel keeps the slab
-    // in registers and only needs it to be small enough for that -- plans that fit only the latter are fused
-    // "JIT only" (the runtime falls back to an unfused plan if the compilation fails)
-    // (plans with exp / log steps have no interpreter micro-ops: the specialised kernel or nothing)
-    // (round 3: 144 KiB instead of 48 -- one 512-thread workgroup per CU -- so that programs whose slab is beyond the registers of
-    //  the specialised kernel but whose lists are short still run as ONE launch: the projected sandwich (R X ~R).g(1) at n = 7, 8
-    //  has two lists of n 2^(n-1) entries over a slab of 2^n + 2 n elements; as two list launches it ran 8 active lanes per item)
-    //  -- for plans of SEVERAL steps only: a single big list is better off on k_product_ell (twice the terms per second)
-    const size_t interp_budget = plan.steps.size() >= 2 ? kInterpLdsBytes : size_t(48 * 1024);
-    const bool interp_ok = !(slab > 4095 || size_t(slab) * elem > 32767 || size_t(slab) * elem * 64 > interp_budget) && !plan.has_explog;
-    // One item per thread, the slab in registers: up to 160 (f64) / 200 (f32) elements always; up to 256 / 320 ON TRIAL -- the
-    // compiler keeps only the LIVE values in registers, the projection (v & bv) & bv.vinv() at n = 12 (slab 171) compiles to 222
-    // registers and runs at 0.75 of the HBM roof against 0.44 with its slabs in LDS, the versor inverse at n = 8 (slab 259: the
-    // whole row is live until it is scaled) to 310 with one wave per SIMD and 0.46 against 0.67.  The runtime measures the compiled
-    // kernel's occupancy and rebuilds the plan with small_reg_slab when the trial fails.
-    const int jit_slab_small = plan.dtype == GAAST_F32 ? 200 : 160;
-    const int jit_slab_limit = small_reg_slab ? jit_slab_small : (plan.dtype == GAAST_F32 ? 320 : 256);
-    const bool jit_allowed = !(plan.flags & GAAST_FLAG_NO_JIT) && slab <= jit_slab_limit;
-    if (!interp_ok && !jit_allowed) return false;
-    if (slab_probe) {
-        *slab_probe = slab;
-        return false;
-    }
-    auto base_of = [&](BufRef r, int canon = 0) {
-        return r.kind == BufKind::NODE    ? node_base[size_t(r.idx)]
-               : r.kind == BufKind::INPUT ? (canon ? in_base_canon : in_base)[size_t(r.idx)]
-                                          : out_base;
-    };
-    auto layout_of = [&](BufRef r) -> const Layout& {
-        return r.kind == BufKind::NODE ? plan.node_buffers[size_t(r.idx)]
-               : r.kind == BufKind::INPUT ? plan.input_layouts[size_t(r.idx)] : plan.out_layout;
-    };
-    // One phase per step; inside a phase the independent result rows (and element-wise ops) are
-    // dealt to the workgroup's waves, least-loaded first.  Any split is exact: rows of one
-    // Product never read what another row of the same Product writes.
-    constexpr int G = uop::GROUPS;
-    constexpr uint32_t LW = 32;                   // words per line
-    std::vector<uint32_t>& prog = f.fused.prog;        // 32-word lines, see kernels.hip.hpp
-    std::vector<uint32_t>& phase_tab = f.fused.phase_tab;   // per (phase, wave): first line, line count
-    std::vector<double>& general = f.fused.general;
-    uint64_t entries = 0;
-    const uint32_t esz = uint32_t(elem);
-    auto mop = [](uint32_t code, uint32_t lo, uint32_t mid = 0) { return (code << 28) | (mid << 12) | lo; };
-    for (const Step& s : plan.steps) {
-        std::vector<std::vector<uint32_t>> glines(G);  // lines of each wave, this phase
-        std::vector<uint64_t> load(G, 0);
-        auto least = [&]() {
-            int g = 0;
-            for (int i = 1; i < G; ++i)
-                if (load[size_t(i)] < load[size_t(g)]) g = i;
-            return g;
-        };
-        auto push_misc = [&](const std::vector<uint32_t>& ops) {  // chunks of <= 30 ops, dealt round
-            const size_t per = std::max<size_t>(1, std::min<size_t>(30, (ops.size() + G - 1) / G));
-            for (size_t i = 0; i < ops.size(); i += per) {
-                const size_t cnt = std::min(per, ops.size() - i);
-                const int g = least();
-                std::vector<uint32_t>& out = glines[size_t(g)];
-                out.push_back((uint32_t(uop::LINE_MISC) << 28) | (uint32_t(cnt) << 15));
-                out.push_back(0u);
-                for (size_t k = 0; k < 30; ++k) out.push_back(k < cnt ? ops[i + k] : 0u);
-                load[size_t(g)] += cnt;
-            }
-        };
-        const uint32_t rb = uint32_t(base_of(s.res));
-        std::vector<uint32_t> misc;
-        switch (s.kind) {
-        case Step::ZERO: {
-            const uint32_t len = uint32_t(layout_of(s.res).row_len);
-            for (uint32_t o = 0; o < len; o += 8) misc.push_back(mop(uop::ZERO, rb + o, std::min<uint32_t>(8, len - o)));
-            push_misc(misc);
-            break;
-        }
-        case Step::AXPY:
-            for (uint32_t m : s.axpy_map) misc.push_back(mop(s.beta ? uop::ADD : uop::COPY, rb + (m & 0xffffu), uint32_t(base_of(s.a)) + (m >> 16)));   // (COPY: the zero fill folded in)
-            push_misc(misc);
-            break;
-        case Step::FLIP:
-            for (uint32_t o : s.flip_offsets) misc.push_back(mop(uop::NEG, rb + o));
-            push_misc(misc);
-            break;
-        case Step::SUNARY:
-            misc.push_back(mop(s.sunary_op == 0 ? uop::INV : uop::SQRT, rb + uint32_t(s.sunary_off)));
-            push_misc(misc);
-            break;
-        case Step::PRODUCT_CSR: {
-            const uint32_t lb = uint32_t(base_of(s.a, s.canon_a)), rrb = uint32_t(base_of(s.b, s.canon_b));
-            for (size_t row = 0; row + 1 < s.list.row_start.size(); ++row) {
-                const uint32_t dst = rb + s.list.row_out[row];
-                const uint32_t e0 = s.list.row_start[row], e1 = s.list.row_start[row + 1];
-                const int g = least();
-                std::vector<uint32_t>& out = glines[size_t(g)];
-                load[size_t(g)] += (e1 - e0) + 2;
-                bool row_general = false;
-                for (uint32_t e = e0; e < e1; ++e) row_general |= (s.list.coeff[e] != 1.0 && s.list.coeff[e] != -1.0);
-                // split long rows evenly over their lines (16 entries -> 8 + 8, not 10 + 6)
-                const uint32_t n_l = e1 > e0 ? (e1 - e0 + 9) / 10 : 1;
-                const uint32_t per = e1 > e0 ? (e1 - e0 + n_l - 1) / n_l : 0;
-                uint32_t e = e0;
-                do {  // a row with no entries still stores its (fresh) 0.0
-                    const uint32_t cnt = std::min<uint32_t>(per, e1 - e);
-                    uint32_t hdr = dst | (cnt << 15);
-                    if (e == e0) hdr |= (1u << 12) | (s.beta ? 0u : (1u << 13));
-                    if (e + cnt == e1) hdr |= 1u << 14;
-                    hdr |= uint32_t(row_general ? uop::LINE_MACS_GEN : uop::LINE_MACS) << 28;
-                    const size_t line0 = out.size();
-                    out.resize(line0 + LW, 0u);
-                    out[line0] = hdr;
-                    for (uint32_t k = 0; k < cnt; ++k) {
-                        const double c = s.list.coeff[e + k];
-                        const uint32_t lo = lb + (s.list.entries[e + k] & 0xffffu), ro = rrb + (s.list.entries[e + k] >> 16);
-                        if (!row_general) {
-                            out[line0 + 2 + 3 * k] = lo * esz;
-                            out[line0 + 3 + 3 * k] = ro * esz;
-                            out[line0 + 4 + 3 * k] = c == -1.0 ? 0x80000000u : 0u;
-                        } else {
-                            uint32_t ci;
-                            if (c == 1.0) {
-                                ci = 0;
-                            } else if (c == -1.0) {
-                                ci = 1;
-                            } else {
-                                size_t gi = 0;
-                                for (; gi < general.size(); ++gi)
-                                    if (std::memcmp(&general[gi], &c, sizeof(double)) == 0) break;
-                                if (gi == general.size()) {
-                                    if (general.size() == size_t(uop::MAX_GENERAL_COEFFS)) return false;
-                                    general.push_back(c);
-                                }
-                                ci = uint32_t(gi) + 2;
-                            }
-                            out[line0 + 2 + 3 * k] = lo | (ro << 12);
-                            out[line0 + 3 + 3 * k] = ci;
-                        }
-                        ++entries;
-                    }
-                    e += cnt;
-                } while (e < e1);
-            }
-            break;
-        }
-        case Step::EXPLOG: break;   // specialised kernel only (interp_ok is false)
-        default: return false;
-        }
-        for (int g = 0; g < G; ++g) {
-            phase_tab.push_back(uint32_t(prog.size() / LW));
-            phase_tab.push_back(uint32_t(glines[size_t(g)].size() / LW));
-            prog.insert(prog.end(), glines[size_t(g)].begin(), glines[size_t(g)].end());
-        }
-    }
-    if (prog.size() > (1u << 20)) return false;
-    if (prog.empty()) prog.assign(LW, uint32_t(uop::LINE_NOP) << 28);
-    // ---- the same plan as straight-line HIP source, specialised at program_create through
-    // hiprtc (the reference's README lists code generation from the specialized AST as roadmap).
-    // lane <-> item, every slab element is a local scalar (a register), offsets and signs are
-    // constants, the statements are the reference's in the reference's order; the runtime
-    // compiles it with -ffp-contract=off so that the roundings stay those of eval.rs:82.
-    if (!interp_ok && entries > 8192) return false;
-    f.fused.jit_only = interp_ok ? 0 : 1;
-    if (jit_allowed && entries <= 8192) {
-        std::string src;
-        char buf[256];
-        const char* ty = plan.dtype == GAAST_F32 ? "float" : "double";
-        auto lit = [&](double c) {
-            std::snprintf(buf, sizeof(buf), plan.dtype == GAAST_F32 ? "%af" : "%a", plan.dtype == GAAST_F32 ? double(float(c)) : c);
-            return std::string(buf);
-        };
-        auto var = [&](uint32_t i) { return "v" + std::to_string(i); };
-        // Row I/O.  lane <-> item, but a lane reading ITS row with 16-byte accesses makes every wave instruction touch 64
-        // different 128-byte lines: the CU's L1 then spends a cycle pair per line for 16 useful bytes and bounds the kernel
-        // (config 5: 56 % of HBM peak with the vector units 30 % busy).  So a wave (= a workgroup of 64 lanes) moves the
-        // rows of its 64 items as ONE contiguous span with fully coalesced 16-byte accesses and transposes through LDS:
-        // rows padded to an odd number of 16-byte units, so that both the span-ordered and the row-per-lane accesses are
-        // conflict-free.  Used per operand when its rows are contiguous (stride == length) and 16-byte aligned and the wave
-        // is full; otherwise (shared rows, strided or unaligned wrapped memory, the last partial wave) the lane reads its row
-        // directly.  GAAST_FLAG_NO_COALESCE: always the direct form (A/B measurements).
-        const size_t esz = plan.dtype == GAAST_F32 ? 4 : 8;
-        const int epc = int(16 / esz);                                   // elements per 16-byte chunk
-        auto padded_len = [&](int len) {                                 // row length in LDS, elements
-            size_t padb = (size_t(len) * esz + 15) / 16 * 16;
-            if ((padb / 16) % 2 == 0) padb += 16;
-            return int(padb / esz);
-        };
-        // which operands go through LDS: largest rows first, within a budget that keeps 16 waves per CU resident
-        // (160 KiB / 16 = 10 KiB per wave); the result rows reuse the operands' space.  Operands left out (and rows
-        // too long for the budget) are read by their lanes directly.
-        const size_t lds_budget = (plan.flags & GAAST_FLAG_DEBUG_LDS_12K) ? 12 * 1024 + 256 : 10 * 1024;
-        std::vector<int> lds_off(f.fused.inputs.size(), -1);
-        size_t lds_in = 0;
-        {
-            std::vector<size_t> order(f.fused.inputs.size());
-            for (size_t i = 0; i < order.size(); ++i) order[i] = i;
-            std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) {
-                return plan.input_layouts[size_t(f.fused.inputs[x].slot)].row_len > plan.input_layouts[size_t(f.fused.inputs[y].slot)].row_len;
-            });
-            for (size_t i : order) {
-                const size_t need = size_t(64) * size_t(padded_len(int(plan.input_layouts[size_t(f.fused.inputs[i].slot)].row_len))) * esz;
-                if (lds_in + need > lds_budget) continue;
-                lds_off[i] = int(lds_in);
-                lds_in += need;
-            }
-        }
-        const int out_len = int(plan.out_layout.row_len);
-        const size_t lds_out_need = size_t(64) * size_t(padded_len(out_len)) * esz;
-        const bool out_via_lds = lds_out_need <= lds_budget;
-        // Rows too long for the budget go through ONE shared 64 x 144-byte buffer, 128 bytes (a cache line) of every
-        // row at a time: 8 lanes move one row's line, a wave instruction 8 whole lines (so the rows need not even be
-        // contiguous, only 16-byte aligned with a 16-byte multiple stride).  Lines of a row are consumed one after the
-        // other: a few more barriers (single-wave workgroups: cheap), the same coalescing.
-        const int line_plen = int(144 / esz);   // padded line in elements: 9 x 16 bytes, odd -> conflict-free both ways
-        // (programs with big slabs are register-bound: the transposition's temporaries would spill -- measured on full R^6
-        // f32 products, 193 elements: 1.93 -> 1.30 TB/s -- so they keep the row-per-lane form)
-        auto line_ok = [&](int len) { return slab <= 128 && size_t(len) * esz >= 128 && (size_t(len) * esz) % 16 == 0; };
-        std::vector<char> by_line(f.fused.inputs.size(), 0);
-        bool any_line = false;
-        for (size_t i = 0; i < f.fused.inputs.size(); ++i)
-            if (lds_off[i] < 0 && line_ok(int(plan.input_layouts[size_t(f.fused.inputs[i].slot)].row_len))) by_line[i] = 1, any_line = true;
-        const bool out_by_line = !out_via_lds && line_ok(out_len);
-        any_line = any_line || out_by_line;
-        const size_t line_bytes = any_line ? size_t(64) * 144 : 0;
-        if (any_line && lds_in + line_bytes > 12 * 1024 + 1024) {   // keep >= 12 waves per CU resident: drop the line path
-            std::fill(by_line.begin(), by_line.end(), 0);
-            any_line = false;
-        }
-        const size_t line_off = lds_in;                      // the shared line buffer sits after the span regions
-        const bool out_line = any_line && out_by_line;
-        const size_t lds_total = std::max(lds_in + (any_line ? line_bytes : 0), out_via_lds ? lds_out_need : size_t(0));
-        const bool coalesce = !(plan.flags & GAAST_FLAG_NO_COALESCE) && lds_total > 0;
-        const int threads = coalesce ? 64 : 256;
-        src += std::string("typedef ") + ty + " T;\n";
-        src += std::string("typedef ") + ty + " VT __attribute__((ext_vector_type(" + std::to_string(epc) + ")));\n";
-        src += "extern \"C\" __global__ __launch_bounds__(" + std::to_string(threads) + ") void gaast_jit(";
-        for (size_t i = 0; i < f.fused.inputs.size(); ++i)
-            src += "const T* __restrict__ in" + std::to_string(i) + ", long long s" + std::to_string(i) + ", ";
-        src += std::string("T* __restrict__ out, long long so, long long batch") + (plan.has_explog ? ", unsigned long long* dom" : "") + ") {\n";
-        if (coalesce) {
-            src += "  __shared__ __attribute__((aligned(16))) unsigned char lds[" + std::to_string(lds_total) + "];\n";
-            src += "  const int lane = threadIdx.x;\n  const long long item0 = blockIdx.x * 64LL;\n";
-            src += "  const long long item = item0 + lane;\n  const bool live = item < batch;\n  const bool full = item0 + 64 <= batch;\n";
-        } else {
-            src += "  const long long item = blockIdx.x * 256LL + threadIdx.x;\n  if (item >= batch) return;\n";
-        }
-        for (int i = 0; i < slab; ++i) src += "  T " + var(uint32_t(i)) + " = 0;\n";
-        for (size_t i = 0; i < f.fused.inputs.size(); ++i) {
-            const Step::FusedInput& fi = f.fused.inputs[i];
-            const int len = int(plan.input_layouts[size_t(fi.slot)].row_len);
-            const std::string I = std::to_string(i);
-            auto assign = [&](const std::string& from_prefix, const std::string& indent) {
-                for (int c = 0; c < len; ++c)
-                    src += indent + var(uint32_t(fi.base + c)) + (fi.canon ? " = T(0) + " : " = ") + from_prefix + "[" + std::to_string(c) + "];\n";
-            };
-            if (!coalesce) {
-                src += "  { const T* r = in" + I + " + item * s" + I + ";\n";
-                assign("r", "    ");
-                src += "  }\n";
-                continue;
-            }
-            if (coalesce && by_line[i]) {   // one cache line of every row at a time through the shared buffer
-                const int nblk = int((size_t(len) * esz + 127) / 128);
-                src += "  if (full && ((s" + I + " * " + std::to_string(esz) + ") & 15) == 0 && (((unsigned long long)in" + I + ") & 15ull) == 0) {\n";
-                src += "    T* buf = (T*)(lds + " + std::to_string(line_off) + ");\n";
-                for (int b = 0; b < nblk; ++b) {
-                    const int blk_bytes = int(std::min<size_t>(128, size_t(len) * esz - size_t(128) * b));
-                    const int cpl = blk_bytes / 16, blk_elems = int(blk_bytes / esz), e0 = int(size_t(128) * b / esz);
-                    src += "    { const T* base = in" + I + " + item0 * s" + I + " + " + std::to_string(e0) + " + (lane & 7) * " + std::to_string(epc) + ";\n";
-                    for (int j = 0; j < 8; ++j) src += "      VT c" + std::to_string(j) + ";\n";
-                    src += std::string("      if ((lane & 7) < ") + std::to_string(cpl) + ") {\n";
-                    for (int j = 0; j < 8; ++j)
-#if GAAST_JIT_NT & 2
-                        src += "        c" + std::to_string(j) + " = __builtin_nontemporal_load((const VT*)(base + (long long)(" + std::to_string(8 * j) + " + (lane >> 3)) * s" + I + "));\n";
-#else
-                        src += "        c" + std::to_string(j) + " = *(const VT*)(base + (long long)(" + std::to_string(8 * j) + " + (lane >> 3)) * s" + I + ");\n";
-#endif
-                    for (int j = 0; j < 8; ++j)
-                        src += "        *(VT*)(buf + (" + std::to_string(8 * j) + " + (lane >> 3)) * " + std::to_string(line_plen) + " + (lane & 7) * " + std::to_string(epc) + ") = c" + std::to_string(j) + ";\n";
-                    src += "      }\n      __syncthreads();\n      const T* r = buf + lane * " + std::to_string(line_plen) + ";\n";
-                    for (int e = 0; e < blk_elems; ++e)
-                        src += "      " + var(uint32_t(fi.base + e0 + e)) + (fi.canon ? " = T(0) + r[" : " = r[") + std::to_string(e) + "];\n";
-                    src += "      __syncthreads();\n    }\n";
-                }
-                src += "  } else if (live) {\n    const T* r = in" + I + " + item * s" + I + ";\n";
-                assign("r", "    ");
-                src += "  }\n";
-                continue;
-            }
-            if (lds_off[i] < 0) {   // not staged: the lane reads its own row
-                src += "  if (live) { const T* r = in" + I + " + item * s" + I + ";\n";
-                assign("r", "    ");
-                src += "  }\n";
-                continue;
-            }
-            const int plen = padded_len(len);
-            const int nch = 64 * len / epc;                  // 16-byte chunks of the wave's span (64 * len * esz is a multiple of 256)
-            const int per_lane = (nch + 63) / 64;
-            const bool whole = (size_t(len) * esz) % 16 == 0;   // a chunk never straddles two rows
-            src += "  if (full && s" + I + " == " + std::to_string(len) + " && (((unsigned long long)in" + I + ") & 15ull) == 0) {\n";
-            src += "    const VT* src" + I + " = (const VT*)(in" + I + " + item0 * " + std::to_string(len) + ");\n";
-            src += "    T* img = (T*)(lds + " + std::to_string(lds_off[i]) + ");\n";
-            for (int j = 0; j < per_lane; ++j) src += "    VT c" + std::to_string(j) + ";\n";
-            for (int j = 0; j < per_lane; ++j) {
-                const bool guard = (j + 1) * 64 > nch;
-                src += std::string("    ") + (guard ? "if (lane + " + std::to_string(64 * j) + " < " + std::to_string(nch) + ") " : "") + "c" +
-#if GAAST_JIT_NT & 2
-                       std::to_string(j) + " = __builtin_nontemporal_load(&src" + I + "[lane + " + std::to_string(64 * j) + "]);\n";
-#else
-                       std::to_string(j) + " = src" + I + "[lane + " + std::to_string(64 * j) + "];\n";
-#endif
-            }
-            for (int j = 0; j < per_lane; ++j) {
-                const bool guard = (j + 1) * 64 > nch;
-                src += std::string("    ") + (guard ? "if (lane + " + std::to_string(64 * j) + " < " + std::to_string(nch) + ") " : "") + "{ const int el = (lane + " +
-                       std::to_string(64 * j) + ") * " + std::to_string(epc) + ";\n";
-                if (whole) {
-                    src += "      *(VT*)(img + (el / " + std::to_string(len) + ") * " + std::to_string(plen) + " + el % " + std::to_string(len) + ") = c" + std::to_string(j) + ";\n";
-                } else {
-                    for (int e = 0; e < epc; ++e)
-                        src += "      img[((el + " + std::to_string(e) + ") / " + std::to_string(len) + ") * " + std::to_string(plen) + " + (el + " + std::to_string(e) + ") % " +
-                               std::to_string(len) + "] = c" + std::to_string(j) + "[" + std::to_string(e) + "];\n";
-                }
-                src += "    }\n";
-            }
-            src += "    __syncthreads();\n    const T* r = img + lane * " + std::to_string(plen) + ";\n";
-            assign("r", "    ");
-            src += "  } else if (live) {\n    const T* r = in" + I + " + item * s" + I + ";\n";
-            assign("r", "    ");
-            src += "  }\n";
-        }
-        for (const Step& s : plan.steps) {
-            const uint32_t rb = uint32_t(base_of(s.res));
-            switch (s.kind) {
-            case Step::ZERO:
-                for (int64_t o = 0; o < layout_of(s.res).row_len; ++o) src += "  " + var(rb + uint32_t(o)) + " = T(0);\n";
-                break;
-            case Step::AXPY:
-                for (uint32_t m : s.axpy_map) {
-                    const std::string d = var(rb + (m & 0xffffu));
-                    src += "  " + d + " = " + (s.beta ? d : std::string("T(0)")) + " + " + var(uint32_t(base_of(s.a)) + (m >> 16)) + ";\n";
-                }
-                break;
-            case Step::FLIP:
-                for (uint32_t o : s.flip_offsets) src += "  " + var(rb + o) + " = -" + var(rb + o) + ";\n";
-                break;
-            case Step::SUNARY: {
-                const std::string d = var(rb + uint32_t(s.sunary_off));
-                if (s.sunary_op == 0)
-                    src += "  " + d + " = T(1) / " + d + ";\n";
-                else
-                    src += "  " + d + (plan.dtype == GAAST_F32 ? " = __builtin_sqrtf(" : " = __builtin_sqrt(") + d + ");\n";
-                break;
-            }
-            case Step::EXPLOG: {   // the statements of oracle/gaast_oracle.c: ext_exp_log, in its order
-                const uint32_t ab = uint32_t(base_of(s.a));
-                const bool f32 = plan.dtype == GAAST_F32;
-                auto fn = [&](const char* name) { return std::string(name) + (f32 ? "f" : ""); };
-                auto B = [&](uint32_t i) { return var(ab + uint32_t(s.explog.arg_k) + i); };
-                src += "  { T sq = T(0), nrm = T(0), viol = T(0);\n";
-                for (int i = 0; i < s.explog.m; ++i) {
-                    src += "    sq = sq + " + B(uint32_t(i)) + " * " + B(uint32_t(i)) + " * T(" + lit(s.explog.sq[size_t(i)]) + ");\n";
-                    src += "    nrm = nrm + " + B(uint32_t(i)) + " * " + B(uint32_t(i)) + ";\n";
-                }
-                for (size_t row = 0; row + 1 < s.explog.row_start.size(); ++row) {
-                    src += "    { T acc = T(0);\n";
-                    for (uint32_t e = s.explog.row_start[row]; e < s.explog.row_start[row + 1]; ++e)
-                        src += "      acc = acc + " + B(s.explog.pairs[e] & 0xffffu) + " * " + B(s.explog.pairs[e] >> 16) + " * T(" + lit(s.explog.pair_coeff[e]) + ");\n";
-                    src += "      viol = viol + acc * acc; }\n";
-                }
-                if (s.explog.row_start.size() > 1)
-                    src += std::string("    if (viol > T(") + lit(9.094947017729282e-13) + ") * (nrm * nrm)) atomicAdd(dom, 1ull);\n";
-                src += "    T c0 = T(0), f;\n";
-                if (s.explog.op == 0) {
-                    src += "    if (sq < T(0)) { const T t = " + fn("sqrt") + "(-sq); c0 = " + fn("cos") + "(t); f = " + fn("sin") + "(t) / t; }\n";
-                    src += "    else if (sq > T(0)) { const T t = " + fn("sqrt") + "(sq); c0 = " + fn("cosh") + "(t); f = " + fn("sinh") + "(t) / t; }\n";
-                    src += "    else if (sq == T(0)) { c0 = T(1); f = T(1); }\n    else { c0 = sq; f = sq; }\n";
-                } else {
-                    const std::string a = s.explog.arg_0 >= 0 ? var(ab + uint32_t(s.explog.arg_0)) : std::string("T(0)");
-                    src += "    if (sq < T(0)) { const T mm = " + fn("sqrt") + "(-sq); f = " + fn("atan2") + "(mm, " + a + ") / mm; }\n";
-                    src += "    else if (sq > T(0)) { const T mm = " + fn("sqrt") + "(sq); f = " + fn("atanh") + "(mm / " + a + ") / mm; }\n";
-                    src += "    else if (sq == T(0)) { f = T(1) / " + a + "; }\n    else { f = sq; }\n";
-                }
-                if (s.explog.res_0 >= 0) {
-                    const std::string d = var(rb + uint32_t(s.explog.res_0));
-                    src += "    " + d + " = " + d + " + c0;\n";
-                }
-                if (s.explog.res_k >= 0)
-                    for (int i = 0; i < s.explog.mres; ++i) {
-                        const std::string d = var(rb + uint32_t(s.explog.res_k) + uint32_t(i));
-                        src += "    " + d + " = " + d + " + f * " + B(uint32_t(i)) + ";\n";
-                    }
-                src += "  }\n";
-                break;
-            }
-            case Step::PRODUCT_CSR: {
-                const uint32_t lb = uint32_t(base_of(s.a, s.canon_a)), rrb = uint32_t(base_of(s.b, s.canon_b));
-                for (size_t row = 0; row + 1 < s.list.row_start.size(); ++row) {
-                    const std::string d = var(rb + s.list.row_out[row]);
-                    src += "  { T acc = " + (s.beta ? d : std::string("T(0)")) + ";\n";
-                    for (uint32_t e = s.list.row_start[row]; e < s.list.row_start[row + 1]; ++e) {
-                        const std::string prod = "(" + var(lb + (s.list.entries[e] & 0xffffu)) + " * " + var(rrb + (s.list.entries[e] >> 16)) + ")";
-                        const double c = s.list.coeff[e];
-                        if (c == 1.0)
-                            src += "    acc = acc + " + prod + ";\n";
-                        else if (c == -1.0)
-                            src += "    acc = acc - " + prod + ";\n";
-                        else
-                            src += "    acc = acc + " + prod + " * T(" + lit(c) + ");\n";
-                    }
-                    src += "    " + d + " = acc; }\n";
-                }
-                break;
-            }
-            default: break;
-            }
-        }
-        if (!coalesce) {
-            src += "  T* o = out + item * so;\n";
-            for (int64_t c = 0; c < plan.out_layout.row_len; ++c)
-                src += "  o[" + std::to_string(c) + "] = " + var(uint32_t(out_base + c)) + ";\n";
-        } else {
-            const int plen = padded_len(out_len);
-            const int nch = 64 * out_len / epc;
-            const int per_lane = (nch + 63) / 64;
-            const bool whole = (size_t(out_len) * esz) % 16 == 0;
-            if (out_line) {
-                const int nblk = int((size_t(out_len) * esz + 127) / 128);
-                src += "  if (full && ((so * " + std::to_string(esz) + ") & 15) == 0 && (((unsigned long long)out) & 15ull) == 0) {\n";
-                src += "    T* buf = (T*)(lds + " + std::to_string(line_off) + ");\n";
-                for (int b = 0; b < nblk; ++b) {
-                    const int blk_bytes = int(std::min<size_t>(128, size_t(out_len) * esz - size_t(128) * b));
-                    const int cpl = blk_bytes / 16, blk_elems = int(blk_bytes / esz), e0 = int(size_t(128) * b / esz);
-                    src += "    { __syncthreads();\n      T* r = buf + lane * " + std::to_string(line_plen) + ";\n";
-                    for (int e = 0; e < blk_elems; ++e) src += "      r[" + std::to_string(e) + "] = " + var(uint32_t(out_base + e0 + e)) + ";\n";
-                    src += "      __syncthreads();\n      T* base = out + item0 * so + " + std::to_string(e0) + " + (lane & 7) * " + std::to_string(epc) + ";\n";
-                    src += std::string("      if ((lane & 7) < ") + std::to_string(cpl) + ") {\n";
-                    for (int j = 0; j < 8; ++j)
-#if GAAST_JIT_NT & 1
-                        src += "        __builtin_nontemporal_store(*(const VT*)(buf + (" + std::to_string(8 * j) + " + (lane >> 3)) * " + std::to_string(line_plen) + " + (lane & 7) * " +
-                               std::to_string(epc) + "), (VT*)(base + (long long)(" + std::to_string(8 * j) + " + (lane >> 3)) * so));\n";
-#else
-                        src += "        *(VT*)(base + (long long)(" + std::to_string(8 * j) + " + (lane >> 3)) * so) = *(const VT*)(buf + (" + std::to_string(8 * j) +
-                               " + (lane >> 3)) * " + std::to_string(line_plen) + " + (lane & 7) * " + std::to_string(epc) + ");\n";
-#endif
-                    src += "      }\n    }\n";
-                }
-                src += "  } else\n";
-            }
-            src += std::string("  if (") + (out_via_lds ? "full" : "false") + " && so == " + std::to_string(out_len) + " && (((unsigned long long)out) & 15ull) == 0) {\n";
-            src += "    __syncthreads();\n    T* img = (T*)lds;\n    { T* r = img + lane * " + std::to_string(plen) + ";\n";
-            for (int c = 0; c < out_len; ++c) src += "      r[" + std::to_string(c) + "] = " + var(uint32_t(out_base + c)) + ";\n";
-            src += "    }\n    __syncthreads();\n    VT* dst = (VT*)(out + item0 * " + std::to_string(out_len) + ");\n";
-            for (int j = 0; j < per_lane; ++j) {
-                const bool guard = (j + 1) * 64 > nch;
-                src += std::string("    ") + (guard ? "if (lane + " + std::to_string(64 * j) + " < " + std::to_string(nch) + ") " : "") + "{ const int el = (lane + " +
-                       std::to_string(64 * j) + ") * " + std::to_string(epc) + ";\n      VT c;\n";
-                if (whole) {
-                    src += "      c = *(const VT*)(img + (el / " + std::to_string(out_len) + ") * " + std::to_string(plen) + " + el % " + std::to_string(out_len) + ");\n";
-                } else {
-                    for (int e = 0; e < epc; ++e)
-                        src += "      c[" + std::to_string(e) + "] = img[((el + " + std::to_string(e) + ") / " + std::to_string(out_len) + ") * " + std::to_string(plen) +
-                               " + (el + " + std::to_string(e) + ") % " + std::to_string(out_len) + "];\n";
-                }
-#if GAAST_JIT_NT & 1
-                src += "      __builtin_nontemporal_store(c, &dst[lane + " + std::to_string(64 * j) + "]);\n    }\n";
-#else
-                src += "      dst[lane + " + std::to_string(64 * j) + "] = c;\n    }\n";
-#endif
-            }
-            src += "  } else if (live) {\n    T* o = out + item * so;\n";
-            for (int64_t c = 0; c < plan.out_layout.row_len; ++c)
-                src += "    o[" + std::to_string(c) + "] = " + var(uint32_t(out_base + c)) + ";\n";
-            src += "  }\n";
-        }
-        src += "}\n";
-        f.fused.jit_threads = threads;
-        f.fused.jit_source = std::move(src);
-        f.fused.jit_reg_trial = slab > jit_slab_small;
-    } else if (!(plan.flags & GAAST_FLAG_NO_JIT) && interp_ok && !plan.has_explog && entries <= 2048 &&
-               size_t(slab | 1) * elem * 64 + 64 <= kLdsBytes) {
-        // ---- MEDIUM programs (round 4): the slab is beyond the registers of the specialised kernel above (160 / 200 elements) but the
-        // program is short -- the versor inverse a.rev() * a.norm_sq().sinv() at n = 8 (slab 259, 256 comp-muls), the projection KAT at
-        // n = 12 (slab 171) -- and used to run on the LDS interpreter (wave-uniform micro-op decode: 0.16 / 0.10 of the HBM roof).  The
-        // same plan as straight-line code over slabs that STAY IN LDS: a workgroup of eight waves owns the slabs of 64 items (item i at
-        // i * stride elements, stride odd: the lanes of a wave touch 64 different banks at any slab offset), lane <-> item, and the
-        // independent rows of every arm are dealt to the waves, least-loaded first -- exactly the interpreter's schedule, with the
-        // decode done by hiprtc: offsets are immediates of the LDS instructions, signs are operators.  Same statements, same order.
-        std::string src;
-        char buf[256];
-        const char* ty = plan.dtype == GAAST_F32 ? "float" : "double";
-        auto lit = [&](double c) {
-            std::snprintf(buf, sizeof(buf), plan.dtype == GAAST_F32 ? "%af" : "%a", plan.dtype == GAAST_F32 ? double(float(c)) : c);
-            return std::string(buf);
-        };
-        const int stride = slab | 1;
-        constexpr int W = 8;   // waves per workgroup
-        auto at = [&](uint32_t i) { return "my[" + std::to_string(i) + "]"; };
-        src += std::string("typedef ") + ty + " T;\n";
-        src += "extern \"C\" __global__ __launch_bounds__(512) void gaast_jit(";
-        for (size_t i = 0; i < f.fused.inputs.size(); ++i)
-            src += "const T* __restrict__ in" + std::to_string(i) + ", long long s" + std::to_string(i) + ", ";
-        src += "T* __restrict__ out, long long so, long long batch) {\n";
-        src += "  __shared__ T slab[" + std::to_string(64 * stride) + "];\n";
-        src += "  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;\n";
-        src += "  T* const my = slab + lane * " + std::to_string(stride) + ";\n";
-        // inputs: element e = item * len + c of the flattened range.  Contiguous, 16-byte aligned rows of a full group of 64 items are
-        // moved as 16-byte pieces through registers, ALL of them in flight at once, and -- the workgroups are persistent -- the NEXT
-        // group's pieces are requested before this group is evaluated (a group is 64 KiB at slab 259: the HBM latency hides under
-        // the arithmetic); anything else -- shared rows, strided wrapped memory, the last partial group -- takes a plain loop
-        const int epc = int(16 / elem);
-        src += std::string("  typedef T VT __attribute__((ext_vector_type(") + std::to_string(epc) + ")));\n";
-        std::string fast_cond = "true";
-        int total_chunks_per_thread = 0;
-        for (size_t i = 0; i < f.fused.inputs.size(); ++i) {
-            const int len = int(plan.input_layouts[size_t(f.fused.inputs[i].slot)].row_len);
-            const std::string I = std::to_string(i);
-            fast_cond += " && s" + I + " == " + std::to_string(len) + " && (((unsigned long long)in" + I + ") & 15ull) == 0";
-            if ((64 * len) % epc) fast_cond += " && false";
-            total_chunks_per_thread += (64 * len / epc + 511) / 512;
-        }
-        if (total_chunks_per_thread > 24) fast_cond = "false";
-        src += "  const bool fast = " + fast_cond + ";\n";
-        src += "  const long long groups = (batch + 63) / 64;\n";
-        for (size_t i = 0; i < f.fused.inputs.size(); ++i) {
-            const int len = int(plan.input_layouts[size_t(f.fused.inputs[i].slot)].row_len);
-            const int nch = 64 * len / epc, cpt = std::max(1, (nch + 511) / 512);
-            src += "  VT r" + std::to_string(i) + "[" + std::to_string(cpt) + "];\n";
-        }
-        src += "  auto issue = [&](long long item0) {\n";
-        for (size_t i = 0; i < f.fused.inputs.size(); ++i) {
-            const int len = int(plan.input_layouts[size_t(f.fused.inputs[i].slot)].row_len);
-            const int nch = 64 * len / epc, cpt = (nch + 511) / 512;
-            const std::string I = std::to_string(i);
-            src += "    { const VT* src = (const VT*)(in" + I + " + item0 * " + std::to_string(len) + ");\n";
-            for (int k = 0; k < cpt; ++k)
-                src += "      if (tid + " + std::to_string(512 * k) + " < " + std::to_string(nch) + ") r" + I + "[" + std::to_string(k) +
-                       "] = __builtin_nontemporal_load(src + tid + " + std::to_string(512 * k) + ");\n";
-            src += "    }\n";
-        }
-        src += "  };\n";
-        src += "  auto commit = [&]() {\n";
-        for (size_t i = 0; i < f.fused.inputs.size(); ++i) {
-            const Step::FusedInput& fi = f.fused.inputs[i];
-            const int len = int(plan.input_layouts[size_t(fi.slot)].row_len);
-            const int nch = 64 * len / epc, cpt = (nch + 511) / 512;
-            const std::string I = std::to_string(i), L = std::to_string(len);
-            for (int k = 0; k < cpt; ++k) {
-                src += "    if (tid + " + std::to_string(512 * k) + " < " + std::to_string(nch) + ") {\n";
-                for (int j = 0; j < epc; ++j)
-                    src += "      { const int e = (tid + " + std::to_string(512 * k) + ") * " + std::to_string(epc) + " + " + std::to_string(j) + ", i2 = e / " + L + ", c = e - i2 * " + L +
-                           "; const T v = r" + I + "[" + std::to_string(k) + "][" + std::to_string(j) + "]; slab[i2 * " + std::to_string(stride) + " + " + std::to_string(fi.base) +
-                           " + c] = " + (fi.canon ? "T(0) + v" : "v") + "; }\n";
-                src += "    }\n";
-            }
-        }
-        src += "  };\n";
-        src += "  auto stage = [&](long long item0, int nitems) {\n";
-        for (size_t i = 0; i < f.fused.inputs.size(); ++i) {
-            const Step::FusedInput& fi = f.fused.inputs[i];
-            const int len = int(plan.input_layouts[size_t(fi.slot)].row_len);
-            const std::string I = std::to_string(i), L = std::to_string(len);
-            src += "#pragma unroll 4\n    for (int e = tid; e < " + std::to_string(64 * len) + "; e += 512) { const int i2 = e / " + L + ", c = e - i2 * " + L +
-                   "; T v = i2 < nitems ? in" + I + "[(item0 + i2) * s" + I + " + c] : T(0); slab[i2 * " + std::to_string(stride) + " + " +
-                   std::to_string(fi.base) + " + c] = " + (fi.canon ? "T(0) + v" : "v") + "; }\n";
-        }
-        src += "  };\n";
-        src += "  long long g = blockIdx.x;\n  if (g >= groups) return;\n";
-        src += "  { const long long item0 = g * 64; const int nitems = int(batch - item0 < 64 ? batch - item0 : 64);\n";
-        src += "    if (fast && nitems == 64) { issue(item0); commit(); } else stage(item0, nitems); }\n";
-        src += "  for (;;) {\n";
-        src += "  const long long item0 = g * 64;\n";
-        src += "  const int nitems = int(batch - item0 < 64 ? batch - item0 : 64);\n";
-        src += "  const long long gn = g + gridDim.x;\n  const bool more = gn < groups;\n";
-        src += "  const int nnext = more ? int(batch - gn * 64 < 64 ? batch - gn * 64 : 64) : 0;\n";
-        src += "  const bool pre_next = fast && more && nnext == 64;\n";
-        src += "  __syncthreads();\n";
-        src += "  if (pre_next) issue(gn * 64);\n";
-        for (const Step& s : plan.steps) {
-            const uint32_t rb = uint32_t(base_of(s.res));
-            // the independent pieces of this arm, each a (cost, statements) pair, dealt to the waves least-loaded first
-            std::vector<std::pair<uint64_t, std::string>> pieces;
-            auto elementwise = [&](const std::vector<std::string>& stmts) {   // chunks of up to 16 statements
-                for (size_t i = 0; i < stmts.size(); i += 16) {
-                    std::string blk;
-                    for (size_t k = i; k < std::min(stmts.size(), i + 16); ++k) blk += "      " + stmts[k] + "\n";
-                    pieces.emplace_back(std::min<size_t>(16, stmts.size() - i), blk);
-                }
-            };
-            std::vector<std::string> st;
-            switch (s.kind) {
-            case Step::ZERO:
-                for (int64_t o = 0; o < layout_of(s.res).row_len; ++o) st.push_back(at(rb + uint32_t(o)) + " = T(0);");
-                elementwise(st);
-                break;
-            case Step::AXPY:
-                for (uint32_t m : s.axpy_map) {
-                    const std::string d = at(rb + (m & 0xffffu));
-                    st.push_back(d + " = " + (s.beta ? d : std::string("T(0)")) + " + " + at(uint32_t(base_of(s.a)) + (m >> 16)) + ";");
-                }
-                elementwise(st);
-                break;
-            case Step::FLIP:
-                for (uint32_t o : s.flip_offsets) st.push_back(at(rb + o) + " = -" + at(rb + o) + ";");
-                elementwise(st);
-                break;
-            case Step::SUNARY: {
-                const std::string d = at(rb + uint32_t(s.sunary_off));
-                st.push_back(s.sunary_op == 0 ? d + " = T(1) / " + d + ";"
-                                              : d + (plan.dtype == GAAST_F32 ? " = __builtin_sqrtf(" : " = __builtin_sqrt(") + d + ");");
-                elementwise(st);
-                break;
-            }
-            case Step::PRODUCT_CSR: {
-                const uint32_t lb = uint32_t(base_of(s.a, s.canon_a)), rrb = uint32_t(base_of(s.b, s.canon_b));
-                for (size_t row = 0; row + 1 < s.list.row_start.size(); ++row) {
-                    const std::string d = at(rb + s.list.row_out[row]);
-                    std::string blk = "      { T acc = " + (s.beta ? d : std::string("T(0)")) + ";\n";
-                    for (uint32_t e = s.list.row_start[row]; e < s.list.row_start[row + 1]; ++e) {
-                        const std::string prod = "(" + at(lb + (s.list.entries[e] & 0xffffu)) + " * " + at(rrb + (s.list.entries[e] >> 16)) + ")";
-                        const double c = s.list.coeff[e];
-                        blk += c == 1.0 ? "        acc = acc + " + prod + ";\n"
-                               : c == -1.0 ? "        acc = acc - " + prod + ";\n"
-                                           : "        acc = acc + " + prod + " * T(" + lit(c) + ");\n";
-                    }
-                    blk += "        " + d + " = acc; }\n";
-                    pieces.emplace_back(uint64_t(s.list.row_start[row + 1] - s.list.row_start[row]) + 2, blk);
-                }
-                break;
-            }
-            default: return false;
-            }
-            std::vector<std::string> per_wave(W);
-            std::vector<uint64_t> load(W, 0);
-            for (const auto& pc : pieces) {
-                int g = 0;
-                for (int i = 1; i < W; ++i)
-                    if (load[size_t(i)] < load[size_t(g)]) g = i;
-                per_wave[size_t(g)] += pc.second;
-                load[size_t(g)] += pc.first;
-            }
-            src += "  switch (wave) {\n";
-            for (int g = 0; g < W; ++g)
-                if (!per_wave[size_t(g)].empty()) src += "    case " + std::to_string(g) + ": {\n" + per_wave[size_t(g)] + "    } break;\n";
-            src += "    default: break;\n  }\n  __syncthreads();\n";
-        }
-        const int out_len = int(plan.out_layout.row_len);
-        {
-            const int nch = 64 * out_len / epc, cpt = (nch + 511) / 512;
-            const std::string OL = std::to_string(out_len);
-            src += "  if (nitems == 64 && so == " + OL + " && (((unsigned long long)out) & 15ull) == 0 && " + ((64 * out_len) % epc == 0 && cpt <= 24 ? "true" : "false") + ") {\n";
-            src += "    VT* dst = (VT*)(out + item0 * " + OL + ");\n";
-            for (int k = 0; k < cpt; ++k) {
-                src += "    if (tid + " + std::to_string(512 * k) + " < " + std::to_string(nch) + ") { VT v;\n";
-                for (int j = 0; j < epc; ++j)
-                    src += "      { const int e = (tid + " + std::to_string(512 * k) + ") * " + std::to_string(epc) + " + " + std::to_string(j) + ", i2 = e / " + OL + ", c = e - i2 * " + OL +
-                           "; v[" + std::to_string(j) + "] = slab[i2 * " + std::to_string(stride) + " + " + std::to_string(out_base) + " + c]; }\n";
-                src += "      __builtin_nontemporal_store(v, dst + tid + " + std::to_string(512 * k) + "); }\n";
-            }
-            src += "  } else {\n";
-            src += "#pragma unroll 4\n    for (int e = tid; e < " + std::to_string(64 * out_len) + "; e += 512) { const int i2 = e / " + OL + ", c = e - i2 * " + OL +
-                   "; if (i2 < nitems) out[(item0 + i2) * so + c] = slab[i2 * " + std::to_string(stride) + " + " + std::to_string(out_base) + " + c]; }\n";
-            src += "  }\n";
-        }
-        src += "  if (!more) break;\n  g = gn;\n  __syncthreads();\n";   // the slabs are rewritten for the next group
-        src += "  if (pre_next) commit(); else stage(gn * 64, nnext);\n";
-        src += "  }\n";
-        src += "}\n";
-        f.fused.jit_threads = 512;
-        f.fused.jit_items = 64;
-        f.fused.jit_persistent = int(std::max<size_t>(1, kLdsBytes / (size_t(64) * size_t(stride) * elem)));   // workgroups resident per CU (LDS)
-        f.fused.jit_source = std::move(src);
-    }
-    f.fused.slab = slab;
-    f.fused.zero_slot = zero_slot;
-    f.fused.out_base = out_base;
-    f.n_entries = entries;
-    f.name = "ast_fused[" + std::to_string(plan.steps.size()) + " arms, " + std::to_string(entries) +
-             " comp-muls, slab " + std::to_string(slab) + "]";
-    plan.steps.clear();
-    plan.steps.push_back(std::move(f));
-    plan.node_buffers.clear();  // the cache buffers live in LDS now
-    return true;
-}
-
 }  // namespace
 
 // Rows of one length with +-1 coefficients (dense products of non-degenerate algebras) that were not fused
@@ -1993,724 +1257,6 @@ static void chain_sparse_into_dense(Plan& plan) {
     for (Step& t : plan.steps)
         if (!(t.kind == Step::ZERO && t.res.kind == BufKind::NODE && t.res.idx < 0)) kept.push_back(std::move(t));
     plan.steps = std::move(kept);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The list chain specialised per program (round 4; the generic k_product_ell_chain is the fallback when hiprtc is not
-// available).  What the generic kernel paid for: run-time widths and lengths, a row-per-lane first list whose 64 lanes gather
-// 64 different offsets of ONE item (bank conflicts: 39 % of the LDS cycles), nine vector instructions per term.  Here:
-//   * lane = (row, item) in BOTH lists, the IPB items of the workgroup fastest: the lanes of one LDS access group read the
-//     SAME offset of different items, item stride odd (in elements) -> no bank conflict at IPB = 32;
-//   * an entry is one word of byte offsets from the ITEM's base: list 1 [15:0] left | [31:16] right, the sign folded into
-//     the choice between the smaller operand's image and its NEGATED image (l * (-r) = -(l * r) exactly: eval.rs:82 with
-//     coeff = -1); list 2 [15:0] mid | [30:16] other | [31] sign, applied as fma(l * r, +-1.0, acc): the product is rounded
-//     first, +-1 is exact, the sum is rounded once -- the reference's three roundings;
-//   * entries are read from global memory (the tables are shared by every workgroup and stay in L2 / L1), a quad of entries
-//     per 16-byte load, the next quads in flight while the current ones are used; no run-time width, no padding terms
-//     (acc + (+0.0) would turn a -0.0 accumulator of a beta = 1 list into +0.0);
-//   * reference order and roundings: bit-identical to the two-launch plan and to the oracle.
-// ---------------------------------------------------------------------------------------------------------------------
-// wp == nullptr: a SINGLE list with few long rows (rows2 x IPB lanes instead of rows2; k_product_ell gives a row to a thread): the
-// left operand plays the staged "mid" row (l1 = r1 = 0, mid = its length), the right one is list 2's own operand r2 (alias 0,
-// side 1).  init_off (single list only): acc starts from 0.0 + init[row's offset] -- a covering copy_grades_from of an input
-// folded into the list that accumulates onto it ((a + b * c).g(2): one launch).
-static void make_chain_jit(const Plan& plan, Step& c, const Step* wp, int64_t l1, int64_t r1, int64_t mid, int64_t r2, int alias, int side,
-                           bool covered, const std::vector<uint32_t>* init_off = nullptr) {
-    if (plan.flags & (GAAST_FLAG_NO_JIT | GAAST_FLAG_DEBUG_JIT_FAILS)) return;
-    const bool single = wp == nullptr;
-    static const Step no_list;
-    const Step& w = single ? no_list : *wp;
-    const int64_t esz = plan.dtype == GAAST_F32 ? 4 : 8;
-    const int64_t neg_len = single ? 0 : std::min(l1, r1);
-    const bool neg_is_left = l1 < r1;
-    // layout of an item in LDS (elements): list 2's own operand first (its offsets have 15 bits), then the rest
-    int64_t off_l1 = 0, off_r1 = 0, off_neg, off_mid, off_r2 = -1, cur = 0;
-    auto place = [&](int64_t len) { const int64_t o = cur; cur += len; return o; };
-    if (alias == 0) off_r2 = place(r2);
-    if (alias == 2) { off_r1 = place(r1); off_l1 = place(l1); }
-    else { off_l1 = place(l1); off_r1 = place(r1); }
-    off_neg = place(neg_len);
-    off_mid = place(mid);
-    // tolerance mode: list 2 sign-sorted (below) -- when the item still fits the 16-bit byte offsets with one more element, and the
-    // rows' signs are balanced enough: every (row, slice) pair is padded to the longest plus and the longest minus segment, and a
-    // padding term costs what a real one does (Euclidean sandwiches at n = 8, 10 have all-plus rows: +50 % terms -- they keep the
-    // sign words; R^{6,3} at n = 9: 64 + 64 of 128, no padding; (a + b c).g(2) at n = 8: 136 + 136 for 256)
-    bool sorted = !(plan.flags & GAAST_FLAG_EXACT_ORDER) && (cur + 1) * esz <= 65536;
-    if (sorted) {
-        const int64_t rows2e = int64_t(c.list.row_out.size()), w2e = c.list.ell_width;
-        int64_t sp = 1;   // (the slice count of the tolerance mode, decided again below with the same rule)
-        while (sp < 4 && w2e % (2 * sp) == 0 && w2e / (2 * sp) >= 32 && rows2e * 32 * 2 * sp <= 1024 && rows2e * 2 * sp <= mid) sp *= 2;
-        const int64_t gran = plan.dtype == GAAST_F32 ? 16 : 8;
-        int64_t wp = 0, wm = 0;
-        for (int64_t row = 0; row < rows2e; ++row) {
-            int64_t np = 0, nm = 0;
-            for (int64_t t = 0; t < w2e; ++t) ((c.list.entries[size_t(t * rows2e + row)] & 0x80000000u) ? nm : np) += 1;
-            wp = std::max(wp, (np + sp - 1) / sp);
-            wm = std::max(wm, (nm + sp - 1) / sp);
-        }
-        wp = (wp + gran - 1) / gran * gran;
-        wm = (wm + gran - 1) / gran * gran;
-        sorted = rows2e > 0 && w2e > 0 && (wp + wm) * sp * 100 <= w2e * 107;
-    }
-    const bool has_zero = !(plan.flags & GAAST_FLAG_EXACT_ORDER) && (cur + 1) * esz <= 65536;
-    const int64_t off_zero = has_zero ? place(1) : 0;             // ... padding terms (sorted list 2, list 1 by right index) multiply this element
-    int64_t stride = cur | 1;   // odd: lanes reading one offset of consecutive items touch consecutive banks (bank pairs in f64)
-    const int64_t off_other = alias == 0 ? off_r2 : alias == 1 ? off_l1 : off_r1;
-    const int64_t other_len = alias == 0 ? r2 : alias == 1 ? l1 : r1;
-    if ((off_other + other_len) * esz > 32768 || cur * esz > 65536) return;   // (15-bit / 16-bit byte offsets from the item's base)
-    const int64_t rows1 = int64_t(w.list.row_out.size()), rows2 = int64_t(c.list.row_out.size());
-    const int64_t w1 = w.list.ell_width, w2 = c.list.ell_width;
-    if (rows2 <= 0 || w2 <= 0) return;
-    if (!single && (rows1 <= 0 || w1 <= 0 || w1 > 32)) return;   // (list 1's operands of a row are all in flight at once)
-    // items per workgroup: a power of two up to 32 (the lanes of an LDS access group), as many as the LDS holds
-    int64_t ipb = 32;
-    const int64_t lds_cap = int64_t(kLdsBytes);
-    while (ipb > 1 && ipb * stride * esz > lds_cap - 4096) ipb >>= 1;
-    if (ipb < 2) return;
-    const int64_t w1p = (w1 + 3) & ~int64_t(3), w2p = (w2 + 3) & ~int64_t(3);
-    // The tables ride in LDS when they fit beside the items (broadcast reads; from global memory every lane would get its own
-    // copy of the words through the vector cache: 16 cycles of its return path per 16-byte load and wave).
-    //   list 2: WIDE entries (8 bytes: [15:0] mid | [31:16] other, then the sign bit alone) cost two vector instructions less per
-    //           term than narrow ones ([15:0] mid | [30:16] other | [31] sign) -- taken when they fit;
-    //   list 1: rows padded to quads (16-byte reads) when that fits, else unpadded rows (4-byte reads), else global memory.
-    const int64_t items_bytes = (ipb * stride * esz + 15) / 16 * 16;
-    int64_t used = items_bytes;
-    // TOLERANCE MODE, SIGN-SORTED (round 4): the order inside a row is free, so the terms of every (row, slice) pair are stored
-    // plus-terms first (padded to WPS), then minus-terms (padded to WMS): the sign is the POSITION -- no sign word, no sign
-    // instruction: a term is two SDWA address additions and one fused multiply-add (exact order: 5, narrow entries: 7) -- and the
-    // entries are clean 16 + 16-bit words (half the wide table: at n = 9 list 1's table then fits in LDS too).  Padding terms
-    // multiply the item's zero element by itself.  The slice count is decided first (it shapes the table).
-    int64_t split = 1;
-    if (!(plan.flags & GAAST_FLAG_EXACT_ORDER))
-        while (split < 4 && w2 % (2 * split) == 0 && w2 / (2 * split) >= 32 && rows2 * ipb * 2 * split <= 1024 && rows2 * 2 * split <= mid) split *= 2;
-    int64_t wps = 0, wms = 0;   // plus / minus terms per (row, slice), multiples of 8 (f32: 16): whole register batches
-    std::vector<std::vector<uint32_t>> plus_terms, minus_terms;   // per row: mid offset | other offset << 16 (bytes)
-    if (sorted) {
-        plus_terms.resize(size_t(rows2));
-        minus_terms.resize(size_t(rows2));
-        const int64_t off_other_b = (alias == 0 ? off_r2 : alias == 1 ? off_l1 : off_r1) * esz;
-        for (int64_t row = 0; row < rows2; ++row)
-            for (int64_t t = 0; t < w2; ++t) {
-                const uint32_t e = c.list.entries[size_t(t * rows2 + row)];
-                const int64_t lo = e & 0x7fffu, ro = (e >> 16) & 0x7fffu;
-                const int64_t ma = off_mid * esz + (side == 1 ? lo : ro), oa = off_other_b + (side == 1 ? ro : lo);
-                ((e & 0x80000000u) ? minus_terms : plus_terms)[size_t(row)].push_back(uint32_t(ma) | (uint32_t(oa) << 16));
-            }
-        const int64_t gran = plan.dtype == GAAST_F32 ? 16 : 8;
-        for (int64_t row = 0; row < rows2; ++row) {
-            wps = std::max<int64_t>(wps, (int64_t(plus_terms[size_t(row)].size()) + split - 1) / split);
-            wms = std::max<int64_t>(wms, (int64_t(minus_terms[size_t(row)].size()) + split - 1) / split);
-        }
-        wps = (wps + gran - 1) / gran * gran;
-        wms = (wms + gran - 1) / gran * gran;
-    }
-    const int64_t wss = wps + wms;
-    int ent2_mode;   // 0: narrow, global; 1: narrow, LDS; 2: wide, LDS; sorted: 3: LDS, 4: global
-    if (sorted) {
-        if (used + rows2 * split * wss * 4 <= lds_cap) ent2_mode = 3, used += rows2 * split * wss * 4;
-        else ent2_mode = 4;
-    } else if (used + rows2 * w2p * 8 <= lds_cap) ent2_mode = 2, used += rows2 * w2p * 8;
-    else if (used + rows2 * w2p * 4 <= lds_cap) ent2_mode = 1, used += rows2 * w2p * 4;
-    else ent2_mode = 0;
-    const int64_t ent2_at = items_bytes;
-    int ent1_mode;   // 0: padded rows, global; 1: unpadded rows, LDS; 2: padded rows, LDS
-    const int64_t ent1_at = used;
-    if (used + rows1 * w1p * 4 <= lds_cap) ent1_mode = 2, used += rows1 * w1p * 4;
-    else if (used + rows1 * w1 * 4 <= lds_cap) ent1_mode = 1, used += rows1 * w1 * 4;
-    else ent1_mode = 0;
-    used = (used + 15) / 16 * 16;
-    // TOLERANCE MODE (without GAAST_FLAG_EXACT_ORDER, like the dense products): a long row of list 2 is cut into `split` slices of
-    // consecutive terms, each summed by a lane of its own in the reference's order, the partial sums added in slice order at the end --
-    // the few long chains that leave most of the workgroup idle become split x as many, half as long.  |error| <= 4 eps sum |terms|
-    // per component (the dense path's contract; one extra rounding per slice).  GAAST_FLAG_EXACT_ORDER: split = 1, bit for bit.
-    // one workgroup per CU (the usual case from n = 9 on): 512 threads -- list 1 and the staging have work for all of them, list 2
-    // (few long rows) for rows2 * split * ipb lanes; two or more workgroups per CU: 256 threads each
-    int64_t threads = 2 * used <= lds_cap ? 256 : 512;
-    threads = std::max<int64_t>(threads, std::min<int64_t>(1024, (rows2 * split * ipb + 63) / 64 * 64));
-    // whole multiples of 256: the waves of a workgroup are dealt round-robin to the CU's four SIMDs, and every phase ends at a
-    // barrier -- 9 or 10 waves leave one SIMD with three where the others have two (measured: sand9g1 576 -> 768 threads +6 %,
-    // sand10g1 640 -> 768 +2 %; 1,024 where list 2 does not ask for them: -3 % / -23 %)
-    threads = std::min<int64_t>(1024, (threads + 255) / 256 * 256);
-    const int64_t w1s = ent1_mode == 1 ? w1 : w1p;   // words per row of list 1's table
-    // tables
-    // TOLERANCE MODE, list 1 with its small right operand IN REGISTERS (the sandwich's X: n components, the same for every row a lane
-    // evaluates): the terms of a row are re-ordered by right index -- term j multiplies by x_j, a register --, so a term is ONE LDS
-    // read (the left operand), its sign a bit of the table word; rows without a term for some j multiply the item's zero element.
-    bool xreg = has_zero && !single && !neg_is_left && r1 <= 12 && w1 <= r1 && ent1_mode != 1 && w1s >= ((r1 + 3) & ~int64_t(3));
-    for (int64_t row = 0; row < rows1 && xreg; ++row) {
-        uint32_t seen = 0;
-        for (int64_t t = 0; t < w1 && xreg; ++t) {
-            const int64_t j = int64_t((w.list.entries[size_t(t * rows1 + row)] >> 16) & 0x7fffu) / esz;
-            xreg = j < r1 && !(seen & (1u << j));
-            seen |= 1u << j;
-        }
-    }
-    c.cj.ent1.assign(size_t(rows1 * w1s), 0u);
-    c.cj.pos1.resize(size_t(rows1));
-    if (init_off) c.cj.pos1 = *init_off;   // (a single list has no row positions: the slot carries the offsets of the folded copy)
-    for (int64_t row = 0; row < rows1; ++row) {
-        c.cj.pos1[size_t(row)] = uint32_t((off_mid + int64_t(w.list.row_out[size_t(row)])) * esz);
-        for (int64_t t = 0; t < w1; ++t) {
-            const uint32_t e = w.list.entries[size_t(t * rows1 + row)];
-            const bool neg = (e & 0x80000000u) != 0;
-            const int64_t lo = e & 0x7fffu, ro = (e >> 16) & 0x7fffu;   // bytes, from the operand rows
-            const int64_t la = ((neg && neg_is_left) ? off_neg : off_l1) * esz + lo;
-            const int64_t ra = ((neg && !neg_is_left) ? off_neg : off_r1) * esz + ro;
-            if (!xreg) c.cj.ent1[size_t(row * w1s + t)] = uint32_t(la) | (uint32_t(ra) << 16);
-        }
-        if (xreg) {
-            for (int64_t j = 0; j < w1s; ++j) c.cj.ent1[size_t(row * w1s + j)] = uint32_t(off_zero * esz);   // no term for x_j: 0 * x_j
-            for (int64_t t = 0; t < w1; ++t) {
-                const uint32_t e = w.list.entries[size_t(t * rows1 + row)];
-                const int64_t lo = e & 0x7fffu, j = int64_t((e >> 16) & 0x7fffu) / esz;
-                c.cj.ent1[size_t(row * w1s + j)] = uint32_t(off_l1 * esz + lo) | (e & 0x80000000u);
-            }
-        }
-    }
-    const int64_t wpt2 = ent2_mode == 2 ? 2 : 1;   // words per term
-    c.cj.out2 = c.list.row_out;
-    if (sorted) {
-        const uint32_t pad = uint32_t(off_zero * esz) | (uint32_t(off_zero * esz) << 16);
-        c.cj.ent2.assign(size_t(rows2 * split * wss), pad);
-        for (int64_t row = 0; row < rows2; ++row)
-            for (int which = 0; which < 2; ++which) {
-                const std::vector<uint32_t>& tv = which ? minus_terms[size_t(row)] : plus_terms[size_t(row)];
-                const int64_t per = (int64_t(tv.size()) + split - 1) / split;   // consecutive chunks, one per slice
-                for (int64_t i = 0; i < int64_t(tv.size()); ++i) {
-                    const int64_t sl = per ? i / per : 0, k = per ? i % per : 0;
-                    c.cj.ent2[size_t((row * split + sl) * wss + (which ? wps : 0) + k)] = tv[size_t(i)];
-                }
-            }
-    } else
-        c.cj.ent2.assign(size_t(rows2 * w2p * wpt2), 0u);
-    for (int64_t row = 0; row < rows2 && !sorted; ++row)
-        for (int64_t t = 0; t < w2; ++t) {
-            const uint32_t e = c.list.entries[size_t(t * rows2 + row)];
-            const int64_t lo = e & 0x7fffu, ro = (e >> 16) & 0x7fffu;
-            const int64_t ma = off_mid * esz + (side == 1 ? lo : ro), oa = off_other * esz + (side == 1 ? ro : lo);
-            if (ent2_mode == 2) {
-                c.cj.ent2[size_t((row * w2p + t) * 2)] = uint32_t(ma) | (uint32_t(oa) << 16);
-                c.cj.ent2[size_t((row * w2p + t) * 2 + 1)] = e & 0x80000000u;
-            } else {
-                c.cj.ent2[size_t(row * w2p + t)] = uint32_t(ma) | (uint32_t(oa) << 16) | (e & 0x80000000u);
-            }
-        }
-    // source
-    std::string src;
-    auto def = [&](const char* name, int64_t v) { src += std::string("#define ") + name + " " + std::to_string(v) + "\n"; };
-    src += plan.dtype == GAAST_F32 ? "typedef float T;\n#define F64 0\n" : "typedef double T;\n#define F64 1\n";
-    def("ESZ", esz); def("NT", threads); def("IPB", ipb); def("NSUB", threads / ipb); def("STRIDE_B", stride * esz);
-    def("L1", l1); def("R1", r1); def("R2", alias ? 0 : r2); def("MID", mid); def("NEGLEN", neg_len); def("NEG_IS_LEFT", neg_is_left ? 1 : 0);
-    def("OFF_L1", off_l1 * esz); def("OFF_R1", off_r1 * esz); def("OFF_NEG", off_neg * esz); def("OFF_MID", off_mid * esz);
-    def("OFF_R2", (alias ? 0 : off_r2) * esz); def("HAS_R2", alias ? 0 : 1);
-    def("ROWS1", rows1); def("W1", w1); def("W1S", w1s); def("ROWS2", rows2); def("W2", w2); def("W2P", w2p);
-    def("CANON_L1", w.canon_a); def("CANON_R1", w.canon_b); def("CANON_R2", side == 1 ? c.canon_b : c.canon_a);
-    def("CANON_MID", side == 1 ? c.canon_a : c.canon_b); def("COVERED", covered ? 1 : 0); def("BETA", init_off ? 0 : c.beta);
-    def("SINGLE", single ? 1 : 0); def("INIT_SRC", init_off ? 1 : 0);
-    bool pos1_linear = true;   // row k of list 1 is component k of the mid row (the usual case): no table, no load
-    for (int64_t row = 0; row < rows1; ++row) pos1_linear = pos1_linear && int64_t(w.list.row_out[size_t(row)]) == row;
-    def("POS1_LINEAR", pos1_linear ? 1 : 0);
-    // EXACT: every product rounded, then added (eval.rs:82), rows summed whole -- the reference's bits.  Otherwise (the default,
-    // the dense products' tolerance contract): rows of list 2 in slices, and l * r + acc as one fused multiply-add
-    def("EXACT", (plan.flags & GAAST_FLAG_EXACT_ORDER) ? 1 : 0);
-    def("XREG", xreg ? 1 : 0);
-    def("SORTED", sorted ? 1 : 0); def("WPS", wps); def("WMS", wms); def("WSS", wss); def("OFF_ZERO", off_zero * esz);
-    def("SPLIT", split); def("WS", w2 / split);                    // slices per row of list 2, terms per slice
-    def("PASSES2", (rows2 * split + threads / ipb - 1) / (threads / ipb));   // (row, slice) pairs of list 2 per thread
-    // terms of list 2 in flight per register set: the registers of two waves per SIMD (512 threads) hold 8 f64 / 16 f32 terms twice; more
-    // threads (a single list with many rows x items), fewer registers each
-    def("TB", (plan.dtype == GAAST_F32 ? 16 : 8) / (threads > 512 ? 2 : 1));
-    def("ENT2_MODE", ent2_mode); def("ENT1_MODE", ent1_mode); def("ENT2_AT", ent2_at); def("ENT1_AT", ent1_at); def("SMEM_BYTES", used);
-    src += R"JIT(
-typedef unsigned int u32;
-typedef unsigned long long u64;
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-typedef T VT __attribute__((ext_vector_type(16 / ESZ)));
-#define EPC (16 / ESZ)
-#if F64
-#define ONE_HI 0x3ff00000u
-__device__ __forceinline__ T with_hi(T v, u32 hi) { return __builtin_bit_cast(double, (u64(hi) << 32) | (__builtin_bit_cast(u64, v) & 0xffffffffull)); }
-__device__ __forceinline__ u32 hi_of(T v) { return u32(__builtin_bit_cast(u64, v) >> 32); }
-__device__ __forceinline__ T pm_one(u32 hi) { return __builtin_bit_cast(double, u64(hi) << 32); }
-#define FMA(a, b, c) __builtin_fma(a, b, c)
-#else
-#define ONE_HI 0x3f800000u
-__device__ __forceinline__ T with_hi(T v, u32 hi) { return __builtin_bit_cast(float, hi); }
-__device__ __forceinline__ u32 hi_of(T v) { return __builtin_bit_cast(u32, v); }
-__device__ __forceinline__ T pm_one(u32 hi) { return __builtin_bit_cast(float, hi); }
-#define FMA(a, b, c) __builtin_fmaf(a, b, c)
-#endif
-#if EXACT
-#define MAC(a, b, c) ((c) + (a) * (b))
-#else
-#define MAC(a, b, c) FMA(a, b, c)
-#endif
-typedef __attribute__((address_space(3))) unsigned char lds_u8;
-#define LDS(addr) (*(const __attribute__((address_space(3))) T*)(smem + (addr)))
-
-// operand rows of the group's items, element e = item * LEN + c of the flattened range; rows beyond the batch are zero
-template <int LEN, int CANON, int OFF, int NEGOFF>
-__device__ __forceinline__ void put(lds_u8* smem, int e, T v) {
-    const int i2 = e / LEN, c = e - i2 * LEN;
-    if (CANON) v = T(0) + v;                                      // init_null_mv + add_grades_from: 0.0 + x (eval.rs:27-31)
-    *(__attribute__((address_space(3))) T*)(smem + i2 * STRIDE_B + OFF + c * ESZ) = v;
-    if (NEGOFF >= 0) *(__attribute__((address_space(3))) T*)(smem + i2 * STRIDE_B + NEGOFF + c * ESZ) = -v;
-}
-template <int LEN, int CANON, int OFF, int NEGOFF>
-__device__ __forceinline__ void stage(lds_u8* smem, const T* __restrict__ src, long long stride, long long item0, int nitems, int tid) {
-    constexpr int TOTAL = IPB * LEN;
-#pragma unroll 4
-    for (int e = tid; e < TOTAL; e += NT) {
-        const int i2 = e / LEN, c = e - i2 * LEN;
-        put<LEN, CANON, OFF, NEGOFF>(smem, e, i2 < nitems ? src[(item0 + i2) * stride + c] : T(0));
-    }
-}
-// ... the same rows as 16-byte pieces through registers: issued for the NEXT group while the current one is evaluated (contiguous,
-// 16-byte aligned rows of a full group; anything else takes stage())
-template <int LEN>
-struct Pre {
-    static constexpr int NCH = IPB * LEN / EPC, CPT = (NCH + NT - 1) / NT;
-    VT v[CPT];
-    __device__ __forceinline__ void issue(const T* __restrict__ src, long long item0, int tid) {
-        const VT* s16 = (const VT*)(src + item0 * LEN);
-#pragma unroll
-        for (int k = 0; k < CPT; ++k)
-            if (tid + k * NT < NCH) v[k] = __builtin_nontemporal_load(s16 + tid + k * NT);
-    }
-    template <int CANON, int OFF, int NEGOFF>
-    __device__ __forceinline__ void commit(lds_u8* smem, int tid) {
-#pragma unroll
-        for (int k = 0; k < CPT; ++k)
-            if (tid + k * NT < NCH) {
-#pragma unroll
-                for (int j = 0; j < EPC; ++j) put<LEN, CANON, OFF, NEGOFF>(smem, (tid + k * NT) * EPC + j, v[k][j]);
-            }
-    }
-};
-
-extern "C" __global__ __launch_bounds__(NT) void gaast_chain(const T* __restrict__ l1, long long s_l1, const T* __restrict__ r1, long long s_r1,
-                                                              const T* __restrict__ r2, long long s_r2, T* __restrict__ out, long long s_out,
-                                                              const u32* __restrict__ ent1, const u32* __restrict__ pos1,
-                                                              const u32* __restrict__ ent2, const u32* __restrict__ out2, long long batch,
-                                                              const T* __restrict__ init, long long s_init) {
-    __shared__ __attribute__((aligned(16))) unsigned char smem_raw[SMEM_BYTES];
-    lds_u8* smem = (lds_u8*)smem_raw;
-    const int tid = threadIdx.x;
-    const int it = tid & (IPB - 1), sub = tid / IPB;
-    const u32 base = u32(it) * STRIDE_B;
-    u32 one_hi = ONE_HI;
-    asm volatile("" : "+v"(one_hi));   // a vector register (the and-or takes one scalar operand)
-    // the tables, once per (persistent) workgroup
-#if SORTED || XREG
-    for (int e = tid; e < IPB; e += NT) *(__attribute__((address_space(3))) T*)(smem + e * STRIDE_B + OFF_ZERO) = T(0);   // the padding terms' operand
-#endif
-#if ENT2_MODE == 3
-    for (int e = tid; e < ROWS2 * SPLIT * WSS / 4; e += NT) ((__attribute__((address_space(3))) u32x4*)(smem + ENT2_AT))[e] = ((const u32x4*)ent2)[e];
-#elif ENT2_MODE == 2
-    for (int e = tid; e < ROWS2 * W2P / 2; e += NT) ((__attribute__((address_space(3))) u32x4*)(smem + ENT2_AT))[e] = ((const u32x4*)ent2)[e];
-#elif ENT2_MODE == 1
-    for (int e = tid; e < ROWS2 * W2P / 4; e += NT) ((__attribute__((address_space(3))) u32x4*)(smem + ENT2_AT))[e] = ((const u32x4*)ent2)[e];
-#endif
-#if ENT1_MODE >= 1 && !SINGLE
-    for (int e = tid; e < ROWS1 * W1S; e += NT) ((__attribute__((address_space(3))) u32*)(smem + ENT1_AT))[e] = ent1[e];
-#endif
-    // entry words: list 1, term t of `row`; list 2, the quad holding terms 4q .. 4q + 3 (narrow) / 2q, 2q + 1 (wide)
-#if !SINGLE
-    auto ent1_quad = [&](int row, int q) -> u32x4 {
-#if ENT1_MODE == 2
-        return ((const __attribute__((address_space(3))) u32x4*)(smem + ENT1_AT))[row * (W1S / 4) + q];
-#elif ENT1_MODE == 1
-        const __attribute__((address_space(3))) u32* pw = (const __attribute__((address_space(3))) u32*)(smem + ENT1_AT) + row * W1S + 4 * q;
-        u32x4 r;
-        r[0] = pw[0];
-        r[1] = 4 * q + 1 < W1 ? pw[1] : 0u;
-        r[2] = 4 * q + 2 < W1 ? pw[2] : 0u;
-        r[3] = 4 * q + 3 < W1 ? pw[3] : 0u;
-        return r;
-#else
-        return ((const u32x4*)ent1)[row * (W1S / 4) + q];
-#endif
-    };
-#endif
-    auto ent2_quad = [&](int row, int q) -> u32x4 {
-#if ENT2_MODE == 2
-        return ((const __attribute__((address_space(3))) u32x4*)(smem + ENT2_AT))[row * (W2P / 2) + q];
-#elif ENT2_MODE == 1
-        return ((const __attribute__((address_space(3))) u32x4*)(smem + ENT2_AT))[row * (W2P / 4) + q];
-#else
-        return ((const u32x4*)ent2)[row * (W2P / 4) + q];
-#endif
-    };
-    u32 oo_reg[PASSES2];   // this thread's rows of list 2: their output offsets, loaded once
-#pragma unroll
-    for (int k = 0; k < PASSES2; ++k) oo_reg[k] = sub + k * NSUB < ROWS2 * SPLIT ? out2[(sub + k * NSUB) / SPLIT] : 0u;
-#if INIT_SRC
-    u32 io_reg[PASSES2];   // ... and where their accumulators start from: 0.0 + init[offset] (a covering copy_grades_from folded in)
-#pragma unroll
-    for (int k = 0; k < PASSES2; ++k) io_reg[k] = sub + k * NSUB < ROWS2 * SPLIT ? pos1[(sub + k * NSUB) / SPLIT] : 0u;
-#endif
-    const long long groups = (batch + IPB - 1) / IPB;
-    // register-prefetch staging needs contiguous, 16-byte aligned rows (wave-uniform test); shared rows (stride 0), wrapped
-    // strided memory and the last, partial group take the plain loop
-    // (the memory counter is IN ORDER: a wait for any later global load would wait for the prefetched rows first, so the evaluation
-    //  issues none where it can: row positions and output offsets in registers, tables in LDS.  A table that has to stay in global
-    //  memory (n = 10: list 1's) makes the first row of list 1 wait for the prefetch -- still better than no prefetch: measured
-    //  0.214 against 0.164 G items/s at n = 10)
-#if SINGLE
-    // a single list: the left operand is the staged "mid" row (pointer l1), the right one list 2's own operand (pointer r2)
-    const bool fast = s_l1 == MID && s_r2 == R2 && ((u64)l1 & 15ull) == 0 && ((u64)r2 & 15ull) == 0 && (IPB * MID) % EPC == 0 && (IPB * R2) % EPC == 0;
-    Pre<MID> pl;
-    Pre<R2> pq;
-    auto issue = [&](long long item0) {
-        pl.issue(l1, item0, tid);
-        pq.issue(r2, item0, tid);
-    };
-    auto commit = [&]() {
-        pl.template commit<CANON_MID, OFF_MID, -1>(smem, tid);
-        pq.template commit<CANON_R2, OFF_R2, -1>(smem, tid);
-    };
-    auto stage_all = [&](long long item0, int nitems) {
-        stage<MID, CANON_MID, OFF_MID, -1>(smem, l1, s_l1, item0, nitems, tid);
-        stage<R2, CANON_R2, OFF_R2, -1>(smem, r2, s_r2, item0, nitems, tid);
-    };
-#else
-    const bool fast = s_l1 == L1 && s_r1 == R1 && ((u64)l1 & 15ull) == 0 && ((u64)r1 & 15ull) == 0 && (IPB * L1) % EPC == 0 && (IPB * R1) % EPC == 0
-#if HAS_R2
-                      && s_r2 == R2 && ((u64)r2 & 15ull) == 0 && (IPB * R2) % EPC == 0
-#endif
-        ;
-    Pre<L1> pl;
-    Pre<R1> pr;
-#if HAS_R2
-    Pre<R2> pq;
-#endif
-    auto issue = [&](long long item0) {
-        pl.issue(l1, item0, tid);
-        pr.issue(r1, item0, tid);
-#if HAS_R2
-        pq.issue(r2, item0, tid);
-#endif
-    };
-    auto commit = [&]() {
-        pl.template commit<CANON_L1, OFF_L1, (NEG_IS_LEFT ? OFF_NEG : -1)>(smem, tid);
-        pr.template commit<CANON_R1, OFF_R1, (NEG_IS_LEFT ? -1 : OFF_NEG)>(smem, tid);
-#if HAS_R2
-        pq.template commit<CANON_R2, OFF_R2, -1>(smem, tid);
-#endif
-    };
-    auto stage_all = [&](long long item0, int nitems) {
-        stage<L1, CANON_L1, OFF_L1, (NEG_IS_LEFT ? OFF_NEG : -1)>(smem, l1, s_l1, item0, nitems, tid);
-        stage<R1, CANON_R1, OFF_R1, (NEG_IS_LEFT ? -1 : OFF_NEG)>(smem, r1, s_r1, item0, nitems, tid);
-#if HAS_R2
-        stage<R2, CANON_R2, OFF_R2, -1>(smem, r2, s_r2, item0, nitems, tid);
-#endif
-    };
-#endif
-    long long g = blockIdx.x;
-    if (g >= groups) return;
-    {
-        const long long item0 = g * IPB;
-        const int nitems = int(batch - item0 < IPB ? batch - item0 : IPB);
-        if (fast && nitems == IPB) {
-            issue(item0);
-            commit();
-        } else {
-            stage_all(item0, nitems);
-        }
-    }
-    for (;;) {   // persistent workgroups
-        const long long item0 = g * IPB;
-        const int nitems = int(batch - item0 < IPB ? batch - item0 : IPB);
-        const long long gn = g + gridDim.x;
-        const bool more = gn < groups;
-        const int nnext = more ? int(batch - gn * IPB < IPB ? batch - gn * IPB : IPB) : 0;
-        const bool pre_next = fast && more && nnext == IPB;
-#if !COVERED && !SINGLE
-        for (int e = tid; e < IPB * MID; e += NT) *(__attribute__((address_space(3))) T*)(smem + (e / MID) * STRIDE_B + OFF_MID + (e % MID) * ESZ) = T(0);
-#endif
-        __syncthreads();
-#if BETA
-        T acc0[PASSES2];   // list 2 adds into what another arm left in `out`: read BEFORE the prefetch is issued (in-order counter)
-#pragma unroll
-        for (int k = 0; k < PASSES2; ++k) acc0[k] = (sub + k * NSUB < ROWS2 * SPLIT && it < nitems) ? out[(item0 + it) * s_out + oo_reg[k]] : T(0);
-#elif INIT_SRC
-        T acc0[PASSES2];   // ... or onto a copy of an input's grades, made here: 0.0 + x (graded.rs:195-201 then :74)
-#pragma unroll
-        for (int k = 0; k < PASSES2; ++k) acc0[k] = T(0) + ((sub + k * NSUB < ROWS2 * SPLIT && it < nitems) ? init[(item0 + it) * s_init + io_reg[k]] : T(0));
-#endif
-        if (pre_next) issue(gn * IPB);   // in flight while this group is evaluated
-        // ---- list 1 -> mid (eval.rs:77-83 into the fresh cache buffer of eval.rs:21-33): the operands of row k + 1 are in
-        // flight while row k's chain is evaluated (two register sets, the loop unrolled by two: no copies) ----
-#if !SINGLE
-#if XREG
-        {   // list 1 with the right operand (R1 components of THIS lane's item) in registers: term j of every row multiplies by xr[j]
-            T xr[R1];
-#pragma unroll
-            for (int j = 0; j < R1; ++j) xr[j] = LDS(base + OFF_R1 + j * ESZ);
-            T la[R1], lb[R1];
-            u32 ea[R1], eb[R1];
-            auto load1 = [&](T (&lv)[R1], u32 (&ev)[R1], int row) {
-#pragma unroll
-                for (int q = 0; q < (R1 + 3) / 4; ++q) {
-                    const u32x4 e4 = ent1_quad(row, q);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (4 * q + j < R1) {
-                            lv[4 * q + j] = LDS(base + (e4[j] & 0xffffu));
-                            ev[4 * q + j] = e4[j];
-                        }
-                }
-            };
-            auto sum1 = [&](const T (&lv)[R1], const u32 (&ev)[R1], int row) {
-                T acc = T(0);
-#pragma unroll
-                for (int t = 0; t < R1; ++t) acc = FMA(with_hi(lv[t], hi_of(lv[t]) ^ (ev[t] & 0x80000000u)), xr[t], acc);
-#if POS1_LINEAR
-                *(__attribute__((address_space(3))) T*)(smem + base + OFF_MID + row * ESZ) = CANON_MID ? T(0) + acc : acc;
-#else
-                *(__attribute__((address_space(3))) T*)(smem + base + pos1[row]) = CANON_MID ? T(0) + acc : acc;
-#endif
-            };
-            constexpr int LAST1 = ROWS1 - 1;
-            int row = sub;
-            if (row < ROWS1) load1(la, ea, row);
-#pragma nounroll
-            for (; row < ROWS1; row += 2 * NSUB) {
-                const int r2_ = row + NSUB, r3_ = row + 2 * NSUB;
-                load1(lb, eb, r2_ < ROWS1 ? r2_ : LAST1);
-                sum1(la, ea, row);
-                load1(la, ea, r3_ < ROWS1 ? r3_ : LAST1);
-                if (r2_ < ROWS1) sum1(lb, eb, r2_);
-            }
-        }
-        __syncthreads();
-#elif !SINGLE
-        {
-            T la[W1], ra[W1], lb[W1], rb[W1];
-            auto load1 = [&](T (&lv)[W1], T (&rv)[W1], int row) {
-#pragma unroll
-                for (int q = 0; q < (W1 + 3) / 4; ++q) {
-                    const u32x4 e4 = ent1_quad(row, q);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (4 * q + j < W1) {
-                            lv[4 * q + j] = LDS(base + (e4[j] & 0xffffu));
-                            rv[4 * q + j] = LDS(base + (e4[j] >> 16));
-                        }
-                }
-            };
-            auto sum1 = [&](const T (&lv)[W1], const T (&rv)[W1], int row) {
-                T acc = T(0);
-#pragma unroll
-                for (int t = 0; t < W1; ++t) acc = MAC(lv[t], rv[t], acc);   // (l * r) * (+-1) then +=: the sign rides in the image
-#if POS1_LINEAR
-                *(__attribute__((address_space(3))) T*)(smem + base + OFF_MID + row * ESZ) = CANON_MID ? T(0) + acc : acc;
-#else
-                *(__attribute__((address_space(3))) T*)(smem + base + pos1[row]) = CANON_MID ? T(0) + acc : acc;
-#endif
-            };
-            constexpr int LAST1 = ROWS1 - 1;
-            int row = sub;
-            if (row < ROWS1) load1(la, ra, row);
-#pragma nounroll
-            for (; row < ROWS1; row += 2 * NSUB) {
-                const int r2_ = row + NSUB, r3_ = row + 2 * NSUB;
-                load1(lb, rb, r2_ < ROWS1 ? r2_ : LAST1);
-                sum1(la, ra, row);
-                load1(la, ra, r3_ < ROWS1 ? r3_ : LAST1);
-                if (r2_ < ROWS1) sum1(lb, rb, r2_);
-            }
-        }
-        __syncthreads();
-#endif
-#endif
-        // ---- list 2: (mid, other operand) -> out; TB terms' operands in flight while the previous TB are summed ----
-#if SPLIT > 1
-        T part[PASSES2];
-#endif
-#pragma unroll
-        for (int pass = 0; pass < PASSES2; ++pass) {
-            const int vrow = sub + pass * NSUB;          // (row, slice)
-            if (vrow >= ROWS2 * SPLIT) break;
-            const int row = vrow / SPLIT, slice = vrow % SPLIT;
-            const u32 oo = oo_reg[pass];
-#if (BETA || INIT_SRC) && SPLIT == 1
-            T acc = acc0[pass];
-#else
-            T acc = T(0);                                // (slices start from zero: what the row adds onto joins them at the end)
-#endif
-#if SORTED
-            // tolerance mode, sign-sorted: WPS plus-terms, then WMS minus-terms (both whole batches of TB; the padding multiplies the item's
-            // zero element by itself): no sign per term -- two address additions and one fused multiply-add
-            {
-                T ma[TB], oa[TB], mb[TB], ob[TB];
-                auto load2 = [&](T (&mv)[TB], T (&ov)[TB], int q) {      // TB terms from quad q of this (row, slice)
-#pragma unroll
-                    for (int i = 0; i < TB / 4; ++i) {
-#if ENT2_MODE == 3
-                        const u32x4 e4 = ((const __attribute__((address_space(3))) u32x4*)(smem + ENT2_AT))[vrow * (WSS / 4) + q + i];
-#else
-                        const u32x4 e4 = ((const u32x4*)ent2)[vrow * (WSS / 4) + q + i];
-#endif
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            mv[4 * i + j] = LDS(base + (e4[j] & 0xffffu));
-                            ov[4 * i + j] = LDS(base + (e4[j] >> 16));
-                        }
-                    }
-                };
-                constexpr int NBT = WSS / TB, NBP = WPS / TB;            // batches in all, plus-batches first
-                auto sum2 = [&](const T (&mv)[TB], const T (&ov)[TB], int b) {
-                    if (b < NBP) {
-#pragma unroll
-                        for (int t = 0; t < TB; ++t) acc = FMA(mv[t], ov[t], acc);
-                    } else {
-#pragma unroll
-                        for (int t = 0; t < TB; ++t) acc = FMA(-mv[t], ov[t], acc);
-                    }
-                };
-                load2(ma, oa, 0);
-                int b = 0;
-#pragma nounroll
-                for (; b + 2 <= NBT; b += 2) {
-                    load2(mb, ob, (b + 1) * (TB / 4));
-                    sum2(ma, oa, b);
-                    load2(ma, oa, (b + 2 < NBT ? b + 2 : NBT - 1) * (TB / 4));
-                    sum2(mb, ob, b + 1);
-                }
-                if (NBT & 1) sum2(ma, oa, NBT - 1);
-            }
-#else
-            constexpr int NB = WS / TB;                  // batches of TB terms
-            constexpr int QPT = ENT2_MODE == 2 ? 2 : 4;  // terms per table quad
-            const int q0 = slice * (WS / QPT);           // the slice's first quad (WS is a multiple of 4)
-#if ENT2_MODE == 2
-            T ma[TB], oa[TB], mb[TB], ob[TB];
-            u32 sa[TB], sb[TB];
-            auto load2 = [&](T (&mv)[TB], T (&ov)[TB], u32 (&sg)[TB], int b) {
-#pragma unroll
-                for (int q = 0; q < TB / 2; ++q) {
-                    const u32x4 e4 = ent2_quad(row, q0 + (TB / 2) * b + q);
-                    mv[2 * q] = LDS(base + (e4[0] & 0xffffu));
-                    ov[2 * q] = LDS(base + (e4[0] >> 16));
-                    sg[2 * q] = e4[1];
-                    mv[2 * q + 1] = LDS(base + (e4[2] & 0xffffu));
-                    ov[2 * q + 1] = LDS(base + (e4[2] >> 16));
-                    sg[2 * q + 1] = e4[3];
-                }
-            };
-            auto sum2 = [&](const T (&mv)[TB], const T (&ov)[TB], const u32 (&sg)[TB]) {
-#pragma unroll
-                for (int t = 0; t < TB; ++t) {
-#if EXACT
-                    const T pr_ = mv[t] * ov[t];
-                    acc = acc + with_hi(pr_, hi_of(pr_) ^ sg[t]);            // eval.rs:82: (l * r) * (+-1), then +=
-#else
-                    acc = FMA(with_hi(mv[t], hi_of(mv[t]) ^ sg[t]), ov[t], acc);   // tolerance mode: one rounding per term
-#endif
-                }
-            };
-#else
-            T ma[TB], oa[TB], sa[TB], mb[TB], ob[TB], sb[TB];
-            auto load2 = [&](T (&mv)[TB], T (&ov)[TB], T (&sg)[TB], int b) {
-#pragma unroll
-                for (int q = 0; q < TB / 4; ++q) {
-                    const u32x4 e4 = ent2_quad(row, q0 + (TB / 4) * b + q);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        mv[4 * q + j] = LDS(base + (e4[j] & 0xffffu));
-                        ov[4 * q + j] = LDS(base + ((e4[j] >> 16) & 0x7fffu));
-                        u32 hi;
-                        asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(hi) : "v"(e4[j]), "s"(0x80000000u), "v"(one_hi));   // +-1.0: the high word
-                        sg[4 * q + j] = pm_one(hi);
-                    }
-                }
-            };
-            auto sum2 = [&](const T (&mv)[TB], const T (&ov)[TB], const T (&sg)[TB]) {
-#pragma unroll
-                for (int t = 0; t < TB; ++t) acc = FMA(mv[t] * ov[t], sg[t], acc);   // eval.rs:82: the product is rounded, +-1 is exact
-            };
-#endif
-            if (NB > 0) load2(ma, oa, sa, 0);
-            int b = 0;
-#pragma nounroll
-            for (; b + 2 <= NB; b += 2) {
-                load2(mb, ob, sb, b + 1);
-                sum2(ma, oa, sa);
-                load2(ma, oa, sa, b + 2 < NB ? b + 2 : NB - 1);
-                sum2(mb, ob, sb);
-            }
-            if (NB & 1) sum2(ma, oa, sa);
-#pragma unroll
-            for (int t = NB * TB; t < WS; ++t) {         // the remainder (compile-time count, no padding terms)
-#if ENT2_MODE == 2
-                const u32x4 e4 = ent2_quad(row, q0 + t / 2);
-                const u32 e = e4[2 * (t & 1)], sgb = e4[2 * (t & 1) + 1];
-#if EXACT
-                const T pr_ = LDS(base + (e & 0xffffu)) * LDS(base + (e >> 16));
-                acc = acc + with_hi(pr_, hi_of(pr_) ^ sgb);
-#else
-                const T m_ = LDS(base + (e & 0xffffu));
-                acc = FMA(with_hi(m_, hi_of(m_) ^ sgb), LDS(base + (e >> 16)), acc);
-#endif
-#else
-                const u32 e = ent2_quad(row, q0 + t / 4)[t & 3];
-                acc = FMA(LDS(base + (e & 0xffffu)) * LDS(base + ((e >> 16) & 0x7fffu)), pm_one((e & 0x80000000u) | ONE_HI), acc);
-#endif
-            }
-#endif
-#if SPLIT > 1
-            part[pass] = acc;
-#else
-            if (it < nitems) out[(item0 + it) * s_out + oo] = acc;
-#endif
-        }
-#if SPLIT > 1
-        // the slices of a row meet through LDS (the mid rows are dead by now): partial sums in slice order onto the row's start value
-        __syncthreads();
-#pragma unroll
-        for (int pass = 0; pass < PASSES2; ++pass) {
-            const int vrow = sub + pass * NSUB;
-            if (vrow < ROWS2 * SPLIT) *(__attribute__((address_space(3))) T*)(smem + base + OFF_MID + vrow * ESZ) = part[pass];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int pass = 0; pass < PASSES2; ++pass) {
-            const int vrow = sub + pass * NSUB;
-            if (vrow < ROWS2 * SPLIT && vrow % SPLIT == 0 && it < nitems) {
-#if BETA || INIT_SRC
-                T acc = acc0[pass];
-#else
-                T acc = T(0);
-#endif
-#pragma unroll
-                for (int sl = 0; sl < SPLIT; ++sl) acc = acc + LDS(base + OFF_MID + (vrow + sl) * ESZ);
-                out[(item0 + it) * s_out + oo_reg[pass]] = acc;
-            }
-        }
-#endif
-        __syncthreads();   // the rows are rewritten by the next group
-        if (!more) break;
-        g = gn;
-        if (pre_next) commit();
-        else stage_all(gn * IPB, nnext);
-    }
-}
-)JIT";
-    c.cj.on = 1;
-    c.cj.source = std::move(src);
-    const int64_t lay[7] = {off_l1, off_r1, off_neg, off_mid, alias ? -1 : off_r2, stride, neg_is_left ? 1 : 0};
-    for (int i = 0; i < 7; ++i) c.cj.layout[i] = int(lay[i]);
-    c.cj.fmt[0] = int(w1s);
-    c.cj.fmt[1] = ent2_mode;
-    c.cj.sorted[0] = int(wps);
-    c.cj.sorted[1] = int(wms);
-    c.cj.sorted[2] = int(off_zero * esz);
-    c.cj.xreg = xreg ? 1 : 0;
-    c.cj.split = int(split);
-    c.cj.ipb = int(ipb);
-    c.cj.threads = int(threads);
-    c.cj.lds = size_t(used);
 }
 
 // A list product whose result is read ONLY by another list product (as either operand): both run in ONE k_product_ell_chain
@@ -3188,8 +1734,7 @@ void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab)
     plan.node_dead.assign(plan.node_buffers.size(), 0);
     // A program that would only fit the LDS interpreter (its slab is beyond the registers of the hiprtc-specialised kernel) but is
     // exactly one list chain -- (R X ~R).g(1) at n = 8 -- runs on k_product_ell_chain instead (same box: 1.43 against 1.59 ms per 1 M items)
-    int slab = 0;
-    try_fuse(plan, small_reg_slab, &slab);
+    const int slab = fused_slab(plan, small_reg_slab);
     if (slab > (plan.dtype == GAAST_F32 ? 200 : 160) && !(plan.flags & (GAAST_FLAG_NO_FUSION | GAAST_FLAG_DEBUG_NO_CHAIN | GAAST_FLAG_NO_JIT))) {
         Plan trial = plan;
         uniform_csr_to_ell(trial);

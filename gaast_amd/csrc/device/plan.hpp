@@ -123,7 +123,7 @@ struct Step {
         int ipb = 0, item_stride = 0, ent2_lds = 0;   // (bytes of this list's words kept in LDS, or 0)
     } chain;
 
-    // ... specialised per program through hiprtc (plan.cpp: make_chain_jit; round 4): lane = (row, item) in BOTH lists with the items
+    // ... specialised per program through hiprtc (plan_chain_jit.cpp: make_chain_jit; round 4): lane = (row, item) in BOTH lists with the items
     // of a workgroup fastest, so that the 32 lanes of an LDS access read one row's operand of 32 different items (odd item stride:
     // no bank conflict); entries carry byte offsets from the item's base (list 1: the sign is folded into a negated image of the
     // smaller operand); compile-time widths, lengths and strides.  The generic k_product_ell_chain stays as the fallback.

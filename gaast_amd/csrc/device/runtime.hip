@@ -448,7 +448,7 @@ int prepare_step(Launch& L, const Layout& la, const Layout& lb, std::string& ker
                            "product operands of " + std::to_string(per_item) + " bytes per item do not fit the " +
                                std::to_string(g_max_lds) + "-byte LDS of the list kernels (" + s.name + ")");
         if (L.jit) {
-            // the chain (or single long-row list) specialised through hiprtc (plan.cpp: make_chain_jit): static LDS, persistent workgroups
+            // the chain (or single long-row list) specialised through hiprtc (plan_chain_jit.cpp: make_chain_jit): static LDS, persistent workgroups
             L.threads = s.cj.threads;
             L.lds = s.cj.lds;
             kernel = "gaast_chain<" + tn + ">[" + (s.cj.single ? "one list, " : "") + std::to_string(s.cj.ipb) + " items, " + std::to_string(s.cj.threads) + " threads" +
@@ -1279,7 +1279,7 @@ bool compile_fused(gaast_hip_program_s& prog, uint32_t flags, uint32_t* rebuild_
             g_err = "hiprtc: " + log;  // informational: the interpreter kernel (or an unfused plan) runs instead
         bool trial_failed = false;
         if (L.jit && s.fused.jit_reg_trial) {
-            // a slab beyond 160 / 200 elements in registers, on trial (plan.cpp: try_fuse): the compiled kernel has to leave two
+            // a slab beyond 160 / 200 elements in registers, on trial (plan_fused.cpp: SlabLayout): the compiled kernel has to leave two
             // waves per SIMD (eight single-wave workgroups per CU), else the plan is rebuilt with the slabs in LDS
             int per_cu = 0;
             trial_failed = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, L.jit.fn, s.fused.jit_threads, 0) != hipSuccess ||

@@ -232,7 +232,7 @@ static void dense_tables_agree_with_the_list(int n, const double* metric, int dt
     std::printf("ok  %s (%s)\n", what, st->name.c_str());
 }
 
-// The list chain specialised per program (plan.cpp: make_chain_jit): its tables are a TRANSFORMATION of the generic chain's
+// The list chain specialised per program (plan_chain_jit.cpp: make_chain_jit): its tables are a TRANSFORMATION of the generic chain's
 // (byte offsets from the item's base in a new LDS layout, list 1's signs folded into a negated image).  Both table sets are
 // executed here, in plain C++ doubles in the kernels' order, on the same random rows: every result bit must agree.  With a
 // directory argument the generated kernel source is written there (tests/test_chain_jit.py compiles it for gfx950).
@@ -751,7 +751,7 @@ int main(int argc, char** argv) {
             every_buffer_read_is_live(sw, n, euclid, GAAST_F64, what, false);
         }
     }
-    // the versor inverse of an even multivector at n = 8 in f32 (plan.cpp, beside jit_slab_small: a slab of 259 elements, on register trial)
+    // the versor inverse of an even multivector at n = 8 in f32 (plan_fused.cpp, beside jit_slab_small: a slab of 259 elements, on register trial)
     reserved_flag_bits_are_ignored(gaast_expr_vinv(gaast_expr_input(0, 0x155, 8)), 8, euclid, GAAST_F32, "flag bit 30 ignored: versor inverse n=8 f32");
     for (gaast_expr_t h : handles) gaast_expr_release(h);
     if (failures) {

@@ -330,7 +330,7 @@ def _chain(name, n, dtype, flags):
         odd = _grades_of(n, mmask)
         S = np.stack([bits_to_row(n, [1], abs_terms_bound(n, row_to_bits(n, odd, mid[i]), row_to_bits(n, even, rows64[0][i]))) for i in range(batch)])
         return want, wmask, S
-    # The staging form is chosen inside the generated kernel (plan.cpp make_chain_jit: `fast = s_l1 == L1 && s_r1 == R1 && both
+    # The staging form is chosen inside the generated kernel (plan_chain_jit.cpp, the kernel text: `fast = s_l1 == L1 && s_r1 == R1 && both
     # bases 16-byte aligned && whole 16-byte pieces per workgroup`): contig rows take the coalesced span, every other layout of
     # slot 0 or 1 the per-lane staging; the result rows are always stored per lane.  One kernel: variant 0.  The order of the sums
     # does not depend on the staging, so all layouts agree in bits -- with GAAST_FLAG_EXACT_ORDER with the oracle's; without, within
@@ -366,11 +366,11 @@ _r5 = lambda B: B.input(0, full_grades(5), 5) * B.input(1, full_grades(5), 5)
 _unary12 = lambda B: (-(B.input(0, [2], 12).rev()) + B.input(1, [2], 12).ginvol()).rev() * B.input(2, [0], 12)
 _unary12_6 = lambda B: (-(B.input(0, [6], 12).rev()) + B.input(1, [6], 12).ginvol()).rev() * B.input(2, [0], 12)
 EXACT_CASES = [
-    # gaast_jit with slabs in LDS (plan.cpp: per operand `fast_cond`: stride == length && base 16-byte aligned, else the lane reads its
+    # gaast_jit with slabs in LDS (plan_fused.cpp: LdsForm::staging, per operand `fast_cond`: stride == length && base 16-byte aligned, else the lane reads its
     # own row; the last partial wave always does).  Inputs scaled by 2^-6 so that the inverse has components beyond 1.
     _exact_case("jit-lds-vinv8-f64", 8, ga.F64, 8, _vinv8, [EVEN(8)], "ast_jit[", scale=2.0 ** -6, label_has=("ast_jit[", "slab in LDS")),
     _exact_case("jit-lds-vinv8-f32", 8, ga.F32, 8, _vinv8, [EVEN(8)], "ast_jit[", scale=2.0 ** -6, label_has=("ast_jit[",)),
-    # gaast_jit in registers, f32 (plan.cpp: `full && s == len && (in & 15) == 0` span form, `line_ok` line form for rows of >= 128
+    # gaast_jit in registers, f32 (plan_fused.cpp: RowIo, `full && s == len && (in & 15) == 0` span form, `line_ok` line form for rows of >= 128
     # bytes with a 16-byte-multiple stride, else per lane): the programs of test_specialised_kernels_row_io_forms_are_bit_exact.
     # Grade 1 of R^5 is a 20-byte row: `contig` rows are themselves misaligned from the second row on.
     _exact_case("jit-reg-cl41-f32", 5, ga.F32, CGA, _cl41, [[0, 2, 4], [1]], "ast_jit[", label_has=("ast_jit[",)),

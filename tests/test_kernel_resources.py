@@ -95,7 +95,8 @@ def test_library_revision_matches_the_sources_it_was_built_from():
     import gaast_amd
     root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gaast_amd", "csrc")
     files = sorted(glob.glob(os.path.join(root, "device", "*.hip.hpp"))) + [os.path.join(root, "device", f) for f in
-                                                                              ("runtime.hip", "plan.cpp", "plan.hpp", "spinor_basis.hpp")]
+                                                                              ("runtime.hip", "plan.cpp", "plan_fused.cpp", "plan_chain_jit.cpp", "plan_internal.hpp", "plan.hpp",
+                                                                               "spinor_basis.hpp")]
     h = hashlib.md5()
     for f in files:
         h.update(open(f, "rb").read())
@@ -107,7 +108,7 @@ def test_library_revision_matches_the_sources_it_was_built_from():
 
 
 def test_a_change_of_the_build_switches_rebuilds_every_object_that_sees_them():
-    """KFLAGS reaches plan.cpp too (GAAST_JIT_NT, GAAST_INTERP_BUDGET_KB): with the revision hashing KFLAGS, a change of switches
+    """KFLAGS reaches the plan*.cpp files too (GAAST_JIT_NT, GAAST_INTERP_BUDGET_KB): with the revision hashing KFLAGS, a change of switches
     in an existing object directory must recompile plan.o and runtime.o, or the library reports the new revision over old code
     (make -n: nothing is built)."""
     import os

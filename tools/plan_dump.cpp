@@ -1,6 +1,6 @@
 // CPU-only: prints the launch plan (step names) gaast::build_plan produces for the whole-AST workloads of bench.py -- no GPU, no HIP.
 // Build: g++ -std=c++17 -O1 -I include -I gaast_amd/csrc/device -I gaast_amd/csrc/common -I gaast_amd/csrc/host tools/plan_dump.cpp
-//        gaast_amd/csrc/host/{expr,c_api_host,wire}.cpp gaast_amd/csrc/device/plan.cpp -o /tmp/plan_dump
+//        gaast_amd/csrc/host/{expr,c_api_host,wire}.cpp gaast_amd/csrc/device/plan*.cpp -o /tmp/plan_dump
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
