@@ -2,6 +2,7 @@
 // Included through kernels.hip.hpp.
 #pragma once
 #include "kernels_common.hip.hpp"
+#include "explog_adj_series.hip.hpp"
 
 namespace gaast {
 
@@ -125,6 +126,153 @@ __global__ __launch_bounds__(256) void k_exp_log(ExpLogArgs<T> p) {
         if (p.res_0 >= 0) r[p.res_0] = r[p.res_0] + c0;
         if (p.res_k >= 0)
             for (int i = 0; i < p.m_res; ++i) r[p.res_k + i] = r[p.res_k + i] + f * B[i];
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Reverse mode of the extension (GAAST_OP_EXP_ADJ / GAAST_OP_LOG_ADJ, gaast_hip.h): res += the cotangent of the operand of
+// exp(B) / log(a + B), from the operand row and the row of the cotangent g of the forward result.
+//   s = sum sq_i B_i^2, d = sum_{i < m_g} g_k[i] B_i, c0 and f as k_exp_log computes them, branch for branch;
+//   exp: w = f g_0 + h d, h = (c0 - f) / s;   log: w = h d, h = (a / D - f) / s, D = a^2 - s, da = -d / D;
+//   dB_i = f g_k[i] (i < m_g) + sq_i B_i w;   h from its series where the quotient cancels (explog_adj_series.hip.hpp).
+// No domain check, no counter, no atomics: the forward counted.  One thread computes one item, but the rows of the items of a
+// workgroup travel through LDS (consecutive lanes move consecutive elements of consecutive rows, as k_product_csr stages its
+// operands; an item's rows sit `lds_stride` elements apart, odd: its thread then walks them without bank conflicts) -- k_exp_log's
+// one-thread-per-item loop strides through memory by a whole row per lane.  items == 0: the rows do not fit the LDS budget,
+// every thread reads and writes its own rows directly.  Rows may be wrapped memory of any stride and alignment: element accesses.
+// ------------------------------------------------------------------------------------------
+template <typename T>
+struct ExpLogAdjArgs {
+    T* res;
+    const T* arg;                 // operand rows (B; log: a)
+    const T* cot;                 // cotangent rows (g)
+    int64_t res_stride, arg_stride, cot_stride;
+    int m, m_g, m_res;            // components of B / of them g holds / res holds
+    int arg_k, arg_0, g_k, g_0, res_k, res_0;   // row offsets, -1 = absent
+    int arg_len, cot_len;         // row lengths (staged whole)
+    int items, lds_stride;        // items per workgroup pass (0: direct form); elements between two items' rows in LDS
+    const T* sq;                  // e_i e_i
+    int64_t batch;
+};
+
+// the series coefficients in constant memory (index n; as immediates the 44 f64 values crowd the scalar registers)
+struct ExpLogAdjSeries {
+    double e[exp_adj_series_terms(false) + 1], l[log_adj_series_terms(false) + 1];
+    constexpr ExpLogAdjSeries() : e(), l() {
+        for (int n = 1; n <= exp_adj_series_terms(false); ++n) e[n] = exp_adj_series_coeff(n);
+        for (int n = 1; n <= log_adj_series_terms(false); ++n) l[n] = log_adj_series_coeff(n);
+    }
+};
+__device__ const ExpLogAdjSeries kExpLogAdjSeries{};
+
+template <typename T>
+struct ExpLogAdjScalars {
+    T f, w, da;
+};
+
+// the scalars of one item; B: its m grade-k components, gk: its m_g cotangent components (unit stride; LDS or global memory)
+template <typename T, int OP>
+__device__ __forceinline__ ExpLogAdjScalars<T> exp_log_adj_scalars(const ExpLogAdjArgs<T>& p, const T* B, const T* gk, T a, T g0) {
+    constexpr bool F32 = sizeof(T) == 4;
+    T s = T(0), d = T(0);
+    for (int i = 0; i < p.m; ++i) s = s + B[i] * B[i] * p.sq[i];
+    for (int i = 0; i < p.m_g; ++i) d = d + gk[i] * B[i];
+    ExpLogAdjScalars<T> r;
+    T h;
+    if (OP == 0) {
+        T c0;
+        if (s < T(0)) { const T t = sqrt_m(-s); c0 = cos_m(t); r.f = sin_m(t) / t; }
+        else if (s > T(0)) { const T t = sqrt_m(s); c0 = cosh_m(t); r.f = sinh_m(t) / t; }
+        else if (s == T(0)) { c0 = T(1); r.f = T(1); }
+        else { c0 = s; r.f = s; }
+        if (s < T(kExpAdjSeriesBelow) && s > T(-kExpAdjSeriesBelow)) {
+            constexpr int N = exp_adj_series_terms(F32);
+            h = T(kExpLogAdjSeries.e[N]);
+#pragma unroll 1
+            for (int n = N - 1; n >= 1; --n) h = h * s + T(kExpLogAdjSeries.e[n]);
+        } else {
+            h = (c0 - r.f) / s;
+        }
+        r.w = r.f * g0 + h * d;
+        r.da = T(0);
+    } else {
+        if (s < T(0)) { const T mm = sqrt_m(-s); r.f = atan2_m(mm, a) / mm; }
+        else if (s > T(0)) { const T mm = sqrt_m(s); r.f = atanh_m(mm / a) / mm; }
+        else if (s == T(0)) { r.f = T(1) / a; }
+        else { r.f = s; }
+        const T a2 = a * a, D = a2 - s, lim = T(kLogAdjSeriesBelow) * a2;
+        if (s == T(0) || (s < lim && s > -lim && (a > T(0) || s > T(0)))) {
+            constexpr int N = log_adj_series_terms(F32);
+            const T u = s / a2;
+            h = T(kExpLogAdjSeries.l[N]);
+#pragma unroll 1
+            for (int n = N - 1; n >= 1; --n) h = h * u + T(kExpLogAdjSeries.l[n]);
+            h = h / (a2 * a);
+        } else {
+            h = (a / D - r.f) / s;
+        }
+        r.w = h * d;
+        r.da = -(d / D);
+    }
+    return r;
+}
+
+// OP: 0 exp, 1 log (one instantiation holds the transcendental functions of one of them)
+template <typename T, int OP>
+__global__ __launch_bounds__(256) void k_exp_log_adj(ExpLogAdjArgs<T> p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    T* lds = reinterpret_cast<T*>(smem_raw);
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const bool staged = p.items > 0;
+    const int per = staged ? p.items : nthr;   // items of one pass of this workgroup
+    const int64_t n_groups = (p.batch + per - 1) / per;
+    for (int64_t grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
+        const int64_t item0 = grp * per;
+        const int nitems = int(p.batch - item0 < per ? p.batch - item0 : per);
+        if (staged) {
+            // stage the operand and cotangent rows: consecutive threads read consecutive elements of consecutive rows
+            for (int i = tid; i < nitems * p.arg_len; i += nthr) {
+                const int it = i / p.arg_len, c = i - it * p.arg_len;
+                lds[it * p.lds_stride + c] = p.arg[(item0 + it) * p.arg_stride + c];
+            }
+            for (int i = tid; i < nitems * p.cot_len; i += nthr) {
+                const int it = i / p.cot_len, c = i - it * p.cot_len;
+                lds[it * p.lds_stride + p.arg_len + c] = p.cot[(item0 + it) * p.cot_stride + c];
+            }
+            __syncthreads();
+        }
+        if (tid < nitems) {
+            // the item's rows: in LDS, or (rows beyond the LDS budget) its own rows in memory
+            const T* row = staged ? lds + tid * p.lds_stride : p.arg + (item0 + tid) * p.arg_stride;
+            const T* g = staged ? lds + tid * p.lds_stride + p.arg_len : p.cot + (item0 + tid) * p.cot_stride;
+            const T* B = row + p.arg_k;
+            const T* gk = g + (p.g_k >= 0 ? p.g_k : 0);   // (m_g == 0 when absent: never read)
+            const ExpLogAdjScalars<T> q = exp_log_adj_scalars<T, OP>(p, B, gk, p.arg_0 >= 0 ? row[p.arg_0] : T(0), p.g_0 >= 0 ? g[p.g_0] : T(0));
+            if (staged) {   // dB over B, da over a: written out below
+                T* Bw = lds + tid * p.lds_stride + p.arg_k;
+                for (int i = 0; i < p.m_res; ++i) Bw[i] = (i < p.m_g ? q.f * gk[i] : T(0)) + p.sq[i] * Bw[i] * q.w;
+                if (p.arg_0 >= 0) lds[tid * p.lds_stride + p.arg_0] = q.da;
+            } else {
+                T* r = p.res + (item0 + tid) * p.res_stride;
+                for (int i = 0; i < p.m_res; ++i) r[p.res_k + i] = r[p.res_k + i] + ((i < p.m_g ? q.f * gk[i] : T(0)) + p.sq[i] * B[i] * q.w);
+                if (p.res_0 >= 0) r[p.res_0] = r[p.res_0] + q.da;
+            }
+        }
+        if (staged) {
+            __syncthreads();
+            // res += : consecutive threads on consecutive elements
+            for (int i = tid; i < nitems * p.m_res; i += nthr) {
+                const int it = i / p.m_res, c = i - it * p.m_res;
+                T* r = p.res + (item0 + it) * p.res_stride + p.res_k + c;
+                *r = *r + lds[it * p.lds_stride + p.arg_k + c];
+            }
+            if (p.res_0 >= 0)
+                for (int it = tid; it < nitems; it += nthr) {
+                    T* r = p.res + (item0 + it) * p.res_stride + p.res_0;
+                    *r = *r + lds[it * p.lds_stride + p.arg_0];
+                }
+            __syncthreads();   // the rows are rewritten for the next group
+        }
     }
 }
 

@@ -207,6 +207,8 @@ struct Lowering {
             }
             fail(GAAST_ERR_UNIMPLEMENTED, "Exponential / Logarithm evaluation is todo!() in the reference");
             return;
+        case GAAST_OP_EXP_ADJ:
+        case GAAST_OP_LOG_ADJ: lower_exp_log_adj(res, id); return;
         case GAAST_OP_PRODUCT: lower_product(res, id); return;
         default: throw std::runtime_error("unknown opcode");
         }
@@ -311,6 +313,92 @@ struct Lowering {
         s.name = keep_name;
         s.a = arg;
         plan.has_explog = 1;
+        touch(res);
+    }
+
+    // Reverse mode of the extension (GAAST_OP_EXP_ADJ / GAAST_OP_LOG_ADJ, gaast_hip.h): res += the cotangent of the exp / log
+    // operand.  Both children are cached like product operands -- child1 is the very operand buffer of the forward node when the
+    // program re-evaluates it -- and the checks are lower_exp_log's.  No domain check: the forward made it.
+    void lower_exp_log_adj(BufRef res, int id) {
+        const gaast_node_desc& nd = node(id);
+        const bool is_exp = nd.opcode == GAAST_OP_EXP_ADJ;
+        if (!(plan.flags & GAAST_FLAG_EXP_LOG)) {   // refused whole at program_create, like every program beyond this back end
+            if (plan.unsupported.empty()) plan.unsupported = "exp / log adjoint nodes need GAAST_FLAG_EXP_LOG";
+            return;
+        }
+        const gaast_node_desc& ch = node(nd.child1);
+        BufRef arg = store_in_cache(nd.child1);
+        if (!ok()) return;
+        BufRef cot = store_in_cache(nd.child0);
+        if (!ok()) return;
+        if (key(arg) == key(res) || key(cot) == key(res)) {
+            fail(GAAST_ERR_MISSING_GRADE, "exp / log adjoint operand aliases its own result buffer");
+            return;
+        }
+        int k = -1, nk = 0;
+        for (int g = 0; g < 64; ++g) nk += int((ch.minimal_grade_mask >> g) & 1ULL);
+        for (int g = 0; g < 64; ++g)
+            if (((ch.minimal_grade_mask >> g) & 1ULL) && (g != 0 || (is_exp && nk == 1))) k = g;
+        if (k < 0) {
+            fail(GAAST_ERR_INVALID_PROGRAM, "log can only be used on multivectors of the form <A>_0 + <A>_k");
+            return;
+        }
+        if (k == 0) {
+            if (plan.unsupported.empty()) plan.unsupported = "exp of a bare scalar has no adjoint node";
+            return;
+        }
+        const Layout &la = layout(arg), &lg = layout(cot), &lr = layout(res);
+        if (!((la.mask >> k) & 1ULL)) {
+            fail(GAAST_ERR_MISSING_GRADE, "grade absent from exp / log operand");
+            return;
+        }
+        if (ch.vec_space_dim != d.vec_space_dim || lg.dim != d.vec_space_dim) {
+            fail(GAAST_ERR_INVALID_PROGRAM, "exp / log adjoint operand lives in another vector space than the algebra");
+            return;
+        }
+        const int64_t m = la.grade_len(k);
+        Step st;   // filled before emit(): emit invalidates references into plan.steps
+        st.adj.op = is_exp ? 0 : 1;
+        st.adj.m = int(m);
+        st.adj.arg_k = int(la.offset(k));
+        st.adj.arg_0 = (!is_exp && (la.mask & 1ULL) && la.grade_len(0) > 0) ? int(la.offset(0)) : -1;
+        if ((lg.mask >> k) & 1ULL) {
+            st.adj.g_k = int(lg.offset(k));
+            st.adj.mg = int(std::min<int64_t>(lg.grade_len(k), m));
+        }
+        if (is_exp && (lg.mask & 1ULL) && lg.grade_len(0) > 0) st.adj.g_0 = int(lg.offset(0));
+        const uint64_t mine = nd.minimal_grade_mask;
+        if ((mine >> k) & 1ULL) {
+            if (!((lr.mask >> k) & 1ULL)) {
+                fail(GAAST_ERR_MISSING_GRADE, "grade " + std::to_string(k) + " absent from result buffer");
+                return;
+            }
+            st.adj.res_k = int(lr.offset(k));
+            st.adj.mres = int(std::min<int64_t>(lr.grade_len(k), m));
+        }
+        if (st.adj.arg_0 >= 0 && (mine & 1ULL)) {
+            if (!(lr.mask & 1ULL)) {
+                fail(GAAST_ERR_MISSING_GRADE, "grade 0 absent from result buffer");
+                return;
+            }
+            st.adj.res_0 = int(lr.offset(0));
+        }
+        st.adj.sq.resize(size_t(m));
+        for (int64_t i = 0; i < m; ++i) {
+            const uint32_t blade = bt.blade_of[size_t(k)][size_t(i)];
+            st.adj.sq[size_t(i)] = blades_gp_coeff(d.vec_space_dim, d.metric_diag, blade, blade);
+        }
+        Step& s = emit(Step::EXPLOG_ADJ, res, std::string(is_exp ? "exponential_adjoint" : "logarithm_adjoint") + "[grade " + std::to_string(k) + ", " +
+                                                  std::to_string(m) + " components]");
+        const BufRef keep_res = s.res;
+        const std::string keep_name = s.name;
+        s = std::move(st);
+        s.kind = Step::EXPLOG_ADJ;
+        s.res = keep_res;
+        s.name = keep_name;
+        s.a = arg;
+        s.b = cot;
+        plan.has_explog_adj = 1;
         touch(res);
     }
 
@@ -1703,6 +1791,8 @@ void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab)
             break;
         case GAAST_OP_ADD:
         case GAAST_OP_PRODUCT:
+        case GAAST_OP_EXP_ADJ:
+        case GAAST_OP_LOG_ADJ:
             if (!child_ok(nd.child0) || !child_ok(nd.child1)) throw std::runtime_error("nodes are not in post-order");
             if (nd.opcode == GAAST_OP_PRODUCT && nd.product_kind >= GAAST_PROD_ADJ_LEFT) {
                 const int adj = nd.product_kind & ~7, base = nd.product_kind & 7;

@@ -7,6 +7,7 @@
 
 #include "../common/algebra.hpp"
 #include "../common/comp_mul_table.hpp"
+#include "explog_adj_series.hip.hpp"
 #include "gaast_hip.h"
 
 namespace gaast {
@@ -51,8 +52,8 @@ enum class DenseFamily {
 // a step in place), each table and setting named after the one thing it holds.  The groups of the other kinds stay empty.  The
 // tables are host images, uploaded once at program_create.
 struct Step {
-    enum Kind { ZERO, AXPY, FLIP, SUNARY, PRODUCT_CSR, PRODUCT_DENSE, FUSED, EXPLOG, REDUCE_SCALE, ELEMENTWISE, LINMAP } kind = ZERO;
-    BufRef res, a, b;        // result; operand rows (PRODUCT_*: left, right; AXPY / EXPLOG / LINMAP: a; REDUCE_SCALE: the reduction's; ELEMENTWISE: b = the scalar)
+    enum Kind { ZERO, AXPY, FLIP, SUNARY, PRODUCT_CSR, PRODUCT_DENSE, FUSED, EXPLOG, REDUCE_SCALE, ELEMENTWISE, LINMAP, EXPLOG_ADJ } kind = ZERO;
+    BufRef res, a, b;        // result; operand rows (PRODUCT_*: left, right; AXPY / EXPLOG / LINMAP: a; EXPLOG_ADJ: a = the forward operand, b = the cotangent; REDUCE_SCALE: the reduction's; ELEMENTWISE: b = the scalar)
     std::string name;
     int canon_a = 0, canon_b = 0;   // the operand is a bound input read in place: the kernel applies the reference's 0.0 + x
     int beta = 1;                   // 0: the zero fill of a fresh result is folded in
@@ -174,6 +175,19 @@ struct Step {
         std::vector<double> pair_coeff;           // 2 e_i e_j
     } explog;
 
+    // EXPLOG_ADJ (GAAST_OP_EXP_ADJ / GAAST_OP_LOG_ADJ, gaast_hip.h): res += the cotangent of the exp / log operand, from the operand
+    // row `a` (the k-vector B; log: + grade 0) and the row `b` holding the cotangent g of the forward result
+    struct ExpLogAdj {
+        int op = 0;                // 0 exp, 1 log
+        int m = 0;                 // components of the k-vector
+        int arg_k = 0, arg_0 = -1; // offsets in the operand row (grade k; grade 0 for log, -1 = absent)
+        int g_k = -1, g_0 = -1;    // offsets in the cotangent row (grade k; exp: grade 0), -1 = absent (reads as 0)
+        int mg = 0;                // grade-k components the cotangent row holds (zip with m): the ones the forward wrote
+        int res_k = -1, res_0 = -1;// offsets in the result row (dB; log: da), -1 = not produced
+        int mres = 0;              // grade-k components of dB that res holds (zip)
+        std::vector<double> sq;    // e_i e_i (blade squares, component order)
+    } adj;
+
     // REDUCE_SCALE (plan.cpp: fuse_reduce_scale): a product whose result is ONE scalar component (a single long row: norm_sq), an
     // optional ScalarUnaryOp on it, and a product of one-term rows that multiplies another row by that scalar -- the versor inverse
     // a.rev() * a.norm_sq().sinv() and normalisations, where the rows no longer fit a fused slab (n >= 9) -- in ONE launch, one wave per
@@ -249,6 +263,7 @@ struct Plan {
     int error = GAAST_OK;              // what the reference would have panicked with, at eval
     std::string error_msg;
     int has_explog = 0;                // some step evaluates exp / log: the program owns a domain-error counter
+    int has_explog_adj = 0;            // some step is an exp / log adjoint (no interpreter micro-ops, no domain check)
     std::string unsupported;           // non-empty: valid in the reference, beyond this back end (program_create fails)
     std::vector<char> slot_used;       // input slots some launch reads (the others may stay unbound)
     std::string jit_source_kept;       // GAAST_FLAG_DEBUG_KEEP_JIT_SOURCE

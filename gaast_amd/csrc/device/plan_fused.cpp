@@ -90,13 +90,13 @@ SlabLayout::SlabLayout(const Plan& p, bool small_reg_slab) : plan(p), elem(p.dty
     // the LDS interpreter kernel needs the slabs of 64 items in 48 KiB; the hiprtc-specialised kernel keeps the slab
     // in registers and only needs it to be small enough for that -- plans that fit only the latter are fused
     // "JIT only" (the runtime falls back to an unfused plan if the compilation fails)
-    // (plans with exp / log steps have no interpreter micro-ops: the specialised kernel or nothing)
+    // (plans with exp / log steps or their adjoints have no interpreter micro-ops: the specialised kernel or nothing)
     // (round 3: 144 KiB instead of 48 -- one 512-thread workgroup per CU -- so that programs whose slab is beyond the registers of
     //  the specialised kernel but whose lists are short still run as ONE launch: the projected sandwich (R X ~R).g(1) at n = 7, 8
     //  has two lists of n 2^(n-1) entries over a slab of 2^n + 2 n elements; as two list launches it ran 8 active lanes per item)
     //  -- for plans of SEVERAL steps only: a single big list is better off on k_product_ell (twice the terms per second)
     const size_t interp_budget = plan.steps.size() >= 2 ? kInterpLdsBytes : size_t(48 * 1024);
-    interp_ok = !(slab > 4095 || size_t(slab) * elem > 32767 || size_t(slab) * elem * 64 > interp_budget) && !plan.has_explog;
+    interp_ok = !(slab > 4095 || size_t(slab) * elem > 32767 || size_t(slab) * elem * 64 > interp_budget) && !plan.has_explog && !plan.has_explog_adj;
     // One item per thread, the slab in registers: up to 160 (f64) / 200 (f32) elements always; up to 256 / 320 ON TRIAL -- the
     // compiler keeps only the LIVE values in registers, the projection (v & bv) & bv.vinv() at n = 12 (slab 171) compiles to 222
     // registers and runs at 0.75 of the HBM roof against 0.44 with its slabs in LDS, the versor inverse at n = 8 (slab 259: the
@@ -207,6 +207,7 @@ bool encode_uops(const SlabLayout& lay, Step::Fused& f, uint64_t& entries) {
             break;
         }
         case Step::EXPLOG: break;   // specialised kernel only (interp_ok is false)
+        case Step::EXPLOG_ADJ: break;
         default: return false;
         }
         const size_t per = std::max<size_t>(1, std::min<size_t>(30, (misc.size() + G - 1) / G));
@@ -299,6 +300,53 @@ std::string explog_statements(const SlabLayout& lay, const Step& s, const StmtSt
     return src + in1 + "}\n";
 }
 
+// exp / log adjoint (gaast_hip.h: GAAST_OP_EXP_ADJ / GAAST_OP_LOG_ADJ): the statements of k_exp_log_adj, in its order
+std::string explog_adj_statements(const SlabLayout& lay, const Step& s, const StmtStyle& st, const CodeText& ct) {
+    const Step::ExpLogAdj& q = s.adj;
+    const uint32_t rb = uint32_t(lay.base_of(s.res)), ab = uint32_t(lay.base_of(s.a)), gb = uint32_t(lay.base_of(s.b));
+    const std::string in1 = st.indent, in2 = in1 + "  ", in3 = in2 + "  ";
+    auto B = [&](int i) { return st.el(ab + uint32_t(q.arg_k) + uint32_t(i)); };
+    auto G = [&](int i) { return st.el(gb + uint32_t(q.g_k) + uint32_t(i)); };
+    auto horner = [&](const std::string& x, int terms, double (*coeff)(int)) {
+        std::string t = in3 + "h = T(" + ct.lit(coeff(terms)) + ");\n";
+        for (int n = terms - 1; n >= 1; --n) t += in3 + "h = h * " + x + " + T(" + ct.lit(coeff(n)) + ");\n";
+        return t;
+    };
+    std::string src = in1 + "{ T sq = T(0), dd = T(0);\n";
+    for (int i = 0; i < q.m; ++i) src += in2 + "sq = sq + " + B(i) + " * " + B(i) + " * T(" + ct.lit(q.sq[size_t(i)]) + ");\n";
+    for (int i = 0; i < q.mg; ++i) src += in2 + "dd = dd + " + G(i) + " * " + B(i) + ";\n";
+    src += in2 + (q.op == 0 ? "T c0 = T(0), f, h, w;\n" : "T f, h, w;\n");
+    if (q.op == 0) {
+        src += in2 + "if (sq < T(0)) { const T t = " + ct.fn("sqrt") + "(-sq); c0 = " + ct.fn("cos") + "(t); f = " + ct.fn("sin") + "(t) / t; }\n";
+        src += in2 + "else if (sq > T(0)) { const T t = " + ct.fn("sqrt") + "(sq); c0 = " + ct.fn("cosh") + "(t); f = " + ct.fn("sinh") + "(t) / t; }\n";
+        src += in2 + "else if (sq == T(0)) { c0 = T(1); f = T(1); }\n" + in2 + "else { c0 = sq; f = sq; }\n";
+        src += in2 + "if (sq < T(" + ct.lit(kExpAdjSeriesBelow) + ") && sq > T(" + ct.lit(-kExpAdjSeriesBelow) + ")) {\n" +
+               horner("sq", exp_adj_series_terms(ct.f32), exp_adj_series_coeff) + in2 + "} else h = (c0 - f) / sq;\n";
+        src += in2 + "w = f * " + (q.g_0 >= 0 ? st.el(gb + uint32_t(q.g_0)) : std::string("T(0)")) + " + h * dd;\n";
+    } else {
+        const std::string a = q.arg_0 >= 0 ? st.el(ab + uint32_t(q.arg_0)) : std::string("T(0)");
+        src += in2 + "const T a = " + a + ";\n";
+        src += in2 + "if (sq < T(0)) { const T mm = " + ct.fn("sqrt") + "(-sq); f = " + ct.fn("atan2") + "(mm, a) / mm; }\n";
+        src += in2 + "else if (sq > T(0)) { const T mm = " + ct.fn("sqrt") + "(sq); f = " + ct.fn("atanh") + "(mm / a) / mm; }\n";
+        src += in2 + "else if (sq == T(0)) { f = T(1) / a; }\n" + in2 + "else { f = sq; }\n";
+        src += in2 + "const T a2 = a * a, D = a2 - sq, lim = T(" + ct.lit(kLogAdjSeriesBelow) + ") * a2;\n";
+        src += in2 + "if (sq == T(0) || (sq < lim && sq > -lim && (a > T(0) || sq > T(0)))) {\n" + in3 + "const T u = sq / a2;\n" +
+               horner("u", log_adj_series_terms(ct.f32), log_adj_series_coeff) + in3 + "h = h / (a2 * a);\n" + in2 + "} else h = (a / D - f) / sq;\n";
+        src += in2 + "w = h * dd;\n";
+    }
+    if (q.res_k >= 0)
+        for (int i = 0; i < q.mres; ++i) {
+            const std::string d = st.el(rb + uint32_t(q.res_k) + uint32_t(i));
+            const std::string second = "T(" + ct.lit(q.sq[size_t(i)]) + ") * " + B(i) + " * w";
+            src += in2 + d + " = " + d + " + (" + (i < q.mg ? "f * " + G(i) + " + " : std::string()) + second + ");\n";
+        }
+    if (q.op == 1 && q.res_0 >= 0) {
+        const std::string d = st.el(rb + uint32_t(q.res_0));
+        src += in2 + d + " = " + d + " + (-(dd / D));\n";
+    }
+    return src + in1 + "}\n";
+}
+
 // THE translation of a step into the reference's statements in the reference's order: per result row of a list
 // acc = d; acc = acc +- (l * r)[ * c]; d = acc, one piece per row; the element-wise arms, `chunk` statements per piece.
 void step_statements(const SlabLayout& lay, const Step& s, const StmtStyle& st, const CodeText& ct, const StmtSink& sink) {
@@ -323,6 +371,7 @@ void step_statements(const SlabLayout& lay, const Step& s, const StmtStyle& st, 
         break;
     }
     case Step::EXPLOG: sink(0, explog_statements(lay, s, st, ct)); break;
+    case Step::EXPLOG_ADJ: sink(0, explog_adj_statements(lay, s, st, ct)); break;
     case Step::PRODUCT_CSR: {
         const uint32_t lb = uint32_t(lay.base_of(s.a, s.canon_a)), rrb = uint32_t(lay.base_of(s.b, s.canon_b));
         for (size_t row = 0; row + 1 < s.list.row_start.size(); ++row) {
@@ -737,7 +786,7 @@ bool try_fuse(Plan& plan, bool small_reg_slab) {
     // exp / log steps (no interpreter micro-ops, plan.has_explog) exist in the register form only: it or nothing
     if (lay.jit_allowed && entries <= 8192)
         emit_register_form(lay, f);
-    else if (!(plan.flags & GAAST_FLAG_NO_JIT) && lay.interp_ok && !plan.has_explog && entries <= 2048 && size_t(lay.slab | 1) * lay.elem * 64 + 64 <= kLdsBytes)
+    else if (!(plan.flags & GAAST_FLAG_NO_JIT) && lay.interp_ok && !plan.has_explog && !plan.has_explog_adj && entries <= 2048 && size_t(lay.slab | 1) * lay.elem * 64 + 64 <= kLdsBytes)
         emit_lds_form(lay, f);
     f.fused.slab = lay.slab;
     f.fused.zero_slot = lay.zero_slot;

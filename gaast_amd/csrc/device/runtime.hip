@@ -219,6 +219,7 @@ struct Launch {
     struct { DevTable ent1, pos1, ent2, out2; } cj;
     struct { DevTable prog, phase_tab; std::vector<double> general; } fused;   // (general: passed by value)
     struct { DevTable sq, row_start, pairs, pair_coeff; } explog;
+    struct { DevTable sq; } adj;
     struct { DevTable ent1, coeff1, ent2, coeff2, sign_words; } reduce;
     struct { DevTable ops, comp_off, out_off, coeff; } ew;
     void* domain = nullptr;            // the program's domain-error counter (borrowed)
@@ -650,6 +651,18 @@ int prepare_step(Launch& L, const Layout& la, const Layout& lb, std::string& ker
     case Step::AXPY: kernel = "k_axpy_map<" + tn + ">"; return GAAST_OK;
     case Step::FLIP: kernel = "k_flip<" + tn + ">"; return GAAST_OK;
     case Step::SUNARY: kernel = "k_scalar_unary<" + tn + ">"; return GAAST_OK;
+    case Step::EXPLOG_ADJ: {
+        // the rows of a workgroup's items through LDS whenever at least a wave's worth of items fits 64 KiB (no attribute to raise,
+        // several workgroups per CU); an item's rows `stride` elements apart, odd.  Otherwise the direct form (max_items = 0).
+        const size_t stride = size_t(la.row_len + lb.row_len) | 1;
+        const size_t fit = (64 * 1024) / (stride * sizeof(T));
+        L.threads = 256;
+        L.max_items = fit >= 256 ? 256 : int(fit / 64 * 64);
+        L.lds = stride * sizeof(T);   // per staged item
+        L.kern[0] = s.adj.op == 0 ? reinterpret_cast<const void*>(&k_exp_log_adj<T, 0>) : reinterpret_cast<const void*>(&k_exp_log_adj<T, 1>);
+        kernel = "k_exp_log_adj<" + tn + "," + std::to_string(s.adj.op) + ">" + (L.max_items ? "[" + std::to_string(L.max_items) + " items through LDS]" : "[direct rows]");
+        return GAAST_OK;
+    }
     case Step::REDUCE_SCALE: {
         L.threads = 256;
         L.kern[0] = reinterpret_cast<const void*>(&k_reduce_scale<T>);
@@ -776,6 +789,35 @@ int run_step(const Launch& L, const Bound& res, const Bound& a, const Bound& b, 
         q.dom = static_cast<unsigned long long*>(L.domain);
         q.batch = batch;
         hipLaunchKernelGGL(k_exp_log<T>, dim3(grid_for(batch, 256)), dim3(256), 0, g_stream, q);
+        break;
+    }
+    case Step::EXPLOG_ADJ: {
+        ExpLogAdjArgs<T> q;
+        q.res = static_cast<T*>(res.ptr);
+        q.arg = static_cast<const T*>(a.ptr);
+        q.cot = static_cast<const T*>(b.ptr);
+        q.res_stride = res.stride;
+        q.arg_stride = a.stride;
+        q.cot_stride = b.stride;
+        q.m = s.adj.m;
+        q.m_g = s.adj.mg;
+        q.m_res = s.adj.res_k >= 0 ? s.adj.mres : 0;
+        q.arg_k = s.adj.arg_k;
+        q.arg_0 = s.adj.arg_0;
+        q.g_k = s.adj.g_k;
+        q.g_0 = s.adj.g_0;
+        q.res_k = s.adj.res_k;
+        q.res_0 = s.adj.res_0;
+        q.arg_len = int(la.row_len);
+        q.cot_len = int(lb.row_len);
+        q.items = L.max_items;
+        q.lds_stride = int(L.lds / sizeof(T));
+        q.sq = L.adj.sq.as<T>();
+        q.batch = batch;
+        using KernA = void (*)(ExpLogAdjArgs<T>);
+        const int64_t groups = (batch + (q.items ? q.items : 256) - 1) / (q.items ? q.items : 256);
+        hipLaunchKernelGGL(reinterpret_cast<KernA>(const_cast<void*>(L.kern[0])), dim3(unsigned(std::min<int64_t>(groups, int64_t(g_num_cu) * 8))),
+                           dim3(256), L.lds * size_t(q.items), g_stream, q);
         break;
     }
     case Step::PRODUCT_CSR: {
@@ -1288,7 +1330,7 @@ bool compile_fused(gaast_hip_program_s& prog, uint32_t flags, uint32_t* rebuild_
         }
         // tolerance mode, one item per thread, and arithmetic-bound at least when every operand is shared by all items: the
         // contracted variant too (run_jit picks per launch, by the operands bound)
-        if (L.jit && !trial_failed && !(flags & GAAST_FLAG_EXACT_ORDER) && !s.fused.jit_items && !prog.plan.has_explog &&
+        if (L.jit && !trial_failed && !(flags & GAAST_FLAG_EXACT_ORDER) && !s.fused.jit_items && !prog.plan.has_explog && !prog.plan.has_explog_adj &&
             arithmetic_bound(s.n_entries, double(prog.plan.out_layout.row_len) * dtype_size(prog.plan.dtype))) {
             std::string log2;
             L.jit_fma = jit_compile(s.fused.jit_source, "gaast_jit", &log2, flags, true);
@@ -1382,6 +1424,7 @@ int prepare_launch(Launch& L, const gaast_hip_program_s& prog) {
     idx(L.fused.prog, s.fused.prog); idx(L.fused.phase_tab, s.fused.phase_tab);
     L.fused.general = std::move(s.fused.general);
     val(L.explog.sq, s.explog.sq); idx(L.explog.row_start, s.explog.row_start); idx(L.explog.pairs, s.explog.pairs); val(L.explog.pair_coeff, s.explog.pair_coeff);
+    val(L.adj.sq, s.adj.sq);
     idx(L.reduce.ent1, s.reduce.ent1); val(L.reduce.coeff1, s.reduce.coeff1); idx(L.reduce.ent2, s.reduce.ent2); val(L.reduce.coeff2, s.reduce.coeff2);
     idx(L.reduce.sign_words, s.reduce.sign_words);
     idx(L.ew.ops, s.ew.ops); idx(L.ew.comp_off, s.ew.comp_off); idx(L.ew.out_off, s.ew.out_off); val(L.ew.coeff, s.ew.coeff);

@@ -9,7 +9,10 @@
 //   product     transposed list -> cotangent of the operand buffers (explicit stays explicit, compact -> GAAST_PROD_ADJ_*);
 //   flip        the same flip of the cotangent (kept as a per-grade sign and folded into the next list's coefficients);
 //   SINV        t = 1/s: ds = -g t t;  SSQRT r = sqrt(s): ds = 0.5 g sinv(r) -- t and r are the buffer's grade 0 right after
-//               the op, recomputed by a node that replays the buffer's events up to it.
+//               the op, recomputed by a node that replays the buffer's events up to it;
+//   exp / log   (GAAST_FLAG_EXP_LOG | GAAST_FLAG_EXP_LOG_GRAD) the operand has a buffer of its own, like a product operand
+//               (plan.cpp: lower_exp_log -> store_in_cache): a one-operand product event -- GAAST_OP_EXP_ADJ / GAAST_OP_LOG_ADJ over
+//               the buffer's cotangent restricted to the node's grades and the forward operand -> cotangent of the operand buffer.
 // Buffers are visited from the root down (decreasing node index: a buffer's users come after it in post-order).  The adjoint
 // program is evaluated in place as well, so every cotangent node it builds is ADDITIVE (input, product, or sums of them): adding
 // it into a buffer adds its value.  Sign changes and projections of a cotangent that cannot be folded into a list are explicit
@@ -34,6 +37,10 @@ struct VjpError {
     int status;
     std::string msg;
 };
+
+bool has_two_children(int opcode) {
+    return opcode == GAAST_OP_ADD || opcode == GAAST_OP_PRODUCT || opcode == GAAST_OP_EXP_ADJ || opcode == GAAST_OP_LOG_ADJ;
+}
 
 enum EventKind { EV_INPUT, EV_PRODUCT, EV_FLIP, EV_SCALAR, EV_OPAQUE };
 struct Event {
@@ -161,6 +168,23 @@ struct Builder {
             return;
         default: ev.push_back({EV_OPAQUE, x, path}); return;  // exp / log
         }
+    }
+    // exp / log: cotangent of the operand's buffer (gaast_hip.h: GAAST_OP_EXP_ADJ / GAAST_OP_LOG_ADJ)
+    void explog_adjoint(int x, const std::vector<Term>& terms, std::vector<std::vector<Term>>& cot) {
+        const gaast_node_desc& xd = d.nodes[x];
+        const int c = xd.child0;
+        if ((d.flags & (GAAST_FLAG_EXP_LOG | GAAST_FLAG_EXP_LOG_GRAD)) != (GAAST_FLAG_EXP_LOG | GAAST_FLAG_EXP_LOG_GRAD))
+            throw VjpError{GAAST_ERR_UNIMPLEMENTED, "exp / log on the path to the differentiated input has no adjoint"};
+        if (!dep[size_t(c)]) return;
+        const uint64_t cmask = d.nodes[c].minimal_grade_mask;
+        if (xd.opcode == GAAST_OP_EXP && cmask == 1ULL)
+            throw VjpError{GAAST_ERR_UNIMPLEMENTED, "exp of a bare scalar on the path to the differentiated input has no adjoint"};
+        const int g = materialize(terms, xd.minimal_grade_mask);
+        if (g < 0) return;
+        gaast_node_desc nd = blank(xd.opcode == GAAST_OP_EXP ? GAAST_OP_EXP_ADJ : GAAST_OP_LOG_ADJ, cmask, n);
+        nd.child0 = g;
+        nd.child1 = c;
+        cot[size_t(c)].push_back(Term{add(nd), 0, ~0ULL});
     }
     static uint64_t flip_set(const gaast_node_desc& nd) {
         const uint64_t gs = nd.minimal_grade_mask;
@@ -313,8 +337,7 @@ struct Builder {
                     break;
                 }
                 case EV_SCALAR: scalar_adjoint(s, e, terms); break;
-                case EV_OPAQUE:
-                    throw VjpError{GAAST_ERR_UNIMPLEMENTED, "exp / log on the path to the differentiated input has no adjoint"};
+                case EV_OPAQUE: explog_adjoint(e.node, terms, cot); break;
                 }
             }
         }
@@ -388,14 +411,14 @@ extern "C" int gaast_program_vjp(const gaast_program_desc* desc, int32_t wrt_slo
             if (!keep[i]) continue;
             const gaast_node_desc& nd = b.nodes[i];
             if (nd.child0 >= 0) keep[size_t(nd.child0)] = 1;
-            if (nd.child1 >= 0 && (nd.opcode == GAAST_OP_ADD || nd.opcode == GAAST_OP_PRODUCT)) keep[size_t(nd.child1)] = 1;
+            if (nd.child1 >= 0 && has_two_children(nd.opcode)) keep[size_t(nd.child1)] = 1;
         }
         std::vector<gaast_node_desc> nodes;
         for (size_t i = 0; i < b.nodes.size(); ++i) {
             if (!keep[i]) continue;
             gaast_node_desc nd = b.nodes[i];
             if (nd.child0 >= 0) nd.child0 = remap[size_t(nd.child0)];
-            if (nd.child1 >= 0) nd.child1 = (nd.opcode == GAAST_OP_ADD || nd.opcode == GAAST_OP_PRODUCT) ? remap[size_t(nd.child1)] : -1;
+            if (nd.child1 >= 0) nd.child1 = has_two_children(nd.opcode) ? remap[size_t(nd.child1)] : -1;
             if (nd.opcode == GAAST_OP_PRODUCT && i >= size_t(d.n_nodes) && nd.product_kind == GAAST_PROD_EXPLICIT)
                 nd.comp_muls = b.lists[i].data();
             remap[i] = int(nodes.size());

@@ -146,7 +146,10 @@ void gaast_program_image_free(gaast_program_image_t img);
  * product (product_kind GAAST_PROD_GEOMETRIC) at n >= 6 whatever its form, a compact GAAST_PROD_ADJ_LEFT / GAAST_PROD_ADJ_RIGHT node,
  * which the dense kernels evaluate where they take the forward product.  The adjoint program inherits desc->flags.
  * Errors: GAAST_ERR_INVALID_ARGUMENT for a wrt_slot out of range or const, or n_inputs + 1 > GAAST_MAX_INPUTS;
- * GAAST_ERR_UNIMPLEMENTED for exp / log on the path to wrt_slot, or GAAST_FLAG_SPINOR_GEMM;
+ * GAAST_ERR_UNIMPLEMENTED for GAAST_FLAG_SPINOR_GEMM, and for exp / log on the path to wrt_slot unless desc->flags holds both
+ * GAAST_FLAG_EXP_LOG and GAAST_FLAG_EXP_LOG_GRAD: then the operand's cotangent is a GAAST_OP_EXP_ADJ / GAAST_OP_LOG_ADJ node
+ * (gaast_hip.h) over the cotangent of the exp / log node's buffer and the forward operand (exp of a bare scalar, grade set {0},
+ * stays GAAST_ERR_UNIMPLEMENTED);
  * GAAST_ERR_INVALID_PROGRAM for a malformed desc.  The message is in gaast_expr_last_error(). */
 int gaast_program_vjp(const gaast_program_desc *desc, int32_t wrt_slot, gaast_program_image_t *out);
 

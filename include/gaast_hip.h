@@ -76,7 +76,24 @@ typedef enum gaast_opcode {
     GAAST_OP_REVERSE = 7,/* Reverse */
     GAAST_OP_GINVOL = 8, /* GradeInvolution */
     GAAST_OP_SINV = 9,   /* ScalarUnaryOp(Inversion) */
-    GAAST_OP_SSQRT = 10  /* ScalarUnaryOp(SquareRoot) */
+    GAAST_OP_SSQRT = 10, /* ScalarUnaryOp(SquareRoot) */
+    /* Reverse mode of Exponential / Logarithm (no reference counterpart; gaast_program_vjp under GAAST_FLAG_EXP_LOG_GRAD emits
+     * them, GAAST_FLAG_EXP_LOG evaluates them -- without that flag gaast_hip_program_create refuses a program that holds one:
+     * GAAST_ERR_UNIMPLEMENTED).  They follow the pattern of GAAST_PROD_ADJ_*: child0 is the cotangent g of the forward node's
+     * result (a node whose minimal grade mask lies within the forward node's: grade 0 and / or grade k), child1 the forward
+     * operand, and the node's own minimal grade mask that of the operand (EXP_ADJ: {k}; LOG_ADJ: {0, k} or {k}).  Both nodes
+     * ADD into the buffer that contains them, like every arm of eval.rs.  With sigma_i = e_i e_i, s = sum sigma_i B_i^2,
+     * d = sum_i g_k[i] B_i over the grade-k components g holds, g_0 the scalar of g (0 when absent), and c0, f exactly as the
+     * forward computes them (its s == 0 and NaN branches included):
+     *   EXP_ADJ  dB_i = f g_k[i] + sigma_i B_i (f g_0 + h d),  h = (c0 - f) / s         (-> 1/3 at s = 0)
+     *   LOG_ADJ  dB_i = f g_k[i] + sigma_i B_i h d,            h = (a / D - f) / s,  D = a^2 - s   (-> 2 / (3 a^3) at s = 0)
+     *            da   = -d / D                                  (only when the operand holds grade 0)
+     * h is summed from its series in s where the quotient cancels (DESIGN.md section 11 has the thresholds).  The adjoint does
+     * NOT repeat the forward's domain check and never touches the domain-error counter; a VJP program that re-evaluates a
+     * forward exp / log (because it needs its value, e.g. R in the sandwich R X ~R) counts there like any forward program.
+     * Exp of a bare scalar (k = 0, raw ABI only) has no adjoint node: GAAST_ERR_UNIMPLEMENTED. */
+    GAAST_OP_EXP_ADJ = 11,
+    GAAST_OP_LOG_ADJ = 12
 } gaast_opcode;
 
 /* the five products of src/ast/expr.rs:180-197, for compact PRODUCT descriptors */
@@ -161,6 +178,11 @@ typedef struct gaast_input_desc {
  * semantics the grade rules imply (grade_set.rs:181-197), see DESIGN.md.  Without the flag such programs report
  * GAAST_ERR_UNIMPLEMENTED exactly where the reference panics. */
 #define GAAST_FLAG_EXP_LOG 0x100u
+/* OPT-IN, only meaningful together with GAAST_FLAG_EXP_LOG: reverse mode differentiates THROUGH Exponential / Logarithm
+ * (gaast_program_vjp emits GAAST_OP_EXP_ADJ / GAAST_OP_LOG_ADJ nodes).  Without it -- GAAST_FLAG_EXP_LOG alone -- an exp / log
+ * on the path to the differentiated input stays GAAST_ERR_UNIMPLEMENTED, and every status, plan, launch name and bit of a
+ * program is what it was before the flag existed.  The flag changes nothing in a forward program. */
+#define GAAST_FLAG_EXP_LOG_GRAD 0x2000u
 #define GAAST_FLAG_DEBUG_LDS_12K 0x400u /* hiprtc-specialised kernels: 12 KiB instead of 10 KiB of LDS per wave for the row transposition (A/B testing) */
 #define GAAST_FLAG_DEBUG_NO_CHAIN 0x800u /* a sparse product that only feeds a dense product stays a launch of its own (default: evaluated in the dense kernel's LDS staging; A/B testing) */
 /* (bits 30 and 31 are reserved and ignored) */
@@ -374,7 +396,8 @@ int gaast_hip_eval_gather(gaast_hip_program_t prog, const gaast_hip_mv_t *inputs
  * program and the cotangent (root grade mask, dimension n, one row per item) at slot desc->n_inputs; gaast_hip_eval writes the
  * gradient rows of input `wrt_slot` (its grade mask and storage dimension).  Batch-1 inputs are shared as usual; the gradient of a
  * shared input is then one row per item, to be summed with gaast_hip_mv_sum_rows.  Programs created with
- * GAAST_FLAG_SPINOR_GEMM or through gaast_hip_program_create_in_basis have no VJP: GAAST_ERR_UNIMPLEMENTED. */
+ * GAAST_FLAG_SPINOR_GEMM or through gaast_hip_program_create_in_basis have no VJP: GAAST_ERR_UNIMPLEMENTED; so has an exp / log on
+ * the path to `wrt_slot` unless desc->flags holds GAAST_FLAG_EXP_LOG | GAAST_FLAG_EXP_LOG_GRAD. */
 int gaast_hip_program_create_vjp(const gaast_program_desc *desc, int32_t wrt_slot, gaast_hip_program_t *out);
 /* out(0) = sum over the B rows of `in` (out: batch 1, same dimension, grade mask and dtype; B >= 1).  Deterministic: rows are
  * summed in index order within chunks of GAAST_SUM_ROWS_CHUNK rows, then the chunk partials in chunk order, so the bits depend

@@ -21,10 +21,14 @@ pub const OP_REVERSE: i32 = 7;
 pub const OP_GINVOL: i32 = 8;
 pub const OP_SINV: i32 = 9;
 pub const OP_SSQRT: i32 = 10;
+// reverse mode of exp / log (no AstNode counterpart): child0 = cotangent of the forward result, child1 = the forward operand
+pub const OP_EXP_ADJ: i32 = 11;
+pub const OP_LOG_ADJ: i32 = 12;
 
 pub const FLAG_EXACT_ORDER: u32 = 0x4; // bit-exact f64 sums even for dense products
 pub const FLAG_SPINOR_GEMM: u32 = 0x20; // opt-in matrix-representation products (norm-wise error bound)
 pub const FLAG_EXP_LOG: u32 = 0x100; // opt-in extension: evaluate Exponential / Logarithm (todo!() upstream, eval.rs:112-113)
+pub const FLAG_EXP_LOG_GRAD: u32 = 0x2000; // with FLAG_EXP_LOG: gaast_hip_program_create_vjp differentiates through exp / log
 
 #[repr(C)]
 pub struct GaastCompMul {

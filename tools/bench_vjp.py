@@ -1,5 +1,7 @@
 """Reverse mode on the MI355X: the dense adjoints of the R^12 and n = 6 f32 full geometric products against their forward,
-gaast_hip_mv_sum_rows against HBM, and the backward of a PGA3D motor sandwich (both VJPs plus sum_rows) against its forward.
+gaast_hip_mv_sum_rows against HBM, the backward of a PGA3D motor sandwich (both VJPs plus sum_rows) against its forward, and
+rotor_grad: the PGA3D sandwich exp(B) X ~exp(B) differentiated through exp (GAAST_FLAG_EXP_LOG | GAAST_FLAG_EXP_LOG_GRAD) with a
+shared and with a batched generator, plus the stand-alone adjoint kernel k_exp_log_adj against HBM at m = 6 and m = 66 components.
 Prints one JSON line.
 
 Timing as bench.py: inputs resident in HBM, a warm-up, then HIP events on the launch stream around every call.
@@ -80,6 +82,48 @@ def pga_case(stream, steps, warmup, batch=1 << 20):
     return {"batch": batch, "forward_ms": fwd, "backward_ms": bwd, "backward_over_forward": bwd / fwd}
 
 
+def rotor_grad_case(shared, stream, steps, warmup, batch=1 << 20):
+    """PGA3D exp(B) X ~exp(B), f32: forward, backward (both VJPs, + sum_rows when B is shared), launches per backward"""
+    n, metric = 4, [0.0, 1.0, 1.0, 1.0]
+    R = ga.mv(ga.Input(0, [2], n)).exp()
+    spec = (R * ga.mv(ga.Input(1, [3], n)) * R.rev()).g(3).specialize(metric, dtype=ga.F32, flags=ga.FLAG_EXP_LOG | ga.FLAG_EXP_LOG_GRAD)
+    f = spec.torch_fn()
+    b_t = rows(1 if shared else batch, 6).mul_(0.5).requires_grad_()
+    x_t = rows(batch, 4).requires_grad_()
+    y = f(b_t, x_t)
+    gy = torch.ones_like(y)
+    fwd = timed(lambda: f(b_t, x_t), stream, steps, warmup)
+    bwd = timed(lambda: torch.autograd.grad(y, (b_t, x_t), gy, retain_graph=True), stream, steps, warmup)
+    launches = [len(spec.vjp(s).launches()) for s in range(2)]
+    return {"batch": batch, "shared_generator": shared, "forward_ms": fwd, "backward_ms": bwd, "backward_over_forward": bwd / fwd,
+            "forward_launches": len(spec.launches()), "vjp_launches": launches,
+            "launches_per_backward": sum(launches) + (1 if shared else 0)}
+
+
+def exp_adj_kernel_case(n, stream, steps, warmup, batch):
+    """k_exp_log_adj alone on R^n bivectors, f32.  The unfused (NO_FUSION) VJP of exp(B) is the copies of B and g into their cache
+    buffers, the zero fill of the result and the adjoint launch; the two copies are timed as programs of their own (an input as the
+    root: zero fill + add_grades_from over the same rows) and subtracted.  HBM fraction from the rows the kernel moves: B and g
+    read, the gradient row read and written."""
+    m = n * (n - 1) // 2
+    grad = ga.FLAG_EXP_LOG | ga.FLAG_EXP_LOG_GRAD | ga.FLAG_NO_FUSION
+    v = ga.mv(ga.Input(0, [2], n)).exp().specialize(n, dtype=ga.F32, flags=grad).vjp(0)
+    b = ga.DeviceMV.wrap_tensor(rows(batch, m).mul_(0.2), n, [2])
+    g = ga.DeviceMV.wrap_tensor(rows(batch, m + 1), n, [0, 2])
+    o = ga.DeviceMV.wrap_tensor(rows(batch, m), n, [2])
+    o_g = ga.DeviceMV.wrap_tensor(rows(batch, m + 1), n, [0, 2])
+    copy_b = ga.mv(ga.Input(0, [2], n)).specialize(n, dtype=ga.F32, flags=ga.FLAG_NO_FUSION)
+    copy_g = ga.mv(ga.Input(0, [0, 2], n)).specialize(n, dtype=ga.F32, flags=ga.FLAG_NO_FUSION)
+    plan_ms = timed(lambda: v.eval_batch([b], g, batch, out=o), stream, steps, warmup)
+    copies_ms = timed(lambda: copy_b.eval_batch([b], batch, out=o), stream, steps, warmup) + \
+        timed(lambda: copy_g.eval_batch([g], batch, out=o_g), stream, steps, warmup)
+    kernel_ms = plan_ms - copies_ms
+    moved = (m + (m + 1) + 2 * m) * 4.0 * batch
+    return {"n": n, "m": m, "batch": batch, "launches": v.launches(), "copy_launches": copy_b.launches() + copy_g.launches(),
+            "plan_ms": plan_ms, "copies_ms": copies_ms, "kernel_ms": kernel_ms, "kernel_bytes": moved,
+            "kernel_frac_hbm_8TBs": moved / (kernel_ms * 1e-3) / HBM_BPS}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -94,7 +138,11 @@ def main():
            "sum_rows_f32_row16": sum_rows_case(1 << 22, 16, 16, [1], stream, args.steps, args.warmup),
            "sum_rows_f32_row8": sum_rows_case(1 << 23, 8, 8, [1], stream, args.steps, args.warmup),
            "sum_rows_f32_row4096": sum_rows_case(1 << 14, 4096, 12, list(range(13)), stream, args.steps, args.warmup),
-           "pga3d_sandwich_f32": pga_case(stream, args.steps, args.warmup)}
+           "pga3d_sandwich_f32": pga_case(stream, args.steps, args.warmup),
+           "rotor_grad_shared_f32": rotor_grad_case(True, stream, args.steps, args.warmup),
+           "rotor_grad_batched_f32": rotor_grad_case(False, stream, args.steps, args.warmup),
+           "exp_adj_kernel_m6_f32": exp_adj_kernel_case(4, stream, args.steps, args.warmup, 1 << 22),
+           "exp_adj_kernel_m66_f32": exp_adj_kernel_case(12, stream, args.steps, args.warmup, 1 << 19)}
     print(json.dumps(out))
 
 
