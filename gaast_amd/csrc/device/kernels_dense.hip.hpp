@@ -2,6 +2,7 @@
 // Included through kernels.hip.hpp.
 #pragma once
 #include "kernels_common.hip.hpp"
+#include "mfma32p_b_planes.hip.hpp"
 
 
 namespace gaast {
@@ -728,6 +729,8 @@ __device__ __forceinline__ constexpr int mfma16_k(int t) {
     constexpr int order[16] = {0, 3, 5, 6, 9, 10, 12, 15, 1, 2, 4, 7, 8, 11, 13, 14};
     return order[t];
 }
+static_assert(mfma16_k(1) == int(b_planes::s2_of_word(1)) && mfma16_k(7) == int(b_planes::s2_of_word(7)) && mfma16_k(8) == int(b_planes::s2_of_word(8)) &&
+              mfma16_k(14) == int(b_planes::s2_of_word(14)), "the quad-plane B image stores the words in mfma16_k order");
 
 // ------------------------------------------------------------------------------------------
 // k_gp_mfma32 in image-pair form (n = 10 ... 13): as k_gp_mfma16 below, NO sign is applied with vector instructions
@@ -741,9 +744,10 @@ __device__ __forceinline__ constexpr int mfma16_k(int t) {
 //     parity, and lanes with odd |c_hi| read the odd-|k| quads from the image of the other sign.
 // Steps run in chunks (immediate offsets for the A reads, the 16 A addresses move once per chunk): per step of 16 MFMAs
 // (1,024 matrix-pipe cycles) 16 ds_read_b32 + 4 ds_read_b128.  Vector instructions per step: ~10 where the B address is
-// rebuilt from its parts (sign bit extract, v_lshl_or, xor + add per quad, A moves: n = 13, DEGENERATE at n = 12); 4.25 at
-// n = 12 (XOR_STEP below: the four B addresses stay live and move by one three-operand xor with a lane-constant delta,
-// the A addresses move once per 64 steps).  There the per-item phases are lean as well: the canonicalising add of the
+// rebuilt from its parts (sign bit extract, v_lshl_or, xor + add per quad, A moves: n = 13, DEGENERATE at n = 12); 2.25 at
+// n = 12 (XOR_STEP below: the B image is the quad-plane one of mfma32p_b_planes.hip.hpp, two B addresses stay live -- the
+// other two quads sit at an immediate offset -- and move by one three-operand xor with a lane-constant delta each, the A
+// addresses move once per 64 steps).  There the per-item phases are lean as well: the canonicalising add of the
 // fast staging is a wave-uniform branch (2-3 instead of 4 instructions per word), and the store phase requests the
 // lane's 16 out_map words together instead of waiting for each in turn.
 // n = 14 does not fit (4 x 64 KiB) and stays on k_gp_mfma32.
@@ -845,11 +849,7 @@ __global__ __launch_bounds__(NDIM == 13 ? 512 : 256, NDIM <= 11 ? 2 : 1) void k_
     const uint32_t c_hi_u = uint32_t(c_hi) | 0x8000u;
     // block sign of step a_hi for this lane's column: wave-uniform part on the scalar unit, lane part = and + popcount
     auto sign_terms = [&](int a_hi, uint32_t& M, uint32_t& u) {   // block sign = u(a_hi) ^ parity(c_hi & M(a_hi)): both wave-uniform
-        uint32_t sp = uint32_t(a_hi) >> 1;
-        sp ^= sp >> 1;
-        sp ^= sp >> 2;
-        sp ^= sp >> 4;
-        sp ^= sp >> 8;
+        const uint32_t sp = b_planes::suffix_parities(uint32_t(a_hi));
         M = sp ^ (uint32_t(a_hi) & p.neg_hi);
         u = (__builtin_popcount(uint32_t(a_hi) & sp) ^ __builtin_popcount(uint32_t(a_hi) & p.neg_hi)) & 1u;
     };
@@ -862,12 +862,14 @@ __global__ __launch_bounds__(NDIM == 13 ? 512 : 256, NDIM <= 11 ? 2 : 1) void k_
     // reuses them for every group); n = 13 (8 words, an 8-fold unrolled loop) and the DEGENERATE instantiation at n = 12
     // (the zero-block select needs the address in two parts) compute them per step
     constexpr int SIGN_WORDS = H <= 64 ? H / 32 : 0;
-    // n = 12: the four B quad addresses stay LIVE in registers and move from step a_hi to a_hi + 1 by ONE xor each.  The
-    // address is (lane constant) ^ (a_hi << 7) ^ (swizzle bits of a_hi) ^ (block sign on the NEG bit), and all but u(a_hi)
-    // is linear over GF(2) in the bits of a_hi (M is: a suffix parity and an AND): a_hi -> a_hi + 1 flips the bits
-    // P_t = 2^(t+1) - 1, t = the number of trailing ones of a_hi (seven patterns for 128 steps), which moves the address by
-    // the lane constant
-    //     dlt[t] = (P_t << 7) ^ (swizzle bits of P_t) ^ (parity(c_hi & M(P_t)) on the NEG bit),
+    // n = 12: the B image is the quad-plane one (mfma32p_b_planes.hip.hpp: quad q of block x at 4096 q + 2048 h + 16 x), and
+    // TWO B addresses stay LIVE in registers -- xe for quad 0 (quad 1 at the immediate offset +4096), xo for quad 2 (quad 3 at
+    // +4096); xo = xe ^ 8192 ^ (parity(c_hi) on the NEG bit): lanes with odd |c_hi| take their odd-|k| quads from the other
+    // image -- and move from step a_hi to a_hi + 1 by ONE xor each.  The address is (lane constant) ^ (a_hi << 4) ^ (block
+    // sign on the NEG bit), and all but u(a_hi) is linear over GF(2) in the bits of a_hi (M is: a suffix parity and an
+    // AND): a_hi -> a_hi + 1 flips the bits P_t = 2^(t+1) - 1, t = the number of trailing ones of a_hi (seven patterns
+    // for 128 steps), which moves the address by the lane constant
+    //     dlt[t] = (P_t << 4) ^ (parity(c_hi & M(P_t)) on the NEG bit)                      (b_planes::delta),
     // seven registers computed once per launch.  u is quadratic in a_hi but wave-uniform: ud holds u(a_hi) ^ u(a_hi + 1)
     // for every step as 128 bits in scalar registers, and joins the xor as its third, scalar operand.
     // The live addresses are LDS addresses (base included), so the xor must not reach the base: the kernel has no static
@@ -878,12 +880,8 @@ __global__ __launch_bounds__(NDIM == 13 ? 512 : 256, NDIM <= 11 ? 2 : 1) void k_
     uint32_t ud[XOR_STEP ? H / 32 : 1] = {0};
     if constexpr (XOR_STEP) {
 #pragma unroll
-        for (int t = 0; t < 7; ++t) {
-            const uint32_t P = (2u << t) - 1u;
-            uint32_t M, u;
-            sign_terms(int(P), M, u);
-            dlt[t] = (P << 7) ^ (((P >> 1) & 7u) << 4) ^ ((uint32_t(__builtin_popcount(uint32_t(c_hi) & M)) & 1u) << (n + 2));
-        }
+        for (int t = 0; t < 7; ++t) dlt[t] = b_planes::delta(t, uint32_t(c_hi), p.neg_hi);
+        static_assert(!XOR_STEP || (NEG == b_planes::kNeg && IPB == 1), "one item per workgroup, the -B image 16 KiB above +B");
 #pragma unroll
         for (int w = 0; w < H / 32; ++w) {
             uint32_t bits = 0;
@@ -1068,11 +1066,10 @@ __global__ __launch_bounds__(NDIM == 13 ? 512 : 256, NDIM <= 11 ? 2 : 1) void k_
                 // n = 12: every read in its step (no software pipeline: the other wave of the SIMD covers the read latency),
                 // two chunks of 64 steps: the A words at immediate offsets 128 j, their 16 addresses move once per chunk; the B
                 // quad addresses move by one three-operand xor each per step (dlt[t] with t a compile-time constant inside
-                // the chunk, the step's u bit from the scalar unit) -- 4 vector instructions per step + 16 per chunk (one xor per A
+                // the chunk, the step's u bit from the scalar unit) -- 2 vector instructions per step + 16 per chunk (one xor per A
                 // address: bit 13 is clear in every ak0, so the second xor restores them for the next item)
-                uint32_t xb[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) xb[q] = lds0 + (b_base | bq[q]);   // step 0: a_hi = 0, block sign +
+                uint32_t xe = lds0 + (b_base | b_planes::xe0(uint32_t(c_hi), uint32_t(h)));   // step 0: a_hi = 0, block sign +
+                uint32_t xo = lds0 + (b_base | b_planes::xo0(uint32_t(c_hi), uint32_t(h)));
 #pragma unroll 1
                 for (int c = 0; c < H / 64; ++c) {
                     const uint32_t udw[2] = {c == 0 ? ud[0] : ud[2], c == 0 ? ud[1] : ud[3]};
@@ -1081,7 +1078,8 @@ __global__ __launch_bounds__(NDIM == 13 ? 512 : 256, NDIM <= 11 ? 2 : 1) void k_
                         uint32_t bw[16], aw[16];
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
-                            const uint4v v = *(__attribute__((address_space(3))) const uint4v*)size_t(xb[q]);
+                            // (bits 12 of xe and xo stay clear: the deltas move bits 4 ... 10 and the NEG bit)
+                            const uint4v v = *(__attribute__((address_space(3))) const uint4v*)size_t((q & 2 ? xo : xe) + uint32_t(q & 1) * b_planes::kQuadStride);
                             bw[4 * q + 0] = v.x; bw[4 * q + 1] = v.y; bw[4 * q + 2] = v.z; bw[4 * q + 3] = v.w;
                         }
 #pragma unroll
@@ -1095,8 +1093,8 @@ __global__ __launch_bounds__(NDIM == 13 ? 512 : 256, NDIM <= 11 ? 2 : 1) void k_
                         uint32_t su = __builtin_amdgcn_readfirstlane(((udw[j >> 5] >> (j & 31)) & 1u) << (n + 2));
                         asm("" : "+s"(su));   // in a scalar register: the third operand of the xor
                         const uint32_t d = dlt[j < 63 ? __builtin_ctz(~uint32_t(j)) : 6];   // (63 -> 64 flips seven bits)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) xb[q] = xor3(xb[q], d, su);
+                        xe = xor3(xe, d, su);
+                        xo = xor3(xo, d, su);
                     }
 #pragma unroll
                     for (int t = 0; t < 16; ++t) ak[t] ^= 64u << 7;   // to the second chunk, and back for the next item

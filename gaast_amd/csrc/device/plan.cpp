@@ -12,6 +12,7 @@
 //   (3) products whose list is a dense slice of the geometric product's table run on the
 //       bitmask-tiled kernel (re-ordered sums: tolerance, not bit-exact; GAAST_FLAG_EXACT_ORDER
 //       keeps them on the exact kernel).
+#include "mfma32p_b_planes.hip.hpp"
 #include "plan_internal.hpp"
 #include "spinor_basis.hpp"
 
@@ -891,6 +892,10 @@ struct Lowering {
                 return (x << 4) | ((((lo >> 2) ^ (x >> 2)) & 3) << 2) | (lo & 3);
             };
             // k_gp_mfma32p's B image: the lane's 16 words (k of one parity) even-|k >> 1| first, quads rotated as in mfma_b_pos
+            // (n = 12 with no null vector among the hi vectors -- the instantiations <false, 12, *, *>, whose step loop keeps
+            //  live B addresses: the quad-plane image of mfma32p_b_planes.hip.hpp instead)
+            bool b_quad_planes = fam == DenseFamily::MFMA32P && n2 == b_planes::kDim;
+            for (int j = 5; j < n2; ++j) b_quad_planes = b_quad_planes && frame.metric[size_t(perm[size_t(j)])] != 0.0;
             auto mfma32p_b_pos = [](uint32_t m) {
                 static const int word_of_s[16] = {0, 8, 9, 1, 10, 2, 3, 11, 12, 4, 5, 13, 6, 14, 15, 7};
                 const uint32_t x = m >> 5, k = m & 31, w = uint32_t(word_of_s[k >> 1]);
@@ -946,7 +951,7 @@ struct Lowering {
                             break;
                         case DenseFamily::MFMA32P:
                             if (right) neg ^= uint32_t(__builtin_popcount(blade >> 5) & __builtin_popcount(blade & 31u) & 1);
-                            if (right) pos = mfma32p_b_pos(blade);
+                            if (right) pos = b_quad_planes ? b_planes::pos(blade) : mfma32p_b_pos(blade);
                             break;
                         case DenseFamily::MFMA32: if (right) pos = mfma_b_pos(blade); break;
                         case DenseFamily::MFMA7:
@@ -1059,6 +1064,10 @@ struct Lowering {
             }
             ds.neg_lo_all = fam == DenseFamily::VECTOR_FMA && ds.neg_lo == 15u;
             ds.degenerate = ds.zero_hi != 0;
+            if (b_quad_planes != (fam == DenseFamily::MFMA32P && n2 == b_planes::kDim && !ds.degenerate)) {   // the launcher picks the kernel by ds.degenerate
+                fail(GAAST_ERR_INVALID_PROGRAM, "B image layout and kernel instantiation disagree");
+                return;
+            }
             static const char* const par_name[2] = {"even", "odd"};
             s.name = std::string(fam == DenseFamily::VECTOR_FMA ? "product_dense" : "product_dense_mfma") + "[gp n=" + std::to_string(n) +
                      (reduced ? std::string(" ") + par_name[frame.lpar] + " x " + par_name[frame.rpar] + " in Cl(" + std::to_string(n2) + ")" : std::string()) +
