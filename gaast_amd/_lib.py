@@ -116,9 +116,12 @@ SIGNATURES = {
     "gaast_hip_eval_gather": (_ci, [_vp, C.POINTER(_vp), _ci, _vp, _vp, C.POINTER(_i64), _ci, _ci]),
     "gaast_hip_linmap_create": (_ci, [_ci, _pd, _ci, C.POINTER(_vp)]),
     "gaast_hip_linmap_apply": (_ci, [_vp, _vp, _vp]),
+    "gaast_hip_linmap_apply_transposed": (_ci, [_vp, _vp, _vp]),
+    "gaast_hip_linmap_matrix_vjp": (_ci, [_vp, _vp, _vp, _vp]),
     "gaast_hip_linmap_destroy": (_ci, [_vp]),
     "gaast_hip_program_create_in_basis": (_ci, [C.POINTER(ProgramDesc), _pd, C.POINTER(_vp)]),
     "gaast_hip_program_create_vjp": (_ci, [C.POINTER(ProgramDesc), C.c_int32, C.POINTER(_vp)]),
+    "gaast_hip_program_create_vjp_in_basis": (_ci, [C.POINTER(ProgramDesc), _pd, C.c_int32, C.POINTER(_vp)]),
     "gaast_hip_mv_sum_rows": (_ci, [_vp, _vp]),
     "gaast_hip_jit_cache_set_dir": (_ci, [C.c_char_p]),
     "gaast_hip_jit_cache_stats": (_ci, [C.POINTER(_i64), _ci]),
@@ -135,6 +138,7 @@ SIGNATURES = {
     "gaast_blades_gp": (_dbl, [_ci, _pd, _u64, _u64, C.POINTER(_u64)]),
     "gaast_metric_diagonalize": (_ci, [_ci, _pd, _pd, _pd]),
     "gaast_compound_matrix": (_ci, [_ci, _pd, _ci, _pd]),
+    "gaast_compound_matrix_vjp": (_ci, [_ci, _ci, _pd, _pd, _pd]),
     "gaast_expr_retain": (_vp, [_vp]),
     "gaast_expr_release": (None, [_vp]),
     "gaast_expr_input": (_vp, [_ci, _u64, _ci]),

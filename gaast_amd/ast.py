@@ -329,9 +329,9 @@ class SpecializedAst:
 
     # -- reverse mode ---------------------------------------------------------------------------
     def vjp(self, slot):
-        """The vector-Jacobian product with respect to input `slot` (gaast_program_vjp), built once per slot."""
-        if self._basis() is not None:
-            raise _lib.GaastError(3, "programs in a non-diagonal Gram metric have no VJP")
+        """The vector-Jacobian product with respect to input `slot` (gaast_program_vjp), built once per slot.  For a GramAlgebra
+        the VJP program runs in the same orthogonal basis as the forward one (gaast_hip_program_create_vjp_in_basis): cotangent
+        and gradient rows are in the caller's basis."""
         cache = self.__dict__.setdefault("_vjps", {})
         if slot not in cache:
             cache[slot] = Vjp(self, int(slot))
@@ -380,7 +380,12 @@ class Vjp:
         if self._prog is None:
             _lib.init_device()
             h = C.c_void_p()
-            _lib.check(_lib.lib().gaast_hip_program_create(C.byref(self.desc), C.byref(h)))
+            q = self.spec._basis()
+            if q is None:
+                _lib.check(_lib.lib().gaast_hip_program_create(C.byref(self.desc), C.byref(h)))
+            else:   # the VJP of an in-basis program is the in-basis version of the VJP program, with the same Q
+                q = np.ascontiguousarray(q, dtype=np.float64)
+                _lib.check(_lib.lib().gaast_hip_program_create_in_basis(C.byref(self.desc), q.ctypes.data_as(_lib._pd), C.byref(h)))
             self._prog = h
         return self._prog
 

@@ -91,3 +91,55 @@ def torch_fn(spec):
         return _ProgramFunction.apply(spec, layouts, *xs)
 
     return fn
+
+
+class _OutermorphismFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, dtype, dim, mask, m, rows):
+        want = _TORCH_DTYPE[dtype]
+        if m.dtype != want or rows.dtype != want:
+            raise TypeError(f"M and rows must be {want}")
+        if tuple(m.shape) != (dim, dim):
+            raise ValueError(f"M: expected [{dim}, {dim}], got {list(m.shape)}")
+        if rows.dim() != 2 or rows.shape[1] != row_len(dim, mask):
+            raise ValueError(f"rows: expected [B, {row_len(dim, mask)}], got {list(rows.shape)}")
+        from .graded import Outermorphism
+        rows = rows.contiguous()
+        _use_torch_stream()
+        om = Outermorphism(m.detach().cpu().numpy(), dtype)   # the download synchronises: compounds are built on the host
+        out = torch.empty_like(rows)
+        om.apply(_wrap(rows, dim, mask), out=_wrap(out, dim, mask))
+        ctx.om, ctx.dim, ctx.mask = om, dim, mask
+        ctx.save_for_backward(rows)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (rows,) = ctx.saved_tensors
+        om, dim, mask = ctx.om, ctx.dim, ctx.mask
+        g = g.contiguous()
+        _use_torch_stream()
+        cot = _wrap(g, dim, mask)
+        dm = drows = None
+        if ctx.needs_input_grad[3]:
+            dm = om.matrix_vjp(_wrap(rows, dim, mask), cot, out=torch.empty((dim, dim), dtype=rows.dtype, device=rows.device))
+        if ctx.needs_input_grad[4]:
+            drows = torch.empty_like(rows)
+            om.apply_transposed(cot, out=_wrap(drows, dim, mask))
+        return None, None, None, dm, drows
+
+
+def outermorphism_fn(dtype=_lib.F64):
+    """f(M, rows, dim, grades) -> rows mapped by the outermorphism of M (C_k(M) on grade k), differentiable in M and in the rows.
+
+    M: an [n, n] GPU tensor, rows: [B, row_len] in the layout of (dim, grades), both of `dtype`.  Forward DOWNLOADS M -- a
+    synchronisation of the current stream -- because the compounds of a linear map are built on the host (gaast_hip_linmap_create),
+    then creates the map and applies it.  Backward returns gaast_hip_linmap_matrix_vjp for M (n <= 8) and
+    gaast_hip_linmap_apply_transposed for the rows.  Both directions run on torch's current stream.  No double backward."""
+
+    def fn(m, rows, dim, grades):
+        mask = grades.mask if isinstance(grades, GradeSet) else sum(1 << int(k) for k in set(grades))
+        return _OutermorphismFunction.apply(dtype, int(dim), mask, m, rows)
+
+    return fn

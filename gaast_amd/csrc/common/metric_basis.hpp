@@ -122,4 +122,57 @@ inline void compound_matrices(int n, const double* m, int kmax, std::vector<std:
     }
 }
 
+// Reverse mode of C_k with respect to the matrix: a k x k minor det M[I, J] is linear in each of its entries, with the cofactor
+//   d det M[I, J] / d M[i, j] = (-1)^(p_I(i) + p_J(j)) det M[I \ i, J \ j]      (i in I, j in J; p: 0-based position in the ascending blade)
+// One term per (I, J, i, j): which entry of W_k = d L / d C_k, which entry of C_{k-1}, the sign and the target (i, j).  The
+// order is I, J, i, j ascending (component order of grade k, then positions) -- the host sum and the device table both start here.
+struct CompoundVjpTerm {
+    uint32_t w;        // I * C(n,k) + J
+    uint32_t minor;    // (I \ i) * C(n,k-1) + (J \ j)
+    uint16_t target;   // i * n + j
+    uint16_t negative; // 1: the cofactor's sign is -1
+};
+
+inline void compound_vjp_terms(const BladeTable& t, int k, std::vector<CompoundVjpTerm>& out) {
+    out.clear();
+    if (k < 1 || k > t.n) return;
+    const size_t d = t.grade_dim[size_t(k)], dp = t.grade_dim[size_t(k - 1)];
+    out.reserve(d * d * size_t(k) * size_t(k));
+    for (size_t I = 0; I < d; ++I) {
+        const uint32_t bi = t.blade_of[size_t(k)][I];
+        for (size_t J = 0; J < d; ++J) {
+            const uint32_t bj = t.blade_of[size_t(k)][J];
+            int pi = 0;
+            for (uint32_t ri = bi; ri; ri &= ri - 1, ++pi) {
+                const int i = __builtin_ctz(ri);
+                int pj = 0;
+                for (uint32_t rj = bj; rj; rj &= rj - 1, ++pj) {
+                    const int j = __builtin_ctz(rj);
+                    CompoundVjpTerm e;
+                    e.w = uint32_t(I * d + J);
+                    e.minor = uint32_t(size_t(t.index_of[bi & ~(1u << i)]) * dp + t.index_of[bj & ~(1u << j)]);
+                    e.target = uint16_t(i * t.n + j);
+                    e.negative = uint16_t((pi + pj) & 1);
+                    out.push_back(e);
+                }
+            }
+        }
+    }
+}
+
+// dmatrix (n x n, row-major) += grade k's part of d L / d M for W_k = d L / d C_k(M) (C(n,k) x C(n,k), row-major).  Grade 0 adds nothing.
+inline void compound_matrix_vjp(int n, int k, const double* m, const double* w, double* dmatrix) {
+    if (k < 1) return;
+    const BladeTable t(n);
+    std::vector<std::vector<double>> c;
+    compound_matrices(n, m, k - 1, c, false);
+    const std::vector<double>& prev = c[size_t(k - 1)];
+    std::vector<CompoundVjpTerm> terms;
+    compound_vjp_terms(t, k, terms);
+    for (const CompoundVjpTerm& e : terms) {
+        const double term = prev[e.minor] * w[e.w];
+        dmatrix[e.target] += e.negative ? -term : term;
+    }
+}
+
 }  // namespace gaast

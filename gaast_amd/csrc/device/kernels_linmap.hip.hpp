@@ -14,6 +14,11 @@
 //                    blockIdx.x walks the (grade, output-column tile) jobs fastest, so the workgroups that read one slab of
 //                    input rows run together and the rows come from L2; blockIdx.y walks item tiles.
 // Sums are fused multiply-add chains in increasing input-component order (the f32 MFMA is bit-for-bit such a chain).
+//
+// Reverse mode with respect to the matrix (gaast_hip_linmap_matrix_vjp, n <= 8), two launches:
+//   k_linmap_outer_sum       W_k[I][J] = sum_items g_k[item][I] x_k[item][J] per grade k >= 1, reduced over one chunk of items
+//   k_linmap_minor_contract  dL/dM[i][j] = sum of sign * C_{k-1}(M)[I \ i][J \ j] * W_k[I][J] over a host-built term table
+// with k_sum_rows (kernels_reduce.hip.hpp) between them when the batch spans more than one chunk.
 #pragma once
 #include "kernels_common.hip.hpp"
 
@@ -170,6 +175,95 @@ __global__ __launch_bounds__(256) void k_linmap_mfma(LinmapArgs<T> p) {
                 }
             }
     }
+}
+
+// ---- reverse mode with respect to the matrix ------------------------------------------------------------------------------------
+constexpr int kOuterChunk = 1024;        // items per partial (= GAAST_SUM_ROWS_CHUNK: the first level of the fixed tree)
+constexpr int kOuterWaves = 4;           // 16 x 16 tiles of W per workgroup, one per wave
+constexpr int kContractThreads = 256;    // interleaved chains per entry of dL/dM
+constexpr int kContractIndexBits = 14;   // a term word: index into W | index into the compounds << 14 | negative << 28
+
+template <typename T>
+struct OuterSumArgs {
+    const T* g;                                // cotangent rows
+    const T* x;                                // input rows
+    T* out;                                    // [chunk][w_total]: W of every present grade >= 1, grade g at woff[g], row-major
+    int64_t g_stride, x_stride, batch;
+    int w_total, n_tiles, n_grades;
+    int goff[kLinmapMaxGrades];                // per present grade >= 1: offset in the row, C(n,k), offset of its W
+    int glen[kLinmapMaxGrades];
+    int woff[kLinmapMaxGrades];
+    int tile0[kLinmapMaxGrades + 1];           // first tile of each present grade (prefix sums of ceil(C(n,k) / 16)^2)
+};
+
+// One wave per 16 x 16 tile of W_k and chunk of kOuterChunk items, K = items, on v_mfma_{f32,f64}_16x16x4: lane (fi, fk) of a step
+// reads g[item0 + fk][I0 + fi] and x[item0 + fk][J0 + fi] straight from the rows (item-major rows ARE the K-major operands: the 16
+// lanes of a group read 16 consecutive elements of one row), element by element, so any stride and element alignment is the same
+// code.  One accumulator per tile, the steps issued in item order: the sum of an entry is ONE chain over the chunk's items in item
+// order, four per instruction (the instruction adds its four products onto the accumulator in k = item order, as k_linmap_mfma's
+// note on the f32 MFMA states), whatever the grid -- the fixed first level of the tree.  Rows and columns beyond C(n,k) and items
+// beyond the chunk enter as exact zeros (selected, never multiplied in from memory) and are not stored.
+template <typename T>
+__global__ __launch_bounds__(64 * kOuterWaves) void k_linmap_outer_sum(OuterSumArgs<T> p) {
+    typedef Mfma16x4<T> F;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int tile = int(blockIdx.x) * kOuterWaves + wave;
+    if (tile >= p.n_tiles) return;             // (uniform over the wave; the kernel has no barrier)
+    int gi = 0;
+    while (gi + 1 < p.n_grades && p.tile0[gi + 1] <= tile) ++gi;
+    const int len = p.glen[gi], tl = (len + 15) >> 4, t = tile - p.tile0[gi];
+    const int I0 = (t / tl) * 16, J0 = (t % tl) * 16;
+    const int fi = lane & 15, fk = lane >> 4;
+    const bool i_ok = I0 + fi < len, j_ok = J0 + fi < len;
+    const int64_t b0 = int64_t(blockIdx.y) * kOuterChunk;
+    const int64_t b1 = b0 + kOuterChunk < p.batch ? b0 + kOuterChunk : p.batch;
+    const int64_t gcol = p.goff[gi] + I0 + fi, xcol = p.goff[gi] + J0 + fi;
+    typename F::acc_t acc = typename F::acc_t{0, 0, 0, 0};
+    for (int64_t b = b0; b < b1; b += 16) {
+        T a[4], c[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int64_t item = b + 4 * s + fk;
+            const bool ok = item < b1;
+            a[s] = (ok && i_ok) ? p.g[item * p.g_stride + gcol] : T(0);
+            c[s] = (ok && j_ok) ? p.x[item * p.x_stride + xcol] : T(0);
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc = F::mma(a[s], c[s], acc);
+    }
+    // accumulator register v of lane (fi, fk): row I0 + F::row(fk, v) of the tile, column J0 + fi
+    T* w = p.out + int64_t(blockIdx.y) * p.w_total + p.woff[gi];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+        const int I = I0 + F::row(fk, v);
+        if (I < len && j_ok) w[I * len + J0 + fi] = acc[v];
+    }
+}
+
+// One workgroup per entry (i, j) of dL/dM.  Its terms terms[row_start[ij] .. row_start[ij + 1]) are ordered by grade, I, J; lane t
+// adds terms t, t + 256, ... in that order (product rounded, then added: no contraction), then the 256 partial sums are joined by
+// the fixed binary tree part[t] += part[t + 128], + 64, ... + 1.
+template <typename T>
+__global__ __launch_bounds__(kContractThreads) void k_linmap_minor_contract(const T* __restrict__ w, const T* __restrict__ mats,
+                                                                            const uint32_t* __restrict__ terms,
+                                                                            const uint32_t* __restrict__ row_start, T* __restrict__ dm) {
+    __shared__ T part[kContractThreads];
+    const int tid = threadIdx.x;
+    const uint32_t e0 = row_start[blockIdx.x], e1 = row_start[blockIdx.x + 1];
+    constexpr uint32_t kMask = (1u << kContractIndexBits) - 1u;
+    T acc = T(0);
+    for (uint32_t e = e0 + uint32_t(tid); e < e1; e += kContractThreads) {
+        const uint32_t t = terms[e];
+        const T term = mats[(t >> kContractIndexBits) & kMask] * w[t & kMask];
+        acc += (t >> (2 * kContractIndexBits)) ? -term : term;
+    }
+    part[tid] = acc;
+    __syncthreads();
+    for (int off = kContractThreads / 2; off > 0; off >>= 1) {
+        if (tid < off) part[tid] += part[tid + off];
+        __syncthreads();
+    }
+    if (tid == 0) dm[blockIdx.x] = part[0];
 }
 
 }  // namespace gaast

@@ -243,6 +243,13 @@ using MvPtr = std::unique_ptr<gaast_hip_mv_s, MvFree>;
 
 struct gaast_hip_linmap_s {
     LinmapDev dev;
+    std::vector<double> matrix;              // M as it was given: the compounds of M^T are built from it on first use
+    std::unique_ptr<LinmapDev> transposed;   // C_k(M^T) = C_k(M)^T (gaast_hip_linmap_apply_transposed)
+    // gaast_hip_linmap_matrix_vjp: the contraction's term table per grade mask of the rows, built when the mask is first seen
+    struct VjpTable {
+        DevTable terms, row_start;           // term words sorted by target (kernels_linmap.hip.hpp); n * n + 1 offsets
+    };
+    std::map<uint64_t, VjpTable> vjp_tables;
 };
 
 struct gaast_hip_program_s;
@@ -1573,6 +1580,7 @@ int gaast_hip_program_create_vjp(const gaast_program_desc* desc, int32_t wrt_slo
 
 extern "C++" {
 namespace {
+int reduce_scratch(size_t bytes, void** ptr);
 template <typename T>
 int launch_sum_rows(gaast_hip_mv_t in, gaast_hip_mv_t out) {
     const int64_t B = in->batch, len = in->layout.row_len;
@@ -1581,25 +1589,9 @@ int launch_sum_rows(gaast_hip_mv_t in, gaast_hip_mv_t out) {
     const unsigned tiles = unsigned((len + kSumCols - 1) / kSumCols);
     T* dst = static_cast<T*>(out->ptr);
     if (chunks > 1) {
-        const size_t bytes = size_t(chunks * len) * sizeof(T);
-        ReduceScratch* sc = nullptr;
-        for (ReduceScratch& r : g_reduce_scratch)
-            if (r.stream == g_stream) sc = &r;
-        if (!sc) {
-            g_reduce_scratch.push_back(ReduceScratch{g_stream, nullptr, 0});
-            sc = &g_reduce_scratch.back();
-        }
-        if (bytes > sc->bytes) {
-            if (sc->ptr) {
-                HIP_TRY(hipStreamSynchronize(g_stream));   // an earlier reduction on this stream may still read it
-                HIP_TRY(hipFree(sc->ptr));
-                sc->ptr = nullptr;
-                sc->bytes = 0;
-            }
-            HIP_TRY(hipMalloc(&sc->ptr, bytes));
-            sc->bytes = bytes;
-        }
-        T* part = static_cast<T*>(sc->ptr);
+        void* scratch = nullptr;
+        if (int st = reduce_scratch(size_t(chunks * len) * sizeof(T), &scratch)) return st;
+        T* part = static_cast<T*>(scratch);
         hipLaunchKernelGGL(k_sum_rows<T>, dim3(unsigned(chunks), tiles), dim3(256), 0, g_stream,
                            static_cast<const T*>(in->ptr), in->row_stride, B, int(len), chunk, part, len);
         HIP_TRY(hipGetLastError());
@@ -1641,6 +1633,7 @@ int gaast_hip_linmap_create(int n, const double* matrix, int dtype, gaast_hip_li
     if (int st = ensure_init()) return st;
     auto m = std::make_unique<gaast_hip_linmap_s>();
     if (int st = linmap_build(n, matrix, dtype, m->dev)) return st;
+    m->matrix.assign(matrix, matrix + n * n);
     *out = m.release();
     return GAAST_OK;
 }
@@ -1652,10 +1645,10 @@ int gaast_hip_linmap_destroy(gaast_hip_linmap_t map) {
     return GAAST_OK;
 }
 
-int gaast_hip_linmap_apply(gaast_hip_linmap_t map, gaast_hip_mv_t in, gaast_hip_mv_t out) {
-    if (!map || !in || !out) return set_err(GAAST_ERR_INVALID_ARGUMENT, "null argument");
-    if (int st = ensure_init()) return st;
-    const LinmapDev& m = map->dev;
+extern "C++" {
+namespace {
+// the argument checks and the launch of gaast_hip_linmap_apply, for the compounds `m` (those of M or of M^T)
+int linmap_apply_impl(const LinmapDev& m, gaast_hip_mv_t in, gaast_hip_mv_t out) {
     if (in->layout.dim != m.n || out->layout.dim != m.n)
         return set_err(GAAST_ERR_INVALID_ARGUMENT, "linmap_apply: the rows' dimension differs from the map's");
     if (in->layout.mask != out->layout.mask) return set_err(GAAST_ERR_INVALID_ARGUMENT, "linmap_apply: in and out grade sets differ");
@@ -1673,6 +1666,161 @@ int gaast_hip_linmap_apply(gaast_hip_linmap_t map, gaast_hip_mv_t in, gaast_hip_
     const Bound src{in->ptr, in->row_stride}, dst{out->ptr, out->row_stride};
     return m.dtype == GAAST_F32 ? launch_linmap<float>(m, in->layout, src, dst, in->batch)
                                 : launch_linmap<double>(m, in->layout, src, dst, in->batch);
+}
+
+// the library's reduction scratch of the current stream (gaast_hip_mv_sum_rows' rules: one buffer per stream, grown after
+// synchronising that stream only)
+int reduce_scratch(size_t bytes, void** ptr) {
+    ReduceScratch* sc = nullptr;
+    for (ReduceScratch& r : g_reduce_scratch)
+        if (r.stream == g_stream) sc = &r;
+    if (!sc) {
+        g_reduce_scratch.push_back(ReduceScratch{g_stream, nullptr, 0});
+        sc = &g_reduce_scratch.back();
+    }
+    if (bytes > sc->bytes) {
+        if (sc->ptr) {
+            HIP_TRY(hipStreamSynchronize(g_stream));   // an earlier reduction on this stream may still read it
+            HIP_TRY(hipFree(sc->ptr));
+            sc->ptr = nullptr;
+            sc->bytes = 0;
+        }
+        HIP_TRY(hipMalloc(&sc->ptr, bytes));
+        sc->bytes = bytes;
+    }
+    *ptr = sc->ptr;
+    return GAAST_OK;
+}
+
+constexpr int kLinmapVjpMaxDim = 8;   // W has C(2n,n) entries; a term word indexes W and the compounds in 14 bits each
+static_assert(kOuterChunk == GAAST_SUM_ROWS_CHUNK, "the first level of the outer-sum tree is gaast_hip_mv_sum_rows' chunk");
+
+// the term table of dL/dM for rows holding the grades of `mask`: W_k at the offset k_linmap_outer_sum writes it, C_{k-1} where the
+// map holds it, stably sorted by target (i, j) -- so a target's terms stay ordered by grade, I, J
+int linmap_vjp_table(gaast_hip_linmap_s& map, uint64_t mask, const gaast_hip_linmap_s::VjpTable** out) {
+    auto it = map.vjp_tables.find(mask);
+    if (it == map.vjp_tables.end()) {
+        const int n = map.dev.n;
+        const BladeTable bt(n);
+        std::vector<std::vector<uint32_t>> per_target(size_t(n * n));
+        std::vector<CompoundVjpTerm> terms;
+        uint32_t woff = 0;
+        for (int k = 1; k <= n; ++k) {
+            if (!((mask >> k) & 1ULL)) continue;
+            compound_vjp_terms(bt, k, terms);
+            for (const CompoundVjpTerm& e : terms) {
+                const uint32_t wi = woff + e.w, ci = uint32_t(map.dev.moff[size_t(k - 1)]) + e.minor;
+                if ((wi | ci) >> kContractIndexBits) return set_err(GAAST_ERR_UNIMPLEMENTED, "linmap_matrix_vjp: term index out of range");
+                per_target[e.target].push_back(wi | ci << kContractIndexBits | uint32_t(e.negative) << (2 * kContractIndexBits));
+            }
+            woff += bt.grade_dim[size_t(k)] * bt.grade_dim[size_t(k)];
+        }
+        std::vector<uint32_t> words, row_start(size_t(n * n + 1), 0);
+        for (size_t t = 0; t < per_target.size(); ++t) {
+            words.insert(words.end(), per_target[t].begin(), per_target[t].end());
+            row_start[t + 1] = uint32_t(words.size());
+        }
+        gaast_hip_linmap_s::VjpTable tab;
+        if (int st = tab.terms.upload(std::move(words))) return st;
+        if (int st = tab.row_start.upload(std::move(row_start))) return st;
+        it = map.vjp_tables.emplace(mask, std::move(tab)).first;
+    }
+    *out = &it->second;
+    return GAAST_OK;
+}
+
+template <typename T>
+int launch_linmap_matrix_vjp(gaast_hip_linmap_s& map, gaast_hip_mv_t in, gaast_hip_mv_t cot, void* dm) {
+    const LinmapDev& m = map.dev;
+    const Layout& l = in->layout;
+    const gaast_hip_linmap_s::VjpTable* tab = nullptr;
+    if (int st = linmap_vjp_table(map, l.mask, &tab)) return st;
+    OuterSumArgs<T> p;
+    std::memset(&p, 0, sizeof(p));
+    p.g = static_cast<const T*>(cot->ptr);
+    p.x = static_cast<const T*>(in->ptr);
+    p.g_stride = cot->row_stride;
+    p.x_stride = in->row_stride;
+    p.batch = in->batch;
+    for (int k = 1; k <= m.n; ++k) {
+        if (!((l.mask >> k) & 1ULL)) continue;
+        const int len = int(n_choose_k(uint64_t(m.n), uint64_t(k))), tl = (len + 15) / 16;
+        const int g = p.n_grades++;
+        p.goff[g] = int(l.offset(k));
+        p.glen[g] = len;
+        p.woff[g] = p.w_total;
+        p.w_total += len * len;
+        p.tile0[g + 1] = p.tile0[g] + tl * tl;
+    }
+    p.n_tiles = p.tile0[p.n_grades];
+    const int64_t chunks = (in->batch + kOuterChunk - 1) / kOuterChunk;
+    T* w = nullptr;
+    if (p.n_tiles > 0) {
+        void* sc = nullptr;   // W, then (more than one chunk) the chunk partials
+        if (int st = reduce_scratch(size_t(chunks > 1 ? chunks + 1 : 1) * size_t(p.w_total) * sizeof(T), &sc)) return st;
+        w = static_cast<T*>(sc);
+        p.out = chunks > 1 ? w + p.w_total : w;
+        hipLaunchKernelGGL(k_linmap_outer_sum<T>, dim3(unsigned((p.n_tiles + kOuterWaves - 1) / kOuterWaves), unsigned(chunks)),
+                           dim3(64 * kOuterWaves), 0, g_stream, p);
+        HIP_TRY(hipGetLastError());
+        if (chunks > 1) {
+            const unsigned tiles = unsigned((p.w_total + kSumCols - 1) / kSumCols);
+            hipLaunchKernelGGL(k_sum_rows<T>, dim3(1u, tiles), dim3(256), 0, g_stream, static_cast<const T*>(p.out), int64_t(p.w_total),
+                               chunks, p.w_total, chunks, w, int64_t(p.w_total));
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    hipLaunchKernelGGL(k_linmap_minor_contract<T>, dim3(unsigned(m.n * m.n)), dim3(kContractThreads), 0, g_stream, static_cast<const T*>(w),
+                       m.mats.as<T>(), tab->terms.template as<uint32_t>(), tab->row_start.template as<uint32_t>(), static_cast<T*>(dm));
+    HIP_TRY(hipGetLastError());
+    return GAAST_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int gaast_hip_linmap_apply(gaast_hip_linmap_t map, gaast_hip_mv_t in, gaast_hip_mv_t out) {
+    if (!map || !in || !out) return set_err(GAAST_ERR_INVALID_ARGUMENT, "null argument");
+    if (int st = ensure_init()) return st;
+    return linmap_apply_impl(map->dev, in, out);
+}
+
+int gaast_hip_linmap_apply_transposed(gaast_hip_linmap_t map, gaast_hip_mv_t in, gaast_hip_mv_t out) {
+    if (!map || !in || !out) return set_err(GAAST_ERR_INVALID_ARGUMENT, "null argument");
+    if (int st = ensure_init()) return st;
+    if (!map->transposed) {
+        const int n = map->dev.n;
+        std::vector<double> mt(size_t(n * n));
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < n; ++j) mt[size_t(i * n + j)] = map->matrix[size_t(j * n + i)];
+        auto t = std::make_unique<LinmapDev>();
+        if (int st = linmap_build(n, mt.data(), map->dev.dtype, *t)) return st;
+        map->transposed = std::move(t);
+    }
+    return linmap_apply_impl(*map->transposed, in, out);
+}
+
+int gaast_hip_linmap_matrix_vjp(gaast_hip_linmap_t map, gaast_hip_mv_t in, gaast_hip_mv_t cotangent, void* dmatrix_dev) {
+    if (!map || !in || !cotangent || !dmatrix_dev) return set_err(GAAST_ERR_INVALID_ARGUMENT, "null argument");
+    if (int st = ensure_init()) return st;
+    const LinmapDev& m = map->dev;
+    if (m.n > kLinmapVjpMaxDim)
+        return set_err(GAAST_ERR_UNIMPLEMENTED, "linmap_matrix_vjp: dimension above " + std::to_string(kLinmapVjpMaxDim));
+    if (in->layout.dim != m.n || cotangent->layout.dim != m.n)
+        return set_err(GAAST_ERR_INVALID_ARGUMENT, "linmap_matrix_vjp: the rows' dimension differs from the map's");
+    if (in->layout.mask != cotangent->layout.mask) return set_err(GAAST_ERR_INVALID_ARGUMENT, "linmap_matrix_vjp: in and cotangent grade sets differ");
+    if (in->batch != cotangent->batch) return set_err(GAAST_ERR_INVALID_ARGUMENT, "linmap_matrix_vjp: in and cotangent batches differ");
+    if (in->batch < 1) return set_err(GAAST_ERR_INVALID_ARGUMENT, "linmap_matrix_vjp: the rows hold no items");
+    if ((in->batch + kOuterChunk - 1) / kOuterChunk > 65535) return set_err(GAAST_ERR_INVALID_ARGUMENT, "linmap_matrix_vjp: more than 65535 chunks of items");
+    if (in->dtype != m.dtype || cotangent->dtype != m.dtype) return set_err(GAAST_ERR_INVALID_ARGUMENT, "linmap_matrix_vjp: dtype differs from the map's");
+    const size_t sz = dtype_size(m.dtype);
+    if (reinterpret_cast<uintptr_t>(dmatrix_dev) % sz) return set_err(GAAST_ERR_INVALID_ARGUMENT, "linmap_matrix_vjp: dmatrix_dev is not element-aligned");
+    const uintptr_t d0 = reinterpret_cast<uintptr_t>(dmatrix_dev), d1 = d0 + size_t(m.n * m.n) * sz;
+    for (gaast_hip_mv_t v : {in, cotangent}) {
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(v->ptr), a1 = a0 + size_t((v->batch - 1) * v->row_stride + v->layout.row_len) * sz;
+        if (a0 < d1 && d0 < a1) return set_err(GAAST_ERR_INVALID_ARGUMENT, "linmap_matrix_vjp: dmatrix_dev overlaps the rows");
+    }
+    return m.dtype == GAAST_F32 ? launch_linmap_matrix_vjp<float>(*map, in, cotangent, dmatrix_dev)
+                                : launch_linmap_matrix_vjp<double>(*map, in, cotangent, dmatrix_dev);
 }
 
 // A program specialised for the orthogonal basis f_j = sum_i Q_ij e_i, evaluated on rows in the caller's basis e: inputs move into f
@@ -1772,6 +1920,18 @@ int gaast_hip_program_create_in_basis(const gaast_program_desc* desc, const doub
     prog->scratch_batch = 0;   // the node buffers are re-allocated at the next eval
     *out = owner.release();
     return GAAST_OK;
+}
+
+// y_e = C(Q) F(C(Q^T) x_e) with orthogonal C_k(Q): the VJP of the in-basis program is the in-basis version of F's VJP program
+int gaast_hip_program_create_vjp_in_basis(const gaast_program_desc* desc, const double* basis, int32_t wrt_slot, gaast_hip_program_t* out) {
+    if (!desc || !basis || !out) return set_err(GAAST_ERR_INVALID_ARGUMENT, "null argument");
+    gaast_program_image_t img = nullptr;
+    if (int st = gaast_program_vjp(desc, wrt_slot, &img)) return set_err(st, std::string("program_create_vjp_in_basis: ") + gaast_expr_last_error());
+    gaast_hip_program_t prog = nullptr;
+    const int st = gaast_hip_program_create_in_basis(gaast_program_image_desc(img), basis, &prog);
+    gaast_program_image_free(img);
+    if (st == GAAST_OK) *out = prog;
+    return st;
 }
 
 int gaast_hip_program_destroy(gaast_hip_program_t prog) {

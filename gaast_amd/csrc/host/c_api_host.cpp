@@ -93,6 +93,15 @@ int gaast_compound_matrix(int n, const double* m, int k, double* out) {
     return GAAST_OK;
 }
 
+int gaast_compound_matrix_vjp(int n, int k, const double* matrix, const double* w, double* dmatrix) {
+    if (n < 1 || n > GAAST_MAX_DIM || k < 0 || k > n || !matrix || !w || !dmatrix) {
+        g_err = "gaast_compound_matrix_vjp: need 1 <= n <= GAAST_MAX_DIM and 0 <= k <= n";
+        return GAAST_ERR_INVALID_ARGUMENT;
+    }
+    compound_matrix_vjp(n, k, matrix, w, dmatrix);
+    return GAAST_OK;
+}
+
 gaast_expr_t gaast_expr_retain(gaast_expr_t e) {
     if (e) e->rc.fetch_add(1);
     return e;

@@ -179,7 +179,8 @@ class DeviceMV:
 
 class Outermorphism:
     """A linear map M of the vector space (n x n, row-major) extended to every grade: on grade k of a row, the k-th compound
-    C_k(M) (gaast_compound_matrix), shared by every item.  `apply` runs on the GPU (gaast_hip_linmap_apply, asynchronous)."""
+    C_k(M) (gaast_compound_matrix), shared by every item.  `apply` runs on the GPU (gaast_hip_linmap_apply, asynchronous); so do
+    its two adjoints, `apply_transposed` (with respect to the rows) and `matrix_vjp` (with respect to M, n <= 8)."""
 
     def __init__(self, matrix, dtype=_lib.F64):
         m = np.ascontiguousarray(np.asarray(matrix, dtype=np.float64))
@@ -205,3 +206,30 @@ class Outermorphism:
         _lib.check(_lib.lib().gaast_hip_linmap_apply(self._h, mv._h, out._h))
         out._keep_inputs = mv
         return out
+
+    def apply_transposed(self, mv, out=None):
+        """out(item)_k = C_k(M)^T mv(item)_k (gaast_hip_linmap_apply_transposed): the adjoint of `apply` with respect to the rows,
+        bit for bit `Outermorphism(M.T).apply`."""
+        if out is None:
+            out = DeviceMV.alloc(mv.dim, GradeSet(mv.mask), mv.batch, self.dtype)
+        _lib.check(_lib.lib().gaast_hip_linmap_apply_transposed(self._h, mv._h, out._h))
+        out._keep_inputs = mv
+        return out
+
+    def matrix_vjp(self, mv, cotangent, out=None):
+        """dL/dM for L = sum over items and grades of <cotangent_k, C_k(M) mv_k> (gaast_hip_linmap_matrix_vjp; n <= 8,
+        deterministic, asynchronous).  out: an [n, n] contiguous torch GPU tensor of the map's dtype, written in place and
+        returned; None: a numpy [n, n] array (this form synchronises to download it)."""
+        n = self.n
+        if out is not None:
+            import torch
+            want = {_lib.F64: torch.float64, _lib.F32: torch.float32}[self.dtype]
+            if out.dtype != want or tuple(out.shape) != (n, n) or not out.is_contiguous() or not out.is_cuda:
+                raise ValueError(f"out: a contiguous [{n}, {n}] GPU tensor of {want} expected")
+            _lib.check(_lib.lib().gaast_hip_linmap_matrix_vjp(self._h, mv._h, cotangent._h, C.c_void_p(out.data_ptr())))
+            return out
+        buf = DeviceMV.alloc(8, GradeSet.of(range(9)), 1, self.dtype)   # 256 >= n * n elements of library-owned device memory
+        ptr = C.c_void_p()
+        _lib.check(_lib.lib().gaast_hip_mv_info(buf._h, None, None, None, None, None, None, C.byref(ptr)))
+        _lib.check(_lib.lib().gaast_hip_linmap_matrix_vjp(self._h, mv._h, cotangent._h, ptr))
+        return buf.download_rows()[0, :n * n].reshape(n, n).copy()

@@ -58,6 +58,13 @@ int gaast_metric_diagonalize(int n, const double *gram, double *diag_out, double
  * columns of blade J], I and J in the component order of grade k (gaast_component_to_blade).  C_k(M) is the outermorphism of M
  * on grade k: the coordinates of M e_J = (M e_j1) ^ ... ^ (M e_jk) are column J. */
 int gaast_compound_matrix(int n, const double *m, int k, double *out);
+/* Reverse mode of gaast_compound_matrix with respect to the matrix.  w: C(n,k) x C(n,k), row-major, w[I*C(n,k) + J] = dL/dC_k(M)[I][J].
+ * ADDS grade k's contribution to dmatrix (n x n, row-major; the caller zeroes it and calls once per grade), in double:
+ *   dmatrix[i*n + j] += sum over blades I containing i and J containing j of (-1)^(p_I(i) + p_J(j)) C_{k-1}(M)[I \ i][J \ j] w[I][J],
+ * p the 0-based position of the vector in the ascending blade: the cofactor expansion of each k x k minor.  C_0 = (1), so k = 1
+ * adds w itself; k = 0 adds nothing (C_0 does not depend on M).  Terms are added in the order I, J, i, j ascending.  The device
+ * contraction of gaast_hip_linmap_matrix_vjp (gaast_hip.h) is built from the same term list. */
+int gaast_compound_matrix_vjp(int n, int k, const double *matrix, const double *w, double *dmatrix);
 
 /* ---- Expr construction (phase 1) -------------------------------------------------------------- */
 gaast_expr_t gaast_expr_retain(gaast_expr_t e);  /* Expr::clone, expr.rs:47-53: same node identity */
@@ -145,6 +152,8 @@ void gaast_program_image_free(gaast_program_image_t img);
  * when the input does not reach the root.  An explicit list gets its explicit transposed list; a compact product, and a geometric
  * product (product_kind GAAST_PROD_GEOMETRIC) at n >= 6 whatever its form, a compact GAAST_PROD_ADJ_LEFT / GAAST_PROD_ADJ_RIGHT node,
  * which the dense kernels evaluate where they take the forward product.  The adjoint program inherits desc->flags.
+ * A program specialised for the orthogonal basis of a Gram metric differentiates like any other: its VJP program is created with the
+ * same basis (gaast_hip_program_create_vjp_in_basis, gaast_hip.h), the cotangent being one more batched input.
  * Errors: GAAST_ERR_INVALID_ARGUMENT for a wrt_slot out of range or const, or n_inputs + 1 > GAAST_MAX_INPUTS;
  * GAAST_ERR_UNIMPLEMENTED for GAAST_FLAG_SPINOR_GEMM, and for exp / log on the path to wrt_slot unless desc->flags holds both
  * GAAST_FLAG_EXP_LOG and GAAST_FLAG_EXP_LOG_GRAD: then the operand's cotangent is a GAAST_OP_EXP_ADJ / GAAST_OP_LOG_ADJ node

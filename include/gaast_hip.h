@@ -331,6 +331,30 @@ int gaast_hip_linmap_create(int n, const double *matrix, int dtype, gaast_hip_li
 /* out(item)_k = C_k(M) in(item)_k for every grade k of the rows.  in and out: dimension n, the map's dtype, the same grade mask
  * and batch, no overlap (rows may be strided: gaast_hip_mv_wrap).  Asynchronous on the library stream. */
 int gaast_hip_linmap_apply(gaast_hip_linmap_t map, gaast_hip_mv_t in, gaast_hip_mv_t out);
+/* The adjoint of gaast_hip_linmap_apply with respect to the rows: out(item)_k = C_k(M)^T in(item)_k.  C_k(M)^T = C_k(M^T), so this is
+ * gaast_hip_linmap_apply of the map of M^T, bit for bit: the same kernels on a second set of compounds, built (synchronously, like
+ * gaast_hip_linmap_create) at the first call and owned by the map.  Arguments, limits and asynchrony as gaast_hip_linmap_apply. */
+int gaast_hip_linmap_apply_transposed(gaast_hip_linmap_t map, gaast_hip_mv_t in, gaast_hip_mv_t out);
+/* The adjoint with respect to the matrix.  in = x and cotangent = g: dimension n, the map's dtype, the same grade mask and batch B >= 1.
+ * For L = sum_items sum_k <g_k, C_k(M) x_k> it writes dL/dM, n x n elements of the map's dtype, row-major, to dmatrix_dev (device
+ * memory that overlaps neither rows):
+ *   W_k[I][J] = sum_items g_k[item][I] x_k[item][J]                                             (k_linmap_outer_sum)
+ *   dL/dM[i][j] = sum_{k >= 1} sum_{I has i, J has j} (-1)^(p_I(i) + p_J(j)) C_{k-1}(M)[I \ i][J \ j] W_k[I][J]     (k_linmap_minor_contract)
+ * as gaast_compound_matrix_vjp (gaast_expr.h) states it; grade 0 contributes nothing.  n <= 8 only (W has C(2n,n) entries: 12,870 at
+ * n = 8, 2.7 M at n = 12): beyond that GAAST_ERR_UNIMPLEMENTED and nothing is written.
+ * Deterministic, no atomics: W is summed over the items in item order within chunks of GAAST_SUM_ROWS_CHUNK items (a chain of fused
+ * multiply-adds on the matrix cores, four items per instruction, added in item order), then the chunk partials in chunk order
+ * (k_sum_rows); each entry of dL/dM then sums its terms -- ordered by k, I, J -- in 256 interleaved chains (term t in chain t mod 256)
+ * joined by a fixed binary tree.  The bits depend on B, the grade mask and the data only.  Everything accumulates in the dtype:
+ *   |result - exact| <= (d + 4) eps sum |terms| per entry, to first order,
+ *   d = min(B, GAAST_SUM_ROWS_CHUNK) + ceil(B / GAAST_SUM_ROWS_CHUNK) + 22
+ * (22 = ceil(C(14,7) / 256) + 8: the longest chain and the tree of the contraction at n = 8), |terms| = |C_{k-1} entry| |g| |x|, with
+ * the compounds as the map holds them (rounded to the dtype from double).
+ * Scratch as gaast_hip_mv_sum_rows: W and its chunk partials live in the library's per-stream reduction buffer, grown on first use
+ * with a larger size after synchronising that stream -- so the first such call on a stream must not be inside a stream capture; the
+ * term table of a grade mask is built and uploaded (synchronously) the first time the map sees that mask.  Otherwise asynchronous on
+ * the library stream, no host synchronisation. */
+int gaast_hip_linmap_matrix_vjp(gaast_hip_linmap_t map, gaast_hip_mv_t in, gaast_hip_mv_t cotangent, void *dmatrix_dev);
 int gaast_hip_linmap_destroy(gaast_hip_linmap_t map);
 /* desc: a program specialised for the orthogonal basis f (its metric_diag is L; explicit comp-mul lists computed in f are fine).
  * basis: Q as gaast_metric_diagonalize returns it, refused (GAAST_ERR_INVALID_ARGUMENT) unless |Q^T Q - I| <= 1e-12 elementwise.
@@ -396,9 +420,19 @@ int gaast_hip_eval_gather(gaast_hip_program_t prog, const gaast_hip_mv_t *inputs
  * program and the cotangent (root grade mask, dimension n, one row per item) at slot desc->n_inputs; gaast_hip_eval writes the
  * gradient rows of input `wrt_slot` (its grade mask and storage dimension).  Batch-1 inputs are shared as usual; the gradient of a
  * shared input is then one row per item, to be summed with gaast_hip_mv_sum_rows.  Programs created with
- * GAAST_FLAG_SPINOR_GEMM or through gaast_hip_program_create_in_basis have no VJP: GAAST_ERR_UNIMPLEMENTED; so has an exp / log on
- * the path to `wrt_slot` unless desc->flags holds GAAST_FLAG_EXP_LOG | GAAST_FLAG_EXP_LOG_GRAD. */
+ * GAAST_FLAG_SPINOR_GEMM have no VJP: GAAST_ERR_UNIMPLEMENTED; so has an exp / log on the path to `wrt_slot` unless desc->flags holds
+ * GAAST_FLAG_EXP_LOG | GAAST_FLAG_EXP_LOG_GRAD.  A program of gaast_hip_program_create_in_basis has the VJP below. */
 int gaast_hip_program_create_vjp(const gaast_program_desc *desc, int32_t wrt_slot, gaast_hip_program_t *out);
+/* gaast_program_vjp followed by gaast_hip_program_create_in_basis: the VJP of a program in a non-diagonal metric.  With the orthogonal
+ * Q of the basis change, y_e = C(Q) F(C(Q^T) x_e) and every C_k(Q) is orthogonal, so the VJP of the in-basis program is the in-basis
+ * version of the VJP program with the same Q: the cotangent (slot desc->n_inputs, an ordinary batched input of dimension n) goes
+ * through C_k(Q^T) like every other input, the gradient comes back through C_k(Q).  desc is the FORWARD program specialised for
+ * diag(L), its constant rows in the caller's basis exactly as gaast_hip_program_create_in_basis takes them.  Q == I exactly: the very
+ * program (plan, launches, bits) of gaast_hip_program_create_vjp.  A wrt_slot whose rows hold only grade 0 gets no result move.  The
+ * exp / log adjoint nodes work unchanged inside f (sigma_i is the metric of f there).  Errors: those of gaast_program_vjp
+ * (GAAST_FLAG_SPINOR_GEMM stays GAAST_ERR_UNIMPLEMENTED) and of gaast_hip_program_create_in_basis; *out is untouched on failure. */
+int gaast_hip_program_create_vjp_in_basis(const gaast_program_desc *desc, const double *basis, int32_t wrt_slot,
+                                          gaast_hip_program_t *out);
 /* out(0) = sum over the B rows of `in` (out: batch 1, same dimension, grade mask and dtype; B >= 1).  Deterministic: rows are
  * summed in index order within chunks of GAAST_SUM_ROWS_CHUNK rows, then the chunk partials in chunk order, so the bits depend
  * on B and the data only.  Sums accumulate in the dtype (f32 in f32): |result - exact| <= (GAAST_SUM_ROWS_CHUNK - 1 + ceil(B /

@@ -115,6 +115,8 @@ extern "C" {
     pub fn gaast_hip_eval(p: Program, inputs: *const Mv, n_inputs: c_int, batch: i64, out: Mv) -> c_int;
     // reverse mode: the VJP of a program w.r.t. one input slot (cotangent at slot n_inputs), and the sum of a batch's rows
     pub fn gaast_hip_program_create_vjp(desc: *const GaastProgramDesc, wrt_slot: i32, out: *mut Program) -> c_int;
+    /// the same for a program in a non-diagonal metric: `basis` is Q (n x n, row-major) of gaast_hip_program_create_in_basis
+    pub fn gaast_hip_program_create_vjp_in_basis(desc: *const GaastProgramDesc, basis: *const f64, wrt_slot: i32, out: *mut Program) -> c_int;
     pub fn gaast_hip_mv_sum_rows(input: Mv, out: Mv) -> c_int;
     // cache of compiled program kernels (eval.rs:12-19 has no set-up): a directory later processes load from, and the counters
     // (compiled, memory hits, disk hits, disk stores, disk rejected, live modules -- GAAST_JIT_CACHE_* in gaast_hip.h)

@@ -15,6 +15,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402  (before gaast_amd: see tests/conftest.py)
 
 import gaast_amd as ga  # noqa: E402
@@ -100,6 +101,32 @@ def rotor_grad_case(shared, stream, steps, warmup, batch=1 << 20):
             "launches_per_backward": sum(launches) + (1 if shared else 0)}
 
 
+def cga_sandwich_case(stream, steps, warmup, batch=1 << 20):
+    """conformal R X ~R (R: grades {0, 2}, shared; X: points), f32: backward against forward in the null basis {e1, e2, e3, e_o,
+    e_inf} (Gram metric: linmap launches around the program) and the same program in the diagonal basis (+ + + + -), alternating"""
+    n = 5
+    null = np.array([[1, 0, 0, 0, 0], [0, 1, 0, 0, 0], [0, 0, 1, 0, 0], [0, 0, 0, 0, -1], [0, 0, 0, -1, 0]], dtype=np.float64)
+    out = {"batch": batch}
+    cases = {}
+    for name, alg in (("null_basis", ga.GramAlgebra(null)), ("diagonal_basis", ga.MetricAlgebra([1.0, 1.0, 1.0, 1.0, -1.0]))):
+        R, X = ga.mv(ga.Input(0, [0, 2], n)), ga.mv(ga.Input(1, [1], n))
+        spec = (R * X * R.rev()).g(1).specialize(alg, dtype=ga.F32)
+        f = spec.torch_fn()
+        r_t, x_t = rows(1, 11).requires_grad_(), rows(batch, 5).requires_grad_()
+        y = f(r_t, x_t)
+        cases[name] = (spec, f, r_t, x_t, y, torch.ones_like(y))
+        out[name] = {"forward_ms": [], "backward_ms": [], "forward_launches": len(spec.launches()),
+                     "vjp_launches": [len(spec.vjp(s).launches()) for s in range(2)]}
+    for _ in range(3):
+        for name, (spec, f, r_t, x_t, y, gy) in cases.items():
+            out[name]["forward_ms"].append(timed(lambda: f(r_t, x_t), stream, steps, warmup))
+            out[name]["backward_ms"].append(timed(lambda: torch.autograd.grad(y, (r_t, x_t), gy, retain_graph=True), stream, steps, warmup))
+    for name in cases:
+        out[name]["backward_over_forward"] = min(out[name]["backward_ms"]) / min(out[name]["forward_ms"])
+    out["null_over_diagonal_backward"] = min(out["null_basis"]["backward_ms"]) / min(out["diagonal_basis"]["backward_ms"])
+    return out
+
+
 def exp_adj_kernel_case(n, stream, steps, warmup, batch):
     """k_exp_log_adj alone on R^n bivectors, f32.  The unfused (NO_FUSION) VJP of exp(B) is the copies of B and g into their cache
     buffers, the zero fill of the result and the adjoint launch; the two copies are timed as programs of their own (an input as the
@@ -141,6 +168,7 @@ def main():
            "pga3d_sandwich_f32": pga_case(stream, args.steps, args.warmup),
            "rotor_grad_shared_f32": rotor_grad_case(True, stream, args.steps, args.warmup),
            "rotor_grad_batched_f32": rotor_grad_case(False, stream, args.steps, args.warmup),
+           "cga_null_basis_sandwich_f32": cga_sandwich_case(stream, args.steps, args.warmup),
            "exp_adj_kernel_m6_f32": exp_adj_kernel_case(4, stream, args.steps, args.warmup, 1 << 22),
            "exp_adj_kernel_m66_f32": exp_adj_kernel_case(12, stream, args.steps, args.warmup, 1 << 19)}
     print(json.dumps(out))
