@@ -1268,7 +1268,7 @@ static void chain_sparse_into_dense(Plan& plan) {
         };
         const int64_t ll = row_len(w.a), rl = row_len(w.b);
         const int n2 = dn.dense.n;
-        // items a workgroup of the dense kernel stages at once (runtime.hip: prepare_step)
+        // items a workgroup of the dense kernel stages at once (runtime.hip: prepare_dense)
         int ipb = 1, images_per_item = 4;   // (image counts: +-A, +-B, or A and B)
         switch (fam) {
         case DenseFamily::MFMA32:
@@ -1671,7 +1671,7 @@ static void fuse_reduce_scale(Plan& plan) {
         // tolerance mode: can a wave keep the row in registers and read it once (k_reduce_scale_wave)?  The reduction must be one term
         // per component, (i, i), coefficient +-1, in any order; the scaling one row per component in place (x offset = out offset),
         // +-1; the row a whole number of 64 x 16 bytes with at most 32 components per lane.  (Whether the three rows ARE one row is
-        // known when they are bound: run_step.)
+        // known when they are bound: run_reduce.)
         if (!(plan.flags & GAAST_FLAG_EXACT_ORDER) && p1.a == p1.b && xop == p1.a) {
             const size_t per_piece = 64 * (plan.dtype == GAAST_F32 ? 4 : 2);   // components a wave moves per 16-byte load
             const Step::Reduce& q = f.reduce;

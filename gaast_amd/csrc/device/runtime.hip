@@ -198,40 +198,64 @@ struct LinmapDev {
     int small_blocks_per_cu = 1;      // k_linmap_small: resident workgroups per CU (persistent grid)
 };
 
-// One launch of a program: the plan's step it runs and what gaast_hip_program_create made of it on the device
+// One launch of a program: the plan's step it runs and what gaast_hip_program_create made of it on the device.  One group per
+// launcher (its prepare_* / run_* pair): the step's tables on the device, under the names of their host images in Step (those
+// are dropped after the upload), and the launch configuration, fixed once by prepare_*.  The groups of the other launchers
+// stay empty.
 struct Launch {
     Step s;
-    // launch configuration, fixed once (prepare_step): kernel, block size, dynamic LDS, persistent-grid size.  ELL products
-    // pick kern[log2(items per pass)] by batch.
-    const void* kern[4] = {nullptr, nullptr, nullptr, nullptr};
     int n = 0;                 // dimension of the algebra the kernel runs in (parity-pure dense products: n - 1)
-    int threads = 0;
-    size_t lds = 0;            // bytes per launch (ELL / CSR: per staged item)
-    int max_items = 0;         // ELL / CSR: items per workgroup when the batch allows
-    int items_per_block = 0;   // dense kernels
-    int blocks_per_cu = 0;     // persistent kernels: resident workgroups per CU
-    size_t pre_scratch_off = 0;   // chained: bytes, where the list's operand rows sit in the kernel's LDS (after its images)
-    // the step's tables on the device, under the names of their host images in Step (those are dropped after the upload)
-    DevTable axpy_map, flip_offsets;
-    struct { DevTable row_start, row_out, entries, coeff; } list;
-    struct { DevTable left_map, right_map, out_map, spinor_out_map, left_scale, right_scale, out_scale; } dense;
-    struct { DevTable row_start, entries, coeff, row_map, row_scale; } pre;
-    struct { DevTable ent1, pos1, ent2, out2; } cj;
-    struct { DevTable prog, phase_tab; std::vector<double> general; } fused;   // (general: passed by value)
+    struct { DevTable axpy_map, flip_offsets; } trivial;   // AXPY, FLIP (SUNARY has no table)
+    struct {   // PRODUCT_CSR: k_product_csr, k_product_ell, k_product_ell_chain or the specialised gaast_chain
+        DevTable row_start, row_out, entries, coeff;
+        struct { DevTable entries, row_map; } pre;        // k_product_ell_chain: the first list
+        struct { DevTable ent1, pos1, ent2, out2; } cj;   // gaast_chain: tables of its own
+        size_t bytes_per_item = 0;      // k_product_csr / k_product_ell: LDS of one staged item
+        int csr_items = 0;              // k_product_csr: items per workgroup when the batch allows
+        const void* ell[4] = {nullptr, nullptr, nullptr, nullptr};   // k_product_ell<T, 1 << i, ...> by i = log2(items per pass)
+        int ell_max_log2 = 0;           // ... the largest i built: picked by batch
+        int chain_threads = 0;          // k_product_ell_chain / gaast_chain: workgroup size
+        size_t chain_bytes = 0;         // k_product_ell_chain: dynamic LDS of a launch
+        int chain_blocks_per_cu = 0;    // k_product_ell_chain / gaast_chain: resident workgroups per CU
+    } list;
+    struct {   // PRODUCT_DENSE
+        DevTable left_map, right_map, out_map, spinor_out_map, left_scale, right_scale, out_scale;
+        struct { DevTable row_start, entries, coeff, row_map, row_scale; } pre;   // chained: the list ahead of the product
+        const void* general = nullptr;       // any rows
+        const void* prefetch = nullptr;      // register-prefetch staging (k_gp_mfma6: its straight-line item loop): by the rows bound
+        const void* whole_rows = nullptr;    // ... with straight-line result stores
+        const void* spinor_fast = nullptr;   // k_gp_spinor12s: full, aligned rows on both sides and in the result
+        int threads = 0;
+        int items_per_block = 0;
+        size_t bytes = 0;                // dynamic LDS of a launch
+        size_t pre_scratch_bytes = 0;    // chained: where the list's operand rows sit in that LDS (after the kernel's images)
+        int blocks_per_cu = 0;           // > 0: persistent workgroups, this many resident per CU
+    } dense;
+    struct {   // REDUCE_SCALE
+        DevTable ent1, coeff1, ent2, coeff2, sign_words;
+        const void* wave = nullptr;      // k_reduce_scale_wave<T, s.reduce.wave>, if built
+        int blocks_per_cu = 0;           // k_reduce_scale: resident workgroups per CU
+    } reduce;
     struct { DevTable sq, row_start, pairs, pair_coeff; } explog;
-    struct { DevTable sq; } adj;
-    struct { DevTable ent1, coeff1, ent2, coeff2, sign_words; } reduce;
+    struct {   // EXPLOG_ADJ
+        DevTable sq;
+        const void* kernel = nullptr;
+        int lds_items = 0;               // items of a workgroup whose rows go through LDS; 0: the direct form
+        size_t bytes_per_item = 0;       // LDS of one such item
+    } adj;
     struct { DevTable ops, comp_off, out_off, coeff; } ew;
+    struct { DevTable prog, phase_tab; std::vector<double> general; } fused;   // the interpreter's (general: passed by value)
     void* domain = nullptr;            // the program's domain-error counter (borrowed)
     const LinmapDev* linmap = nullptr; // LINMAP: the program's map (borrowed)
     // FUSED: the plan specialised through hiprtc, or a list chain (Step::cj); a FUSED step also gets the same source
     // compiled with floating-point contraction (l * r + acc as ONE fused multiply-add: fewer roundings than the reference, so
     // within the tolerance contract but not its bits): built only without GAAST_FLAG_EXACT_ORDER, launched only when an item's
-    // arithmetic outweighs its bytes (run_jit -- in practice: operands shared by all items)
+    // arithmetic outweighs its bytes (run_fused -- in practice: operands shared by all items)
     JitKernel jit, jit_fma;
     std::string label;   // what the step is, then WHICH HIP kernel runs it (the name rocprofv3 reports)
-    // index into kern[] (REDUCE_SCALE: 1 = wave kernel; jit: 1 = jit_fma) the most recent evaluation launched: host-side record
-    // for gaast_hip_program_launch_variant, -1 before any evaluation
+    // which of a launch's kernels the most recent evaluation took (what its run_* returned): ELL: log2 of the items per pass;
+    // dense: 0 general, 1 prefetch, 2 whole rows; spinor: 1 = the fast form; REDUCE_SCALE: 1 = the wave kernel; FUSED: 1 =
+    // jit_fma; 0 where there is one kernel.  Host-side record for gaast_hip_program_launch_variant, -1 before any evaluation
     mutable int variant = -1;
 };
 
@@ -251,8 +275,6 @@ struct gaast_hip_linmap_s {
     };
     std::map<uint64_t, VjpTable> vjp_tables;
 };
-
-struct gaast_hip_program_s;
 
 // Everything a program owns is freed through its members: gaast_hip_program_destroy synchronises the stream first
 struct gaast_hip_program_s {
@@ -295,14 +317,6 @@ void mv_free_impl(gaast_hip_mv_t m) {
 }
 void MvFree::operator()(gaast_hip_mv_t m) const { mv_free_impl(m); }
 
-int grid_for(int64_t total, int block) {
-    int64_t g = (total + block - 1) / block;
-    const int64_t cap = int64_t(g_num_cu) * 8;  // grid-stride beyond 8 blocks per CU
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return int(g);
-}
-
 struct Bound {  // a buffer resolved for one eval call
     void* ptr;
     int64_t stride;
@@ -321,38 +335,51 @@ int resident_blocks(const void* kern, int threads, size_t lds, int* per_cu) {
     return GAAST_OK;
 }
 
-// ------------------------------------------------------------------------------------------
-// Launch configuration of one step, decided ONCE at gaast_hip_program_create: which kernel instantiation,
-// block size, dynamic LDS, persistent grid.  A step no kernel of this back end can run (operands beyond the LDS
-// budget) makes program_create fail with UNIMPLEMENTED: an eval then either runs every step or none.
-// ------------------------------------------------------------------------------------------
-// k_gp_mfma16x4<T, DEG, n, MODE, SC, CH> by run-time n and degeneracy.  f64 runs n = 8 ... 12 on it, f32 only n = 8, 9 (f32 at
-// n >= 10 is k_gp_mfma32p's): the f32 instantiations for n = 10 ... 12 would be unreachable, so they are not built.
-template <typename T, int MODE, bool SC, bool CH>
-void (*mfma16x4_kernel(int n, bool degenerate))(DenseArgs<T>) {
-    switch (n) {
-    case 8: return degenerate ? &k_gp_mfma16x4<T, true, 8, MODE, SC, CH> : &k_gp_mfma16x4<T, false, 8, MODE, SC, CH>;
-    case 9: return degenerate ? &k_gp_mfma16x4<T, true, 9, MODE, SC, CH> : &k_gp_mfma16x4<T, false, 9, MODE, SC, CH>;
-    default: break;
-    }
-    if constexpr (std::is_same<T, double>::value) {
-        switch (n) {
-        case 10: return degenerate ? &k_gp_mfma16x4<T, true, 10, MODE, SC, CH> : &k_gp_mfma16x4<T, false, 10, MODE, SC, CH>;
-        case 11: return degenerate ? &k_gp_mfma16x4<T, true, 11, MODE, SC, CH> : &k_gp_mfma16x4<T, false, 11, MODE, SC, CH>;
-        case 12: return degenerate ? &k_gp_mfma16x4<T, true, 12, MODE, SC, CH> : &k_gp_mfma16x4<T, false, 12, MODE, SC, CH>;
-        default: break;
-        }
-    }
-    return nullptr;
+// after a kernel launch
+int launch_status() {
+    HIP_TRY(hipGetLastError());
+    return GAAST_OK;
 }
 
-// picks the (SCALED, CHAINED) instantiation of a dense kernel family: f(std::bool_constant<SC>, std::bool_constant<CH>)
+// grid of a persistent kernel: a workgroup per group of items, at most the `per_cu` workgroups per CU that are resident at once
+// (per_cu <= 0: not persistent, every group gets its workgroup)
+int64_t persistent_grid(int64_t groups, int per_cu) {
+    return per_cu > 0 ? std::min<int64_t>(groups, int64_t(g_num_cu) * per_cu) : groups;
+}
+
+int grid_for(int64_t total, int block) {   // grid-stride beyond 8 blocks per CU
+    return int(std::max<int64_t>(1, persistent_grid((total + block - 1) / block, 8)));
+}
+
+// 16-byte vector loads and stores of rows: base pointer and row pitch are multiples of 16 bytes
+template <typename T>
+bool rows_aligned16(const Bound& rows) {
+    return reinterpret_cast<uintptr_t>(rows.ptr) % 16 == 0 && (size_t(rows.stride) * sizeof(T)) % 16 == 0;
+}
+
+// A kernel chosen at gaast_hip_program_create is kept as its address; launch_kernel gives it its type back, from the arguments
+template <typename K>
+const void* kernel_address(K kern) { return reinterpret_cast<const void*>(kern); }
+template <typename... P>
+void launch_kernel(const void* kern, int64_t blocks, int threads, size_t lds, const P&... params) {
+    hipLaunchKernelGGL(reinterpret_cast<void (*)(P...)>(const_cast<void*>(kern)), dim3(unsigned(blocks)), dim3(unsigned(threads)), lds, g_stream, params...);
+}
+
+// Run-time values as template arguments, the one way a kernel family's instantiation is picked:
+// static_bools(f, b0, b1, ...) = f(std::bool_constant<b0>, std::bool_constant<b1>, ...)
 template <typename F>
-auto pick_variant(bool scaled, bool chained, F&& f) {
-    if (scaled && chained) return f(std::true_type{}, std::true_type{});
-    if (scaled) return f(std::true_type{}, std::false_type{});
-    if (chained) return f(std::false_type{}, std::true_type{});
-    return f(std::false_type{}, std::false_type{});
+auto static_bools(F&& f) { return f(); }
+template <typename F, typename... Bs>
+auto static_bools(F&& f, bool b, Bs... rest) {
+    return b ? static_bools([&](auto... t) { return f(std::true_type{}, t...); }, rest...)
+             : static_bools([&](auto... t) { return f(std::false_type{}, t...); }, rest...);
+}
+// static_int<V0, V1, ...>(v, f) = f(std::integral_constant<int, v>) if v is one of the Vs, else null: only the Vs are instantiated
+template <int... Vs, typename F>
+auto static_int(int v, F&& f) {
+    std::common_type_t<decltype(f(std::integral_constant<int, Vs>{}))...> r = nullptr;
+    (void)((v == Vs && ((r = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return r;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -364,6 +391,10 @@ constexpr int kLinmapMaxDim = 14;   // the compounds at n = 14: C(28,14) ~ 40 M 
 size_t linmap_small_lds(const LinmapDev& m, int64_t row_len, size_t elem) {
     return (size_t((m.mat_total + 3) & ~3) + size_t(2 * kLinmapItems) * size_t(row_len + 1)) * elem;
 }
+
+// k_linmap_small's vector row I/O asks more than rows_aligned16: the rows are packed as well (pitch = row length)
+template <typename T>
+bool rows_packed_aligned16(const Bound& rows, int64_t row_len) { return rows.stride == row_len && rows_aligned16<T>(rows); }
 
 template <typename T>
 int launch_linmap(const LinmapDev& m, const Layout& l, const Bound& in, const Bound& out, int64_t batch) {
@@ -392,19 +423,15 @@ int launch_linmap(const LinmapDev& m, const Layout& l, const Bound& in, const Bo
     }
     p.n_jobs = p.job0[p.n_grades];
     if (m.n <= kLinmapSmallMaxDim) {
-        auto vec_ok = [&](const Bound& b) {
-            return b.stride == l.row_len && reinterpret_cast<uintptr_t>(b.ptr) % 16 == 0 && (size_t(l.row_len) * sizeof(T)) % 16 == 0;
-        };
-        p.in_vec = vec_ok(in);
-        p.out_vec = vec_ok(out);
-        const int64_t blocks = std::min<int64_t>((batch + kLinmapItems - 1) / kLinmapItems, int64_t(g_num_cu) * m.small_blocks_per_cu);
+        p.in_vec = rows_packed_aligned16<T>(in, l.row_len);
+        p.out_vec = rows_packed_aligned16<T>(out, l.row_len);
+        const int64_t blocks = persistent_grid((batch + kLinmapItems - 1) / kLinmapItems, m.small_blocks_per_cu);
         hipLaunchKernelGGL(k_linmap_small<T>, dim3(unsigned(blocks)), dim3(256), linmap_small_lds(m, l.row_len, sizeof(T)), g_stream, p);
     } else {
         const int64_t tiles = std::min<int64_t>((batch + kLinmapBM - 1) / kLinmapBM, 65535);
         hipLaunchKernelGGL(k_linmap_mfma<T>, dim3(unsigned(p.n_jobs), unsigned(tiles)), dim3(256), 0, g_stream, p);
     }
-    HIP_TRY(hipGetLastError());
-    return GAAST_OK;
+    return launch_status();
 }
 
 const char* linmap_kernel_name(int n, int dtype) {
@@ -439,625 +466,710 @@ int linmap_build(int n, const double* mat, int dtype, LinmapDev& dev, std::vecto
     return GAAST_OK;
 }
 
-template <typename T>
-int prepare_step(Launch& L, const Layout& la, const Layout& lb, std::string& kernel) {
-    Step& s = L.s;
-    const int n = L.n;
-    constexpr bool is_f64 = std::is_same<T, double>::value;
-    const std::string tn = is_f64 ? "double" : "float";
-    const std::string dg = s.dense.degenerate ? "true" : "false";
-    // (SCALED, CHAINED) template arguments as they appear in the kernel's name: ",true" = rescaled basis, ",false,true" = chained
-    const std::string vs = s.dense.chained ? (s.dense.scaled ? ",true,true" : ",false,true") : (s.dense.scaled ? ",true" : "");
-    switch (s.kind) {
-    case Step::PRODUCT_CSR: {
-        const size_t per_item = size_t(la.row_len + lb.row_len) * sizeof(T);
-        if (per_item > g_max_lds)
-            return set_err(GAAST_ERR_UNIMPLEMENTED,
-                           "product operands of " + std::to_string(per_item) + " bytes per item do not fit the " +
-                               std::to_string(g_max_lds) + "-byte LDS of the list kernels (" + s.name + ")");
-        if (L.jit) {
-            // the chain (or single long-row list) specialised through hiprtc (plan_chain_jit.cpp: make_chain_jit): static LDS, persistent workgroups
-            L.threads = s.cj.threads;
-            L.lds = s.cj.lds;
-            kernel = "gaast_chain<" + tn + ">[" + (s.cj.single ? "one list, " : "") + std::to_string(s.cj.ipb) + " items, " + std::to_string(s.cj.threads) + " threads" +
-                      (s.cj.split > 1 ? ", rows in " + std::to_string(s.cj.split) + " slices: re-ordered sums" : "") +
-                      (s.cj.fmt[1] >= 3 ? ", sign-sorted terms" : "") + "]";
-            int per_cu = 0;
-            HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, L.jit.fn, L.threads, 0));
-            L.blocks_per_cu = per_cu < 1 ? 1 : per_cu;
-            return GAAST_OK;
+// ------------------------------------------------------------------------------------------
+// The launchers, one per kind of step (dispatch: prepare_launch, run_launch).  prepare_*: at gaast_hip_program_create, ONCE --
+// the step's tables go to the device, the launch configuration is fixed (which kernel instantiation, block size, dynamic LDS,
+// persistent grid) and `kernel` says which HIP kernel it is.  A step no kernel of this back end can run (operands beyond the
+// LDS budget) makes program_create fail with UNIMPLEMENTED: an eval then either runs every step or none.  run_*: per
+// evaluation -- the argument struct, the row form the bound rows allow, the launch; where a launcher has several kernels,
+// *variant says which it took.
+// ------------------------------------------------------------------------------------------
+// The rows of one evaluation: what every buffer reference of a step resolves to
+struct EvalRows {
+    const gaast_hip_program_s* prog;
+    const Layout* out_layout;
+    // per input slot and for the result: the rows as the caller bound them, and as the steps of a program in a non-orthonormal
+    // basis see them (moved into the orthogonal basis; the same rows in any other program)
+    std::vector<Bound> callers, moved;
+    Bound out_callers, out_moved;
+    Bound at(BufRef r, Layout* lay, bool callers_rows = false) const {
+        switch (r.kind) {
+        case BufKind::NODE: {
+            gaast_hip_mv_t m = prog->scratch[size_t(r.idx)].get();
+            *lay = m->layout;
+            return Bound{m->ptr, m->row_stride};
         }
-        if (s.chain.side) {
-            // two lists in one launch, the mid row in LDS (plan.cpp: chain_list_into_list): IPB items per workgroup
-            L.lds = size_t(s.chain.ent2_lds) + size_t(s.chain.item_stride) * size_t(s.chain.ipb) * sizeof(T);
-            if (L.lds > g_max_lds) return set_err(kChainTooBig, "list chain does not fit in LDS (" + s.name + ")");
-            const int64_t pairs2 = int64_t(s.list.row_out.size()) * s.chain.ipb;
-            L.threads = int(std::min<int64_t>(512, std::max<int64_t>(256, (pairs2 + 63) / 64 * 64)));
-            L.kern[0] = reinterpret_cast<const void*>(&k_product_ell_chain<T>);
-            kernel = "k_product_ell_chain<" + tn + ">";
-            if (int st = allow_lds(L.kern[0], L.lds)) return st;
-            return resident_blocks(L.kern[0], L.threads, L.lds, &L.blocks_per_cu);   // persistent workgroups
+        case BufKind::INPUT: *lay = prog->plan.input_layouts[size_t(r.idx)]; return (callers_rows ? callers : moved)[size_t(r.idx)];
+        default: *lay = *out_layout; return callers_rows ? out_callers : out_moved;
         }
-        L.lds = per_item;
-        L.threads = 256;
-        if (s.list.ell_width > 0) {
-            // items per pass over the list: as many as a 64 KiB share of LDS holds (at least one), at most 8
-            int items = int((64 * 1024) / per_item);
-            items = items >= 8 ? 8 : items >= 4 ? 4 : items >= 2 ? 2 : 1;
-            L.max_items = items;
-            using KernE = void (*)(EllArgs<T>);
-            const KernE tab[2][4] = {{&k_product_ell<T, 1, false>, &k_product_ell<T, 2, false>, &k_product_ell<T, 4, false>, &k_product_ell<T, 8, false>},
-                                     {&k_product_ell<T, 1, true>, &k_product_ell<T, 2, true>, &k_product_ell<T, 4, true>, &k_product_ell<T, 8, true>}};
-            kernel = "k_product_ell<" + tn + ",1.." + std::to_string(items) + "," + (s.list.ell_bytes ? "true" : "false") + ">";
-            for (int l2 = 0; (1 << l2) <= items; ++l2) {
-                L.kern[l2] = reinterpret_cast<const void*>(tab[s.list.ell_bytes ? 1 : 0][l2]);
-                if (int st = allow_lds(L.kern[l2], per_item << l2)) return st;
-            }
-            return GAAST_OK;
-        }
-        // enough items per block to give 256 threads work, within a 64 KiB LDS budget
-        const int n_rows = int(s.list.row_out.size());
-        int items = int((256 + n_rows - 1) / (n_rows > 0 ? n_rows : 1));
-        const size_t budget = 64 * 1024;
-        if (per_item * size_t(items) > budget) items = int(budget / per_item);
-        if (items < 1) items = 1;
-        L.max_items = items;
-        L.kern[0] = reinterpret_cast<const void*>(&k_product_csr<T>);
-        kernel = "k_product_csr<" + tn + ">";
-        return allow_lds(L.kern[0], per_item * size_t(items));
     }
-    case Step::PRODUCT_DENSE: {
-        switch (s.dense.family) {
-        case DenseFamily::SPINOR: {
-            using KernS = void (*)(SpinorArgs);
-            const int m = s.dense.spinor_m;
-            const size_t D = size_t(1) << m, plane = (D * (D + 1) + 63) / 64 * 64;
-            L.lds = (m == 6 ? 2 * plane + (is_f64 ? 0 : 16) : 2 * D * (D + 1)) * sizeof(T);   // k_gp_spinor12s: second plane 16 words further
-            const int lb5 = s.dense.spinor_lam_bit;
-            KernS kern = nullptr;
-            if (is_f64 && m == 6) kern = lb5 == 5 ? &k_gp_spinor12d<5> : lb5 == 4 ? &k_gp_spinor12d<4> : &k_gp_spinor12d<-1>;
-            else if (is_f64 && m == 5) kern = lb5 == 4 ? &k_gp_spinor_wave1d<5, 4> : lb5 == 3 ? &k_gp_spinor_wave1d<5, 3> : &k_gp_spinor_wave1d<5, -1>;
-            else if (is_f64) kern = lb5 == 3 ? &k_gp_spinor_wave1d<4, 3> : lb5 == 2 ? &k_gp_spinor_wave1d<4, 2> : &k_gp_spinor_wave1d<4, -1>;
-            else if (m == 6) {
-                kern = lb5 == 5 ? &k_gp_spinor12s<5, false> : lb5 == 4 ? &k_gp_spinor12s<4, false> : &k_gp_spinor12s<-1, false>;
-                const KernS fast = lb5 == 5 ? &k_gp_spinor12s<5, true> : lb5 == 4 ? &k_gp_spinor12s<4, true> : &k_gp_spinor12s<-1, true>;
-                L.kern[1] = reinterpret_cast<const void*>(fast);   // full, aligned rows on both sides and in the result
-                if (int st = allow_lds(L.kern[1], L.lds)) return st;
-            }
-            else if (m == 5) kern = lb5 == 4 ? &k_gp_spinor_wave1<5, 4> : lb5 == 3 ? &k_gp_spinor_wave1<5, 3> : &k_gp_spinor_wave1<5, -1>;
-            else kern = lb5 == 3 ? &k_gp_spinor_wave1<4, 3> : lb5 == 2 ? &k_gp_spinor_wave1<4, 2> : &k_gp_spinor_wave1<4, -1>;
-            L.kern[0] = reinterpret_cast<const void*>(kern);
-            kernel = (m == 6 ? (is_f64 ? "k_gp_spinor12d<" : "k_gp_spinor12s<") : (is_f64 ? "k_gp_spinor_wave1d<" : "k_gp_spinor_wave1<") + std::to_string(m) + ",") +
-                      std::to_string(lb5) + ">";
-            L.threads = m == 6 ? 256 : 64;
-            if (int st = allow_lds(L.kern[0], L.lds)) return st;
-            return resident_blocks(L.kern[0], L.threads, L.lds, &L.blocks_per_cu);
-        }
-        case DenseFamily::MFMA32:
-        case DenseFamily::MFMA32P:
-            if constexpr (!is_f64) {
-                const int wpi = 1 << (n - 10);                 // waves per item
-                L.threads = wpi > 4 ? wpi * 64 : 256;
-                L.items_per_block = (L.threads / 64) / wpi;
-                if (s.dense.family == DenseFamily::MFMA32P) {
-                    L.lds = (size_t(L.items_per_block) * size_t(4 << n) + 16) * sizeof(float);
-                    if (L.lds > g_max_lds) return set_err(GAAST_ERR_UNIMPLEMENTED, "dense product does not fit in LDS");
-                    using KernD = void (*)(DenseArgs<float>);
-                    const KernD kernp = pick_variant(s.dense.scaled, s.dense.chained, [&](auto sc, auto ch) -> KernD {
-                        constexpr bool SC = decltype(sc)::value, CH = decltype(ch)::value;
-                        return n == 10   ? (s.dense.degenerate ? &k_gp_mfma32p<true, 10, SC, CH> : &k_gp_mfma32p<false, 10, SC, CH>)
-                               : n == 11 ? (s.dense.degenerate ? &k_gp_mfma32p<true, 11, SC, CH> : &k_gp_mfma32p<false, 11, SC, CH>)
-                               : n == 12 ? (s.dense.degenerate ? &k_gp_mfma32p<true, 12, SC, CH> : &k_gp_mfma32p<false, 12, SC, CH>)
-                                         : (s.dense.degenerate ? &k_gp_mfma32p<true, 13, SC, CH> : &k_gp_mfma32p<false, 13, SC, CH>);
-                    });
-                    L.kern[0] = reinterpret_cast<const void*>(kernp);
-                    kernel = "k_gp_mfma32p<" + dg + "," + std::to_string(n) + vs + ">";
-                    if (int st = allow_lds(L.kern[0], L.lds)) return st;
-                    return resident_blocks(L.kern[0], L.threads, L.lds, &L.blocks_per_cu);   // persistent workgroups
-                }
-                L.lds = size_t(L.items_per_block) * size_t(2 << n) * sizeof(float);
-                if (L.lds > g_max_lds) return set_err(GAAST_ERR_UNIMPLEMENTED, "dense product does not fit in LDS");
-                using KernD = void (*)(DenseArgs<float>);
-                // (k_gp_mfma32 serves n = 14 only -- 16 waves and 128 KiB of LDS per item; n = 10 ... 13 run on k_gp_mfma32p)
-                if (L.threads != 1024) return set_err(GAAST_ERR_UNIMPLEMENTED, "k_gp_mfma32 is built for n = 14 only");
-                const KernD kern = pick_variant(s.dense.scaled, s.dense.chained, [&](auto sc, auto ch) -> KernD {
-                    constexpr bool SC = decltype(sc)::value, CH = decltype(ch)::value;
-                    return s.dense.degenerate ? &k_gp_mfma32<true, 1024, SC, CH> : &k_gp_mfma32<false, 1024, SC, CH>;
-                });
-                L.kern[0] = reinterpret_cast<const void*>(kern);
-                kernel = "k_gp_mfma32<" + dg + "," + std::to_string(L.threads) + vs + ">";
-                return allow_lds(L.kern[0], L.lds);
-            }
-            break;
-        case DenseFamily::MFMA16X4: {
-            // k_gp_mfma16x4<T>: one wave per 16 result columns, one item per workgroup (f64: n = 8 ... 12; f32: build switch)
-            L.threads = 64 << (n - 8);
-            L.items_per_block = 1;
-            L.lds = size_t(4 * (size_t(1) << n) + 32) * sizeof(T);   // +B, -B, +A, 16 spare, -A images, 16 zeros
-            if (L.lds > g_max_lds) return set_err(GAAST_ERR_UNIMPLEMENTED, "dense product does not fit in LDS");
-            using KernD = void (*)(DenseArgs<T>);
-            // [0]: general staging; [1]: register prefetch (full, contiguous, 16-byte aligned rows at launch); [2]: ... and
-            // every blade produced, nothing accumulated: straight-line result stores
-            auto pick = [&](auto mode_tag) -> KernD { return mfma16x4_kernel<T, decltype(mode_tag)::value, false, false>(n, s.dense.degenerate != 0); };
-            // a rescaled basis (general diagonal metric): general staging and stores only; a chained product: every mode
-            const KernD kd = pick_variant(s.dense.scaled, s.dense.chained, [&](auto sc, auto ch) -> KernD {
-                return mfma16x4_kernel<T, 0, decltype(sc)::value, decltype(ch)::value>(n, s.dense.degenerate != 0);
-            });
-            auto pick_chained = [&](auto mode_tag) -> KernD { return mfma16x4_kernel<T, decltype(mode_tag)::value, false, true>(n, s.dense.degenerate != 0); };
-            const bool chained_fast = s.dense.chained && !s.dense.scaled;
-            const KernD kf = chained_fast ? pick_chained(std::integral_constant<int, 1>{}) : pick(std::integral_constant<int, 1>{}),
-                        kw = chained_fast ? pick_chained(std::integral_constant<int, 2>{}) : pick(std::integral_constant<int, 2>{});
-            if (!kd || !kf || !kw) return set_err(GAAST_ERR_UNIMPLEMENTED, "no k_gp_mfma16x4 instantiation for this dimension and value type");
-            L.kern[0] = reinterpret_cast<const void*>(kd);
-            L.kern[1] = reinterpret_cast<const void*>(kf);
-            L.kern[2] = reinterpret_cast<const void*>(kw);
-            kernel = "k_gp_mfma16x4<" + tn + "," + dg + "," + std::to_string(n) + (s.dense.scaled ? ",0" + vs + ">" : ",0|1|2" + vs + ">");   // staging / store mode: by alignment at launch
-            for (int v = 0; v < 3; ++v)
-                if (int st = allow_lds(L.kern[v], L.lds)) return st;
-            return resident_blocks(L.kern[1], L.threads, L.lds, &L.blocks_per_cu);   // persistent workgroups
-        }
-        case DenseFamily::MFMA6: {
-            // k_gp_mfma6<T>: one wave per item, persistent single-wave workgroups, 2 KiB (f32) / 4 KiB (f64) of operand images
-            L.threads = 64 * GAAST_MFMA6_WAVES;
-            L.items_per_block = GAAST_MFMA6_WAVES;
-            L.lds = (size_t(is_f64 ? 4096 : 2048) + 64 * sizeof(T)) * GAAST_MFMA6_WAVES;   // + a dummy element per lane (stores of vanishing slots)
-            using KernD = void (*)(DenseArgs<T>);
-            // [0]: any operands (partial grade sets, projected or accumulated results); [1]: full operands, every blade produced, nothing
-            // accumulated -- straight-line item loop with counted waits
-            const KernD k6 = s.dense.scaled ? &k_gp_mfma6<T, true, false> : &k_gp_mfma6<T, false, false>;
-            const KernD k6f = s.dense.scaled ? &k_gp_mfma6<T, true, true> : &k_gp_mfma6<T, false, true>;
-            L.kern[0] = reinterpret_cast<const void*>(k6);
-            L.kern[1] = reinterpret_cast<const void*>(k6f);
-            kernel = "k_gp_mfma6<" + tn + (s.dense.scaled ? ",true,0|1>" : ",false,0|1>");
-            return resident_blocks(L.kern[1], L.threads, L.lds, &L.blocks_per_cu);
-        }
-        case DenseFamily::MFMA7: {
-            // k_gp_mfma7<T>: one wave per item, single-wave workgroups
-            L.threads = 64;
-            L.items_per_block = 1;
-            L.lds = size_t(560) * sizeof(T);   // +B, -B, +A (u = 1 half 72 further), -A 144 further, 16 zeros
-            using KernD = void (*)(DenseArgs<T>);
-            const KernD kd = pick_variant(s.dense.scaled, s.dense.chained, [&](auto sc, auto ch) -> KernD {
-                return &k_gp_mfma7<T, 0, decltype(sc)::value, decltype(ch)::value>;
-            });
-            const bool chained_fast = s.dense.chained && !s.dense.scaled;
-            const KernD kf = chained_fast ? &k_gp_mfma7<T, 1, false, true> : &k_gp_mfma7<T, 1>;
-            const KernD kw = chained_fast ? &k_gp_mfma7<T, 2, false, true> : &k_gp_mfma7<T, 2>;
-            L.kern[0] = reinterpret_cast<const void*>(kd);
-            L.kern[1] = reinterpret_cast<const void*>(kf);
-            L.kern[2] = reinterpret_cast<const void*>(kw);
-            kernel = "k_gp_mfma7<" + tn + (s.dense.scaled ? ",0" + vs + ">" : ",0|1|2" + vs + ">");   // (null vectors: run-time, no instantiation of their own)
-            return resident_blocks(L.kern[1], L.threads, L.lds, &L.blocks_per_cu);   // persistent single-wave workgroups
-        }
-        case DenseFamily::VECTOR_FMA: break;
-        }
-        const int lpi = 1 << (n - 4);
-        L.threads = lpi > 256 ? lpi : 256;
-        L.items_per_block = L.threads / lpi;
-        L.lds = size_t(L.items_per_block) * size_t(2 * (1 << n) + (L.items_per_block > 1 ? 4 : 0)) * sizeof(T);
-        if (L.lds > g_max_lds)
-            return set_err(GAAST_ERR_UNIMPLEMENTED, "dense product of dimension " + std::to_string(n) + " does not fit in LDS");
-        using KernD = void (*)(DenseArgs<T>);
-        const KernD kern = pick_variant(s.dense.scaled, s.dense.chained, [&](auto sc, auto ch) -> KernD {
-            constexpr bool SC = decltype(sc)::value, CH = decltype(ch)::value;
-            if (s.dense.neg_lo_all)
-                return L.threads == 256 ? (s.dense.degenerate ? &k_gp_dense<T, true, 256, true, SC, CH> : &k_gp_dense<T, false, 256, true, SC, CH>)
-                                        : (s.dense.degenerate ? &k_gp_dense<T, true, 512, true, SC, CH> : &k_gp_dense<T, false, 512, true, SC, CH>);
-            return L.threads == 256 ? (s.dense.degenerate ? &k_gp_dense<T, true, 256, false, SC, CH> : &k_gp_dense<T, false, 256, false, SC, CH>)
-                                    : (s.dense.degenerate ? &k_gp_dense<T, true, 512, false, SC, CH> : &k_gp_dense<T, false, 512, false, SC, CH>);
-        });
-        L.kern[0] = reinterpret_cast<const void*>(kern);
-        kernel = "k_gp_dense<" + tn + "," + dg + "," + std::to_string(L.threads) + "," + (s.dense.neg_lo_all ? "true" : "false") + vs + ">";
-        if (int st = allow_lds(L.kern[0], L.lds)) return st;
-        // persistent workgroups: as many as are resident at once (register- and LDS-limited)
-        return resident_blocks(L.kern[0], L.threads, L.lds, &L.blocks_per_cu);
-    }
-    case Step::ELEMENTWISE:
-        kernel = "k_elementwise<" + tn + (s.ew.n_ops <= 4 ? ",4>" : ",8>");
-        return GAAST_OK;
-    case Step::AXPY: kernel = "k_axpy_map<" + tn + ">"; return GAAST_OK;
-    case Step::FLIP: kernel = "k_flip<" + tn + ">"; return GAAST_OK;
-    case Step::SUNARY: kernel = "k_scalar_unary<" + tn + ">"; return GAAST_OK;
-    case Step::EXPLOG_ADJ: {
-        // the rows of a workgroup's items through LDS whenever at least a wave's worth of items fits 64 KiB (no attribute to raise,
-        // several workgroups per CU); an item's rows `stride` elements apart, odd.  Otherwise the direct form (max_items = 0).
-        const size_t stride = size_t(la.row_len + lb.row_len) | 1;
-        const size_t fit = (64 * 1024) / (stride * sizeof(T));
-        L.threads = 256;
-        L.max_items = fit >= 256 ? 256 : int(fit / 64 * 64);
-        L.lds = stride * sizeof(T);   // per staged item
-        L.kern[0] = s.adj.op == 0 ? reinterpret_cast<const void*>(&k_exp_log_adj<T, 0>) : reinterpret_cast<const void*>(&k_exp_log_adj<T, 1>);
-        kernel = "k_exp_log_adj<" + tn + "," + std::to_string(s.adj.op) + ">" + (L.max_items ? "[" + std::to_string(L.max_items) + " items through LDS]" : "[direct rows]");
-        return GAAST_OK;
-    }
-    case Step::REDUCE_SCALE: {
-        L.threads = 256;
-        L.kern[0] = reinterpret_cast<const void*>(&k_reduce_scale<T>);
-        kernel = "k_reduce_scale<" + tn + ">";
-        if (s.reduce.wave) {   // tolerance mode: one wave per item, the row read once -- taken at launch when the three rows are one (run_step)
-            using KernW = void (*)(ReduceScaleArgs<T>, const uint32_t*);
-            KernW kw = nullptr;
-            switch (s.reduce.wave) {
-            case 1: kw = &k_reduce_scale_wave<T, 1>; break;
-            case 2: kw = &k_reduce_scale_wave<T, 2>; break;
-            case 4: kw = &k_reduce_scale_wave<T, 4>; break;
-            case 8: kw = &k_reduce_scale_wave<T, 8>; break;
-            case 16:
-                if constexpr (sizeof(T) == 8) kw = &k_reduce_scale_wave<T, 16>;
-                break;
-            default: break;
-            }
-            L.kern[1] = reinterpret_cast<const void*>(kw);
-            if (kw) kernel += " | k_reduce_scale_wave<" + tn + "," + std::to_string(s.reduce.wave) + "> (lane-parallel sums) when the rows are one";
-            else s.reduce.wave = 0;
-        }
-        return resident_blocks(L.kern[0], L.threads, 0, &L.blocks_per_cu);
-    }
-    case Step::FUSED: {
-        if (L.jit) return GAAST_OK;
-        const size_t lds = (size_t(s.fused.slab) * FUSED_ITEMS + 8) * sizeof(T);
-        return allow_lds(reinterpret_cast<const void*>(&k_ast_fused<T>), lds);
-    }
-    case Step::LINMAP:
-        kernel = linmap_kernel_name(L.linmap->n, is_f64 ? GAAST_F64 : GAAST_F32);
-        return GAAST_OK;
-    default: return GAAST_OK;
-    }
-}
+};
 
-// the operands of a launch beyond a and b (Step: pre.a, pre.b, reduce.x, cj.init_src); null where the step has none
-struct Extra {
-    Bound pre_a{nullptr, 0}, pre_b{nullptr, 0}, scaled_row{nullptr, 0}, init{nullptr, 0};
+// ... and the operands of one launch among them (null where the step has none)
+struct Operands {
+    Bound res{nullptr, 0}, a{nullptr, 0}, b{nullptr, 0};
+    Layout lres, la, lb;
+    Bound pre_a{nullptr, 0}, pre_b{nullptr, 0}, scaled_row{nullptr, 0}, init{nullptr, 0};   // Step: pre.a, pre.b, reduce.x, cj.init_src
+    const EvalRows* rows = nullptr;   // FUSED, ELEMENTWISE: they read by slot and by source list
 };
 
 template <typename T>
-int run_step(const Launch& L, const Bound& res, const Bound& a, const Bound& b, const Layout& la, const Layout& lb, int64_t batch,
-             const Extra& x = Extra()) {
+const char* type_name() { return std::is_same<T, double>::value ? "double" : "float"; }
+
+// L.X from s.X: an index table as it is, a value table in the program's dtype T.  The first failure sticks.
+template <typename T>
+struct Upload {
+    int status = GAAST_OK;
+    template <typename I>
+    void idx(DevTable& dev, std::vector<I>& host) { if (!status) status = dev.upload(std::move(host)); }
+    void val(DevTable& dev, std::vector<double>& host) { if (!status) status = dev.upload(std::move(host), std::is_same<T, double>::value ? GAAST_F64 : GAAST_F32); }
+};
+
+// ---- AXPY, FLIP, SUNARY --------------------------------------------------------------------------------------------------
+template <typename T>
+int prepare_trivial(Launch& L, std::string& kernel) {
+    Step& s = L.s;
+    Upload<T> up;
+    up.idx(L.trivial.axpy_map, s.axpy_map);
+    up.idx(L.trivial.flip_offsets, s.flip_offsets);
+    kernel = std::string(s.kind == Step::AXPY ? "k_axpy_map<" : s.kind == Step::FLIP ? "k_flip<" : "k_scalar_unary<") + type_name<T>() + ">";
+    return up.status;
+}
+
+template <typename T>
+int run_trivial(const Launch& L, const Operands& o, int64_t batch) {
     const Step& s = L.s;
-    const int n = L.n;
-    switch (s.kind) {
-    case Step::ZERO: return GAAST_OK;  // handled by the caller (needs the row length)
-    case Step::AXPY: {
-        const int nm = int(L.axpy_map.count);
+    if (s.kind == Step::AXPY) {
+        const int nm = int(L.trivial.axpy_map.count);
         hipLaunchKernelGGL(k_axpy_map<T>, dim3(grid_for(batch * nm, 256)), dim3(256), 0, g_stream,
-                           static_cast<T*>(res.ptr), res.stride, static_cast<const T*>(a.ptr), a.stride,
-                           L.axpy_map.as<uint32_t>(), nm, batch, s.beta);
-        break;
-    }
-    case Step::FLIP: {
-        const int nm = int(L.flip_offsets.count);
+                           static_cast<T*>(o.res.ptr), o.res.stride, static_cast<const T*>(o.a.ptr), o.a.stride,
+                           L.trivial.axpy_map.as<uint32_t>(), nm, batch, s.beta);
+    } else if (s.kind == Step::FLIP) {
+        const int nm = int(L.trivial.flip_offsets.count);
         hipLaunchKernelGGL(k_flip<T>, dim3(grid_for(batch * nm, 256)), dim3(256), 0, g_stream,
-                           static_cast<T*>(res.ptr), res.stride, L.flip_offsets.as<uint32_t>(), nm, batch);
-        break;
-    }
-    case Step::SUNARY:
+                           static_cast<T*>(o.res.ptr), o.res.stride, L.trivial.flip_offsets.as<uint32_t>(), nm, batch);
+    } else {
         hipLaunchKernelGGL(k_scalar_unary<T>, dim3(grid_for(batch, 256)), dim3(256), 0, g_stream,
-                           static_cast<T*>(res.ptr), res.stride, s.sunary_off, s.sunary_op, batch);
-        break;
-    case Step::REDUCE_SCALE: {
-        ReduceScaleArgs<T> q;
-        q.l1 = static_cast<const T*>(a.ptr);
-        q.r1 = static_cast<const T*>(b.ptr);
-        q.x = static_cast<const T*>(x.scaled_row.ptr);
+                           static_cast<T*>(o.res.ptr), o.res.stride, s.sunary_off, s.sunary_op, batch);
+    }
+    return launch_status();
+}
+
+// ---- LINMAP --------------------------------------------------------------------------------------------------------------
+// (nothing to prepare but the kernel's name; its operands are the caller's rows: run_launches)
+template <typename T>
+int run_linmap(const Launch& L, const Operands& o, int64_t batch) {
+    const bool shared = L.s.a.kind == BufKind::INPUT && o.a.stride == 0;   // an input shared by every item: moved once
+    return launch_linmap<T>(*L.linmap, o.la, o.a, o.res, shared ? 1 : batch);
+}
+
+// What the argument struct of every product kernel (CsrArgs, EllArgs, DenseArgs, SpinorArgs) holds under the same names
+template <typename T, typename Args>
+void product_operands(Args& q, const Step& s, const Operands& o, int64_t batch) {
+    q.left = static_cast<const T*>(o.a.ptr);
+    q.right = static_cast<const T*>(o.b.ptr);
+    q.out = static_cast<T*>(o.res.ptr);
+    q.left_stride = o.a.stride;
+    q.right_stride = o.b.stride;
+    q.out_stride = o.res.stride;
+    q.canon_left = s.canon_a;
+    q.canon_right = s.canon_b;
+    q.beta = s.beta;
+    q.batch = batch;
+}
+
+// ---- PRODUCT_CSR: a comp-mul list (CSR or ELL form), two chained lists, or the list chain specialised through hiprtc -------
+template <typename T>
+int prepare_list(Launch& L, const Layout& la, const Layout& lb, std::string& kernel) {
+    Step& s = L.s;
+    auto& c = L.list;
+    const std::string tn = type_name<T>();
+    Upload<T> up;
+    up.idx(c.row_start, s.list.row_start); up.idx(c.row_out, s.list.row_out); up.idx(c.entries, s.list.entries); up.val(c.coeff, s.list.coeff);
+    if (L.jit) {   // the specialised kernel has tables of its own: cj, not pre
+        up.idx(c.cj.ent1, s.cj.ent1); up.idx(c.cj.pos1, s.cj.pos1); up.idx(c.cj.ent2, s.cj.ent2); up.idx(c.cj.out2, s.cj.out2);
+    } else {
+        up.idx(c.pre.entries, s.pre.entries); up.idx(c.pre.row_map, s.pre.row_map);
+    }
+    if (up.status) return up.status;
+    const size_t per_item = size_t(la.row_len + lb.row_len) * sizeof(T);
+    if (per_item > g_max_lds)
+        return set_err(GAAST_ERR_UNIMPLEMENTED,
+                       "product operands of " + std::to_string(per_item) + " bytes per item do not fit the " +
+                           std::to_string(g_max_lds) + "-byte LDS of the list kernels (" + s.name + ")");
+    if (L.jit) {
+        // the chain (or single long-row list) specialised through hiprtc (plan_chain_jit.cpp: make_chain_jit): static LDS, persistent workgroups
+        c.chain_threads = s.cj.threads;
+        kernel = "gaast_chain<" + tn + ">[" + (s.cj.single ? "one list, " : "") + std::to_string(s.cj.ipb) + " items, " + std::to_string(s.cj.threads) + " threads" +
+                  (s.cj.split > 1 ? ", rows in " + std::to_string(s.cj.split) + " slices: re-ordered sums" : "") +
+                  (s.cj.fmt[1] >= 3 ? ", sign-sorted terms" : "") + "]";
+        int per_cu = 0;
+        HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, L.jit.fn, c.chain_threads, 0));
+        c.chain_blocks_per_cu = per_cu < 1 ? 1 : per_cu;
+        return GAAST_OK;
+    }
+    if (s.chain.side) {
+        // two lists in one launch, the mid row in LDS (plan.cpp: chain_list_into_list): IPB items per workgroup
+        c.chain_bytes = size_t(s.chain.ent2_lds) + size_t(s.chain.item_stride) * size_t(s.chain.ipb) * sizeof(T);
+        if (c.chain_bytes > g_max_lds) return set_err(kChainTooBig, "list chain does not fit in LDS (" + s.name + ")");
+        const int64_t pairs2 = int64_t(c.row_out.count) * s.chain.ipb;
+        c.chain_threads = int(std::min<int64_t>(512, std::max<int64_t>(256, (pairs2 + 63) / 64 * 64)));
+        const void* kern = kernel_address(&k_product_ell_chain<T>);
+        kernel = "k_product_ell_chain<" + tn + ">";
+        if (int st = allow_lds(kern, c.chain_bytes)) return st;
+        return resident_blocks(kern, c.chain_threads, c.chain_bytes, &c.chain_blocks_per_cu);   // persistent workgroups
+    }
+    c.bytes_per_item = per_item;
+    if (s.list.ell_width > 0) {
+        // items per pass over the list: as many as a 64 KiB share of LDS holds (at least one), at most 8
+        const int fit = int((64 * 1024) / per_item);
+        c.ell_max_log2 = fit >= 8 ? 3 : fit >= 4 ? 2 : fit >= 2 ? 1 : 0;
+        using KernE = void (*)(EllArgs<T>);
+        const KernE tab[2][4] = {{&k_product_ell<T, 1, false>, &k_product_ell<T, 2, false>, &k_product_ell<T, 4, false>, &k_product_ell<T, 8, false>},
+                                 {&k_product_ell<T, 1, true>, &k_product_ell<T, 2, true>, &k_product_ell<T, 4, true>, &k_product_ell<T, 8, true>}};
+        kernel = "k_product_ell<" + tn + ",1.." + std::to_string(1 << c.ell_max_log2) + "," + (s.list.ell_bytes ? "true" : "false") + ">";
+        for (int l2 = 0; l2 <= c.ell_max_log2; ++l2) {
+            c.ell[l2] = kernel_address(tab[s.list.ell_bytes ? 1 : 0][l2]);
+            if (int st = allow_lds(c.ell[l2], per_item << l2)) return st;
+        }
+        return GAAST_OK;
+    }
+    // enough items per block to give 256 threads work, within a 64 KiB LDS budget
+    const int n_rows = int(c.row_out.count);
+    int items = int((256 + n_rows - 1) / (n_rows > 0 ? n_rows : 1));
+    const size_t budget = 64 * 1024;
+    if (per_item * size_t(items) > budget) items = int(budget / per_item);
+    if (items < 1) items = 1;
+    c.csr_items = items;
+    kernel = "k_product_csr<" + tn + ">";
+    return allow_lds(kernel_address(&k_product_csr<T>), per_item * size_t(items));
+}
+
+template <typename T>
+int run_list(const Launch& L, const Operands& o, int64_t batch, int* variant) {
+    const Step& s = L.s;
+    const auto& c = L.list;
+    const Bound &res = o.res, &a = o.a, &b = o.b;
+    if (L.jit) {
+        const bool mid_left = s.chain.side == 1, single = s.cj.single != 0;
+        const Bound& other = single ? b : s.chain.alias ? o.pre_a : (mid_left ? b : a);
+        // a single list: its left operand is staged as the "mid" row (pointer l1), its right one is list 2's own operand (r2)
+        const void *l1 = single ? a.ptr : o.pre_a.ptr, *r1 = single ? nullptr : o.pre_b.ptr, *r2 = other.ptr;
+        long long s_l1 = single ? a.stride : o.pre_a.stride, s_r1 = single ? 0 : o.pre_b.stride, s_r2 = other.stride, s_out = res.stride, nb = batch;
+        void* optr = res.ptr;
+        const void *e1 = c.cj.ent1.ptr, *p1 = c.cj.pos1.ptr, *e2 = c.cj.ent2.ptr, *o2 = c.cj.out2.ptr;
+        const void* init = o.init.ptr;   // the folded copy's source, if any
+        long long s_init = o.init.stride;
+        void* args[] = {&l1, &s_l1, &r1, &s_r1, &r2, &s_r2, &optr, &s_out, &e1, &p1, &e2, &o2, &nb, &init, &s_init};
+        const int64_t blocks = persistent_grid((batch + s.cj.ipb - 1) / s.cj.ipb, c.chain_blocks_per_cu);
+        // (the argument block is copied into the dispatch packet at call time, like run_fused's)
+        HIP_TRY(hipModuleLaunchKernel(L.jit.fn, unsigned(blocks), 1, 1, unsigned(c.chain_threads), 1, 1, 0, g_stream,
+                                      args, nullptr));
+    } else if (s.chain.side) {
+        EllChainArgs<T> q;
+        const bool mid_left = s.chain.side == 1;
+        const Bound& other = mid_left ? b : a;
+        const Layout& lo = mid_left ? o.lb : o.la;
+        q.l1 = static_cast<const T*>(o.pre_a.ptr);
+        q.r1 = static_cast<const T*>(o.pre_b.ptr);
+        q.r2 = static_cast<const T*>(other.ptr);
         q.out = static_cast<T*>(res.ptr);
-        q.l1_stride = a.stride;
-        q.r1_stride = b.stride;
-        q.x_stride = x.scaled_row.stride;
+        q.l1_stride = o.pre_a.stride;
+        q.r1_stride = o.pre_b.stride;
+        q.r2_stride = other.stride;
         q.out_stride = res.stride;
-        q.ent1 = L.reduce.ent1.as<uint32_t>();
-        q.coeff1 = L.reduce.coeff1.as<T>();
-        q.ent2 = L.reduce.ent2.as<uint32_t>();
-        q.coeff2 = L.reduce.coeff2.as<T>();
-        q.n1 = int(L.reduce.ent1.count);
-        q.n2 = int(L.reduce.ent2.count);
-        q.canon_l1 = s.canon_a;
-        q.canon_r1 = s.canon_b;
-        q.canon_x = s.reduce.canon_x;
-        q.canon_s = s.reduce.canon_s;
-        q.s_is_left = s.reduce.s_is_left;
-        q.op = s.reduce.op;
+        q.l1_len = s.pre.left_len;
+        q.r1_len = s.pre.right_len;
+        q.r2_len = int(lo.row_len);
+        q.mid_len = s.chain.mid_len;
+        q.canon_l1 = s.pre.canon_a;
+        q.canon_r1 = s.pre.canon_b;
+        q.canon_r2 = mid_left ? s.canon_b : s.canon_a;
+        q.canon_mid = s.chain.canon_mid;
+        q.ent1 = c.pre.entries.as<uint32_t>();
+        q.pos1 = c.pre.row_map.as<uint32_t>();
+        q.rows1 = int(c.pre.row_map.count);
+        q.width1 = s.pre.width;
+        q.ent2 = c.entries.as<uint32_t>();
+        q.out2 = c.row_out.as<uint32_t>();
+        q.rows2 = int(c.row_out.count);
+        q.width2 = s.list.ell_width;
+        q.mid_is_left = mid_left ? 1 : 0;
+        q.r2_alias = s.chain.alias;
+        q.mid_covered = s.chain.covered;
+        q.beta = s.beta;
+        q.ipb = s.chain.ipb;
+        q.item_stride = s.chain.item_stride;
         q.batch = batch;
-        if (s.reduce.wave && L.kern[1] && a.ptr == b.ptr && a.ptr == x.scaled_row.ptr && a.stride == b.stride && a.stride == x.scaled_row.stride &&
-            (reinterpret_cast<uintptr_t>(a.ptr) & 15u) == 0 && (size_t(a.stride) * sizeof(T)) % 16 == 0 &&
-            (reinterpret_cast<uintptr_t>(res.ptr) & 15u) == 0 && (size_t(res.stride) * sizeof(T)) % 16 == 0 && res.ptr != a.ptr) {
-            // one wave per item, four per workgroup, persistent
-            using KernW = void (*)(ReduceScaleArgs<T>, const uint32_t*);
-            int64_t blocks = (batch + 3) / 4;
-            blocks = std::min<int64_t>(blocks, int64_t(g_num_cu) * 8);
-            L.variant = 1;
-            hipLaunchKernelGGL(reinterpret_cast<KernW>(const_cast<void*>(L.kern[1])), dim3(unsigned(blocks)), dim3(256), 0, g_stream, q,
-                               L.reduce.sign_words.as<uint32_t>());
-            break;
-        }
-        // sixteen items per wave, four waves per workgroup, persistent: as many workgroups as are resident at once
-        int64_t blocks = (batch + 63) / 64;
-        blocks = std::min<int64_t>(blocks, int64_t(g_num_cu) * (L.blocks_per_cu > 0 ? L.blocks_per_cu : 8));
-        hipLaunchKernelGGL(k_reduce_scale<T>, dim3(unsigned(blocks)), dim3(256), 0, g_stream, q);
-        break;
-    }
-    case Step::EXPLOG: {
-        ExpLogArgs<T> q;
-        q.res = static_cast<T*>(res.ptr);
-        q.arg = static_cast<const T*>(a.ptr);
-        q.res_stride = res.stride;
-        q.arg_stride = a.stride;
-        q.op = s.explog.op;
-        q.m = s.explog.m;
-        q.m_res = s.explog.mres;
-        q.arg_k = s.explog.arg_k;
-        q.arg_0 = s.explog.arg_0;
-        q.res_k = s.explog.res_k;
-        q.res_0 = s.explog.res_0;
-        q.sq = L.explog.sq.as<T>();
-        q.row_start = L.explog.row_start.as<uint32_t>();
-        q.pairs = L.explog.pairs.as<uint32_t>();
-        q.pair_coeff = L.explog.pair_coeff.as<T>();
-        q.n_rows = int(L.explog.row_start.count) - 1;
-        q.dom = static_cast<unsigned long long*>(L.domain);
-        q.batch = batch;
-        hipLaunchKernelGGL(k_exp_log<T>, dim3(grid_for(batch, 256)), dim3(256), 0, g_stream, q);
-        break;
-    }
-    case Step::EXPLOG_ADJ: {
-        ExpLogAdjArgs<T> q;
-        q.res = static_cast<T*>(res.ptr);
-        q.arg = static_cast<const T*>(a.ptr);
-        q.cot = static_cast<const T*>(b.ptr);
-        q.res_stride = res.stride;
-        q.arg_stride = a.stride;
-        q.cot_stride = b.stride;
-        q.m = s.adj.m;
-        q.m_g = s.adj.mg;
-        q.m_res = s.adj.res_k >= 0 ? s.adj.mres : 0;
-        q.arg_k = s.adj.arg_k;
-        q.arg_0 = s.adj.arg_0;
-        q.g_k = s.adj.g_k;
-        q.g_0 = s.adj.g_0;
-        q.res_k = s.adj.res_k;
-        q.res_0 = s.adj.res_0;
-        q.arg_len = int(la.row_len);
-        q.cot_len = int(lb.row_len);
-        q.items = L.max_items;
-        q.lds_stride = int(L.lds / sizeof(T));
-        q.sq = L.adj.sq.as<T>();
-        q.batch = batch;
-        using KernA = void (*)(ExpLogAdjArgs<T>);
-        const int64_t groups = (batch + (q.items ? q.items : 256) - 1) / (q.items ? q.items : 256);
-        hipLaunchKernelGGL(reinterpret_cast<KernA>(const_cast<void*>(L.kern[0])), dim3(unsigned(std::min<int64_t>(groups, int64_t(g_num_cu) * 8))),
-                           dim3(256), L.lds * size_t(q.items), g_stream, q);
-        break;
-    }
-    case Step::PRODUCT_CSR: {
-        if (L.jit) {
-            const bool mid_left = s.chain.side == 1, single = s.cj.single != 0;
-            const Bound& other = single ? b : s.chain.alias ? x.pre_a : (mid_left ? b : a);
-            // a single list: its left operand is staged as the "mid" row (pointer l1), its right one is list 2's own operand (r2)
-            const void *l1 = single ? a.ptr : x.pre_a.ptr, *r1 = single ? nullptr : x.pre_b.ptr, *r2 = other.ptr;
-            long long s_l1 = single ? a.stride : x.pre_a.stride, s_r1 = single ? 0 : x.pre_b.stride, s_r2 = other.stride, s_out = res.stride, nb = batch;
-            void* optr = res.ptr;
-            const void *e1 = L.cj.ent1.ptr, *p1 = L.cj.pos1.ptr, *e2 = L.cj.ent2.ptr, *o2 = L.cj.out2.ptr;
-            const void* init = x.init.ptr;   // the folded copy's source, if any
-            long long s_init = x.init.stride;
-            void* args[] = {&l1, &s_l1, &r1, &s_r1, &r2, &s_r2, &optr, &s_out, &e1, &p1, &e2, &o2, &nb, &init, &s_init};
-            int64_t blocks = (batch + s.cj.ipb - 1) / s.cj.ipb;
-            blocks = std::min<int64_t>(blocks, int64_t(g_num_cu) * L.blocks_per_cu);
-            // (the argument block is copied into the dispatch packet at call time, like run_jit's)
-            HIP_TRY(hipModuleLaunchKernel(L.jit.fn, unsigned(blocks), 1, 1, unsigned(L.threads), 1, 1, 0, g_stream,
-                                          args, nullptr));
-            break;
-        }
-        if (s.chain.side) {
-            EllChainArgs<T> q;
-            const bool mid_left = s.chain.side == 1;
-            const Bound& other = mid_left ? b : a;
-            const Layout& lo = mid_left ? lb : la;
-            q.l1 = static_cast<const T*>(x.pre_a.ptr);
-            q.r1 = static_cast<const T*>(x.pre_b.ptr);
-            q.r2 = static_cast<const T*>(other.ptr);
-            q.out = static_cast<T*>(res.ptr);
-            q.l1_stride = x.pre_a.stride;
-            q.r1_stride = x.pre_b.stride;
-            q.r2_stride = other.stride;
-            q.out_stride = res.stride;
-            q.l1_len = s.pre.left_len;
-            q.r1_len = s.pre.right_len;
-            q.r2_len = int(lo.row_len);
-            q.mid_len = s.chain.mid_len;
-            q.canon_l1 = s.pre.canon_a;
-            q.canon_r1 = s.pre.canon_b;
-            q.canon_r2 = mid_left ? s.canon_b : s.canon_a;
-            q.canon_mid = s.chain.canon_mid;
-            q.ent1 = L.pre.entries.as<uint32_t>();
-            q.pos1 = L.pre.row_map.as<uint32_t>();
-            q.rows1 = int(L.pre.row_map.count);
-            q.width1 = s.pre.width;
-            q.ent2 = L.list.entries.as<uint32_t>();
-            q.out2 = L.list.row_out.as<uint32_t>();
-            q.rows2 = int(L.list.row_out.count);
-            q.width2 = s.list.ell_width;
-            q.mid_is_left = mid_left ? 1 : 0;
-            q.r2_alias = s.chain.alias;
-            q.mid_covered = s.chain.covered;
-            q.beta = s.beta;
-            q.ipb = s.chain.ipb;
-            q.item_stride = s.chain.item_stride;
-            q.batch = batch;
-            q.ent2_lds_bytes = s.chain.ent2_lds;
-            int64_t blocks = (batch + s.chain.ipb - 1) / s.chain.ipb;
-            if (L.blocks_per_cu > 0) blocks = std::min<int64_t>(blocks, int64_t(g_num_cu) * L.blocks_per_cu);
-            hipLaunchKernelGGL(k_product_ell_chain<T>, dim3(unsigned(blocks)), dim3(unsigned(L.threads)), L.lds, g_stream, q);
-            break;
-        }
-        if (s.list.ell_width > 0) {
-            EllArgs<T> q;
-            q.left = static_cast<const T*>(a.ptr);
-            q.right = static_cast<const T*>(b.ptr);
-            q.out = static_cast<T*>(res.ptr);
-            q.left_stride = a.stride;
-            q.right_stride = b.stride;
-            q.out_stride = res.stride;
-            q.left_len = int(la.row_len);
-            q.right_len = int(lb.row_len);
-            q.canon_left = s.canon_a;
-            q.canon_right = s.canon_b;
-            q.row_out = L.list.row_out.as<uint32_t>();
-            q.entries = L.list.entries.as<uint32_t>();
-            q.n_rows = int(L.list.row_out.count);
-            q.width = s.list.ell_width;
-            q.beta = s.beta;
-            q.batch = batch;
-            int l2 = L.max_items >= 8 ? 3 : L.max_items >= 4 ? 2 : L.max_items >= 2 ? 1 : 0;
-            while (l2 > 0 && (int64_t(1) << l2) > batch) --l2;
-            using KernE = void (*)(EllArgs<T>);
-            const int64_t blocks = (batch + (int64_t(1) << l2) - 1) >> l2;
-            L.variant = l2;
-            hipLaunchKernelGGL(reinterpret_cast<KernE>(const_cast<void*>(L.kern[l2])), dim3(unsigned(blocks)), dim3(256),
-                               L.lds << l2, g_stream, q);
-            break;
-        }
+        q.ent2_lds_bytes = s.chain.ent2_lds;
+        const int64_t blocks = persistent_grid((batch + s.chain.ipb - 1) / s.chain.ipb, c.chain_blocks_per_cu);
+        hipLaunchKernelGGL(k_product_ell_chain<T>, dim3(unsigned(blocks)), dim3(unsigned(c.chain_threads)), c.chain_bytes, g_stream, q);
+    } else if (s.list.ell_width > 0) {
+        EllArgs<T> q;
+        product_operands<T>(q, s, o, batch);
+        q.left_len = int(o.la.row_len);
+        q.right_len = int(o.lb.row_len);
+        q.row_out = c.row_out.as<uint32_t>();
+        q.entries = c.entries.as<uint32_t>();
+        q.n_rows = int(c.row_out.count);
+        q.width = s.list.ell_width;
+        int l2 = c.ell_max_log2;
+        while (l2 > 0 && (int64_t(1) << l2) > batch) --l2;
+        *variant = l2;
+        launch_kernel(c.ell[l2], (batch + (int64_t(1) << l2) - 1) >> l2, 256, c.bytes_per_item << l2, q);
+    } else {
         CsrArgs<T> p;
-        p.left = static_cast<const T*>(a.ptr);
-        p.right = static_cast<const T*>(b.ptr);
-        p.out = static_cast<T*>(res.ptr);
-        p.left_stride = a.stride;
-        p.right_stride = b.stride;
-        p.out_stride = res.stride;
-        p.left_len = int(la.row_len);
-        p.right_len = int(lb.row_len);
-        p.canon_left = s.canon_a;
-        p.canon_right = s.canon_b;
-        p.row_start = L.list.row_start.as<uint32_t>();
-        p.row_out = L.list.row_out.as<uint32_t>();
-        p.entries = L.list.entries.as<uint32_t>();
-        p.coeff = L.list.coeff.as<T>();
-        p.n_rows = int(L.list.row_out.count);
-        p.beta = s.beta;
-        p.batch = batch;
-        int items = L.max_items;
-        if (int64_t(items) > batch) items = int(batch);
-        p.items = items;
-        const int64_t blocks = (batch + items - 1) / items;
-        hipLaunchKernelGGL(k_product_csr<T>, dim3(unsigned(blocks)), dim3(256), L.lds * size_t(items), g_stream, p);
+        product_operands<T>(p, s, o, batch);
+        p.left_len = int(o.la.row_len);
+        p.right_len = int(o.lb.row_len);
+        p.row_start = c.row_start.as<uint32_t>();
+        p.row_out = c.row_out.as<uint32_t>();
+        p.entries = c.entries.as<uint32_t>();
+        p.coeff = c.coeff.as<T>();
+        p.n_rows = int(c.row_out.count);
+        p.items = int(std::min<int64_t>(c.csr_items, batch));
+        const int64_t blocks = (batch + p.items - 1) / p.items;
+        hipLaunchKernelGGL(k_product_csr<T>, dim3(unsigned(blocks)), dim3(256), c.bytes_per_item * size_t(p.items), g_stream, p);
+    }
+    return launch_status();
+}
+
+// ---- PRODUCT_DENSE: the matrix-core and vector-FMA families, the matrix-representation (spinor) kernels ---------------------
+// staging / store mode of k_gp_mfma16x4 and k_gp_mfma7 as a template argument
+template <int V>
+using Mode = std::integral_constant<int, V>;
+
+// the spinor kernels see a full row as a D x D matrix, D = 2^m, and stage two of them (rows one element apart)
+int64_t spinor_matrix_len(int m) { return int64_t(1) << (2 * m); }
+template <typename T>
+size_t spinor_planes_bytes(int m) {
+    const size_t D = size_t(1) << m, plane = (D * (D + 1) + 63) / 64 * 64;
+    return (m == 6 ? 2 * plane + (sizeof(T) == 8 ? 0 : 16) : 2 * D * (D + 1)) * sizeof(T);   // k_gp_spinor12s: second plane 16 words further
+}
+
+template <typename T>
+int prepare_dense(Launch& L, std::string& kernel) {
+    Step& s = L.s;
+    auto& c = L.dense;
+    const int n = L.n;
+    Upload<T> up;
+    up.idx(c.left_map, s.dense.left_map); up.idx(c.right_map, s.dense.right_map); up.idx(c.out_map, s.dense.out_map);
+    up.idx(c.spinor_out_map, s.dense.spinor_out_map);
+    up.val(c.left_scale, s.dense.left_scale); up.val(c.right_scale, s.dense.right_scale); up.val(c.out_scale, s.dense.out_scale);
+    up.idx(c.pre.row_start, s.pre.row_start); up.idx(c.pre.entries, s.pre.entries); up.idx(c.pre.row_map, s.pre.row_map);
+    up.val(c.pre.coeff, s.pre.coeff); up.val(c.pre.row_scale, s.pre.row_scale);
+    if (up.status) return up.status;
+    constexpr bool is_f64 = std::is_same<T, double>::value;
+    const bool degenerate = s.dense.degenerate != 0, scaled = s.dense.scaled != 0, chained = s.dense.chained != 0;
+    const std::string tn = type_name<T>();
+    const std::string dg = degenerate ? "true" : "false";
+    // (SCALED, CHAINED) template arguments as they appear in the kernel's name: ",true" = rescaled basis, ",false,true" = chained
+    const std::string vs = chained ? (scaled ? ",true,true" : ",false,true") : (scaled ? ",true" : "");
+    using KernD = void (*)(DenseArgs<T>);
+    // k_gp_mfma16x4 / k_gp_mfma7, k(MODE, SCALED, CHAINED): general staging for any basis; register prefetch (full, contiguous,
+    // 16-byte aligned rows at launch) and, on top, straight-line result stores (every blade produced, nothing accumulated) --
+    // never for a rescaled basis (general diagonal metric), for a chained product in every mode
+    auto staging_modes = [&](auto&& k) {
+        c.general = kernel_address(static_bools([&](auto sc, auto ch) -> KernD { return k(Mode<0>{}, sc, ch); }, scaled, chained));
+        c.prefetch = kernel_address(static_bools([&](auto ch) -> KernD { return k(Mode<1>{}, std::false_type{}, ch); }, chained && !scaled));
+        c.whole_rows = kernel_address(static_bools([&](auto ch) -> KernD { return k(Mode<2>{}, std::false_type{}, ch); }, chained && !scaled));
+    };
+    bool persistent = true;   // as many workgroups as are resident at once (register- and LDS-limited) loop over the items
+    switch (s.dense.family) {
+    case DenseFamily::SPINOR: {
+        using KernS = void (*)(SpinorArgs);
+        const int m = s.dense.spinor_m;
+        c.bytes = spinor_planes_bytes<T>(m);
+        const int lb5 = s.dense.spinor_lam_bit;
+        KernS kern = nullptr;
+        if (is_f64 && m == 6) kern = lb5 == 5 ? &k_gp_spinor12d<5> : lb5 == 4 ? &k_gp_spinor12d<4> : &k_gp_spinor12d<-1>;
+        else if (is_f64 && m == 5) kern = lb5 == 4 ? &k_gp_spinor_wave1d<5, 4> : lb5 == 3 ? &k_gp_spinor_wave1d<5, 3> : &k_gp_spinor_wave1d<5, -1>;
+        else if (is_f64) kern = lb5 == 3 ? &k_gp_spinor_wave1d<4, 3> : lb5 == 2 ? &k_gp_spinor_wave1d<4, 2> : &k_gp_spinor_wave1d<4, -1>;
+        else if (m == 6) {
+            kern = lb5 == 5 ? &k_gp_spinor12s<5, false> : lb5 == 4 ? &k_gp_spinor12s<4, false> : &k_gp_spinor12s<-1, false>;
+            const KernS fast = lb5 == 5 ? &k_gp_spinor12s<5, true> : lb5 == 4 ? &k_gp_spinor12s<4, true> : &k_gp_spinor12s<-1, true>;
+            c.spinor_fast = kernel_address(fast);
+        }
+        else if (m == 5) kern = lb5 == 4 ? &k_gp_spinor_wave1<5, 4> : lb5 == 3 ? &k_gp_spinor_wave1<5, 3> : &k_gp_spinor_wave1<5, -1>;
+        else kern = lb5 == 3 ? &k_gp_spinor_wave1<4, 3> : lb5 == 2 ? &k_gp_spinor_wave1<4, 2> : &k_gp_spinor_wave1<4, -1>;
+        c.general = kernel_address(kern);
+        kernel = (m == 6 ? (is_f64 ? "k_gp_spinor12d<" : "k_gp_spinor12s<") : (is_f64 ? "k_gp_spinor_wave1d<" : "k_gp_spinor_wave1<") + std::to_string(m) + ",") +
+                  std::to_string(lb5) + ">";
+        c.threads = m == 6 ? 256 : 64;
         break;
     }
-    case Step::FUSED: return GAAST_OK;  // launched by run_fused (needs every bound buffer)
-    case Step::ELEMENTWISE: return GAAST_OK;  // launched by run_elementwise (needs every source buffer)
-    case Step::LINMAP: return launch_linmap<T>(*L.linmap, la, a, res, batch);
-    case Step::PRODUCT_DENSE: {
-        if (s.dense.family == DenseFamily::SPINOR) {
-            SpinorArgs q;
-            q.left = a.ptr;
-            q.right = b.ptr;
-            q.out = res.ptr;
-            q.left_stride = a.stride;
-            q.right_stride = b.stride;
-            q.out_stride = res.stride;
-            q.left_map = L.dense.left_map.as<uint16_t>();
-            q.right_map = L.dense.right_map.as<uint16_t>();
-            q.left_full = s.dense.left_full;
-            q.right_full = s.dense.right_full;
-            q.out_map = L.dense.spinor_out_map.as<uint16_t>();
-            q.out_full = s.dense.out_full;
-            q.left_len = int(la.row_len);
-            q.right_len = int(lb.row_len);
-            q.canon_left = s.canon_a;
-            q.canon_right = s.canon_b;
-            q.beta = s.beta;
-            q.batch = batch;
-            q.has_alpha = s.dense.spinor_has_alpha;
-            using KernS = void (*)(SpinorArgs);
-            int64_t blocks = int64_t(g_num_cu) * L.blocks_per_cu;
-            if (blocks > batch) blocks = batch;
-            auto aligned16 = [](const void* ptr, int64_t stride) {
-                return (reinterpret_cast<uintptr_t>(ptr) % 16 == 0) && ((size_t(stride) * sizeof(T)) % 16 == 0);
-            };
-            const bool fast = L.kern[1] && s.dense.left_full && s.dense.right_full && s.dense.out_full && !s.beta && q.left_len == 4096 && q.right_len == 4096 &&
-                              aligned16(a.ptr, a.stride) && aligned16(b.ptr, b.stride) && aligned16(res.ptr, res.stride);
-            L.variant = fast ? 1 : 0;
-            hipLaunchKernelGGL(reinterpret_cast<KernS>(const_cast<void*>(L.kern[fast ? 1 : 0])), dim3(unsigned(blocks)),
-                               dim3(unsigned(L.threads)), L.lds, g_stream, q);
+    case DenseFamily::MFMA32:
+    case DenseFamily::MFMA32P:
+        if constexpr (!is_f64) {
+            const int wpi = 1 << (n - 10);                 // waves per item
+            c.threads = wpi > 4 ? wpi * 64 : 256;
+            c.items_per_block = (c.threads / 64) / wpi;
+            const bool image_pairs = s.dense.family == DenseFamily::MFMA32P;
+            c.bytes = (image_pairs ? size_t(c.items_per_block) * size_t(4 << n) + 16 : size_t(c.items_per_block) * size_t(2 << n)) * sizeof(float);
+            if (c.bytes > g_max_lds) return set_err(GAAST_ERR_UNIMPLEMENTED, "dense product does not fit in LDS");
+            if (image_pairs) {
+                c.general = kernel_address(static_bools([&](auto dgn, auto sc, auto ch) -> KernD {
+                    return static_int<10, 11, 12, 13>(n, [](auto nn) -> KernD {
+                        return &k_gp_mfma32p<decltype(dgn)::value, decltype(nn)::value, decltype(sc)::value, decltype(ch)::value>;
+                    });
+                }, degenerate, scaled, chained));
+                kernel = "k_gp_mfma32p<" + dg + "," + std::to_string(n) + vs + ">";
+                break;
+            }
+            // (k_gp_mfma32 serves n = 14 only -- 16 waves and 128 KiB of LDS per item; n = 10 ... 13 run on k_gp_mfma32p)
+            if (c.threads != 1024) return set_err(GAAST_ERR_UNIMPLEMENTED, "k_gp_mfma32 is built for n = 14 only");
+            c.general = kernel_address(static_bools([](auto dgn, auto sc, auto ch) -> KernD {
+                return &k_gp_mfma32<decltype(dgn)::value, 1024, decltype(sc)::value, decltype(ch)::value>;
+            }, degenerate, scaled, chained));
+            kernel = "k_gp_mfma32<" + dg + "," + std::to_string(c.threads) + vs + ">";
+            persistent = false;
             break;
         }
-        DenseArgs<T> p;
-        p.left = static_cast<const T*>(a.ptr);
-        p.right = static_cast<const T*>(b.ptr);
-        p.out = static_cast<T*>(res.ptr);
-        p.left_stride = a.stride;
-        p.right_stride = b.stride;
-        p.out_stride = res.stride;
-        p.left_map = L.dense.left_map.as<uint32_t>();
-        p.right_map = L.dense.right_map.as<uint32_t>();
-        p.left_count = int(L.dense.left_map.count);
-        p.right_count = int(L.dense.right_map.count);
-        p.left_full = s.dense.left_full;
-        p.right_full = s.dense.right_full;
-        // vector loads need 16-byte aligned rows: base pointer and row stride
-        auto aligned = [](const void* ptr, int64_t stride) {
-            return (reinterpret_cast<uintptr_t>(ptr) % 16 == 0) && ((size_t(stride) * sizeof(T)) % 16 == 0);
-        };
-        p.left_contig = s.dense.left_contig && aligned(a.ptr, a.stride);
-        p.right_contig = s.dense.right_contig && aligned(b.ptr, b.stride);
-        p.out_map = L.dense.out_map.as<int32_t>();
-        p.canon_left = s.canon_a;
-        p.canon_right = s.canon_b;
-        p.n = n;
-        p.neg_hi = s.dense.neg_hi;
-        p.zero_hi = s.dense.zero_hi;
-        p.neg_lo = s.dense.neg_lo;
-        p.beta = s.beta;
-        p.batch = batch;
-        using KernD = void (*)(DenseArgs<T>);
-        const int64_t groups = (batch + L.items_per_block - 1) / L.items_per_block;
-        int64_t blocks = groups;
-        if (L.blocks_per_cu > 0) {  // persistent workgroups (vector-FMA form)
-            blocks = int64_t(g_num_cu) * L.blocks_per_cu;
-            if (blocks > groups) blocks = groups;
-        }
-        p.left_signs = s.dense.left_signs;
-        p.out_signs = s.dense.out_signs;
-        p.pre_left = p.pre_right = nullptr;
-        p.pre_entries = nullptr;
-        if (s.dense.chained) {   // the left operand is a comp-mul list over two other rows, evaluated in LDS while staging
-            p.pre_left = static_cast<const T*>(x.pre_a.ptr);
-            p.pre_right = static_cast<const T*>(x.pre_b.ptr);
-            p.pre_left_stride = x.pre_a.stride;
-            p.pre_right_stride = x.pre_b.stride;
-            p.pre_left_len = s.pre.left_len;
-            p.pre_right_len = s.pre.right_len;
-            p.pre_canon_left = s.pre.canon_a;
-            p.pre_canon_right = s.pre.canon_b;
-            p.pre_row_start = L.pre.row_start.as<uint32_t>();
-            p.pre_entries = L.pre.entries.as<uint32_t>();
-            p.pre_coeff = L.pre.coeff.as<T>();
-            p.pre_row_map = L.pre.row_map.as<uint32_t>();
-            p.pre_row_scale = L.pre.row_scale.as<T>();
-            p.pre_rows = int(L.pre.row_map.count);
-            p.pre_width = s.pre.width;
-            p.pre_scratch = int(L.pre_scratch_off / sizeof(T));
-            p.left_count = 0;
-        }
-        p.left_scale = s.dense.scaled ? L.dense.left_scale.as<T>() : nullptr;
-        p.right_scale = s.dense.scaled ? L.dense.right_scale.as<T>() : nullptr;
-        p.out_scale = s.dense.scaled ? L.dense.out_scale.as<T>() : nullptr;
-        // register-prefetch staging: full, contiguous, aligned operand rows; a chained step computes its left operand from a list
-        // (then only the right row is prefetched)
-        bool prefetch = false;
-        switch (s.dense.family) {
-        case DenseFamily::MFMA6: prefetch = p.left_full && p.right_full && s.dense.out_full && !s.beta; break;   // k_gp_mfma6's straight-line instantiation
-        case DenseFamily::MFMA7: prefetch = L.kern[1] && p.right_full && !s.dense.scaled && (s.dense.chained || p.left_full); break;   // one component per lane and load: no alignment needed
-        case DenseFamily::MFMA16X4: prefetch = L.kern[1] && p.right_contig && p.right_full && !s.dense.scaled && (s.dense.chained || (p.left_contig && p.left_full)); break;
-        default: break;
-        }
-        const bool whole_rows = prefetch && L.kern[2] && s.dense.out_full && !s.beta;   // k_gp_mfma16x4: straight-line result stores
-        L.variant = whole_rows ? 2 : prefetch ? 1 : 0;
-        hipLaunchKernelGGL(reinterpret_cast<KernD>(const_cast<void*>(L.kern[L.variant])), dim3(unsigned(blocks)),
-                           dim3(unsigned(L.threads)), L.lds, g_stream, p);
+        [[fallthrough]];   // (f64 has no such kernel)
+    case DenseFamily::VECTOR_FMA: {
+        const int lpi = 1 << (n - 4);
+        c.threads = lpi > 256 ? lpi : 256;
+        c.items_per_block = c.threads / lpi;
+        c.bytes = size_t(c.items_per_block) * size_t(2 * (1 << n) + (c.items_per_block > 1 ? 4 : 0)) * sizeof(T);
+        if (c.bytes > g_max_lds)
+            return set_err(GAAST_ERR_UNIMPLEMENTED, "dense product of dimension " + std::to_string(n) + " does not fit in LDS");
+        c.general = kernel_address(static_bools([](auto dgn, auto wide, auto neglo, auto sc, auto ch) -> KernD {
+            return &k_gp_dense<T, decltype(dgn)::value, decltype(wide)::value ? 512 : 256, decltype(neglo)::value, decltype(sc)::value, decltype(ch)::value>;
+        }, degenerate, c.threads != 256, s.dense.neg_lo_all != 0, scaled, chained));
+        kernel = "k_gp_dense<" + tn + "," + dg + "," + std::to_string(c.threads) + "," + (s.dense.neg_lo_all ? "true" : "false") + vs + ">";
         break;
     }
-    default: return set_err(GAAST_ERR_INVALID_PROGRAM, "run_step: unknown step kind " + std::to_string(int(s.kind)) + " (" + s.name + ")");
+    case DenseFamily::MFMA16X4: {
+        // k_gp_mfma16x4<T, DEG, n, MODE, SC, CH>: one wave per 16 result columns, one item per workgroup.  f64 runs n = 8 ... 12 on
+        // it, f32 only n = 8, 9 (f32 at n >= 10 is k_gp_mfma32p's): the f32 instantiations for n = 10 ... 12 would be unreachable,
+        // so they are not built.
+        c.threads = 64 << (n - 8);
+        c.items_per_block = 1;
+        c.bytes = size_t(4 * (size_t(1) << n) + 32) * sizeof(T);   // +B, -B, +A, 16 spare, -A images, 16 zeros
+        if (c.bytes > g_max_lds) return set_err(GAAST_ERR_UNIMPLEMENTED, "dense product does not fit in LDS");
+        staging_modes([&](auto mode, auto sc, auto ch) -> KernD {
+            auto of_n = [&](auto nn) -> KernD {
+                return static_bools([](auto dgn) -> KernD {
+                    return &k_gp_mfma16x4<T, decltype(dgn)::value, decltype(nn)::value, decltype(mode)::value, decltype(sc)::value, decltype(ch)::value>;
+                }, degenerate);
+            };
+            if constexpr (is_f64) return static_int<8, 9, 10, 11, 12>(n, of_n);
+            else return static_int<8, 9>(n, of_n);
+        });
+        if (!c.general || !c.prefetch || !c.whole_rows) return set_err(GAAST_ERR_UNIMPLEMENTED, "no k_gp_mfma16x4 instantiation for this dimension and value type");
+        kernel = "k_gp_mfma16x4<" + tn + "," + dg + "," + std::to_string(n) + (scaled ? ",0" + vs + ">" : ",0|1|2" + vs + ">");   // staging / store mode: by alignment at launch
+        break;
     }
-    HIP_TRY(hipGetLastError());
-    return GAAST_OK;
+    case DenseFamily::MFMA6: {
+        // k_gp_mfma6<T>: one wave per item, persistent single-wave workgroups, 2 KiB (f32) / 4 KiB (f64) of operand images
+        c.threads = 64 * GAAST_MFMA6_WAVES;
+        c.items_per_block = GAAST_MFMA6_WAVES;
+        c.bytes = (size_t(is_f64 ? 4096 : 2048) + 64 * sizeof(T)) * GAAST_MFMA6_WAVES;   // + a dummy element per lane (stores of vanishing slots)
+        // general: any operands (partial grade sets, projected or accumulated results); prefetch: full operands, every blade produced,
+        // nothing accumulated -- straight-line item loop with counted waits
+        auto k6 = [](auto sc, auto straight) -> KernD { return &k_gp_mfma6<T, decltype(sc)::value, decltype(straight)::value>; };
+        c.general = kernel_address(static_bools(k6, scaled, false));
+        c.prefetch = kernel_address(static_bools(k6, scaled, true));
+        kernel = "k_gp_mfma6<" + tn + (scaled ? ",true,0|1>" : ",false,0|1>");
+        break;
+    }
+    case DenseFamily::MFMA7: {
+        // k_gp_mfma7<T>: one wave per item, persistent single-wave workgroups
+        c.threads = 64;
+        c.items_per_block = 1;
+        c.bytes = size_t(560) * sizeof(T);   // +B, -B, +A (u = 1 half 72 further), -A 144 further, 16 zeros
+        staging_modes([](auto mode, auto sc, auto ch) -> KernD { return &k_gp_mfma7<T, decltype(mode)::value, decltype(sc)::value, decltype(ch)::value>; });
+        kernel = "k_gp_mfma7<" + tn + (scaled ? ",0" + vs + ">" : ",0|1|2" + vs + ">");   // (null vectors: run-time, no instantiation of their own)
+        break;
+    }
+    }
+    if (chained) {
+        // the list's operand rows of every item a workgroup stages at once, after the kernel's own images
+        c.pre_scratch_bytes = (c.bytes + 15) / 16 * 16;
+        const size_t items = size_t(c.items_per_block > 0 ? c.items_per_block : 1);
+        // + the zero pair; the one-item matrix kernels keep the list's right row twice (+x, -x: a term's sign is an address)
+        c.bytes = c.pre_scratch_bytes + (items * size_t(s.pre.left_len + s.pre.right_len + 1) + (items == 1 ? size_t(s.pre.right_len) : 0)) * sizeof(T);
+        // The plan builder sizes a chain's LDS with its own estimate of the kernel's images; this is the real figure, checked
+        // against the device.  On a mismatch gaast_hip_program_create rebuilds the program without chains.
+        if (c.bytes > g_max_lds) return set_err(kChainTooBig, "chained product does not fit in LDS (" + s.name + ")");
+    }
+    for (const void* kern : {c.general, c.prefetch, c.whole_rows, c.spinor_fast})
+        if (kern)
+            if (int st = allow_lds(kern, c.bytes)) return st;
+    if (!persistent) return GAAST_OK;
+    // (the residency of the prefetch form where there is one; of the general form under a chain, whose LDS is the greater part)
+    return resident_blocks(c.prefetch && !chained ? c.prefetch : c.general, c.threads, c.bytes, &c.blocks_per_cu);
+}
+
+template <typename T>
+int run_dense(const Launch& L, const Operands& o, int64_t batch, int* variant) {
+    const Step& s = L.s;
+    const auto& c = L.dense;
+    const Bound &res = o.res, &a = o.a, &b = o.b;
+    if (s.dense.family == DenseFamily::SPINOR) {
+        SpinorArgs q;
+        product_operands<T>(q, s, o, batch);
+        q.left_map = c.left_map.as<uint16_t>();
+        q.right_map = c.right_map.as<uint16_t>();
+        q.left_full = s.dense.left_full;
+        q.right_full = s.dense.right_full;
+        q.out_map = c.spinor_out_map.as<uint16_t>();
+        q.out_full = s.dense.out_full;
+        q.left_len = int(o.la.row_len);
+        q.right_len = int(o.lb.row_len);
+        q.has_alpha = s.dense.spinor_has_alpha;
+        const int64_t full = spinor_matrix_len(s.dense.spinor_m);
+        const bool fast = c.spinor_fast && s.dense.left_full && s.dense.right_full && s.dense.out_full && !s.beta && o.la.row_len == full && o.lb.row_len == full &&
+                          rows_aligned16<T>(a) && rows_aligned16<T>(b) && rows_aligned16<T>(res);
+        *variant = fast ? 1 : 0;
+        launch_kernel(fast ? c.spinor_fast : c.general, persistent_grid(batch, c.blocks_per_cu), c.threads, c.bytes, q);
+        return launch_status();
+    }
+    DenseArgs<T> p;
+    product_operands<T>(p, s, o, batch);
+    p.left_map = c.left_map.as<uint32_t>();
+    p.right_map = c.right_map.as<uint32_t>();
+    p.left_count = int(c.left_map.count);
+    p.right_count = int(c.right_map.count);
+    p.left_full = s.dense.left_full;
+    p.right_full = s.dense.right_full;
+    p.left_contig = s.dense.left_contig && rows_aligned16<T>(a);
+    p.right_contig = s.dense.right_contig && rows_aligned16<T>(b);
+    p.out_map = c.out_map.as<int32_t>();
+    p.n = L.n;
+    p.neg_hi = s.dense.neg_hi;
+    p.zero_hi = s.dense.zero_hi;
+    p.neg_lo = s.dense.neg_lo;
+    p.left_signs = s.dense.left_signs;
+    p.out_signs = s.dense.out_signs;
+    p.pre_left = p.pre_right = nullptr;
+    p.pre_entries = nullptr;
+    if (s.dense.chained) {   // the left operand is a comp-mul list over two other rows, evaluated in LDS while staging
+        p.pre_left = static_cast<const T*>(o.pre_a.ptr);
+        p.pre_right = static_cast<const T*>(o.pre_b.ptr);
+        p.pre_left_stride = o.pre_a.stride;
+        p.pre_right_stride = o.pre_b.stride;
+        p.pre_left_len = s.pre.left_len;
+        p.pre_right_len = s.pre.right_len;
+        p.pre_canon_left = s.pre.canon_a;
+        p.pre_canon_right = s.pre.canon_b;
+        p.pre_row_start = c.pre.row_start.as<uint32_t>();
+        p.pre_entries = c.pre.entries.as<uint32_t>();
+        p.pre_coeff = c.pre.coeff.as<T>();
+        p.pre_row_map = c.pre.row_map.as<uint32_t>();
+        p.pre_row_scale = c.pre.row_scale.as<T>();
+        p.pre_rows = int(c.pre.row_map.count);
+        p.pre_width = s.pre.width;
+        p.pre_scratch = int(c.pre_scratch_bytes / sizeof(T));
+        p.left_count = 0;
+    }
+    p.left_scale = s.dense.scaled ? c.left_scale.as<T>() : nullptr;
+    p.right_scale = s.dense.scaled ? c.right_scale.as<T>() : nullptr;
+    p.out_scale = s.dense.scaled ? c.out_scale.as<T>() : nullptr;
+    // register-prefetch staging: full, contiguous, aligned operand rows; a chained step computes its left operand from a list
+    // (then only the right row is prefetched)
+    bool prefetch = false;
+    switch (s.dense.family) {
+    case DenseFamily::MFMA6: prefetch = p.left_full && p.right_full && s.dense.out_full && !s.beta; break;   // k_gp_mfma6's straight-line instantiation
+    case DenseFamily::MFMA7: prefetch = p.right_full && !s.dense.scaled && (s.dense.chained || p.left_full); break;   // one component per lane and load: no alignment needed
+    case DenseFamily::MFMA16X4: prefetch = p.right_contig && p.right_full && !s.dense.scaled && (s.dense.chained || (p.left_contig && p.left_full)); break;
+    default: break;   // (one form)
+    }
+    const bool whole_rows = prefetch && c.whole_rows && s.dense.out_full && !s.beta;   // straight-line result stores
+    *variant = whole_rows ? 2 : prefetch ? 1 : 0;
+    launch_kernel(whole_rows ? c.whole_rows : prefetch ? c.prefetch : c.general, persistent_grid((batch + c.items_per_block - 1) / c.items_per_block, c.blocks_per_cu),
+                  c.threads, c.bytes, p);
+    return launch_status();
+}
+
+// ---- REDUCE_SCALE --------------------------------------------------------------------------------------------------------
+template <typename T>
+int prepare_reduce(Launch& L, std::string& kernel) {
+    Step& s = L.s;
+    auto& c = L.reduce;
+    const std::string tn = type_name<T>();
+    Upload<T> up;
+    up.idx(c.ent1, s.reduce.ent1); up.val(c.coeff1, s.reduce.coeff1); up.idx(c.ent2, s.reduce.ent2); up.val(c.coeff2, s.reduce.coeff2);
+    up.idx(c.sign_words, s.reduce.sign_words);
+    if (up.status) return up.status;
+    kernel = "k_reduce_scale<" + tn + ">";
+    if (s.reduce.wave) {   // tolerance mode: one wave per item, the row read once -- taken at launch when the three rows are one (run_reduce)
+        using KernW = void (*)(ReduceScaleArgs<T>, const uint32_t*);
+        KernW kw = nullptr;
+        if constexpr (sizeof(T) == 8) kw = static_int<1, 2, 4, 8, 16>(s.reduce.wave, [](auto w) -> KernW { return &k_reduce_scale_wave<T, decltype(w)::value>; });
+        else kw = static_int<1, 2, 4, 8>(s.reduce.wave, [](auto w) -> KernW { return &k_reduce_scale_wave<T, decltype(w)::value>; });
+        c.wave = kernel_address(kw);
+        if (kw) kernel += " | k_reduce_scale_wave<" + tn + "," + std::to_string(s.reduce.wave) + "> (lane-parallel sums) when the rows are one";
+        else s.reduce.wave = 0;
+    }
+    return resident_blocks(kernel_address(&k_reduce_scale<T>), 256, 0, &c.blocks_per_cu);
+}
+
+template <typename T>
+int run_reduce(const Launch& L, const Operands& o, int64_t batch, int* variant) {
+    const Step& s = L.s;
+    const auto& c = L.reduce;
+    const Bound &res = o.res, &a = o.a, &b = o.b, &x = o.scaled_row;
+    ReduceScaleArgs<T> q;
+    q.l1 = static_cast<const T*>(a.ptr);
+    q.r1 = static_cast<const T*>(b.ptr);
+    q.x = static_cast<const T*>(x.ptr);
+    q.out = static_cast<T*>(res.ptr);
+    q.l1_stride = a.stride;
+    q.r1_stride = b.stride;
+    q.x_stride = x.stride;
+    q.out_stride = res.stride;
+    q.ent1 = c.ent1.as<uint32_t>();
+    q.coeff1 = c.coeff1.as<T>();
+    q.ent2 = c.ent2.as<uint32_t>();
+    q.coeff2 = c.coeff2.as<T>();
+    q.n1 = int(c.ent1.count);
+    q.n2 = int(c.ent2.count);
+    q.canon_l1 = s.canon_a;
+    q.canon_r1 = s.canon_b;
+    q.canon_x = s.reduce.canon_x;
+    q.canon_s = s.reduce.canon_s;
+    q.s_is_left = s.reduce.s_is_left;
+    q.op = s.reduce.op;
+    q.batch = batch;
+    if (s.reduce.wave && c.wave && a.ptr == b.ptr && a.ptr == x.ptr && a.stride == b.stride && a.stride == x.stride &&
+        rows_aligned16<T>(a) && rows_aligned16<T>(res) && res.ptr != a.ptr) {
+        // one wave per item, four per workgroup, persistent
+        *variant = 1;
+        launch_kernel(c.wave, persistent_grid((batch + 3) / 4, 8), 256, 0, q, c.sign_words.as<uint32_t>());
+    } else {
+        // sixteen items per wave, four waves per workgroup, persistent: as many workgroups as are resident at once
+        const int64_t blocks = persistent_grid((batch + 63) / 64, c.blocks_per_cu > 0 ? c.blocks_per_cu : 8);
+        hipLaunchKernelGGL(k_reduce_scale<T>, dim3(unsigned(blocks)), dim3(256), 0, g_stream, q);
+    }
+    return launch_status();
+}
+
+// ---- EXPLOG --------------------------------------------------------------------------------------------------------------
+template <typename T>
+int prepare_explog(Launch& L) {
+    Step& s = L.s;
+    Upload<T> up;
+    up.val(L.explog.sq, s.explog.sq); up.idx(L.explog.row_start, s.explog.row_start); up.idx(L.explog.pairs, s.explog.pairs);
+    up.val(L.explog.pair_coeff, s.explog.pair_coeff);
+    return up.status;   // (its label names no kernel)
+}
+
+template <typename T>
+int run_explog(const Launch& L, const Operands& o, int64_t batch) {
+    const Step& s = L.s;
+    ExpLogArgs<T> q;
+    q.res = static_cast<T*>(o.res.ptr);
+    q.arg = static_cast<const T*>(o.a.ptr);
+    q.res_stride = o.res.stride;
+    q.arg_stride = o.a.stride;
+    q.op = s.explog.op;
+    q.m = s.explog.m;
+    q.m_res = s.explog.mres;
+    q.arg_k = s.explog.arg_k;
+    q.arg_0 = s.explog.arg_0;
+    q.res_k = s.explog.res_k;
+    q.res_0 = s.explog.res_0;
+    q.sq = L.explog.sq.as<T>();
+    q.row_start = L.explog.row_start.as<uint32_t>();
+    q.pairs = L.explog.pairs.as<uint32_t>();
+    q.pair_coeff = L.explog.pair_coeff.as<T>();
+    q.n_rows = int(L.explog.row_start.count) - 1;
+    q.dom = static_cast<unsigned long long*>(L.domain);
+    q.batch = batch;
+    hipLaunchKernelGGL(k_exp_log<T>, dim3(grid_for(batch, 256)), dim3(256), 0, g_stream, q);
+    return launch_status();
+}
+
+// ---- EXPLOG_ADJ ----------------------------------------------------------------------------------------------------------
+template <typename T>
+int prepare_explog_adj(Launch& L, const Layout& la, const Layout& lb, std::string& kernel) {
+    Step& s = L.s;
+    auto& c = L.adj;
+    Upload<T> up;
+    up.val(c.sq, s.adj.sq);
+    // the rows of a workgroup's items through LDS whenever at least a wave's worth of items fits 64 KiB (no attribute to raise,
+    // several workgroups per CU); an item's rows `stride` elements apart, odd.  Otherwise the direct form.
+    const size_t stride = size_t(la.row_len + lb.row_len) | 1;
+    const size_t fit = (64 * 1024) / (stride * sizeof(T));
+    c.lds_items = fit >= 256 ? 256 : int(fit / 64 * 64);
+    c.bytes_per_item = stride * sizeof(T);
+    c.kernel = s.adj.op == 0 ? kernel_address(&k_exp_log_adj<T, 0>) : kernel_address(&k_exp_log_adj<T, 1>);
+    kernel = std::string("k_exp_log_adj<") + type_name<T>() + "," + std::to_string(s.adj.op) + ">" +
+             (c.lds_items ? "[" + std::to_string(c.lds_items) + " items through LDS]" : "[direct rows]");
+    return up.status;
+}
+
+template <typename T>
+int run_explog_adj(const Launch& L, const Operands& o, int64_t batch) {
+    const Step& s = L.s;
+    const auto& c = L.adj;
+    ExpLogAdjArgs<T> q;
+    q.res = static_cast<T*>(o.res.ptr);
+    q.arg = static_cast<const T*>(o.a.ptr);
+    q.cot = static_cast<const T*>(o.b.ptr);
+    q.res_stride = o.res.stride;
+    q.arg_stride = o.a.stride;
+    q.cot_stride = o.b.stride;
+    q.m = s.adj.m;
+    q.m_g = s.adj.mg;
+    q.m_res = s.adj.res_k >= 0 ? s.adj.mres : 0;
+    q.arg_k = s.adj.arg_k;
+    q.arg_0 = s.adj.arg_0;
+    q.g_k = s.adj.g_k;
+    q.g_0 = s.adj.g_0;
+    q.res_k = s.adj.res_k;
+    q.res_0 = s.adj.res_0;
+    q.arg_len = int(o.la.row_len);
+    q.cot_len = int(o.lb.row_len);
+    q.items = c.lds_items;
+    q.lds_stride = int(c.bytes_per_item / sizeof(T));
+    q.sq = c.sq.as<T>();
+    q.batch = batch;
+    const int per_block = c.lds_items ? c.lds_items : 256;   // the direct form: an item per thread
+    launch_kernel(c.kernel, persistent_grid((batch + per_block - 1) / per_block, 8), 256, c.bytes_per_item * size_t(c.lds_items), q);
+    return launch_status();
+}
+
+// ---- ELEMENTWISE: a run of element-wise arms (and the scaling product after it) in one pass: plan.cpp: fuse_elementwise_runs ---
+template <typename T>
+int prepare_elementwise(Launch& L, std::string& kernel) {
+    Step& s = L.s;
+    Upload<T> up;
+    up.idx(L.ew.ops, s.ew.ops); up.idx(L.ew.comp_off, s.ew.comp_off); up.idx(L.ew.out_off, s.ew.out_off); up.val(L.ew.coeff, s.ew.coeff);
+    kernel = std::string("k_elementwise<") + type_name<T>() + (s.ew.n_ops <= 4 ? ",4>" : ",8>");
+    return up.status;
+}
+
+template <typename T>
+int run_elementwise(const Launch& L, const Operands& o, int64_t batch) {
+    const Step& s = L.s;
+    ElementwiseArgs<T> q;
+    std::memset(&q, 0, sizeof(q));
+    Layout unused;
+    for (size_t i = 0; i < s.ew.src.size() && i < size_t(ELEMENTWISE_MAX_SRC); ++i) {
+        const Bound src = o.rows->at(s.ew.src[i], &unused);
+        q.src[i] = static_cast<const T*>(src.ptr);
+        q.src_stride[i] = src.stride;
+    }
+    q.ops = L.ew.ops.as<uint32_t>();
+    q.comp_off = L.ew.comp_off.as<uint32_t>();
+    q.n_ops = s.ew.n_ops;
+    q.n_comp = int(L.ew.comp_off.count);
+    q.load_first = s.ew.load_first;
+    q.batch = batch;
+    if (s.ew.scale) {
+        q.out = static_cast<T*>(o.res.ptr);
+        q.out_stride = o.res.stride;
+        q.out_off = L.ew.out_off.as<uint32_t>();
+        q.coeff = L.ew.coeff.as<T>();
+        q.scalar = static_cast<const T*>(o.b.ptr);
+        q.scalar_stride = o.b.stride;
+        q.scalar_off = s.ew.scalar_off;
+        q.canon_v = s.ew.canon_v;
+        q.canon_s = s.ew.canon_s;
+        q.s_is_left = s.ew.s_is_left;
+    } else {
+        q.res = static_cast<T*>(o.res.ptr);
+        q.res_stride = o.res.stride;
+    }
+    // x: the components (a thread keeps one), y: strides over the items -- enough workgroups to fill the chip a few times over
+    const unsigned gx = unsigned((q.n_comp + 255) / 256);
+    const int64_t want_y = std::max<int64_t>(1, int64_t(g_num_cu) * 16 / gx);
+    const unsigned gy = unsigned(std::min<int64_t>(std::min<int64_t>((batch + 3) / 4, want_y), 65535));   // (a thread takes four items per step)
+    if (q.n_ops <= 4) hipLaunchKernelGGL((k_elementwise<T, 4>), dim3(gx, gy), dim3(256), 0, g_stream, q);
+    else hipLaunchKernelGGL((k_elementwise<T, ELEMENTWISE_MAX_OPS>), dim3(gx, gy), dim3(256), 0, g_stream, q);
+    return launch_status();
 }
 
 // Loads a code image as a module of its own; null when HIP refuses it
@@ -1170,9 +1282,26 @@ bool arithmetic_bound(uint64_t comp_muls, double bytes) {
     return valu_ps > 0.6 * hbm_ps;
 }
 
+// ---- FUSED: the interpreter k_ast_fused, or the plan specialised through hiprtc (gaast_jit) --------------------------------------
+// the slabs of the FUSED_ITEMS items of a k_ast_fused workgroup
 template <typename T>
-int run_jit(const Launch& L, const Plan& plan, const std::vector<Bound>& in_bound, const Bound& out, int64_t batch) {
+size_t fused_slabs_bytes(int slab) { return (size_t(slab) * FUSED_ITEMS + 8) * sizeof(T); }
+
+template <typename T>
+int prepare_fused(Launch& L) {
+    Step& s = L.s;
+    Upload<T> up;
+    up.idx(L.fused.prog, s.fused.prog); up.idx(L.fused.phase_tab, s.fused.phase_tab);
+    L.fused.general = std::move(s.fused.general);
+    if (up.status || L.jit) return up.status;   // (the step's name says which kernel it is: compile_fused)
+    return allow_lds(kernel_address(&k_ast_fused<T>), fused_slabs_bytes<T>(s.fused.slab));
+}
+
+template <typename T>
+int run_jit(const Launch& L, const Operands& o, int64_t batch, int* variant) {
     const Step& s = L.s;
+    const Plan& plan = o.rows->prog->plan;
+    const std::vector<Bound>& in_bound = o.rows->moved;
     // argument block: (ptr, stride) per staged input image, then out, out stride, batch
     std::vector<void*> args;
     std::vector<const void*> ptrs(s.fused.inputs.size());
@@ -1180,13 +1309,11 @@ int run_jit(const Launch& L, const Plan& plan, const std::vector<Bound>& in_boun
     for (size_t i = 0; i < s.fused.inputs.size(); ++i) {
         ptrs[i] = in_bound[size_t(s.fused.inputs[i].slot)].ptr;
         strides[i] = in_bound[size_t(s.fused.inputs[i].slot)].stride;
-    }
-    for (size_t i = 0; i < s.fused.inputs.size(); ++i) {
         args.push_back(&ptrs[i]);
         args.push_back(&strides[i]);
     }
-    void* optr = out.ptr;
-    long long ostride = out.stride, b = batch;
+    void* optr = o.res.ptr;
+    long long ostride = o.res.stride, b = batch;
     args.push_back(&optr);
     args.push_back(&ostride);
     args.push_back(&b);
@@ -1194,8 +1321,7 @@ int run_jit(const Launch& L, const Plan& plan, const std::vector<Bound>& in_boun
     if (plan.has_explog) args.push_back(&dom);
     const unsigned threads = unsigned(s.fused.jit_threads);
     const unsigned per_block = unsigned(s.fused.jit_items > 0 ? s.fused.jit_items : s.fused.jit_threads);   // (the slab-in-LDS form: 64 items per 512 threads)
-    unsigned blocks = unsigned((batch + per_block - 1) / per_block);
-    if (s.fused.jit_persistent > 0) blocks = unsigned(std::min<int64_t>(blocks, int64_t(g_num_cu) * std::min(s.fused.jit_persistent, 4)));   // persistent workgroups
+    const int64_t blocks = persistent_grid((batch + per_block - 1) / per_block, std::min(s.fused.jit_persistent, 4));   // (jit_persistent = 0: a workgroup per group)
     // (the argument block -- args, ptrs, strides and the locals they point at -- only has to live until this call returns:
     //  hipModuleLaunchKernel copies the kernel arguments into the dispatch packet's kernarg segment at call time)
     hipFunction_t fn = L.jit.fn;
@@ -1210,15 +1336,16 @@ int run_jit(const Launch& L, const Plan& plan, const std::vector<Bound>& in_boun
         }
         if (shared && arithmetic_bound(s.n_entries, bytes)) fn = L.jit_fma.fn;
     }
-    L.variant = fn == L.jit.fn ? 0 : 1;
-    HIP_TRY(hipModuleLaunchKernel(fn, blocks, 1, 1, threads, 1, 1, 0, g_stream, args.data(), nullptr));
+    *variant = fn == L.jit.fn ? 0 : 1;
+    HIP_TRY(hipModuleLaunchKernel(fn, unsigned(blocks), 1, 1, threads, 1, 1, 0, g_stream, args.data(), nullptr));
     return GAAST_OK;
 }
 
 template <typename T>
-int run_fused(const Launch& L, const Plan& plan, const std::vector<Bound>& in_bound, const Bound& out, int64_t batch) {
-    if (L.jit) return run_jit<T>(L, plan, in_bound, out, batch);
+int run_fused(const Launch& L, const Operands& o, int64_t batch, int* variant) {
+    if (L.jit) return run_jit<T>(L, o, batch, variant);
     const Step& s = L.s;
+    const Plan& plan = o.rows->prog->plan;
     FusedArgs<T> p;
     std::memset(&p, 0, sizeof(p));
     p.prog = L.fused.prog.as<uint32_t>();
@@ -1230,68 +1357,21 @@ int run_fused(const Launch& L, const Plan& plan, const std::vector<Bound>& in_bo
     p.n_in = int(s.fused.inputs.size());
     for (int i = 0; i < p.n_in; ++i) {
         const Step::FusedInput& fi = s.fused.inputs[size_t(i)];
-        p.in_ptr[i] = static_cast<const T*>(in_bound[size_t(fi.slot)].ptr);
-        p.in_stride[i] = in_bound[size_t(fi.slot)].stride;
+        p.in_ptr[i] = static_cast<const T*>(o.rows->moved[size_t(fi.slot)].ptr);
+        p.in_stride[i] = o.rows->moved[size_t(fi.slot)].stride;
         p.in_len[i] = int(plan.input_layouts[size_t(fi.slot)].row_len);
         p.in_base[i] = fi.base;
         p.in_canon[i] = fi.canon;
     }
-    p.out_ptr = static_cast<T*>(out.ptr);
-    p.out_stride = out.stride;
+    p.out_ptr = static_cast<T*>(o.res.ptr);
+    p.out_stride = o.res.stride;
     p.out_len = int(plan.out_layout.row_len);
     p.out_base = s.fused.out_base;
     p.batch = batch;
-    const size_t lds = (size_t(p.slab) * FUSED_ITEMS + 8) * sizeof(T);
     const int64_t blocks = (batch + FUSED_ITEMS - 1) / FUSED_ITEMS;
-    hipLaunchKernelGGL(k_ast_fused<T>, dim3(unsigned(blocks)), dim3(FUSED_THREADS), lds, g_stream, p);
-    HIP_TRY(hipGetLastError());
-    return GAAST_OK;
+    hipLaunchKernelGGL(k_ast_fused<T>, dim3(unsigned(blocks)), dim3(FUSED_THREADS), fused_slabs_bytes<T>(s.fused.slab), g_stream, p);
+    return launch_status();
 }
-
-// a run of element-wise arms (and the scaling product after it) in one pass: plan.cpp: fuse_elementwise_runs
-template <typename T, typename Resolve>
-int run_elementwise(const Launch& L, const Bound& res, Resolve&& resolve, int64_t batch) {
-    const Step& s = L.s;
-    ElementwiseArgs<T> q;
-    std::memset(&q, 0, sizeof(q));
-    Layout unused;
-    for (size_t i = 0; i < s.ew.src.size() && i < size_t(ELEMENTWISE_MAX_SRC); ++i) {
-        const Bound b = resolve(s.ew.src[i], &unused);
-        q.src[i] = static_cast<const T*>(b.ptr);
-        q.src_stride[i] = b.stride;
-    }
-    q.ops = L.ew.ops.as<uint32_t>();
-    q.comp_off = L.ew.comp_off.as<uint32_t>();
-    q.n_ops = s.ew.n_ops;
-    q.n_comp = int(L.ew.comp_off.count);
-    q.load_first = s.ew.load_first;
-    q.batch = batch;
-    if (s.ew.scale) {
-        const Bound sc = resolve(s.b, &unused);
-        q.out = static_cast<T*>(res.ptr);
-        q.out_stride = res.stride;
-        q.out_off = L.ew.out_off.as<uint32_t>();
-        q.coeff = L.ew.coeff.as<T>();
-        q.scalar = static_cast<const T*>(sc.ptr);
-        q.scalar_stride = sc.stride;
-        q.scalar_off = s.ew.scalar_off;
-        q.canon_v = s.ew.canon_v;
-        q.canon_s = s.ew.canon_s;
-        q.s_is_left = s.ew.s_is_left;
-    } else {
-        q.res = static_cast<T*>(res.ptr);
-        q.res_stride = res.stride;
-    }
-    // x: the components (a thread keeps one), y: strides over the items -- enough workgroups to fill the chip a few times over
-    const unsigned gx = unsigned((q.n_comp + 255) / 256);
-    const int64_t want_y = std::max<int64_t>(1, int64_t(g_num_cu) * 16 / gx);
-    const unsigned gy = unsigned(std::min<int64_t>(std::min<int64_t>((batch + 3) / 4, want_y), 65535));   // (a thread takes four items per step)
-    if (q.n_ops <= 4) hipLaunchKernelGGL((k_elementwise<T, 4>), dim3(gx, gy), dim3(256), 0, g_stream, q);
-    else hipLaunchKernelGGL((k_elementwise<T, ELEMENTWISE_MAX_OPS>), dim3(gx, gy), dim3(256), 0, g_stream, q);
-    HIP_TRY(hipGetLastError());
-    return GAAST_OK;
-}
-
 // ------------------------------------------------------------------------------------------
 // Program creation (program_create_impl), phase by phase
 // ------------------------------------------------------------------------------------------
@@ -1378,8 +1458,9 @@ void compile_chains(gaast_hip_program_s& prog, uint32_t flags) {
     ls = std::move(kept);
 }
 
-// Kernel choice, LDS budget, persistent grid, device tables and label of one launch: fixed here, and a program no kernel can
-// run is refused whole (an eval then either runs every launch or none)
+// Kernel choice, LDS budget, persistent grid, device tables and label of one launch: fixed here, by the launcher of its kind,
+// and a program no kernel can run is refused whole (an eval then either runs every launch or none)
+template <typename T>
 int prepare_launch(Launch& L, const gaast_hip_program_s& prog) {
     const Plan& plan = prog.plan;
     Step& s = L.s;
@@ -1395,49 +1476,27 @@ int prepare_launch(Launch& L, const gaast_hip_program_s& prog) {
     L.domain = prog.domain.ptr;
     std::string kernel;
     const Layout la = layout_of(s.a), lb = layout_of(s.b);
-    if (int st = plan.dtype == GAAST_F32 ? prepare_step<float>(L, la, lb, kernel) : prepare_step<double>(L, la, lb, kernel)) return st;
-    if (s.dense.chained) {
-        // the list's operand rows of every item a workgroup stages at once, after the kernel's own images
-        L.pre_scratch_off = (L.lds + 15) / 16 * 16;
-        const size_t items = size_t(L.items_per_block > 0 ? L.items_per_block : 1);
-        // + the zero pair; the one-item matrix kernels keep the list's right row twice (+x, -x: a term's sign is an address)
-        L.lds = L.pre_scratch_off + (items * size_t(s.pre.left_len + s.pre.right_len + 1) + (items == 1 ? size_t(s.pre.right_len) : 0)) * dtype_size(plan.dtype);
-        // The plan builder sizes a chain's LDS with its own estimate of the kernel's images; this is the real figure, checked
-        // against the device.  On a mismatch gaast_hip_program_create rebuilds the program without chains.
-        if (L.lds > g_max_lds) return set_err(kChainTooBig, "chained product does not fit in LDS (" + s.name + ")");
-        for (int v = 0; v < 3; ++v)
-            if (L.kern[v])
-                if (int st = allow_lds(L.kern[v], L.lds)) return st;
-        if (L.blocks_per_cu > 0)
-            if (int st = resident_blocks(L.kern[0], L.threads, L.lds, &L.blocks_per_cu)) return st;
-    }
-    // every table of the step under its own name: L.X from s.X (index tables as they are, value tables in the program's dtype; the
-    // tables of the groups this step does not use are empty and cost nothing)
     int st = GAAST_OK;
-    auto idx = [&](DevTable& dev, auto& host) { if (!st) st = dev.upload(std::move(host)); };
-    auto val = [&](DevTable& dev, std::vector<double>& host) { if (!st) st = dev.upload(std::move(host), plan.dtype); };
-    const bool chain_jit = s.kind == Step::PRODUCT_CSR && bool(L.jit);   // the specialised kernel has tables of its own: cj, not pre
-    if (!chain_jit) {
-        idx(L.pre.row_start, s.pre.row_start); idx(L.pre.entries, s.pre.entries); idx(L.pre.row_map, s.pre.row_map);
-        val(L.pre.coeff, s.pre.coeff); val(L.pre.row_scale, s.pre.row_scale);
-    } else {
-        idx(L.cj.ent1, s.cj.ent1); idx(L.cj.pos1, s.cj.pos1); idx(L.cj.ent2, s.cj.ent2); idx(L.cj.out2, s.cj.out2);
+    switch (s.kind) {
+    case Step::ZERO: break;   // (a memset: nothing to prepare)
+    case Step::AXPY:
+    case Step::FLIP:
+    case Step::SUNARY: st = prepare_trivial<T>(L, kernel); break;
+    case Step::PRODUCT_CSR: st = prepare_list<T>(L, la, lb, kernel); break;
+    case Step::PRODUCT_DENSE: st = prepare_dense<T>(L, kernel); break;
+    case Step::FUSED: st = prepare_fused<T>(L); break;
+    case Step::EXPLOG: st = prepare_explog<T>(L); break;
+    case Step::REDUCE_SCALE: st = prepare_reduce<T>(L, kernel); break;
+    case Step::ELEMENTWISE: st = prepare_elementwise<T>(L, kernel); break;
+    case Step::LINMAP: kernel = linmap_kernel_name(L.linmap->n, plan.dtype); break;
+    case Step::EXPLOG_ADJ: st = prepare_explog_adj<T>(L, la, lb, kernel); break;
     }
-    idx(L.axpy_map, s.axpy_map); idx(L.flip_offsets, s.flip_offsets);
-    idx(L.list.row_start, s.list.row_start); idx(L.list.row_out, s.list.row_out); idx(L.list.entries, s.list.entries); val(L.list.coeff, s.list.coeff);
-    idx(L.dense.left_map, s.dense.left_map); idx(L.dense.right_map, s.dense.right_map); idx(L.dense.out_map, s.dense.out_map);
-    idx(L.dense.spinor_out_map, s.dense.spinor_out_map);
-    val(L.dense.left_scale, s.dense.left_scale); val(L.dense.right_scale, s.dense.right_scale); val(L.dense.out_scale, s.dense.out_scale);
-    idx(L.fused.prog, s.fused.prog); idx(L.fused.phase_tab, s.fused.phase_tab);
-    L.fused.general = std::move(s.fused.general);
-    val(L.explog.sq, s.explog.sq); idx(L.explog.row_start, s.explog.row_start); idx(L.explog.pairs, s.explog.pairs); val(L.explog.pair_coeff, s.explog.pair_coeff);
-    val(L.adj.sq, s.adj.sq);
-    idx(L.reduce.ent1, s.reduce.ent1); val(L.reduce.coeff1, s.reduce.coeff1); idx(L.reduce.ent2, s.reduce.ent2); val(L.reduce.coeff2, s.reduce.coeff2);
-    idx(L.reduce.sign_words, s.reduce.sign_words);
-    idx(L.ew.ops, s.ew.ops); idx(L.ew.comp_off, s.ew.comp_off); idx(L.ew.out_off, s.ew.out_off); val(L.ew.coeff, s.ew.coeff);
     if (st) return st;
     L.label = kernel.empty() ? s.name : s.name + " :: " + kernel;
     return GAAST_OK;
+}
+int prepare_launch(Launch& L, const gaast_hip_program_s& prog) {
+    return prog.plan.dtype == GAAST_F32 ? prepare_launch<float>(L, prog) : prepare_launch<double>(L, prog);
 }
 
 // input slots some launch reads (the others may stay unbound)
@@ -2144,17 +2203,43 @@ int bind_eval(gaast_hip_program_t prog, const gaast_hip_mv_t* inputs, int n_inpu
     return GAAST_OK;
 }
 
+// One launch of an evaluation over `batch` items, by the launcher of its kind
 template <typename T>
-int run_launches(gaast_hip_program_t prog, const std::vector<Bound>& in_bound0, gaast_hip_mv_t out, int64_t first, int64_t count) {
+int run_launch(const Launch& L, const Operands& o, int64_t batch) {
+    int variant = 0, st = GAAST_OK;   // (0: a launcher with one kernel)
+    switch (L.s.kind) {
+    case Step::ZERO:
+        if (o.lres.row_len) HIP_TRY(hipMemset2DAsync(o.res.ptr, size_t(o.res.stride) * sizeof(T), 0, size_t(o.lres.row_len) * sizeof(T), size_t(batch), g_stream));
+        break;
+    case Step::AXPY:
+    case Step::FLIP:
+    case Step::SUNARY: st = run_trivial<T>(L, o, batch); break;
+    case Step::PRODUCT_CSR: st = run_list<T>(L, o, batch, &variant); break;
+    case Step::PRODUCT_DENSE: st = run_dense<T>(L, o, batch, &variant); break;
+    case Step::FUSED: st = run_fused<T>(L, o, batch, &variant); break;
+    case Step::EXPLOG: st = run_explog<T>(L, o, batch); break;
+    case Step::REDUCE_SCALE: st = run_reduce<T>(L, o, batch, &variant); break;
+    case Step::ELEMENTWISE: st = run_elementwise<T>(L, o, batch); break;
+    case Step::LINMAP: st = run_linmap<T>(L, o, batch); break;
+    case Step::EXPLOG_ADJ: st = run_explog_adj<T>(L, o, batch); break;
+    }
+    L.variant = variant;
+    return st;
+}
+
+template <typename T>
+int run_launches(gaast_hip_program_t prog, const std::vector<Bound>& in_bound, gaast_hip_mv_t out, int64_t first, int64_t count) {
     const Plan& plan = prog->plan;
-    const size_t sz = sizeof(T);
     auto shifted = [&](Bound b) {
-        if (b.ptr && first) b.ptr = static_cast<char*>(b.ptr) + size_t(first) * size_t(b.stride) * sz;
+        if (b.ptr && first) b.ptr = static_cast<char*>(b.ptr) + size_t(first) * size_t(b.stride) * sizeof(T);
         return b;
     };
-    std::vector<Bound> in_bound(in_bound0.size());
-    for (size_t i = 0; i < in_bound0.size(); ++i) in_bound[i] = shifted(in_bound0[i]);
-    const Bound out_b = shifted(Bound{out->ptr, out->row_stride});
+    EvalRows rows;
+    rows.prog = prog;
+    rows.out_layout = &out->layout;
+    rows.callers.resize(in_bound.size());
+    for (size_t i = 0; i < in_bound.size(); ++i) rows.callers[i] = shifted(in_bound[i]);
+    rows.out_callers = shifted(Bound{out->ptr, out->row_stride});
 
     // cache buffers of the product operands (the per-eval HashMap<NodeId, R> of eval.rs:16)
     if (prog->scratch_batch < count || prog->scratch.size() != plan.node_buffers.size()) {
@@ -2173,75 +2258,34 @@ int run_launches(gaast_hip_program_t prog, const std::vector<Bound>& in_bound0, 
 
     // a program in a non-orthonormal basis: every step but LINMAP reads the inputs' rows moved into the orthogonal basis (a shared
     // input: one row, broadcast) and writes the root into a node buffer that the last LINMAP step moves back into `out`
-    std::vector<Bound> inner_bound = in_bound;
-    Bound out_inner = out_b;
+    rows.moved = rows.callers;
+    rows.out_moved = rows.out_callers;
     for (size_t i = 0; i < plan.basis_slot_buf.size(); ++i) {
-        if (plan.basis_slot_buf[i] < 0 || !in_bound[i].ptr) continue;
+        if (plan.basis_slot_buf[i] < 0 || !rows.callers[i].ptr) continue;
         gaast_hip_mv_t m = prog->scratch[size_t(plan.basis_slot_buf[i])].get();
-        inner_bound[i] = Bound{m->ptr, in_bound[i].stride == 0 ? 0 : m->row_stride};
+        rows.moved[i] = Bound{m->ptr, rows.callers[i].stride == 0 ? 0 : m->row_stride};
     }
     if (plan.basis_out_buf >= 0) {
         gaast_hip_mv_t m = prog->scratch[size_t(plan.basis_out_buf)].get();
-        out_inner = Bound{m->ptr, m->row_stride};
+        rows.out_moved = Bound{m->ptr, m->row_stride};
     }
-    auto resolve = [&](BufRef r, Layout* lay) -> Bound {
-        switch (r.kind) {
-        case BufKind::NODE: {
-            gaast_hip_mv_t m = prog->scratch[size_t(r.idx)].get();
-            *lay = m->layout;
-            return Bound{m->ptr, m->row_stride};
-        }
-        case BufKind::INPUT: *lay = plan.input_layouts[size_t(r.idx)]; return inner_bound[size_t(r.idx)];
-        default: *lay = out->layout; return out_inner;
-        }
-    };
     for (const Launch& L : prog->launches) {
         const Step& s = L.s;
-        Layout lres, la, lb;
-        L.variant = 0;   // a launch with one kernel; run_step / run_jit record which of several they took
-        if (s.kind == Step::LINMAP) {   // the caller's rows in, the caller's rows out
-            Bound src, dst;
-            int64_t items = count;
-            if (s.a.kind == BufKind::INPUT) {
-                la = plan.input_layouts[size_t(s.a.idx)];
-                src = in_bound[size_t(s.a.idx)];
-                if (src.stride == 0) items = 1;   // shared by every item: moved once
-            } else {
-                src = resolve(s.a, &la);
-            }
-            if (s.res.kind == BufKind::OUT) {
-                lres = out->layout;
-                dst = out_b;
-            } else {
-                dst = resolve(s.res, &lres);
-            }
-            if (int st = run_step<T>(L, dst, src, Bound{nullptr, 0}, la, lb, items)) return st;
-            continue;
-        }
-        const Bound res = resolve(s.res, &lres);
-        if (s.kind == Step::FUSED) {
-            if (int st = run_fused<T>(L, plan, inner_bound, res, count)) return st;
-            continue;
-        }
-        if (s.kind == Step::ELEMENTWISE) {
-            if (int st = run_elementwise<T>(L, res, resolve, count)) return st;
-            continue;
-        }
-        if (s.kind == Step::ZERO) {
-            if (lres.row_len)
-                HIP_TRY(hipMemset2DAsync(res.ptr, size_t(res.stride) * sz, 0, size_t(lres.row_len) * sz,
-                                         size_t(count), g_stream));
-            continue;
-        }
-        Bound a{nullptr, 0}, b{nullptr, 0};
-        if (s.a.idx >= 0) a = resolve(s.a, &la);
-        if (s.b.idx >= 0) b = resolve(s.b, &lb);
-        auto extra = [&](BufRef r) {   // (an operand the step does not have stays null)
-            Layout unused;
-            return r.idx >= 0 ? resolve(r, &unused) : Bound{nullptr, 0};
+        const bool callers_rows = s.kind == Step::LINMAP;   // the caller's rows in, the caller's rows out
+        Operands o;
+        o.rows = &rows;
+        Layout unused;
+        auto at = [&](BufRef r, Layout* lay) {   // (an operand the step does not have stays null)
+            return r.idx >= 0 ? rows.at(r, lay, callers_rows) : Bound{nullptr, 0};
         };
-        const Extra x{extra(s.pre.a), extra(s.pre.b), extra(s.reduce.x), extra(s.cj.init_src)};
-        if (int st = run_step<T>(L, res, a, b, la, lb, count, x)) return st;
+        o.res = rows.at(s.res, &o.lres, callers_rows);
+        o.a = at(s.a, &o.la);
+        o.b = at(s.b, &o.lb);
+        o.pre_a = at(s.pre.a, &unused);
+        o.pre_b = at(s.pre.b, &unused);
+        o.scaled_row = at(s.reduce.x, &unused);
+        o.init = at(s.cj.init_src, &unused);
+        if (int st = run_launch<T>(L, o, count)) return st;
     }
     return GAAST_OK;
 }

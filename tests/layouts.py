@@ -87,7 +87,7 @@ class Placed:
         self.mv = ga.DeviceMV(h, dim, mask, self.batch, dtype, keep=self.flat)
         assert self.mv.row_len == self.row_len
 
-    # the launch-time rule of runtime.hip (vector row I/O): base pointer and row stride both multiples of 16 bytes.  A single
+    # the launch-time rule of runtime.hip (`rows_aligned16`, vector row I/O): base pointer and row stride both multiples of 16 bytes.  A single
     # (shared) row is bound with stride 0.
     def aligned16(self, bound_stride=None):
         stride = self.stride if bound_stride is None else bound_stride

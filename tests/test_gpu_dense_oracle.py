@@ -1,5 +1,5 @@
 """Dense geometric products against the ORACLE ITSELF at the sizes the dense kernels are quoted on (n = 10 ... 13):
-every (kernel, block size, waves per item) instantiation runtime.hip:prepare_step can pick is named here by a test that
+every (kernel, block size, waves per item) instantiation runtime.hip:prepare_dense can pick is named here by a test that
 compares with oracle_eval_batch.  The oracle builds the reference's 4^n-entry table (940 MB at n = 12), so the batches are
 1-3 items; n = 13 restricts the LEFT operand to grades 0..5 (the leading 29 % of the table: 1.1 GB instead of 3.8 GB), which
 keeps the product on the dense kernels (>= 1/8 of the full table).
@@ -28,7 +28,7 @@ def _gp(n, left_grades=None, right_grades=None):
 def _check(n, metric, left_grades, variants, batch, seed, out_grades=None, eps_factor=4, exact_order_too=False, right_grades=None,
            label_has=None):
     """variants: [(dtype, flags, expected launch-name prefix, HIP kernel)]; one oracle evaluation serves them all.  The launch
-    label names the HIP kernel instantiation prepare_step picked ("<what> :: <kernel<...>>", the name rocprofv3 reports):
+    label names the HIP kernel instantiation prepare_dense picked ("<what> :: <kernel<...>>", the name rocprofv3 reports):
     the test asserts it, so a docstring cannot go stale about which kernel it covers."""
     build, lg = _gp(n, left_grades, right_grades)
     rg = full_grades(n) if right_grades is None else right_grades

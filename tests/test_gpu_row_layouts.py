@@ -6,8 +6,8 @@ same values are evaluated under the layouts of tests/layouts.py -- applied to ON
 the right pointer shows only then) and to all rows at once -- against one reference evaluation per case:
 
   * the launch's kernel family is asserted from its label, the run-time variant from SpecializedAst.launch_variants()
-    (gaast_hip_program_launch_variant): the fast one under `contig`, the general one under every layout the rule in run_step
-    excludes, the fast one again under a layout the rule still admits.  Forms chosen INSIDE a generated kernel (gaast_jit,
+    (gaast_hip_program_launch_variant): the fast one under `contig`, the general one under every layout the rule in the launcher's
+    run_* function excludes, the fast one again under a layout the rule still admits.  Forms chosen INSIDE a generated kernel (gaast_jit,
     gaast_chain) or inside k_linmap_small / k_sum_rows are not visible to the host: the rule is cited where the case is defined;
   * values: the bound the project already states for the kernel (cited per case), never a new one;
   * two layouts that report the same variant give the same bits;
@@ -74,7 +74,7 @@ def _assignments(names, dtype, shared=()):
 
 
 def _aligned(p, batch):
-    """the launcher's test of a bound row (runtime.hip run_step: `aligned`): base and bound stride multiples of 16 bytes; a row
+    """the launcher's test of a bound row (runtime.hip: `rows_aligned16`): base and bound stride multiples of 16 bytes; a row
     shared by all items of a batch > 1 is bound with stride 0"""
     return p.aligned16(0 if (p.batch == 1 and batch != 1) else None)
 
@@ -199,13 +199,13 @@ def _const(v):
 
 
 def _both_operands_aligned(fast):
-    """k_gp_mfma16x4 (runtime.hip run_step, `prefetch`): the register-prefetch staging needs BOTH operand rows 16-byte aligned in
+    """k_gp_mfma16x4 (runtime.hip run_dense, `prefetch`): the register-prefetch staging needs BOTH operand rows 16-byte aligned in
     base and stride; the result's layout does not enter (`whole_rows` adds out_full && !beta, properties of the program)"""
     return lambda placed, batch: {None: fast if (_aligned(placed["in0"], batch) and _aligned(placed["in1"], batch)) else 0}
 
 
 # ITEMS PER WORKGROUP.  Only gaast_chain's label carries the figure (parsed there); for the others it is the launch geometry of
-# runtime.hip prepare_step / run_step, restated here -- if a geometry changes, the batch must follow:
+# runtime.hip prepare_* / run_* (per launcher), restated here -- if a geometry changes, the batch must follow:
 #   k_gp_mfma6      one wave per workgroup (GAAST_MFMA6_WAVES = 1) that keeps GAAST_MFMA6_DEPTH = 4 items in flight: 4
 #   k_gp_mfma7, k_gp_mfma16x4      one item per workgroup (items_per_block = 1): every batch > 1 ends in a full group; 1
 #   k_gp_mfma32p, n = 10           4 waves per workgroup, 1 wave per item (threads / 64 / (1 << (n - 10))): 4
@@ -226,7 +226,7 @@ DENSE_CASES = [
     _dense("mfma6-null-f32", 6, ga.F32, NULL6, "k_gp_mfma6<float,false,", _const(1), ipb=4),
     _dense("mfma6-general-f32", 6, ga.F32, [1.0] * 6, "k_gp_mfma6<float,false,", _const(0), left=[0, 1, 2, 3, 4, 6], ipb=4),
     # k_gp_mfma7: [2] full rows, [1] accumulating (beta), [0] a partial operand; "one component per lane and load: no alignment
-    # needed" (run_step), so again the variant is the program's under every layout
+    # needed" (run_dense), so again the variant is the program's under every layout
     _dense("mfma7-f32", 7, ga.F32, [1.0] * 7, "k_gp_mfma7<float,", _const(2)),
     _dense("mfma7-f64", 7, ga.F64, [1.0] * 7, "k_gp_mfma7<double,", _const(2)),
     _dense("mfma7-beta-f32", 7, ga.F32, [1.0] * 7, "k_gp_mfma7<float,", lambda p, b: {0: 2, 1: 1}, beta=True, factor=5),
@@ -239,7 +239,7 @@ DENSE_CASES = [
     _dense("mfma16-n8-f32-projected", 8, ga.F32, [1.0] * 8, "k_gp_mfma16x4<float,false,8,", _both_operands_aligned(1), out_sel=[0, 2, 3, 5, 8]),
     _dense("mfma16-n9-f64-projected", 9, ga.F64, [1.0] * 9, "k_gp_mfma16x4<double,false,9,", _both_operands_aligned(1), out_sel=[1, 2, 4, 6, 9]),
     # one kernel per launch; the 16-byte-piece branch of stage_operands is taken per operand INSIDE the kernel from
-    # DenseArgs::left_contig / right_contig = (full, sequential map) && aligned(base, stride), set in run_step: contig and pad16 rows
+    # DenseArgs::left_contig / right_contig = (full, sequential map) && rows_aligned16(row), set in run_dense: contig and pad16 rows
     # take it, pad_odd and every shift take the scalar branch
     _dense("mfma32p-n10-f32", 10, ga.F32, [1.0] * 10, "k_gp_mfma32p<false,10>", _const(0), ipb=4),
     _dense("dense-n10-f32", 10, ga.F32, MIXED10, "k_gp_dense<float,false,256,", _const(0), flags=ga.FLAG_NO_MFMA, ipb=4),
@@ -295,7 +295,7 @@ def _sandwich(name, n, family, shared):
         return want, wmask, S
 
     def expect(placed, batch):
-        # a chained step prefetches only its right operand (run_step: `s.chained ? true : ...`), here ~R = the rows of slot 0;
+        # a chained step prefetches only its right operand (run_dense: `s.dense.chained || ...`), here ~R = the rows of slot 0;
         # k_gp_mfma7 needs no alignment at all.  The list's own operands (pre_left / pre_right: slots 0 and 1) are read
         # component by component with strides of their own.
         if "mfma7" in family:
@@ -398,7 +398,7 @@ def _vinv_case(n):
     build = lambda B: B.input(0, even, n).vinv()
 
     def expect(placed, batch):
-        # run_step: k_reduce_scale_wave only if the operand rows AND the result rows are 16-byte aligned in base and stride
+        # run_reduce: k_reduce_scale_wave only if the operand rows AND the result rows are 16-byte aligned in base and stride
         # (its lanes move 16-byte pieces); anything else silently runs k_reduce_scale
         return {None: 1 if (_aligned(placed["in0"], batch) and _aligned(placed["out"], batch)) else 0}
 
@@ -504,7 +504,7 @@ def test_dense_adjoints_under_every_row_layout(n, dtype, slot):
 def test_linmap_under_every_row_layout(n, grades, dtype):
     """k_linmap_small (n <= 6) and k_linmap_mfma: full rows and a partial mask with an odd row length (15 elements at n = 5, 29 at n = 8,
     where `contig` rows are themselves not 16-byte aligned).  k_linmap_small takes 16-byte row I/O per side when
-    `stride == row_len && base % 16 == 0 && row bytes % 16 == 0` (runtime.hip launch_linmap: in_vec / out_vec, flags of the kernel's
+    `stride == row_len && base % 16 == 0 && row bytes % 16 == 0` (runtime.hip `rows_packed_aligned16`, launch_linmap: in_vec / out_vec, flags of the kernel's
     arguments, not a kernel table); k_linmap_mfma has one form.  Bound: the norm-wise one of test_gpu_linmap.py `check`.  The order
     of the sums does not depend on the row I/O: every layout gives the same bits."""
     grades = full_grades(n) if grades is None else grades
