@@ -18,11 +18,12 @@ STATUS_NAMES = {1: "INVALID_PROGRAM", 2: "MISSING_GRADE", 3: "UNIMPLEMENTED", 4:
                 6: "INVALID_ARGUMENT", 7: "NO_DEVICE", 8: "OVERFLOW"}
 F64, F32 = 0, 1
 (OP_INPUT, OP_ADD, OP_PRODUCT, OP_NEG, OP_EXP, OP_LOG, OP_PROJ, OP_REVERSE, OP_GINVOL, OP_SINV,
- OP_SSQRT, OP_EXP_ADJ, OP_LOG_ADJ) = range(13)
+ OP_SSQRT, OP_EXP_ADJ, OP_LOG_ADJ, OP_DUAL, OP_UNDUAL) = range(15)
 OP_NAMES = ["GradedObj", "Addition", "Product", "Negation", "Exponential", "Logarithm",
             "GradeProjection", "Reverse", "GradeInvolution", "ScalarInversion", "ScalarSqrt",
-            "ExponentialAdjoint", "LogarithmAdjoint"]
+            "ExponentialAdjoint", "LogarithmAdjoint", "Dual", "Undual"]
 PROD_EXPLICIT, PROD_GEOMETRIC, PROD_OUTER, PROD_INNER, PROD_LCONTRACT, PROD_RCONTRACT = -1, 0, 1, 2, 3, 4
+PROD_REGRESSIVE = 5   # a v b = undual(dual(a) ^ dual(b)): join / meet, metric-free
 PROD_ADJ_LEFT, PROD_ADJ_RIGHT = 8, 16   # added to a forward kind: compact adjoint products (reverse mode)
 FLAG_DEBUG_OVERFLOW, FLAG_NO_FUSION, FLAG_EXACT_ORDER, FLAG_NO_MFMA, FLAG_NO_JIT, FLAG_SPINOR_GEMM = 1, 2, 4, 8, 16, 32
 FLAG_DEBUG_JIT_FAILS, FLAG_DEBUG_KEEP_JIT_SOURCE, FLAG_EXP_LOG, FLAG_NO_COALESCE, FLAG_DEBUG_LDS_12K = 0x40, 0x80, 0x100, 0x200, 0x400
@@ -164,6 +165,8 @@ SIGNATURES = {
     "gaast_expr_norm_sq": (_vp, [_vp]),
     "gaast_expr_sinv": (_vp, [_vp]),
     "gaast_expr_vinv": (_vp, [_vp]),
+    "gaast_expr_dual": (_vp, [_vp]),
+    "gaast_expr_undual": (_vp, [_vp]),
     "gaast_expr_specialize": (_vp, [_vp, _ci, _pd, _u64]),
     "gaast_spec_free": (None, [_vp]),
     "gaast_spec_num_nodes": (_ci, [_vp]),

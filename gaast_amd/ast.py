@@ -2,7 +2,8 @@
 
 Same operator surface as the reference: `*` geometric, `^` outer, `&` inner, `<<` / `>>`
 contractions, `+ - unary-`, `.g(k) .rev() .ginvol() .conj() .scal() .norm_sq() .sinv() .vinv()
-.sqrt() .pow() .exp() .log()`.  Phases 1-3 run in the C++ host code of libgaast_hip.so;
+.sqrt() .pow() .exp() .log()`; beyond the reference, the metric-free complements `.dual() .undual()` and the regressive
+product `.vee(rhs)` (join of points / meet of planes).  Phases 1-3 run in the C++ host code of libgaast_hip.so;
 `SpecializedAst.eval*` is phase 4 on the GPU through the C ABI -- there is no CPU path.
 """
 from __future__ import annotations
@@ -79,6 +80,10 @@ class Expr:
     def __rshift__(self, rhs):
         return self._bin(rhs, _lib.lib().gaast_expr_product, _lib.PROD_RCONTRACT)
 
+    def vee(self, rhs):
+        """The regressive product a v b = undual(dual(a) ^ dual(b)): grade k_a + k_b - n, no metric factor."""
+        return self._bin(rhs, _lib.lib().gaast_expr_product, _lib.PROD_REGRESSIVE)
+
     def product(self, rhs, grades_to_produce):                       # expr.rs:123-144
         """Custom product: grades_to_produce(k1, k2) -> iterable of grades / GradeSet."""
         def cb(k1, k2, _user):
@@ -144,6 +149,14 @@ class Expr:
 
     def vinv(self):
         return self._un(_lib.lib().gaast_expr_vinv)
+
+    def dual(self):
+        """Right complement: dual(e_S) = +-e_~S with e_S ^ dual(e_S) = I (GAAST_OP_DUAL); grade k -> n - k."""
+        return self._un(_lib.lib().gaast_expr_dual)
+
+    def undual(self):
+        """Left complement, the exact inverse (and the transpose) of dual() (GAAST_OP_UNDUAL)."""
+        return self._un(_lib.lib().gaast_expr_undual)
 
     # -- phases 2-3 ----------------------------------------------------------------------------
     def specialize(self, alg, dtype=_lib.F64, flags=0, materialize_limit=DEFAULT_MATERIALIZE_LIMIT):

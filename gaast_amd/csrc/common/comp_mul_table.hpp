@@ -14,8 +14,17 @@ namespace gaast {
 
 // Exact length of the list without generating it: pairs (a,b) with |a|=kl, |b|=kr sharing s
 // basis vectors number C(n,kl) C(kl,s) C(n-kl,kr-s) and land in grade kl+kr-2s.
-inline uint64_t comp_mul_count(int n, const std::vector<Contrib>& contribs) {
+// regressive: C(n,kl) left blades, and a right blade is the left one's complement (n - kl vectors) plus kr - (n - kl) of the left's kl
+inline uint64_t comp_mul_count(int n, const std::vector<Contrib>& contribs, bool regressive = false) {
     uint64_t total = 0;
+    if (regressive) {
+        for (const Contrib& c : contribs) {
+            const int g = c.k_left + c.k_right - n;
+            if (g < 0 || g > 63 || c.k_left > n || c.k_right > n || !((c.contribs >> g) & 1ULL)) continue;
+            total += n_choose_k(n, c.k_left) * n_choose_k(c.k_left, g);
+        }
+        return total;
+    }
     for (const Contrib& c : contribs) {
         for (int s = 0; s <= c.k_left && s <= c.k_right; ++s) {
             int g = c.k_left + c.k_right - 2 * s;
@@ -27,14 +36,42 @@ inline uint64_t comp_mul_count(int n, const std::vector<Contrib>& contribs) {
     return total;
 }
 
+// 1 when the right complement of blade s (GAAST_OP_DUAL, gaast_hip.h) carries a minus sign: par(S, ~S); the left complement
+// (GAAST_OP_UNDUAL) has par(~S, S) = complement_parity(~S)
+inline int complement_parity(int n, uint64_t s) {
+    const uint64_t full = n >= 64 ? ~0ULL : ((1ULL << n) - 1ULL);
+    return reorder_parity(s & full, ~s & full);
+}
+
+// e_a v e_b = undual(dual(e_a) ^ dual(e_b)): non-zero only when a | b is full, then +-e_{a & b}; *neg = the sign
+inline bool regressive_blades(int n, uint64_t a, uint64_t b, int* neg) {
+    const uint64_t full = n >= 64 ? ~0ULL : ((1ULL << n) - 1ULL);
+    if ((a | b) != full) return false;
+    const uint64_t ca = ~a & full, cb = ~b & full;   // disjoint: their outer product is +-e_{ca | cb}
+    *neg = (complement_parity(n, a) + complement_parity(n, b) + reorder_parity(ca, cb) + complement_parity(n, a & b)) & 1;
+    return true;                                      // (undual(e_{ca|cb}) has par(~(ca|cb), ca|cb) = complement_parity(a & b))
+}
+
 template <class Emit>
 inline void for_each_comp_mul(const BladeTable& bt, const double* metric_diag,
-                              const std::vector<Contrib>& contribs, Emit&& emit) {
+                              const std::vector<Contrib>& contribs, Emit&& emit, bool regressive = false) {
     const int n = bt.n;
     for (const Contrib& c : contribs) {
         if (c.k_left > n || c.k_right > n) continue;  // grade_dim == 0: no blades
         const auto& lb = bt.blade_of[c.k_left];
         const auto& rb = bt.blade_of[c.k_right];
+        if (regressive) {  // the same order T4 over the pairs with a | b full; no metric factor
+            for (uint32_t li = 0; li < lb.size(); ++li)
+                for (uint32_t ri = 0; ri < rb.size(); ++ri) {
+                    const uint64_t a = lb[li], b = rb[ri];
+                    int neg = 0;
+                    if (!regressive_blades(n, a, b, &neg)) continue;
+                    const int g = __builtin_popcountll(a & b);
+                    if (!((c.contribs >> g) & 1ULL)) continue;
+                    emit(gaast_comp_mul{uint32_t(c.k_left), li, uint32_t(c.k_right), ri, uint32_t(g), bt.index_of[a & b], neg ? -1.0 : 1.0});
+                }
+            continue;
+        }
         for (uint32_t li = 0; li < lb.size(); ++li) {
             const uint64_t a = lb[li];
             for (uint32_t ri = 0; ri < rb.size(); ++ri) {

@@ -32,14 +32,23 @@ inline uint64_t gs_mul(uint64_t a, uint64_t b) {
     return res;
 }
 
-// The five grades_to_produce closures of expr.rs:180-197
-inline uint64_t gs_select(int kind, int64_t k1, int64_t k2) {
+// grades of a complement (GAAST_OP_DUAL / GAAST_OP_UNDUAL): k -> n - k
+inline uint64_t gs_mirror(uint64_t mask, int n) {
+    uint64_t m = 0;
+    for (int k = 0; k <= n && k < 64; ++k)
+        if ((mask >> k) & 1ULL) m |= 1ULL << (n - k);
+    return m;
+}
+
+// The five grades_to_produce closures of expr.rs:180-197, and the regressive product's (the only one that needs the dimension n)
+inline uint64_t gs_select(int kind, int64_t k1, int64_t k2, int n = 0) {
     switch (kind) {
     case GAAST_PROD_GEOMETRIC: return gs_mul(gs_single(k1), gs_single(k2));
     case GAAST_PROD_OUTER: return gs_single(k1 + k2);
     case GAAST_PROD_INNER: return (k1 == 0 || k2 == 0) ? 0 : gs_single(k1 > k2 ? k1 - k2 : k2 - k1);
     case GAAST_PROD_LCONTRACT: return gs_single(k2 - k1);
     case GAAST_PROD_RCONTRACT: return gs_single(k1 - k2);
+    case GAAST_PROD_REGRESSIVE: return gs_single(k1 + k2 - n);
     default: return 0;
     }
 }
@@ -48,8 +57,9 @@ struct Selection {  // KVecsProductGradeSelection, base_types.rs:60-82
     int kind = GAAST_PROD_GEOMETRIC;   // GAAST_PROD_EXPLICIT => custom closure below
     gaast_select_fn fn = nullptr;
     void* user = nullptr;
+    int n = 0;                         // the algebra's dimension: GAAST_PROD_REGRESSIVE produces grade k1 + k2 - n
     uint64_t operator()(int64_t k1, int64_t k2) const {
-        return kind >= 0 ? gs_select(kind, k1, k2) : fn(k1, k2, user);
+        return kind >= 0 ? gs_select(kind, k1, k2, n) : fn(k1, k2, user);
     }
 };
 

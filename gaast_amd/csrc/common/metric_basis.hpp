@@ -175,4 +175,30 @@ inline void compound_matrix_vjp(int n, int k, const double* m, const double* w, 
     }
 }
 
+// determinant by Gaussian elimination with partial pivoting (m: n x n, row-major)
+inline double matrix_determinant(int n, const double* m) {
+    std::vector<double> a(m, m + size_t(n) * size_t(n));
+    double det = 1.0;
+    for (int c = 0; c < n; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < n; ++r)
+            if (std::fabs(a[size_t(r * n + c)]) > std::fabs(a[size_t(piv * n + c)])) piv = r;
+        if (a[size_t(piv * n + c)] == 0.0) return 0.0;
+        if (piv != c) {
+            for (int k = 0; k < n; ++k) std::swap(a[size_t(piv * n + k)], a[size_t(c * n + k)]);
+            det = -det;
+        }
+        det *= a[size_t(c * n + c)];
+        for (int r = c + 1; r < n; ++r) {
+            const double f = a[size_t(r * n + c)] / a[size_t(c * n + c)];
+            for (int k = c; k < n; ++k) a[size_t(r * n + k)] -= f * a[size_t(c * n + k)];
+        }
+    }
+    return det;
+}
+
+// does the orthogonal basis Q of a Gram metric reverse the orientation (det Q = -1)?  The complement in the caller's basis is
+// det(Q) times the complement in the orthogonal basis (gaast_hip.h: GAAST_OP_DUAL): such a program is lowered with Plan::mirrored
+inline bool basis_is_mirrored(int n, const double* q) { return matrix_determinant(n, q) < 0.0; }
+
 }  // namespace gaast

@@ -57,6 +57,48 @@ __global__ __launch_bounds__(256) void k_scalar_unary(T* __restrict__ res, int64
 }
 
 // ------------------------------------------------------------------------------------------
+// Complements (GAAST_OP_DUAL / GAAST_OP_UNDUAL, gaast_hip.h): res += the signed, grade-mirroring copy of `in` (Step::Dual).
+// A thread owns one component t of the segments laid end to end and walks the items: the segment look-up (uniform loads of a
+// table of at most GAAST_MAX_DIM + 1 rows) and the sign bit are paid once per thread, not per element.  Consecutive lanes read
+// consecutive components of a source grade (coalesced) and write consecutive components of the target grade in descending order:
+// a wave's stores cover one contiguous span.  Rows narrower than a workgroup share it between 256 >> col_shift items.  Scalar
+// accesses only: any row stride, padding or alignment of the bound rows takes the same code.
+// ------------------------------------------------------------------------------------------
+template <typename T>
+struct DualArgs {
+    T* res;
+    const T* in;
+    int64_t res_stride, in_stride, batch;
+    const uint32_t* segs;   // per segment: first component t, operand offset of it, result offset of it, (unused)
+    const uint32_t* neg;    // bit t: negate
+    int n_segs, total;
+    int col_shift;          // a workgroup covers 1 << col_shift components of 256 >> col_shift items
+    int beta;               // 0: the zero fill of a fresh result is folded in
+    int canon;              // the operand is a bound input read in place: 0.0 + x, as its cache buffer would hold it
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_dual(const DualArgs<T> p) {
+    const uint32_t cols = 1u << p.col_shift;
+    const uint32_t t = blockIdx.x * cols + (threadIdx.x & (cols - 1u));
+    if (t >= uint32_t(p.total)) return;
+    uint32_t first = 0, a0 = 0, r0 = 0;
+    for (int g = 0; g < p.n_segs; ++g) {   // segments ascend in t: the last one that starts at or before t
+        const uint32_t f = p.segs[4 * g];
+        if (t >= f) first = f, a0 = p.segs[4 * g + 1], r0 = p.segs[4 * g + 2];
+    }
+    const uint32_t a = a0 + (t - first), r = r0 - (t - first);
+    const bool neg = ((p.neg[t >> 5] >> (t & 31u)) & 1u) != 0;
+    const int64_t per_block = 256 >> p.col_shift;
+    for (int64_t item = int64_t(blockIdx.y) * per_block + (threadIdx.x >> p.col_shift); item < p.batch; item += int64_t(gridDim.y) * per_block) {
+        T x = p.in[item * p.in_stride + a];
+        if (p.canon) x = T(0) + x;
+        T* d = p.res + item * p.res_stride + r;
+        *d = (p.beta ? *d : T(0)) + (neg ? -x : x);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // EXTENSION (GAAST_FLAG_EXP_LOG; eval.rs:112-113 is todo!() upstream): res += exp(B) / log(a + B) for a k-vector B whose
 // square is scalar -- the statements of oracle/gaast_oracle.c: ext_exp_log in its order, one thread per item.  Items whose
 // B B has a non-negligible non-scalar part are counted in *dom (gaast_hip_program_domain_errors).
@@ -559,7 +601,7 @@ __global__ __launch_bounds__(256) void k_reduce_scale_wave(ReduceScaleArgs<T> p,
 // produces -- k_axpy_map, k_flip, k_flip, ... each a full read-modify-write of the buffer (an expression like
 // (-(a.rev()) + b.ginvol()).rev() * s at n = 12: six passes over 268 MB instead of one).
 //   ops: [n_ops][n_comp] words, statement k of component c:  [1:0] 0 nothing, 1 v = v + src, 2 v = -v, 3 v = 0.0 + src;
-//        [4:2] source slot;  [31:16] source offset.   Epilogue (scale): out[out_off[c]] = 0.0 + ((0.0 + v) * s) * coeff[c].
+//        [4:2] source slot;  [5] negate the source, [6] read it as 0.0 + src (a complement, Step::DUAL);  [31:16] source offset.   Epilogue (scale): out[out_off[c]] = 0.0 + ((0.0 + v) * s) * coeff[c].
 // ------------------------------------------------------------------------------------------
 constexpr int ELEMENTWISE_MAX_SRC = 6;
 template <typename T>
@@ -602,7 +644,7 @@ __global__ __launch_bounds__(256) void k_elementwise(ElementwiseArgs<T> p) {
 #pragma unroll
     for (int k = 0; k < NOPS; ++k) {
         const uint32_t w = k < p.n_ops ? p.ops[size_t(k) * p.n_comp + c] : 0u;
-        op[k] = w & 3u;
+        op[k] = w & 0x63u;   // statement, negate, canon
         const int sl = int((w >> 2) & 7u);
         ld_ptr[k] = p.src[sl] + (w >> 16);      // (only dereferenced when the statement reads a source)
         ld_stride[k] = p.src_stride[sl];
@@ -616,7 +658,11 @@ __global__ __launch_bounds__(256) void k_elementwise(ElementwiseArgs<T> p) {
         for (int u = 0; u < U; ++u) {
             const int64_t item = item0 + u < p.batch ? item0 + u : item0;   // (the tail re-reads the step's first item; it is not stored twice)
 #pragma unroll
-            for (int k = 0; k < NOPS; ++k) x[u][k] = (op[k] & 1u) ? ld_ptr[k][item * ld_stride[k]] : zero;   // ops 1 and 3 read
+            for (int k = 0; k < NOPS; ++k) {
+                T ld = (op[k] & 1u) ? ld_ptr[k][item * ld_stride[k]] : zero;   // ops 1 and 3 read
+                if (op[k] & 64u) ld = zero + ld;
+                x[u][k] = (op[k] & 32u) ? -ld : ld;
+            }
             v[u] = p.load_first ? p.res[item * p.res_stride + own] : zero;
             s[u] = p.out_off ? p.scalar[item * p.scalar_stride + p.scalar_off] : zero;
         }
@@ -626,8 +672,8 @@ __global__ __launch_bounds__(256) void k_elementwise(ElementwiseArgs<T> p) {
             T val = v[u];
 #pragma unroll
             for (int k = 0; k < NOPS; ++k) {
-                if (op[k] == 2u) val = -val;                                       // graded.rs:63
-                else if (op[k]) val = (op[k] == 3u ? zero : val) + x[u][k];       // graded.rs:74 (op 3: onto the fresh +0.0 of init_null_mv)
+                if ((op[k] & 3u) == 2u) val = -val;                                // graded.rs:63
+                else if (op[k] & 3u) val = ((op[k] & 3u) == 3u ? zero : val) + x[u][k];       // graded.rs:74 (op 3: onto the fresh +0.0 of init_null_mv)
             }
             const int64_t item = item0 + u;
             if (p.out_off) {

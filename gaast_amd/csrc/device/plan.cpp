@@ -210,9 +210,64 @@ struct Lowering {
             return;
         case GAAST_OP_EXP_ADJ:
         case GAAST_OP_LOG_ADJ: lower_exp_log_adj(res, id); return;
+        case GAAST_OP_DUAL:
+        case GAAST_OP_UNDUAL: lower_dual(res, id); return;
         case GAAST_OP_PRODUCT: lower_product(res, id); return;
         default: throw std::runtime_error("unknown opcode");
         }
+    }
+
+    // Complements (GAAST_OP_DUAL / GAAST_OP_UNDUAL, gaast_hip.h; no reference counterpart): a one-operand product arm.  The operand is
+    // read like a Product's (operand(): a bound input in place, sign-only arms over it folded into the signs, else its cache buffer,
+    // eval.rs:67-68); res += +-x, component i of grade k at component C(n,k) - 1 - i of grade n - k.
+    void lower_dual(BufRef res, int id) {
+        const gaast_node_desc& nd = node(id);
+        const int n = d.vec_space_dim;
+        const bool undual = nd.opcode == GAAST_OP_UNDUAL;
+        const uint64_t want = gs_mirror(nd.minimal_grade_mask, n) & node(nd.child0).minimal_grade_mask;   // source grades
+        if (!want) return;
+        int canon = 0;
+        uint64_t flip = 0;
+        BufRef a = operand(nd.child0, &canon, &flip);
+        if (!ok()) return;
+        if (key(a) == key(res)) {
+            fail(GAAST_ERR_MISSING_GRADE, "complement operand aliases its own result buffer");
+            return;
+        }
+        const Layout &la = layout(a), &lr = layout(res);
+        Step::Dual q;
+        q.undual = undual;
+        const uint64_t full = (uint64_t(1) << n) - 1;
+        for (int k = 0; k <= n; ++k) {
+            if (!((want >> k) & 1ULL) || !((la.mask >> k) & 1ULL)) continue;
+            if (!((lr.mask >> (n - k)) & 1ULL)) {
+                fail(GAAST_ERR_MISSING_GRADE, "grade " + std::to_string(n - k) + " absent from result buffer");
+                return;
+            }
+            const int64_t c = int64_t(bt.grade_dim[size_t(k)]);
+            if (lr.grade_len(n - k) != c) throw std::runtime_error("complement into a buffer of another dimension");
+            const int64_t len = std::min(la.grade_len(k), c);   // (an operand stored in a smaller dimension: its leading components)
+            if (len <= 0) continue;
+            q.segs.push_back({uint32_t(la.offset(k)), uint32_t(lr.offset(n - k) + c - 1), uint32_t(len)});
+            for (int64_t i = 0; i < len; ++i) {
+                const uint64_t s = bt.blade_of[size_t(k)][size_t(i)];
+                const int neg = (complement_parity(n, undual ? (~s & full) : s) + int((flip >> k) & 1ULL) + plan.mirrored) & 1;
+                if ((q.total & 31) == 0) q.neg.push_back(0u);
+                if (neg) q.neg.back() |= 1u << (q.total & 31);
+                ++q.total;
+            }
+        }
+        if (!q.total) return;
+        // the first writer of a fresh buffer that covers every component of it: the zero fill is folded in (res = 0.0 + (+-x))
+        const auto fr = fresh.find(key(res));
+        const bool covers = fr != fresh.end() && !(plan.flags & GAAST_FLAG_NO_FUSION) && int64_t(q.total) == lr.row_len;
+        if (covers) removed[size_t(fr->second)] = 1;
+        Step& s = emit(Step::DUAL, res, std::string(undual ? "undual" : "dual") + "[" + std::to_string(q.total) + " components, n=" + std::to_string(n) + "]");
+        s.a = a;
+        s.canon_a = canon;
+        s.beta = covers ? 0 : 1;
+        s.dual = std::move(q);
+        touch(res);
     }
 
     // EXTENSION (GAAST_FLAG_EXP_LOG; eval.rs:112-113 is todo!() upstream, "no reference behaviour"): the semantics the
@@ -1078,6 +1133,9 @@ struct Lowering {
         }
 
         // ---- exact path: CSR by output component, entries in the reference's order ----
+        // (a regressive list -- generated here, or explicit and naming its kind -- takes the orientation sign of a Gram basis)
+        const bool regressive = nd.product_kind >= 0 && (nd.product_kind & 7) == GAAST_PROD_REGRESSIVE;
+        const bool mirror_list = regressive && plan.mirrored;
         std::vector<gaast_comp_mul> generated;
         const gaast_comp_mul* muls = nd.comp_muls;
         uint64_t n_muls = nd.n_comp_muls;
@@ -1097,9 +1155,9 @@ struct Lowering {
         if (!muls && nd.product_kind >= GAAST_PROD_ADJ_LEFT) {
             // compact adjoint: regenerate the forward list from the node's three grade sets, then transpose it
             const bool right = (nd.product_kind & GAAST_PROD_ADJ_RIGHT) != 0;
-            const Selection sel{nd.product_kind & 7, nullptr, nullptr};
+            const Selection sel{nd.product_kind & 7, nullptr, nullptr, d.vec_space_dim};
             auto contribs = right ? iter_contribs(lmin, sel, rmin, omin) : iter_contribs(lmin, sel, omin, rmin);
-            const uint64_t count = comp_mul_count(d.vec_space_dim, contribs);
+            const uint64_t count = comp_mul_count(d.vec_space_dim, contribs, regressive);
             // no dense kernel took it (EXACT_ORDER, a kind other than geometric, a metric the kernels cannot scale): the list is
             // regenerated, transposed and sorted on the host -- refused beyond kMaxAdjointListEntries instead of building GBs
             if (count > kMaxAdjointListEntries && plan.unsupported.empty())
@@ -1108,21 +1166,21 @@ struct Lowering {
             if (!plan.unsupported.empty()) return;
             std::vector<gaast_comp_mul> fwd;
             fwd.reserve(size_t(count));
-            for_each_comp_mul(bt, d.metric_diag, contribs, [&](const gaast_comp_mul& m) { fwd.push_back(m); });
+            for_each_comp_mul(bt, d.metric_diag, contribs, [&](const gaast_comp_mul& m) { fwd.push_back(m); }, regressive);
             generated = transpose_comp_muls(fwd.data(), fwd.size(), right, true);
             muls = generated.data();
             n_muls = generated.size();
         }
         if (!muls) {
-            Selection sel{nd.product_kind, nullptr, nullptr};
+            Selection sel{nd.product_kind, nullptr, nullptr, d.vec_space_dim};
             auto contribs = iter_contribs(omin, sel, lmin, rmin);
-            if (comp_mul_count(d.vec_space_dim, contribs) > kMaxListEntries && plan.unsupported.empty())
-                plan.unsupported = "a comp-mul list of " + std::to_string(comp_mul_count(d.vec_space_dim, contribs)) +
+            if (comp_mul_count(d.vec_space_dim, contribs, regressive) > kMaxListEntries && plan.unsupported.empty())
+                plan.unsupported = "a comp-mul list of " + std::to_string(comp_mul_count(d.vec_space_dim, contribs, regressive)) +
                                    " entries exceeds this back end's table budget";
             if (!plan.unsupported.empty()) return;
-            generated.reserve(size_t(comp_mul_count(d.vec_space_dim, contribs)));
+            generated.reserve(size_t(comp_mul_count(d.vec_space_dim, contribs, regressive)));
             for_each_comp_mul(bt, d.metric_diag, contribs,
-                              [&](const gaast_comp_mul& m) { generated.push_back(m); });
+                              [&](const gaast_comp_mul& m) { generated.push_back(m); }, regressive);
             muls = generated.data();
             n_muls = generated.size();
         }
@@ -1182,7 +1240,7 @@ struct Lowering {
             const uint32_t lo = uint32_t(ll.offset(int(m.left_grade)) + m.left_index);
             const uint32_t ro = uint32_t(lrr.offset(int(m.right_grade)) + m.right_index);
             s.list.entries[pos] = lo | (ro << 16);
-            const bool neg = (((flip_l >> m.left_grade) ^ (flip_r >> m.right_grade)) & 1ULL) != 0;
+            const bool neg = ((((flip_l >> m.left_grade) ^ (flip_r >> m.right_grade)) & 1ULL) != 0) != mirror_list;
             s.list.coeff[pos] = neg ? -m.coeff : m.coeff;
         }
         touch(res);
@@ -1470,15 +1528,15 @@ static void fuse_elementwise_runs(Plan& plan) {
     };
     for (size_t i = 0; i < plan.steps.size(); ++i) {
         const Step& first = plan.steps[i];
-        if (first.kind != Step::AXPY && first.kind != Step::FLIP) continue;
+        if (first.kind != Step::AXPY && first.kind != Step::FLIP && first.kind != Step::DUAL) continue;
         const BufRef R = first.res;
         size_t j = i;
         std::vector<BufRef> srcs;
         bool ok = true;
         while (j < plan.steps.size() && ok) {
             const Step& t = plan.steps[j];
-            if ((t.kind != Step::AXPY && t.kind != Step::FLIP) || t.res != R) break;
-            if (t.kind == Step::AXPY) {
+            if ((t.kind != Step::AXPY && t.kind != Step::FLIP && t.kind != Step::DUAL) || t.res != R) break;
+            if (t.kind != Step::FLIP) {   // AXPY, DUAL: statements that read a bound input
                 if (t.a.kind != BufKind::INPUT) break;
                 bool known = false;
                 for (const BufRef& b : srcs) known = known || b == t.a;
@@ -1499,6 +1557,7 @@ static void fuse_elementwise_runs(Plan& plan) {
         for (size_t k = i; k < j; ++k) {
             for (uint32_t w : plan.steps[k].axpy_map) comp_of[w & 0xffffu] = 0;
             for (uint32_t off : plan.steps[k].flip_offsets) comp_of[off] = 0;
+            if (plan.steps[k].kind == Step::DUAL) plan.steps[k].dual.for_each([&](uint32_t r, uint32_t, bool) { comp_of[r] = 0; });
         }
         for (int64_t o = 0; o < rl; ++o)
             if (comp_of[size_t(o)] == 0) {
@@ -1517,6 +1576,10 @@ static void fuse_elementwise_runs(Plan& plan) {
                 for (size_t q = 0; q < srcs.size(); ++q)
                     if (srcs[q] == t.a) slot = uint32_t(q);
                 for (uint32_t w : t.axpy_map) ops[(k - i) * nc + size_t(comp_of[w & 0xffffu])] = (t.beta ? 1u : 3u) | (slot << 2) | ((w >> 16) << 16);
+                if (t.kind == Step::DUAL)   // a complement: the same statement with the source negated (bit 5) and read as a product operand (bit 6)
+                    t.dual.for_each([&](uint32_t r, uint32_t a, bool neg) {
+                        ops[(k - i) * nc + size_t(comp_of[r])] = (t.beta ? 1u : 3u) | (slot << 2) | (neg ? 32u : 0u) | (t.canon_a ? 64u : 0u) | (a << 16);
+                    });
             }
         }
         // Every component executes ITS OWN statements in order, so each list is compacted on its own: empty statements go, and two
@@ -1768,7 +1831,8 @@ static void jit_long_row_lists(Plan& plan) {
     }
 }
 
-void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab) {
+void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab, bool mirrored) {
+    plan.mirrored = mirrored ? 1 : 0;
     if (desc.vec_space_dim < 0 || desc.vec_space_dim > GAAST_MAX_DIM) throw std::runtime_error("vec_space_dim out of range");
     if (desc.n_nodes <= 0 || desc.root < 0 || desc.root >= desc.n_nodes) throw std::runtime_error("bad node count / root");
     if (desc.dtype != GAAST_F64 && desc.dtype != GAAST_F32) throw std::runtime_error("bad dtype");
@@ -1805,12 +1869,13 @@ void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab)
             if (!child_ok(nd.child0) || !child_ok(nd.child1)) throw std::runtime_error("nodes are not in post-order");
             if (nd.opcode == GAAST_OP_PRODUCT && nd.product_kind >= GAAST_PROD_ADJ_LEFT) {
                 const int adj = nd.product_kind & ~7, base = nd.product_kind & 7;
-                if ((adj != GAAST_PROD_ADJ_LEFT && adj != GAAST_PROD_ADJ_RIGHT) || base > GAAST_PROD_RCONTRACT)
+                if ((adj != GAAST_PROD_ADJ_LEFT && adj != GAAST_PROD_ADJ_RIGHT) || base > GAAST_PROD_REGRESSIVE)
                     throw std::runtime_error("unknown product kind");
             }
             break;
         case GAAST_OP_NEG: case GAAST_OP_EXP: case GAAST_OP_LOG: case GAAST_OP_PROJ:
         case GAAST_OP_REVERSE: case GAAST_OP_GINVOL: case GAAST_OP_SINV: case GAAST_OP_SSQRT:
+        case GAAST_OP_DUAL: case GAAST_OP_UNDUAL:
             if (!child_ok(nd.child0)) throw std::runtime_error("nodes are not in post-order");
             break;
         default: throw std::runtime_error("unknown opcode");

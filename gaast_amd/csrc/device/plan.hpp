@@ -52,8 +52,8 @@ enum class DenseFamily {
 // a step in place), each table and setting named after the one thing it holds.  The groups of the other kinds stay empty.  The
 // tables are host images, uploaded once at program_create.
 struct Step {
-    enum Kind { ZERO, AXPY, FLIP, SUNARY, PRODUCT_CSR, PRODUCT_DENSE, FUSED, EXPLOG, REDUCE_SCALE, ELEMENTWISE, LINMAP, EXPLOG_ADJ } kind = ZERO;
-    BufRef res, a, b;        // result; operand rows (PRODUCT_*: left, right; AXPY / EXPLOG / LINMAP: a; EXPLOG_ADJ: a = the forward operand, b = the cotangent; REDUCE_SCALE: the reduction's; ELEMENTWISE: b = the scalar)
+    enum Kind { ZERO, AXPY, FLIP, SUNARY, PRODUCT_CSR, PRODUCT_DENSE, FUSED, EXPLOG, REDUCE_SCALE, ELEMENTWISE, LINMAP, EXPLOG_ADJ, DUAL } kind = ZERO;
+    BufRef res, a, b;        // result; operand rows (PRODUCT_*: left, right; AXPY / EXPLOG / LINMAP / DUAL: a; EXPLOG_ADJ: a = the forward operand, b = the cotangent; REDUCE_SCALE: the reduction's; ELEMENTWISE: b = the scalar)
     std::string name;
     int canon_a = 0, canon_b = 0;   // the operand is a bound input read in place: the kernel applies the reference's 0.0 + x
     int beta = 1;                   // 0: the zero fill of a fresh result is folded in
@@ -188,6 +188,24 @@ struct Step {
         std::vector<double> sq;    // e_i e_i (blade squares, component order)
     } adj;
 
+    // DUAL (GAAST_OP_DUAL / GAAST_OP_UNDUAL, gaast_hip.h): res += the signed, grade-mirroring copy of row `a`.  One segment per source
+    // grade, in ascending grade order: its `len` components are read at a_off, a_off + 1, ... and written at res_last, res_last - 1, ...
+    // (component i of grade k goes to C(n,k) - 1 - i of grade n - k); bit t of `neg` negates the t-th component of the segments
+    // laid end to end
+    struct Dual {
+        struct Seg { uint32_t a_off, res_last, len; };
+        std::vector<Seg> segs;
+        std::vector<uint32_t> neg;
+        int total = 0;                  // components over all segments
+        int undual = 0;                 // (the name only)
+        template <typename F>
+        void for_each(F&& f) const {    // f(result offset, operand offset, negate) in the order of the segments
+            uint32_t t = 0;
+            for (const Seg& g : segs)
+                for (uint32_t i = 0; i < g.len; ++i, ++t) f(g.res_last - i, g.a_off + i, ((neg[t >> 5] >> (t & 31u)) & 1u) != 0);
+        }
+    } dual;
+
     // REDUCE_SCALE (plan.cpp: fuse_reduce_scale): a product whose result is ONE scalar component (a single long row: norm_sq), an
     // optional ScalarUnaryOp on it, and a product of one-term rows that multiplies another row by that scalar -- the versor inverse
     // a.rev() * a.norm_sq().sinv() and normalisations, where the rows no longer fit a fused slab (n >= 9) -- in ONE launch, one wave per
@@ -264,6 +282,8 @@ struct Plan {
     std::string error_msg;
     int has_explog = 0;                // some step evaluates exp / log: the program owns a domain-error counter
     int has_explog_adj = 0;            // some step is an exp / log adjoint (no interpreter micro-ops, no domain check)
+    int mirrored = 0;                  // the program runs in the orthogonal basis of a Gram metric whose Q has det -1: every
+                                       // complement sign and regressive coefficient is negated (gaast_hip.h: GAAST_OP_DUAL)
     std::string unsupported;           // non-empty: valid in the reference, beyond this back end (program_create fails)
     std::vector<char> slot_used;       // input slots some launch reads (the others may stay unbound)
     std::string jit_source_kept;       // GAAST_FLAG_DEBUG_KEEP_JIT_SOURCE
@@ -277,11 +297,11 @@ struct Plan {
 // Throws std::runtime_error (-> GAAST_ERR_INVALID_PROGRAM) on malformed input.  small_reg_slab: the one-item-per-thread
 // specialised kernel is limited to slabs of 160 / 200 elements (runtime.hip rebuilds a plan so when a bigger slab's trial
 // compilation needs more than half of a SIMD's registers)
-void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab = false);
+void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab = false, bool mirrored = false);
 
 // Micro-op encoding shared by the plan builder and k_ast_fused (see kernels.hip.hpp).
 namespace uop {
-enum : uint32_t { LINE_MACS = 0, LINE_MISC = 1, LINE_NOP = 2, LINE_MACS_GEN = 3, LINE_MACS_CNT = 4, ADD = 3, NEG = 4, ZERO = 5, INV = 6, SQRT = 7, COPY = 8 };
+enum : uint32_t { LINE_MACS = 0, LINE_MISC = 1, LINE_NOP = 2, LINE_MACS_GEN = 3, LINE_MACS_CNT = 4, ADD = 3, NEG = 4, ZERO = 5, INV = 6, SQRT = 7, COPY = 8, SUB = 9, NCOPY = 10 };
 constexpr int MAX_GENERAL_COEFFS = 6;
 constexpr int MAX_INPUTS = 8;
 constexpr int GROUPS = 8;  // waves per workgroup of k_ast_fused (FUSED_GROUPS)

@@ -55,6 +55,7 @@ SlabLayout::SlabLayout(const Plan& p, bool small_reg_slab) : plan(p), elem(p.dty
     for (const Step& s : plan.steps) {
         if (s.kind == Step::PRODUCT_DENSE || s.kind == Step::FUSED) return;
         if (s.kind == Step::AXPY) in_axpy[size_t(s.a.idx)] = 1;
+        if (s.kind == Step::DUAL && s.a.kind == BufKind::INPUT) (s.canon_a ? in_direct : in_axpy)[size_t(s.a.idx)] = 1;
         if (s.kind == Step::PRODUCT_CSR) {
             if (s.a.kind == BufKind::INPUT) (s.canon_a ? in_direct : in_axpy)[size_t(s.a.idx)] = 1;
             if (s.b.kind == BufKind::INPUT) (s.canon_b ? in_direct : in_axpy)[size_t(s.b.idx)] = 1;
@@ -208,6 +209,13 @@ bool encode_uops(const SlabLayout& lay, Step::Fused& f, uint64_t& entries) {
         }
         case Step::EXPLOG: break;   // specialised kernel only (interp_ok is false)
         case Step::EXPLOG_ADJ: break;
+        case Step::DUAL: {
+            const uint32_t ab = uint32_t(lay.base_of(s.a, s.canon_a));
+            s.dual.for_each([&](uint32_t r, uint32_t a, bool neg) {
+                misc.push_back(mop(s.beta ? (neg ? uop::SUB : uop::ADD) : (neg ? uop::NCOPY : uop::COPY), rb + r, ab + a));
+            });
+            break;
+        }
         default: return false;
         }
         const size_t per = std::max<size_t>(1, std::min<size_t>(30, (misc.size() + G - 1) / G));
@@ -370,6 +378,12 @@ void step_statements(const SlabLayout& lay, const Step& s, const StmtStyle& st, 
         ew.push_back(s.sunary_op == 0 ? d + " = T(1) / " + d + ";" : d + (ct.f32 ? " = __builtin_sqrtf(" : " = __builtin_sqrt(") + d + ");");
         break;
     }
+    case Step::DUAL:   // the sign is folded into the operand: d = d + (-x)
+        s.dual.for_each([&](uint32_t r, uint32_t a, bool neg) {
+            const std::string d = st.el(rb + r), x = st.el(uint32_t(lay.base_of(s.a, s.canon_a)) + a);
+            ew.push_back(d + " = " + (s.beta ? d : std::string("T(0)")) + " + " + (neg ? "(-" + x + ")" : x) + ";");
+        });
+        break;
     case Step::EXPLOG: sink(0, explog_statements(lay, s, st, ct)); break;
     case Step::EXPLOG_ADJ: sink(0, explog_adj_statements(lay, s, st, ct)); break;
     case Step::PRODUCT_CSR: {

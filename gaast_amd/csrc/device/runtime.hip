@@ -206,6 +206,10 @@ struct Launch {
     Step s;
     int n = 0;                 // dimension of the algebra the kernel runs in (parity-pure dense products: n - 1)
     struct { DevTable axpy_map, flip_offsets; } trivial;   // AXPY, FLIP (SUNARY has no table)
+    struct {   // DUAL
+        DevTable segs, neg;
+        int col_shift = 8;              // log2 of the components a workgroup of k_dual covers
+    } dual;
     struct {   // PRODUCT_CSR: k_product_csr, k_product_ell, k_product_ell_chain or the specialised gaast_chain
         DevTable row_start, row_out, entries, coeff;
         struct { DevTable entries, row_map; } pre;        // k_product_ell_chain: the first list
@@ -542,6 +546,49 @@ int run_trivial(const Launch& L, const Operands& o, int64_t batch) {
         hipLaunchKernelGGL(k_scalar_unary<T>, dim3(grid_for(batch, 256)), dim3(256), 0, g_stream,
                            static_cast<T*>(o.res.ptr), o.res.stride, s.sunary_off, s.sunary_op, batch);
     }
+    return launch_status();
+}
+
+// ---- DUAL ----------------------------------------------------------------------------------------------------------------
+template <typename T>
+int prepare_dual(Launch& L, std::string& kernel) {
+    Step& s = L.s;
+    std::vector<uint32_t> segs;
+    uint32_t first = 0;
+    for (const Step::Dual::Seg& g : s.dual.segs) {
+        segs.insert(segs.end(), {first, g.a_off, g.res_last, 0u});
+        first += g.len;
+    }
+    L.dual.col_shift = 0;
+    while (L.dual.col_shift < 8 && (1 << L.dual.col_shift) < s.dual.total) ++L.dual.col_shift;
+    Upload<T> up;
+    up.idx(L.dual.segs, segs);
+    up.idx(L.dual.neg, s.dual.neg);
+    kernel = std::string("k_dual<") + type_name<T>() + ">";
+    return up.status;
+}
+
+template <typename T>
+int run_dual(const Launch& L, const Operands& o, int64_t batch) {
+    const Step& s = L.s;
+    if (batch <= 0 || s.dual.total <= 0) return GAAST_OK;
+    DualArgs<T> p;
+    p.res = static_cast<T*>(o.res.ptr);
+    p.in = static_cast<const T*>(o.a.ptr);
+    p.res_stride = o.res.stride;
+    p.in_stride = o.a.stride;
+    p.batch = batch;
+    p.segs = L.dual.segs.as<uint32_t>();
+    p.neg = L.dual.neg.as<uint32_t>();
+    p.n_segs = int(L.dual.segs.count / 4);
+    p.total = s.dual.total;
+    p.col_shift = L.dual.col_shift;
+    p.beta = s.beta;
+    p.canon = s.canon_a;
+    const int64_t per_block = 256 >> p.col_shift;
+    const unsigned gx = unsigned((s.dual.total + (1 << p.col_shift) - 1) >> p.col_shift);
+    const unsigned gy = unsigned(std::min<int64_t>((batch + per_block - 1) / per_block, 65535));
+    hipLaunchKernelGGL(k_dual<T>, dim3(gx, gy), dim3(256), 0, g_stream, p);
     return launch_status();
 }
 
@@ -1376,11 +1423,11 @@ int run_fused(const Launch& L, const Operands& o, int64_t batch, int* variant) {
 // Program creation (program_create_impl), phase by phase
 // ------------------------------------------------------------------------------------------
 // the plan of `desc` and one launch per step (plan.steps is left empty); a rebuild discards the launches made so far
-int make_launches(const gaast_program_desc& desc, bool small_reg_slab, gaast_hip_program_s& prog) {
+int make_launches(const gaast_program_desc& desc, bool small_reg_slab, bool mirrored, gaast_hip_program_s& prog) {
     prog.launches.clear();
     prog.plan = Plan();
     try {
-        build_plan(desc, prog.plan, small_reg_slab);
+        build_plan(desc, prog.plan, small_reg_slab, mirrored);
     } catch (const std::exception& ex) {
         return set_err(GAAST_ERR_INVALID_PROGRAM, ex.what());
     }
@@ -1490,6 +1537,7 @@ int prepare_launch(Launch& L, const gaast_hip_program_s& prog) {
     case Step::ELEMENTWISE: st = prepare_elementwise<T>(L, kernel); break;
     case Step::LINMAP: kernel = linmap_kernel_name(L.linmap->n, plan.dtype); break;
     case Step::EXPLOG_ADJ: st = prepare_explog_adj<T>(L, la, lb, kernel); break;
+    case Step::DUAL: st = prepare_dual<T>(L, kernel); break;
     }
     if (st) return st;
     L.label = kernel.empty() ? s.name : s.name + " :: " + kernel;
@@ -1518,16 +1566,17 @@ int upload_const_rows(gaast_hip_program_s& prog) {
     return GAAST_OK;
 }
 
-int program_create_impl(const gaast_program_desc* desc, gaast_hip_program_t* out) {
+// mirrored: the program runs in the orthogonal basis of a Gram metric whose Q has determinant -1 (Plan::mirrored)
+int program_create_impl(const gaast_program_desc* desc, gaast_hip_program_t* out, bool mirrored) {
     auto prog = std::make_unique<gaast_hip_program_s>();  // its destructor releases whatever a failure leaves behind
-    if (int st = make_launches(*desc, false, *prog)) return st;
+    if (int st = make_launches(*desc, false, mirrored, *prog)) return st;
     // a plan that can only run as the specialised kernel is rebuilt without run-time compilation if the compiler is not available
     uint32_t rebuild_flags = 0;
     bool small_reg_slab = false;
     for (int attempt = 0; attempt < 3 && compile_fused(*prog, desc->flags, &rebuild_flags, &small_reg_slab); ++attempt) {
         gaast_program_desc d2 = *desc;
         d2.flags |= rebuild_flags;
-        if (int st = make_launches(d2, small_reg_slab, *prog)) return st;
+        if (int st = make_launches(d2, small_reg_slab, mirrored, *prog)) return st;
     }
     compile_chains(*prog, desc->flags);
     if (prog->plan.has_explog)
@@ -1613,19 +1662,20 @@ int gaast_hip_synchronize(void) {
     return GAAST_OK;
 }
 
-int gaast_hip_program_create(const gaast_program_desc* desc, gaast_hip_program_t* out) {
+static int program_create_oriented(const gaast_program_desc* desc, gaast_hip_program_t* out, bool mirrored) {
     if (!desc || !out) return set_err(GAAST_ERR_INVALID_ARGUMENT, "null argument");
     if (int st = ensure_init()) return st;
-    int st = program_create_impl(desc, out);
+    int st = program_create_impl(desc, out, mirrored);
     // a chain beyond the device's LDS: the unchained plan of the same program still runs -- rebuild without chains (as the
     // hiprtc-failure fallback does) instead of refusing the program
     if (st == kChainTooBig && !(desc->flags & GAAST_FLAG_DEBUG_NO_CHAIN)) {
         gaast_program_desc d2 = *desc;
         d2.flags |= GAAST_FLAG_DEBUG_NO_CHAIN;
-        st = program_create_impl(&d2, out);
+        st = program_create_impl(&d2, out, mirrored);
     }
     return st == kChainTooBig ? GAAST_ERR_UNIMPLEMENTED : st;
 }
+int gaast_hip_program_create(const gaast_program_desc* desc, gaast_hip_program_t* out) { return program_create_oriented(desc, out, false); }
 
 // ---- reverse mode -------------------------------------------------------------------------------------------------------
 int gaast_hip_program_create_vjp(const gaast_program_desc* desc, int32_t wrt_slot, gaast_hip_program_t* out) {
@@ -1935,8 +1985,9 @@ int gaast_hip_program_create_in_basis(const gaast_program_desc* desc, const doub
         ins[i].const_row = rows[i].data();
     }
     d2.inputs = ins.empty() ? nullptr : ins.data();
+    // the complement of the caller's basis is det(Q) = +-1 times the one of the orthogonal basis (gaast_hip.h: GAAST_OP_DUAL)
     gaast_hip_program_t prog = nullptr;
-    if (int st = gaast_hip_program_create(&d2, &prog)) return st;
+    if (int st = program_create_oriented(&d2, &prog, basis_is_mirrored(n, basis))) return st;
     std::unique_ptr<gaast_hip_program_s> owner(prog);
     Plan& plan = prog->plan;
     if (plan.out_layout.dim != n && (plan.out_layout.mask & ~1ULL))
@@ -2222,6 +2273,7 @@ int run_launch(const Launch& L, const Operands& o, int64_t batch) {
     case Step::ELEMENTWISE: st = run_elementwise<T>(L, o, batch); break;
     case Step::LINMAP: st = run_linmap<T>(L, o, batch); break;
     case Step::EXPLOG_ADJ: st = run_explog_adj<T>(L, o, batch); break;
+    case Step::DUAL: st = run_dual<T>(L, o, batch); break;
     }
     L.variant = variant;
     return st;

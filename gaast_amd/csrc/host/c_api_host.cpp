@@ -36,9 +36,14 @@ const char* gaast_expr_last_error(void) { return g_err.c_str(); }
 uint64_t gaast_gs_single(int64_t k) { return gs_single(k); }
 uint64_t gaast_gs_range(int x, int y) { return gs_range(x, y); }
 uint64_t gaast_gs_mul(uint64_t a, uint64_t b) { return gs_mul(a, b); }
-uint64_t gaast_gs_select(int kind, int64_t k1, int64_t k2) { return gs_select(kind, k1, k2); }
+// (GAAST_PROD_REGRESSIVE needs the dimension, which these two do not take: it selects nothing here)
+uint64_t gaast_gs_select(int kind, int64_t k1, int64_t k2) { return kind == GAAST_PROD_REGRESSIVE ? 0 : gs_select(kind, k1, k2); }
 void gaast_gs_parts_contributing_to_product(uint64_t self, int kind, uint64_t left, uint64_t right,
                                             uint64_t* out_left, uint64_t* out_right) {
+    if (kind == GAAST_PROD_REGRESSIVE) {
+        *out_left = *out_right = 0;
+        return;
+    }
     parts_contributing(self, builtin(kind), left, right, out_left, out_right);
 }
 
@@ -133,7 +138,7 @@ gaast_expr_t gaast_expr_basis_vector(int dim, int i) {
     return wrap(make_basis_vector(dim, i));
 }
 gaast_expr_t gaast_expr_product(gaast_expr_t l, gaast_expr_t r, int kind) {
-    if (kind < 0 || kind > GAAST_PROD_RCONTRACT) {
+    if (kind < 0 || kind > GAAST_PROD_REGRESSIVE) {
         g_err = "unknown product kind";
         return nullptr;
     }
@@ -159,6 +164,8 @@ gaast_expr_t gaast_expr_scal(gaast_expr_t e, gaast_expr_t rhs) { return wrap(mak
 gaast_expr_t gaast_expr_norm_sq(gaast_expr_t e) { return wrap(make_norm_sq(e->node)); }
 gaast_expr_t gaast_expr_sinv(gaast_expr_t e) { return wrap(make_unary(ExprNode::SINV, e->node)); }
 gaast_expr_t gaast_expr_vinv(gaast_expr_t e) { return wrap(make_unary(ExprNode::WRAP_VINV, e->node)); }
+gaast_expr_t gaast_expr_dual(gaast_expr_t e) { return wrap(make_unary(ExprNode::DUAL, e->node)); }
+gaast_expr_t gaast_expr_undual(gaast_expr_t e) { return wrap(make_unary(ExprNode::UNDUAL, e->node)); }
 
 gaast_spec_t gaast_expr_specialize(gaast_expr_t e, int n, const double* metric_diag,
                                    uint64_t materialize_limit) {

@@ -121,6 +121,7 @@ inline GS sel_gs(const Selection& sel, int64_t k1, int64_t k2) {
     case GAAST_PROD_INNER: g.len = (k1 == 0 || k2 == 0) ? 0 : int((k1 > k2 ? k1 - k2 : k2 - k1) + 1); break;
     case GAAST_PROD_LCONTRACT: g.len = k2 - k1 < 0 ? 0 : int(k2 - k1 + 1); break;
     case GAAST_PROD_RCONTRACT: g.len = k1 - k2 < 0 ? 0 : int(k1 - k2 + 1); break;
+    case GAAST_PROD_REGRESSIVE: g.len = k1 + k2 - sel.n < 0 ? 0 : int(k1 + k2 - sel.n + 1); break;
     default: g.len = top_len(g.mask); break;  // user closure: as built by add_grade
     }
     return g;
@@ -186,10 +187,11 @@ struct Builder {
             p.child1 = reify_or_reuse(e->b, &rgs);
             p.opcode = GAAST_OP_PRODUCT;
             p.sel = e->sel;
+            p.sel.n = ast.n;  // (the regressive product's grade depends on the dimension)
             for (int kl = 0; kl < 64; ++kl)
                 if ((lgs.mask >> kl) & 1ULL)
                     for (int kr = 0; kr < 64; ++kr)
-                        if ((rgs.mask >> kr) & 1ULL) gs = gs_union(gs, sel_gs(e->sel, kl, kr));
+                        if ((rgs.mask >> kr) & 1ULL) gs = gs_union(gs, sel_gs(p.sel, kl, kr));
             add_node(this_id, p, gs);
             return;
         }
@@ -203,6 +205,14 @@ struct Builder {
                        : e->kind == ExprNode::GINVOL ? GAAST_OP_GINVOL
                                                      : GAAST_OP_SINV;
             add_node(this_id, p, gs);
+            return;
+        }
+        case ExprNode::DUAL:
+        case ExprNode::UNDUAL: {  // complements: every grade k of the operand goes to n - k (gaast_hip.h)
+            p.child0 = reify_or_reuse(e->a, &gs);
+            p.opcode = e->kind == ExprNode::DUAL ? GAAST_OP_DUAL : GAAST_OP_UNDUAL;
+            const uint64_t m = gs_mirror(gs.mask, ast.n);
+            add_node(this_id, p, GS{m, top_len(m)});
             return;
         }
         case ExprNode::EXP: {  // GradeSet::exp, grade_set.rs:181-187
@@ -274,6 +284,8 @@ void rec_update_minimal(SpecializedAst& s, int idx, uint64_t wanted) {  // speci
     case GAAST_OP_GINVOL:
     case GAAST_OP_SINV:
     case GAAST_OP_SSQRT: rec_update_minimal(s, n.child0, wanted); return;
+    case GAAST_OP_DUAL:
+    case GAAST_OP_UNDUAL: rec_update_minimal(s, n.child0, gs_mirror(wanted, s.n)); return;
     case GAAST_OP_ADD: {
         int l = n.child0, r = n.child1;
         rec_update_minimal(s, l, wanted);
@@ -336,14 +348,15 @@ void rec_apply_algebra(SpecializedAst& s, int idx, const BladeTable& bt, uint64_
         GradedNode& p = s.nodes[size_t(idx)];
         auto contribs = iter_contribs(p.minimal, p.sel, s.nodes[size_t(l)].minimal,
                                       s.nodes[size_t(r)].minimal);
-        p.n_comp_muls = comp_mul_count(s.n, contribs);
+        const bool regressive = p.sel.kind == GAAST_PROD_REGRESSIVE;
+        p.n_comp_muls = comp_mul_count(s.n, contribs, regressive);
         if (limit != 0 && p.n_comp_muls > limit && p.sel.kind >= 0) {
             p.compact = true;  // the device regenerates (or never needs) the list
             return;
         }
         p.comp_muls.reserve(size_t(p.n_comp_muls));
         for_each_comp_mul(bt, s.metric.data(), contribs,
-                          [&](const gaast_comp_mul& m) { p.comp_muls.push_back(m); });
+                          [&](const gaast_comp_mul& m) { p.comp_muls.push_back(m); }, regressive);
         return;
     }
     default: rec_apply_algebra(s, n.child0, bt, limit); return;

@@ -10,6 +10,9 @@
 //   flip        the same flip of the cotangent (kept as a per-grade sign and folded into the next list's coefficients);
 //   SINV        t = 1/s: ds = -g t t;  SSQRT r = sqrt(s): ds = 0.5 g sinv(r) -- t and r are the buffer's grade 0 right after
 //               the op, recomputed by a node that replays the buffer's events up to it;
+//   dual/undual the operand has a buffer of its own or is read from a bound input (plan.cpp: lower_dual), so the node is a one-operand
+//               product event: the operand's cotangent is the OTHER complement (the transpose of a signed permutation is its
+//               inverse) of the buffer's cotangent restricted to the node's grades;
 //   exp / log   (GAAST_FLAG_EXP_LOG | GAAST_FLAG_EXP_LOG_GRAD) the operand has a buffer of its own, like a product operand
 //               (plan.cpp: lower_exp_log -> store_in_cache): a one-operand product event -- GAAST_OP_EXP_ADJ / GAAST_OP_LOG_ADJ over
 //               the buffer's cotangent restricted to the node's grades and the forward operand -> cotangent of the operand buffer.
@@ -166,8 +169,20 @@ struct Builder {
             if (nd.opcode == GAAST_OP_SINV || nd.opcode == GAAST_OP_SSQRT) ev.push_back({EV_SCALAR, x, path});
             else if (nd.opcode != GAAST_OP_PROJ) ev.push_back({EV_FLIP, x, path});
             return;
-        default: ev.push_back({EV_OPAQUE, x, path}); return;  // exp / log
+        default: ev.push_back({EV_OPAQUE, x, path}); return;  // exp / log, dual / undual
         }
+    }
+    // dual / undual: cotangent of the operand's buffer
+    void dual_adjoint(int x, const std::vector<Term>& terms, std::vector<std::vector<Term>>& cot) {
+        const gaast_node_desc& xd = d.nodes[x];
+        const int c = xd.child0;
+        if (!dep[size_t(c)]) return;
+        const uint64_t cmask = d.nodes[c].minimal_grade_mask & gs_mirror(xd.minimal_grade_mask, n);
+        const int g = materialize(terms, xd.minimal_grade_mask);
+        if (g < 0 || !cmask) return;
+        gaast_node_desc nd = blank(xd.opcode == GAAST_OP_DUAL ? GAAST_OP_UNDUAL : GAAST_OP_DUAL, cmask, n);
+        nd.child0 = g;
+        cot[size_t(c)].push_back(Term{add(nd), 0, ~0ULL});
     }
     // exp / log: cotangent of the operand's buffer (gaast_hip.h: GAAST_OP_EXP_ADJ / GAAST_OP_LOG_ADJ)
     void explog_adjoint(int x, const std::vector<Term>& terms, std::vector<std::vector<Term>>& cot) {
@@ -238,10 +253,13 @@ struct Builder {
                     auto adj = transpose_comp_muls(fwd.data(), fwd.size(), side == 1, false);
                     const int node = side ? explicit_product(other, t.node, std::move(adj), cmask, n)
                                           : explicit_product(t.node, other, std::move(adj), cmask, n);
+                    // the entries of a regressive list are pseudoscalar-valued: an explicit list that names the kind gets the
+                    // orientation sign of a Gram basis at lowering (gaast_hip.h: GAAST_PROD_REGRESSIVE), and so must its transpose
+                    if (pd.product_kind == GAAST_PROD_REGRESSIVE) nodes[size_t(node)].product_kind = GAAST_PROD_REGRESSIVE;
                     cot[size_t(c)].push_back(Term{node, 0, ~0ULL});
                 }
             } else {
-                if (pd.product_kind < 0 || pd.product_kind > GAAST_PROD_RCONTRACT)
+                if (pd.product_kind < 0 || pd.product_kind > GAAST_PROD_REGRESSIVE)
                     throw VjpError{GAAST_ERR_INVALID_PROGRAM, "PRODUCT node has neither a comp-mul list nor a product kind"};
                 const int g = materialize(terms, pd.minimal_grade_mask);
                 if (g < 0) continue;
@@ -249,9 +267,9 @@ struct Builder {
                 nd.child0 = g;
                 nd.child1 = other;
                 nd.product_kind = pd.product_kind + (side ? GAAST_PROD_ADJ_RIGHT : GAAST_PROD_ADJ_LEFT);
-                const Selection sel{pd.product_kind, nullptr, nullptr};
+                const Selection sel{pd.product_kind, nullptr, nullptr, n};
                 const uint64_t lmask = side ? mask_of(other) : cmask, rmask = side ? cmask : mask_of(other);
-                nd.n_comp_muls = comp_mul_count(n, iter_contribs(mask_of(g), sel, lmask, rmask));
+                nd.n_comp_muls = comp_mul_count(n, iter_contribs(mask_of(g), sel, lmask, rmask), pd.product_kind == GAAST_PROD_REGRESSIVE);
                 cot[size_t(c)].push_back(Term{add(nd), 0, ~0ULL});
             }
         }
@@ -337,7 +355,10 @@ struct Builder {
                     break;
                 }
                 case EV_SCALAR: scalar_adjoint(s, e, terms); break;
-                case EV_OPAQUE: explog_adjoint(e.node, terms, cot); break;
+                case EV_OPAQUE:   // a node whose operand has a buffer of its own
+                    if (x.opcode == GAAST_OP_DUAL || x.opcode == GAAST_OP_UNDUAL) dual_adjoint(e.node, terms, cot);
+                    else explog_adjoint(e.node, terms, cot);
+                    break;
                 }
             }
         }
@@ -390,7 +411,8 @@ extern "C" int gaast_program_vjp(const gaast_program_desc* desc, int32_t wrt_slo
         const gaast_node_desc& nd = d.nodes[i];
         const bool two = nd.opcode == GAAST_OP_ADD || nd.opcode == GAAST_OP_PRODUCT;
         const bool ok = nd.opcode == GAAST_OP_INPUT ? (nd.input_slot >= 0 && nd.input_slot < d.n_inputs)
-                        : (nd.opcode > GAAST_OP_INPUT && nd.opcode <= GAAST_OP_SSQRT && nd.child0 >= 0 && nd.child0 < i &&
+                        : (nd.opcode > GAAST_OP_INPUT && (nd.opcode <= GAAST_OP_SSQRT || nd.opcode == GAAST_OP_DUAL || nd.opcode == GAAST_OP_UNDUAL) &&
+                           nd.child0 >= 0 && nd.child0 < i &&
                            (!two || (nd.child1 >= 0 && nd.child1 < i)));
         if (!ok || (nd.opcode == GAAST_OP_PRODUCT && nd.product_kind >= GAAST_PROD_ADJ_LEFT)) {
             gaast_set_expr_error("malformed program description (node " + std::to_string(i) + ")");
@@ -419,7 +441,7 @@ extern "C" int gaast_program_vjp(const gaast_program_desc* desc, int32_t wrt_slo
             gaast_node_desc nd = b.nodes[i];
             if (nd.child0 >= 0) nd.child0 = remap[size_t(nd.child0)];
             if (nd.child1 >= 0) nd.child1 = has_two_children(nd.opcode) ? remap[size_t(nd.child1)] : -1;
-            if (nd.opcode == GAAST_OP_PRODUCT && i >= size_t(d.n_nodes) && nd.product_kind == GAAST_PROD_EXPLICIT)
+            if (nd.opcode == GAAST_OP_PRODUCT && i >= size_t(d.n_nodes) && !b.lists[i].empty())   // (explicit; a regressive one names its kind)
                 nd.comp_muls = b.lists[i].data();
             remap[i] = int(nodes.size());
             nodes.push_back(nd);

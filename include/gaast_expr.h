@@ -36,7 +36,10 @@ const char *gaast_expr_last_error(void);
 uint64_t gaast_gs_single(int64_t k);                      /* grade_set.rs:65-71 (negative -> empty) */
 uint64_t gaast_gs_range(int x, int y);                    /* grade_set.rs:74-80 */
 uint64_t gaast_gs_mul(uint64_t a, uint64_t b);            /* grade_set.rs:305-327 (no dimension cap) */
-uint64_t gaast_gs_select(int kind, int64_t k1, int64_t k2); /* the five closures of expr.rs:180-197 */
+/* the five closures of expr.rs:180-197.  GAAST_PROD_REGRESSIVE produces grade k1 + k2 - n, which depends on the dimension that
+ * neither this function nor gaast_gs_parts_contributing_to_product takes: both answer "nothing" (0) for that kind; specialise an
+ * expression to see its grades. */
+uint64_t gaast_gs_select(int kind, int64_t k1, int64_t k2);
 /* grade_set.rs:239-252 */
 void gaast_gs_parts_contributing_to_product(uint64_t self, int kind, uint64_t left, uint64_t right,
                                             uint64_t *out_left, uint64_t *out_right);
@@ -96,6 +99,10 @@ gaast_expr_t gaast_expr_scal(gaast_expr_t e, gaast_expr_t rhs);   /* expr.rs:343
 gaast_expr_t gaast_expr_norm_sq(gaast_expr_t e);                  /* expr.rs:348-350 */
 gaast_expr_t gaast_expr_sinv(gaast_expr_t e);                     /* expr.rs:353-358 */
 gaast_expr_t gaast_expr_vinv(gaast_expr_t e);                     /* expr.rs:363-371 */
+/* no reference counterpart: the right / left complement (GAAST_OP_DUAL / GAAST_OP_UNDUAL, gaast_hip.h); a v b is
+ * gaast_expr_product with GAAST_PROD_REGRESSIVE */
+gaast_expr_t gaast_expr_dual(gaast_expr_t e);
+gaast_expr_t gaast_expr_undual(gaast_expr_t e);
 
 /* ---- reify + specialize (phases 2-3) ---------------------------------------------------------- */
 /* Expr::specialize(&alg), specialize.rs:36-50, with alg = the diagonal metric `metric_diag[n]`
@@ -152,6 +159,9 @@ void gaast_program_image_free(gaast_program_image_t img);
  * when the input does not reach the root.  An explicit list gets its explicit transposed list; a compact product, and a geometric
  * product (product_kind GAAST_PROD_GEOMETRIC) at n >= 6 whatever its form, a compact GAAST_PROD_ADJ_LEFT / GAAST_PROD_ADJ_RIGHT node,
  * which the dense kernels evaluate where they take the forward product.  The adjoint program inherits desc->flags.
+ * A GAAST_OP_DUAL / GAAST_OP_UNDUAL node gives its operand the OTHER complement of its buffer's cotangent restricted to the node's
+ * grades (the transpose of a signed permutation is its inverse); GAAST_PROD_REGRESSIVE differentiates like kinds 1-4, and an explicit
+ * transposed list of it keeps product_kind = GAAST_PROD_REGRESSIVE (the orientation sign of a Gram basis applies to it too).
  * A program specialised for the orthogonal basis of a Gram metric differentiates like any other: its VJP program is created with the
  * same basis (gaast_hip_program_create_vjp_in_basis, gaast_hip.h), the cotangent being one more batched input.
  * Errors: GAAST_ERR_INVALID_ARGUMENT for a wrt_slot out of range or const, or n_inputs + 1 > GAAST_MAX_INPUTS;

@@ -93,10 +93,22 @@ typedef enum gaast_opcode {
      * forward exp / log (because it needs its value, e.g. R in the sandwich R X ~R) counts there like any forward program.
      * Exp of a bare scalar (k = 0, raw ABI only) has no adjoint node: GAAST_ERR_UNIMPLEMENTED. */
     GAAST_OP_EXP_ADJ = 11,
-    GAAST_OP_LOG_ADJ = 12
+    GAAST_OP_LOG_ADJ = 12,
+    /* Complements (no reference counterpart; metric-free, so they work in a degenerate metric such as PGA's where a * I.rev() is
+     * identically zero).  Blades are bitmasks S over n bits, ~S the complement of S, par(A,B) the parity of #{(i in A, j in B): i > j}:
+     *   DUAL    right complement  dual(e_S)   = (-1)^par(S,~S) e_~S, so that e_S ^ dual(e_S) = I = e_{1..n};
+     *   UNDUAL  left complement   undual(e_S) = (-1)^par(~S,S) e_~S, the exact inverse (and the transpose) of DUAL.
+     * One child.  Component i of grade k goes to component C(n,k) - 1 - i of grade n - k (ascending bitmask within a grade), so the
+     * node's minimal grade mask is the child's mirrored, k -> n - k.  Signed permutations: bit-exact in every mode and both dtypes;
+     * like every arm of eval.rs the node ADDS +-x into the buffer that contains it, with one rounding.  An operand stored in another
+     * dimension (a scalar literal: storage dimension 0) is taken as the leading components of the algebra's grades: a scalar
+     * dualises to grade n of the algebra.  In a program of gaast_hip_program_create_in_basis the complement of the caller's basis is
+     * det(Q) = +-1 times the one of the orthogonal basis: the library multiplies every sign by sign(det Q). */
+    GAAST_OP_DUAL = 13,
+    GAAST_OP_UNDUAL = 14
 } gaast_opcode;
 
-/* the five products of src/ast/expr.rs:180-197, for compact PRODUCT descriptors */
+/* the five products of src/ast/expr.rs:180-197 (and the regressive product), for compact PRODUCT descriptors */
 typedef enum gaast_product_kind {
     GAAST_PROD_EXPLICIT = -1, /* use the comp_muls list */
     GAAST_PROD_GEOMETRIC = 0,
@@ -104,7 +116,13 @@ typedef enum gaast_product_kind {
     GAAST_PROD_INNER = 2,
     GAAST_PROD_LCONTRACT = 3,
     GAAST_PROD_RCONTRACT = 4,
-    /* Compact ADJOINT products (reverse mode, gaast_program_vjp in gaast_expr.h): added to a forward kind 0..4, e.g.
+    /* the regressive product a v b = undual(dual(a) ^ dual(b)) (join of points / meet of planes; complements as GAAST_OP_DUAL).
+     * On blades it is non-zero only when A | B is full; the result blade is A & B, of grade k_a + k_b - n, and the coefficient is
+     * +-1 whatever the metric.  Its list (order T4, only the pairs with A | B full: 3^n entries for full multivectors) always runs on
+     * the list kernels, never on a dense kernel.  With a Gram basis every coefficient is multiplied by sign(det Q), like the
+     * complements. */
+    GAAST_PROD_REGRESSIVE = 5,
+    /* Compact ADJOINT products (reverse mode, gaast_program_vjp in gaast_expr.h): added to a forward kind 0..5, e.g.
      * GAAST_PROD_ADJ_LEFT + GAAST_PROD_GEOMETRIC.  child0 is the cotangent of the forward product's result, child1 the
      * other forward operand, and the node's own minimal grade mask that of the differentiated operand.  These three grade
      * sets regenerate the forward list (specialize.rs:132-183); the library evaluates its transpose: (l, r -> o, c) becomes

@@ -198,6 +198,13 @@ impl<T: GradedData + std::fmt::Debug> SpecializedAst<T> {
                 N::GradeInvolution(e) => { d.opcode = OP_GINVOL; d.child0 = index[e]; }
                 N::ScalarUnaryOp(ScalarUnaryOp::Inversion, e) => { d.opcode = OP_SINV; d.child0 = index[e]; }
                 N::ScalarUnaryOp(ScalarUnaryOp::SquareRoot, e) => { d.opcode = OP_SSQRT; d.child0 = index[e]; }
+                // The complements and the regressive product are extensions of the back end: AstNode has no variant for them
+                // (base_types.rs:8-30).  A fork that adds `Dual(e)` / `Undual(e)` flattens them like the other one-child arms,
+                //     N::Dual(e) => { d.opcode = OP_DUAL; d.child0 = index[e]; }
+                //     N::Undual(e) => { d.opcode = OP_UNDUAL; d.child0 = index[e]; }
+                // with the node's grade set the child's mirrored (k -> dim - k); a v b needs no new arm here: it is a Product
+                // whose grades_to_produce closure returns single(k1 + k2 - dim), sent as an explicit list like any other
+                // (product_kind PROD_REGRESSIVE instead of -1 lets the library apply the orientation sign of a Gram basis).
             }
             nodes.push(d);
         }

@@ -24,6 +24,11 @@ pub const OP_SSQRT: i32 = 10;
 // reverse mode of exp / log (no AstNode counterpart): child0 = cotangent of the forward result, child1 = the forward operand
 pub const OP_EXP_ADJ: i32 = 11;
 pub const OP_LOG_ADJ: i32 = 12;
+// complements (no AstNode counterpart; metric-free): one child, grade k -> n - k
+pub const OP_DUAL: i32 = 13;
+pub const OP_UNDUAL: i32 = 14;
+// compact product kinds (gaast_product_kind); 5 = the regressive product a v b = undual(dual(a) ^ dual(b))
+pub const PROD_REGRESSIVE: i32 = 5;
 
 pub const FLAG_EXACT_ORDER: u32 = 0x4; // bit-exact f64 sums even for dense products
 pub const FLAG_SPINOR_GEMM: u32 = 0x20; // opt-in matrix-representation products (norm-wise error bound)
