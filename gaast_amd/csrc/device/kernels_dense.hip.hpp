@@ -2,7 +2,7 @@
 // Included through kernels.hip.hpp.
 #pragma once
 #include "kernels_common.hip.hpp"
-#include "mfma32p_b_planes.hip.hpp"
+#include "dense_images.hip.hpp"
 
 
 namespace gaast {
@@ -21,7 +21,7 @@ namespace gaast {
 // The lo basis vectors must square to +-1 (never 0): their factor (-1)^|a_lo & b_lo & NEG_lo| is a lane
 // constant in the matrix-core kernels (any NEG_lo) and a compile-time pattern in the vector-FMA kernel
 // (NEG_lo = none or all four).  The host gets any diagonal metric into that shape by PERMUTING the basis
-// vectors (plan.cpp: dense_basis_permutation): the kernels work on blades of the permuted basis, the index maps
+// vectors (plan_dense.cpp: dense_basis_permutation): the kernels work on blades of the permuted basis, the index maps
 // carry the blade bijection and the reordering sign of every blade in their negate bits.
 //
 // Mapping: lane <-> c_hi (one 16-component block of the result in 16 accumulators),
@@ -76,14 +76,9 @@ struct DenseArgs {
     int64_t batch;
 };
 
-// physical position of blade bitmask m inside an operand's LDS image: blocks of 16, the four
+// (physical position of blade bitmask m inside an operand's LDS image: dense_images::vec_pos -- blocks of 16, the four
 // 16-byte quads of block x rotated by (x >> 2) & 3 so that 16 lanes reading the same logical
-// quad of 16 different blocks touch 16 different bank quads.
-__device__ __forceinline__ int dense_lds_pos(int m) {
-    const int x = m >> 4, lo = m & 15;
-    return (x << 4) | ((((lo >> 2) ^ (x >> 2)) & 3) << 2) | (lo & 3);
-}
-
+// quad of 16 different blocks touch 16 different bank quads.)
 
 // e = it * cnt + j with 0 <= j < cnt, for e < 2^24: a float reciprocal and one correction step instead of the ~30
 // instructions of an integer division by a run-time value (every vector instruction of a resident wave costs its SIMD ~4.8
@@ -568,13 +563,7 @@ __device__ __forceinline__ constexpr int lo5_reorder_parity(int a, int b) {
     return par;
 }
 
-// LDS position of blade m inside the B image: block x = m >> 5; inside it the components are
-// de-interleaved by the parity of k = m & 31 (even k first), 8 quads rotated by (x >> 1) & 7.
-__device__ __forceinline__ int mfma_b_pos(int m) {
-    const int x = m >> 5, k = m & 31;
-    const int lq = ((k & 1) << 2) | (k >> 3);   // logical quad: parity * 4 + (k/2)/4
-    return (x << 5) | (((lq ^ (x >> 1)) & 7) << 2) | ((k >> 1) & 3);
-}
+// (LDS position of blade m inside the B image: dense_images::mfma32_b_pos)
 
 template <bool DEGENERATE, int THREADS, bool SCALED = false, bool CHAINED = false>
 __global__ __launch_bounds__(THREADS) void k_gp_mfma32(DenseArgs<float> p) {
@@ -724,13 +713,8 @@ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
 #endif
 }
 
-// term t of a step multiplies the words k = mfma16_k(t): even |k| first
-__device__ __forceinline__ constexpr int mfma16_k(int t) {
-    constexpr int order[16] = {0, 3, 5, 6, 9, 10, 12, 15, 1, 2, 4, 7, 8, 11, 13, 14};
-    return order[t];
-}
-static_assert(mfma16_k(1) == int(b_planes::s2_of_word(1)) && mfma16_k(7) == int(b_planes::s2_of_word(7)) && mfma16_k(8) == int(b_planes::s2_of_word(8)) &&
-              mfma16_k(14) == int(b_planes::s2_of_word(14)), "the quad-plane B image stores the words in mfma16_k order");
+// term t of a step multiplies the words k = mfma16_k(t): even |k| first (the one table the block image and the quad-plane image store by)
+using dense_images::mfma16_k;
 
 // ------------------------------------------------------------------------------------------
 // k_gp_mfma32 in image-pair form (n = 10 ... 13): as k_gp_mfma16 below, NO sign is applied with vector instructions
@@ -1176,7 +1160,7 @@ struct Mfma16x4<double> {
     static __device__ __forceinline__ acc_t mma(double a, double b, acc_t c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ int row(int kq, int r) { return 4 * r + kq; }
     static constexpr bool QUAD = false;           // B operands: one ds_read_b64 per instruction
-    static __device__ __forceinline__ constexpr int k_of(int kq, int s) { return 4 * s + kq; }
+    static __device__ __forceinline__ constexpr int k_of(int kq, int s) { return dense_images::mfma16d_k(kq, s); }
     static __device__ __forceinline__ double flip(double v, uint32_t bit31) { return __hiloint2double(__double2hiint(v) ^ int(bit31), __double2loint(v)); }
 };
 template <>
@@ -1189,10 +1173,7 @@ struct Mfma16x4<float> {
     // side).  Lane group kq then multiplies the k values k_of(kq, 0..3); each group's four have one |k| parity -- groups
     // 0, 1 even, 2, 3 odd -- because a quad comes from one image and the factor (-1)^(|c_hi| |k|) picks the image.
     static constexpr bool QUAD = true;
-    static __device__ __forceinline__ constexpr int k_of(int kq, int s) {
-        constexpr int tab[4][4] = {{0, 3, 5, 6}, {9, 10, 12, 15}, {1, 2, 4, 7}, {8, 11, 13, 14}};
-        return tab[kq][s];
-    }
+    static __device__ __forceinline__ constexpr int k_of(int kq, int s) { return dense_images::mfma16q_k(kq, s); }
     static __device__ __forceinline__ float flip(float v, uint32_t bit31) { return __uint_as_float(__float_as_uint(v) ^ bit31); }
 };
 
@@ -1639,10 +1620,7 @@ __global__ __launch_bounds__(64 << (NDIM - 8)) __attribute__((amdgpu_waves_per_e
 // MODE as in k_gp_mfma16x4: 0 general staging, 1 register prefetch of full rows (a lane moves two components of each row,
 // one per load, dealt by LDS bank on the host), 2 ... and straight-line result stores.
 // ------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ constexpr int mfma7_k(int kq, int s) {
-    constexpr int tab[4][2] = {{0, 3}, {5, 6}, {1, 2}, {4, 7}};
-    return tab[kq][s];
-}
+using dense_images::mfma7_k;
 
 #ifndef GAAST_MFMA7_CHAIN_WAVES
 #define GAAST_MFMA7_CHAIN_WAVES 4   /* the chained kernels: at most 128 registers, four waves per SIMD (A/B switch; 3: the same time) */
@@ -1719,7 +1697,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CHAINED ? GA
 
     // FAST: every blade of both operands is loaded (the host checks): entry q = load * 64 + lane of a map is this lane's
     // component of load `load` -- row offset, image address, negate bit -- dealt by the host so that the lanes sharing an
-    // LDS cycle store to different banks (plan.cpp: build_map); the rows need no alignment
+    // LDS cycle store to different banks (plan_dense.cpp: deal_mfma7_by_bank); the rows need no alignment
     uint32_t wa[2] = {0, 0}, wb[2] = {0, 0}, sa[2] = {0, 0}, sb[2] = {0, 0}, oa[2] = {0, 0}, ob[2] = {0, 0};
     // TWO items are in flight per wave (register sets 0 / 1, the item loop is unrolled by two): with one, the 32 waves of a CU
     // keep 32 KiB of loads in flight (f32) -- measured 3.6 TB/s; an HBM access under load takes the time of ~2 items

@@ -29,7 +29,7 @@ namespace gaast {
 // lane and item -- so that a lane's operands of all four instructions are ONE 16-byte read per operand (f64: two).
 // Missing components (operands that hold only some grades) and vanishing slots (null vectors) are slots nobody writes: they stay
 // zero from the initial clear.
-// Which lane moves which component is the host's choice (plan.cpp: build_map deals full operands by LDS bank; the B stores go
+// Which lane moves which component is the host's choice (dense_images::mfma6_lane_of deals full operands by LDS bank; the B stores go
 // out in the slot order i ^ b_lo): no bank conflict on the eight stores.
 // DEPTH items are in flight per wave (two loads each): 32 waves x DEPTH x 512 B per CU hide the HBM latency.
 // ------------------------------------------------------------------------------------------
@@ -47,9 +47,7 @@ __device__ __forceinline__ uint32_t group_reorder_parity(uint32_t a, uint32_t b)
 #ifndef GAAST_MFMA6_SPLIT
 #define GAAST_MFMA6_SPLIT 0   /* (build switch for A/B runs) two accumulator chains of two instructions instead of one of four: measured -4 % */
 #endif
-#ifndef GAAST_MFMA6_WAVES
-#define GAAST_MFMA6_WAVES 1   /* (build switch for A/B runs) independent waves per workgroup */
-#endif
+// (GAAST_MFMA6_WAVES, independent waves per workgroup: dense_images.hip.hpp, with the workgroup's geometry)
 template <typename T, bool SCALED, bool FAST>
 __global__ __launch_bounds__(64 * GAAST_MFMA6_WAVES) void k_gp_mfma6(DenseArgs<T> p) {
     typedef Mfma16x4<T> MM;

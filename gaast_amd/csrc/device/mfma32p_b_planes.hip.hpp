@@ -1,5 +1,5 @@
 // k_gp_mfma32p at n = 12, non-degenerate metric: the quad-plane B image and the address algebra of its step loop.
-// ONE statement of the layout for the plan builder (plan.cpp: build_map), the kernel (kernels_dense.hip.hpp: the XOR_STEP
+// ONE statement of the layout for the plan builder (plan_dense.cpp: build_operand_map), the kernel (kernels_dense.hip.hpp: the XOR_STEP
 // path) and the host test (tests/cpp/b_planes_driver.cpp).  Plain constexpr functions, no HIP types: the file compiles as
 // C++ and as HIP.  (It keeps the .hip.hpp suffix because it decides which bytes the kernel reads: the library's revision
 // string hashes device/*.hip.hpp.)

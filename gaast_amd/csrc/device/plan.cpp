@@ -12,9 +12,7 @@
 //   (3) products whose list is a dense slice of the geometric product's table run on the
 //       bitmask-tiled kernel (re-ordered sums: tolerance, not bit-exact; GAAST_FLAG_EXACT_ORDER
 //       keeps them on the exact kernel).
-#include "mfma32p_b_planes.hip.hpp"
 #include "plan_internal.hpp"
-#include "spinor_basis.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -27,47 +25,10 @@
 namespace gaast {
 namespace {
 
-struct Lowering {
-    const gaast_program_desc& d;
-    Plan& plan;
-    BladeTable bt;
+struct Lowering : LowerState {
     std::vector<int> cache;               // node -> node_buffers index, -1 = not cached
-    std::map<std::pair<int, int>, int> fresh;  // buffer -> index of its still-untouched ZERO step
-    std::vector<char> removed;
 
-    Lowering(const gaast_program_desc& desc, Plan& p)
-        : d(desc), plan(p), bt(desc.vec_space_dim), cache(size_t(desc.n_nodes), -1) {}
-
-    const gaast_node_desc& node(int i) const { return d.nodes[i]; }
-
-    const Layout& layout(BufRef r) const {
-        switch (r.kind) {
-        case BufKind::NODE: return plan.node_buffers[size_t(r.idx)];
-        case BufKind::INPUT: return plan.input_layouts[size_t(r.idx)];
-        default: return plan.out_layout;
-        }
-    }
-    static std::pair<int, int> key(BufRef r) { return {int(r.kind), r.idx}; }
-    void touch(BufRef r) { fresh.erase(key(r)); }
-
-    bool fail(int status, const std::string& msg) {
-        if (plan.error == GAAST_OK) {
-            plan.error = status;
-            plan.error_msg = msg;
-        }
-        return false;
-    }
-    bool ok() const { return plan.error == GAAST_OK; }
-
-    Step& emit(Step::Kind k, BufRef res, const std::string& name) {
-        plan.steps.emplace_back();
-        removed.push_back(0);
-        Step& s = plan.steps.back();
-        s.kind = k;
-        s.res = res;
-        s.name = name;
-        return s;
-    }
+    Lowering(const gaast_program_desc& desc, Plan& p) : LowerState(desc, p), cache(size_t(desc.n_nodes), -1) {}
 
     void emit_zero(BufRef buf) {
         emit(Step::ZERO, buf, "zero_fill[init_null_mv]");
@@ -501,242 +462,8 @@ struct Lowering {
         return store_in_cache(id);  // eval.rs:67-68
     }
 
-    // A host that cannot name the product (the Rust shim: the grades_to_produce closure is opaque,
-    // base_types.rs:60-64) sends GAAST_PROD_EXPLICIT.  A list big enough to matter for the dense
-    // kernels is compared entry by entry with the geometric product's list for the same grade
-    // sets and metric; only an exact match (indices and coefficient bits) is treated as one.
-    bool is_geometric_list(const gaast_node_desc& nd) const {
-        if (nd.product_kind == GAAST_PROD_GEOMETRIC) return true;
-        if (nd.product_kind != GAAST_PROD_EXPLICIT || !nd.comp_muls) return false;
-        const int n = d.vec_space_dim;
-        if (n < 6 || double(nd.n_comp_muls) * 32.0 < double(uint64_t(1) << (2 * n))) return false;   // (4^(n-1) / 8: parity-pure products)
-        const uint64_t lmin = node(nd.child0).minimal_grade_mask, rmin = node(nd.child1).minimal_grade_mask;
-        auto contribs = iter_contribs(nd.minimal_grade_mask, Selection{GAAST_PROD_GEOMETRIC, nullptr, nullptr}, lmin, rmin);
-        if (comp_mul_count(n, contribs) != nd.n_comp_muls) return false;
-        uint64_t e = 0;
-        bool same = true;
-        for_each_comp_mul(bt, d.metric_diag, contribs, [&](const gaast_comp_mul& m) {
-            if (same && std::memcmp(&m, &nd.comp_muls[e], sizeof(gaast_comp_mul)) != 0) same = false;
-            ++e;
-        });
-        return same;
-    }
-
-    // The algebra a dense kernel runs in: the program's (n, metric), or -- for a product of parity-pure operands -- the
-    // even subalgebra Cl+(p, q) = Cl(n - 1) built on a pivot vector e_p (parity_reduced_frame below).
-    struct DenseFrame {
-        int n = 0;
-        std::vector<double> metric;
-        int pivot = -1;            // >= 0: parity-reduced; the basis vector of the program's algebra the reduction is built on
-        int lpar = -1, rpar = -1;  // parity of the left / right operand (0 even, 1 odd) when reduced
-    };
-    static int parity_of(uint64_t mask) {   // 0: only even grades, 1: only odd grades, -1: mixed or empty
-        const uint64_t EVEN = 0x5555555555555555ULL;
-        if (!mask) return -1;
-        if (!(mask & ~EVEN)) return 0;
-        if (!(mask & EVEN)) return 1;
-        return -1;
-    }
-
-    // Basis permutation that brings a diagonal metric into the shape the dense kernels want: position j of the
-    // permuted basis holds original vector perm[j]; positions [0, L) (the "lo" bits of a blade) hold vectors that
-    // square to +-1 (+1 first), never 0.  uniform: the four lo vectors must all square to the same sign (vector-FMA
-    // kernel: compile-time sign pattern).  The identity is kept whenever it already qualifies.
-    static bool dense_basis_permutation(const DenseFrame& f, int L, bool uniform, std::vector<int>& perm) {
-        const int n = f.n;
-        std::vector<int> plus, minus;   // by the SIGN of the square: a general entry g is rescaled to g / |g| (blade_scale)
-        for (int i = 0; i < n; ++i) {
-            if (f.metric[size_t(i)] > 0.0) plus.push_back(i);
-            if (f.metric[size_t(i)] < 0.0) minus.push_back(i);
-        }
-        std::vector<int> lo;
-        if (uniform) {
-            if (int(plus.size()) >= L) lo.assign(plus.begin(), plus.begin() + L);
-            else if (int(minus.size()) >= L) lo.assign(minus.begin(), minus.begin() + L);
-            else return false;
-        } else {
-            if (int(plus.size() + minus.size()) < L) return false;
-            for (int i : plus) if (int(lo.size()) < L) lo.push_back(i);
-            for (int i : minus) if (int(lo.size()) < L) lo.push_back(i);
-        }
-        std::sort(lo.begin(), lo.end());
-        std::vector<char> is_lo(size_t(n), 0);
-        for (int i : lo) is_lo[size_t(i)] = 1;
-        perm = lo;
-        for (int i = 0; i < n; ++i)
-            if (!is_lo[size_t(i)]) perm.push_back(i);
-        return true;
-    }
-
-    // General diagonal metric on the dense kernels.  e_i = r_i f_i with r_i = sqrt|g_i| (1 for a null vector) gives a basis
-    // whose metric is sign(g_i) in {+1, -1, 0}; a blade e_S = w_S f_S, w_S = prod_{i in S} r_i.  So
-    //     C_T = (1 / w_T) * sum_{S ^ U = T} s'(S, U) (w_S A_S) (w_U B_U),
-    // s' the sign-metric coefficient: w_S w_U / w_T = prod_{i in S & U} |g_i| is the reference's coefficient magnitude
-    // (algebra.rs:78-81).  The operands are multiplied by w while they are staged, the result by 1 / w_T when it is stored:
-    // three more roundings per term than the +-1 / 0 case (the factors themselves are rounded once, from long double).
-    // Used only when every w_S and 1 / w_S stays within 2^+-40 (f32) / 2^+-300 (f64) -- no overflow or gradual underflow
-    // introduced by the rescaling for operands of ordinary magnitude; otherwise the exact list kernels keep the product.
-    static bool metric_is_unit(const DenseFrame& f) {
-        for (double g : f.metric)
-            if (g != 1.0 && g != -1.0 && g != 0.0) return false;
-        return true;
-    }
-    bool dense_scales_ok(const DenseFrame& f) const {
-        long double up = 1.0L, down = 1.0L;
-        for (double g : f.metric) {
-            if (!(g == g) || g == 1.0 / 0.0 || g == -1.0 / 0.0) return false;
-            if (g == 0.0) continue;
-            const long double r = sqrtl(fabsl((long double)g));
-            if (r > 1.0L) up *= r;
-            else down *= r;
-        }
-        if (f.pivot >= 0) {   // the reduction's own factors are powers of 1 / g_p up to (n - 1) / 2, and g_p itself
-            const long double gp = fabsl((long double)d.metric_diag[f.pivot]);
-            const long double worst = powl(gp > 1.0L ? gp : 1.0L / gp, (long double)((d.vec_space_dim + 1) / 2));
-            up *= worst;
-            down /= worst;
-        }
-        if (metric_is_unit(f) && (f.pivot < 0 || fabs(d.metric_diag[f.pivot]) == 1.0)) return true;
-        const long double lim = plan.dtype == GAAST_F32 ? 0x1p40L : 0x1p300L;
-        return up <= lim && down >= 1.0L / lim;
-    }
-    static long double blade_scale(const DenseFrame& f, uint32_t S) {   // w_S in the frame's algebra
-        long double w = 1.0L;
-        for (int i = 0; i < f.n; ++i)
-            if (((S >> i) & 1u) && f.metric[size_t(i)] != 0.0) w *= sqrtl(fabsl((long double)f.metric[size_t(i)]));
-        return w;
-    }
-
-    // Parity-pure operands (the reference only ever multiplies the entries it needs, specialize.rs:162-183; even x even --
-    // rotor composition, the second product of every sandwich -- needs a quarter of the 4^n table).  The even subalgebra
-    // Cl+ of Cl(n) is a Clifford algebra of dimension n - 1 on the generators f_i = e_i e_p (i != p, e_p any non-null basis
-    // vector): f_i f_j = -f_j f_i, f_i^2 = -g_i g_p.  An even blade e_E is a multiple of the f-blade on E \ {p},
-    //     e_E = c(E) f_{E \ p},   c(E) = sigma(E) (-g_p)^(-floor(|E \ p| / 2)),   sigma(E) = (-1)^#{i in E : i > p} if p in E, else 1
-    // and an odd multivector is (even) e_p:  A = A~ e_p,  A~_{S ^ p} = A_S tau(S) (p in S ? 1 : 1 / g_p),  tau(S) = (-1)^#{i in S : i > p}.
-    // With X^ = e_p X e_p^-1 (even X: the blades containing p change sign):
-    //     even x even: A B                      odd x even: (A~ B^) e_p
-    //     even x odd : (A B~) e_p               odd x odd : g_p A~ B~^
-    // Every case is ONE product of two elements of Cl(n - 1) -- 4^(n-1) multiply-adds -- with per-component factors on the
-    // way in and on the way out: exactly what the operand maps (position, negate bit, scale) and the result map carry.
-    bool parity_reduced_frame(uint64_t lmask, uint64_t rmask, DenseFrame& f) const {
-        const int n = d.vec_space_dim;
-        const int lp = parity_of(lmask), rp = parity_of(rmask);
-        if (lp < 0 || rp < 0 || n - 1 < 6) return false;
-        int p = -1;
-        for (int i = n - 1; i >= 0 && p < 0; --i)
-            if (d.metric_diag[i] != 0.0) p = i;
-        if (p < 0) return false;
-        f.n = n - 1;
-        f.metric.clear();
-        for (int i = 0; i < n; ++i)
-            if (i != p) f.metric.push_back(-d.metric_diag[i] * d.metric_diag[p] == 0.0 ? 0.0 : -d.metric_diag[i] * d.metric_diag[p]);
-        f.pivot = p;
-        f.lpar = lp;
-        f.rpar = rp;
-        return true;
-    }
-
-    // which dense kernel family (false: none), in which algebra (frame) and in which basis of it (perm)
-    bool dense_family_for(const DenseFrame& f, uint64_t n_comp_muls, std::vector<int>& perm, DenseFamily& fam) const {
-        const int n = f.n;
-        auto take = [&](DenseFamily x) { fam = x; return true; };
-        if (n < 6 || n > 14) return false;  // small algebras: the exact kernel is HBM-bound anyway
-        // A general diagonal metric (algebra.rs:148-165 multiplies by ANY base_vec_dot, :79-81) runs in the rescaled basis
-        // f_i = e_i / sqrt|g_i|; it needs finite, well-scaled factors, else the list kernels keep the product
-        if (!dense_scales_ok(f)) return false;
-        if (double(n_comp_muls) * 8.0 < double(uint64_t(1) << (2 * n))) return false;  // the tiled kernels always do 4^n multiply-adds
-        const bool mfma_ok = plan.dtype == GAAST_F32 && !(plan.flags & GAAST_FLAG_NO_MFMA);
-        // matrix-core variants: f32, n >= 10 (32 result columns per wave, five lo vectors) / n = 8, 9 (lo = 4 bits)
-        // (k_gp_mfma32p: +A, -A, +B, -B images; n = 14 does not fit and runs on k_gp_mfma32)
-        if (mfma_ok && n >= 10 && dense_basis_permutation(f, 5, false, perm)) return take(n <= 13 ? DenseFamily::MFMA32P : DenseFamily::MFMA32);
-        if (n == 14) return false;      // both operands of an item (128 KiB in f32) fit the LDS of the matrix-core kernel only
-        if (mfma_ok && (n == 8 || n == 9) && dense_basis_permutation(f, 4, false, perm)) return take(DenseFamily::MFMA16X4);   // k_gp_mfma16x4<float>
-        // f64 (the reference's value type), n = 8 ... 12: v_mfma_f64_16x16x4_f64, one item per workgroup
-        if (plan.dtype == GAAST_F64 && !(plan.flags & GAAST_FLAG_NO_MFMA) && n >= 8 && n <= 12 &&
-            dense_basis_permutation(f, 4, false, perm))
-            return take(DenseFamily::MFMA16X4);
-        // n = 7, both value types: one wave per item on the 16x16x4 instructions (lo = 3 bits: three non-null vectors)
-        if (n == 7 && !(plan.flags & GAAST_FLAG_NO_MFMA) && dense_basis_permutation(f, 3, false, perm)) return take(DenseFamily::MFMA7);
-        // n = 6, both value types: four 16x16x4 instructions per item, ANY +-1 / 0 metric in the basis as it stands (signs and
-        // vanishing terms are slots of the operand images and bits of the accumulators: no lo vectors, no permutation)
-        if (n == 6 && !(plan.flags & GAAST_FLAG_NO_MFMA) && dense_basis_permutation(f, 0, false, perm)) return take(DenseFamily::MFMA6);
-        if (dense_basis_permutation(f, 4, true, perm)) return take(DenseFamily::VECTOR_FMA);
-        return false;
-    }
-    bool dense_choice(const gaast_node_desc& nd, BufRef res, BufRef l, BufRef r, std::vector<int>& perm, DenseFrame& frame, DenseFamily& fam) const {
-        if (plan.flags & (GAAST_FLAG_EXACT_ORDER | GAAST_FLAG_NO_FUSION)) return false;
-        const int n = d.vec_space_dim;
-        if (n < 6 || n > 15) return false;
-        if (layout(res).dim != n || layout(l).dim != n || layout(r).dim != n) return false;
-        if (nd.product_kind >= GAAST_PROD_ADJ_LEFT) {
-            // adjoint of a geometric product: a forward product in the metric m' (1 / m off the null
-            // vectors, 0 on them) of relabelled / re-signed / rescaled operands, always in the full frame
-            if ((nd.product_kind & 7) != GAAST_PROD_GEOMETRIC || n > 14) return false;
-            DenseFrame f;
-            f.n = n;
-            for (int i = 0; i < n; ++i) f.metric.push_back(d.metric_diag[i] == 0.0 ? 0.0 : 1.0 / d.metric_diag[i]);
-            const bool found = dense_family_for(f, nd.n_comp_muls, perm, fam);
-            if (found) frame = f;
-            return found;
-        }
-        const uint64_t lmask = node(nd.child0).minimal_grade_mask & layout(l).mask, rmask = node(nd.child1).minimal_grade_mask & layout(r).mask;
-        bool geometric_known = false, geometric = false;
-        auto is_gp = [&]() {
-            if (!geometric_known) {
-                geometric = is_geometric_list(nd);
-                geometric_known = true;
-            }
-            return geometric;
-        };
-        DenseFrame reduced;
-        if (parity_reduced_frame(lmask, rmask, reduced) && dense_family_for(reduced, nd.n_comp_muls, perm, fam) && is_gp()) {
-            frame = reduced;
-            return true;
-        }
-        DenseFrame full;
-        full.n = n;
-        full.metric.assign(d.metric_diag, d.metric_diag + n);
-        if (n <= 14 && dense_family_for(full, nd.n_comp_muls, perm, fam) && is_gp()) {
-            frame = full;
-            return true;
-        }
-        return false;
-    }
-
-    // opt-in matrix-representation kernels: f32, n = 7..12 (odd n as the subalgebra of n + 1), every
-    // vector squaring to +-1
-    bool spinor_eligible(const gaast_node_desc& nd, BufRef res, BufRef l, BufRef r) const {
-        if (!(plan.flags & GAAST_FLAG_SPINOR_GEMM)) return false;
-        if (plan.flags & (GAAST_FLAG_EXACT_ORDER | GAAST_FLAG_NO_FUSION)) return false;
-        const int n = d.vec_space_dim;
-        if (n < 7 || n > 12) return false;
-        if (layout(res).dim != n || layout(l).dim != n || layout(r).dim != n) return false;
-        for (int i = 0; i < n; ++i)
-            if (d.metric_diag[i] != 1.0 && d.metric_diag[i] != -1.0) return false;
-        if (!is_geometric_list(nd)) return false;
-        return double(nd.n_comp_muls) * 8.0 >= double(uint64_t(1) << (2 * n));
-    }
-
-    // blade -> Pauli string i^k X^x Z^z under the Jordan-Wigner generators (kernels_spinor.hip.hpp);
-    // vectors beyond the algebra's dimension (odd n padded to n + 1) square to +1
-    void pauli_string(uint32_t blade, uint32_t* x, uint32_t* z, uint32_t* k) const {
-        uint32_t px = 0, pz = 0, pk = 0;
-        for (int v = 0; v < 32 && (blade >> v); ++v) {
-            if (!((blade >> v) & 1u)) continue;
-            const int j = v >> 1;
-            const uint32_t gx = 1u << j;
-            const uint32_t gz = (v & 1) ? (1u << (j + 1)) - 1u : (1u << j) - 1u;
-            const bool negative = v < d.vec_space_dim && d.metric_diag[v] < 0.0;
-            const uint32_t gk = uint32_t(v & 1) + (negative ? 1u : 0u);
-            pk = (pk + gk + 2u * uint32_t(__builtin_popcount(pz & gx))) & 3u;
-            px ^= gx;
-            pz ^= gz;
-        }
-        *x = px;
-        *z = pz;
-        *k = pk;
-    }
-
+    // What the three paths of a Product share; then the opt-in matrix-representation kernels, a dense kernel (both plan_dense.cpp),
+    // or the exact list
     void lower_product(BufRef res, int id) {  // eval.rs:61-86
         const gaast_node_desc& nd = node(id);
         int canon_l = 0, canon_r = 0;
@@ -749,390 +476,34 @@ struct Lowering {
             fail(GAAST_ERR_MISSING_GRADE, "product operand aliases its own result buffer");
             return;
         }
-        const Layout &lr = layout(res), &ll = layout(l), &lrr = layout(r);
-        const uint64_t lmin = node(nd.child0).minimal_grade_mask, rmin = node(nd.child1).minimal_grade_mask;
-        const uint64_t omin = nd.minimal_grade_mask;
         if (nd.comp_muls == nullptr && nd.product_kind < 0)
             throw std::runtime_error("PRODUCT node has neither a comp-mul list nor a product kind");
-
         // may the zero-fill of a fresh result buffer be folded into this product?
-        auto fr = fresh.find(key(res));
+        const auto fr = fresh.find(key(res));
         const bool is_fresh = fr != fresh.end() && !(plan.flags & GAAST_FLAG_NO_FUSION);
-
-        if (spinor_eligible(nd, res, l, r)) {
-            if ((omin & lr.mask) != omin) {
+        const ProductOperands po{nd, res, l, r, canon_l, canon_r, flip_l, flip_r, node(nd.child0).minimal_grade_mask, node(nd.child1).minimal_grade_mask,
+                                 is_fresh ? fr->second : -1};
+        DenseChoice choice;
+        const bool spinor = spinor_eligible(*this, po);
+        if (spinor || dense_choice(*this, po, choice)) {
+            if ((nd.minimal_grade_mask & layout(res).mask) != nd.minimal_grade_mask) {
                 fail(GAAST_ERR_MISSING_GRADE, "product result grade absent from result buffer");
                 return;
             }
-            const bool beta0 = is_fresh && (lr.mask & ~omin) == 0;
-            if (beta0) removed[size_t(fr->second)] = 1;
-            const int n = d.vec_space_dim;
-            const int m = (n + 1) / 2;                 // 2^m x 2^m complex matrices
-            const uint32_t D = 1u << m, LD = D + 1u;
-            Step& s = emit(Step::PRODUCT_DENSE, res, "product_spinor_gemm[gp n=" + std::to_string(n) + "]");
-            s.a = l;
-            s.b = r;
-            s.canon_a = canon_l;
-            s.canon_b = canon_r;
-            s.beta = beta0 ? 0 : 1;
-            s.n_entries = nd.n_comp_muls;
-            s.dense.family = DenseFamily::SPINOR;
-            s.dense.spinor_m = m;
-            {
-                // D*D 16-bit table entries indexed by row offset, two per word (format: SpinorArgs);
-                // one real plane per operand: indices in the basis of spinor_basis.hpp
-                uint32_t alpha = 0, lam = 0;
-                for (uint32_t blade = 0; blade < (1u << (2 * m)); ++blade) {
-                    uint32_t px, pz, pk;
-                    pauli_string(blade, &px, &pz, &pk);
-                    if (pz == 0 && __builtin_popcount(px) == 1 && (pk & 1u)) alpha |= px;
-                    if (px == 0 && __builtin_popcount(pz) == 1 && (pk & 1u)) lam |= pz;
-                }
-                const SpinorBasis sb = choose_spinor_basis(m, alpha, lam);
-                s.dense.spinor_lam_bit = sb.lam_bit;
-                s.dense.spinor_has_alpha = sb.has_alpha ? 1 : 0;
-                auto build1 = [&](const Layout& lay, uint64_t want, uint64_t flip, int role, std::vector<uint32_t>& packed, int* full) {
-                    // operands: bit 0 = negate, bits [14:2] = x'*LD + z'; result: bit 0 = negate, bit 1 = nothing
-                    // to store, bits [15:2] = x'*LD + z'
-                    const uint16_t nothing = role == 2 ? uint16_t(2u) : uint16_t(D << 2);
-                    std::vector<uint16_t> map(size_t(D) * D, nothing);
-                    size_t count = 0;
-                    for (int k = 0; k <= n; ++k) {
-                        if (!((want >> k) & 1ULL)) continue;
-                        for (uint32_t i = 0; i < bt.grade_dim[size_t(k)]; ++i) {
-                            uint32_t px, pz, pk;
-                            pauli_string(bt.blade_of[size_t(k)][i], &px, &pz, &pk);
-                            const uint32_t x2 = sb.map_x(px), z2 = sb.map_z(pz);
-                            const uint32_t f = (sb.has_alpha ? (x2 >> (m - 1)) & 1u : 0u) ^
-                                               (sb.lam_bit >= 0 ? (z2 >> sb.lam_bit) & 1u : 0u);
-                            if (f != (pk & 1u)) throw std::runtime_error("spinor basis: phase parity mismatch");
-                            uint32_t neg = uint32_t((flip >> k) & 1ULL) ^ (pk >> 1);
-                            if (role != 0) neg ^= uint32_t(__builtin_popcount(x2 & z2) & 1);
-                            map[size_t(lay.offset(k) + i)] = uint16_t((x2 * LD + z2) << 2 | neg);
-                            ++count;
-                        }
-                    }
-                    *full = count == size_t(D) * D;
-                    packed.resize(map.size() / 2);
-                    std::memcpy(packed.data(), map.data(), map.size() * sizeof(uint16_t));
-                };
-                build1(ll, lmin & ll.mask, flip_l, 0, s.dense.left_map, &s.dense.left_full);
-                build1(lrr, rmin & lrr.mask, flip_r, 1, s.dense.right_map, &s.dense.right_full);
-                build1(lr, omin, 0, 2, s.dense.spinor_out_map, &s.dense.out_full);
-                s.name = "product_spinor_gemm[gp n=" + std::to_string(n) + " lam=" + std::to_string(sb.lam_bit) + "]";
-                touch(res);
-                return;
-            }
-        }
-        std::vector<int> perm;
-        DenseFrame frame;
-        DenseFamily fam = DenseFamily::VECTOR_FMA;
-        if (dense_choice(nd, res, l, r, perm, frame, fam)) {
-            if ((omin & lr.mask) != omin) {
-                fail(GAAST_ERR_MISSING_GRADE, "product result grade absent from result buffer");
-                return;
-            }
-            const int n = d.vec_space_dim;   // the program's algebra: graded rows, blade <-> (grade, index)
-            const int n2 = frame.n;          // the kernel's algebra: n, or n - 1 for parity-pure operands
-            const bool reduced = frame.pivot >= 0;
-            // grades this step produces: a parity-pure product fills only the grades of its own parity
-            uint64_t prod_mask = omin;
-            if (reduced) prod_mask &= ((frame.lpar ^ frame.rpar) ? 0xAAAAAAAAAAAAAAAAULL : 0x5555555555555555ULL);
-            const bool beta0 = is_fresh && (lr.mask & ~prod_mask) == 0;
-            if (beta0) {
-                removed[size_t(fr->second)] = 1;
-            }
-            // adjoint products (GAAST_PROD_ADJ_*): ADJ_LEFT multiplies (cotangent, B), ADJ_RIGHT (A, cotangent), so the kernel's
-            // operands are (child0, child1) or (child1, child0); the cotangent's blades and the result's are relabelled k -> k ^ Z
-            // (Z: the null vectors), the other operand's component j is scaled by rev(j) mn(j) (-1)^R(Z, j) (left adjoint) or
-            // (-1)^R(j, Z) (right adjoint), mn the product of the non-null squares (tools/proto/adjoint_dense.py)
-            const int adj = nd.product_kind >= GAAST_PROD_ADJ_LEFT ? (nd.product_kind & ~7) : 0;
-            uint32_t adj_z = 0;
-            for (int i = 0; adj && i < n; ++i)
-                if (d.metric_diag[i] == 0.0) adj_z |= 1u << i;
-            const bool swap_ops = adj == GAAST_PROD_ADJ_RIGHT;
-            const BufRef ka = swap_ops ? r : l, kb = swap_ops ? l : r;
-            const Layout &kla = swap_ops ? lrr : ll, &klb = swap_ops ? ll : lrr;
-            const uint64_t kfa = swap_ops ? flip_r : flip_l, kfb = swap_ops ? flip_l : flip_r;
-            const uint64_t kwa = swap_ops ? (rmin & lrr.mask) : (lmin & ll.mask), kwb = swap_ops ? (lmin & ll.mask) : (rmin & lrr.mask);
-            auto adj_operand = [&](uint32_t S, bool right, long double* f) -> uint32_t {
-                *f = 1.0L;
-                if (!adj) return S;
-                if ((adj == GAAST_PROD_ADJ_LEFT) != right) return S ^ adj_z;   // the cotangent
-                const int k = __builtin_popcount(S);
-                int sign = (k * (k - 1) / 2) & 1;
-                sign ^= adj == GAAST_PROD_ADJ_LEFT ? reorder_parity(adj_z, S) : reorder_parity(S, adj_z);
-                long double m = 1.0L;
-                for (int i = 0; i < n; ++i)
-                    if (((S >> i) & 1u) && d.metric_diag[i] != 0.0) m *= (long double)d.metric_diag[i];
-                *f = sign ? -m : m;
-                return S;
-            };
-            Step& s = emit(Step::PRODUCT_DENSE, res, "product_dense[gp n=" + std::to_string(n) + "]");
-            s.a = ka;
-            s.b = kb;
-            s.canon_a = swap_ops ? canon_r : canon_l;
-            s.canon_b = swap_ops ? canon_l : canon_r;
-            s.beta = beta0 ? 0 : 1;
-            s.n_entries = nd.n_comp_muls;
-            Step::Dense& ds = s.dense;   // (no step is emitted below: the reference stays valid)
-            ds.n = n2;
-            ds.family = fam;
-            ds.mfma16_quads = fam == DenseFamily::MFMA16X4 && plan.dtype == GAAST_F32;   // k_gp_mfma16x4<float>: B words in 16-byte quads
-            // blade R of the frame's basis <-> blade R' of its permuted basis, f_R = sign(R) f'_R' (the parity of the
-            // inversions of the new positions of R's vectors taken in ascending original order)
-            std::vector<int> inv(size_t(n2), 0);
-            bool identity = true;
-            for (int j = 0; j < n2; ++j) {
-                inv[size_t(perm[size_t(j)])] = j;
-                identity = identity && perm[size_t(j)] == j;
-            }
-            std::vector<uint32_t> new_blade(size_t(1) << n2), blade_sign(size_t(1) << n2);
-            for (uint32_t S = 0; S < (1u << n2); ++S) {
-                uint32_t S2 = 0, par = 0;
-                for (int p = 0; p < n2; ++p) {
-                    if (!((S >> p) & 1u)) continue;
-                    const int q = inv[size_t(p)];
-                    par ^= uint32_t(__builtin_popcount(S2 >> (q + 1))) & 1u;
-                    S2 |= 1u << q;
-                }
-                new_blade[S] = S2;
-                blade_sign[S] = par;
-            }
-            // ---- stage 1: blade of the program's algebra -> blade of the frame's algebra, with a factor ----
-            const int pv = frame.pivot;
-            const long double gp = reduced ? (long double)d.metric_diag[pv] : 1.0L;
-            auto has_p = [&](uint32_t S) { return ((S >> pv) & 1u) != 0; };
-            auto tau = [&](uint32_t S) -> long double { return (__builtin_popcount(S >> (pv + 1)) & 1) ? -1.0L : 1.0L; };
-            auto compress = [&](uint32_t E) -> uint32_t {   // drop bit p
-                E &= ~(1u << pv);
-                return (E & ((1u << pv) - 1u)) | ((E >> (pv + 1)) << pv);
-            };
-            auto c_of = [&](uint32_t E) -> long double {    // e_E = c(E) f_{E \ p} for an even blade E
-                const int k = __builtin_popcount(E & ~(1u << pv));
-                long double v = powl(-1.0L / gp, (long double)(k / 2));
-                return has_p(E) ? v * tau(E) : v;
-            };
-            auto t_of = [&](uint32_t S) -> long double { return tau(S) * (has_p(S) ? 1.0L : 1.0L / gp); };   // odd S: A~_{S ^ p} = A_S t(S)
-            // operand component on blade S -> (frame blade R, factor): image value = A_S * factor
-            auto operand_to_frame = [&](uint32_t S, bool right, long double* factor) -> uint32_t {
-                if (!reduced) {
-                    *factor = 1.0L;
-                    return S;
-                }
-                const int par = right ? frame.rpar : frame.lpar;
-                const uint32_t E = par ? S ^ (1u << pv) : S;
-                long double f = (par ? t_of(S) : 1.0L) * c_of(E);
-                if (right && frame.lpar == 1 && has_p(E)) f = -f;   // the conjugation e_p X e_p^-1 of the right operand
-                *factor = f;
-                return compress(E);
-            };
-            // result component on blade T <- (frame blade R, factor): C_T = C'_R * factor
-            auto result_from_frame = [&](uint32_t T, long double* factor) -> uint32_t {
-                if (!reduced) {
-                    *factor = 1.0L;
-                    return T;
-                }
-                if ((frame.lpar ^ frame.rpar) == 0) {
-                    *factor = ((frame.lpar == 1) ? gp : 1.0L) / c_of(T);
-                    return compress(T);
-                }
-                const uint32_t E = T ^ (1u << pv);   // C = P e_p: C_{E ^ p} = P_E tau(E) (p in E ? g_p : 1)
-                *factor = tau(E) * (has_p(E) ? gp : 1.0L) / c_of(E);
-                return compress(E);
-            };
-            // position of blade m in the LDS image the kernel reads (mirrors kernels.hip.hpp)
-            auto vec_pos = [](uint32_t m) {  // dense_lds_pos
-                const uint32_t x = m >> 4, lo = m & 15;
-                return (x << 4) | ((((lo >> 2) ^ (x >> 2)) & 3) << 2) | (lo & 3);
-            };
-            // k_gp_mfma32p's B image: the lane's 16 words (k of one parity) even-|k >> 1| first, quads rotated as in mfma_b_pos
-            // (n = 12 with no null vector among the hi vectors -- the instantiations <false, 12, *, *>, whose step loop keeps
-            //  live B addresses: the quad-plane image of mfma32p_b_planes.hip.hpp instead)
-            bool b_quad_planes = fam == DenseFamily::MFMA32P && n2 == b_planes::kDim;
-            for (int j = 5; j < n2; ++j) b_quad_planes = b_quad_planes && frame.metric[size_t(perm[size_t(j)])] != 0.0;
-            auto mfma32p_b_pos = [](uint32_t m) {
-                static const int word_of_s[16] = {0, 8, 9, 1, 10, 2, 3, 11, 12, 4, 5, 13, 6, 14, 15, 7};
-                const uint32_t x = m >> 5, k = m & 31, w = uint32_t(word_of_s[k >> 1]);
-                const uint32_t lq = ((k & 1) << 2) | (w >> 2);
-                return (x << 5) | (((lq ^ (x >> 1)) & 7) << 2) | (w & 3);
-            };
-            // k_gp_mfma16d's B image (f64): word k of block x at k ^ (((x >> 1) & 7) << 1)
-            auto mfma16d_b_pos = [](uint32_t m) {
-                const uint32_t x = m >> 4, k = m & 15u;
-                return (x << 4) | (k ^ (((x >> 1) & 7u) << 1));
-            };
-            // k_gp_mfma16x4<float>'s B image: word k of block x in quad kq(k) ^ (((x >> 2) & 1) << 1), slot s(k), with
-            // (kq, s) from the kernel's k table (Mfma16x4<float>::k_of)
-            auto mfma16q_b_pos = [](uint32_t m) {
-                static const int kq_of[16] = {0, 2, 2, 0, 2, 0, 0, 2, 3, 1, 1, 3, 1, 3, 3, 1};
-                static const int s_of[16] = {0, 0, 1, 1, 2, 2, 3, 3, 0, 0, 1, 1, 2, 2, 3, 3};
-                const uint32_t x = m >> 4, k = m & 15u;
-                return (x << 4) | (uint32_t(kq_of[k] ^ int(((x >> 2) & 1u) << 1)) << 2) | uint32_t(s_of[k]);
-            };
-            // k_gp_mfma7: A image u * 72 + (a_hi3, a_lo); B image [kq][v][b_hi3][s] with (kq, s) from the kernel's k table (mfma7_k)
-            auto mfma7_a_pos = [](uint32_t m) { return (m & 63u) + (m >> 6) * 72u; };
-            auto mfma7_b_pos = [](uint32_t m) {
-                static const int kq_of[8] = {0, 2, 2, 0, 3, 1, 1, 3};
-                static const int s_of[8] = {0, 0, 1, 1, 0, 0, 1, 1};
-                const uint32_t v = m >> 6, bh = (m >> 3) & 7u, k = m & 7u;
-                return ((uint32_t(kq_of[k]) * 16u + v * 8u + bh) << 1) | uint32_t(s_of[k]);
-            };
-            auto mfma_b_pos = [](uint32_t m) {
-                const uint32_t x = m >> 5, k = m & 31;
-                const uint32_t lq = ((k & 1) << 2) | (k >> 3);
-                return (x << 5) | (((lq ^ (x >> 1)) & 7) << 2) | ((k >> 1) & 3);
-            };
-            // entry: row offset | image position << 16 | (negate while staging) << 31; scale[entry] = |factor| (when any != 1)
-            auto build_map = [&](const Layout& lay, uint64_t want, uint64_t flip, bool right, std::vector<uint32_t>& map,
-                                 std::vector<double>& scale, int* full, int* contig) {
-                bool seq = true;
-                for (int k = 0; k <= n; ++k) {
-                    if (!((want >> k) & 1ULL)) continue;
-                    for (uint32_t i = 0; i < bt.grade_dim[size_t(k)]; ++i) {
-                        long double fa;
-                        const uint32_t orig = adj_operand(bt.blade_of[size_t(k)][i], right, &fa);
-                        long double f1;
-                        const uint32_t R = operand_to_frame(orig, right, &f1);
-                        const uint32_t blade = new_blade[R];
-                        const long double factor = fa * f1 * blade_scale(frame, R);
-                        uint32_t neg = uint32_t((flip >> k) & 1ULL) ^ blade_sign[R] ^ (factor < 0.0L ? 1u : 0u);
-                        // image-pair kernels: the b_hi part of (-1)^(|a_hi| |b_lo|), |a_hi| = |b_hi| + |c_hi| (mod 2), lives in the B image
-                        uint32_t pos = blade;   // the A images of the matrix-core kernels; k_gp_mfma6 derives its image slots from the blade itself
-                        switch (fam) {
-                        case DenseFamily::MFMA16X4:
-                            if (right) neg ^= uint32_t(__builtin_popcount(blade >> 4) & __builtin_popcount(blade & 15u) & 1);
-                            if (right) pos = ds.mfma16_quads ? mfma16q_b_pos(blade) : mfma16d_b_pos(blade);
-                            break;
-                        case DenseFamily::MFMA32P:
-                            if (right) neg ^= uint32_t(__builtin_popcount(blade >> 5) & __builtin_popcount(blade & 31u) & 1);
-                            if (right) pos = b_quad_planes ? b_planes::pos(blade) : mfma32p_b_pos(blade);
-                            break;
-                        case DenseFamily::MFMA32: if (right) pos = mfma_b_pos(blade); break;
-                        case DenseFamily::MFMA7:
-                            if (right) neg ^= uint32_t(__builtin_popcount((blade >> 3) & 7u) & __builtin_popcount(blade & 7u) & 1);
-                            pos = right ? mfma7_b_pos(blade) : mfma7_a_pos(blade);
-                            break;
-                        case DenseFamily::MFMA6: break;
-                        default: pos = vec_pos(blade); break;
-                        }
-                        const uint32_t sgn = neg ? 0x80000000u : 0u;
-                        const uint32_t off = uint32_t(lay.offset(k) + i);
-                        seq = seq && off == map.size();
-                        map.push_back(off | (pos << 16) | sgn);
-                        scale.push_back(double(fabsl(factor)));
-                    }
-                }
-                *full = map.size() == (size_t(1) << n2);
-                *contig = seq && map.size() % 4 == 0 && !map.empty();
-                if (fam == DenseFamily::MFMA6 && *full) {
-                    // k_gp_mfma6: lane q moves the component of entry q into its four image slots.  Entries are dealt to lanes so
-                    // that the lanes sharing an LDS cycle of a store hit different banks (row order: 73 % of the LDS cycles were
-                    // conflicts, profiles/r04_gp6f32_pmc_first_version.csv).  blade = (top2 | hi2 | lo2) = (u, ah, al) / (v, bh, bl):
-                    //   f32 (32 lanes per cycle): A: bank = 16 (al ^ kq)_0 + 4 u + ah    -> group = al_1;       B (slot order
-                    //        rotated by bl in the kernel): bank = 16 (bh ^ s)_0 + 4 v + s -> group = bh_1
-                    //   f64 (16 lanes per cycle, 8-byte units mod 16): A: (u_0, al ^ kq, ah_0) -> group = (u_1, ah_1);  B: (v, bh_0, bl_0)
-                    //        -> group = (bh_1, bl_1)
-                    const bool f32 = plan.dtype == GAAST_F32;
-                    auto lane_of = [&](uint32_t blade) -> uint32_t {
-                        const uint32_t t = blade >> 4, h = (blade >> 2) & 3u, l = blade & 3u;
-                        if (!right) return f32 ? ((l >> 1) << 5) | ((l & 1u) << 4) | (t << 2) | h
-                                               : ((((t >> 1) << 1) | (h >> 1)) << 4) | ((t & 1u) << 3) | (l << 1) | (h & 1u);
-                        return f32 ? ((h >> 1) << 5) | ((h & 1u) << 4) | (t << 2) | l
-                                   : ((((h >> 1) << 1) | (l >> 1)) << 4) | (t << 2) | ((h & 1u) << 1) | (l & 1u);
-                    };
-                    std::vector<uint32_t> m2(map.size());
-                    std::vector<double> s2(scale.size());
-                    for (size_t e = 0; e < map.size(); ++e) {
-                        const uint32_t q = lane_of((map[e] >> 16) & 63u);
-                        m2[q] = map[e];
-                        s2[q] = scale[e];
-                    }
-                    map.swap(m2);
-                    scale.swap(s2);
-                    *contig = 0;
-                }
-                if (fam == DenseFamily::MFMA7 && *full) {
-                    // k_gp_mfma7 moves ONE component per lane and load (entry q = load * 64 + lane), so the entries can be dealt
-                    // to lanes by LDS bank: the lanes that share an LDS cycle of a store (f32: 32 lanes, bank = position mod 32;
-                    // f64: 16 lanes of 8 bytes, position mod 16) get components of different banks -- every residue holds
-                    // 128 / G positions of an image, one per run of G entries.  (Row order put 36 conflict cycles into the
-                    // ~108 LDS cycles an item cost.)  The row offsets are no longer 0, 1, 2, ...: no 16-byte vector path.
-                    const uint32_t G = plan.dtype == GAAST_F32 ? 32u : 16u;
-                    std::vector<std::vector<size_t>> bucket(G);
-                    for (size_t e = 0; e < map.size(); ++e) bucket[((map[e] >> 16) & 0x7fffu) % G].push_back(e);
-                    bool even = true;
-                    for (const auto& b : bucket) even = even && b.size() == map.size() / G;
-                    if (even) {
-                        std::vector<uint32_t> m2;
-                        std::vector<double> s2;
-                        for (size_t r = 0; r < map.size() / G; ++r)
-                            for (uint32_t k = 0; k < G; ++k) {
-                                m2.push_back(map[bucket[k][r]]);
-                                s2.push_back(scale[bucket[k][r]]);
-                            }
-                        map.swap(m2);
-                        scale.swap(s2);
-                        *contig = 0;
-                    }
-                }
-            };
-            build_map(kla, kwa, kfa, false, ds.left_map, ds.left_scale, &ds.left_full, &ds.left_contig);
-            build_map(klb, kwb, kfb, true, ds.right_map, ds.right_scale, &ds.right_full, &ds.right_contig);
-            // out_map: indexed by the blade of the frame's permuted basis; offset | sign << 30, or -1; out_scale: |factor|
-            ds.out_map.assign(size_t(1) << n2, -1);
-            ds.out_scale.assign(size_t(1) << n2, 1.0);
-            for (uint32_t m = 0; m < (1u << n); ++m) {
-                const int g = __builtin_popcount(m);
-                if (!((prod_mask >> g) & 1ULL)) continue;
-                long double f1;
-                const uint32_t R = result_from_frame(adj ? (m ^ adj_z) : m, &f1);
-                const long double factor = f1 / blade_scale(frame, R);
-                const uint32_t sgn = blade_sign[R] ^ (factor < 0.0L ? 1u : 0u);
-                ds.out_map[new_blade[R]] = int32_t(uint32_t(lr.offset(g) + bt.index_of[m]) | (sgn << 30));
-                ds.out_scale[new_blade[R]] = double(fabsl(factor));
-            }
-            // scale tables only when some factor is not 1 (a general metric): +-1 / 0 metrics keep the register-prefetch paths
-            ds.scaled = 0;
-            for (const std::vector<double>* v : {&ds.left_scale, &ds.right_scale, &ds.out_scale})
-                for (double x : *v) ds.scaled |= int(x != 1.0);
-            if (!ds.scaled) {
-                ds.left_scale.clear();
-                ds.right_scale.clear();
-                ds.out_scale.clear();
-            }
-            // every blade produced into a row that holds nothing else: whole rows can be written in 16-byte pieces
-            ds.out_full = lr.row_len == (int64_t(1) << n2);
-            for (uint32_t m = 0; m < (1u << n2); ++m) ds.out_full = ds.out_full && ds.out_map[m] >= 0;
-            for (uint32_t w : ds.left_map) ds.left_signs |= int(w >> 31);
-            for (int32_t w : ds.out_map) ds.out_signs |= int(w >= 0 && (uint32_t(w) & 0x40000000u));
-            const bool mfma32 = fam == DenseFamily::MFMA32 || fam == DenseFamily::MFMA32P;
-            const int lo_bits = mfma32 ? 5 : fam == DenseFamily::MFMA7 ? 3 : fam == DenseFamily::MFMA6 ? 0 : 4;
-            for (int j = 0; j < n2; ++j) {
-                const double g = frame.metric[size_t(perm[size_t(j)])];   // only its sign matters here: the magnitude is in the scales
-                if (j < lo_bits) {
-                    if (g < 0.0) ds.neg_lo |= 1u << j;
-                } else {
-                    if (g < 0.0) ds.neg_hi |= 1u << (j - lo_bits);
-                    if (g == 0.0) ds.zero_hi |= 1u << (j - lo_bits);
-                }
-            }
-            ds.neg_lo_all = fam == DenseFamily::VECTOR_FMA && ds.neg_lo == 15u;
-            ds.degenerate = ds.zero_hi != 0;
-            if (b_quad_planes != (fam == DenseFamily::MFMA32P && n2 == b_planes::kDim && !ds.degenerate)) {   // the launcher picks the kernel by ds.degenerate
-                fail(GAAST_ERR_INVALID_PROGRAM, "B image layout and kernel instantiation disagree");
-                return;
-            }
-            static const char* const par_name[2] = {"even", "odd"};
-            s.name = std::string(fam == DenseFamily::VECTOR_FMA ? "product_dense" : "product_dense_mfma") + "[gp n=" + std::to_string(n) +
-                     (reduced ? std::string(" ") + par_name[frame.lpar] + " x " + par_name[frame.rpar] + " in Cl(" + std::to_string(n2) + ")" : std::string()) +
-                     (identity ? "" : " permuted basis") + (ds.scaled ? " rescaled basis" : "") +
-                     (adj == GAAST_PROD_ADJ_LEFT ? " adjoint left" : adj ? " adjoint right" : "") + "]";
-            touch(res);
+            if (spinor) lower_product_spinor(*this, po);
+            else lower_product_dense(*this, po, choice);
             return;
         }
+        lower_product_list(po);
+    }
 
-        // ---- exact path: CSR by output component, entries in the reference's order ----
+    // ---- exact path: CSR by output component, entries in the reference's order ----
+    void lower_product_list(const ProductOperands& po) {
+        const gaast_node_desc& nd = po.nd;
+        const BufRef res = po.res, l = po.l, r = po.r;
+        const Layout &lr = layout(res), &ll = layout(l), &lrr = layout(r);
+        const uint64_t lmin = po.lmin, rmin = po.rmin, omin = nd.minimal_grade_mask;
+        const uint64_t flip_l = po.flip_l, flip_r = po.flip_r;
         // (a regressive list -- generated here, or explicit and naming its kind -- takes the orientation sign of a Gram basis)
         const bool regressive = nd.product_kind >= 0 && (nd.product_kind & 7) == GAAST_PROD_REGRESSIVE;
         const bool mirror_list = regressive && plan.mirrored;
@@ -1187,7 +558,7 @@ struct Lowering {
         if (n_muls == 0) return;  // nothing is added to res
         if (ll.row_len > 65536 || lrr.row_len > 65536) throw std::runtime_error("operand row too long");
 
-        const bool beta0 = is_fresh;
+        const bool beta0 = po.fresh_zero >= 0;
         // rows: with beta0 every component of the result row gets a row (empty rows write 0.0)
         std::vector<int32_t> row_of(size_t(lr.row_len), -1);
         std::vector<uint32_t> row_out, counts;
@@ -1220,12 +591,12 @@ struct Lowering {
             counts[size_t(row_of[size_t(oo)])]++;
             eo[size_t(e)] = uint32_t(oo);
         }
-        if (beta0) removed[size_t(fr->second)] = 1;
+        if (beta0) removed[size_t(po.fresh_zero)] = 1;
         Step& s = emit(Step::PRODUCT_CSR, res, "product_csr[" + std::to_string(n_muls) + " comp-muls]");
         s.a = l;
         s.b = r;
-        s.canon_a = canon_l;
-        s.canon_b = canon_r;
+        s.canon_a = po.canon_l;
+        s.canon_b = po.canon_r;
         s.beta = beta0 ? 0 : 1;
         s.n_entries = n_muls;
         s.list.row_start.assign(row_out.size() + 1, 0);
@@ -1326,20 +697,12 @@ static void chain_sparse_into_dense(Plan& plan) {
         };
         const int64_t ll = row_len(w.a), rl = row_len(w.b);
         const int n2 = dn.dense.n;
-        // items a workgroup of the dense kernel stages at once (runtime.hip: prepare_dense)
-        int ipb = 1, images_per_item = 4;   // (image counts: +-A, +-B, or A and B)
-        switch (fam) {
-        case DenseFamily::MFMA32:
-        case DenseFamily::MFMA32P:
-            ipb = n2 <= 10 ? 4 : n2 == 11 ? 2 : 1;
-            images_per_item = fam == DenseFamily::MFMA32 ? 2 : 4;
-            break;
-        case DenseFamily::MFMA16X4:
-        case DenseFamily::MFMA7: break;
-        default: ipb = std::max(256, 1 << (n2 - 4)) >> (n2 - 4); images_per_item = 2; break;
-        }
+        // items a workgroup of the dense kernel stages at once and its operand images (dense_images::geometry, which the launcher
+        // fills its launch from too); 256 bytes stand for the kernel's padding and zero words
+        const dense_images::Geometry g = dense_images::geometry(fam, n2, int(elem));
+        const int ipb = g.items;
         const size_t scratch = size_t(ipb) * size_t(ll + rl + 1) * elem;
-        const size_t images = size_t(ipb) * (size_t(images_per_item) << n2) * elem + 256;
+        const size_t images = size_t(ipb) * (size_t(g.images) << n2) * elem + 256;
         if (scratch > 48 * 1024 || images + scratch > kLdsBytes - 1024 || w.list.row_out.size() > 32768) continue;
         // rows of the list -> components of the dense step's left image
         std::vector<int32_t> map_of(size_t(row_len(buf)), -1);

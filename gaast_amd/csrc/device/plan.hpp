@@ -7,6 +7,7 @@
 
 #include "../common/algebra.hpp"
 #include "../common/comp_mul_table.hpp"
+#include "dense_images.hip.hpp"
 #include "explog_adj_series.hip.hpp"
 #include "gaast_hip.h"
 
@@ -37,16 +38,7 @@ inline Layout make_layout(int dim, uint64_t mask) {
     return l;
 }
 
-// which kernel family runs a PRODUCT_DENSE step
-enum class DenseFamily {
-    VECTOR_FMA,  // k_gp_dense<T>
-    MFMA6,       // k_gp_mfma6<T> (n = 6: four 16x16x4 instructions per item, the two top vectors split over the tile's rows and columns)
-    MFMA7,       // k_gp_mfma7<T> (n = 7: lo = 3 bits, the top vector split over the two sides of the 16 x 16 tile)
-    MFMA16X4,    // k_gp_mfma16x4<T> (lo = 4 bits, one item per workgroup): f64 n = 8 ... 12, f32 n = 8, 9
-    MFMA32,      // k_gp_mfma32 (f32, n = 14)
-    MFMA32P,     // k_gp_mfma32p (image-pair form, f32, n = 10 ... 13)
-    SPINOR       // opt-in matrix-representation kernels (GAAST_FLAG_SPINOR_GEMM)
-};
+// (DenseFamily, which kernel family runs a PRODUCT_DENSE step: dense_images.hip.hpp, with the families' operand images)
 
 // One launch of the plan.  What every step has comes first; then one group of fields per step kind (and per rewrite a pass applies to
 // a step in place), each table and setting named after the one thing it holds.  The groups of the other kinds stay empty.  The

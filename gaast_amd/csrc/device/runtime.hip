@@ -812,6 +812,12 @@ int prepare_dense(Launch& L, std::string& kernel) {
         c.whole_rows = kernel_address(static_bools([&](auto ch) -> KernD { return k(Mode<2>{}, std::false_type{}, ch); }, chained && !scaled));
     };
     bool persistent = true;   // as many workgroups as are resident at once (register- and LDS-limited) loop over the items
+    if (s.dense.family != DenseFamily::SPINOR) {   // the workgroup of the family: dense_images.hip.hpp, where the plan builder sizes its chains from too
+        const dense_images::Geometry g = dense_images::geometry(s.dense.family, n, int(sizeof(T)));
+        c.threads = g.threads;
+        c.items_per_block = g.items;
+        c.bytes = g.bytes;
+    }
     switch (s.dense.family) {
     case DenseFamily::SPINOR: {
         using KernS = void (*)(SpinorArgs);
@@ -838,11 +844,7 @@ int prepare_dense(Launch& L, std::string& kernel) {
     case DenseFamily::MFMA32:
     case DenseFamily::MFMA32P:
         if constexpr (!is_f64) {
-            const int wpi = 1 << (n - 10);                 // waves per item
-            c.threads = wpi > 4 ? wpi * 64 : 256;
-            c.items_per_block = (c.threads / 64) / wpi;
             const bool image_pairs = s.dense.family == DenseFamily::MFMA32P;
-            c.bytes = (image_pairs ? size_t(c.items_per_block) * size_t(4 << n) + 16 : size_t(c.items_per_block) * size_t(2 << n)) * sizeof(float);
             if (c.bytes > g_max_lds) return set_err(GAAST_ERR_UNIMPLEMENTED, "dense product does not fit in LDS");
             if (image_pairs) {
                 c.general = kernel_address(static_bools([&](auto dgn, auto sc, auto ch) -> KernD {
@@ -864,10 +866,6 @@ int prepare_dense(Launch& L, std::string& kernel) {
         }
         [[fallthrough]];   // (f64 has no such kernel)
     case DenseFamily::VECTOR_FMA: {
-        const int lpi = 1 << (n - 4);
-        c.threads = lpi > 256 ? lpi : 256;
-        c.items_per_block = c.threads / lpi;
-        c.bytes = size_t(c.items_per_block) * size_t(2 * (1 << n) + (c.items_per_block > 1 ? 4 : 0)) * sizeof(T);
         if (c.bytes > g_max_lds)
             return set_err(GAAST_ERR_UNIMPLEMENTED, "dense product of dimension " + std::to_string(n) + " does not fit in LDS");
         c.general = kernel_address(static_bools([](auto dgn, auto wide, auto neglo, auto sc, auto ch) -> KernD {
@@ -880,9 +878,6 @@ int prepare_dense(Launch& L, std::string& kernel) {
         // k_gp_mfma16x4<T, DEG, n, MODE, SC, CH>: one wave per 16 result columns, one item per workgroup.  f64 runs n = 8 ... 12 on
         // it, f32 only n = 8, 9 (f32 at n >= 10 is k_gp_mfma32p's): the f32 instantiations for n = 10 ... 12 would be unreachable,
         // so they are not built.
-        c.threads = 64 << (n - 8);
-        c.items_per_block = 1;
-        c.bytes = size_t(4 * (size_t(1) << n) + 32) * sizeof(T);   // +B, -B, +A, 16 spare, -A images, 16 zeros
         if (c.bytes > g_max_lds) return set_err(GAAST_ERR_UNIMPLEMENTED, "dense product does not fit in LDS");
         staging_modes([&](auto mode, auto sc, auto ch) -> KernD {
             auto of_n = [&](auto nn) -> KernD {
@@ -899,9 +894,6 @@ int prepare_dense(Launch& L, std::string& kernel) {
     }
     case DenseFamily::MFMA6: {
         // k_gp_mfma6<T>: one wave per item, persistent single-wave workgroups, 2 KiB (f32) / 4 KiB (f64) of operand images
-        c.threads = 64 * GAAST_MFMA6_WAVES;
-        c.items_per_block = GAAST_MFMA6_WAVES;
-        c.bytes = (size_t(is_f64 ? 4096 : 2048) + 64 * sizeof(T)) * GAAST_MFMA6_WAVES;   // + a dummy element per lane (stores of vanishing slots)
         // general: any operands (partial grade sets, projected or accumulated results); prefetch: full operands, every blade produced,
         // nothing accumulated -- straight-line item loop with counted waits
         auto k6 = [](auto sc, auto straight) -> KernD { return &k_gp_mfma6<T, decltype(sc)::value, decltype(straight)::value>; };
@@ -912,9 +904,6 @@ int prepare_dense(Launch& L, std::string& kernel) {
     }
     case DenseFamily::MFMA7: {
         // k_gp_mfma7<T>: one wave per item, persistent single-wave workgroups
-        c.threads = 64;
-        c.items_per_block = 1;
-        c.bytes = size_t(560) * sizeof(T);   // +B, -B, +A (u = 1 half 72 further), -A 144 further, 16 zeros
         staging_modes([](auto mode, auto sc, auto ch) -> KernD { return &k_gp_mfma7<T, decltype(mode)::value, decltype(sc)::value, decltype(ch)::value>; });
         kernel = "k_gp_mfma7<" + tn + (scaled ? ",0" + vs + ">" : ",0|1|2" + vs + ">");   // (null vectors: run-time, no instantiation of their own)
         break;
@@ -926,8 +915,8 @@ int prepare_dense(Launch& L, std::string& kernel) {
         const size_t items = size_t(c.items_per_block > 0 ? c.items_per_block : 1);
         // + the zero pair; the one-item matrix kernels keep the list's right row twice (+x, -x: a term's sign is an address)
         c.bytes = c.pre_scratch_bytes + (items * size_t(s.pre.left_len + s.pre.right_len + 1) + (items == 1 ? size_t(s.pre.right_len) : 0)) * sizeof(T);
-        // The plan builder sizes a chain's LDS with its own estimate of the kernel's images; this is the real figure, checked
-        // against the device.  On a mismatch gaast_hip_program_create rebuilds the program without chains.
+        // The plan builder sizes a chain from the same geometry, against the LDS this back end is built for; the device's own limit is
+        // only known here.  Beyond it gaast_hip_program_create rebuilds the program without chains.
         if (c.bytes > g_max_lds) return set_err(kChainTooBig, "chained product does not fit in LDS (" + s.name + ")");
     }
     for (const void* kern : {c.general, c.prefetch, c.whole_rows, c.spinor_fast})

@@ -120,13 +120,6 @@ static void header_invariants(uint32_t neg_hi, const char* what) {
     std::printf("%s  header invariants (%s)\n", failures ? "FAILED" : "ok", what);
 }
 
-static uint32_t old_block_pos(uint32_t m) {   // plan.cpp: mfma32p_b_pos, the image of every other instantiation
-    static const int word_of_s[16] = {0, 8, 9, 1, 10, 2, 3, 11, 12, 4, 5, 13, 6, 14, 15, 7};
-    const uint32_t x = m >> 5, k = m & 31, w = uint32_t(word_of_s[k >> 1]);
-    const uint32_t lq = ((k & 1) << 2) | (w >> 2);
-    return (x << 5) | (((lq ^ (x >> 1)) & 7) << 2) | (w & 3);
-}
-
 static void plan_images_multiply_right(const double* metric, bool expect_planes, const char* what) {
     const int n = 12;
     const uint64_t full = (uint64_t(2) << n) - 1;
@@ -149,7 +142,7 @@ static void plan_images_multiply_right(const double* metric, bool expect_planes,
             const uint32_t N = 1u << n;
             CHECK(ds.left_map.size() == N && ds.right_map.size() == N && !ds.scaled);
             std::vector<int> inv(N, -1);
-            for (uint32_t m = 0; m < N; ++m) inv[expect_planes ? bp::pos(m) : old_block_pos(m)] = int(m);
+            for (uint32_t m = 0; m < N; ++m) inv[expect_planes ? bp::pos(m) : gaast::dense_images::mfma32p_b_pos(m)] = int(m);   // (the block image of every other instantiation)
             // images as the staging writes them (+ image; the - image is its negation), exact small integers
             std::vector<double> lrow(N), rrow(N), Aimg(N, 0.0), Bimg(N, 0.0), Bblade(N, 0.0);
             uint64_t x = 88172645463325252ULL;

@@ -3,13 +3,14 @@
 // to them -- into the directory argv[1], one file per (case, step, artifact).  tests/test_codegen_digests.py compares length and
 // SHA-256 of each file with tests/golden/codegen_digests.json: the strings are what the runtime compiles and what the compiled-code
 // cache is keyed by, so equal bytes mean equal results, speed and cache behaviour.  Reads only plan.hpp fields, calls only
-// build_plan.  One line per step on stdout (the test checks from them that the corpus still reaches every form).
+// build_plan (and gaast_program_vjp for the adjoint programs).  One line per step on stdout (the test checks from them that the corpus still reaches every form).
 // Build: g++ -std=c++17 -O1 -I include -I gaast_amd/csrc/device -I gaast_amd/csrc/common -I gaast_amd/csrc/host
-//        tests/cpp/codegen_dump_driver.cpp gaast_amd/csrc/host/{expr,c_api_host,wire}.cpp gaast_amd/csrc/device/plan*.cpp
+//        tests/cpp/codegen_dump_driver.cpp gaast_amd/csrc/host/{expr,c_api_host,wire,vjp}.cpp gaast_amd/csrc/device/plan*.cpp
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "gaast_expr.h"
@@ -34,24 +35,68 @@ static void put(const std::string& stem, const char* artifact, const std::string
 template <typename V>
 static void put_vec(const std::string& stem, const char* artifact, const std::vector<V>& v) { put(stem, artifact, v.data(), v.size() * sizeof(V)); }
 
-// small_reg_slab: what runtime.hip passes when it rebuilds a plan whose one-item-per-thread trial compilation used too many registers
-static void dump(const char* what, gaast_expr_t e, int n, const std::vector<double>& metric, int dtype, uint32_t flags, bool small_reg_slab = false) {
-    gaast_spec_t spec = gaast_expr_specialize(e, n, metric.data(), uint64_t(1) << 22);
-    if (!spec) {
-        std::printf("%s: specialization failed\n", what);
-        g_fail = 1;
-        return;
+static std::string ref_text(gaast::BufRef r) { return std::to_string(int(r.kind)) + ":" + std::to_string(r.idx); }
+static const char* const kFamily[] = {"VECTOR_FMA", "MFMA6", "MFMA7", "MFMA16X4", "MFMA32", "MFMA32P", "SPINOR"};
+
+// every table and every scalar field of a product step (Step::Dense, Step::Pre under a chain, Step::List)
+static void put_product(const std::string& stem, const gaast::Step& s) {
+    const std::string common = "beta " + std::to_string(s.beta) + " canon_a " + std::to_string(s.canon_a) + " canon_b " + std::to_string(s.canon_b) + " a " + ref_text(s.a) +
+                               " b " + ref_text(s.b) + " n_entries " + std::to_string(s.n_entries) + "\n";
+    if (s.kind == gaast::Step::PRODUCT_DENSE) {
+        const gaast::Step::Dense& q = s.dense;
+        put_vec(stem, "dense_left_map", q.left_map);
+        put_vec(stem, "dense_right_map", q.right_map);
+        put_vec(stem, "dense_out_map", q.out_map);
+        put_vec(stem, "dense_spinor_out_map", q.spinor_out_map);
+        put_vec(stem, "dense_left_scale", q.left_scale);
+        put_vec(stem, "dense_right_scale", q.right_scale);
+        put_vec(stem, "dense_out_scale", q.out_scale);
+        std::string sc = common + "family " + kFamily[int(q.family)] + " n " + std::to_string(q.n) + " scaled " + std::to_string(q.scaled) + " left_full " +
+                         std::to_string(q.left_full) + " right_full " + std::to_string(q.right_full) + " out_full " + std::to_string(q.out_full) + " left_contig " +
+                         std::to_string(q.left_contig) + " right_contig " + std::to_string(q.right_contig) + " left_signs " + std::to_string(q.left_signs) +
+                         " out_signs " + std::to_string(q.out_signs) + "\nneg_hi " + std::to_string(q.neg_hi) + " zero_hi " + std::to_string(q.zero_hi) + " neg_lo " +
+                         std::to_string(q.neg_lo) + " neg_lo_all " + std::to_string(q.neg_lo_all) + " degenerate " + std::to_string(q.degenerate) + " mfma16_quads " +
+                         std::to_string(q.mfma16_quads) + " spinor_lam_bit " + std::to_string(q.spinor_lam_bit) + " spinor_has_alpha " +
+                         std::to_string(q.spinor_has_alpha) + " spinor_m " + std::to_string(q.spinor_m) + " chained " + std::to_string(q.chained) + "\n";
+        put(stem, "dense_scalars", sc);
+        std::printf(" | DENSE family=%s n=%d full=%d%d contig=%d%d scaled=%d degenerate=%d neg_lo_all=%d quads=%d chained=%d row_scale=%d", kFamily[int(q.family)], q.n,
+                    q.left_full, q.right_full, q.left_contig, q.right_contig, q.scaled, q.degenerate, q.neg_lo_all, q.mfma16_quads, q.chained, s.pre.row_scale.empty() ? 0 : 1);
+        if (q.chained) {
+            const gaast::Step::Pre& r = s.pre;
+            put_vec(stem, "pre_row_start", r.row_start);
+            put_vec(stem, "pre_entries", r.entries);
+            put_vec(stem, "pre_coeff", r.coeff);
+            put_vec(stem, "pre_row_map", r.row_map);
+            put_vec(stem, "pre_row_scale", r.row_scale);
+            put(stem, "pre_scalars", "a " + ref_text(r.a) + " b " + ref_text(r.b) + " canon_a " + std::to_string(r.canon_a) + " canon_b " + std::to_string(r.canon_b) +
+                                         " left_len " + std::to_string(r.left_len) + " right_len " + std::to_string(r.right_len) + " width " + std::to_string(r.width) + "\n");
+        }
     }
-    gaast_program_desc desc;
-    gaast_spec_program_desc(spec, dtype, flags, &desc);
+    if (s.kind == gaast::Step::PRODUCT_CSR) {
+        const gaast::Step::List& q = s.list;
+        put_vec(stem, "list_row_start", q.row_start);
+        put_vec(stem, "list_row_out", q.row_out);
+        put_vec(stem, "list_entries", q.entries);
+        put_vec(stem, "list_coeff", q.coeff);
+        put(stem, "list_scalars", common + "ell_width " + std::to_string(q.ell_width) + " ell_bytes " + std::to_string(q.ell_bytes) + "\n");
+        size_t empty = 0;
+        for (size_t r = 0; r + 1 < q.row_start.size(); ++r) empty += q.row_start[r + 1] == q.row_start[r];
+        std::printf(" | LIST beta=%d rows=%zu empty_rows=%zu ell=%d", s.beta, q.row_out.size(), empty, q.ell_width);
+    }
+}
+
+// small_reg_slab: what runtime.hip passes when it rebuilds a plan whose one-item-per-thread trial compilation used too many registers;
+// mirrored: the orthogonal basis of a Gram metric whose Q has det -1
+static void dump_desc(const char* what, const gaast_program_desc& desc, bool small_reg_slab = false, bool mirrored = false) {
     gaast::Plan plan;
-    gaast::build_plan(desc, plan, small_reg_slab);
+    gaast::build_plan(desc, plan, small_reg_slab, mirrored);
     if (plan.steps.empty()) std::printf("%s: no steps\n", what);
     for (size_t k = 0; k < plan.steps.size(); ++k) {
         const gaast::Step& s = plan.steps[k];
         const std::string stem = std::string(what) + ".s" + std::to_string(k);
         put(stem, "name", s.name);
         std::printf("%s s%zu %s", what, k, s.name.c_str());
+        put_product(stem, s);
         if (s.kind == gaast::Step::FUSED) {
             const gaast::Step::Fused& f = s.fused;
             put(stem, "fused_jit_source", f.jit_source);
@@ -85,7 +130,34 @@ static void dump(const char* what, gaast_expr_t e, int n, const std::vector<doub
         }
         std::printf("\n");
     }
+}
+
+static void dump(const char* what, gaast_expr_t e, int n, const std::vector<double>& metric, int dtype, uint32_t flags, bool small_reg_slab = false, bool mirrored = false) {
+    gaast_spec_t spec = gaast_expr_specialize(e, n, metric.data(), uint64_t(1) << 22);
+    if (!spec) {
+        std::printf("%s: specialization failed: %s\n", what, gaast_expr_last_error());
+        g_fail = 1;
+        return;
+    }
+    gaast_program_desc desc;
+    gaast_spec_program_desc(spec, dtype, flags, &desc);
+    dump_desc(what, desc, small_reg_slab, mirrored);
     gaast_spec_free(spec);
+}
+
+// the reverse-mode program of `e` with respect to input `wrt` (gaast_program_vjp): adjoint product nodes
+static void dump_vjp(const char* what, gaast_expr_t e, int n, const std::vector<double>& metric, int dtype, uint32_t flags, int wrt) {
+    gaast_spec_t spec = gaast_expr_specialize(e, n, metric.data(), uint64_t(1) << 22);
+    gaast_program_desc desc;
+    gaast_program_image_t img = nullptr;
+    if (!spec || gaast_spec_program_desc(spec, dtype, flags, &desc) != 0 || gaast_program_vjp(&desc, wrt, &img) != 0 || !img) {
+        std::printf("%s: no reverse-mode program\n", what);
+        g_fail = 1;
+    } else {
+        dump_desc(what, *gaast_program_image_desc(img));
+        gaast_program_image_free(img);
+    }
+    if (spec) gaast_spec_free(spec);
 }
 
 static gaast_expr_t sandwich(int n, uint64_t rmask = 0) {
@@ -208,5 +280,62 @@ int main(int argc, char** argv) {
             for (int n : {8, 12})      // a single list, the covering copy folded in
                 dump(("cfg1_" + std::to_string(n) + tag).c_str(), cfg1(n), n, euclid(n), dtype, flags);
         }
+
+    // ---- the product lowering: every dense kernel family and every branch of its operand images, the matrix-representation tables,
+    // chained products and the exact list (tests/test_codegen_digests.py: test_corpus_reaches_every_branch_of_the_product_lowering)
+    const uint32_t NO_MFMA = GAAST_FLAG_NO_MFMA, SPINOR = GAAST_FLAG_SPINOR_GEMM;
+    auto with = [&](int n, std::initializer_list<std::pair<int, double>> entries) {
+        std::vector<double> m = euclid(n);
+        for (const auto& e : entries) m[size_t(e.first)] = e.second;
+        return m;
+    };
+    auto full = [](int n) { return gp(n, full_mask(n), full_mask(n)); };
+    const uint64_t odd8 = full_mask(8) & ~even_mask(8);
+    const std::vector<double> primes8{2, 3, 5, 7, 11, 13, 17, 19}, null8 = with(8, {{7, 0.0}});
+    for (int dtype : {GAAST_F32, GAAST_F64}) {
+        const std::string t = dtype == GAAST_F32 ? "_f32" : "_f64";
+        dump(("dense_vf8" + t).c_str(), full(8), 8, euclid(8), dtype, NO_MFMA);                          // VECTOR_FMA
+        dump(("dense_gp6" + t).c_str(), full(6), 6, euclid(6), dtype, 0);                                // MFMA6, entries dealt to lanes
+        dump(("dense_gp6_partial" + t).c_str(), gp(6, full_mask(6), even_mask(6)), 6, euclid(6), dtype, 0);
+        dump(("dense_gp7" + t).c_str(), full(7), 7, euclid(7), dtype, 0);                                // MFMA7, entries dealt by bank
+        dump(("dense_gp7_partial" + t).c_str(), gp(7, full_mask(7), even_mask(7)), 7, euclid(7), dtype, 0);
+        dump(("dense_gp8" + t).c_str(), full(8), 8, euclid(8), dtype, 0);                                // MFMA16X4: f64 B image / f32 quad image
+        dump(("dense_gp8_null" + t).c_str(), full(8), 8, null8, dtype, 0);
+        for (int n : {8, 9})                                                                              // R X ~R: the list R X in the dense kernel's LDS
+            dump(("dense_sandwich" + std::to_string(n) + t).c_str(), sandwich(n), n, euclid(n), dtype, 0);
+    }
+    dump("dense_sandwich8_primes_f32", sandwich(8), 8, primes8, GAAST_F32, 0);                            // ... on a rescaled basis: row_scale
+    dump("dense_vf8_neglo_f32", full(8), 8, with(8, {{0, -1.0}, {1, -1.0}, {2, -1.0}, {3, -1.0}, {7, -1.0}}), GAAST_F32, NO_MFMA);   // all four lo vectors negative
+    dump("dense_vf8_permuted_f32", full(8), 8, with(8, {{0, -1.0}}), GAAST_F32, NO_MFMA);               // the identity basis does not qualify
+    dump("dense_gp10_f32", full(10), 10, euclid(10), GAAST_F32, 0);                                      // MFMA32P, block image
+    dump("dense_gp12_f32", full(12), 12, euclid(12), GAAST_F32, 0);                                      // ... quad-plane image
+    dump("dense_gp12_null_f32", full(12), 12, with(12, {{11, 0.0}}), GAAST_F32, 0);                      // ... a null hi vector: block image, degenerate
+    dump("dense_gp14_f32", full(14), 14, euclid(14), GAAST_F32, 0);                                      // MFMA32
+    dump("dense_ee8_f32", gp(8, even_mask(8), even_mask(8)), 8, euclid(8), GAAST_F32, 0);                // parity-pure operands: one product in Cl(7)
+    dump("dense_oe8_f32", gp(8, odd8, even_mask(8)), 8, euclid(8), GAAST_F32, 0);
+    dump("dense_eo8_f32", gp(8, even_mask(8), odd8), 8, euclid(8), GAAST_F32, 0);
+    dump("dense_oo8_f32", gp(8, odd8, odd8), 8, euclid(8), GAAST_F32, 0);
+    dump("dense_oe8_pivot2_f32", gp(8, odd8, even_mask(8)), 8, with(8, {{7, 2.0}}), GAAST_F32, 0);       // a pivot that squares to 2
+    dump("dense_oo8_pivot2_f64", gp(8, odd8, odd8), 8, with(8, {{7, 2.0}}), GAAST_F64, 0);
+    dump("dense_gp8_primes_f32", full(8), 8, primes8, GAAST_F32, 0);                                     // rescaled basis
+    dump("dense_gp8_primes_f64", full(8), 8, primes8, GAAST_F64, 0);
+    dump("dense_gp8_negfirst_f32", full(8), 8, with(8, {{0, -1.0}, {1, -1.0}}), GAAST_F32, 0);           // negative vectors first
+    for (int wrt : {0, 1}) {                                                                              // adjoints of a geometric product
+        const std::string w = wrt ? "_right" : "_left";
+        dump_vjp(("dense_adj8" + w + "_f32").c_str(), full(8), 8, euclid(8), GAAST_F32, 0, wrt);
+        dump_vjp(("dense_adj8_null" + w + "_f32").c_str(), full(8), 8, null8, GAAST_F32, 0, wrt);
+        dump_vjp(("dense_adj8_primes" + w + "_f64").c_str(), full(8), 8, primes8, GAAST_F64, 0, wrt);
+    }
+    dump("spinor8_f32", full(8), 8, euclid(8), GAAST_F32, SPINOR);
+    dump("spinor7_f32", full(7), 7, euclid(7), GAAST_F32, SPINOR);                                        // padded to n + 1
+    dump("spinor8_neg_f32", full(8), 8, with(8, {{2, -1.0}}), GAAST_F32, SPINOR);
+    {   // the exact list: a fresh result; one whose buffer holds a grade only the NEXT arm fills (rows nothing is added to; an accumulated
+        // list: cfg1_* above); the orientation sign of a mirrored Gram basis on a regressive list; a compact adjoint no dense kernel takes
+        gaast_expr_t a = gaast_expr_input(0, 0x4, 12), b = gaast_expr_input(1, full_mask(12), 12), c = gaast_expr_input(2, full_mask(11), 12);
+        dump("list_fresh12_null_f64", gaast_expr_product(a, b, GAAST_PROD_INNER), 12, with(12, {{11, 0.0}}), GAAST_F64, 0);
+        dump("list_fresh12_empty_rows_f32", gaast_expr_add(gaast_expr_product(a, b, GAAST_PROD_INNER), c), 12, euclid(12), GAAST_F32, 0);
+        dump("list_regressive12_mirrored_f64", gaast_expr_product(b, gaast_expr_input(3, uint64_t(3) << 10, 12), GAAST_PROD_REGRESSIVE), 12, euclid(12), GAAST_F64, 0, false, true);
+        dump_vjp("list_adj8_exact_f32", full(8), 8, euclid(8), GAAST_F32, EXACT, 0);
+    }
     return g_fail;
 }

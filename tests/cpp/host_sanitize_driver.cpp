@@ -75,47 +75,15 @@ static void lower(gaast_expr_t e, int n, const double* metric, int dtype, uint32
 // What the dense kernels compute, restated from the step's tables alone (operand maps with image positions and
 // negate bits, out_map with its sign bit, neg_lo / neg_hi / zero_hi of the PERMUTED basis), compared with the
 // reference's own comp-mul list for the same product.  Checks the host half of the basis permutation
-// (plan.cpp: dense_basis_permutation): blade bijection, reordering signs, permuted metric masks.
-static uint32_t vec_pos(uint32_t m) {
-    const uint32_t x = m >> 4, lo = m & 15;
-    return (x << 4) | ((((lo >> 2) ^ (x >> 2)) & 3) << 2) | (lo & 3);
-}
-static uint32_t mfma_b_pos(uint32_t m) {
-    const uint32_t x = m >> 5, k = m & 31;
-    const uint32_t lq = ((k & 1) << 2) | (k >> 3);
-    return (x << 5) | (((lq ^ (x >> 1)) & 7) << 2) | ((k >> 1) & 3);
-}
-
-// k_gp_mfma32p's B image (plan.cpp: mfma32p_b_pos)
-static uint32_t mfma32p_b_pos(uint32_t m) {
-    static const int word_of_s[16] = {0, 8, 9, 1, 10, 2, 3, 11, 12, 4, 5, 13, 6, 14, 15, 7};
-    const uint32_t x = m >> 5, k = m & 31, w = uint32_t(word_of_s[k >> 1]);
-    const uint32_t lq = ((k & 1) << 2) | (w >> 2);
-    return (x << 5) | (((lq ^ (x >> 1)) & 7) << 2) | (w & 3);
-}
-
-// k_gp_mfma16d's B image (f64; plan.cpp: mfma16d_b_pos)
-static uint32_t mfma16d_b_pos(uint32_t m) {
-    const uint32_t x = m >> 4, k = m & 15u;
-    return (x << 4) | (k ^ (((x >> 1) & 7u) << 1));
-}
-
-// k_gp_mfma16x4<float>'s B image (plan.cpp: mfma16q_b_pos)
-static uint32_t mfma16q_b_pos(uint32_t m) {
-    static const int kq_of[16] = {0, 2, 2, 0, 2, 0, 0, 2, 3, 1, 1, 3, 1, 3, 3, 1};
-    static const int s_of[16] = {0, 0, 1, 1, 2, 2, 3, 3, 0, 0, 1, 1, 2, 2, 3, 3};
-    const uint32_t x = m >> 4, k = m & 15u;
-    return (x << 4) | (uint32_t(kq_of[k] ^ int(((x >> 2) & 1u) << 1)) << 2) | uint32_t(s_of[k]);
-}
-
-// k_gp_mfma7's images (plan.cpp: mfma7_a_pos / mfma7_b_pos)
-static uint32_t mfma7_a_pos(uint32_t m) { return (m & 63u) + (m >> 6) * 72u; }
-static uint32_t mfma7_b_pos(uint32_t m) {
-    static const int kq_of[8] = {0, 2, 2, 0, 3, 1, 1, 3};
-    static const int s_of[8] = {0, 0, 1, 1, 0, 0, 1, 1};
-    const uint32_t v = m >> 6, bh = (m >> 3) & 7u, k = m & 7u;
-    return ((uint32_t(kq_of[k]) * 16u + v * 8u + bh) << 1) | uint32_t(s_of[k]);
-}
+// (plan_dense.cpp: dense_basis_permutation): blade bijection, reordering signs, permuted metric masks.
+// (where a blade sits inside an operand image: dense_images.hip.hpp, checked on its own by tests/cpp/dense_images_driver.cpp)
+using gaast::dense_images::mfma16d_b_pos;
+using gaast::dense_images::mfma16q_b_pos;
+using gaast::dense_images::mfma32_b_pos;
+using gaast::dense_images::mfma32p_b_pos;
+using gaast::dense_images::mfma7_a_pos;
+using gaast::dense_images::mfma7_b_pos;
+using gaast::dense_images::vec_pos;
 
 static void dense_tables_agree_with_the_list(int n, const double* metric, int dtype, uint32_t flags, const char* what,
                                              const char* expect_step, uint64_t lmask = 0, uint64_t rmask = 0) {
@@ -158,7 +126,7 @@ static void dense_tables_agree_with_the_list(int n, const double* metric, int dt
     for (uint32_t m = 0; m < N; ++m) inv_vec[vec_pos(m)] = m;
     if (fam == DenseFamily::MFMA7) for (uint32_t m = 0; m < N; ++m) { inv_b[mfma7_b_pos(m)] = m; inv_a7[mfma7_a_pos(m)] = m; }
     else if (fam == DenseFamily::MFMA32P) for (uint32_t m = 0; m < N; ++m) inv_b[mfma32p_b_pos(m)] = m;
-    else if (fam == DenseFamily::MFMA32) for (uint32_t m = 0; m < N; ++m) inv_b[mfma_b_pos(m)] = m;
+    else if (fam == DenseFamily::MFMA32) for (uint32_t m = 0; m < N; ++m) inv_b[mfma32_b_pos(m)] = m;
     else if (st->dense.mfma16_quads) for (uint32_t m = 0; m < N; ++m) inv_b[mfma16q_b_pos(m)] = m;
     else if (fam == DenseFamily::MFMA16X4) for (uint32_t m = 0; m < N; ++m) inv_b[mfma16d_b_pos(m)] = m;
     // a general diagonal metric: the step carries w_S per loaded component (left_scale / right_scale) and 1 / w_T per permuted blade
@@ -678,7 +646,7 @@ int main(int argc, char** argv) {
         dense_tables_agree_with_the_list(8, mix8, GAAST_F64, 0, "parity-pure n=8 -> mfma7 even x odd", "even x odd in Cl(7)", 0x155, 0x0aa);
         dense_tables_agree_with_the_list(10, gen10, GAAST_F32, 0, "mfma32p tables n=10 general metric", "rescaled basis");
         dense_tables_agree_with_the_list(10, gen10, GAAST_F64, 0, "mfma16x4 f64 tables n=10 general metric", "rescaled basis");
-        // parity-pure operands: one product in the even subalgebra Cl(n - 1) (plan.cpp: parity_reduced_frame), all four
+        // parity-pure operands: one product in the even subalgebra Cl(n - 1) (plan_dense.cpp: parity_reduced_frame), all four
         // parity cases, Euclidean / mixed / degenerate / general metrics, the pivot not always the last vector
         const uint64_t EV = 0x5555555555555555ULL, OD = 0xAAAAAAAAAAAAAAAAULL;
         const double mix9[9] = {1, -1, 1, 1, -1, 1, -1, 1, -1};

@@ -10,10 +10,20 @@ and then specialised / evaluated by both.
 """
 from __future__ import annotations
 
+import glob
+import os
+
 import numpy as np
 
 import gaast_amd as ga
 from oracle import pyoracle as og
+
+
+def plan_sources(csrc):
+    """The host sources a stand-alone C++ driver links to call gaast::build_plan: the host side (expression, C API, wire format,
+    reverse mode) and every translation unit of the plan builder, device/plan*.cpp in sorted order (as csrc/Makefile lists them)."""
+    host = [os.path.join(csrc, "host", f) for f in ("expr.cpp", "c_api_host.cpp", "wire.cpp", "vjp.cpp")]
+    return host + sorted(glob.glob(os.path.join(csrc, "device", "plan*.cpp")))
 
 
 def n_choose_k(n, k):

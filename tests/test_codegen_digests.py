@@ -1,11 +1,11 @@
 """The plan builder's generated code, pinned byte for byte -- CPU only, no HIP.
 
 tests/cpp/codegen_dump_driver.cpp lowers a fixed corpus with gaast::build_plan and writes every generated artifact of every step:
-the hiprtc sources of gaast_jit (slab in registers / slabs in LDS) and gaast_chain, the k_ast_fused micro-op stream, and the tables
-and settings built next to them.  Length and SHA-256 of each must equal tests/golden/codegen_digests.json (recorded by
+the hiprtc sources of gaast_jit (slab in registers / slabs in LDS) and gaast_chain, the k_ast_fused micro-op stream, the tables
+and settings built next to them, and every table and setting of every product step (the dense kernels' operand maps, result maps and
+scales, the lists chained into them, the exact lists).  Length and SHA-256 of each must equal tests/golden/codegen_digests.json (recorded by
 tools/record_codegen_digests.py BEFORE a change to the generators).  The runtime compiles these strings and keys its compiled-code
-cache by their hash: equal bytes are equal kernels."""
-import glob
+cache by their hash, and uploads these tables as they are: equal bytes are equal kernels on equal operand images."""
 import hashlib
 import json
 import os
@@ -13,6 +13,8 @@ import re
 import subprocess
 
 import pytest
+
+from helpers import plan_sources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "codegen_digests.json")
@@ -50,8 +52,7 @@ def build_and_run(csrc, out_dir, exe):
     cmd = ["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"),
            "-I", os.path.join(csrc, "device"), "-I", os.path.join(csrc, "common"), "-I", os.path.join(csrc, "host"),
            os.path.join(ROOT, "tests", "cpp", "codegen_dump_driver.cpp")]
-    cmd += [os.path.join(csrc, f) for f in ("host/expr.cpp", "host/c_api_host.cpp", "host/wire.cpp")]
-    cmd += sorted(glob.glob(os.path.join(csrc, "device", "plan*.cpp")))
+    cmd += plan_sources(csrc)
     subprocess.run(cmd + ["-o", str(exe)], check=True)
     os.makedirs(out_dir, exist_ok=True)
     run = subprocess.run([str(exe), str(out_dir)], capture_output=True, text=True)
@@ -101,3 +102,74 @@ def test_corpus_reaches_every_form_of_the_generators(dumped):
                 sources.append(f.read())
     missing = [form for form, mark in JIT_FORMS.items() if not any(mark in s for s in sources)]
     assert not missing, missing
+
+
+def test_corpus_reaches_every_branch_of_the_product_lowering(dumped):
+    """Every dense kernel family with every branch of its operand-image and step-field code, the matrix-representation tables, chained
+    products and the exact list: the set of (family, branch) pairs the corpus reaches is complete."""
+    _, stdout, _ = dumped
+    reached = set()
+    for line in stdout.splitlines():
+        case, name = line.split(" ", 1)[0], line.split(" | ")[0]
+        m = re.search(r"DENSE family=(\w+) n=(\d+) full=(\d)(\d) contig=(\d)(\d) scaled=(\d) degenerate=(\d) neg_lo_all=(\d) quads=(\d) chained=(\d) row_scale=(\d)", line)
+        if m:
+            fam, n = m.group(1), int(m.group(2))
+            lfull, rfull, lcontig, rcontig, scaled, degenerate, neg_lo_all, quads, chained, row_scale = (int(x) for x in m.groups()[2:])
+            dt = "f64" if "_f64" in case else "f32"
+            dealt = lfull and rfull and not lcontig and not rcontig      # the bank-dealing passes run on full operands only
+            reached.add((fam, dt))
+            if fam in ("MFMA6", "MFMA7") and not chained:
+                reached.add((fam, dt, "dealt" if dealt else "row order"))
+            if fam == "VECTOR_FMA":
+                reached.add((fam, "neg_lo_all" if neg_lo_all else "permuted basis" if "permuted basis" in name else "plain"))
+            if fam == "MFMA16X4":
+                reached.add((fam, "quad image" if quads else "f64 image"))
+                assert quads == (dt == "f32"), line
+            if fam in ("MFMA32P", "MFMA32"):
+                reached.add((fam, n, "degenerate" if degenerate else "quad planes" if fam == "MFMA32P" and n == 12 else "block image"))
+            par = re.search(r"(even|odd) x (even|odd) in Cl\((\d+)\)", name)
+            if par and not chained:
+                reached.add(("parity", par.group(1), par.group(2)))
+                if scaled:
+                    reached.add(("parity", "pivot not +-1"))
+            if not par and not chained and "adjoint" not in name:
+                for tag in ("rescaled basis", "permuted basis"):
+                    if tag in name:
+                        reached.add(("metric", tag))
+                if degenerate:
+                    reached.add(("metric", "null vector"))
+            adj = re.search(r"adjoint (left|right)", name)
+            if adj:
+                reached.add(("adjoint", adj.group(1)))
+                if degenerate:
+                    reached.add(("adjoint", "null vector"))
+            if chained:
+                assert line.split(" | ")[0].endswith("in LDS"), line
+                reached.add(("chained", n + (1 if par else 0), dt))
+                if row_scale:
+                    reached.add(("chained", "row_scale"))
+            if fam == "SPINOR":
+                reached.add(("SPINOR", "padded" if case.startswith("spinor7") else "negative vector" if "_neg_" in case else "n = 8"))
+        m = re.search(r"LIST beta=(\d) rows=(\d+) empty_rows=(\d+) ell=(\d+)", line)
+        if m and case.startswith(("list_", "cfg1_")):
+            beta, _, empty_rows, _ = (int(x) for x in m.groups())
+            reached.add(("list", "accumulated" if beta else "fresh, empty rows" if empty_rows else "fresh"))
+            if "mirrored" in case:
+                reached.add(("list", "regressive, mirrored"))
+            if case.startswith("list_adj"):
+                reached.add(("list", "compact adjoint, exact order"))
+    want = {("VECTOR_FMA", "f32"), ("VECTOR_FMA", "f64"), ("VECTOR_FMA", "plain"), ("VECTOR_FMA", "neg_lo_all"), ("VECTOR_FMA", "permuted basis"),
+            ("MFMA16X4", "f32"), ("MFMA16X4", "f64"), ("MFMA16X4", "quad image"), ("MFMA16X4", "f64 image"),
+            ("MFMA32P", "f32"), ("MFMA32", "f32"), ("MFMA32P", 10, "block image"), ("MFMA32P", 12, "quad planes"), ("MFMA32P", 12, "degenerate"),
+            ("MFMA32", 14, "block image"),
+            ("metric", "rescaled basis"), ("metric", "permuted basis"), ("metric", "null vector"),
+            ("adjoint", "left"), ("adjoint", "right"), ("adjoint", "null vector"),
+            ("SPINOR", "f32"), ("SPINOR", "n = 8"), ("SPINOR", "padded"), ("SPINOR", "negative vector"),
+            ("chained", "row_scale"),
+            ("list", "fresh"), ("list", "fresh, empty rows"), ("list", "accumulated"), ("list", "regressive, mirrored"), ("list", "compact adjoint, exact order"),
+            ("parity", "pivot not +-1")}
+    want |= {(fam, dt) for fam in ("MFMA6", "MFMA7") for dt in ("f32", "f64")}
+    want |= {(fam, dt, how) for fam in ("MFMA6", "MFMA7") for dt in ("f32", "f64") for how in ("dealt", "row order")}
+    want |= {("parity", l, r) for l in ("even", "odd") for r in ("even", "odd")}
+    want |= {("chained", n, dt) for n in (8, 9) for dt in ("f32", "f64")}
+    assert reached == want, (sorted(map(str, want - reached)), sorted(map(str, reached - want)))

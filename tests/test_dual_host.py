@@ -16,7 +16,7 @@ import gaast_amd as ga
 from gaast_amd import _lib
 
 import dual_numpy as dn
-from helpers import HipBackend, OracleBackend
+from helpers import HipBackend, OracleBackend, plan_sources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PGA = [0.0, 1.0, 1.0, 1.0]
@@ -35,8 +35,7 @@ def driver(tmp_path_factory):
            "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
            "-I", os.path.join(csrc, "device"), "-I", os.path.join(csrc, "common"), "-I", os.path.join(csrc, "host"),
            os.path.join(ROOT, "tests", "cpp", "dual_sanitize_driver.cpp")]
-    cmd += [os.path.join(csrc, f) for f in ("host/expr.cpp", "host/c_api_host.cpp", "host/wire.cpp", "host/vjp.cpp",
-                                            "device/plan.cpp", "device/plan_fused.cpp", "device/plan_chain_jit.cpp")]
+    cmd += plan_sources(csrc)
     subprocess.run(cmd + ["-o", str(exe)], check=True, cwd=csrc)
     run = subprocess.run([str(exe)], capture_output=True, text=True)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]

@@ -271,7 +271,7 @@ def test_negative_zero_operands_leave_no_trace(n, dtype):
 def test_general_diagonal_metrics_run_on_the_dense_kernels(metric):
     """algebra.rs:148-165 (`impl MetricAlgebra for [f64; D]`) multiplies by ANY base_vec_dot (:79-81).  Round 2 sent every
     entry other than +-1 / 0 to k_product_csr (2.2 M products/s at n = 8 against ~800 M/s).  Now the dense kernels run in the
-    rescaled basis f_i = e_i / sqrt|g_i|: operands times w_S while staged, result times 1 / w_T when stored (plan.cpp:
+    rescaled basis f_i = e_i / sqrt|g_i|: operands times w_S while staged, result times 1 / w_T when stored (plan_dense.cpp:
     dense_scales_ok / blade_scale).  Bound: 8 eps sum|terms| per component -- the 4 eps of the +-1 case plus three roundings
     per term (w_S A_S, w_U B_U, C'_T / w_T) and the roundings of the three factors themselves.  With GAAST_FLAG_EXACT_ORDER the
     product stays on k_product_csr and is bit-exact."""
@@ -295,7 +295,7 @@ def test_general_diagonal_metric_at_n12_and_partial_operands():
 
 def test_a_metric_too_wild_to_rescale_stays_on_the_list_kernels():
     """1e200 and 1e-200 among the squares: w_S would leave the range in which the rescaling is harmless (2^+-300 in f64,
-    2^+-40 in f32: plan.cpp dense_scales_ok) -> the exact kernels, bit-exact"""
+    2^+-40 in f32: plan_dense.cpp dense_scales_ok) -> the exact kernels, bit-exact"""
     metric = [1e200, 1e-200, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0]
     build, lg = _gp(8)
     rng = np.random.default_rng(5)
@@ -315,7 +315,7 @@ ODD = lambda n: [k for k in range(n + 1) if k % 2 == 1]
 def test_parity_pure_operands_run_in_the_even_subalgebra(n, metric, lpar, rpar):
     """The reference only multiplies the entries it needs (specialize.rs:162-183): even x even (rotor composition, the second
     product of every sandwich) is a quarter of the 4^n table.  Round 2's dense kernels always did 4^n multiply-adds; now a
-    product of parity-pure operands is ONE product in Cl(n - 1) (plan.cpp: parity_reduced_frame) -- 4^(n-1) multiply-adds --
+    product of parity-pure operands is ONE product in Cl(n - 1) (plan_dense.cpp: parity_reduced_frame) -- 4^(n-1) multiply-adds --
     for all four parity combinations, against the oracle within 4 eps sum|terms| in both value types."""
     if n == 12 and (lpar, rpar) not in (("even", "even"), ("odd", "even")):
         pytest.skip("n = 12: two of the four cases (each builds a 4.2 M-entry oracle table)")
@@ -634,7 +634,7 @@ def test_n6_partial_operands_projected_result_accumulation_and_shared_rows(dtype
 
 
 def test_n7_parity_pure_products_run_in_cl6_on_the_matrix_cores():
-    """even x even and odd x even at n = 7 are ONE product in the even subalgebra Cl(6) (plan.cpp rewrite 7): k_gp_mfma6"""
+    """even x even and odd x even at n = 7 are ONE product in the even subalgebra Cl(6) (plan_dense.cpp: parity_reduced_frame): k_gp_mfma6"""
     n = 7
     for lpar, rpar in (("even", "even"), ("odd", "even")):
         grades = {"even": EVEN(n), "odd": ODD(n)}

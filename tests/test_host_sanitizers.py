@@ -4,6 +4,8 @@ GPU pool cannot offer.  See tests/cpp/host_sanitize_driver.cpp for what is exerc
 import os
 import subprocess
 
+from helpers import plan_sources
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -14,8 +16,7 @@ def test_host_logic_is_clean_under_asan_and_ubsan(tmp_path):
            "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
            "-I", os.path.join(csrc, "device"), "-I", os.path.join(csrc, "common"), "-I", os.path.join(csrc, "host"),
            os.path.join(ROOT, "tests", "cpp", "host_sanitize_driver.cpp")]
-    cmd += [os.path.join(csrc, f) for f in ("host/expr.cpp", "host/c_api_host.cpp", "host/wire.cpp", "device/plan.cpp",
-                                                "device/plan_fused.cpp", "device/plan_chain_jit.cpp")]
+    cmd += plan_sources(csrc)
     subprocess.run(cmd + ["-o", str(exe)], check=True, cwd=csrc)
     run = subprocess.run([str(exe)], capture_output=True, text=True)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]

@@ -94,9 +94,9 @@ def test_library_revision_matches_the_sources_it_was_built_from():
     import os
     import gaast_amd
     root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gaast_amd", "csrc")
-    files = sorted(glob.glob(os.path.join(root, "device", "*.hip.hpp"))) + [os.path.join(root, "device", f) for f in
-                                                                              ("runtime.hip", "plan.cpp", "plan_fused.cpp", "plan_chain_jit.cpp", "plan_internal.hpp", "plan.hpp",
-                                                                               "spinor_basis.hpp")]
+    files = (sorted(glob.glob(os.path.join(root, "device", "*.hip.hpp"))) + [os.path.join(root, "device", "runtime.hip")] +
+             sorted(glob.glob(os.path.join(root, "device", "plan*.cpp"))) +
+             [os.path.join(root, "device", f) for f in ("plan_internal.hpp", "plan.hpp", "spinor_basis.hpp")])
     h = hashlib.md5()
     for f in files:
         h.update(open(f, "rb").read())

@@ -18,7 +18,7 @@ import pytest
 import explog_grad_numpy as eg
 import gaast_amd as ga
 from gaast_amd import _lib
-from helpers import HipBackend, oracle_eval_batch
+from helpers import HipBackend, oracle_eval_batch, plan_sources
 from oracle import pyoracle as og
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -219,8 +219,7 @@ def test_host_driver_is_clean_under_asan_and_ubsan(tmp_path):
            "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
            "-I", os.path.join(csrc, "device"), "-I", os.path.join(csrc, "common"), "-I", os.path.join(csrc, "host"),
            os.path.join(ROOT, "tests", "cpp", "explog_vjp_sanitize_driver.cpp")]
-    cmd += [os.path.join(csrc, f) for f in ("host/expr.cpp", "host/c_api_host.cpp", "host/wire.cpp", "host/vjp.cpp", "device/plan.cpp",
-                                                "device/plan_fused.cpp", "device/plan_chain_jit.cpp")]
+    cmd += plan_sources(csrc)
     subprocess.run(cmd + ["-o", str(exe)], check=True, cwd=csrc)
     run = subprocess.run([str(exe)], capture_output=True, text=True)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
