@@ -3,7 +3,7 @@
 Same operator surface as the reference: `*` geometric, `^` outer, `&` inner, `<<` / `>>`
 contractions, `+ - unary-`, `.g(k) .rev() .ginvol() .conj() .scal() .norm_sq() .sinv() .vinv()
 .sqrt() .pow() .exp() .log()`; beyond the reference, the metric-free complements `.dual() .undual()` and the regressive
-product `.vee(rhs)` (join of points / meet of planes).  Phases 1-3 run in the C++ host code of libgaast_hip.so;
+product `.vee(rhs)` (join of points / meet of planes), and the general inverse `.inv()` with `a / b` and `1 / a`.  Phases 1-3 run in the C++ host code of libgaast_hip.so;
 `SpecializedAst.eval*` is phase 4 on the GPU through the C ABI -- there is no CPU path.
 """
 from __future__ import annotations
@@ -107,7 +107,12 @@ class Expr:
         return self._bin(rhs, _lib.lib().gaast_expr_sub)
 
     def __truediv__(self, s):                                        # expr.rs:263-270
-        return self._un(_lib.lib().gaast_expr_div_scalar, float(s))
+        if isinstance(s, (int, float)):
+            return self._un(_lib.lib().gaast_expr_div_scalar, float(s))
+        return self * Expr._lift(s).inv()                            # a / b = a * inv(b): right division by any invertible multivector
+
+    def __rtruediv__(self, lhs):                                     # 1 / a
+        return Expr._lift(lhs) * self.inv()
 
     # -- unary ops & shortcuts, expr.rs:276-372 ----------------------------------------------
     def rev(self):
@@ -149,6 +154,11 @@ class Expr:
 
     def vinv(self):
         return self._un(_lib.lib().gaast_expr_vinv)
+
+    def inv(self):
+        """The general inverse, the Y with self * Y = 1 (GAAST_OP_INV): any invertible multivector, versor or not; even grades for
+        an even operand, every grade otherwise; singular items come back NaN and are counted (domain_errors()).  N <= 64 blades."""
+        return self._un(_lib.lib().gaast_expr_inv)
 
     def dual(self):
         """Right complement: dual(e_S) = +-e_~S with e_S ^ dual(e_S) = I (GAAST_OP_DUAL); grade k -> n - k."""
@@ -275,7 +285,8 @@ class SpecializedAst:
         return self._out_info
 
     def domain_errors(self):
-        """GAAST_FLAG_EXP_LOG extension: items refused by the exp / log domain check since the last call (synchronises)."""
+        """Items refused by the exp / log domain check (GAAST_FLAG_EXP_LOG) or found singular by inv() since the last call
+        (synchronises)."""
         n = C.c_int64()
         _lib.check(_lib.lib().gaast_hip_program_domain_errors(self.program(), C.byref(n)))
         return n.value

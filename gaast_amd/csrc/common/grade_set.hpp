@@ -40,6 +40,13 @@ inline uint64_t gs_mirror(uint64_t mask, int n) {
     return m;
 }
 
+// grades of a general inverse (GAAST_OP_INV): the even subalgebra is closed, so an even operand has an even inverse; any other
+// operand's inverse may hold every grade
+inline uint64_t gs_inverse(uint64_t mask, int n) {
+    const uint64_t full = n >= 63 ? ~0ULL : ((1ULL << (n + 1)) - 1ULL);
+    return (mask & 0xAAAAAAAAAAAAAAAAULL) ? full : (full & 0x5555555555555555ULL);
+}
+
 // The five grades_to_produce closures of expr.rs:180-197, and the regressive product's (the only one that needs the dimension n)
 inline uint64_t gs_select(int kind, int64_t k1, int64_t k2, int n = 0) {
     switch (kind) {

@@ -173,6 +173,7 @@ struct Lowering : LowerState {
         case GAAST_OP_LOG_ADJ: lower_exp_log_adj(res, id); return;
         case GAAST_OP_DUAL:
         case GAAST_OP_UNDUAL: lower_dual(res, id); return;
+        case GAAST_OP_INV: lower_inverse(res, id); return;
         case GAAST_OP_PRODUCT: lower_product(res, id); return;
         default: throw std::runtime_error("unknown opcode");
         }
@@ -228,6 +229,91 @@ struct Lowering : LowerState {
         s.canon_a = canon;
         s.beta = covers ? 0 : 1;
         s.dual = std::move(q);
+        touch(res);
+    }
+
+    // The general inverse (GAAST_OP_INV, gaast_hip.h; no reference counterpart): a one-operand product arm, always a launch of its
+    // own (Step::INVERSE, k_mv_inverse).  The operand is read like a Product's (operand()); res += the Y with A Y = 1 in the wanted
+    // grades.  Of a bare scalar it is ScalarInversion, arm for arm.
+    void lower_inverse(BufRef res, int id) {
+        const gaast_node_desc& nd = node(id);
+        const gaast_node_desc& ch = node(nd.child0);
+        const int n = d.vec_space_dim;
+        if (ch.minimal_grade_mask == 1ULL) {   // eval.rs:103-110
+            add_to_res(res, nd.child0);
+            if (!ok()) return;
+            const Layout& r = layout(res);
+            if (!(r.mask & 1ULL)) {
+                fail(GAAST_ERR_MISSING_GRADE, "scalar op on a buffer without grade 0");
+                return;
+            }
+            Step& s = emit(Step::SUNARY, res, "scalar_inversion");
+            s.sunary_op = 0;
+            s.sunary_off = int(r.offset(0));
+            touch(res);
+            return;
+        }
+        if (ch.vec_space_dim != n || nd.vec_space_dim != n) {
+            fail(GAAST_ERR_INVALID_PROGRAM, "inverse operand lives in another vector space than the algebra");
+            return;
+        }
+        const uint64_t amask = ch.minimal_grade_mask & ((uint64_t(2) << n) - 1);
+        const bool even = !(amask & 0xAAAAAAAAAAAAAAAAULL);
+        if ((even ? n - 1 : n) > 6) {
+            if (plan.unsupported.empty())
+                plan.unsupported = "the general inverse over " + std::string(even ? "the even blades" : "every blade") + " of a " + std::to_string(n) +
+                                   "-dimensional algebra: the elimination kernel is built for up to 64 blades";
+            return;
+        }
+        int canon = 0;
+        uint64_t flip = 0;
+        BufRef a = operand(nd.child0, &canon, &flip);
+        if (!ok()) return;
+        if (key(a) == key(res)) {
+            fail(GAAST_ERR_MISSING_GRADE, "inverse operand aliases its own result buffer");
+            return;
+        }
+        const Layout &la = layout(a), &lr = layout(res);
+        Step::Inverse q;
+        q.even = even ? 1 : 0;
+        q.N = 1 << (even ? n - 1 : n);
+        q.weight.assign(size_t(1) << n, 1.0);
+        for (uint32_t sset = 0; sset < (uint32_t(1) << n); ++sset)
+            for (int bit = 0; bit < n; ++bit)   // ascending bit order, as blades_gp_coeff multiplies
+                if ((sset >> bit) & 1u) q.weight[sset] *= d.metric_diag[bit];
+        for (int j = 0; j < q.N; ++j) {
+            const uint32_t b = even ? (uint32_t(j) << 1) | uint32_t(__builtin_popcount(uint32_t(j)) & 1) : uint32_t(j);
+            const int k = __builtin_popcount(b);
+            q.blade.push_back(b);
+            const bool held = ((amask >> k) & 1ULL) && ((la.mask >> k) & 1ULL) && int64_t(bt.index_of[b]) < la.grade_len(k);
+            q.a_off.push_back(held ? int32_t(la.offset(k) + bt.index_of[b]) : -1);
+            if (held && ((flip >> k) & 1ULL)) q.a_neg |= uint64_t(1) << j;
+            int32_t ro = -1;
+            if ((nd.minimal_grade_mask >> k) & 1ULL) {
+                if (!((lr.mask >> k) & 1ULL) || lr.grade_len(k) != int64_t(bt.grade_dim[size_t(k)])) {
+                    fail(GAAST_ERR_MISSING_GRADE, "grade " + std::to_string(k) + " absent from result buffer");
+                    return;
+                }
+                ro = int32_t(lr.offset(k) + bt.index_of[b]);
+                ++q.n_out;
+            }
+            q.res_off.push_back(ro);
+        }
+        q.neg.assign(size_t(q.N), 0);
+        for (int r = 0; r < q.N; ++r)
+            for (int j = 0; j < q.N; ++j)
+                if (reorder_parity(q.blade[size_t(r)] ^ q.blade[size_t(j)], q.blade[size_t(j)])) q.neg[size_t(r)] |= uint64_t(1) << j;
+        if (!q.n_out) return;
+        // the first writer of a fresh buffer that covers every component of it: the zero fill is folded in
+        const auto fr = fresh.find(key(res));
+        const bool covers = fr != fresh.end() && !(plan.flags & GAAST_FLAG_NO_FUSION) && int64_t(q.n_out) == lr.row_len;
+        if (covers) removed[size_t(fr->second)] = 1;
+        Step& s = emit(Step::INVERSE, res, "inverse[" + std::to_string(q.N) + (even ? " even" : "") + " blades, " + std::to_string(q.n_out) + " produced, n=" + std::to_string(n) + "]");
+        s.a = a;
+        s.canon_a = canon;
+        s.beta = covers ? 0 : 1;
+        s.inv = std::move(q);
+        plan.has_inverse = 1;
         touch(res);
     }
 
@@ -1238,7 +1324,7 @@ void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab,
             break;
         case GAAST_OP_NEG: case GAAST_OP_EXP: case GAAST_OP_LOG: case GAAST_OP_PROJ:
         case GAAST_OP_REVERSE: case GAAST_OP_GINVOL: case GAAST_OP_SINV: case GAAST_OP_SSQRT:
-        case GAAST_OP_DUAL: case GAAST_OP_UNDUAL:
+        case GAAST_OP_DUAL: case GAAST_OP_UNDUAL: case GAAST_OP_INV:
             if (!child_ok(nd.child0)) throw std::runtime_error("nodes are not in post-order");
             break;
         default: throw std::runtime_error("unknown opcode");

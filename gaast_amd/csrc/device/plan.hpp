@@ -44,8 +44,8 @@ inline Layout make_layout(int dim, uint64_t mask) {
 // a step in place), each table and setting named after the one thing it holds.  The groups of the other kinds stay empty.  The
 // tables are host images, uploaded once at program_create.
 struct Step {
-    enum Kind { ZERO, AXPY, FLIP, SUNARY, PRODUCT_CSR, PRODUCT_DENSE, FUSED, EXPLOG, REDUCE_SCALE, ELEMENTWISE, LINMAP, EXPLOG_ADJ, DUAL } kind = ZERO;
-    BufRef res, a, b;        // result; operand rows (PRODUCT_*: left, right; AXPY / EXPLOG / LINMAP / DUAL: a; EXPLOG_ADJ: a = the forward operand, b = the cotangent; REDUCE_SCALE: the reduction's; ELEMENTWISE: b = the scalar)
+    enum Kind { ZERO, AXPY, FLIP, SUNARY, PRODUCT_CSR, PRODUCT_DENSE, FUSED, EXPLOG, REDUCE_SCALE, ELEMENTWISE, LINMAP, EXPLOG_ADJ, DUAL, INVERSE } kind = ZERO;
+    BufRef res, a, b;        // result; operand rows (PRODUCT_*: left, right; AXPY / EXPLOG / LINMAP / DUAL / INVERSE: a; EXPLOG_ADJ: a = the forward operand, b = the cotangent; REDUCE_SCALE: the reduction's; ELEMENTWISE: b = the scalar)
     std::string name;
     int canon_a = 0, canon_b = 0;   // the operand is a bound input read in place: the kernel applies the reference's 0.0 + x
     int beta = 1;                   // 0: the zero fill of a fresh result is folded in
@@ -198,6 +198,26 @@ struct Step {
         }
     } dual;
 
+    // INVERSE (GAAST_OP_INV, gaast_hip.h): res += the Y with A Y = 1, A = row `a`.  The blade set S (every blade, or the even ones) in
+    // ascending bitmask order: S[j] = j, or (j << 1) | parity(j) for the even set, so that the index of S[r] xor S[j] is r xor j.
+    // Y solves L y = e_0 with L[r][j] = coeff(r, j) A[r xor j]: the matrix is held as what k_mv_inverse rebuilds it from -- the
+    // reordering signs, one 64-bit word per row, and the metric factor by shared-vector set -- 4096 sign bits and at most 128 values
+    struct Inverse {
+        int N = 0;                          // |S|: 2, 4, ... 64
+        int even = 0;                       // S is the even blades
+        std::vector<uint32_t> blade;        // [N] the blade of index j
+        std::vector<int32_t> a_off;         // [N] offset of blade j in the operand row; -1: the operand lacks its grade (reads as 0)
+        std::vector<int32_t> res_off;       // [N] offset of blade j in the result row; -1: not produced
+        uint64_t a_neg = 0;                 // bit j: the operand component is negated (sign-only arms over a bound input, folded)
+        std::vector<uint64_t> neg;          // [N] bit j of neg[r]: e_a e_b = -(...) for a = S[r] xor S[j], b = S[j]
+        std::vector<double> weight;         // [2^n] product of the metric diagonal over the vectors of the set s (a & b = S[j] & ~S[r])
+        int n_out = 0;                      // produced components
+        double coeff(int r, int j) const {  // L[r][j] = coeff(r, j) * A[r xor j]
+            const double w = weight[size_t(blade[size_t(j)] & ~blade[size_t(r)])];
+            return ((neg[size_t(r)] >> j) & 1ULL) ? -w : w;
+        }
+    } inv;
+
     // REDUCE_SCALE (plan.cpp: fuse_reduce_scale): a product whose result is ONE scalar component (a single long row: norm_sq), an
     // optional ScalarUnaryOp on it, and a product of one-term rows that multiplies another row by that scalar -- the versor inverse
     // a.rev() * a.norm_sq().sinv() and normalisations, where the rows no longer fit a fused slab (n >= 9) -- in ONE launch, one wave per
@@ -273,6 +293,7 @@ struct Plan {
     int error = GAAST_OK;              // what the reference would have panicked with, at eval
     std::string error_msg;
     int has_explog = 0;                // some step evaluates exp / log: the program owns a domain-error counter
+    int has_inverse = 0;               // some step is a general inverse: the program owns the domain-error counter too (singular items)
     int has_explog_adj = 0;            // some step is an exp / log adjoint (no interpreter micro-ops, no domain check)
     int mirrored = 0;                  // the program runs in the orthogonal basis of a Gram metric whose Q has det -1: every
                                        // complement sign and regressive coefficient is negated (gaast_hip.h: GAAST_OP_DUAL)

@@ -210,6 +210,10 @@ struct Launch {
         DevTable segs, neg;
         int col_shift = 8;              // log2 of the components a workgroup of k_dual covers
     } dual;
+    struct {   // INVERSE
+        DevTable a_off, res_off, neg, weight;
+        const void* kernel = nullptr;   // k_mv_inverse<T, N>
+    } inv;
     struct {   // PRODUCT_CSR: k_product_csr, k_product_ell, k_product_ell_chain or the specialised gaast_chain
         DevTable row_start, row_out, entries, coeff;
         struct { DevTable entries, row_map; } pre;        // k_product_ell_chain: the first list
@@ -589,6 +593,45 @@ int run_dual(const Launch& L, const Operands& o, int64_t batch) {
     const unsigned gx = unsigned((s.dual.total + (1 << p.col_shift) - 1) >> p.col_shift);
     const unsigned gy = unsigned(std::min<int64_t>((batch + per_block - 1) / per_block, 65535));
     hipLaunchKernelGGL(k_dual<T>, dim3(gx, gy), dim3(256), 0, g_stream, p);
+    return launch_status();
+}
+
+// ---- INVERSE -------------------------------------------------------------------------------------------------------------
+// (one kernel per (T, N): nothing is chosen at launch, the variant is 0)
+template <typename T>
+int prepare_inverse(Launch& L, std::string& kernel) {
+    Step& s = L.s;
+    auto& c = L.inv;
+    using Kern = void (*)(InverseArgs<T>);
+    c.kernel = kernel_address(static_int<2, 4, 8, 16, 32, 64>(s.inv.N, [](auto n) -> Kern { return k_mv_inverse<T, decltype(n)::value>; }));
+    if (!c.kernel) return set_err(GAAST_ERR_UNIMPLEMENTED, "no inverse kernel for " + std::to_string(s.inv.N) + " blades");
+    Upload<T> up;
+    up.idx(c.a_off, s.inv.a_off); up.idx(c.res_off, s.inv.res_off); up.idx(c.neg, s.inv.neg); up.val(c.weight, s.inv.weight);
+    kernel = std::string("k_mv_inverse<") + type_name<T>() + "," + std::to_string(s.inv.N) + ">";
+    return up.status;
+}
+
+template <typename T>
+int run_inverse(const Launch& L, const Operands& o, int64_t batch) {
+    const Step& s = L.s;
+    if (batch <= 0) return GAAST_OK;
+    InverseArgs<T> p;
+    p.res = static_cast<T*>(o.res.ptr);
+    p.in = static_cast<const T*>(o.a.ptr);
+    p.res_stride = o.res.stride;
+    p.in_stride = o.a.stride;
+    p.batch = batch;
+    p.a_off = L.inv.a_off.as<int32_t>();
+    p.res_off = L.inv.res_off.as<int32_t>();
+    p.neg = L.inv.neg.as<uint64_t>();
+    p.weight = L.inv.weight.as<T>();
+    p.a_neg = s.inv.a_neg;
+    p.n = L.n;
+    p.even = s.inv.even;
+    p.beta = s.beta;
+    p.dom = static_cast<unsigned long long*>(L.domain);
+    const int64_t per_block = 256 / s.inv.N;
+    launch_kernel(L.inv.kernel, persistent_grid((batch + per_block - 1) / per_block, 8), 256, 0, p);
     return launch_status();
 }
 
@@ -1527,6 +1570,7 @@ int prepare_launch(Launch& L, const gaast_hip_program_s& prog) {
     case Step::LINMAP: kernel = linmap_kernel_name(L.linmap->n, plan.dtype); break;
     case Step::EXPLOG_ADJ: st = prepare_explog_adj<T>(L, la, lb, kernel); break;
     case Step::DUAL: st = prepare_dual<T>(L, kernel); break;
+    case Step::INVERSE: st = prepare_inverse<T>(L, kernel); break;
     }
     if (st) return st;
     L.label = kernel.empty() ? s.name : s.name + " :: " + kernel;
@@ -1568,7 +1612,7 @@ int program_create_impl(const gaast_program_desc* desc, gaast_hip_program_t* out
         if (int st = make_launches(d2, small_reg_slab, mirrored, *prog)) return st;
     }
     compile_chains(*prog, desc->flags);
-    if (prog->plan.has_explog)
+    if (prog->plan.has_explog || prog->plan.has_inverse)
         if (int st = prog->domain.upload(std::vector<unsigned long long>(1, 0))) return st;
     for (Launch& L : prog->launches)
         if (int st = prepare_launch(L, *prog)) return st;
@@ -2263,6 +2307,7 @@ int run_launch(const Launch& L, const Operands& o, int64_t batch) {
     case Step::LINMAP: st = run_linmap<T>(L, o, batch); break;
     case Step::EXPLOG_ADJ: st = run_explog_adj<T>(L, o, batch); break;
     case Step::DUAL: st = run_dual<T>(L, o, batch); break;
+    case Step::INVERSE: st = run_inverse<T>(L, o, batch); break;
     }
     L.variant = variant;
     return st;

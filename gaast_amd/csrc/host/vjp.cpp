@@ -13,6 +13,12 @@
 //   dual/undual the operand has a buffer of its own or is read from a bound input (plan.cpp: lower_dual), so the node is a one-operand
 //               product event: the operand's cotangent is the OTHER complement (the transpose of a signed permutation is its
 //               inverse) of the buffer's cotangent restricted to the node's grades;
+//   inv         (GAAST_OP_INV, gaast_hip.h) the operand has a buffer of its own or is read from a bound input (plan.cpp: lower_inverse):
+//               a one-operand product event.  d(A^-1) = -(Y dA) Y with Y = A^-1, so the operand's cotangent is
+//               -ADJ_RIGHT(ADJ_LEFT(g, Y), Y) over geometric products: Y is one more INV node over the forward operand that
+//               produces every grade of its blade set, and the sign is a Negation of g -- of the innermost child, where it has a
+//               buffer of its own (a product operand), so that every node added to a cotangent stays additive; by linearity the
+//               bits are those of negating the result.  An INV node over a bare scalar (raw ABI) is a SINV event;
 //   exp / log   (GAAST_FLAG_EXP_LOG | GAAST_FLAG_EXP_LOG_GRAD) the operand has a buffer of its own, like a product operand
 //               (plan.cpp: lower_exp_log -> store_in_cache): a one-operand product event -- GAAST_OP_EXP_ADJ / GAAST_OP_LOG_ADJ over
 //               the buffer's cotangent restricted to the node's grades and the forward operand -> cotangent of the operand buffer.
@@ -169,8 +175,46 @@ struct Builder {
             if (nd.opcode == GAAST_OP_SINV || nd.opcode == GAAST_OP_SSQRT) ev.push_back({EV_SCALAR, x, path});
             else if (nd.opcode != GAAST_OP_PROJ) ev.push_back({EV_FLIP, x, path});
             return;
+        case GAAST_OP_INV:
+            if (d.nodes[nd.child0].minimal_grade_mask == 1ULL) {  // of a bare scalar: lowered as ScalarInversion
+                path.push_back({x, 0});
+                collect(nd.child0, path, ev);
+                path.pop_back();
+                ev.push_back({EV_SCALAR, x, path});
+                return;
+            }
+            ev.push_back({EV_OPAQUE, x, path});
+            return;
         default: ev.push_back({EV_OPAQUE, x, path}); return;  // exp / log, dual / undual
         }
+    }
+    // inv: cotangent of the operand's buffer
+    void inv_adjoint(int x, const std::vector<Term>& terms, std::vector<std::vector<Term>>& cot) {
+        const gaast_node_desc& xd = d.nodes[x];
+        const int c = xd.child0;
+        if (!dep[size_t(c)]) return;
+        const uint64_t cmask = d.nodes[c].minimal_grade_mask, smask = gs_inverse(cmask, n);
+        const int g = materialize(terms, xd.minimal_grade_mask);
+        if (g < 0 || !cmask) return;
+        gaast_node_desc y = blank(GAAST_OP_INV, smask, n);
+        y.child0 = c;
+        const int yn = add(y);
+        gaast_node_desc neg = blank(GAAST_OP_NEG, mask_of(g), n);
+        neg.child0 = g;
+        const int ng = add(neg);
+        const Selection sel{GAAST_PROD_GEOMETRIC, nullptr, nullptr, n};
+        gaast_node_desc m = blank(GAAST_OP_PRODUCT, smask, n);   // cotangent of M = Y dA in P = M Y
+        m.child0 = ng;
+        m.child1 = yn;
+        m.product_kind = GAAST_PROD_GEOMETRIC + GAAST_PROD_ADJ_LEFT;
+        m.n_comp_muls = comp_mul_count(n, iter_contribs(mask_of(ng), sel, smask, smask));
+        const int mn = add(m);
+        gaast_node_desc a = blank(GAAST_OP_PRODUCT, cmask, n);   // cotangent of dA in M = Y dA
+        a.child0 = mn;
+        a.child1 = yn;
+        a.product_kind = GAAST_PROD_GEOMETRIC + GAAST_PROD_ADJ_RIGHT;
+        a.n_comp_muls = comp_mul_count(n, iter_contribs(smask, sel, smask, cmask));
+        cot[size_t(c)].push_back(Term{add(a), 0, ~0ULL});
     }
     // dual / undual: cotangent of the operand's buffer
     void dual_adjoint(int x, const std::vector<Term>& terms, std::vector<std::vector<Term>>& cot) {
@@ -296,7 +340,7 @@ struct Builder {
         }
         int ds = sum(parts, 1ULL, n);
         if (ds < 0) return;
-        if (x.opcode == GAAST_OP_SINV) ds = explicit_product(ds, t, {gaast_comp_mul{0, 0, 0, 0, 0, 0, 1.0}}, 1ULL, n);
+        if (x.opcode != GAAST_OP_SSQRT) ds = explicit_product(ds, t, {gaast_comp_mul{0, 0, 0, 0, 0, 0, 1.0}}, 1ULL, n);
         terms.push_back(Term{ds, 0, ~0ULL});
     }
 
@@ -357,6 +401,7 @@ struct Builder {
                 case EV_SCALAR: scalar_adjoint(s, e, terms); break;
                 case EV_OPAQUE:   // a node whose operand has a buffer of its own
                     if (x.opcode == GAAST_OP_DUAL || x.opcode == GAAST_OP_UNDUAL) dual_adjoint(e.node, terms, cot);
+                    else if (x.opcode == GAAST_OP_INV) inv_adjoint(e.node, terms, cot);
                     else explog_adjoint(e.node, terms, cot);
                     break;
                 }
@@ -411,7 +456,7 @@ extern "C" int gaast_program_vjp(const gaast_program_desc* desc, int32_t wrt_slo
         const gaast_node_desc& nd = d.nodes[i];
         const bool two = nd.opcode == GAAST_OP_ADD || nd.opcode == GAAST_OP_PRODUCT;
         const bool ok = nd.opcode == GAAST_OP_INPUT ? (nd.input_slot >= 0 && nd.input_slot < d.n_inputs)
-                        : (nd.opcode > GAAST_OP_INPUT && (nd.opcode <= GAAST_OP_SSQRT || nd.opcode == GAAST_OP_DUAL || nd.opcode == GAAST_OP_UNDUAL) &&
+                        : (nd.opcode > GAAST_OP_INPUT && (nd.opcode <= GAAST_OP_SSQRT || nd.opcode == GAAST_OP_DUAL || nd.opcode == GAAST_OP_UNDUAL || nd.opcode == GAAST_OP_INV) &&
                            nd.child0 >= 0 && nd.child0 < i &&
                            (!two || (nd.child1 >= 0 && nd.child1 < i)));
         if (!ok || (nd.opcode == GAAST_OP_PRODUCT && nd.product_kind >= GAAST_PROD_ADJ_LEFT)) {

@@ -105,7 +105,28 @@ typedef enum gaast_opcode {
      * dualises to grade n of the algebra.  In a program of gaast_hip_program_create_in_basis the complement of the caller's basis is
      * det(Q) = +-1 times the one of the orthogonal basis: the library multiplies every sign by sign(det Q). */
     GAAST_OP_DUAL = 13,
-    GAAST_OP_UNDUAL = 14
+    GAAST_OP_UNDUAL = 14,
+    /* General multivector inverse (no reference counterpart): the Y with A Y = 1.  One child.  Let S be the even blades when the
+     * child's minimal grade mask holds only even grades (the even subalgebra is closed), else all 2^n blades, N = |S|.  Y solves
+     * L_A y = e_scalar with the left-multiplication matrix L_A[c][b] = coeff(a, b) A[a], a = c xor b (coeff: the blade-product sign
+     * and metric factor of every product here; 0 where the child does not hold grade(a)); where A is invertible the left and right
+     * inverses coincide.  The node's maximal grade set is {0, 2, 4, ... <= n} for an even child and {0 .. n} otherwise; it
+     * produces the wanted grades of that set, while its child is wanted in ALL of the child's own grades.  Like every arm it ADDS
+     * into the buffer that contains it.  A child whose mask is {0} is GAAST_OP_SINV (the expression layer lowers it so; the raw
+     * ABI may carry GAAST_OP_INV on a scalar and gets the same launch as GAAST_OP_SINV).
+     * Supported: N <= 64 (any mask for n <= 6, even masks for n = 7); beyond that gaast_hip_program_create returns
+     * GAAST_ERR_UNIMPLEMENTED and creates nothing (phases 1-3 succeed on the host for any n).
+     * Singular items: Gauss-Jordan elimination with partial pivoting; an item is singular when at any column the pivot p has
+     * !(|p| > N eps max_i |A_i|) (eps of the program's dtype, max over the item's operand components; a NaN pivot is singular
+     * too).  It is counted in gaast_hip_program_domain_errors (a program with an INV step owns the counter as one with exp / log
+     * does) and every produced component of it is a quiet NaN.  An all-zero column gives an exact zero pivot: deterministic.
+     * Non-finite inputs propagate as IEEE 754 dictates and may or may not be counted.
+     * Accuracy: per non-singular item the normwise backward error ||L_A y - e||_inf / (||L_A||_inf ||y||_inf) <= 2 N eps to first
+     * order (||L_A||_inf the largest absolute row sum): the scale of Gaussian elimination with partial pivoting.
+     * GAAST_FLAG_EXACT_ORDER changes nothing here: there are no reference bits for an operation the reference lacks.
+     * Reverse mode (gaast_program_vjp): with Y the inverse recomputed in every grade of S and g the cotangent of the node,
+     * the child gets -ADJ_RIGHT_geometric(ADJ_LEFT_geometric(g, Y), Y), the adjoint of dA -> -(Y dA) Y. */
+    GAAST_OP_INV = 15
 } gaast_opcode;
 
 /* the five products of src/ast/expr.rs:180-197 (and the regressive product), for compact PRODUCT descriptors */
@@ -252,7 +273,8 @@ const char *gaast_hip_program_launch_name(gaast_hip_program_t prog, int i);
 int gaast_hip_program_launch_variant(gaast_hip_program_t prog, int i);
 /* GAAST_FLAG_EXP_LOG extension: how many items, since the last call, had an exp / log operand outside the domain (a
  * k-vector whose square is not scalar: |<B B>_{not 0}|^2 > 2^-40 (sum B_i^2)^2); their results are the closed form applied
- * to <B B>_0 regardless.  Synchronises the library stream; resets the counter.  0 for programs without exp / log. */
+ * to <B B>_0 regardless.  A program with a GAAST_OP_INV step counts its singular items here too (their produced components are
+ * NaN).  Synchronises the library stream; resets the counter.  0 for programs without exp / log / inv. */
 int gaast_hip_program_domain_errors(gaast_hip_program_t prog, int64_t *count);
 /* GAAST_FLAG_DEBUG_KEEP_JIT_SOURCE: the HIP source generated for this program ("" if none). */
 const char *gaast_hip_program_jit_source(gaast_hip_program_t prog);

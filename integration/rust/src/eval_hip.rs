@@ -205,6 +205,10 @@ impl<T: GradedData + std::fmt::Debug> SpecializedAst<T> {
                 // with the node's grade set the child's mirrored (k -> dim - k); a v b needs no new arm here: it is a Product
                 // whose grades_to_produce closure returns single(k1 + k2 - dim), sent as an explicit list like any other
                 // (product_kind PROD_REGRESSIVE instead of -1 lets the library apply the orientation sign of a Gram basis).
+                // The general inverse is an extension too: a fork that adds `Inverse(e)` flattens it as
+                //     N::Inverse(e) => { d.opcode = OP_INV; d.child0 = index[e]; }
+                // with the node's grade set the even grades for an even child and every grade otherwise, and the child wanted
+                // in all of its grades (a scalar child: ScalarUnaryOp::Inversion, as above).
             }
             nodes.push(d);
         }

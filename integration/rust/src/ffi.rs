@@ -27,6 +27,8 @@ pub const OP_LOG_ADJ: i32 = 12;
 // complements (no AstNode counterpart; metric-free): one child, grade k -> n - k
 pub const OP_DUAL: i32 = 13;
 pub const OP_UNDUAL: i32 = 14;
+// general multivector inverse (no AstNode counterpart): one child, A Y = 1 over the even or the full blade set, N <= 64 blades
+pub const OP_INV: i32 = 15;
 // compact product kinds (gaast_product_kind); 5 = the regressive product a v b = undual(dual(a) ^ dual(b))
 pub const PROD_REGRESSIVE: i32 = 5;
 
