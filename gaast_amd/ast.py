@@ -3,7 +3,8 @@
 Same operator surface as the reference: `*` geometric, `^` outer, `&` inner, `<<` / `>>`
 contractions, `+ - unary-`, `.g(k) .rev() .ginvol() .conj() .scal() .norm_sq() .sinv() .vinv()
 .sqrt() .pow() .exp() .log()`; beyond the reference, the metric-free complements `.dual() .undual()` and the regressive
-product `.vee(rhs)` (join of points / meet of planes), and the general inverse `.inv()` with `a / b` and `1 / a`.  Phases 1-3 run in the C++ host code of libgaast_hip.so;
+product `.vee(rhs)` (join of points / meet of planes), the general inverse `.inv()` with `a / b` and `1 / a`, and the general
+exponential `.gexp()`.  Phases 1-3 run in the C++ host code of libgaast_hip.so;
 `SpecializedAst.eval*` is phase 4 on the GPU through the C ABI -- there is no CPU path.
 """
 from __future__ import annotations
@@ -160,6 +161,13 @@ class Expr:
         an even operand, every grade otherwise; singular items come back NaN and are counted (domain_errors()).  N <= 64 blades."""
         return self._un(_lib.lib().gaast_expr_inv)
 
+    def gexp(self):
+        """The general exponential sum_k self^k / k! (GAAST_OP_GEXP) by scaling and squaring: any multivector -- a PGA screw
+        bivector, a non-simple bivector, mixed grades -- where exp() is a closed form for k-vectors whose square is a scalar.  Even
+        grades for an even operand, every grade otherwise; items with sum |A_i| > 2048 or a non-finite component come back NaN
+        and are counted (domain_errors()).  Differentiable (vjp, torch_fn) without a flag.  N <= 64 blades."""
+        return self._un(_lib.lib().gaast_expr_gexp)
+
     def dual(self):
         """Right complement: dual(e_S) = +-e_~S with e_S ^ dual(e_S) = I (GAAST_OP_DUAL); grade k -> n - k."""
         return self._un(_lib.lib().gaast_expr_dual)
@@ -285,8 +293,8 @@ class SpecializedAst:
         return self._out_info
 
     def domain_errors(self):
-        """Items refused by the exp / log domain check (GAAST_FLAG_EXP_LOG) or found singular by inv() since the last call
-        (synchronises)."""
+        """Items refused by the exp / log domain check (GAAST_FLAG_EXP_LOG), found singular by inv() or out of gexp()'s domain since
+        the last call (synchronises)."""
         n = C.c_int64()
         _lib.check(_lib.lib().gaast_hip_program_domain_errors(self.program(), C.byref(n)))
         return n.value

@@ -174,6 +174,8 @@ struct Lowering : LowerState {
         case GAAST_OP_DUAL:
         case GAAST_OP_UNDUAL: lower_dual(res, id); return;
         case GAAST_OP_INV: lower_inverse(res, id); return;
+        case GAAST_OP_GEXP: lower_gexp(res, id); return;
+        case GAAST_OP_GEXP_ADJ: lower_gexp_adj(res, id); return;
         case GAAST_OP_PRODUCT: lower_product(res, id); return;
         default: throw std::runtime_error("unknown opcode");
         }
@@ -232,6 +234,152 @@ struct Lowering : LowerState {
         touch(res);
     }
 
+    // The tables of a step over the blade set S (Step::Inverse: INVERSE, GEXP, GEXP_ADJ): S itself, where operand row `a` (grades
+    // `amask`, those of `flip` negated) and result row `res` (grades `produce`) hold its blades, the reordering signs and the metric
+    // factors of the left-multiplication matrix.  false: failed (a produced grade is absent from res)
+    bool blade_set_tables(Step::Inverse& q, bool even, BufRef a, uint64_t amask, uint64_t flip, BufRef res, uint64_t produce) {
+        const int n = d.vec_space_dim;
+        const Layout &la = layout(a), &lr = layout(res);
+        q.even = even ? 1 : 0;
+        q.N = 1 << (even ? n - 1 : n);
+        q.weight.assign(size_t(1) << n, 1.0);
+        for (uint32_t sset = 0; sset < (uint32_t(1) << n); ++sset)
+            for (int bit = 0; bit < n; ++bit)   // ascending bit order, as blades_gp_coeff multiplies
+                if ((sset >> bit) & 1u) q.weight[sset] *= d.metric_diag[bit];
+        for (int j = 0; j < q.N; ++j) {
+            const uint32_t b = even ? (uint32_t(j) << 1) | uint32_t(__builtin_popcount(uint32_t(j)) & 1) : uint32_t(j);
+            const int k = __builtin_popcount(b);
+            q.blade.push_back(b);
+            const bool held = ((amask >> k) & 1ULL) && ((la.mask >> k) & 1ULL) && int64_t(bt.index_of[b]) < la.grade_len(k);
+            q.a_off.push_back(held ? int32_t(la.offset(k) + bt.index_of[b]) : -1);
+            if (held && ((flip >> k) & 1ULL)) q.a_neg |= uint64_t(1) << j;
+            int32_t ro = -1;
+            if ((produce >> k) & 1ULL) {
+                if (!((lr.mask >> k) & 1ULL) || lr.grade_len(k) != int64_t(bt.grade_dim[size_t(k)])) {
+                    fail(GAAST_ERR_MISSING_GRADE, "grade " + std::to_string(k) + " absent from result buffer");
+                    return false;
+                }
+                ro = int32_t(lr.offset(k) + bt.index_of[b]);
+                ++q.n_out;
+            }
+            q.res_off.push_back(ro);
+        }
+        q.neg.assign(size_t(q.N), 0);
+        for (int r = 0; r < q.N; ++r)
+            for (int j = 0; j < q.N; ++j)
+                if (reorder_parity(q.blade[size_t(r)] ^ q.blade[size_t(j)], q.blade[size_t(j)])) q.neg[size_t(r)] |= uint64_t(1) << j;
+        return true;
+    }
+
+    // is a general exponential over this blade set beyond the kernels (N = 2 ... 64)?  Then the plan is marked unsupported
+    bool blade_set_unsupported(const char* what, bool even) {
+        const int n = d.vec_space_dim, bits = even ? n - 1 : n;
+        if (bits >= 1 && bits <= 6) return false;
+        if (plan.unsupported.empty())
+            plan.unsupported = std::string(what) + " over " + (even ? "the even blades" : "every blade") + " of a " + std::to_string(n) +
+                               "-dimensional algebra: the kernel is built for 2 to 64 blades";
+        return true;
+    }
+
+    // The general exponential (GAAST_OP_GEXP, gaast_hip.h; no reference counterpart): a one-operand product arm, always a launch of
+    // its own (Step::GEXP, k_mv_gexp).  The operand is read like the inverse's; res += exp(A) in the wanted grades.
+    void lower_gexp(BufRef res, int id) {
+        const gaast_node_desc& nd = node(id);
+        const gaast_node_desc& ch = node(nd.child0);
+        const int n = d.vec_space_dim;
+        if (ch.vec_space_dim != n || nd.vec_space_dim != n) {
+            fail(GAAST_ERR_INVALID_PROGRAM, "gexp operand lives in another vector space than the algebra");
+            return;
+        }
+        const uint64_t amask = ch.minimal_grade_mask & ((uint64_t(2) << n) - 1);
+        const bool even = !(amask & 0xAAAAAAAAAAAAAAAAULL);
+        if (blade_set_unsupported("the general exponential", even)) return;
+        int canon = 0;
+        uint64_t flip = 0;
+        BufRef a = operand(nd.child0, &canon, &flip);
+        if (!ok()) return;
+        if (key(a) == key(res)) {
+            fail(GAAST_ERR_MISSING_GRADE, "gexp operand aliases its own result buffer");
+            return;
+        }
+        const Layout& lr = layout(res);
+        Step::Inverse q;
+        if (!blade_set_tables(q, even, a, amask, flip, res, nd.minimal_grade_mask)) return;
+        q.wmax = 0.0;
+        for (double w : q.weight) q.wmax = std::max(q.wmax, std::fabs(w));
+        if (!q.n_out) return;
+        // the first writer of a fresh buffer that covers every component of it: the zero fill is folded in
+        const auto fr = fresh.find(key(res));
+        const bool covers = fr != fresh.end() && !(plan.flags & GAAST_FLAG_NO_FUSION) && int64_t(q.n_out) == lr.row_len;
+        if (covers) removed[size_t(fr->second)] = 1;
+        Step& s = emit(Step::GEXP, res, "general_exponential[" + std::to_string(q.N) + (even ? " even" : "") + " blades, " + std::to_string(q.n_out) + " produced, n=" + std::to_string(n) + "]");
+        s.a = a;
+        s.canon_a = canon;
+        s.beta = covers ? 0 : 1;
+        s.inv = std::move(q);
+        plan.has_gexp = 1;
+        touch(res);
+    }
+
+    // Reverse mode of the general exponential (GAAST_OP_GEXP_ADJ, gaast_hip.h): res += the cotangent of the operand, in the operand's
+    // grades.  child1, the forward operand, is read like the forward's; child0, the cotangent, is cached like a product operand.
+    void lower_gexp_adj(BufRef res, int id) {
+        const gaast_node_desc& nd = node(id);
+        const gaast_node_desc& ch = node(nd.child1);
+        const int n = d.vec_space_dim;
+        if (ch.vec_space_dim != n || nd.vec_space_dim != n || node(nd.child0).vec_space_dim != n) {
+            fail(GAAST_ERR_INVALID_PROGRAM, "gexp adjoint operand lives in another vector space than the algebra");
+            return;
+        }
+        const uint64_t amask = ch.minimal_grade_mask & ((uint64_t(2) << n) - 1);
+        const bool even = !(amask & 0xAAAAAAAAAAAAAAAAULL);
+        if (blade_set_unsupported("the general exponential's adjoint", even)) return;
+        const uint64_t smask = gs_inverse(amask, n);
+        if (node(nd.child0).minimal_grade_mask & ~smask) {
+            fail(GAAST_ERR_INVALID_PROGRAM, "gexp adjoint: the cotangent holds grades outside the blade set of the operand");
+            return;
+        }
+        int canon = 0;
+        uint64_t flip = 0;
+        BufRef a = operand(nd.child1, &canon, &flip);
+        if (!ok()) return;
+        BufRef cot = store_in_cache(nd.child0);
+        if (!ok()) return;
+        if (key(a) == key(res) || key(cot) == key(res)) {
+            fail(GAAST_ERR_MISSING_GRADE, "gexp adjoint operand aliases its own result buffer");
+            return;
+        }
+        const Layout &lg = layout(cot), &lr = layout(res);
+        Step::Inverse q;
+        if (!blade_set_tables(q, even, a, amask, flip, res, nd.minimal_grade_mask & amask)) return;
+        q.wmax = 0.0;
+        for (double w : q.weight) q.wmax = std::max(q.wmax, std::fabs(w));
+        q.adj_neg_l.assign(size_t(q.N), 0);
+        q.adj_neg_r.assign(size_t(q.N), 0);
+        for (int j = 0; j < q.N; ++j) {
+            const uint32_t b = q.blade[size_t(j)];
+            const int k = __builtin_popcount(b);
+            const bool held = ((lg.mask >> k) & 1ULL) && int64_t(bt.index_of[b]) < lg.grade_len(k);
+            q.g_off.push_back(held ? int32_t(lg.offset(k) + bt.index_of[b]) : -1);
+            for (int t = 0; t < q.N; ++t)
+                if ((q.neg[size_t(j ^ t)] >> t) & 1ULL) {   // the sign of L[j xor t][t]: coeff(a = j, b = t)
+                    q.adj_neg_l[size_t(j)] |= uint64_t(1) << t;
+                    q.adj_neg_r[size_t(t)] |= uint64_t(1) << j;
+                }
+        }
+        if (!q.n_out) return;
+        const auto fr = fresh.find(key(res));
+        const bool covers = fr != fresh.end() && !(plan.flags & GAAST_FLAG_NO_FUSION) && int64_t(q.n_out) == lr.row_len;
+        if (covers) removed[size_t(fr->second)] = 1;
+        Step& s = emit(Step::GEXP_ADJ, res, "general_exponential_adjoint[" + std::to_string(q.N) + (even ? " even" : "") + " blades, " + std::to_string(q.n_out) + " produced, n=" + std::to_string(n) + "]");
+        s.a = a;
+        s.b = cot;
+        s.canon_a = canon;
+        s.beta = covers ? 0 : 1;
+        s.inv = std::move(q);
+        touch(res);
+    }
+
     // The general inverse (GAAST_OP_INV, gaast_hip.h; no reference counterpart): a one-operand product arm, always a launch of its
     // own (Step::INVERSE, k_mv_inverse).  The operand is read like a Product's (operand()); res += the Y with A Y = 1 in the wanted
     // grades.  Of a bare scalar it is ScalarInversion, arm for arm.
@@ -273,36 +421,9 @@ struct Lowering : LowerState {
             fail(GAAST_ERR_MISSING_GRADE, "inverse operand aliases its own result buffer");
             return;
         }
-        const Layout &la = layout(a), &lr = layout(res);
+        const Layout& lr = layout(res);
         Step::Inverse q;
-        q.even = even ? 1 : 0;
-        q.N = 1 << (even ? n - 1 : n);
-        q.weight.assign(size_t(1) << n, 1.0);
-        for (uint32_t sset = 0; sset < (uint32_t(1) << n); ++sset)
-            for (int bit = 0; bit < n; ++bit)   // ascending bit order, as blades_gp_coeff multiplies
-                if ((sset >> bit) & 1u) q.weight[sset] *= d.metric_diag[bit];
-        for (int j = 0; j < q.N; ++j) {
-            const uint32_t b = even ? (uint32_t(j) << 1) | uint32_t(__builtin_popcount(uint32_t(j)) & 1) : uint32_t(j);
-            const int k = __builtin_popcount(b);
-            q.blade.push_back(b);
-            const bool held = ((amask >> k) & 1ULL) && ((la.mask >> k) & 1ULL) && int64_t(bt.index_of[b]) < la.grade_len(k);
-            q.a_off.push_back(held ? int32_t(la.offset(k) + bt.index_of[b]) : -1);
-            if (held && ((flip >> k) & 1ULL)) q.a_neg |= uint64_t(1) << j;
-            int32_t ro = -1;
-            if ((nd.minimal_grade_mask >> k) & 1ULL) {
-                if (!((lr.mask >> k) & 1ULL) || lr.grade_len(k) != int64_t(bt.grade_dim[size_t(k)])) {
-                    fail(GAAST_ERR_MISSING_GRADE, "grade " + std::to_string(k) + " absent from result buffer");
-                    return;
-                }
-                ro = int32_t(lr.offset(k) + bt.index_of[b]);
-                ++q.n_out;
-            }
-            q.res_off.push_back(ro);
-        }
-        q.neg.assign(size_t(q.N), 0);
-        for (int r = 0; r < q.N; ++r)
-            for (int j = 0; j < q.N; ++j)
-                if (reorder_parity(q.blade[size_t(r)] ^ q.blade[size_t(j)], q.blade[size_t(j)])) q.neg[size_t(r)] |= uint64_t(1) << j;
+        if (!blade_set_tables(q, even, a, amask, flip, res, nd.minimal_grade_mask)) return;
         if (!q.n_out) return;
         // the first writer of a fresh buffer that covers every component of it: the zero fill is folded in
         const auto fr = fresh.find(key(res));
@@ -1315,6 +1436,7 @@ void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab,
         case GAAST_OP_PRODUCT:
         case GAAST_OP_EXP_ADJ:
         case GAAST_OP_LOG_ADJ:
+        case GAAST_OP_GEXP_ADJ:
             if (!child_ok(nd.child0) || !child_ok(nd.child1)) throw std::runtime_error("nodes are not in post-order");
             if (nd.opcode == GAAST_OP_PRODUCT && nd.product_kind >= GAAST_PROD_ADJ_LEFT) {
                 const int adj = nd.product_kind & ~7, base = nd.product_kind & 7;
@@ -1324,7 +1446,7 @@ void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab,
             break;
         case GAAST_OP_NEG: case GAAST_OP_EXP: case GAAST_OP_LOG: case GAAST_OP_PROJ:
         case GAAST_OP_REVERSE: case GAAST_OP_GINVOL: case GAAST_OP_SINV: case GAAST_OP_SSQRT:
-        case GAAST_OP_DUAL: case GAAST_OP_UNDUAL: case GAAST_OP_INV:
+        case GAAST_OP_DUAL: case GAAST_OP_UNDUAL: case GAAST_OP_INV: case GAAST_OP_GEXP:
             if (!child_ok(nd.child0)) throw std::runtime_error("nodes are not in post-order");
             break;
         default: throw std::runtime_error("unknown opcode");

@@ -214,6 +214,10 @@ struct Launch {
         DevTable a_off, res_off, neg, weight;
         const void* kernel = nullptr;   // k_mv_inverse<T, N>
     } inv;
+    struct {   // GEXP, GEXP_ADJ
+        DevTable a_off, res_off, g_off, neg, neg_l, neg_r, weight;
+        const void* kernel = nullptr;   // k_mv_gexp<T, N> / k_mv_gexp_adj<T, N>
+    } gexp;
     struct {   // PRODUCT_CSR: k_product_csr, k_product_ell, k_product_ell_chain or the specialised gaast_chain
         DevTable row_start, row_out, entries, coeff;
         struct { DevTable entries, row_map; } pre;        // k_product_ell_chain: the first list
@@ -632,6 +636,57 @@ int run_inverse(const Launch& L, const Operands& o, int64_t batch) {
     p.dom = static_cast<unsigned long long*>(L.domain);
     const int64_t per_block = 256 / s.inv.N;
     launch_kernel(L.inv.kernel, persistent_grid((batch + per_block - 1) / per_block, 8), 256, 0, p);
+    return launch_status();
+}
+
+// ---- GEXP, GEXP_ADJ ------------------------------------------------------------------------------------------------------
+// (one kernel per (T, N) each: nothing is chosen at launch, the variant is 0)
+template <typename T>
+int prepare_gexp(Launch& L, std::string& kernel) {
+    Step& s = L.s;
+    auto& c = L.gexp;
+    const bool adj = s.kind == Step::GEXP_ADJ;
+    using Kern = void (*)(GexpArgs<T>);
+    c.kernel = kernel_address(adj ? static_int<2, 4, 8, 16, 32, 64>(s.inv.N, [](auto n) -> Kern { return k_mv_gexp_adj<T, decltype(n)::value>; })
+                                  : static_int<2, 4, 8, 16, 32, 64>(s.inv.N, [](auto n) -> Kern { return k_mv_gexp<T, decltype(n)::value>; }));
+    if (!c.kernel) return set_err(GAAST_ERR_UNIMPLEMENTED, "no general-exponential kernel for " + std::to_string(s.inv.N) + " blades");
+    Upload<T> up;
+    up.idx(c.a_off, s.inv.a_off); up.idx(c.res_off, s.inv.res_off); up.idx(c.neg, s.inv.neg); up.val(c.weight, s.inv.weight);
+    if (adj) {
+        up.idx(c.g_off, s.inv.g_off); up.idx(c.neg_l, s.inv.adj_neg_l); up.idx(c.neg_r, s.inv.adj_neg_r);
+    }
+    kernel = std::string(adj ? "k_mv_gexp_adj<" : "k_mv_gexp<") + type_name<T>() + "," + std::to_string(s.inv.N) + ">";
+    return up.status;
+}
+
+template <typename T>
+int run_gexp(const Launch& L, const Operands& o, int64_t batch) {
+    const Step& s = L.s;
+    if (batch <= 0) return GAAST_OK;
+    const bool adj = s.kind == Step::GEXP_ADJ;
+    GexpArgs<T> p;
+    p.res = static_cast<T*>(o.res.ptr);
+    p.in = static_cast<const T*>(o.a.ptr);
+    p.cot = adj ? static_cast<const T*>(o.b.ptr) : nullptr;
+    p.res_stride = o.res.stride;
+    p.in_stride = o.a.stride;
+    p.cot_stride = adj ? o.b.stride : 0;
+    p.batch = batch;
+    p.a_off = L.gexp.a_off.as<int32_t>();
+    p.res_off = L.gexp.res_off.as<int32_t>();
+    p.g_off = L.gexp.g_off.as<int32_t>();
+    p.neg = L.gexp.neg.as<uint64_t>();
+    p.neg_l = L.gexp.neg_l.as<uint64_t>();
+    p.neg_r = L.gexp.neg_r.as<uint64_t>();
+    p.weight = L.gexp.weight.as<T>();
+    p.a_neg = s.inv.a_neg;
+    p.wmax = T(s.inv.wmax);
+    p.n = L.n;
+    p.even = s.inv.even;
+    p.beta = s.beta;
+    p.dom = static_cast<unsigned long long*>(L.domain);
+    const int64_t per_block = 256 / s.inv.N;
+    launch_kernel(L.gexp.kernel, persistent_grid((batch + per_block - 1) / per_block, 8), 256, 0, p);
     return launch_status();
 }
 
@@ -1571,6 +1626,8 @@ int prepare_launch(Launch& L, const gaast_hip_program_s& prog) {
     case Step::EXPLOG_ADJ: st = prepare_explog_adj<T>(L, la, lb, kernel); break;
     case Step::DUAL: st = prepare_dual<T>(L, kernel); break;
     case Step::INVERSE: st = prepare_inverse<T>(L, kernel); break;
+    case Step::GEXP:
+    case Step::GEXP_ADJ: st = prepare_gexp<T>(L, kernel); break;
     }
     if (st) return st;
     L.label = kernel.empty() ? s.name : s.name + " :: " + kernel;
@@ -1612,7 +1669,7 @@ int program_create_impl(const gaast_program_desc* desc, gaast_hip_program_t* out
         if (int st = make_launches(d2, small_reg_slab, mirrored, *prog)) return st;
     }
     compile_chains(*prog, desc->flags);
-    if (prog->plan.has_explog || prog->plan.has_inverse)
+    if (prog->plan.has_explog || prog->plan.has_inverse || prog->plan.has_gexp)
         if (int st = prog->domain.upload(std::vector<unsigned long long>(1, 0))) return st;
     for (Launch& L : prog->launches)
         if (int st = prepare_launch(L, *prog)) return st;
@@ -2308,6 +2365,8 @@ int run_launch(const Launch& L, const Operands& o, int64_t batch) {
     case Step::EXPLOG_ADJ: st = run_explog_adj<T>(L, o, batch); break;
     case Step::DUAL: st = run_dual<T>(L, o, batch); break;
     case Step::INVERSE: st = run_inverse<T>(L, o, batch); break;
+    case Step::GEXP:
+    case Step::GEXP_ADJ: st = run_gexp<T>(L, o, batch); break;
     }
     L.variant = variant;
     return st;

@@ -126,7 +126,38 @@ typedef enum gaast_opcode {
      * GAAST_FLAG_EXACT_ORDER changes nothing here: there are no reference bits for an operation the reference lacks.
      * Reverse mode (gaast_program_vjp): with Y the inverse recomputed in every grade of S and g the cotangent of the node,
      * the child gets -ADJ_RIGHT_geometric(ADJ_LEFT_geometric(g, Y), Y), the adjoint of dA -> -(Y dA) Y. */
-    GAAST_OP_INV = 15
+    GAAST_OP_INV = 15,
+    /* General multivector exponential (no reference counterpart): gexp(A) = sum_k A^k / k! under the geometric product, for ANY
+     * multivector -- GAAST_OP_EXP is a closed form that is only right for a single-grade k-vector whose square is a scalar.  One
+     * child.  The blade set S, N = |S|, its ordering (S[j] = j, or (j << 1) | parity(j) for the even set) and the matrix
+     * L_A[r][j] = coeff(r, j) A[r xor j] are those of GAAST_OP_INV; y = exp(L_A) e_scalar.  The node's maximal grade set is
+     * GAAST_OP_INV's: {0, 2, 4, ...} for an even child, {0 .. n} otherwise; it produces the wanted grades of that set, its child is
+     * wanted in all of the child's own grades, and like every arm it ADDS into the buffer that contains it.
+     * Supported: N = 2 ... 64 (any mask for n <= 6, even masks for n = 7; not a bare scalar in a 0-dimensional algebra); anything
+     * else is GAAST_ERR_UNIMPLEMENTED from gaast_hip_program_create, phases 1-3 succeeding on the host.  No flag gates the node and
+     * GAAST_FLAG_EXACT_ORDER changes nothing: there are no reference bits.
+     * Algorithm (scaling and squaring; every sum over j ascending), per item:
+     *   1. theta = wmax * sum_a |A_a|, wmax the largest |metric factor| of the algebra (1 for +-1 / 0 metrics): theta >= ||L_A||_inf.
+     *      The sum is a butterfly over the N components: v <- v + v[j xor m] for m = N/2, N/4, ... 1.
+     *   2. s = the smallest integer >= 0 with theta 2^-s <= 1/2;  A_s = A 2^-s (exact).
+     *   3. theta not finite, or s > 12 (theta > 2048): a domain error.  Every produced component of the item is a quiet NaN and the
+     *      item is counted once in gaast_hip_program_domain_errors (a program with a GEXP step owns the counter).
+     *   4. Taylor by Horner, degree m the smallest with (1/2)^(m+1) / (m+1)! <= eps / 2: m = 8 in f32, 14 in f64.
+     *      q_m = e_0;  q_(k-1) = e_0 + (A_s q_k) / k  for k = m ... 1.
+     *   5. Y_0 = q_0;  Y_(i+1) = Y_i Y_i for i < s;  the result is Y_s.
+     * Accuracy: ||y - exp(A)||_inf <= 2 N eps max(1, theta) ||exp(A)||_inf per item that is no domain error. */
+    GAAST_OP_GEXP = 16,
+    /* Reverse mode of GAAST_OP_GEXP, emitted by gaast_program_vjp: child0 = the cotangent g of the GEXP node (any grades within
+     * S), child1 = the forward operand A; the node's own minimal grade mask is the operand's.  It ADDS into its buffer; no flag.
+     * The reverse sweep of the recurrences above, differentiating what is computed with s held fixed.  For P = X Z let
+     *   ADJL(g, Z)[a] = sum_b coeff(a, b) Z[b] g[a xor b],   ADJR(g, X)[b] = sum_a coeff(a, b) X[a] g[a xor b],
+     * coeff(a, b) the sign and metric factor of L[a xor b][b] (factor index S[a] & S[b]; degenerate metrics included).  Then
+     *   g <- ADJL(g, Y_i) + ADJR(g, Y_i)  for i = s-1 ... 0;   dA_s = 0;
+     *   for k = 1 ... m:  h = g / k;  dA_s += ADJL(h, q_k);  g <- ADJR(h, A_s);
+     *   dA = 2^-s dA_s, restricted to the grades the operand holds.
+     * The forward is recomputed.  No domain check and no count: a domain-error item of the forward has every component NaN (its
+     * scaling factor is taken as NaN, so the arithmetic carries it). */
+    GAAST_OP_GEXP_ADJ = 17
 } gaast_opcode;
 
 /* the five products of src/ast/expr.rs:180-197 (and the regressive product), for compact PRODUCT descriptors */
@@ -274,7 +305,8 @@ int gaast_hip_program_launch_variant(gaast_hip_program_t prog, int i);
 /* GAAST_FLAG_EXP_LOG extension: how many items, since the last call, had an exp / log operand outside the domain (a
  * k-vector whose square is not scalar: |<B B>_{not 0}|^2 > 2^-40 (sum B_i^2)^2); their results are the closed form applied
  * to <B B>_0 regardless.  A program with a GAAST_OP_INV step counts its singular items here too (their produced components are
- * NaN).  Synchronises the library stream; resets the counter.  0 for programs without exp / log / inv. */
+ * NaN), one with a GAAST_OP_GEXP step its domain errors (theta not finite or > 2048; NaN likewise).  Synchronises the library
+ * stream; resets the counter.  0 for programs without exp / log / inv / gexp. */
 int gaast_hip_program_domain_errors(gaast_hip_program_t prog, int64_t *count);
 /* GAAST_FLAG_DEBUG_KEEP_JIT_SOURCE: the HIP source generated for this program ("" if none). */
 const char *gaast_hip_program_jit_source(gaast_hip_program_t prog);

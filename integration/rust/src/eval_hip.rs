@@ -209,6 +209,7 @@ impl<T: GradedData + std::fmt::Debug> SpecializedAst<T> {
                 //     N::Inverse(e) => { d.opcode = OP_INV; d.child0 = index[e]; }
                 // with the node's grade set the even grades for an even child and every grade otherwise, and the child wanted
                 // in all of its grades (a scalar child: ScalarUnaryOp::Inversion, as above).
+                // The general exponential (OP_GEXP) flattens the same way, with the same grade set; its adjoint node OP_GEXP_ADJ is only ever emitted by gaast_program_vjp.
             }
             nodes.push(d);
         }

@@ -29,6 +29,9 @@ pub const OP_DUAL: i32 = 13;
 pub const OP_UNDUAL: i32 = 14;
 // general multivector inverse (no AstNode counterpart): one child, A Y = 1 over the even or the full blade set, N <= 64 blades
 pub const OP_INV: i32 = 15;
+// general multivector exponential by scaling and squaring (no AstNode counterpart), and its reverse-mode node (child0 = cotangent, child1 = operand)
+pub const OP_GEXP: i32 = 16;
+pub const OP_GEXP_ADJ: i32 = 17;
 // compact product kinds (gaast_product_kind); 5 = the regressive product a v b = undual(dual(a) ^ dual(b))
 pub const PROD_REGRESSIVE: i32 = 5;
 
