@@ -73,6 +73,9 @@ struct DenseArgs {
     int pre_scratch;                 // element offset of the list's operand rows in the kernel's LDS
     int left_signs;             // some left_map word has its negate bit set (folded sign arms, permuted basis)
     int out_signs;              // some out_map word has its sign bit set (permuted basis)
+    // k_gp_mfma32p<false, 12, *, *> only (plan.hpp: dense_whole_row_stores; the other kernels do not read them)
+    int right_signs;            // some right_map word has its negate bit set
+    int out_whole;              // every blade has a place in the result row, no reordering sign, beta = 0, no out_scale
     int64_t batch;
 };
 
@@ -732,8 +735,11 @@ using dense_images::mfma16_k;
 // n = 12 (XOR_STEP below: the B image is the quad-plane one of mfma32p_b_planes.hip.hpp, two B addresses stay live -- the
 // other two quads sit at an immediate offset -- and move by one three-operand xor with a lane-constant delta each, the A
 // addresses move once per 64 steps).  There the per-item phases are lean as well: the canonicalising add of the
-// fast staging is a wave-uniform branch (2-3 instead of 4 instructions per word), and the store phase requests the
-// lane's 16 out_map words together instead of waiting for each in turn.
+// fast staging is a wave-uniform branch (2-3 instead of 4 instructions per word), as is the sign xor of a side whose map
+// words carry no sign; the item's first MFMA takes a zero C operand instead of a zeroed accumulator; and where every blade
+// has a plain place in the result row (p.out_whole) the lane's 16 out_map words are read once per launch and each result is
+// one store at a register-held offset from the row's uniform base -- otherwise the store phase requests the 16 words
+// together instead of waiting for each in turn.
 // n = 14 does not fit (4 x 64 KiB) and stays on k_gp_mfma32.
 // ------------------------------------------------------------------------------------------
 // Persistent workgroups: a workgroup walks the groups of IPB items blockIdx.x, blockIdx.x + gridDim.x, ...; when both
@@ -887,13 +893,23 @@ __global__ __launch_bounds__(NDIM == 13 ? 512 : 256, NDIM <= 11 ? 2 : 1) void k_
         for (int b = 0; b < 32; ++b) bits |= block_sign(32 * w + b) << b;
         sgn[w] = bits;
     }
+    // n = 12, whole rows (p.out_whole: every out_map word is a plain offset, nothing accumulated or rescaled): the lane's 16
+    // out_map words depend on (c_hi, h) only -- read once per launch and kept as byte offsets into the item's result row
+    uint32_t ooff[XOR_STEP ? 16 : 1] = {0};
+    if constexpr (XOR_STEP) {
+        if (p.out_whole) {
+            const int32_t* om = p.out_map + (c_hi << 5);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) ooff[r] = uint32_t(om[(r & 3) + 8 * (r >> 2) + 4 * h]) << 2;
+        }
+    }
 
     for (int64_t g = blockIdx.x; g < num_groups; g += gridDim.x) {
         const int64_t item0 = g * IPB;
         const int nitems = int(p.batch - item0 < IPB ? p.batch - item0 : IPB);
         // ---- both operands of the group's items into their +/- images ----
         if (fast) {
-            auto stage_row = [&](int r, bool canon) {
+            auto stage_row = [&](int r, bool canon, bool signs) {
                 const int k = r % IPB, side = r / IPB;
                 if (k < nitems) {
 #pragma unroll
@@ -905,7 +921,7 @@ __global__ __launch_bounds__(NDIM == 13 ? 512 : 256, NDIM <= 11 ? 2 : 1) void k_
                             const uint32_t w = mw[side][4 * m + c];
                             float y = x[c];
                             if (canon) y = 0.f + y;   // the reference's zero-init + add_grades_from copy
-                            const uint32_t yb = __float_as_uint(y) ^ (w & 0x80000000u);
+                            const uint32_t yb = signs ? __float_as_uint(y) ^ (w & 0x80000000u) : __float_as_uint(y);
                             const uint32_t at = uint32_t(k) * uint32_t(item_stride * 4) + (side ? 2u * NEG : 0u) + (((w >> 16) & 0x7fffu) << 2);
                             *(__attribute__((address_space(3))) uint32_t*)(lds + at) = yb;
                             *(__attribute__((address_space(3))) uint32_t*)(lds + at + NEG) = yb ^ 0x80000000u;
@@ -916,11 +932,18 @@ __global__ __launch_bounds__(NDIM == 13 ? 512 : 256, NDIM <= 11 ? 2 : 1) void k_
 #pragma unroll
             for (int r = 0; r < ROWS; ++r) {
                 if constexpr (XOR_STEP) {
-                    // canon is wave-uniform: a branch around two copies instead of an add + a select for every word
-                    if (r / IPB ? p.canon_right : p.canon_left) stage_row(r, true);
-                    else stage_row(r, false);
+                    // canon is wave-uniform: a branch around two copies instead of an add + a select for every word; so is
+                    // "some map word of this side negates" (a side without: no sign xor -- the left side of a Euclidean product)
+                    const bool signs = r / IPB ? p.right_signs : p.left_signs;
+                    if (r / IPB ? p.canon_right : p.canon_left) {
+                        if (signs) stage_row(r, true, true);
+                        else stage_row(r, true, false);
+                    } else {
+                        if (signs) stage_row(r, false, true);
+                        else stage_row(r, false, false);
+                    }
                 } else {
-                    stage_row(r, r / IPB ? p.canon_right : p.canon_left);
+                    stage_row(r, r / IPB ? p.canon_right : p.canon_left, true);
                 }
             }
         } else {
@@ -1052,36 +1075,45 @@ __global__ __launch_bounds__(NDIM == 13 ? 512 : 256, NDIM <= 11 ? 2 : 1) void k_
                 // quad addresses move by one three-operand xor each per step (dlt[t] with t a compile-time constant inside
                 // the chunk, the step's u bit from the scalar unit) -- 2 vector instructions per step + 16 per chunk (one xor per A
                 // address: bit 13 is clear in every ak0, so the second xor restores them for the next item)
+                // The item's first MFMA takes a zero C operand (an inline constant: 0 + a b has the bits of a b added to a zeroed
+                // accumulator, and 16 accumulator writes per item go away).  For that, step 0 stands in front of the chunk loop,
+                // whose body is steps 1 ... 63 of its chunk, the move of the A addresses and, after the first chunk, step 0 of
+                // the second: the steps run in the order 0 ... 127 as before.
+                static_assert(!XOR_STEP || H == 128, "two chunks of 64 steps");
                 uint32_t xe = lds0 + (b_base | b_planes::xe0(uint32_t(c_hi), uint32_t(h)));   // step 0: a_hi = 0, block sign +
                 uint32_t xo = lds0 + (b_base | b_planes::xo0(uint32_t(c_hi), uint32_t(h)));
-#pragma unroll 1
-                for (int c = 0; c < H / 64; ++c) {
-                    const uint32_t udw[2] = {c == 0 ? ud[0] : ud[2], c == 0 ? ud[1] : ud[3]};
+                // step j of a chunk (udw: the chunk's 64 u bits); first: the item's first step
+                auto xstep = [&](int j, uint32_t udw0, uint32_t udw1, bool first) __attribute__((always_inline)) {
+                    uint32_t bw[16], aw[16];
 #pragma unroll
-                    for (int j = 0; j < 64; ++j) {
-                        uint32_t bw[16], aw[16];
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            // (bits 12 of xe and xo stay clear: the deltas move bits 4 ... 10 and the NEG bit)
-                            const uint4v v = *(__attribute__((address_space(3))) const uint4v*)size_t((q & 2 ? xo : xe) + uint32_t(q & 1) * b_planes::kQuadStride);
-                            bw[4 * q + 0] = v.x; bw[4 * q + 1] = v.y; bw[4 * q + 2] = v.z; bw[4 * q + 3] = v.w;
-                        }
-#pragma unroll
-                        for (int t = 0; t < 16; ++t)
-                            aw[t] = *(__attribute__((address_space(3))) const uint32_t*)size_t(ak[t] + uint32_t(j << 7));
-#pragma unroll
-                        for (int t = 0; t < 16; ++t)
-                            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(aw[t]), __uint_as_float(bw[t]), acc, 0, 0, 0);
-                        asm volatile("" ::: "memory");   // keep the LDS reads of a step in their step
-                        // on to step a_hi + 1
-                        uint32_t su = __builtin_amdgcn_readfirstlane(((udw[j >> 5] >> (j & 31)) & 1u) << (n + 2));
-                        asm("" : "+s"(su));   // in a scalar register: the third operand of the xor
-                        const uint32_t d = dlt[j < 63 ? __builtin_ctz(~uint32_t(j)) : 6];   // (63 -> 64 flips seven bits)
-                        xe = xor3(xe, d, su);
-                        xo = xor3(xo, d, su);
+                    for (int q = 0; q < 4; ++q) {
+                        // (bits 12 of xe and xo stay clear: the deltas move bits 4 ... 10 and the NEG bit)
+                        const uint4v v = *(__attribute__((address_space(3))) const uint4v*)size_t((q & 2 ? xo : xe) + uint32_t(q & 1) * b_planes::kQuadStride);
+                        bw[4 * q + 0] = v.x; bw[4 * q + 1] = v.y; bw[4 * q + 2] = v.z; bw[4 * q + 3] = v.w;
                     }
 #pragma unroll
+                    for (int t = 0; t < 16; ++t)
+                        aw[t] = *(__attribute__((address_space(3))) const uint32_t*)size_t(ak[t] + uint32_t(j << 7));
+#pragma unroll
+                    for (int t = 0; t < 16; ++t)
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(aw[t]), __uint_as_float(bw[t]), first && t == 0 ? float16v(0.f) : acc, 0, 0, 0);
+                    asm volatile("" ::: "memory");   // keep the LDS reads of a step in their step
+                    // on to step a_hi + 1
+                    uint32_t su = __builtin_amdgcn_readfirstlane((((j >> 5 ? udw1 : udw0) >> (j & 31)) & 1u) << (n + 2));
+                    asm("" : "+s"(su));   // in a scalar register: the third operand of the xor
+                    const uint32_t d = dlt[j < 63 ? __builtin_ctz(~uint32_t(j)) : 6];   // (63 -> 64 flips seven bits)
+                    xe = xor3(xe, d, su);
+                    xo = xor3(xo, d, su);
+                };
+                xstep(0, ud[0], ud[1], true);
+#pragma unroll 1
+                for (int c = 0; c < 2; ++c) {
+                    const uint32_t udw0 = c == 0 ? ud[0] : ud[2], udw1 = c == 0 ? ud[1] : ud[3];
+#pragma unroll
+                    for (int j = 1; j < 64; ++j) xstep(j, udw0, udw1, false);
+#pragma unroll
                     for (int t = 0; t < 16; ++t) ak[t] ^= 64u << 7;   // to the second chunk, and back for the next item
+                    if (c == 0) xstep(0, ud[2], ud[3], false);
                 }
             } else {
                 for (int a0 = 0; a0 < H; a0 += 8) {
@@ -1099,27 +1131,38 @@ __global__ __launch_bounds__(NDIM == 13 ? 512 : 256, NDIM <= 11 ? 2 : 1) void k_
             // ---- accumulator (row = c_lo, column = this lane's c_hi) -> graded row ----
             float* orow = p.out + (item0 + it) * p.out_stride;
             if constexpr (XOR_STEP) {
-                // store_result's arithmetic, with the lane's 16 out_map words requested together (one round trip to the
-                // cache instead of sixteen in turn) and the reordering signs behind a wave-uniform branch
-                const int32_t* om = p.out_map + (c_hi << 5);
-                int32_t ow[16];
+                // (the offsets are re-defined in place, on every path: otherwise their zero-extension is hoisted out of the item loop
+                // as a 64-bit lane constant and every store pays a 64-bit addition -- docs/DESIGN_rounds_1-3.md, 4.1)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) ow[r] = om[(r & 3) + 8 * (r >> 2) + 4 * h];
-                asm volatile("" ::: "memory");
-                auto put = [&](bool signs, bool beta) {
+                for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(ooff[r]));
+                if (p.out_whole) {
+                    // whole rows: one store per result in (uniform row base) + (32-bit lane offset) form: no compare, no select,
+                    // no address arithmetic
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int32_t w = ow[r];
-                        if (w < 0) continue;
-                        float v = acc[r];
-                        if (out_scale) v = v * out_scale[(c_hi << 5) + (r & 3) + 8 * (r >> 2) + 4 * h];
-                        if (signs && (w & 0x40000000)) v = beta ? -v : 0.f + (-v);
-                        float* dst = orow + (signs ? w & 0x3fffffff : w);
-                        *dst = beta ? *dst + v : v;
-                    }
-                };
-                if (p.out_signs) put(true, p.beta != 0);
-                else put(false, p.beta != 0);
+                    for (int r = 0; r < 16; ++r) *reinterpret_cast<float*>(reinterpret_cast<char*>(orow) + ooff[r]) = acc[r];
+                } else {
+                    // store_result's arithmetic, with the lane's 16 out_map words requested together (one round trip to the
+                    // cache instead of sixteen in turn) and the reordering signs behind a wave-uniform branch
+                    const int32_t* om = p.out_map + (c_hi << 5);
+                    int32_t ow[16];
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) ow[r] = om[(r & 3) + 8 * (r >> 2) + 4 * h];
+                    asm volatile("" ::: "memory");
+                    auto put = [&](bool signs, bool beta) {
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const int32_t w = ow[r];
+                            if (w < 0) continue;
+                            float v = acc[r];
+                            if (out_scale) v = v * out_scale[(c_hi << 5) + (r & 3) + 8 * (r >> 2) + 4 * h];
+                            if (signs && (w & 0x40000000)) v = beta ? -v : 0.f + (-v);
+                            float* dst = orow + (signs ? w & 0x3fffffff : w);
+                            *dst = beta ? *dst + v : v;
+                        }
+                    };
+                    if (p.out_signs) put(true, p.beta != 0);
+                    else put(false, p.beta != 0);
+                }
             } else {
                 const int32_t* om = p.out_map + (c_hi << 5);
 #pragma unroll

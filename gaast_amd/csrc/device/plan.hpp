@@ -79,6 +79,8 @@ struct Step {
         int left_full = 0, right_full = 0, out_full = 0;
         int left_contig = 0, right_contig = 0;
         int left_signs = 0, out_signs = 0;   // some left_map word negates / some out_map word carries a reordering sign
+        int right_signs = 0;                 // some right_map word negates (the image signs of the B side, folded sign arms)
+        int out_all = 0;                     // every blade of the permuted basis is produced: no out_map word is -1
         uint32_t neg_hi = 0, zero_hi = 0;
         uint32_t neg_lo = 0;   // lo basis vectors (of the permuted basis) that square to -1
         int neg_lo_all = 0;    // vector-FMA kernel: the NEGLO instantiation (all four lo vectors square to -1)
@@ -277,6 +279,13 @@ inline bool reads(const Step& s, BufRef buf) {
     for_each_read(s, [&](BufRef r) { hit = hit || r == buf; });
     return hit;
 }
+
+// Launch-time forms of k_gp_mfma32p<false, 12, *, *>, as the dense launcher (runtime.hip: run_dense) derives them from the plan's
+// maps; tests/cpp/dense_flags_driver.cpp checks them against the map words.
+//   whole rows: every blade of the permuted basis has a place in the result row, no reordering sign, nothing accumulated, no rescaled
+//   basis -- each result is one store at a lane-constant offset from the item's row;
+//   signs per side: a side whose map words carry no sign bit is staged without the sign xor.
+inline bool dense_whole_row_stores(const Step& s) { return s.dense.out_all && !s.dense.out_signs && !s.beta && !s.dense.scaled; }
 
 // limits of this back end (gfx950): a product whose staged operands exceed the LDS of a CU, or whose comp-mul list
 // exceeds the table budget, is valid in the reference but refused by gaast_hip_program_create (UNIMPLEMENTED)

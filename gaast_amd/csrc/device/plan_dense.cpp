@@ -398,7 +398,10 @@ void build_out_map(const LowerState& st, const FrameMap& fm, const Layout& lr, u
     ds.out_full = lr.row_len == (int64_t(1) << n2);
     for (uint32_t m = 0; m < (1u << n2); ++m) ds.out_full = ds.out_full && ds.out_map[m] >= 0;
     for (uint32_t w : ds.left_map) ds.left_signs |= int(w >> 31);
+    for (uint32_t w : ds.right_map) ds.right_signs |= int(w >> 31);
     for (int32_t w : ds.out_map) ds.out_signs |= int(w >= 0 && (uint32_t(w) & 0x40000000u));
+    ds.out_all = 1;
+    for (int32_t w : ds.out_map) ds.out_all = ds.out_all && w >= 0;
 }
 
 // the metric of the permuted basis as the kernels take it: sign bits of the lo vectors, sign and null bits of the hi vectors

@@ -1066,6 +1066,8 @@ int run_dense(const Launch& L, const Operands& o, int64_t batch, int* variant) {
     p.neg_lo = s.dense.neg_lo;
     p.left_signs = s.dense.left_signs;
     p.out_signs = s.dense.out_signs;
+    p.right_signs = s.dense.right_signs;
+    p.out_whole = dense_whole_row_stores(s);
     p.pre_left = p.pre_right = nullptr;
     p.pre_entries = nullptr;
     if (s.dense.chained) {   // the left operand is a comp-mul list over two other rows, evaluated in LDS while staging
