@@ -1,7 +1,7 @@
 // The operand images of the dense-product kernels, stated once: the order in which a kernel multiplies the words of a block (its
 // term-order table), where the staging puts blade m of the permuted basis inside an image (its position function), how many low
 // basis vectors a family folds into compile-time signs, how k_gp_mfma6 deals components to lanes, and what a workgroup of each
-// family holds in LDS.  The plan builder (plan_dense.cpp: build_operand_map; plan.cpp: chain_sparse_into_dense), the kernels
+// family holds in LDS.  The plan builder (plan_dense.cpp: build_operand_map; plan_passes.cpp: chain_sparse_into_dense), the kernels
 // (kernels_dense.hip.hpp take their term orders from here), the launcher (runtime.hip: prepare_dense) and a host test
 // (tests/cpp/dense_images_driver.cpp) read this file.  Plain constexpr functions, no HIP types: it compiles as C++ and as HIP.
 // (The .hip.hpp suffix puts it into the library's revision string, which hashes device/*.hip.hpp.)

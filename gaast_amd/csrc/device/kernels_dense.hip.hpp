@@ -57,7 +57,7 @@ struct DenseArgs {
     const T* left_scale;
     const T* right_scale;
     const T* out_scale;
-    // chained product (plan.cpp: chain_sparse_into_dense): the LEFT operand is the result of a short comp-mul list over two
+    // chained product (plan_passes.cpp: chain_sparse_into_dense): the LEFT operand is the result of a short comp-mul list over two
     // other rows; it is evaluated in LDS while staging (stage_from_list), `left` is unused.  NULL otherwise.
     const T* pre_left;
     const T* pre_right;

@@ -88,7 +88,7 @@ struct Step {
         int mfma16_quads = 0;  // MFMA16X4 in f32: the B image in the 16-byte-quad layout
         int spinor_lam_bit = -1, spinor_has_alpha = 0;  // index basis of the matrix-representation kernels: spinor_basis.hpp
         int spinor_m = 0;      // SPINOR: log2 of the matrix size
-        // (plan.cpp: chain_sparse_into_dense): the LEFT operand is the result of a short comp-mul list over two other rows
+        // (plan_passes.cpp: chain_sparse_into_dense): the LEFT operand is the result of a short comp-mul list over two other rows
         // (eval.rs:61-86 with a cached operand that nothing else reads: R X in R X ~R) -- `pre`.  The list is evaluated in LDS while
         // the dense kernel stages its operands -- reference order, same roundings -- and the intermediate never goes through HBM.
         int chained = 0;
@@ -108,7 +108,7 @@ struct Step {
         int width = 0;                    // > 0: rows of one length with +-1 coefficients
     } pre;
 
-    // PRODUCT_CSR (ELL form), list chain (plan.cpp: chain_list_into_list): one operand of this list is the result of ANOTHER list
+    // PRODUCT_CSR (ELL form), list chain (plan_passes.cpp: chain_list_into_list): one operand of this list is the result of ANOTHER list
     // (`pre`) that nothing else reads -- (R X) ~R projected on a grade.  Both lists run in one k_product_ell_chain launch, the mid
     // row stays in LDS.
     struct Chain {
@@ -126,7 +126,7 @@ struct Step {
         int on = 0;                      // 1: source was generated (runtime.hip compiles it)
         std::string source;
         std::vector<uint32_t> ent1, pos1, ent2, out2;
-        int single = 0;                  // the kernel runs a SINGLE list (few long rows): plan.cpp: jit_long_row_lists
+        int single = 0;                  // the kernel runs a SINGLE list (few long rows): plan_passes.cpp: jit_long_row_lists
         int fold_prev = 0;               // ... and, once compiled, also the covering copy_grades_from step right before it
         BufRef init_src;                 // ... whose source gives the accumulators' starting values (pos1 = its offsets)
         int ipb = 0, threads = 0;
@@ -230,7 +230,7 @@ struct Step {
     // (`inv`, built by the same function: plan.cpp: blade_set_tables).  GEXP_ADJ (GAAST_OP_GEXP_ADJ): res += the cotangent of A from
     // A = row `a` and the cotangent g = row `b` of the forward result; inv.res_off then addresses the operand's grades in res.
 
-    // REDUCE_SCALE (plan.cpp: fuse_reduce_scale): a product whose result is ONE scalar component (a single long row: norm_sq), an
+    // REDUCE_SCALE (plan_passes.cpp: fuse_reduce_scale): a product whose result is ONE scalar component (a single long row: norm_sq), an
     // optional ScalarUnaryOp on it, and a product of one-term rows that multiplies another row by that scalar -- the versor inverse
     // a.rev() * a.norm_sq().sinv() and normalisations, where the rows no longer fit a fused slab (n >= 9) -- in ONE launch, one wave per
     // item.  a / b = the reduction's operands.
@@ -249,7 +249,7 @@ struct Step {
         std::vector<uint32_t> sign_words;   // ... and the lanes' sign words
     } reduce;
 
-    // ELEMENTWISE (plan.cpp: fuse_elementwise_runs): a run of AXPY / FLIP steps on one buffer (and, when that buffer is only the operand
+    // ELEMENTWISE (plan_passes.cpp: fuse_elementwise_runs): a run of AXPY / FLIP steps on one buffer (and, when that buffer is only the operand
     // of a product of one-term rows with a scalar, that product too: the scaling epilogue) in one pass
     struct Elementwise {
         std::vector<BufRef> src;           // the source buffers
@@ -306,7 +306,10 @@ struct Plan {
     std::vector<std::vector<double>> const_rows;
     std::vector<Layout> input_layouts;
     std::vector<Layout> node_buffers;  // cache buffers other than the root's
-    std::vector<char> node_dead;       // ... that a chained product made unnecessary (never allocated)
+    std::vector<char> node_dead;       // ... that no step touches any more, never allocated: the mid row of a chain (chain_sparse_into_dense,
+                                       // chain_list_into_list), the buffer of an element-wise run with its scaling folded in
+                                       // (fuse_elementwise_runs), the scalar of fuse_reduce_scale.  Sized by build_plan; plan_passes.cpp: mark_dead
+                                       // is its only writer
     Layout out_layout;
     std::vector<Step> steps;
     int error = GAAST_OK;              // what the reference would have panicked with, at eval
@@ -325,6 +328,14 @@ struct Plan {
     // (>= 0), which the last LINMAP step moves back into `out`
     std::vector<int> basis_slot_buf;
     int basis_out_buf = -1;
+
+    const Layout& layout(BufRef r) const {   // the rows of a buffer a step names (r.idx >= 0)
+        switch (r.kind) {
+        case BufKind::NODE: return node_buffers[size_t(r.idx)];
+        case BufKind::INPUT: return input_layouts[size_t(r.idx)];
+        default: return out_layout;
+        }
+    }
 };
 
 // Throws std::runtime_error (-> GAAST_ERR_INVALID_PROGRAM) on malformed input.  small_reg_slab: the one-item-per-thread

@@ -40,10 +40,6 @@ struct SlabLayout {
                : r.kind == BufKind::INPUT ? (canon ? in_base_canon : in_base)[size_t(r.idx)]
                                           : out_base;
     }
-    const Layout& layout_of(BufRef r) const {
-        return r.kind == BufKind::NODE ? plan.node_buffers[size_t(r.idx)]
-               : r.kind == BufKind::INPUT ? plan.input_layouts[size_t(r.idx)] : plan.out_layout;
-    }
     int input_len(size_t i) const { return int(plan.input_layouts[size_t(inputs[i].slot)].row_len); }
 };
 
@@ -185,7 +181,7 @@ bool encode_uops(const SlabLayout& lay, Step::Fused& f, uint64_t& entries) {
         std::vector<uint32_t> misc;   // element-wise ops: chunks of <= 30, dealt round
         switch (s.kind) {
         case Step::ZERO: {
-            const uint32_t len = uint32_t(lay.layout_of(s.res).row_len);
+            const uint32_t len = uint32_t(lay.plan.layout(s.res).row_len);
             for (uint32_t o = 0; o < len; o += 8) misc.push_back(mop(uop::ZERO, rb + o, std::min<uint32_t>(8, len - o)));
             break;
         }
@@ -362,7 +358,7 @@ void step_statements(const SlabLayout& lay, const Step& s, const StmtStyle& st, 
     std::vector<std::string> ew;   // element-wise statements
     switch (s.kind) {
     case Step::ZERO:
-        for (int64_t o = 0; o < lay.layout_of(s.res).row_len; ++o) ew.push_back(st.el(rb + uint32_t(o)) + " = T(0);");
+        for (int64_t o = 0; o < lay.plan.layout(s.res).row_len; ++o) ew.push_back(st.el(rb + uint32_t(o)) + " = T(0);");
         break;
     case Step::AXPY:
         for (uint32_t m : s.axpy_map) {

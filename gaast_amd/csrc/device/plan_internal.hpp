@@ -1,5 +1,5 @@
 // What the translation units of the plan builder share (device/plan*.cpp: plan.cpp, plan_dense.cpp, plan_fused.cpp,
-// plan_chain_jit.cpp); not part of plan.hpp's interface.
+// plan_chain_jit.cpp, plan_passes.cpp); not part of plan.hpp's interface.
 #pragma once
 #include <map>
 #include <utility>
@@ -18,6 +18,13 @@ int fused_slab(const Plan& plan, bool small_reg_slab);
 void make_chain_jit(const Plan& plan, Step& c, const Step* wp, int64_t l1, int64_t r1, int64_t mid, int64_t r2, int alias, int side, bool covered,
                     const std::vector<uint32_t>* init_off = nullptr);
 
+// plan_passes.cpp.  The whole-plan rewrites of a lowered plan that was not fused whole, in this order: fuse_elementwise_runs,
+// fuse_reduce_scale, chain_sparse_into_dense, uniform_csr_to_ell, chain_list_into_list, jit_long_row_lists.
+void run_plan_passes(Plan& plan);
+// ... two of them, which build_plan also tries on their own (a program that is exactly one list chain)
+void uniform_csr_to_ell(Plan& plan);
+void chain_list_into_list(Plan& plan);
+
 // The state of the walk over the program (plan.cpp: struct Lowering derives from it) that the product paths of plan_dense.cpp work on.
 struct LowerState {
     const gaast_program_desc& d;
@@ -29,13 +36,7 @@ struct LowerState {
     LowerState(const gaast_program_desc& desc, Plan& p) : d(desc), plan(p), bt(desc.vec_space_dim) {}
 
     const gaast_node_desc& node(int i) const { return d.nodes[i]; }
-    const Layout& layout(BufRef r) const {
-        switch (r.kind) {
-        case BufKind::NODE: return plan.node_buffers[size_t(r.idx)];
-        case BufKind::INPUT: return plan.input_layouts[size_t(r.idx)];
-        default: return plan.out_layout;
-        }
-    }
+    const Layout& layout(BufRef r) const { return plan.layout(r); }
     static std::pair<int, int> key(BufRef r) { return {int(r.kind), r.idx}; }
     void touch(BufRef r) { fresh.erase(key(r)); }
 

@@ -744,7 +744,7 @@ int prepare_list(Launch& L, const Layout& la, const Layout& lb, std::string& ker
         return GAAST_OK;
     }
     if (s.chain.side) {
-        // two lists in one launch, the mid row in LDS (plan.cpp: chain_list_into_list): IPB items per workgroup
+        // two lists in one launch, the mid row in LDS (plan_passes.cpp: chain_list_into_list): IPB items per workgroup
         c.chain_bytes = size_t(s.chain.ent2_lds) + size_t(s.chain.item_stride) * size_t(s.chain.ipb) * sizeof(T);
         if (c.chain_bytes > g_max_lds) return set_err(kChainTooBig, "list chain does not fit in LDS (" + s.name + ")");
         const int64_t pairs2 = int64_t(c.row_out.count) * s.chain.ipb;
@@ -1257,7 +1257,7 @@ int run_explog_adj(const Launch& L, const Operands& o, int64_t batch) {
     return launch_status();
 }
 
-// ---- ELEMENTWISE: a run of element-wise arms (and the scaling product after it) in one pass: plan.cpp: fuse_elementwise_runs ---
+// ---- ELEMENTWISE: a run of element-wise arms (and the scaling product after it) in one pass: plan_passes.cpp: fuse_elementwise_runs ---
 template <typename T>
 int prepare_elementwise(Launch& L, std::string& kernel) {
     Step& s = L.s;
@@ -1600,14 +1600,7 @@ template <typename T>
 int prepare_launch(Launch& L, const gaast_hip_program_s& prog) {
     const Plan& plan = prog.plan;
     Step& s = L.s;
-    auto layout_of = [&](BufRef r) -> Layout {
-        if (r.idx < 0) return Layout();
-        switch (r.kind) {
-        case BufKind::NODE: return plan.node_buffers[size_t(r.idx)];
-        case BufKind::INPUT: return plan.input_layouts[size_t(r.idx)];
-        default: return plan.out_layout;
-        }
-    };
+    auto layout_of = [&](BufRef r) { return r.idx < 0 ? Layout() : plan.layout(r); };
     L.n = (s.kind == Step::PRODUCT_DENSE && s.dense.n) ? s.dense.n : plan.n;   // parity-pure products run in Cl(n - 1)
     L.domain = prog.domain.ptr;
     std::string kernel;

@@ -1,6 +1,7 @@
 // CPU-only: writes every generated artifact of every step gaast::build_plan produces for a fixed corpus -- the hiprtc sources of
 // the fused-plan kernels (gaast_jit) and of the list chain (gaast_chain), the k_ast_fused micro-op stream and the tables built next
-// to them -- into the directory argv[1], one file per (case, step, artifact).  tests/test_codegen_digests.py compares length and
+// to them, the wiring of every step, what the whole-plan passes build (plan_passes.cpp) and the plan's dead cache buffers -- into the
+// directory argv[1], one file per (case, step, artifact).  tests/test_codegen_digests.py compares length and
 // SHA-256 of each file with tests/golden/codegen_digests.json: the strings are what the runtime compiles and what the compiled-code
 // cache is keyed by, so equal bytes mean equal results, speed and cache behaviour.  Reads only plan.hpp fields, calls only
 // build_plan (and gaast_program_vjp for the adjoint programs).  One line per step on stdout (the test checks from them that the corpus still reaches every form).
@@ -85,18 +86,63 @@ static void put_product(const std::string& stem, const gaast::Step& s) {
     }
 }
 
+static std::string field(const char* name, long long v) { return std::string(" ") + name + " " + std::to_string(v); }
+
+// how a step is wired into the plan (every kind), and every table and scalar field the whole-plan passes build (plan_passes.cpp): the
+// element-wise pass, the reduction with its scaling, the list chain
+static void put_pass_fields(const std::string& stem, const gaast::Step& s) {
+    put(stem, "wiring", "kind " + std::to_string(int(s.kind)) + " res " + ref_text(s.res) + " a " + ref_text(s.a) + " b " + ref_text(s.b) + field("beta", s.beta) +
+                            field("canon_a", s.canon_a) + field("canon_b", s.canon_b) + " pre.a " + ref_text(s.pre.a) + " pre.b " + ref_text(s.pre.b) +
+                            field("n_entries", (long long)s.n_entries) + "\n");
+    if (s.kind == gaast::Step::ELEMENTWISE) {
+        const gaast::Step::Elementwise& q = s.ew;
+        std::string src = "src";
+        for (gaast::BufRef r : q.src) src += " " + ref_text(r);
+        put(stem, "ew_scalars", src + "\n" + field("n_ops", q.n_ops).substr(1) + field("load_first", q.load_first) + field("scale", q.scale) + field("scalar_off", q.scalar_off) +
+                                    field("canon_v", q.canon_v) + field("canon_s", q.canon_s) + field("s_is_left", q.s_is_left) + "\n");
+        put_vec(stem, "ew_ops", q.ops);
+        put_vec(stem, "ew_comp_off", q.comp_off);
+        put_vec(stem, "ew_out_off", q.out_off);
+        put_vec(stem, "ew_coeff", q.coeff);
+        std::printf(" | EW scale=%d n_ops=%d", q.scale, q.n_ops);
+    }
+    if (s.kind == gaast::Step::REDUCE_SCALE) {
+        const gaast::Step::Reduce& q = s.reduce;
+        put_vec(stem, "reduce_ent1", q.ent1);
+        put_vec(stem, "reduce_coeff1", q.coeff1);
+        put_vec(stem, "reduce_ent2", q.ent2);
+        put_vec(stem, "reduce_coeff2", q.coeff2);
+        put_vec(stem, "reduce_sign_words", q.sign_words);
+        put(stem, "reduce_scalars", "x " + ref_text(q.x) + field("canon_x", q.canon_x) + field("canon_s", q.canon_s) + field("s_is_left", q.s_is_left) + field("op", q.op) +
+                                        field("wave", q.wave) + "\n");
+        std::printf(" | REDUCE op=%d wave=%d", q.op, q.wave);
+    }
+    if (s.chain.side) {
+        const gaast::Step::Chain& q = s.chain;
+        put(stem, "chain_scalars", "side " + std::to_string(q.side) + field("alias", q.alias) + field("mid_len", q.mid_len) + field("canon_mid", q.canon_mid) +
+                                       field("covered", q.covered) + field("ipb", q.ipb) + field("item_stride", q.item_stride) + field("ent2_lds", q.ent2_lds) + "\n");
+        std::printf(" | LINK side=%d alias=%d", q.side, q.alias);
+    }
+}
+
 // small_reg_slab: what runtime.hip passes when it rebuilds a plan whose one-item-per-thread trial compilation used too many registers;
 // mirrored: the orthogonal basis of a Gram metric whose Q has det -1
 static void dump_desc(const char* what, const gaast_program_desc& desc, bool small_reg_slab = false, bool mirrored = false) {
     gaast::Plan plan;
     gaast::build_plan(desc, plan, small_reg_slab, mirrored);
     if (plan.steps.empty()) std::printf("%s: no steps\n", what);
+    {   // the cache buffers no launch needs
+        std::string dead = "node_buffers " + std::to_string(plan.node_buffers.size()) + " node_dead";
+        for (char c : plan.node_dead) dead += c ? " 1" : " 0";
+        put(what, "plan_node_dead", dead + "\n");
+    }
     for (size_t k = 0; k < plan.steps.size(); ++k) {
         const gaast::Step& s = plan.steps[k];
         const std::string stem = std::string(what) + ".s" + std::to_string(k);
         put(stem, "name", s.name);
         std::printf("%s s%zu %s", what, k, s.name.c_str());
         put_product(stem, s);
+        put_pass_fields(stem, s);
         if (s.kind == gaast::Step::FUSED) {
             const gaast::Step::Fused& f = s.fused;
             put(stem, "fused_jit_source", f.jit_source);
@@ -174,6 +220,19 @@ static gaast_expr_t unary(int n) {   // element-wise arms, then a scaling produc
     const int k = n / 2;
     gaast_expr_t a = gaast_expr_input(0, uint64_t(1) << k, n), b = gaast_expr_input(1, uint64_t(1) << k, n), sc = gaast_expr_input(2, 1, n);
     return gaast_expr_product(gaast_expr_rev(gaast_expr_add(gaast_expr_neg(gaast_expr_rev(a)), gaast_expr_ginvol(b))), sc, GP);
+}
+static gaast_expr_t unary_unscaled(int n) {   // ... without the scaling product
+    const int k = n / 2;
+    gaast_expr_t a = gaast_expr_input(0, uint64_t(1) << k, n), b = gaast_expr_input(1, uint64_t(1) << k, n);
+    return gaast_expr_rev(gaast_expr_add(gaast_expr_neg(gaast_expr_rev(a)), gaast_expr_ginvol(b)));
+}
+static gaast_expr_t times_norm(int n, bool root) {   // a * norm_sq(a) / a * sqrt(norm_sq(a)), a even
+    gaast_expr_t a = gaast_expr_input(0, even_mask(n), n), s = gaast_expr_norm_sq(a);
+    return gaast_expr_product(a, root ? gaast_expr_sqrt(s) : s, GP);
+}
+static gaast_expr_t sandwich_right_first(int n) {   // R (X ~R): the mid row is the second list's RIGHT operand
+    gaast_expr_t r = gaast_expr_input(0, even_mask(n), n), x = gaast_expr_input(1, 0x2, n);
+    return gaast_expr_product(r, gaast_expr_product(x, gaast_expr_rev(r), GP), GP);
 }
 static gaast_expr_t cfg1(int n) {   // (a + b * c).g(2), full operands
     gaast_expr_t a = gaast_expr_input(0, full_mask(n), n), b = gaast_expr_input(1, full_mask(n), n), c = gaast_expr_input(2, full_mask(n), n);
@@ -337,5 +396,19 @@ int main(int argc, char** argv) {
         dump("list_regressive12_mirrored_f64", gaast_expr_product(b, gaast_expr_input(3, uint64_t(3) << 10, 12), GAAST_PROD_REGRESSIVE), 12, euclid(12), GAAST_F64, 0, false, true);
         dump_vjp("list_adj8_exact_f32", full(8), 8, euclid(8), GAAST_F32, EXACT, 0);
     }
+
+    // ---- the whole-plan passes the cases above do not reach (tests/test_codegen_digests.py: test_corpus_reaches_every_form_of_the_plan_passes)
+    for (int dtype : {GAAST_F32, GAAST_F64}) {
+        const std::string t = dtype == GAAST_F32 ? "_f32" : "_f64";
+        // five element-wise arms on grade-6 rows in one pass; with the scaling product as its epilogue: the run's buffer is dead
+        dump(("unary12" + t).c_str(), unary(12), 12, euclid(12), dtype, 0);
+        dump(("unary12_unscaled" + t).c_str(), unary_unscaled(12), 12, euclid(12), dtype, 0);
+        for (int n : {10, 12})   // reduce_scale, 1 / s: a wave keeps the row in registers (tolerance mode) / streams it (exact order)
+            for (uint32_t flags : {0u, EXACT})
+                dump(("vinv" + std::to_string(n) + t + (flags ? "_exact" : "")).c_str(), vinv(n), n, euclid(n), dtype, flags);
+    }
+    dump("times_sqrt_norm12_f64", times_norm(12, true), 12, euclid(12), GAAST_F64, 0);    // reduce_scale, sqrt(s)
+    dump("times_norm12_f64", times_norm(12, false), 12, euclid(12), GAAST_F64, 0);        // reduce_scale, the scalar as it is
+    dump("sand9g1_right_first_f64", gaast_expr_g(sandwich_right_first(9), 1), 9, euclid(9), GAAST_F64, 0);   // list chain, side 2
     return g_fail;
 }

@@ -29,14 +29,9 @@ static gaast_expr_t H(gaast_expr_t e) {
     return e;
 }
 
-static const gaast::Layout& layout_of(const gaast::Plan& plan, gaast::BufRef r) {
-    return r.kind == gaast::BufKind::NODE ? plan.node_buffers[size_t(r.idx)]
-           : r.kind == gaast::BufKind::INPUT ? plan.input_layouts[size_t(r.idx)] : plan.out_layout;
-}
-
 // every offset of a DUAL step stays inside the rows it indexes, and no result component is written twice
 static void check_dual_step(const gaast::Plan& plan, const gaast::Step& s) {
-    const gaast::Layout &la = layout_of(plan, s.a), &lr = layout_of(plan, s.res);
+    const gaast::Layout &la = plan.layout(s.a), &lr = plan.layout(s.res);
     CHECK(!(s.a == s.res));
     CHECK(s.dual.total > 0 && s.dual.neg.size() == size_t((s.dual.total + 31) / 32));
     CHECK(s.dual.segs.size() <= size_t(GAAST_MAX_DIM + 1));

@@ -35,12 +35,8 @@ static int count_op(const gaast_program_desc& d, int opcode) {
 
 // every table and offset of an EXPLOG_ADJ step stays inside the rows it indexes
 static void check_adj_step(const gaast::Plan& plan, const gaast::Step& s) {
-    auto layout = [&](gaast::BufRef r) -> const gaast::Layout& {
-        return r.kind == gaast::BufKind::NODE ? plan.node_buffers[size_t(r.idx)]
-               : r.kind == gaast::BufKind::INPUT ? plan.input_layouts[size_t(r.idx)] : plan.out_layout;
-    };
     const gaast::Step::ExpLogAdj& q = s.adj;
-    const gaast::Layout &la = layout(s.a), &lg = layout(s.b), &lr = layout(s.res);
+    const gaast::Layout &la = plan.layout(s.a), &lg = plan.layout(s.b), &lr = plan.layout(s.res);
     CHECK(int(q.sq.size()) == q.m && q.m > 0);
     CHECK(q.arg_k >= 0 && q.arg_k + q.m <= la.row_len);
     CHECK(q.arg_0 < la.row_len);

@@ -28,16 +28,11 @@ static gaast_expr_t H(gaast_expr_t e) {
     return e;
 }
 
-static const gaast::Layout& layout_of(const gaast::Plan& plan, gaast::BufRef r) {
-    return r.kind == gaast::BufKind::NODE ? plan.node_buffers[size_t(r.idx)]
-           : r.kind == gaast::BufKind::INPUT ? plan.input_layouts[size_t(r.idx)] : plan.out_layout;
-}
-
 // every table of a GEXP / GEXP_ADJ step has its size, every offset stays inside the row it indexes, no result component is written
 // twice, every index the kernels form stays inside the table it reads
 static void check_gexp_step(const gaast::Plan& plan, const gaast::Step& s) {
     const bool adj = s.kind == gaast::Step::GEXP_ADJ;
-    const gaast::Layout &la = layout_of(plan, s.a), &lr = layout_of(plan, s.res);
+    const gaast::Layout &la = plan.layout(s.a), &lr = plan.layout(s.res);
     const gaast::Step::Inverse& q = s.inv;
     CHECK(!(s.a == s.res));
     CHECK(q.N == 2 || q.N == 4 || q.N == 8 || q.N == 16 || q.N == 32 || q.N == 64);
@@ -60,7 +55,7 @@ static void check_gexp_step(const gaast::Plan& plan, const gaast::Step& s) {
         if (j) CHECK(q.blade[size_t(j)] > q.blade[size_t(j - 1)]);
         CHECK(q.a_off[size_t(j)] >= -1 && int64_t(q.a_off[size_t(j)]) < la.row_len);
         CHECK(q.res_off[size_t(j)] >= -1 && int64_t(q.res_off[size_t(j)]) < lr.row_len);
-        if (adj && size_t(j) < q.g_off.size()) CHECK(q.g_off[size_t(j)] >= -1 && int64_t(q.g_off[size_t(j)]) < layout_of(plan, s.b).row_len);
+        if (adj && size_t(j) < q.g_off.size()) CHECK(q.g_off[size_t(j)] >= -1 && int64_t(q.g_off[size_t(j)]) < plan.layout(s.b).row_len);
         if (q.res_off[size_t(j)] >= 0 && int64_t(q.res_off[size_t(j)]) < lr.row_len) {
             CHECK(!seen[size_t(q.res_off[size_t(j)])]);
             seen[size_t(q.res_off[size_t(j)])] = 1;

@@ -339,7 +339,7 @@ static void chain_tables_agree(int n, const double* metric, int dtype, const cha
     gaast_spec_free(spec);
 }
 
-// ... and a SINGLE list with few long rows on the same kernel (plan.cpp: jit_long_row_lists): d = (a + b * c).g(2), the covering copy of
+// ... and a SINGLE list with few long rows on the same kernel (plan_passes.cpp: jit_long_row_lists): d = (a + b * c).g(2), the covering copy of
 // a's grade 2 folded into the list's accumulators.  Generic ELL words against the specialised tables, bit for bit.
 static void single_list_tables_agree(int n, int dtype, const char* dump_dir, uint32_t flags = GAAST_FLAG_EXACT_ORDER) {
     std::vector<double> metric(size_t(n), 1.0);
@@ -470,9 +470,11 @@ static void reserved_flag_bits_are_ignored(gaast_expr_t e, int n, const double* 
     std::printf("ok  %s\n", what);
 }
 
-// No step may read a cache buffer the plan has declared dead (never allocated), and every cache buffer a step reads has a writer
-// before it: asked through the one definition of a step's reads (plan.hpp: for_each_read).
-static void every_buffer_read_is_live(gaast_expr_t e, int n, const double* metric, int dtype, const char* what, bool expect_reduce_scale) {
+// No step may read OR WRITE a cache buffer the plan has declared dead (never allocated), and every cache buffer a step reads has a
+// writer before it: asked through the one definition of a step's reads (plan.hpp: for_each_read).  The plan declares exactly
+// expect_dead buffers dead (a guard that sees no dead buffer guards nothing).
+static void every_buffer_read_is_live(gaast_expr_t e, int n, const double* metric, int dtype, const char* what, bool expect_reduce_scale, int expect_dead,
+                                      const char* expect_name = nullptr) {
     gaast_spec_t spec = gaast_expr_specialize(e, n, metric, 1 << 16);
     CHECK(spec != nullptr);
     if (!spec) return;
@@ -481,14 +483,21 @@ static void every_buffer_read_is_live(gaast_expr_t e, int n, const double* metri
     gaast::Plan plan;
     gaast::build_plan(desc, plan);
     CHECK(plan.error == GAAST_OK && plan.unsupported.empty());
-    bool live = true, reduce_scale = false;
+    CHECK(plan.node_dead.size() == plan.node_buffers.size());
+    auto is_dead = [&](gaast::BufRef r) { return r.kind == gaast::BufKind::NODE && r.idx >= 0 && size_t(r.idx) < plan.node_dead.size() && plan.node_dead[size_t(r.idx)]; };
+    bool live = true, reduce_scale = false, named = expect_name == nullptr;
     for (size_t i = 0; i < plan.steps.size(); ++i) {
         reduce_scale = reduce_scale || plan.steps[i].kind == gaast::Step::REDUCE_SCALE;
+        named = named || plan.steps[i].name.find(expect_name) != std::string::npos;
+        if (is_dead(plan.steps[i].res)) {
+            std::printf("%s: step %zu (%s) writes cache buffer %d, declared dead\n", what, i, plan.steps[i].name.c_str(), plan.steps[i].res.idx);
+            live = false;
+        }
         gaast::for_each_read(plan.steps[i], [&](gaast::BufRef r) {
             if (r.kind != gaast::BufKind::NODE) return;
             bool written = false;
             for (size_t k = 0; k < i; ++k) written = written || plan.steps[k].res == r;
-            const bool dead = size_t(r.idx) < plan.node_dead.size() && plan.node_dead[size_t(r.idx)];
+            const bool dead = is_dead(r);
             if (dead || !written) {
                 std::printf("%s: step %zu (%s) reads cache buffer %d, %s\n", what, i, plan.steps[i].name.c_str(), r.idx, dead ? "declared dead" : "never written");
                 live = false;
@@ -497,6 +506,11 @@ static void every_buffer_read_is_live(gaast_expr_t e, int n, const double* metri
     }
     CHECK(live);
     CHECK(reduce_scale == expect_reduce_scale);
+    CHECK(named);
+    int n_dead = 0;
+    for (char d : plan.node_dead) n_dead += d ? 1 : 0;
+    if (n_dead != expect_dead) std::printf("%s: %d of %zu cache buffers declared dead, expected %d\n", what, n_dead, plan.node_buffers.size(), expect_dead);
+    CHECK(n_dead == expect_dead);
     gaast_spec_free(spec);
     std::printf("ok  %s\n", what);
 }
@@ -713,11 +727,20 @@ int main(int argc, char** argv) {
             gaast_expr_t e = gaast_expr_add(gaast_expr_product(p, s, GAAST_PROD_GEOMETRIC), gaast_expr_product(p, gaast_expr_rev(r), GAAST_PROD_GEOMETRIC));
             char what[96];
             std::snprintf(what, sizeof what, "scaled AND dense-multiplied sparse product n=%d: its buffer stays live", n);
-            every_buffer_read_is_live(e, n, euclid, n == 8 ? GAAST_F32 : GAAST_F64, what, true);
+            every_buffer_read_is_live(e, n, euclid, n == 8 ? GAAST_F32 : GAAST_F64, what, true, 1);   // the scalar 1 / |R|^2
             gaast_expr_t sw = gaast_expr_product(p, gaast_expr_rev(r), GAAST_PROD_GEOMETRIC);
             std::snprintf(what, sizeof what, "sandwich n=%d: every buffer read is live", n);
-            every_buffer_read_is_live(sw, n, euclid, GAAST_F64, what, false);
+            every_buffer_read_is_live(sw, n, euclid, GAAST_F64, what, false, 1);                       // R X, evaluated in the dense kernel's LDS
         }
+    }
+    {   // buffers the passes before chain_sparse_into_dense declare dead: the run's buffer of an element-wise pass with its scaling
+        // product folded in, (-(a.rev()) + b.ginvol()).rev() * s on grade 6 at n = 12, and the scalar of a versor inverse at n = 10
+        gaast_expr_t a = gaast_expr_input(0, 1 << 6, 12), b = gaast_expr_input(1, 1 << 6, 12), sc = gaast_expr_input(2, 1, 12);
+        gaast_expr_t sum = gaast_expr_add(gaast_expr_neg(gaast_expr_rev(a)), gaast_expr_ginvol(b));
+        every_buffer_read_is_live(gaast_expr_product(gaast_expr_rev(sum), sc, GAAST_PROD_GEOMETRIC), 12, euclid, GAAST_F32,
+                                  "element-wise run with the scaling folded in, n=12: its buffer is dead, nothing touches it", false, 1, "* scalar -> product_csr[");
+        every_buffer_read_is_live(gaast_expr_vinv(gaast_expr_input(0, 0x555, 10)), 10, euclid, GAAST_F64,
+                                  "versor inverse n=10: the scalar is dead, nothing touches it", true, 1, "reduce_scale[");
     }
     // the versor inverse of an even multivector at n = 8 in f32 (plan_fused.cpp, beside jit_slab_small: a slab of 259 elements, on register trial)
     reserved_flag_bits_are_ignored(gaast_expr_vinv(gaast_expr_input(0, 0x155, 8)), 8, euclid, GAAST_F32, "flag bit 30 ignored: versor inverse n=8 f32");

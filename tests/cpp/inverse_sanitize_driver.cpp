@@ -28,14 +28,9 @@ static gaast_expr_t H(gaast_expr_t e) {
     return e;
 }
 
-static const gaast::Layout& layout_of(const gaast::Plan& plan, gaast::BufRef r) {
-    return r.kind == gaast::BufKind::NODE ? plan.node_buffers[size_t(r.idx)]
-           : r.kind == gaast::BufKind::INPUT ? plan.input_layouts[size_t(r.idx)] : plan.out_layout;
-}
-
 // every table of an INVERSE step has its size, every offset stays inside the row it indexes, no result component is written twice
 static void check_inverse_step(const gaast::Plan& plan, const gaast::Step& s) {
-    const gaast::Layout &la = layout_of(plan, s.a), &lr = layout_of(plan, s.res);
+    const gaast::Layout &la = plan.layout(s.a), &lr = plan.layout(s.res);
     const gaast::Step::Inverse& q = s.inv;
     CHECK(!(s.a == s.res));
     CHECK(q.N == 2 || q.N == 4 || q.N == 8 || q.N == 16 || q.N == 32 || q.N == 64);

@@ -3,7 +3,8 @@
 tests/cpp/codegen_dump_driver.cpp lowers a fixed corpus with gaast::build_plan and writes every generated artifact of every step:
 the hiprtc sources of gaast_jit (slab in registers / slabs in LDS) and gaast_chain, the k_ast_fused micro-op stream, the tables
 and settings built next to them, and every table and setting of every product step (the dense kernels' operand maps, result maps and
-scales, the lists chained into them, the exact lists).  Length and SHA-256 of each must equal tests/golden/codegen_digests.json (recorded by
+scales, the lists chained into them, the exact lists), the wiring of every step, every table and setting of the steps the whole-plan
+passes build (element-wise pass, reduction with scaling, list chain) and the plan's dead cache buffers.  Length and SHA-256 of each must equal tests/golden/codegen_digests.json (recorded by
 tools/record_codegen_digests.py BEFORE a change to the generators).  The runtime compiles these strings and keys its compiled-code
 cache by their hash, and uploads these tables as they are: equal bytes are equal kernels on equal operand images."""
 import hashlib
@@ -102,6 +103,26 @@ def test_corpus_reaches_every_form_of_the_generators(dumped):
                 sources.append(f.read())
     missing = [form for form, mark in JIT_FORMS.items() if not any(mark in s for s in sources)]
     assert not missing, missing
+
+
+def test_corpus_reaches_every_form_of_the_plan_passes(dumped):
+    """The steps the whole-plan passes build: the element-wise pass with and without its scaling epilogue, the reduction with
+    every scalar operation in both of its kernels' forms, the list chain on either side (the sand*g1 cases chain the LEFT operand
+    only: sand9g1_right_first chains the right one) and with an aliased operand; and a cache buffer that a pass marked dead."""
+    digests, stdout, out = dumped
+    assert {m for m in re.findall(r"EW scale=(\d)", stdout)} == {"0", "1"}
+    reduce = re.findall(r"REDUCE op=(\d) wave=(\d+)", stdout)
+    assert {r[0] for r in reduce} == {"0", "1", "2"}
+    assert {r[1] != "0" for r in reduce} == {True, False}
+    links = re.findall(r"LINK side=(\d) alias=(\d)", stdout)
+    assert {l[0] for l in links} == {"1", "2"}
+    assert any(l[1] != "0" for l in links)
+    dead = []
+    for name in digests:
+        if name.endswith(".plan_node_dead"):
+            with open(os.path.join(out, name)) as f:
+                dead.append(f.read())
+    assert any(" 1" in d.split("node_dead")[1] for d in dead)
 
 
 def test_corpus_reaches_every_branch_of_the_product_lowering(dumped):

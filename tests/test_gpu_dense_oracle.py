@@ -11,7 +11,7 @@ import pytest
 
 import gaast_amd as ga
 from oracle import pyoracle as ogm
-from helpers import abs_terms_bound, bits_to_row, full_grades, hip_eval_batch, oracle_eval_batch, row_to_bits, rows_of
+from helpers import HipBackend, abs_terms_bound, bits_to_row, full_grades, hip_eval_batch, oracle_eval_batch, row_to_bits, rows_of
 
 pytestmark = pytest.mark.gpu
 
@@ -796,3 +796,32 @@ def test_runs_of_element_wise_arms_are_one_pass(shape, dtype):
     per_arm, _, spec2 = hip_eval_batch(build, n, rows, batch, dtype=dtype, flags=ga.FLAG_DEBUG_NO_CHAIN)
     assert len(spec2.launches()) > 2 and any("k_flip<" in l for l in spec2.launches()) and any("k_axpy_map<" in l for l in spec2.launches()), spec2.launches()
     assert np.array_equal(per_arm.view(np.uint32 if dtype == ga.F32 else np.uint64), got.view(np.uint32 if dtype == ga.F32 else np.uint64))
+
+
+@pytest.mark.parametrize("name", ["elementwise-scaled-f32", "vinv10-f64-exact"])
+def test_a_cache_buffer_a_fused_step_made_unnecessary_is_never_allocated(name):
+    """The run's buffer of an element-wise pass with its scaling product folded in (924 elements per item at n = 12, grade 6) and the
+    scalar of a reduce_scale step are dead: no step touches them, the program allocates zero rows for them.  The SAME program object is
+    evaluated at batch 3 and then at batch 70 -- the second call allocates the cache buffers anew; 70 items are more than one
+    workgroup at 4 and at 64 items per workgroup, with a ragged tail -- and agrees bit for bit with the unfused plan (one launch per
+    eval.rs arm, every buffer allocated), whose bits both passes promise in these modes."""
+    if name == "elementwise-scaled-f32":
+        n, dtype, flags, grades, fused = 12, ga.F32, 0, {0: [6], 1: [6], 2: [0]}, ("elementwise[", "* scalar -> product_csr[", "k_elementwise<float")
+        build = lambda B: (-(B.input(0, [6], n).rev()) + B.input(1, [6], n).ginvol()).rev() * B.input(2, [0], n)
+    else:
+        n, dtype, flags, grades, fused = 10, ga.F64, ga.FLAG_EXACT_ORDER, {0: list(range(0, 11, 2))}, ("reduce_scale[", "1/s", "k_reduce_scale<double")
+        build = lambda B: B.input(0, grades[0], n).vinv()
+    npdt, bits = (np.float32, np.uint32) if dtype == ga.F32 else (np.float64, np.uint64)
+    spec = build(HipBackend()).specialize(n, dtype=dtype, flags=flags)
+    plain = build(HipBackend()).specialize(n, dtype=dtype, flags=flags | ga.FLAG_NO_FUSION)
+    assert len(spec.launches()) == 1 and all(f in spec.launches()[0] for f in fused), spec.launches()
+    assert len(plain.launches()) > 2 and not any("elementwise[" in l or "reduce_scale[" in l for l in plain.launches()), plain.launches()
+    rng = np.random.default_rng(924)
+    for batch in (3, 70):
+        rows = [rows_of(n, grades[s], batch, rng, npdt) for s in sorted(grades)]
+        got = spec.eval_batch(rows, batch)
+        want = plain.eval_batch(rows, batch)
+        ga.lib().gaast_hip_synchronize()
+        got, want = got.download_rows(), want.download_rows()
+        assert got.shape == want.shape == (batch, want.shape[1]) and np.all(np.isfinite(want)) and np.any(want != 0)
+        assert np.array_equal(got.view(bits), want.view(bits)), batch
