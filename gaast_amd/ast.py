@@ -3,8 +3,8 @@
 Same operator surface as the reference: `*` geometric, `^` outer, `&` inner, `<<` / `>>`
 contractions, `+ - unary-`, `.g(k) .rev() .ginvol() .conj() .scal() .norm_sq() .sinv() .vinv()
 .sqrt() .pow() .exp() .log()`; beyond the reference, the metric-free complements `.dual() .undual()` and the regressive
-product `.vee(rhs)` (join of points / meet of planes), the general inverse `.inv()` with `a / b` and `1 / a`, and the general
-exponential `.gexp()`.  Phases 1-3 run in the C++ host code of libgaast_hip.so;
+product `.vee(rhs)` (join of points / meet of planes), the general inverse `.inv()` with `a / b` and `1 / a`, the general
+exponential `.gexp()` and the general (principal) square root `.gsqrt()`.  Phases 1-3 run in the C++ host code of libgaast_hip.so;
 `SpecializedAst.eval*` is phase 4 on the GPU through the C ABI -- there is no CPU path.
 """
 from __future__ import annotations
@@ -168,6 +168,15 @@ class Expr:
         and are counted (domain_errors()).  Differentiable (vjp, torch_fn) without a flag.  N <= 64 blades."""
         return self._un(_lib.lib().gaast_expr_gexp)
 
+    def gsqrt(self):
+        """The general square root (GAAST_OP_GSQRT): the principal X with X * X = self, whose left-multiplication matrix has every
+        eigenvalue in the open right half plane, by the product form of the Denman-Beavers iteration -- a PGA screw motor, a rotor
+        with two unequal angles, a Study number, mixed grades -- where sqrt() is a closed form for k-vectors whose square is a
+        scalar.  Even grades for an even operand, every grade otherwise; items without such a root (-1, a vector, 0, ideal elements),
+        with a non-finite component or not converged in 16 steps come back NaN and are counted (domain_errors()).  Differentiable
+        (vjp, torch_fn) without a flag.  A scalar operand is the scalar square root.  N <= 64 blades."""
+        return self._un(_lib.lib().gaast_expr_gsqrt)
+
     def dual(self):
         """Right complement: dual(e_S) = +-e_~S with e_S ^ dual(e_S) = I (GAAST_OP_DUAL); grade k -> n - k."""
         return self._un(_lib.lib().gaast_expr_dual)
@@ -293,8 +302,8 @@ class SpecializedAst:
         return self._out_info
 
     def domain_errors(self):
-        """Items refused by the exp / log domain check (GAAST_FLAG_EXP_LOG), found singular by inv() or out of gexp()'s domain since
-        the last call (synchronises)."""
+        """Items refused by the exp / log domain check (GAAST_FLAG_EXP_LOG), found singular by inv() or out of gexp()'s or gsqrt()'s domain
+        since the last call (synchronises)."""
         n = C.c_int64()
         _lib.check(_lib.lib().gaast_hip_program_domain_errors(self.program(), C.byref(n)))
         return n.value

@@ -40,8 +40,9 @@ inline uint64_t gs_mirror(uint64_t mask, int n) {
     return m;
 }
 
-// grades of a general inverse (GAAST_OP_INV) and of a general exponential (GAAST_OP_GEXP): the even subalgebra is closed, so an
-// even operand has an even inverse / exponential; any other operand's may hold every grade
+// grades of a general inverse (GAAST_OP_INV), of a general exponential (GAAST_OP_GEXP) and of a general square root (GAAST_OP_GSQRT):
+// the even subalgebra is closed, so an even operand has an even inverse / exponential / principal root; any other operand's may hold
+// every grade
 inline uint64_t gs_inverse(uint64_t mask, int n) {
     const uint64_t full = n >= 63 ? ~0ULL : ((1ULL << (n + 1)) - 1ULL);
     return (mask & 0xAAAAAAAAAAAAAAAAULL) ? full : (full & 0x5555555555555555ULL);

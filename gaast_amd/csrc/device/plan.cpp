@@ -174,8 +174,10 @@ struct Lowering : LowerState {
         case GAAST_OP_DUAL:
         case GAAST_OP_UNDUAL: lower_dual(res, id); return;
         case GAAST_OP_INV: lower_inverse(res, id); return;
-        case GAAST_OP_GEXP: lower_gexp(res, id); return;
-        case GAAST_OP_GEXP_ADJ: lower_gexp_adj(res, id); return;
+        case GAAST_OP_GEXP: lower_gexp(res, id, Step::GEXP, "gexp", "the general exponential", "general_exponential"); return;
+        case GAAST_OP_GEXP_ADJ: lower_gexp_adj(res, id, Step::GEXP_ADJ, "gexp", "the general exponential's adjoint", "general_exponential_adjoint"); return;
+        case GAAST_OP_GSQRT: lower_gexp(res, id, Step::GSQRT, "gsqrt", "the general square root", "general_sqrt"); return;
+        case GAAST_OP_GSQRT_ADJ: lower_gexp_adj(res, id, Step::GSQRT_ADJ, "gsqrt", "the general square root's adjoint", "general_sqrt_adjoint"); return;
         case GAAST_OP_PRODUCT: lower_product(res, id); return;
         default: throw std::runtime_error("unknown opcode");
         }
@@ -234,7 +236,7 @@ struct Lowering : LowerState {
         touch(res);
     }
 
-    // The tables of a step over the blade set S (Step::Inverse: INVERSE, GEXP, GEXP_ADJ): S itself, where operand row `a` (grades
+    // The tables of a step over the blade set S (Step::Inverse: INVERSE, GEXP, GEXP_ADJ, GSQRT, GSQRT_ADJ): S itself, where operand row `a` (grades
     // `amask`, those of `flip` negated) and result row `res` (grades `produce`) hold its blades, the reordering signs and the metric
     // factors of the left-multiplication matrix.  false: failed (a produced grade is absent from res)
     bool blade_set_tables(Step::Inverse& q, bool even, BufRef a, uint64_t amask, uint64_t flip, BufRef res, uint64_t produce) {
@@ -271,7 +273,7 @@ struct Lowering : LowerState {
         return true;
     }
 
-    // is a general exponential over this blade set beyond the kernels (N = 2 ... 64)?  Then the plan is marked unsupported
+    // is a general exponential or square root over this blade set beyond the kernels (N = 2 ... 64)?  Then the plan is marked unsupported
     bool blade_set_unsupported(const char* what, bool even) {
         const int n = d.vec_space_dim, bits = even ? n - 1 : n;
         if (bits >= 1 && bits <= 6) return false;
@@ -282,24 +284,26 @@ struct Lowering : LowerState {
     }
 
     // The general exponential (GAAST_OP_GEXP, gaast_hip.h; no reference counterpart): a one-operand product arm, always a launch of
-    // its own (Step::GEXP, k_mv_gexp).  The operand is read like the inverse's; res += exp(A) in the wanted grades.
-    void lower_gexp(BufRef res, int id) {
+    // its own (Step::GEXP, k_mv_gexp).  The operand is read like the inverse's; res += exp(A) in the wanted grades.  The general square
+    // root (GAAST_OP_GSQRT; Step::GSQRT, k_mv_gsqrt) is lowered by the same lines: `kind` the step's, `op` / `what` / `label` its names
+    // in messages and in the launch name.
+    void lower_gexp(BufRef res, int id, Step::Kind kind, const std::string& op, const char* what, const char* label) {
         const gaast_node_desc& nd = node(id);
         const gaast_node_desc& ch = node(nd.child0);
         const int n = d.vec_space_dim;
         if (ch.vec_space_dim != n || nd.vec_space_dim != n) {
-            fail(GAAST_ERR_INVALID_PROGRAM, "gexp operand lives in another vector space than the algebra");
+            fail(GAAST_ERR_INVALID_PROGRAM, op + " operand lives in another vector space than the algebra");
             return;
         }
         const uint64_t amask = ch.minimal_grade_mask & ((uint64_t(2) << n) - 1);
         const bool even = !(amask & 0xAAAAAAAAAAAAAAAAULL);
-        if (blade_set_unsupported("the general exponential", even)) return;
+        if (blade_set_unsupported(what, even)) return;
         int canon = 0;
         uint64_t flip = 0;
         BufRef a = operand(nd.child0, &canon, &flip);
         if (!ok()) return;
         if (key(a) == key(res)) {
-            fail(GAAST_ERR_MISSING_GRADE, "gexp operand aliases its own result buffer");
+            fail(GAAST_ERR_MISSING_GRADE, op + " operand aliases its own result buffer");
             return;
         }
         const Layout& lr = layout(res);
@@ -312,31 +316,33 @@ struct Lowering : LowerState {
         const auto fr = fresh.find(key(res));
         const bool covers = fr != fresh.end() && !(plan.flags & GAAST_FLAG_NO_FUSION) && int64_t(q.n_out) == lr.row_len;
         if (covers) removed[size_t(fr->second)] = 1;
-        Step& s = emit(Step::GEXP, res, "general_exponential[" + std::to_string(q.N) + (even ? " even" : "") + " blades, " + std::to_string(q.n_out) + " produced, n=" + std::to_string(n) + "]");
+        Step& s = emit(kind, res, std::string(label) + "[" + std::to_string(q.N) + (even ? " even" : "") + " blades, " + std::to_string(q.n_out) + " produced, n=" + std::to_string(n) + "]");
         s.a = a;
         s.canon_a = canon;
         s.beta = covers ? 0 : 1;
         s.inv = std::move(q);
-        plan.has_gexp = 1;
+        (kind == Step::GSQRT ? plan.has_gsqrt : plan.has_gexp) = 1;
         touch(res);
     }
 
     // Reverse mode of the general exponential (GAAST_OP_GEXP_ADJ, gaast_hip.h): res += the cotangent of the operand, in the operand's
     // grades.  child1, the forward operand, is read like the forward's; child0, the cotangent, is cached like a product operand.
-    void lower_gexp_adj(BufRef res, int id) {
+    // Reverse mode of the general square root (GAAST_OP_GSQRT_ADJ; Step::GSQRT_ADJ, k_mv_gsqrt_adj) has the same operands and the same
+    // tables -- the two transposed sign words are the rows of the transposed L_X + R_X -- and is lowered by the same lines.
+    void lower_gexp_adj(BufRef res, int id, Step::Kind kind, const std::string& op, const char* what, const char* label) {
         const gaast_node_desc& nd = node(id);
         const gaast_node_desc& ch = node(nd.child1);
         const int n = d.vec_space_dim;
         if (ch.vec_space_dim != n || nd.vec_space_dim != n || node(nd.child0).vec_space_dim != n) {
-            fail(GAAST_ERR_INVALID_PROGRAM, "gexp adjoint operand lives in another vector space than the algebra");
+            fail(GAAST_ERR_INVALID_PROGRAM, op + " adjoint operand lives in another vector space than the algebra");
             return;
         }
         const uint64_t amask = ch.minimal_grade_mask & ((uint64_t(2) << n) - 1);
         const bool even = !(amask & 0xAAAAAAAAAAAAAAAAULL);
-        if (blade_set_unsupported("the general exponential's adjoint", even)) return;
+        if (blade_set_unsupported(what, even)) return;
         const uint64_t smask = gs_inverse(amask, n);
         if (node(nd.child0).minimal_grade_mask & ~smask) {
-            fail(GAAST_ERR_INVALID_PROGRAM, "gexp adjoint: the cotangent holds grades outside the blade set of the operand");
+            fail(GAAST_ERR_INVALID_PROGRAM, op + " adjoint: the cotangent holds grades outside the blade set of the operand");
             return;
         }
         int canon = 0;
@@ -346,7 +352,7 @@ struct Lowering : LowerState {
         BufRef cot = store_in_cache(nd.child0);
         if (!ok()) return;
         if (key(a) == key(res) || key(cot) == key(res)) {
-            fail(GAAST_ERR_MISSING_GRADE, "gexp adjoint operand aliases its own result buffer");
+            fail(GAAST_ERR_MISSING_GRADE, op + " adjoint operand aliases its own result buffer");
             return;
         }
         const Layout &lg = layout(cot), &lr = layout(res);
@@ -371,7 +377,7 @@ struct Lowering : LowerState {
         const auto fr = fresh.find(key(res));
         const bool covers = fr != fresh.end() && !(plan.flags & GAAST_FLAG_NO_FUSION) && int64_t(q.n_out) == lr.row_len;
         if (covers) removed[size_t(fr->second)] = 1;
-        Step& s = emit(Step::GEXP_ADJ, res, "general_exponential_adjoint[" + std::to_string(q.N) + (even ? " even" : "") + " blades, " + std::to_string(q.n_out) + " produced, n=" + std::to_string(n) + "]");
+        Step& s = emit(kind, res, std::string(label) + "[" + std::to_string(q.N) + (even ? " even" : "") + " blades, " + std::to_string(q.n_out) + " produced, n=" + std::to_string(n) + "]");
         s.a = a;
         s.b = cot;
         s.canon_a = canon;
@@ -863,6 +869,7 @@ void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab,
         case GAAST_OP_EXP_ADJ:
         case GAAST_OP_LOG_ADJ:
         case GAAST_OP_GEXP_ADJ:
+        case GAAST_OP_GSQRT_ADJ:
             if (!child_ok(nd.child0) || !child_ok(nd.child1)) throw std::runtime_error("nodes are not in post-order");
             if (nd.opcode == GAAST_OP_PRODUCT && nd.product_kind >= GAAST_PROD_ADJ_LEFT) {
                 const int adj = nd.product_kind & ~7, base = nd.product_kind & 7;
@@ -872,7 +879,7 @@ void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab,
             break;
         case GAAST_OP_NEG: case GAAST_OP_EXP: case GAAST_OP_LOG: case GAAST_OP_PROJ:
         case GAAST_OP_REVERSE: case GAAST_OP_GINVOL: case GAAST_OP_SINV: case GAAST_OP_SSQRT:
-        case GAAST_OP_DUAL: case GAAST_OP_UNDUAL: case GAAST_OP_INV: case GAAST_OP_GEXP:
+        case GAAST_OP_DUAL: case GAAST_OP_UNDUAL: case GAAST_OP_INV: case GAAST_OP_GEXP: case GAAST_OP_GSQRT:
             if (!child_ok(nd.child0)) throw std::runtime_error("nodes are not in post-order");
             break;
         default: throw std::runtime_error("unknown opcode");

@@ -157,7 +157,43 @@ typedef enum gaast_opcode {
      *   dA = 2^-s dA_s, restricted to the grades the operand holds.
      * The forward is recomputed.  No domain check and no count: a domain-error item of the forward has every component NaN (its
      * scaling factor is taken as NaN, so the arithmetic carries it). */
-    GAAST_OP_GEXP_ADJ = 17
+    GAAST_OP_GEXP_ADJ = 17,
+    /* General multivector square root (no reference counterpart): gsqrt(A) is the PRINCIPAL square root, the X with X X = A whose
+     * left-multiplication matrix L_X has every eigenvalue in the open right half plane.  It exists and is unique when L_A is
+     * nonsingular and has no eigenvalue on the negative real axis; it is then a polynomial in A, so it lies in the blade set S of
+     * GAAST_OP_INV and commutes with A.  The reference's sqrt (pow / exp / log behind GAAST_FLAG_EXP_LOG) is a closed form for
+     * k-vectors whose square is a scalar and stays what it is.  One child.  S, N = |S|, its ordering and L_A are GAAST_OP_INV's; so
+     * are the node's maximal grade set, the grades it produces and what it wants of its child, and like every arm it ADDS into the
+     * buffer that contains it.  Supported: N = 2 ... 64 (any mask for n <= 6, even masks for n = 7); anything else is
+     * GAAST_ERR_UNIMPLEMENTED from gaast_hip_program_create, phases 1-3 succeeding on the host (the expression layer lowers a scalar
+     * operand to GAAST_OP_SSQRT).  No flag gates the node and GAAST_FLAG_EXACT_ORDER changes nothing: there are no reference bits.
+     * Algorithm (the product form of the Denman-Beavers iteration, in multivector space: every iterate is a multivector over S;
+     * every sum over j ascending), per item, with e_0 the scalar unit:
+     *   M_0 = A, Y_0 = A;  for k = 0, 1, ...:
+     *     d_k = sum_r |(M_k - e_0)_r|, a butterfly over the N components: v <- v + v[j xor m] for m = N/2, N/4, ... 1;
+     *     stop (the result is Y_k) when d_k <= N eps, or when the step before had d_(k-1) <= sqrt(eps) (convergence is quadratic: one
+     *     step past that point is at the rounding floor, where d_k itself may stagnate), or at k = K = 16;
+     *     W = M_k^-1, the solve L_(M_k) W = e_0 of GAAST_OP_INV (Gauss-Jordan, implicit partial pivoting, the same pivot test
+     *     !(|p| > N eps max_i |(M_k)_i|));
+     *     Y_(k+1) = 1/2 (Y_k (e_0 + W));   M_(k+1) = 1/2 (e_0 + 1/2 (M_k + W)).
+     * Domain errors: an item that meets a singular pivot in any inverse it runs, that has a non-finite d_k (a non-finite component),
+     * or that has not stopped at k = K.  Every produced component of it is a quiet NaN and it is counted once in
+     * gaast_hip_program_domain_errors (a program with a GSQRT step owns the counter).  -1, a vector (eigenvalues +-1), 0 and PGA's
+     * ideal elements are such items by nature.
+     * Accuracy: per item that is no domain error, the residual ||X X - A||_inf <= 9.2 N eps ||L_X||_inf ||X||_inf, which is four times
+     * the worst of the numpy restatement of these recurrences over the test sweep (tests/gsqrt_numpy.py: FWD_SCALE = 2.3, measured
+     * 2.12 in f32 and 2.24 in f64; operands gexp(B) with sum |B_i| <= 2.5 and operands with a dominant positive scalar), rounded up. */
+    GAAST_OP_GSQRT = 18,
+    /* Reverse mode of GAAST_OP_GSQRT, emitted by gaast_program_vjp: child0 = the cotangent g of the GSQRT node (any grades within
+     * S), child1 = the forward operand A; the node's own minimal grade mask is the operand's.  It ADDS into its buffer; no flag.
+     * From X X = A follows dX X + X dX = dA, so with GAAST_OP_GEXP_ADJ's operators the cotangent a of the operand is the solution
+     * of the N x N system  ADJL(a, X) + ADJR(a, X) = g,  restricted to the grades the operand holds.  The operator is the transpose
+     * of L_X + R_X: row c has, at column c xor t, coeff(c, t) X[t] once with ADJL's sign and once with ADJR's (exactly 0 where the
+     * two blades anticommute); it is nonsingular whenever X is a principal root, no two eigenvalues of L_X summing to zero.  The
+     * forward is recomputed, the system solved by GAAST_OP_INV's elimination.  A failed pivot test of this solve makes every
+     * component of the item's cotangent NaN; it is not counted, and neither is a domain-error item of the recomputed forward, whose
+     * cotangent is NaN likewise. */
+    GAAST_OP_GSQRT_ADJ = 19
 } gaast_opcode;
 
 /* the five products of src/ast/expr.rs:180-197 (and the regressive product), for compact PRODUCT descriptors */
@@ -305,8 +341,9 @@ int gaast_hip_program_launch_variant(gaast_hip_program_t prog, int i);
 /* GAAST_FLAG_EXP_LOG extension: how many items, since the last call, had an exp / log operand outside the domain (a
  * k-vector whose square is not scalar: |<B B>_{not 0}|^2 > 2^-40 (sum B_i^2)^2); their results are the closed form applied
  * to <B B>_0 regardless.  A program with a GAAST_OP_INV step counts its singular items here too (their produced components are
- * NaN), one with a GAAST_OP_GEXP step its domain errors (theta not finite or > 2048; NaN likewise).  Synchronises the library
- * stream; resets the counter.  0 for programs without exp / log / inv / gexp. */
+ * NaN), one with a GAAST_OP_GEXP step its domain errors (theta not finite or > 2048; NaN likewise), one with a GAAST_OP_GSQRT step
+ * the items without a principal root it can reach (GAAST_OP_GSQRT; NaN likewise).  Synchronises the library stream; resets the
+ * counter.  0 for programs without exp / log / inv / gexp / gsqrt. */
 int gaast_hip_program_domain_errors(gaast_hip_program_t prog, int64_t *count);
 /* GAAST_FLAG_DEBUG_KEEP_JIT_SOURCE: the HIP source generated for this program ("" if none). */
 const char *gaast_hip_program_jit_source(gaast_hip_program_t prog);

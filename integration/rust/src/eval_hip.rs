@@ -210,6 +210,7 @@ impl<T: GradedData + std::fmt::Debug> SpecializedAst<T> {
                 // with the node's grade set the even grades for an even child and every grade otherwise, and the child wanted
                 // in all of its grades (a scalar child: ScalarUnaryOp::Inversion, as above).
                 // The general exponential (OP_GEXP) flattens the same way, with the same grade set; its adjoint node OP_GEXP_ADJ is only ever emitted by gaast_program_vjp.
+                // The general square root (OP_GSQRT / OP_GSQRT_ADJ) likewise; of a scalar child it is ScalarUnaryOp::Sqrt.
             }
             nodes.push(d);
         }

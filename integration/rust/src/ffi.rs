@@ -32,6 +32,9 @@ pub const OP_INV: i32 = 15;
 // general multivector exponential by scaling and squaring (no AstNode counterpart), and its reverse-mode node (child0 = cotangent, child1 = operand)
 pub const OP_GEXP: i32 = 16;
 pub const OP_GEXP_ADJ: i32 = 17;
+// general (principal) multivector square root by the Denman-Beavers product iteration (no AstNode counterpart), and its reverse-mode node (child0 = cotangent, child1 = operand)
+pub const OP_GSQRT: i32 = 18;
+pub const OP_GSQRT_ADJ: i32 = 19;
 // compact product kinds (gaast_product_kind); 5 = the regressive product a v b = undual(dual(a) ^ dual(b))
 pub const PROD_REGRESSIVE: i32 = 5;
 
