@@ -18,11 +18,13 @@ STATUS_NAMES = {1: "INVALID_PROGRAM", 2: "MISSING_GRADE", 3: "UNIMPLEMENTED", 4:
                 6: "INVALID_ARGUMENT", 7: "NO_DEVICE", 8: "OVERFLOW"}
 F64, F32 = 0, 1
 (OP_INPUT, OP_ADD, OP_PRODUCT, OP_NEG, OP_EXP, OP_LOG, OP_PROJ, OP_REVERSE, OP_GINVOL, OP_SINV,
- OP_SSQRT, OP_EXP_ADJ, OP_LOG_ADJ, OP_DUAL, OP_UNDUAL, OP_INV, OP_GEXP, OP_GEXP_ADJ, OP_GSQRT, OP_GSQRT_ADJ) = range(20)
+ OP_SSQRT, OP_EXP_ADJ, OP_LOG_ADJ, OP_DUAL, OP_UNDUAL, OP_INV, OP_GEXP, OP_GEXP_ADJ, OP_GSQRT, OP_GSQRT_ADJ,
+ OP_GLOG, OP_GLOG_ADJ) = range(22)
 OP_NAMES = ["GradedObj", "Addition", "Product", "Negation", "Exponential", "Logarithm",
             "GradeProjection", "Reverse", "GradeInvolution", "ScalarInversion", "ScalarSqrt",
             "ExponentialAdjoint", "LogarithmAdjoint", "Dual", "Undual", "Inverse", "GeneralExponential",
-            "GeneralExponentialAdjoint", "GeneralSqrt", "GeneralSqrtAdjoint"]
+            "GeneralExponentialAdjoint", "GeneralSqrt", "GeneralSqrtAdjoint",
+            "GeneralLogarithm", "GeneralLogarithmAdjoint"]
 PROD_EXPLICIT, PROD_GEOMETRIC, PROD_OUTER, PROD_INNER, PROD_LCONTRACT, PROD_RCONTRACT = -1, 0, 1, 2, 3, 4
 PROD_REGRESSIVE = 5   # a v b = undual(dual(a) ^ dual(b)): join / meet, metric-free
 PROD_ADJ_LEFT, PROD_ADJ_RIGHT = 8, 16   # added to a forward kind: compact adjoint products (reverse mode)
@@ -171,6 +173,7 @@ SIGNATURES = {
     "gaast_expr_inv": (_vp, [_vp]),
     "gaast_expr_gexp": (_vp, [_vp]),
     "gaast_expr_gsqrt": (_vp, [_vp]),
+    "gaast_expr_glog": (_vp, [_vp]),
     "gaast_expr_specialize": (_vp, [_vp, _ci, _pd, _u64]),
     "gaast_spec_free": (None, [_vp]),
     "gaast_spec_num_nodes": (_ci, [_vp]),

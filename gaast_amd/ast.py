@@ -4,7 +4,7 @@ Same operator surface as the reference: `*` geometric, `^` outer, `&` inner, `<<
 contractions, `+ - unary-`, `.g(k) .rev() .ginvol() .conj() .scal() .norm_sq() .sinv() .vinv()
 .sqrt() .pow() .exp() .log()`; beyond the reference, the metric-free complements `.dual() .undual()` and the regressive
 product `.vee(rhs)` (join of points / meet of planes), the general inverse `.inv()` with `a / b` and `1 / a`, the general
-exponential `.gexp()` and the general (principal) square root `.gsqrt()`.  Phases 1-3 run in the C++ host code of libgaast_hip.so;
+exponential `.gexp()`, the general (principal) square root `.gsqrt()` and the general (principal) logarithm `.glog()`.  Phases 1-3 run in the C++ host code of libgaast_hip.so;
 `SpecializedAst.eval*` is phase 4 on the GPU through the C ABI -- there is no CPU path.
 """
 from __future__ import annotations
@@ -177,6 +177,15 @@ class Expr:
         (vjp, torch_fn) without a flag.  A scalar operand is the scalar square root.  N <= 64 blades."""
         return self._un(_lib.lib().gaast_expr_gsqrt)
 
+    def glog(self):
+        """The general logarithm (GAAST_OP_GLOG): the principal Y with Y.gexp() = self, whose left-multiplication matrix has every
+        eigenvalue in the strip |Im| < pi, by inverse scaling and squaring (gsqrt()'s roots, then a [7/7] Pade approximant) -- the
+        generator of a PGA screw motor, of a rotor with two unequal angles, mixed grades -- where log() is a closed form for
+        k-vectors whose square is a scalar.  Even grades for an even operand, every grade otherwise; items without such a
+        logarithm (-1, a vector, 0, ideal elements), with a non-finite component or still far from 1 after 16 roots come back NaN
+        and are counted (domain_errors()).  Differentiable (vjp, torch_fn) without a flag.  N <= 64 blades."""
+        return self._un(_lib.lib().gaast_expr_glog)
+
     def dual(self):
         """Right complement: dual(e_S) = +-e_~S with e_S ^ dual(e_S) = I (GAAST_OP_DUAL); grade k -> n - k."""
         return self._un(_lib.lib().gaast_expr_dual)
@@ -302,7 +311,7 @@ class SpecializedAst:
         return self._out_info
 
     def domain_errors(self):
-        """Items refused by the exp / log domain check (GAAST_FLAG_EXP_LOG), found singular by inv() or out of gexp()'s or gsqrt()'s domain
+        """Items refused by the exp / log domain check (GAAST_FLAG_EXP_LOG), found singular by inv() or out of gexp()'s, gsqrt()'s or glog()'s domain
         since the last call (synchronises)."""
         n = C.c_int64()
         _lib.check(_lib.lib().gaast_hip_program_domain_errors(self.program(), C.byref(n)))

@@ -178,6 +178,8 @@ struct Lowering : LowerState {
         case GAAST_OP_GEXP_ADJ: lower_gexp_adj(res, id, Step::GEXP_ADJ, "gexp", "the general exponential's adjoint", "general_exponential_adjoint"); return;
         case GAAST_OP_GSQRT: lower_gexp(res, id, Step::GSQRT, "gsqrt", "the general square root", "general_sqrt"); return;
         case GAAST_OP_GSQRT_ADJ: lower_gexp_adj(res, id, Step::GSQRT_ADJ, "gsqrt", "the general square root's adjoint", "general_sqrt_adjoint"); return;
+        case GAAST_OP_GLOG: lower_gexp(res, id, Step::GLOG, "glog", "the general logarithm", "general_log"); return;
+        case GAAST_OP_GLOG_ADJ: lower_gexp_adj(res, id, Step::GLOG_ADJ, "glog", "the general logarithm's adjoint", "general_log_adjoint"); return;
         case GAAST_OP_PRODUCT: lower_product(res, id); return;
         default: throw std::runtime_error("unknown opcode");
         }
@@ -236,7 +238,7 @@ struct Lowering : LowerState {
         touch(res);
     }
 
-    // The tables of a step over the blade set S (Step::Inverse: INVERSE, GEXP, GEXP_ADJ, GSQRT, GSQRT_ADJ): S itself, where operand row `a` (grades
+    // The tables of a step over the blade set S (Step::Inverse: INVERSE, GEXP, GEXP_ADJ, GSQRT, GSQRT_ADJ, GLOG, GLOG_ADJ): S itself, where operand row `a` (grades
     // `amask`, those of `flip` negated) and result row `res` (grades `produce`) hold its blades, the reordering signs and the metric
     // factors of the left-multiplication matrix.  false: failed (a produced grade is absent from res)
     bool blade_set_tables(Step::Inverse& q, bool even, BufRef a, uint64_t amask, uint64_t flip, BufRef res, uint64_t produce) {
@@ -273,7 +275,7 @@ struct Lowering : LowerState {
         return true;
     }
 
-    // is a general exponential or square root over this blade set beyond the kernels (N = 2 ... 64)?  Then the plan is marked unsupported
+    // is a general exponential, square root or logarithm over this blade set beyond the kernels (N = 2 ... 64)?  Then the plan is marked unsupported
     bool blade_set_unsupported(const char* what, bool even) {
         const int n = d.vec_space_dim, bits = even ? n - 1 : n;
         if (bits >= 1 && bits <= 6) return false;
@@ -286,7 +288,7 @@ struct Lowering : LowerState {
     // The general exponential (GAAST_OP_GEXP, gaast_hip.h; no reference counterpart): a one-operand product arm, always a launch of
     // its own (Step::GEXP, k_mv_gexp).  The operand is read like the inverse's; res += exp(A) in the wanted grades.  The general square
     // root (GAAST_OP_GSQRT; Step::GSQRT, k_mv_gsqrt) is lowered by the same lines: `kind` the step's, `op` / `what` / `label` its names
-    // in messages and in the launch name.
+    // in messages and in the launch name.  So is the general logarithm (GAAST_OP_GLOG; Step::GLOG, k_mv_glog).
     void lower_gexp(BufRef res, int id, Step::Kind kind, const std::string& op, const char* what, const char* label) {
         const gaast_node_desc& nd = node(id);
         const gaast_node_desc& ch = node(nd.child0);
@@ -321,14 +323,15 @@ struct Lowering : LowerState {
         s.canon_a = canon;
         s.beta = covers ? 0 : 1;
         s.inv = std::move(q);
-        (kind == Step::GSQRT ? plan.has_gsqrt : plan.has_gexp) = 1;
+        (kind == Step::GLOG ? plan.has_glog : kind == Step::GSQRT ? plan.has_gsqrt : plan.has_gexp) = 1;
         touch(res);
     }
 
     // Reverse mode of the general exponential (GAAST_OP_GEXP_ADJ, gaast_hip.h): res += the cotangent of the operand, in the operand's
     // grades.  child1, the forward operand, is read like the forward's; child0, the cotangent, is cached like a product operand.
     // Reverse mode of the general square root (GAAST_OP_GSQRT_ADJ; Step::GSQRT_ADJ, k_mv_gsqrt_adj) has the same operands and the same
-    // tables -- the two transposed sign words are the rows of the transposed L_X + R_X -- and is lowered by the same lines.
+    // tables -- the two transposed sign words are the rows of the transposed L_X + R_X -- and is lowered by the same lines.  So is
+    // reverse mode of the general logarithm (GAAST_OP_GLOG_ADJ; Step::GLOG_ADJ, k_mv_glog_adj), which uses the two words one at a time too.
     void lower_gexp_adj(BufRef res, int id, Step::Kind kind, const std::string& op, const char* what, const char* label) {
         const gaast_node_desc& nd = node(id);
         const gaast_node_desc& ch = node(nd.child1);
@@ -870,6 +873,7 @@ void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab,
         case GAAST_OP_LOG_ADJ:
         case GAAST_OP_GEXP_ADJ:
         case GAAST_OP_GSQRT_ADJ:
+        case GAAST_OP_GLOG_ADJ:
             if (!child_ok(nd.child0) || !child_ok(nd.child1)) throw std::runtime_error("nodes are not in post-order");
             if (nd.opcode == GAAST_OP_PRODUCT && nd.product_kind >= GAAST_PROD_ADJ_LEFT) {
                 const int adj = nd.product_kind & ~7, base = nd.product_kind & 7;
@@ -879,7 +883,7 @@ void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab,
             break;
         case GAAST_OP_NEG: case GAAST_OP_EXP: case GAAST_OP_LOG: case GAAST_OP_PROJ:
         case GAAST_OP_REVERSE: case GAAST_OP_GINVOL: case GAAST_OP_SINV: case GAAST_OP_SSQRT:
-        case GAAST_OP_DUAL: case GAAST_OP_UNDUAL: case GAAST_OP_INV: case GAAST_OP_GEXP: case GAAST_OP_GSQRT:
+        case GAAST_OP_DUAL: case GAAST_OP_UNDUAL: case GAAST_OP_INV: case GAAST_OP_GEXP: case GAAST_OP_GSQRT: case GAAST_OP_GLOG:
             if (!child_ok(nd.child0)) throw std::runtime_error("nodes are not in post-order");
             break;
         default: throw std::runtime_error("unknown opcode");

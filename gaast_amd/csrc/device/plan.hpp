@@ -44,8 +44,8 @@ inline Layout make_layout(int dim, uint64_t mask) {
 // a step in place), each table and setting named after the one thing it holds.  The groups of the other kinds stay empty.  The
 // tables are host images, uploaded once at program_create.
 struct Step {
-    enum Kind { ZERO, AXPY, FLIP, SUNARY, PRODUCT_CSR, PRODUCT_DENSE, FUSED, EXPLOG, REDUCE_SCALE, ELEMENTWISE, LINMAP, EXPLOG_ADJ, DUAL, INVERSE, GEXP, GEXP_ADJ, GSQRT, GSQRT_ADJ } kind = ZERO;
-    BufRef res, a, b;        // result; operand rows (PRODUCT_*: left, right; AXPY / EXPLOG / LINMAP / DUAL / INVERSE / GEXP / GSQRT: a; EXPLOG_ADJ / GEXP_ADJ / GSQRT_ADJ: a = the forward operand, b = the cotangent; REDUCE_SCALE: the reduction's; ELEMENTWISE: b = the scalar)
+    enum Kind { ZERO, AXPY, FLIP, SUNARY, PRODUCT_CSR, PRODUCT_DENSE, FUSED, EXPLOG, REDUCE_SCALE, ELEMENTWISE, LINMAP, EXPLOG_ADJ, DUAL, INVERSE, GEXP, GEXP_ADJ, GSQRT, GSQRT_ADJ, GLOG, GLOG_ADJ } kind = ZERO;
+    BufRef res, a, b;        // result; operand rows (PRODUCT_*: left, right; AXPY / EXPLOG / LINMAP / DUAL / INVERSE / GEXP / GSQRT / GLOG: a; EXPLOG_ADJ / GEXP_ADJ / GSQRT_ADJ / GLOG_ADJ: a = the forward operand, b = the cotangent; REDUCE_SCALE: the reduction's; ELEMENTWISE: b = the scalar)
     std::string name;
     int canon_a = 0, canon_b = 0;   // the operand is a bound input read in place: the kernel applies the reference's 0.0 + x
     int beta = 1;                   // 0: the zero fill of a fresh result is folded in
@@ -218,9 +218,9 @@ struct Step {
             const double w = weight[size_t(blade[size_t(j)] & ~blade[size_t(r)])];
             return ((neg[size_t(r)] >> j) & 1ULL) ? -w : w;
         }
-        // GEXP / GEXP_ADJ / GSQRT / GSQRT_ADJ only (empty for INVERSE)
+        // GEXP / GEXP_ADJ / GSQRT / GSQRT_ADJ / GLOG / GLOG_ADJ only (empty for INVERSE)
         double wmax = 1.0;                  // the largest |weight|: theta = wmax * sum |A_a| bounds the largest absolute row sum of L
-        std::vector<int32_t> g_off;         // GEXP_ADJ, GSQRT_ADJ [N] offset of blade j in the cotangent row; -1: absent (reads as 0)
+        std::vector<int32_t> g_off;         // GEXP_ADJ, GSQRT_ADJ, GLOG_ADJ [N] offset of blade j in the cotangent row; -1: absent (reads as 0)
         // GEXP_ADJ: the sign words of the two adjoint products of P = X Z, both with the metric factor weight[S[a] & S[b]]:
         std::vector<uint64_t> adj_neg_l;    // [N] bit b of adj_neg_l[a] = bit b of neg[a xor b]:  ADJL(g, Z)[a] = sum_b +-w Z[b] g[a xor b]
         std::vector<uint64_t> adj_neg_r;    // [N] bit a of adj_neg_r[b] = bit b of neg[a xor b]:  ADJR(g, X)[b] = sum_a +-w X[a] g[a xor b]
@@ -233,6 +233,10 @@ struct Step {
     // GSQRT_ADJ (GAAST_OP_GSQRT_ADJ): res += the cotangent of A, the solution of ADJL(a, X) + ADJR(a, X) = g.  Operands, blade set and
     // tables are GEXP's and GEXP_ADJ's, field for field (inv.wmax is not used; inv.adj_neg_l / adj_neg_r are the two sign words of a row of
     // the transposed L_X + R_X).  Like them the steps are always launches of their own.
+    // GLOG (GAAST_OP_GLOG, gaast_hip.h): res += the principal logarithm of A = row `a` by inverse scaling and squaring (roots of GSQRT, a
+    // [7/7] Pade approximant in partial fractions), and GLOG_ADJ (GAAST_OP_GLOG_ADJ): res += the cotangent of A.  Operands, blade set and
+    // tables are GEXP's and GEXP_ADJ's again (inv.wmax scales the distance from e_0; inv.adj_neg_l is the sign word of a row of the
+    // transposed R_M, inv.adj_neg_r of the transposed L_M).  Always launches of their own.
 
     // REDUCE_SCALE (plan_passes.cpp: fuse_reduce_scale): a product whose result is ONE scalar component (a single long row: norm_sq), an
     // optional ScalarUnaryOp on it, and a product of one-term rows that multiplies another row by that scalar -- the versor inverse
@@ -322,6 +326,7 @@ struct Plan {
     int has_inverse = 0;               // some step is a general inverse: the program owns the domain-error counter too (singular items)
     int has_gexp = 0;                  // some step is a general exponential: it owns the domain-error counter too (theta out of range)
     int has_gsqrt = 0;                 // some step is a general square root: it owns the domain-error counter too (no principal root reached)
+    int has_glog = 0;                  // some step is a general logarithm: it owns the domain-error counter too (no principal logarithm reached)
     int has_explog_adj = 0;            // some step is an exp / log adjoint (no interpreter micro-ops, no domain check)
     int mirrored = 0;                  // the program runs in the orthogonal basis of a Gram metric whose Q has det -1: every
                                        // complement sign and regressive coefficient is negated (gaast_hip.h: GAAST_OP_DUAL)

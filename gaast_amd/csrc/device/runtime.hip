@@ -222,6 +222,10 @@ struct Launch {
         DevTable a_off, res_off, g_off, neg, neg_l, neg_r, weight;
         const void* kernel = nullptr;   // k_mv_gsqrt<T, N> / k_mv_gsqrt_adj<T, N>
     } gsqrt;
+    struct {   // GLOG, GLOG_ADJ
+        DevTable a_off, res_off, g_off, neg, neg_l, neg_r, weight;
+        const void* kernel = nullptr;   // k_mv_glog<T, N> / k_mv_glog_adj<T, N>
+    } glog;
     struct {   // PRODUCT_CSR: k_product_csr, k_product_ell, k_product_ell_chain or the specialised gaast_chain
         DevTable row_start, row_out, entries, coeff;
         struct { DevTable entries, row_map; } pre;        // k_product_ell_chain: the first list
@@ -741,6 +745,57 @@ int run_gsqrt(const Launch& L, const Operands& o, int64_t batch) {
     p.dom = static_cast<unsigned long long*>(L.domain);
     const int64_t per_block = 256 / s.inv.N;
     launch_kernel(L.gsqrt.kernel, persistent_grid((batch + per_block - 1) / per_block, 8), 256, 0, p);
+    return launch_status();
+}
+
+// ---- GLOG, GLOG_ADJ ----------------------------------------------------------------------------------------------------
+// (one kernel per (T, N) each, chosen by step kind and N: nothing is chosen at launch, the variant is 0)
+template <typename T>
+int prepare_glog(Launch& L, std::string& kernel) {
+    Step& s = L.s;
+    auto& c = L.glog;
+    const bool adj = s.kind == Step::GLOG_ADJ;
+    using Kern = void (*)(GlogArgs<T>);
+    c.kernel = kernel_address(adj ? static_int<2, 4, 8, 16, 32, 64>(s.inv.N, [](auto n) -> Kern { return k_mv_glog_adj<T, decltype(n)::value>; })
+                                  : static_int<2, 4, 8, 16, 32, 64>(s.inv.N, [](auto n) -> Kern { return k_mv_glog<T, decltype(n)::value>; }));
+    if (!c.kernel) return set_err(GAAST_ERR_UNIMPLEMENTED, "no general-logarithm kernel for " + std::to_string(s.inv.N) + " blades");
+    Upload<T> up;
+    up.idx(c.a_off, s.inv.a_off); up.idx(c.res_off, s.inv.res_off); up.idx(c.neg, s.inv.neg); up.val(c.weight, s.inv.weight);
+    if (adj) {
+        up.idx(c.g_off, s.inv.g_off); up.idx(c.neg_l, s.inv.adj_neg_l); up.idx(c.neg_r, s.inv.adj_neg_r);
+    }
+    kernel = std::string(adj ? "k_mv_glog_adj<" : "k_mv_glog<") + type_name<T>() + "," + std::to_string(s.inv.N) + ">";
+    return up.status;
+}
+
+template <typename T>
+int run_glog(const Launch& L, const Operands& o, int64_t batch) {
+    const Step& s = L.s;
+    if (batch <= 0) return GAAST_OK;
+    const bool adj = s.kind == Step::GLOG_ADJ;
+    GlogArgs<T> p;
+    p.res = static_cast<T*>(o.res.ptr);
+    p.in = static_cast<const T*>(o.a.ptr);
+    p.cot = adj ? static_cast<const T*>(o.b.ptr) : nullptr;
+    p.res_stride = o.res.stride;
+    p.in_stride = o.a.stride;
+    p.cot_stride = adj ? o.b.stride : 0;
+    p.batch = batch;
+    p.a_off = L.glog.a_off.as<int32_t>();
+    p.res_off = L.glog.res_off.as<int32_t>();
+    p.g_off = L.glog.g_off.as<int32_t>();
+    p.neg = L.glog.neg.as<uint64_t>();
+    p.neg_l = L.glog.neg_l.as<uint64_t>();
+    p.neg_r = L.glog.neg_r.as<uint64_t>();
+    p.weight = L.glog.weight.as<T>();
+    p.a_neg = s.inv.a_neg;
+    p.wmax = T(s.inv.wmax);
+    p.n = L.n;
+    p.even = s.inv.even;
+    p.beta = s.beta;
+    p.dom = static_cast<unsigned long long*>(L.domain);
+    const int64_t per_block = 256 / s.inv.N;
+    launch_kernel(L.glog.kernel, persistent_grid((batch + per_block - 1) / per_block, 8), 256, 0, p);
     return launch_status();
 }
 
@@ -1679,6 +1734,8 @@ int prepare_launch(Launch& L, const gaast_hip_program_s& prog) {
     case Step::GEXP_ADJ: st = prepare_gexp<T>(L, kernel); break;
     case Step::GSQRT:
     case Step::GSQRT_ADJ: st = prepare_gsqrt<T>(L, kernel); break;
+    case Step::GLOG:
+    case Step::GLOG_ADJ: st = prepare_glog<T>(L, kernel); break;
     }
     if (st) return st;
     L.label = kernel.empty() ? s.name : s.name + " :: " + kernel;
@@ -1720,7 +1777,7 @@ int program_create_impl(const gaast_program_desc* desc, gaast_hip_program_t* out
         if (int st = make_launches(d2, small_reg_slab, mirrored, *prog)) return st;
     }
     compile_chains(*prog, desc->flags);
-    if (prog->plan.has_explog || prog->plan.has_inverse || prog->plan.has_gexp || prog->plan.has_gsqrt)
+    if (prog->plan.has_explog || prog->plan.has_inverse || prog->plan.has_gexp || prog->plan.has_gsqrt || prog->plan.has_glog)
         if (int st = prog->domain.upload(std::vector<unsigned long long>(1, 0))) return st;
     for (Launch& L : prog->launches)
         if (int st = prepare_launch(L, *prog)) return st;
@@ -2420,6 +2477,8 @@ int run_launch(const Launch& L, const Operands& o, int64_t batch) {
     case Step::GEXP_ADJ: st = run_gexp<T>(L, o, batch); break;
     case Step::GSQRT:
     case Step::GSQRT_ADJ: st = run_gsqrt<T>(L, o, batch); break;
+    case Step::GLOG:
+    case Step::GLOG_ADJ: st = run_glog<T>(L, o, batch); break;
     }
     L.variant = variant;
     return st;

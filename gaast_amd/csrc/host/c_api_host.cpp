@@ -169,6 +169,7 @@ gaast_expr_t gaast_expr_undual(gaast_expr_t e) { return wrap(make_unary(ExprNode
 gaast_expr_t gaast_expr_inv(gaast_expr_t e) { return wrap(make_unary(ExprNode::INV, e->node)); }
 gaast_expr_t gaast_expr_gexp(gaast_expr_t e) { return wrap(make_unary(ExprNode::GEXP, e->node)); }
 gaast_expr_t gaast_expr_gsqrt(gaast_expr_t e) { return wrap(make_unary(ExprNode::GSQRT, e->node)); }
+gaast_expr_t gaast_expr_glog(gaast_expr_t e) { return wrap(make_unary(ExprNode::GLOG, e->node)); }
 
 gaast_spec_t gaast_expr_specialize(gaast_expr_t e, int n, const double* metric_diag,
                                    uint64_t materialize_limit) {

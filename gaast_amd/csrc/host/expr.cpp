@@ -246,6 +246,13 @@ struct Builder {
             add_node(this_id, p, GS{m, top_len(m)});
             return;
         }
+        case ExprNode::GLOG: {  // the general logarithm (gaast_hip.h: GAAST_OP_GLOG): the grades of the general inverse; no scalar lowering
+            p.child0 = reify_or_reuse(e->a, &gs);
+            p.opcode = GAAST_OP_GLOG;
+            const uint64_t m = gs_inverse(gs.mask, ast.n);
+            add_node(this_id, p, GS{m, top_len(m)});
+            return;
+        }
         case ExprNode::EXP: {  // GradeSet::exp, grade_set.rs:181-187
             p.child0 = reify_or_reuse(e->a, &gs);
             if (__builtin_popcountll(gs.mask) != 1)
@@ -319,6 +326,7 @@ void rec_update_minimal(SpecializedAst& s, int idx, uint64_t wanted) {  // speci
     case GAAST_OP_UNDUAL: rec_update_minimal(s, n.child0, gs_mirror(wanted, s.n)); return;
     case GAAST_OP_GEXP:
     case GAAST_OP_GSQRT:
+    case GAAST_OP_GLOG:
     case GAAST_OP_INV: rec_update_minimal(s, n.child0, s.nodes[size_t(n.child0)].maximal); return;  // every component of the operand enters every component of the inverse
     case GAAST_OP_ADD: {
         int l = n.child0, r = n.child1;

@@ -20,7 +20,7 @@ namespace gaast {
 // (expr.rs:74-76); here the node object itself plays that role: identity == address, clones
 // (shared_ptr copies) share it.
 struct ExprNode {
-    enum Kind { MV, ADD, NEG, PRODUCT, REV, GINVOL, EXP, LOG, GSELECT, SINV, WRAP_SQRT, WRAP_VINV, DUAL, UNDUAL, INV, GEXP, GSQRT };
+    enum Kind { MV, ADD, NEG, PRODUCT, REV, GINVOL, EXP, LOG, GSELECT, SINV, WRAP_SQRT, WRAP_VINV, DUAL, UNDUAL, INV, GEXP, GSQRT, GLOG };
     Kind kind;
     std::shared_ptr<ExprNode> a, b;
     Selection sel;            // PRODUCT

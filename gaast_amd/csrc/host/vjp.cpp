@@ -25,6 +25,9 @@
 //   gsqrt       (GAAST_OP_GSQRT, gaast_hip.h) like gexp: the operand's cotangent is one GAAST_OP_GSQRT_ADJ node over (the buffer's cotangent
 //               restricted to the node's grades, the forward operand): the solve of ADJL(a, X) + ADJR(a, X) = g with the recomputed
 //               root X.  No flag;
+//   glog        (GAAST_OP_GLOG, gaast_hip.h) like gsqrt: the operand's cotangent is one GAAST_OP_GLOG_ADJ node over (the buffer's cotangent
+//               restricted to the node's grades, the forward operand): the transposed Pade solves and the chain of root adjoints,
+//               with the recomputed forward.  No flag;
 //   exp / log   (GAAST_FLAG_EXP_LOG | GAAST_FLAG_EXP_LOG_GRAD) the operand has a buffer of its own, like a product operand
 //               (plan.cpp: lower_exp_log -> store_in_cache): a one-operand product event -- GAAST_OP_EXP_ADJ / GAAST_OP_LOG_ADJ over
 //               the buffer's cotangent restricted to the node's grades and the forward operand -> cotangent of the operand buffer.
@@ -54,7 +57,7 @@ struct VjpError {
 };
 
 bool has_two_children(int opcode) {
-    return opcode == GAAST_OP_ADD || opcode == GAAST_OP_PRODUCT || opcode == GAAST_OP_EXP_ADJ || opcode == GAAST_OP_LOG_ADJ || opcode == GAAST_OP_GEXP_ADJ || opcode == GAAST_OP_GSQRT_ADJ;
+    return opcode == GAAST_OP_ADD || opcode == GAAST_OP_PRODUCT || opcode == GAAST_OP_EXP_ADJ || opcode == GAAST_OP_LOG_ADJ || opcode == GAAST_OP_GEXP_ADJ || opcode == GAAST_OP_GSQRT_ADJ || opcode == GAAST_OP_GLOG_ADJ;
 }
 
 enum EventKind { EV_INPUT, EV_PRODUCT, EV_FLIP, EV_SCALAR, EV_OPAQUE };
@@ -191,7 +194,7 @@ struct Builder {
             }
             ev.push_back({EV_OPAQUE, x, path});
             return;
-        default: ev.push_back({EV_OPAQUE, x, path}); return;  // exp / log, dual / undual, gexp, gsqrt
+        default: ev.push_back({EV_OPAQUE, x, path}); return;  // exp / log, dual / undual, gexp, gsqrt, glog
         }
     }
     // inv: cotangent of the operand's buffer
@@ -244,6 +247,19 @@ struct Builder {
         const int g = materialize(terms, xd.minimal_grade_mask);
         if (g < 0 || !cmask) return;
         gaast_node_desc nd = blank(GAAST_OP_GSQRT_ADJ, cmask, n);
+        nd.child0 = g;
+        nd.child1 = c;
+        cot[size_t(c)].push_back(Term{add(nd), 0, ~0ULL});
+    }
+    // glog: cotangent of the operand's buffer (gaast_hip.h: GAAST_OP_GLOG_ADJ)
+    void glog_adjoint(int x, const std::vector<Term>& terms, std::vector<std::vector<Term>>& cot) {
+        const gaast_node_desc& xd = d.nodes[x];
+        const int c = xd.child0;
+        if (!dep[size_t(c)]) return;
+        const uint64_t cmask = d.nodes[c].minimal_grade_mask;
+        const int g = materialize(terms, xd.minimal_grade_mask);
+        if (g < 0 || !cmask) return;
+        gaast_node_desc nd = blank(GAAST_OP_GLOG_ADJ, cmask, n);
         nd.child0 = g;
         nd.child1 = c;
         cot[size_t(c)].push_back(Term{add(nd), 0, ~0ULL});
@@ -436,6 +452,7 @@ struct Builder {
                     else if (x.opcode == GAAST_OP_INV) inv_adjoint(e.node, terms, cot);
                     else if (x.opcode == GAAST_OP_GEXP) gexp_adjoint(e.node, terms, cot);
                     else if (x.opcode == GAAST_OP_GSQRT) gsqrt_adjoint(e.node, terms, cot);
+                    else if (x.opcode == GAAST_OP_GLOG) glog_adjoint(e.node, terms, cot);
                     else explog_adjoint(e.node, terms, cot);
                     break;
                 }
@@ -490,7 +507,7 @@ extern "C" int gaast_program_vjp(const gaast_program_desc* desc, int32_t wrt_slo
         const gaast_node_desc& nd = d.nodes[i];
         const bool two = nd.opcode == GAAST_OP_ADD || nd.opcode == GAAST_OP_PRODUCT;
         const bool ok = nd.opcode == GAAST_OP_INPUT ? (nd.input_slot >= 0 && nd.input_slot < d.n_inputs)
-                        : (nd.opcode > GAAST_OP_INPUT && (nd.opcode <= GAAST_OP_SSQRT || nd.opcode == GAAST_OP_DUAL || nd.opcode == GAAST_OP_UNDUAL || nd.opcode == GAAST_OP_INV || nd.opcode == GAAST_OP_GEXP || nd.opcode == GAAST_OP_GSQRT) &&
+                        : (nd.opcode > GAAST_OP_INPUT && (nd.opcode <= GAAST_OP_SSQRT || nd.opcode == GAAST_OP_DUAL || nd.opcode == GAAST_OP_UNDUAL || nd.opcode == GAAST_OP_INV || nd.opcode == GAAST_OP_GEXP || nd.opcode == GAAST_OP_GSQRT || nd.opcode == GAAST_OP_GLOG) &&
                            nd.child0 >= 0 && nd.child0 < i &&
                            (!two || (nd.child1 >= 0 && nd.child1 < i)));
         if (!ok || (nd.opcode == GAAST_OP_PRODUCT && nd.product_kind >= GAAST_PROD_ADJ_LEFT)) {

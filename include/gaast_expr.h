@@ -113,6 +113,10 @@ gaast_expr_t gaast_expr_gexp(gaast_expr_t e);
  * multivector that has one, where gaast_expr_sqrt is a closed form for k-vectors whose square is a scalar; grades as
  * gaast_expr_inv; a scalar operand is the scalar square root (GAAST_OP_SSQRT) */
 gaast_expr_t gaast_expr_gsqrt(gaast_expr_t e);
+/* no reference counterpart: the general multivector logarithm (GAAST_OP_GLOG, gaast_hip.h), the principal Y with gexp(Y) = e for any
+ * multivector that has one, by inverse scaling and squaring, where gaast_expr_log is a closed form for k-vectors whose square is a
+ * scalar; grades as gaast_expr_inv; no scalar lowering (a scalar operand is evaluated over the even blades) */
+gaast_expr_t gaast_expr_glog(gaast_expr_t e);
 
 /* ---- reify + specialize (phases 2-3) ---------------------------------------------------------- */
 /* Expr::specialize(&alg), specialize.rs:36-50, with alg = the diagonal metric `metric_diag[n]`
@@ -175,7 +179,8 @@ void gaast_program_image_free(gaast_program_image_t img);
  * A GAAST_OP_INV node Y = inv(A) gives A the cotangent -ADJ_RIGHT(ADJ_LEFT(g, Y), Y) (geometric adjoint products and a
  * GAAST_OP_NEG; Y is one more GAAST_OP_INV node over the forward operand, producing every grade of its blade set).
  * A GAAST_OP_GEXP node gives its operand one GAAST_OP_GEXP_ADJ node over (the buffer's cotangent restricted to the node's grades,
- * the forward operand); no flag is needed.  A GAAST_OP_GSQRT node likewise gives its operand one GAAST_OP_GSQRT_ADJ node.
+ * the forward operand); no flag is needed.  A GAAST_OP_GSQRT node likewise gives its operand one GAAST_OP_GSQRT_ADJ node,
+ * a GAAST_OP_GLOG node one GAAST_OP_GLOG_ADJ node.
  * A program specialised for the orthogonal basis of a Gram metric differentiates like any other: its VJP program is created with the
  * same basis (gaast_hip_program_create_vjp_in_basis, gaast_hip.h), the cotangent being one more batched input.
  * Errors: GAAST_ERR_INVALID_ARGUMENT for a wrt_slot out of range or const, or n_inputs + 1 > GAAST_MAX_INPUTS;

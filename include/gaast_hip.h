@@ -193,7 +193,56 @@ typedef enum gaast_opcode {
      * forward is recomputed, the system solved by GAAST_OP_INV's elimination.  A failed pivot test of this solve makes every
      * component of the item's cotangent NaN; it is not counted, and neither is a domain-error item of the recomputed forward, whose
      * cotangent is NaN likewise. */
-    GAAST_OP_GSQRT_ADJ = 19
+    GAAST_OP_GSQRT_ADJ = 19,
+    /* General multivector logarithm (no reference counterpart): glog(A) is the PRINCIPAL logarithm, the Y with gexp(Y) = A whose
+     * left-multiplication matrix L_Y has every eigenvalue in the strip |Im| < pi.  It exists and is unique when L_A is nonsingular
+     * and has no eigenvalue on the negative real axis; it is then a primary function of A, lies in the blade set S of
+     * GAAST_OP_INV and commutes with A.  The reference's log (behind GAAST_FLAG_EXP_LOG) is a closed form for k-vectors whose square
+     * is a scalar and stays what it is.  One child.  S, N = |S|, its ordering and L_A are GAAST_OP_INV's; so are the node's maximal
+     * grade set (GAAST_OP_GEXP's), the grades it produces and what it wants of its child (every grade it holds), and like every arm
+     * it ADDS into the buffer that contains it.  There is no scalar lowering (no scalar-log opcode exists): a scalar operand is
+     * evaluated over the even set, as GAAST_OP_GEXP does it.  Supported: N = 2 ... 64 (any mask for n <= 6, even masks for n = 7);
+     * anything else is GAAST_ERR_UNIMPLEMENTED from gaast_hip_program_create, phases 1-3 succeeding on the host.  No flag gates the
+     * node and GAAST_FLAG_EXACT_ORDER changes nothing: there are no reference bits.
+     * Algorithm (inverse scaling and squaring, in multivector space: every iterate is a multivector over S; every sum over j
+     * ascending), per item, with e_0 the scalar unit and wmax as GAAST_OP_GEXP defines it:
+     *   X_0 = A, s = 0;
+     *   while wmax * sum_r |(X_s - e_0)_r| > 1/4 (the butterfly sum of GAAST_OP_GSQRT) and s < S = 16:
+     *     X_(s+1) = the principal root of X_s, exactly GAAST_OP_GSQRT's iteration (same stop rule, same K = 16 steps);  s += 1;
+     *   E = X_s - e_0;   Y = sum_(j = 1 ... 7) alpha_j y_j,  y_j the solution of L_(e_0 + beta_j E) y_j = E,
+     *     the [7/7] Pade approximant of log(1 + x) in partial fractions: alpha_j, beta_j are the weights and nodes of 7-point
+     *     Gauss-Legendre quadrature on [0, 1] (gaast_amd/csrc/common/glog_pade.hpp).  Each term is one run of GAAST_OP_INV's
+     *     elimination with right-hand side E and the pivot test !(|p| > N eps max_i |(e_0 + beta_j E)_i|): no inverse, no product;
+     *   the result is 2^s Y (the factor is exact).
+     * For ||L_E||_inf <= 1/4 the truncation error of the approximant is at most |r_7(-1/4) - log(3/4)| < 1e-16 (Kenney and Laub);
+     * the same threshold 1/4 and degree 7 serve both value types.
+     * Domain errors: an item with a non-finite component, with any domain error of a root it takes, still beyond 1/4 at s = S, or with
+     * a failed pivot in a Pade solve.  Every produced component of it is a quiet NaN and it is counted once in
+     * gaast_hip_program_domain_errors (a program with a GLOG step owns the counter).  -1, a vector (eigenvalues +-1), 0 and PGA's
+     * ideal elements are such items by nature; so are unipotent items with sum |A - e_0| > 2^14 (1 + t e01 with a large t: each root
+     * only halves t), a documented limitation and not a mathematical one.  The root's pivot test sets a second such limit: the
+     * first root of 1 + t e01 meets the pivot 1 / t against N eps t, so the translator needs t^2 < 1 / (N eps) (in f32 over the 8
+     * even blades of PGA3D: t < 1024).
+     * Accuracy: per item that is no domain error, ||Y - log A||_inf <= 4 FWD_SCALE N eps max(1, sum_i |(log A)_i|), FWD_SCALE the
+     * worst of the numpy restatement of these recurrences over the test sweep (tests/glog_numpy.py: FWD_SCALE = 8.0 in f32 and 7.5
+     * in f64, measured 7.96 and 7.19, both on R^1; operands gexp(B) with sum |B_i| <= 2.5, operands with a dominant positive
+     * scalar, and the former scaled by 37.5 and by 0.01: 0 ... 5 roots).  The reverse mode likewise: GRAD_SCALE = 2.3 / 2.0
+     * (measured 2.20 / 1.95) in units of N eps max(1, sum_i |(log A)_i|) ||J^T||_inf ||g||_inf. */
+    GAAST_OP_GLOG = 20,
+    /* Reverse mode of GAAST_OP_GLOG, emitted by gaast_program_vjp: child0 = the cotangent g of the GLOG node (any grades within S),
+     * child1 = the forward operand A; the node's own minimal grade mask is the operand's.  It ADDS into its buffer; no flag.
+     * The forward is recomputed, keeping X_1 ... X_s.  Then, with GAAST_OP_GEXP_ADJ's operators:
+     *   g' = 2^s g;
+     *   a = sum_j alpha_j u_j,  where v_j solves R_(M_j)^T v_j = g' and u_j solves L_(M_j)^T u_j = v_j,  M_j = e_0 + beta_j E:
+     *     the exact derivative of the approximant, d r(E) = sum_j alpha_j M_j^-1 dE M_j^-1 (the two solves commute).  Row c of
+     *     R_M^T has coeff(c, t) M[t] with ADJL's sign at column c xor t, row c of L_M^T the same with ADJR's sign: the two halves of
+     *     GAAST_OP_GSQRT_ADJ's row;
+     *   for i = s ... 1:  a <- the solution of ADJL(a, X_i) + ADJR(a, X_i) = a, GAAST_OP_GSQRT_ADJ's system at X_i;
+     *   a restricted to the grades the operand holds.
+     * Every solve is GAAST_OP_INV's elimination, the pivot test against N eps max_i |M_i| of the multivector whose matrix it is.  A
+     * failed pivot test, or a domain error of the recomputed forward, makes every component of the item's cotangent NaN; it is not
+     * counted.  Accuracy: 4 GRAD_SCALE in the units GAAST_OP_GLOG states (tests/glog_numpy.py). */
+    GAAST_OP_GLOG_ADJ = 21
 } gaast_opcode;
 
 /* the five products of src/ast/expr.rs:180-197 (and the regressive product), for compact PRODUCT descriptors */
@@ -342,8 +391,9 @@ int gaast_hip_program_launch_variant(gaast_hip_program_t prog, int i);
  * k-vector whose square is not scalar: |<B B>_{not 0}|^2 > 2^-40 (sum B_i^2)^2); their results are the closed form applied
  * to <B B>_0 regardless.  A program with a GAAST_OP_INV step counts its singular items here too (their produced components are
  * NaN), one with a GAAST_OP_GEXP step its domain errors (theta not finite or > 2048; NaN likewise), one with a GAAST_OP_GSQRT step
- * the items without a principal root it can reach (GAAST_OP_GSQRT; NaN likewise).  Synchronises the library stream; resets the
- * counter.  0 for programs without exp / log / inv / gexp / gsqrt. */
+ * the items without a principal root it can reach (GAAST_OP_GSQRT; NaN likewise), one with a GAAST_OP_GLOG step the items without a
+ * principal logarithm it can reach (GAAST_OP_GLOG; NaN likewise).  Synchronises the library stream; resets the counter.  0 for
+ * programs without exp / log / inv / gexp / gsqrt / glog. */
 int gaast_hip_program_domain_errors(gaast_hip_program_t prog, int64_t *count);
 /* GAAST_FLAG_DEBUG_KEEP_JIT_SOURCE: the HIP source generated for this program ("" if none). */
 const char *gaast_hip_program_jit_source(gaast_hip_program_t prog);

@@ -211,6 +211,7 @@ impl<T: GradedData + std::fmt::Debug> SpecializedAst<T> {
                 // in all of its grades (a scalar child: ScalarUnaryOp::Inversion, as above).
                 // The general exponential (OP_GEXP) flattens the same way, with the same grade set; its adjoint node OP_GEXP_ADJ is only ever emitted by gaast_program_vjp.
                 // The general square root (OP_GSQRT / OP_GSQRT_ADJ) likewise; of a scalar child it is ScalarUnaryOp::Sqrt.
+                // The general logarithm (OP_GLOG / OP_GLOG_ADJ) likewise, with no scalar lowering.
             }
             nodes.push(d);
         }

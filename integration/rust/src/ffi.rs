@@ -35,6 +35,9 @@ pub const OP_GEXP_ADJ: i32 = 17;
 // general (principal) multivector square root by the Denman-Beavers product iteration (no AstNode counterpart), and its reverse-mode node (child0 = cotangent, child1 = operand)
 pub const OP_GSQRT: i32 = 18;
 pub const OP_GSQRT_ADJ: i32 = 19;
+// general (principal) multivector logarithm by inverse scaling and squaring (no AstNode counterpart), and its reverse-mode node (child0 = cotangent, child1 = operand)
+pub const OP_GLOG: i32 = 20;
+pub const OP_GLOG_ADJ: i32 = 21;
 // compact product kinds (gaast_product_kind); 5 = the regressive product a v b = undual(dual(a) ^ dual(b))
 pub const PROD_REGRESSIVE: i32 = 5;
 
