@@ -387,6 +387,14 @@ class SpecializedAst:
             cache[slot] = Vjp(self, int(slot))
         return cache[slot]
 
+    def jvp(self, slot):
+        """Forward mode with respect to input `slot` (the double-VJP trick: the VJP program differentiated with respect to its
+        cotangent), built once per slot: an object with eval_batch(inputs, tangent, batch, out=None) -> J v."""
+        cache = self.__dict__.setdefault("_jvps", {})
+        if slot not in cache:
+            cache[slot] = Jvp(self, int(slot))
+        return cache[slot]
+
     def torch_fn(self):
         """A callable on torch tensors [B or 1, row_len] backed by a torch.autograd.Function (gaast_amd.autograd)."""
         from .autograd import torch_fn
@@ -400,13 +408,17 @@ class SpecializedAst:
 
 
 class Vjp:
-    """Reverse mode of a SpecializedAst with respect to one input slot: a program whose inputs are the forward inputs and the
-    cotangent (slot = number of forward slots), and whose output is the gradient in the layout of input `slot`."""
+    """Reverse mode of a program with respect to one input slot: a program whose inputs are those of the program it differentiates
+    and the cotangent (slot = that program's number of slots), and whose output is the gradient in the layout of input `slot`.
+    The program differentiated (`parent`) is a SpecializedAst or another Vjp: gaast_program_vjp is closed under itself, except
+    through the adjoint nodes of exp / log / gexp / gsqrt / glog (GAAST_ERR_UNIMPLEMENTED)."""
 
-    def __init__(self, spec, slot):
+    def __init__(self, parent, slot):
         L = _lib.lib()
-        self.spec, self.slot, self.dtype = spec, slot, spec.dtype
-        d = spec.program_desc()
+        self.parent = parent
+        self.spec = parent.spec if isinstance(parent, Vjp) else parent     # the forward program: dtype, flags and basis
+        self.slot, self.dtype = slot, self.spec.dtype
+        d = parent.program_desc()
         img = C.c_void_p()
         st = L.gaast_program_vjp(C.byref(d), slot, C.byref(img))
         if st:
@@ -416,6 +428,7 @@ class Vjp:
         self.n_fwd = d.n_inputs
         self.wrt_dim, self.wrt_mask = d.inputs[slot].storage_dim, d.inputs[slot].grade_mask
         self._prog = None
+        self._vjps = {}
 
     def __del__(self):
         try:
@@ -425,6 +438,20 @@ class Vjp:
                 _lib.lib().gaast_program_image_free(self._img)
         except Exception:
             pass
+
+    def program_desc(self):
+        """The flat VJP program (owned by this object)."""
+        return self.desc
+
+    def vjp(self, slot):
+        """The VJP of this VJP program with respect to one of its non-const slots: a forward slot, or `n_fwd`, the cotangent.  Built
+        once per slot.  Its `inputs` are this program's bound slots -- the inputs of the program differentiated here, then the
+        cotangent -- and its cotangent has the layout of this program's output.  For a GramAlgebra every level is created in the
+        forward program's basis; all rows are in the caller's basis."""
+        slot = int(slot)
+        if slot not in self._vjps:
+            self._vjps[slot] = Vjp(self, slot)
+        return self._vjps[slot]
 
     def program(self):
         if self._prog is None:
@@ -449,14 +476,31 @@ class Vjp:
         p = self.program()
         return [_lib.lib().gaast_hip_program_launch_variant(p, i) for i in range(_lib.lib().gaast_hip_program_num_launches(p))]
 
+    def domain_errors(self):
+        """As SpecializedAst.domain_errors, for the items this program refused (its inv / gexp / gsqrt / glog nodes recompute the
+        forward)."""
+        n = C.c_int64()
+        _lib.check(_lib.lib().gaast_hip_program_domain_errors(self.program(), C.byref(n)))
+        return n.value
+
+    def _place(self, inputs, cotangent):
+        """[(slot, value)] of what is bound: the parent's inputs where the parent has them, the cotangent at slot n_fwd."""
+        inputs = list(inputs)
+        if isinstance(self.parent, Vjp):   # the parent's bound slots: its own inputs, then its cotangent
+            below = self.parent._place(inputs[:-1], inputs[-1]) if inputs else []
+        else:
+            below = list(enumerate(inputs[:self.n_fwd]))
+        return below + [(self.n_fwd, cotangent)]
+
     def eval_batch(self, inputs, cotangent, batch, reduce=False, out=None):
-        """Gradient rows of input `slot` for each item (inputs as for SpecializedAst.eval_batch, cotangent: [batch, root row]
-        or a DeviceMV).  reduce=True: their sum over the batch (gaast_hip_mv_sum_rows), one row."""
+        """Gradient rows of input `slot` for each item (inputs as for the program differentiated: SpecializedAst.eval_batch's, or for
+        a Vjp its inputs followed by its cotangent; cotangent: [batch, row of that program's output] or a DeviceMV).
+        reduce=True: their sum over the batch (gaast_hip_mv_sum_rows), one row."""
         prog = self.program()
         n_slots = self.desc.n_inputs
         handles = (C.c_void_p * n_slots)()
         keep = []
-        for s, x in enumerate(list(inputs)[:self.n_fwd] + [None] * (self.n_fwd - min(len(inputs), self.n_fwd)) + [cotangent]):
+        for s, x in self._place(inputs, cotangent):
             if x is None:
                 continue
             if not isinstance(x, DeviceMV):
@@ -473,6 +517,33 @@ class Vjp:
         if reduce:
             return grad.sum_rows(out)
         return grad
+
+
+class Jvp:
+    """Forward mode of a SpecializedAst with respect to one input slot, by the double-VJP trick: the VJP program is linear in its
+    cotangent g, so its own VJP with respect to g, given a cotangent v in the layout of input `slot`, is J v in the root's layout
+    and never reads g."""
+
+    def __init__(self, spec, slot):
+        self.spec, self.slot = spec, int(slot)
+        first = spec.vjp(self.slot)
+        self.vjp2 = first.vjp(first.n_fwd)
+        d = self.vjp2.desc
+        if any(d.nodes[i].opcode == _lib.OP_INPUT and d.nodes[i].input_slot == first.n_fwd for i in range(d.n_nodes)):
+            raise _lib.GaastError(1, "the JVP program reads the cotangent of the VJP it differentiates")
+
+    def program(self):
+        return self.vjp2.program()
+
+    def launches(self):
+        return self.vjp2.launches()
+
+    def eval_batch(self, inputs, tangent, batch, out=None):
+        """J v for each item: inputs as for SpecializedAst.eval_batch, tangent: [batch, row of input `slot`] or a DeviceMV.
+        Returns rows in the layout of the forward program's output."""
+        n_user = self.spec.num_user_inputs()
+        inputs = list(inputs)[:n_user] + [None] * (n_user - min(len(inputs), n_user))
+        return self.vjp2.eval_batch(inputs + [None], tangent, batch, out=out)
 
 
 class ProgramImage:

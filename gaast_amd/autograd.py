@@ -4,6 +4,10 @@ Every argument is a contiguous f32 / f64 GPU tensor [B or 1, row_len] in the lay
 tensor is shared by every item).  Forward evaluates the program, backward its VJP programs (gaast_program_vjp): one per input that
 needs a gradient, built on first use and kept by the spec.  The gradient of a shared (batch-1) input among batch-B inputs is the sum
 of its per-item gradients (gaast_hip_mv_sum_rows).  Both directions run on torch's current stream.
+
+Backward is differentiable to any order (create_graph=True: Hessian-vector products, gradient penalties): each gradient is a second
+autograd.Function over the Vjp object, whose own backward evaluates Vjp.vjp(slot), built when first asked for.  Programs that hold
+exp / log / gexp / gsqrt / glog on the path differentiate once; asking for their second derivative raises GaastError UNIMPLEMENTED.
 """
 from __future__ import annotations
 
@@ -54,30 +58,74 @@ class _ProgramFunction(torch.autograd.Function):
         return out
 
     @staticmethod
-    @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         xs = ctx.saved_tensors
-        spec, B = ctx.spec, ctx.batch
         g = g.contiguous()
-        _use_torch_stream()
-        ins = [_wrap(x, *ctx.layouts[i]) for i, x in enumerate(xs)]
-        cot = _wrap(g, *ctx.out_layout)
         grads = [None, None]
-        for i, x in enumerate(xs):
-            if not ctx.needs_input_grad[i + 2]:
-                grads.append(None)
-                continue
-            dim, mask = ctx.layouts[i]
-            v = spec.vjp(i)
-            per_item = torch.empty((B, x.shape[1]), dtype=x.dtype, device=x.device)
-            pm = v.eval_batch(ins, cot, B, out=_wrap(per_item, dim, mask))
-            if x.shape[0] == 1 and B > 1:
-                total = torch.empty((1, x.shape[1]), dtype=x.dtype, device=x.device)
-                pm.sum_rows(_wrap(total, dim, mask))
-                grads.append(total)
-            else:
-                grads.append(per_item)
+        for i in range(len(xs)):
+            grads.append(_gradient(ctx.spec, i, xs, g, ctx.batch) if ctx.needs_input_grad[i + 2] else None)
         return tuple(grads)
+
+
+def _bound_slots(prog):
+    """The slots of `prog` (a SpecializedAst or a Vjp) that tensors are bound to, in the order of the tensors."""
+    if hasattr(prog, "parent"):
+        return _bound_slots(prog.parent) + [prog.n_fwd]
+    return list(range(prog.num_user_inputs()))
+
+
+def _gradient(prog, k, ts, cot, B):
+    """The gradient of <cot, prog(*ts)> with respect to ts[k]: one row per item, or their sum for a shared (batch-1) tensor among
+    B items.  Differentiable when grad mode is on (backward under create_graph=True); the VJP program is built on first use."""
+    v = prog.vjp(_bound_slots(prog)[k])
+    per_item = _VjpFunction.apply(v, B, *ts, cot)
+    if ts[k].shape[0] == 1 and B > 1:
+        return _SumRowsFunction.apply(per_item, v.wrt_dim, v.wrt_mask)
+    return per_item
+
+
+class _VjpFunction(torch.autograd.Function):
+    """The per-item gradient rows of a Vjp object as a function of its bound tensors (those of the program it differentiates,
+    then the cotangent).  Its own backward evaluates Vjp.vjp(slot) through this same class, so any order differentiates."""
+
+    @staticmethod
+    def forward(ctx, v, B, *ts):
+        _use_torch_stream()
+        d = v.desc
+        slots = _bound_slots(v)
+        ins = [_wrap(t, d.inputs[s].storage_dim, d.inputs[s].grade_mask) for s, t in zip(slots, ts)]
+        per_item = torch.empty((B, row_len(v.wrt_dim, v.wrt_mask)), dtype=ts[-1].dtype, device=ts[-1].device)
+        v.eval_batch(ins[:-1], ins[-1], B, out=_wrap(per_item, v.wrt_dim, v.wrt_mask))
+        ctx.v, ctx.batch = v, B
+        ctx.save_for_backward(*ts)
+        return per_item
+
+    @staticmethod
+    def backward(ctx, h):
+        ts = ctx.saved_tensors
+        # the cotangent of a summed gradient arrives as a stride-0 expansion of one row: a batch-1 tensor binds as shared
+        h = h[:1].contiguous() if h.shape[0] > 1 and h.stride(0) == 0 else h.contiguous()
+        grads = [None, None]
+        for k in range(len(ts)):
+            grads.append(_gradient(ctx.v, k, ts, h, ctx.batch) if ctx.needs_input_grad[k + 2] else None)
+        return tuple(grads)
+
+
+class _SumRowsFunction(torch.autograd.Function):
+    """gaast_hip_mv_sum_rows: the reduction of the per-item gradients of a shared input.  Linear: its backward hands the one-row
+    cotangent to every item, as a stride-0 expansion that is bound as a shared input again (no expansion kernel)."""
+
+    @staticmethod
+    def forward(ctx, per_item, dim, mask):
+        _use_torch_stream()
+        total = torch.empty((1, per_item.shape[1]), dtype=per_item.dtype, device=per_item.device)
+        _wrap(per_item, dim, mask).sum_rows(_wrap(total, dim, mask))
+        ctx.batch = per_item.shape[0]
+        return total
+
+    @staticmethod
+    def backward(ctx, h):
+        return h.expand(ctx.batch, h.shape[1]), None, None
 
 
 def torch_fn(spec):

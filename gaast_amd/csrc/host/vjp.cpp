@@ -31,6 +31,11 @@
 //   exp / log   (GAAST_FLAG_EXP_LOG | GAAST_FLAG_EXP_LOG_GRAD) the operand has a buffer of its own, like a product operand
 //               (plan.cpp: lower_exp_log -> store_in_cache): a one-operand product event -- GAAST_OP_EXP_ADJ / GAAST_OP_LOG_ADJ over
 //               the buffer's cotangent restricted to the node's grades and the forward operand -> cotangent of the operand buffer.
+// The function is closed under itself: a program it returned differentiates again.  Its explicit lists, NEG, INV, DUAL and PROJ
+// nodes are forward nodes like any other; a compact GAAST_PROD_ADJ_* node is a product event whose operands' cotangents are, by the
+// trilinear form <g, a o b> of the forward kind, the forward product or the other adjoint of the same kind (product_adjoint, table
+// in gaast_expr.h); the adjoint op nodes (GAAST_OP_*_ADJ) are opaque events that are carried along off the path and refused by name
+// on it (their derivative is a Frechet derivative of a matrix function).
 // Buffers are visited from the root down (decreasing node index: a buffer's users come after it in post-order).  The adjoint
 // program is evaluated in place as well, so every cotangent node it builds is ADDITIVE (input, product, or sums of them): adding
 // it into a buffer adds its value.  Sign changes and projections of a cotangent that cannot be folded into a list are explicit
@@ -58,6 +63,18 @@ struct VjpError {
 
 bool has_two_children(int opcode) {
     return opcode == GAAST_OP_ADD || opcode == GAAST_OP_PRODUCT || opcode == GAAST_OP_EXP_ADJ || opcode == GAAST_OP_LOG_ADJ || opcode == GAAST_OP_GEXP_ADJ || opcode == GAAST_OP_GSQRT_ADJ || opcode == GAAST_OP_GLOG_ADJ;
+}
+
+// the adjoint op nodes that gaast_program_vjp itself emits (child0 = a cotangent, child1 = the forward operand)
+const char* adjoint_op_name(int opcode) {
+    switch (opcode) {
+    case GAAST_OP_EXP_ADJ: return "GAAST_OP_EXP_ADJ";
+    case GAAST_OP_LOG_ADJ: return "GAAST_OP_LOG_ADJ";
+    case GAAST_OP_GEXP_ADJ: return "GAAST_OP_GEXP_ADJ";
+    case GAAST_OP_GSQRT_ADJ: return "GAAST_OP_GSQRT_ADJ";
+    case GAAST_OP_GLOG_ADJ: return "GAAST_OP_GLOG_ADJ";
+    default: return nullptr;
+    }
 }
 
 enum EventKind { EV_INPUT, EV_PRODUCT, EV_FLIP, EV_SCALAR, EV_OPAQUE };
@@ -194,7 +211,7 @@ struct Builder {
             }
             ev.push_back({EV_OPAQUE, x, path});
             return;
-        default: ev.push_back({EV_OPAQUE, x, path}); return;  // exp / log, dual / undual, gexp, gsqrt, glog
+        default: ev.push_back({EV_OPAQUE, x, path}); return;  // exp / log, dual / undual, gexp, gsqrt, glog and the adjoint op nodes
         }
     }
     // inv: cotangent of the operand's buffer
@@ -351,17 +368,36 @@ struct Builder {
                     cot[size_t(c)].push_back(Term{node, 0, ~0ULL});
                 }
             } else {
-                if (pd.product_kind < 0 || pd.product_kind > GAAST_PROD_REGRESSIVE)
+                const int adj = pd.product_kind >= 0 ? (pd.product_kind & ~7) : 0, base = pd.product_kind & 7;
+                if (pd.product_kind < 0 || base > GAAST_PROD_REGRESSIVE || (adj && adj != GAAST_PROD_ADJ_LEFT && adj != GAAST_PROD_ADJ_RIGHT))
                     throw VjpError{GAAST_ERR_INVALID_PROGRAM, "PRODUCT node has neither a comp-mul list nor a product kind"};
                 const int g = materialize(terms, pd.minimal_grade_mask);
                 if (g < 0) continue;
                 gaast_node_desc nd = blank(GAAST_OP_PRODUCT, cmask, n);
-                nd.child0 = g;
-                nd.child1 = other;
-                nd.product_kind = pd.product_kind + (side ? GAAST_PROD_ADJ_RIGHT : GAAST_PROD_ADJ_LEFT);
-                const Selection sel{pd.product_kind, nullptr, nullptr, n};
-                const uint64_t lmask = side ? mask_of(other) : cmask, rmask = side ? cmask : mask_of(other);
-                nd.n_comp_muls = comp_mul_count(n, iter_contribs(mask_of(g), sel, lmask, rmask), pd.product_kind == GAAST_PROD_REGRESSIVE);
+                const Selection sel{base, nullptr, nullptr, n};
+                const bool regressive = base == GAAST_PROD_REGRESSIVE;
+                if (!adj) {
+                    nd.child0 = g;
+                    nd.child1 = other;
+                    nd.product_kind = pd.product_kind + (side ? GAAST_PROD_ADJ_RIGHT : GAAST_PROD_ADJ_LEFT);
+                    const uint64_t lmask = side ? mask_of(other) : cmask, rmask = side ? cmask : mask_of(other);
+                    nd.n_comp_muls = comp_mul_count(n, iter_contribs(mask_of(g), sel, lmask, rmask), regressive);
+                } else if (side == 0) {
+                    // a compact adjoint node P = ADJ(g0, x) is <h, P> = T(g0, h, x) (ADJ_LEFT) or T(g0, x, h) (ADJ_RIGHT) with the
+                    // trilinear form T(g, a, b) = <g, a o b> of the forward kind and h = g here, the cotangent of P.  For g0, the
+                    // forward product of the other two in their forward order
+                    nd.child0 = adj == GAAST_PROD_ADJ_LEFT ? g : other;
+                    nd.child1 = adj == GAAST_PROD_ADJ_LEFT ? other : g;
+                    nd.product_kind = base;
+                    nd.n_comp_muls = comp_mul_count(n, iter_contribs(cmask, sel, mask_of(nd.child0), mask_of(nd.child1)), regressive);
+                } else {
+                    // for x, the adjoint of the other side over (g0, h)
+                    nd.child0 = other;
+                    nd.child1 = g;
+                    nd.product_kind = base + (adj == GAAST_PROD_ADJ_LEFT ? GAAST_PROD_ADJ_RIGHT : GAAST_PROD_ADJ_LEFT);
+                    const uint64_t lmask = adj == GAAST_PROD_ADJ_LEFT ? mask_of(g) : cmask, rmask = adj == GAAST_PROD_ADJ_LEFT ? cmask : mask_of(g);
+                    nd.n_comp_muls = comp_mul_count(n, iter_contribs(mask_of(other), sel, lmask, rmask), regressive);
+                }
                 cot[size_t(c)].push_back(Term{add(nd), 0, ~0ULL});
             }
         }
@@ -401,7 +437,7 @@ struct Builder {
         for (int i = 0; i < nf; ++i) {
             const gaast_node_desc& nd = d.nodes[i];
             if (nd.opcode == GAAST_OP_INPUT) dep[size_t(i)] = nd.input_slot == wrt;
-            else dep[size_t(i)] = dep[size_t(nd.child0)] || (nd.child1 >= 0 && (nd.opcode == GAAST_OP_ADD || nd.opcode == GAAST_OP_PRODUCT) && dep[size_t(nd.child1)]);
+            else dep[size_t(i)] = dep[size_t(nd.child0)] || (nd.child1 >= 0 && has_two_children(nd.opcode) && dep[size_t(nd.child1)]);
         }
         std::vector<std::vector<Term>> cot(static_cast<size_t>(nf));
         std::vector<int> outs;
@@ -448,7 +484,10 @@ struct Builder {
                 }
                 case EV_SCALAR: scalar_adjoint(s, e, terms); break;
                 case EV_OPAQUE:   // a node whose operand has a buffer of its own
-                    if (x.opcode == GAAST_OP_DUAL || x.opcode == GAAST_OP_UNDUAL) dual_adjoint(e.node, terms, cot);
+                    if (const char* name = adjoint_op_name(x.opcode)) {   // its second derivative needs a Frechet-derivative kernel
+                        if (dep[size_t(e.node)])
+                            throw VjpError{GAAST_ERR_UNIMPLEMENTED, std::string("second-order reverse mode through ") + name + " is not implemented"};
+                    } else if (x.opcode == GAAST_OP_DUAL || x.opcode == GAAST_OP_UNDUAL) dual_adjoint(e.node, terms, cot);
                     else if (x.opcode == GAAST_OP_INV) inv_adjoint(e.node, terms, cot);
                     else if (x.opcode == GAAST_OP_GEXP) gexp_adjoint(e.node, terms, cot);
                     else if (x.opcode == GAAST_OP_GSQRT) gsqrt_adjoint(e.node, terms, cot);
@@ -505,12 +544,16 @@ extern "C" int gaast_program_vjp(const gaast_program_desc* desc, int32_t wrt_slo
     }
     for (int i = 0; i < d.n_nodes; ++i) {
         const gaast_node_desc& nd = d.nodes[i];
-        const bool two = nd.opcode == GAAST_OP_ADD || nd.opcode == GAAST_OP_PRODUCT;
+        const bool two = has_two_children(nd.opcode);
         const bool ok = nd.opcode == GAAST_OP_INPUT ? (nd.input_slot >= 0 && nd.input_slot < d.n_inputs)
-                        : (nd.opcode > GAAST_OP_INPUT && (nd.opcode <= GAAST_OP_SSQRT || nd.opcode == GAAST_OP_DUAL || nd.opcode == GAAST_OP_UNDUAL || nd.opcode == GAAST_OP_INV || nd.opcode == GAAST_OP_GEXP || nd.opcode == GAAST_OP_GSQRT || nd.opcode == GAAST_OP_GLOG) &&
+                        : (nd.opcode > GAAST_OP_INPUT && nd.opcode <= GAAST_OP_GLOG_ADJ &&
                            nd.child0 >= 0 && nd.child0 < i &&
                            (!two || (nd.child1 >= 0 && nd.child1 < i)));
-        if (!ok || (nd.opcode == GAAST_OP_PRODUCT && nd.product_kind >= GAAST_PROD_ADJ_LEFT)) {
+        // a compact adjoint product (a VJP program differentiates again): GAAST_PROD_ADJ_LEFT or GAAST_PROD_ADJ_RIGHT over a kind 0..5
+        const int adj = nd.product_kind & ~7, base = nd.product_kind & 7;
+        const bool kind_ok = nd.opcode != GAAST_OP_PRODUCT || nd.product_kind < GAAST_PROD_ADJ_LEFT ||
+                             ((adj == GAAST_PROD_ADJ_LEFT || adj == GAAST_PROD_ADJ_RIGHT) && base <= GAAST_PROD_REGRESSIVE);
+        if (!ok || !kind_ok) {
             gaast_set_expr_error("malformed program description (node " + std::to_string(i) + ")");
             return GAAST_ERR_INVALID_PROGRAM;
         }

@@ -183,7 +183,27 @@ void gaast_program_image_free(gaast_program_image_t img);
  * a GAAST_OP_GLOG node one GAAST_OP_GLOG_ADJ node.
  * A program specialised for the orthogonal basis of a Gram metric differentiates like any other: its VJP program is created with the
  * same basis (gaast_hip_program_create_vjp_in_basis, gaast_hip.h), the cotangent being one more batched input.
+ * Closure: desc may itself be a program this function returned, to any depth (second-order reverse mode, Hessian-vector products,
+ * forward mode as the VJP of a VJP with respect to its cotangent).  Every non-const slot of such a program is a valid wrt_slot, its
+ * cotangent slot included; the const 1 of the program differentiated stays where it is, the new cotangent is appended at its
+ * n_inputs and a const 1 of the new program after that.  The image returned for a forward program is not affected by any of this.
+ * A compact adjoint product (product_kind = base + GAAST_PROD_ADJ_LEFT or base + GAAST_PROD_ADJ_RIGHT, base = 0..5; any other kind
+ * above 7 is GAAST_ERR_INVALID_PROGRAM) is an ordinary product of two operand buffers.  With T(g, a, b) = <g, a o b> the trilinear
+ * form of the forward kind and h the cotangent of the node, restricted to the node's grades:
+ *     node P                                    operand      its cotangent
+ *     ADJ_LEFT + base, children (g, b),         child0 = g   forward base, children (h, b), mask of g
+ *       mask of a                               child1 = b   ADJ_RIGHT + base, children (g, h), mask of b
+ *     ADJ_RIGHT + base, children (g, a),        child0 = g   forward base, children (a, h), mask of g  (note the order)
+ *       mask of b                               child1 = a   ADJ_LEFT + base, children (g, h), mask of a
+ * so a product differentiated any number of times stays within {base, ADJ_LEFT + base, ADJ_RIGHT + base} of one kind, n_comp_muls
+ * counted from the three grade sets as at first order; GAAST_PROD_REGRESSIVE keeps its kind in every form (a Gram basis applies its
+ * orientation sign once per node), and an explicit list stays explicit.  GAAST_OP_INV needs nothing else: its adjoint is a
+ * GAAST_OP_NEG, one more GAAST_OP_INV and two geometric adjoint products.
+ * The adjoint op nodes GAAST_OP_EXP_ADJ, GAAST_OP_LOG_ADJ, GAAST_OP_GEXP_ADJ, GAAST_OP_GSQRT_ADJ and GAAST_OP_GLOG_ADJ are valid nodes
+ * with two children; off the path to wrt_slot they are carried along untouched.
  * Errors: GAAST_ERR_INVALID_ARGUMENT for a wrt_slot out of range or const, or n_inputs + 1 > GAAST_MAX_INPUTS;
+ * GAAST_ERR_UNIMPLEMENTED for one of the five adjoint op nodes on the path to wrt_slot, through either child (the message names the
+ * op: the second derivative of these matrix functions needs Frechet-derivative kernels the library does not have);
  * GAAST_ERR_UNIMPLEMENTED for GAAST_FLAG_SPINOR_GEMM, and for exp / log on the path to wrt_slot unless desc->flags holds both
  * GAAST_FLAG_EXP_LOG and GAAST_FLAG_EXP_LOG_GRAD: then the operand's cotangent is a GAAST_OP_EXP_ADJ / GAAST_OP_LOG_ADJ node
  * (gaast_hip.h) over the cotangent of the exp / log node's buffer and the forward operand (exp of a bare scalar, grade set {0},

@@ -580,14 +580,20 @@ int gaast_hip_eval_gather(gaast_hip_program_t prog, const gaast_hip_mv_t *inputs
  * gradient rows of input `wrt_slot` (its grade mask and storage dimension).  Batch-1 inputs are shared as usual; the gradient of a
  * shared input is then one row per item, to be summed with gaast_hip_mv_sum_rows.  Programs created with
  * GAAST_FLAG_SPINOR_GEMM have no VJP: GAAST_ERR_UNIMPLEMENTED; so has an exp / log on the path to `wrt_slot` unless desc->flags holds
- * GAAST_FLAG_EXP_LOG | GAAST_FLAG_EXP_LOG_GRAD.  A program of gaast_hip_program_create_in_basis has the VJP below. */
+ * GAAST_FLAG_EXP_LOG | GAAST_FLAG_EXP_LOG_GRAD.  A program of gaast_hip_program_create_in_basis has the VJP below.
+ * desc may itself be a VJP program (read from the image of gaast_program_vjp): gaast_program_vjp is closed under itself, so this
+ * creates second- and higher-order programs, the cotangent of desc being one of its slots and wrt_slot any non-const one.  Adjoint
+ * products of dense geometric products run on the forward's dense kernels at every order.  One of the adjoint op nodes
+ * (GAAST_OP_EXP_ADJ, LOG_ADJ, GEXP_ADJ, GSQRT_ADJ, GLOG_ADJ) on the path to wrt_slot: GAAST_ERR_UNIMPLEMENTED. */
 int gaast_hip_program_create_vjp(const gaast_program_desc *desc, int32_t wrt_slot, gaast_hip_program_t *out);
 /* gaast_program_vjp followed by gaast_hip_program_create_in_basis: the VJP of a program in a non-diagonal metric.  With the orthogonal
  * Q of the basis change, y_e = C(Q) F(C(Q^T) x_e) and every C_k(Q) is orthogonal, so the VJP of the in-basis program is the in-basis
  * version of the VJP program with the same Q: the cotangent (slot desc->n_inputs, an ordinary batched input of dimension n) goes
  * through C_k(Q^T) like every other input, the gradient comes back through C_k(Q).  desc is the FORWARD program specialised for
  * diag(L), its constant rows in the caller's basis exactly as gaast_hip_program_create_in_basis takes them.  Q == I exactly: the very
- * program (plan, launches, bits) of gaast_hip_program_create_vjp.  A wrt_slot whose rows hold only grade 0 gets no result move.  The
+ * program (plan, launches, bits) of gaast_hip_program_create_vjp.  desc may also be a VJP program of such a forward program, with the
+ * same Q: every level of a higher-order program is the in-basis version of the plain one, all rows in the caller's basis.
+ * A wrt_slot whose rows hold only grade 0 gets no result move.  The
  * exp / log adjoint nodes work unchanged inside f (sigma_i is the metric of f there).  Errors: those of gaast_program_vjp
  * (GAAST_FLAG_SPINOR_GEMM stays GAAST_ERR_UNIMPLEMENTED) and of gaast_hip_program_create_in_basis; *out is untouched on failure. */
 int gaast_hip_program_create_vjp_in_basis(const gaast_program_desc *desc, const double *basis, int32_t wrt_slot,
