@@ -7,7 +7,9 @@ of its per-item gradients (gaast_hip_mv_sum_rows).  Both directions run on torch
 
 Backward is differentiable to any order (create_graph=True: Hessian-vector products, gradient penalties): each gradient is a second
 autograd.Function over the Vjp object, whose own backward evaluates Vjp.vjp(slot), built when first asked for.  Programs that hold
-exp / log / gexp / gsqrt / glog on the path differentiate once; asking for their second derivative raises GaastError UNIMPLEMENTED.
+exp / log / gexp / gsqrt / glog on the path differentiate once; asking for their second derivative raises GaastError UNIMPLEMENTED --
+except through gexp on a spec built with specialize(..., flags=FLAG_GEXP_GRAD2): there second order (and forward mode, spec.jvp)
+works, and it is the third order that is refused.  gsqrt / glog / exp / log are unchanged by that flag.
 """
 from __future__ import annotations
 

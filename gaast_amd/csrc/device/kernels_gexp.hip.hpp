@@ -26,6 +26,24 @@
 //                  with ADJL(g, Z)[a] = sum_b coeff(a, b) Z[b] g[a xor b], ADJR(g, X)[b] = sum_a coeff(a, b) X[a] g[a xor b] (the sign
 //                  words of both are built on the host; the metric factor of either is weight[S[a] & S[b]]).  No domain check: a
 //                  domain-error item scales by NaN, so every component of its cotangent is NaN by arithmetic.
+//   k_mv_gexp_jvp<T, N>   res += the Frechet derivative of exp at A in direction h (GAAST_OP_GEXP_JVP; Step::GEXP_JVP)
+//   k_mv_gexp_adj2<T, N>  res += the gradient in A of <g, that derivative> (GAAST_OP_GEXP_ADJ2; Step::GEXP_ADJ2)
+// The second-order pair, in k_mv_gexp_adj's layout, s from A alone, h_s = 2^-s h, everything gathered from LDS:
+//   k_mv_gexp_jvp  a pure forward with no stored history.  A_s and h_s stay in LDS; (q, qd) ping-pong between two LDS rows each
+//                  through the Horner steps qd_(k-1) = (h_s q_k + A_s qd_k) / k (three products with the value's; qd_M = 0: two
+//                  at k = M), then (Y, Yd) through the squarings Yd_(i+1) = Yd_i Y_i + Y_i Yd_i (three products).
+//                  Static LDS: 6 rows of 256 T (A_s, h_s; q, qd twice each) + the 128 weights + 4 ints = (6 * 256 + 128) sizeof(T) + 16.
+//   k_mv_gexp_adj2 recomputes that forward pair keeping q_0 ... q_M and qd_0 ... qd_M of its component in registers (2 (M + 1)
+//                  values, static indices) and Y_0 ... Y_s, Yd_0 ... Yd_s in LDS (2 x 13 rows), then sweeps with the cotangent pair
+//                  (G of the values, Gd of the tangents; Gd = g, G = 0):
+//                      G <- ((ADJL(G, Y_i) + ADJR(G, Y_i)) + ADJR(Gd, Yd_i)) + ADJL(Gd, Yd_i);  Gd <- ADJL(Gd, Y_i) + ADJR(Gd, Y_i)
+//                      for k = 1 ... M:  w = G / k, wd = Gd / k;  dA_s += ADJL(w, q_k) + ADJL(wd, qd_k);
+//                                        G <- ADJR(w, A_s) + ADJR(wd, h_s);  Gd <- ADJR(wd, A_s);             dA = 2^-s dA_s
+//                  six adjoint rows per squaring, five per Horner step.
+//                  Static LDS: 36 rows of 256 T (A_s, h_s; q, qd, G, Gd twice each; 13 Y, 13 Yd) + the 128 weights + 4 ints
+//                  = (36 * 256 + 128) sizeof(T) + 16: 37392 bytes in f32, 74768 in f64 -- above 64 KiB, which gfx950 allows a
+//                  workgroup (160 KiB per CU), and two workgroups still share a CU.
+//                  Neither kernel checks a domain or counts: a domain-error item scales A and h by NaN.
 // Offsets in int64_t; any row stride (0: one operand shared by every item), padding or alignment takes the same scalar accesses.
 #pragma once
 #include "kernels_inverse.hip.hpp"
@@ -285,6 +303,240 @@ __global__ __launch_bounds__(256) void k_mv_gexp_adj(const GexpArgs<T> p) {
                 cur ^= 1;
                 grow[cur][tid] = gn / T(k + 1);
                 qrow[(k + 1) & 1][tid] = q[k + 1];
+                __syncthreads();
+            }
+        }
+        if (live && res_off >= 0) {
+            T* d = p.res + item * p.res_stride + res_off;
+            *d = (p.beta ? *d : T(0)) + da * scale;
+        }
+    }
+}
+
+// ---- second order: GAAST_OP_GEXP_JVP / GAAST_OP_GEXP_ADJ2 ------------------------------------------------------------------------
+template <typename T>
+struct Gexp2Args {
+    T* res;
+    const T* in;              // the forward operand A
+    const T* cot;             // g (k_mv_gexp_adj2)
+    const T* tan;             // h
+    int64_t res_stride, in_stride, cot_stride, tan_stride, batch;
+    const int32_t* a_off;     // [N] operand offset of blade j, -1 = absent
+    const int32_t* res_off;   // [N] result offset of blade j, -1 = not produced
+    const int32_t* g_off;     // [N] offset of blade j in g's row, -1 = absent (k_mv_gexp_adj2)
+    const int32_t* h_off;     // [N] offset of blade j in h's row, -1 = absent
+    const uint64_t* neg;      // [N] the sign words of L
+    const uint64_t* neg_l;    // [N] ADJL's (k_mv_gexp_adj2)
+    const uint64_t* neg_r;    // [N] ADJR's (k_mv_gexp_adj2)
+    const T* weight;          // [1 << n] metric factor by shared-vector set
+    uint64_t a_neg;           // bit j: operand component j is negated
+    T wmax;
+    int n;
+    int even;
+    int beta;                 // 0: the zero fill of a fresh result is folded in
+};
+
+template <typename T, int N>
+__global__ __launch_bounds__(256) void k_mv_gexp_jvp(const Gexp2Args<T> p) {
+    using namespace gexp_detail;
+    static_assert(N == 2 || N == 4 || N == 8 || N == 16 || N == 32 || N == 64, "one item per N lanes of a wave");
+    constexpr int IPB = 256 / N;
+    constexpr int M = taylor_degree<T>();
+    __shared__ T arow[256];                          // A_s
+    __shared__ T hrow[256];                          // h_s
+    __shared__ T qrow[2][256];                       // q of the Horner steps, then Y of the squarings
+    __shared__ T drow[2][256];                       // qd, then Yd
+    __shared__ T weight[128];
+    __shared__ int wave_s[4];
+    const int tid = int(threadIdx.x);
+    const int r = tid & (N - 1), g = tid / N;
+    if (tid < (1 << p.n)) weight[tid] = p.weight[tid];
+    const int32_t a_off = p.a_off[r], res_off = p.res_off[r], h_off = p.h_off[r];
+    const bool a_neg = ((p.a_neg >> r) & 1ULL) != 0;
+    const uint64_t neg = p.neg[r];
+    const uint32_t e = uint32_t(p.even);
+    const T e0 = r == 0 ? T(1) : T(0);
+    const int it0 = g * N;
+    for (int64_t base = int64_t(blockIdx.x) * IPB; base < p.batch; base += int64_t(gridDim.x) * IPB) {
+        uint32_t ur = uint32_t(r);                   // (opaque per pass, as in k_mv_gexp_adj)
+        asm volatile("" : "+v"(ur));
+        const int64_t item = base + g;
+        const bool live = item < p.batch;
+        T v = T(0), hv = T(0);
+        if (live && a_off >= 0) v = p.in[item * p.in_stride + a_off];
+        if (live && h_off >= 0) hv = p.tan[item * p.tan_stride + h_off];
+        if (a_neg) v = -v;
+        bool bad;
+        const int s = squarings_of<T, N>(v, p.wmax, &bad);
+        const T scale = bad ? qnan(T(0)) : ldexp_m(T(1), -s);
+        const int ws = wave_max(s);
+        __syncthreads();                             // (the previous group's rows have been read; the first pass: `weight` is written)
+        arow[tid] = v * scale;
+        hrow[tid] = hv * scale;
+        qrow[0][tid] = e0;                           // q_M
+        drow[0][tid] = T(0);                         // qd_M
+        if ((tid & 63) == 0) wave_s[tid >> 6] = ws;
+        __syncthreads();
+        T y = e0, yd = T(0);
+#pragma unroll
+        for (int k = M; k >= 1; --k) {               // q_(k-1) = e_0 + (A_s q_k) / k;  qd_(k-1) = (h_s q_k + A_s qd_k) / k
+            const T* const q = qrow[(M - k) & 1] + it0;
+            const T* const qd = drow[(M - k) & 1] + it0;
+            const T aq = product_row<T, N>(arow + it0, q, weight, ur, neg, e);
+            const T hq = product_row<T, N>(hrow + it0, q, weight, ur, neg, e);
+            const T ad = k < M ? product_row<T, N>(arow + it0, qd, weight, ur, neg, e) : T(0);   // (qd_M = 0)
+            y = e0 + aq / T(k);
+            yd = (hq + ad) / T(k);
+            qrow[(M - k + 1) & 1][tid] = y;
+            drow[(M - k + 1) & 1][tid] = yd;
+            __syncthreads();
+        }
+        int cur = M & 1;                             // (Y_0, Yd_0) sit in qrow[cur], drow[cur]
+        const int smax = max(max(wave_s[0], wave_s[1]), max(wave_s[2], wave_s[3]));
+        for (int i = 0; i < smax; ++i) {             // Yd_(i+1) = Yd_i Y_i + Y_i Yd_i,  Y_(i+1) = Y_i Y_i  while i < s
+            const T* const Y = qrow[cur] + it0;
+            const T* const Yd = drow[cur] + it0;
+            const T sq = product_row<T, N>(Y, Y, weight, ur, neg, e);
+            const T dl = product_row<T, N>(Yd, Y, weight, ur, neg, e);
+            const T dr = product_row<T, N>(Y, Yd, weight, ur, neg, e);
+            y = i < s ? sq : y;
+            yd = i < s ? dl + dr : yd;
+            cur ^= 1;
+            qrow[cur][tid] = y;
+            drow[cur][tid] = yd;
+            __syncthreads();
+        }
+        if (live && res_off >= 0) {
+            T* d = p.res + item * p.res_stride + res_off;
+            *d = (p.beta ? *d : T(0)) + yd;
+        }
+    }
+}
+
+template <typename T, int N>
+__global__ __launch_bounds__(256) void k_mv_gexp_adj2(const Gexp2Args<T> p) {
+    using namespace gexp_detail;
+    static_assert(N == 2 || N == 4 || N == 8 || N == 16 || N == 32 || N == 64, "one item per N lanes of a wave");
+    constexpr int IPB = 256 / N;
+    constexpr int M = taylor_degree<T>();
+    __shared__ T arow[256];                          // A_s
+    __shared__ T hrow[256];                          // h_s
+    __shared__ T qrow[2][256];                       // the forward's q, then q_k of the sweep
+    __shared__ T drow[2][256];                       // the forward's qd, then qd_k of the sweep
+    __shared__ T grow[2][256];                       // G (w = G / k in the Horner part of the sweep)
+    __shared__ T gdrow[2][256];                      // Gd (wd)
+    __shared__ T yrow[kMaxSquarings + 1][256];       // Y_0 ... Y_s
+    __shared__ T ydrow[kMaxSquarings + 1][256];      // Yd_0 ... Yd_s
+    __shared__ T weight[128];
+    __shared__ int wave_s[4];
+    const int tid = int(threadIdx.x);
+    const int r = tid & (N - 1), g = tid / N;
+    if (tid < (1 << p.n)) weight[tid] = p.weight[tid];
+    const int32_t a_off = p.a_off[r], res_off = p.res_off[r], g_off = p.g_off[r], h_off = p.h_off[r];
+    const bool a_neg = ((p.a_neg >> r) & 1ULL) != 0;
+    const uint64_t neg = p.neg[r], neg_l = p.neg_l[r], neg_r = p.neg_r[r];
+    const uint32_t e = uint32_t(p.even);
+    const T e0 = r == 0 ? T(1) : T(0);
+    const int it0 = g * N;
+    for (int64_t base = int64_t(blockIdx.x) * IPB; base < p.batch; base += int64_t(gridDim.x) * IPB) {
+        uint32_t ur = uint32_t(r);                   // (opaque per pass, as in k_mv_gexp_adj)
+        asm volatile("" : "+v"(ur));
+        const int64_t item = base + g;
+        const bool live = item < p.batch;
+        T v = T(0), gv = T(0), hv = T(0);
+        if (live && a_off >= 0) v = p.in[item * p.in_stride + a_off];
+        if (live && g_off >= 0) gv = p.cot[item * p.cot_stride + g_off];
+        if (live && h_off >= 0) hv = p.tan[item * p.tan_stride + h_off];
+        if (a_neg) v = -v;
+        bool bad;
+        const int s = squarings_of<T, N>(v, p.wmax, &bad);
+        const T scale = bad ? qnan(T(0)) : ldexp_m(T(1), -s);
+        const int ws = wave_max(s);
+        __syncthreads();                             // (the previous group's rows have been read; the first pass: `weight` is written)
+        arow[tid] = v * scale;
+        hrow[tid] = hv * scale;
+        qrow[0][tid] = e0;                           // q_M
+        drow[0][tid] = T(0);                         // qd_M
+        if ((tid & 63) == 0) wave_s[tid >> 6] = ws;
+        __syncthreads();
+        // the forward pair again, keeping every q_k and qd_k of my component
+        T q[M + 1], qd[M + 1];
+        q[M] = e0;
+        qd[M] = T(0);
+#pragma unroll
+        for (int k = M; k >= 1; --k) {
+            const T* const qk = qrow[(M - k) & 1] + it0;
+            const T aq = product_row<T, N>(arow + it0, qk, weight, ur, neg, e);
+            const T hq = product_row<T, N>(hrow + it0, qk, weight, ur, neg, e);
+            const T ad = k < M ? product_row<T, N>(arow + it0, drow[(M - k) & 1] + it0, weight, ur, neg, e) : T(0);   // (qd_M = 0)
+            q[k - 1] = e0 + aq / T(k);
+            qd[k - 1] = (hq + ad) / T(k);
+            qrow[(M - k + 1) & 1][tid] = q[k - 1];
+            drow[(M - k + 1) & 1][tid] = qd[k - 1];
+            if (k == 1) {
+                yrow[0][tid] = q[0];                 // Y_0, Yd_0
+                ydrow[0][tid] = qd[0];
+                grow[0][tid] = T(0);                 // the sweep starts from G = 0, Gd = g
+                gdrow[0][tid] = gv;
+            }
+            __syncthreads();
+        }
+        const int smax = max(max(wave_s[0], wave_s[1]), max(wave_s[2], wave_s[3]));
+        T y = q[0], yd = qd[0];
+        for (int i = 0; i < smax; ++i) {             // (smax <= 12: row i + 1 exists)
+            const T* const Y = yrow[i] + it0;
+            const T* const Yd = ydrow[i] + it0;
+            const T sq = product_row<T, N>(Y, Y, weight, ur, neg, e);
+            const T dl = product_row<T, N>(Yd, Y, weight, ur, neg, e);
+            const T dr = product_row<T, N>(Y, Yd, weight, ur, neg, e);
+            y = i < s ? sq : y;
+            yd = i < s ? dl + dr : yd;
+            yrow[i + 1][tid] = y;
+            ydrow[i + 1][tid] = yd;
+            __syncthreads();
+        }
+        // the sweep.  Squarings, i = s-1 ... 0, both members from the old pair
+        int cur = 0;
+        T gc = T(0), gdc = gv;
+        for (int i = smax - 1; i >= 0; --i) {
+            const T* const Y = yrow[i] + it0;
+            const T* const Yd = ydrow[i] + it0;
+            const T* const G = grow[cur] + it0;
+            const T* const Gd = gdrow[cur] + it0;
+            const T t1 = adjoint_row<T, N>(Y, G, weight, ur, neg_l, e);
+            const T t2 = adjoint_row<T, N>(Y, G, weight, ur, neg_r, e);
+            const T t3 = adjoint_row<T, N>(Yd, Gd, weight, ur, neg_r, e);
+            const T t4 = adjoint_row<T, N>(Yd, Gd, weight, ur, neg_l, e);
+            const T u1 = adjoint_row<T, N>(Y, Gd, weight, ur, neg_l, e);
+            const T u2 = adjoint_row<T, N>(Y, Gd, weight, ur, neg_r, e);
+            gc = i < s ? ((t1 + t2) + t3) + t4 : gc;
+            gdc = i < s ? u1 + u2 : gdc;
+            cur ^= 1;
+            grow[cur][tid] = gc;
+            gdrow[cur][tid] = gdc;
+            __syncthreads();
+        }
+        // Horner: grow[cur] / gdrow[cur] hold w / wd (k = 1: G / Gd themselves), qrow[k & 1] / drow[k & 1] hold q_k / qd_k
+        qrow[1][tid] = q[1];
+        drow[1][tid] = qd[1];
+        __syncthreads();
+        T da = T(0);
+#pragma unroll
+        for (int k = 1; k <= M; ++k) {
+            const T* const W = grow[cur] + it0;
+            const T* const Wd = gdrow[cur] + it0;
+            const T l1 = adjoint_row<T, N>(qrow[k & 1] + it0, W, weight, ur, neg_l, e);
+            const T l2 = adjoint_row<T, N>(drow[k & 1] + it0, Wd, weight, ur, neg_l, e);
+            da = da + (l1 + l2);
+            if (k < M) {
+                const T r1 = adjoint_row<T, N>(arow + it0, W, weight, ur, neg_r, e);
+                const T r2 = adjoint_row<T, N>(hrow + it0, Wd, weight, ur, neg_r, e);
+                const T r3 = adjoint_row<T, N>(arow + it0, Wd, weight, ur, neg_r, e);
+                cur ^= 1;
+                grow[cur][tid] = (r1 + r2) / T(k + 1);
+                gdrow[cur][tid] = r3 / T(k + 1);
+                qrow[(k + 1) & 1][tid] = q[k + 1];
+                drow[(k + 1) & 1][tid] = qd[k + 1];
                 __syncthreads();
             }
         }

@@ -176,6 +176,8 @@ struct Lowering : LowerState {
         case GAAST_OP_INV: lower_inverse(res, id); return;
         case GAAST_OP_GEXP: lower_gexp(res, id, Step::GEXP, "gexp", "the general exponential", "general_exponential"); return;
         case GAAST_OP_GEXP_ADJ: lower_gexp_adj(res, id, Step::GEXP_ADJ, "gexp", "the general exponential's adjoint", "general_exponential_adjoint"); return;
+        case GAAST_OP_GEXP_JVP:
+        case GAAST_OP_GEXP_ADJ2: lower_gexp2(res, id); return;
         case GAAST_OP_GSQRT: lower_gexp(res, id, Step::GSQRT, "gsqrt", "the general square root", "general_sqrt"); return;
         case GAAST_OP_GSQRT_ADJ: lower_gexp_adj(res, id, Step::GSQRT_ADJ, "gsqrt", "the general square root's adjoint", "general_sqrt_adjoint"); return;
         case GAAST_OP_GLOG: lower_gexp(res, id, Step::GLOG, "glog", "the general logarithm", "general_log"); return;
@@ -238,7 +240,7 @@ struct Lowering : LowerState {
         touch(res);
     }
 
-    // The tables of a step over the blade set S (Step::Inverse: INVERSE, GEXP, GEXP_ADJ, GSQRT, GSQRT_ADJ, GLOG, GLOG_ADJ): S itself, where operand row `a` (grades
+    // The tables of a step over the blade set S (Step::Inverse: INVERSE, GEXP, GEXP_ADJ, GEXP_JVP, GEXP_ADJ2, GSQRT, GSQRT_ADJ, GLOG, GLOG_ADJ): S itself, where operand row `a` (grades
     // `amask`, those of `flip` negated) and result row `res` (grades `produce`) hold its blades, the reordering signs and the metric
     // factors of the left-multiplication matrix.  false: failed (a produced grade is absent from res)
     bool blade_set_tables(Step::Inverse& q, bool even, BufRef a, uint64_t amask, uint64_t flip, BufRef res, uint64_t produce) {
@@ -327,6 +329,29 @@ struct Lowering : LowerState {
         touch(res);
     }
 
+    // [N] where row layout `l` holds the blades of the set; -1: absent (a cotangent or tangent row: read as 0)
+    std::vector<int32_t> blade_offsets(const Step::Inverse& q, const Layout& l) const {
+        std::vector<int32_t> off;
+        for (int j = 0; j < q.N; ++j) {
+            const uint32_t b = q.blade[size_t(j)];
+            const int k = __builtin_popcount(b);
+            const bool held = ((l.mask >> k) & 1ULL) && int64_t(bt.index_of[b]) < l.grade_len(k);
+            off.push_back(held ? int32_t(l.offset(k) + bt.index_of[b]) : -1);
+        }
+        return off;
+    }
+    // the sign words of ADJL and ADJR (Step::Inverse: adj_neg_l, adj_neg_r) from those of L
+    static void adjoint_sign_words(Step::Inverse& q) {
+        q.adj_neg_l.assign(size_t(q.N), 0);
+        q.adj_neg_r.assign(size_t(q.N), 0);
+        for (int j = 0; j < q.N; ++j)
+            for (int t = 0; t < q.N; ++t)
+                if ((q.neg[size_t(j ^ t)] >> t) & 1ULL) {   // the sign of L[j xor t][t]: coeff(a = j, b = t)
+                    q.adj_neg_l[size_t(j)] |= uint64_t(1) << t;
+                    q.adj_neg_r[size_t(t)] |= uint64_t(1) << j;
+                }
+    }
+
     // Reverse mode of the general exponential (GAAST_OP_GEXP_ADJ, gaast_hip.h): res += the cotangent of the operand, in the operand's
     // grades.  child1, the forward operand, is read like the forward's; child0, the cotangent, is cached like a product operand.
     // Reverse mode of the general square root (GAAST_OP_GSQRT_ADJ; Step::GSQRT_ADJ, k_mv_gsqrt_adj) has the same operands and the same
@@ -363,19 +388,8 @@ struct Lowering : LowerState {
         if (!blade_set_tables(q, even, a, amask, flip, res, nd.minimal_grade_mask & amask)) return;
         q.wmax = 0.0;
         for (double w : q.weight) q.wmax = std::max(q.wmax, std::fabs(w));
-        q.adj_neg_l.assign(size_t(q.N), 0);
-        q.adj_neg_r.assign(size_t(q.N), 0);
-        for (int j = 0; j < q.N; ++j) {
-            const uint32_t b = q.blade[size_t(j)];
-            const int k = __builtin_popcount(b);
-            const bool held = ((lg.mask >> k) & 1ULL) && int64_t(bt.index_of[b]) < lg.grade_len(k);
-            q.g_off.push_back(held ? int32_t(lg.offset(k) + bt.index_of[b]) : -1);
-            for (int t = 0; t < q.N; ++t)
-                if ((q.neg[size_t(j ^ t)] >> t) & 1ULL) {   // the sign of L[j xor t][t]: coeff(a = j, b = t)
-                    q.adj_neg_l[size_t(j)] |= uint64_t(1) << t;
-                    q.adj_neg_r[size_t(t)] |= uint64_t(1) << j;
-                }
-        }
+        q.g_off = blade_offsets(q, lg);
+        adjoint_sign_words(q);
         if (!q.n_out) return;
         const auto fr = fresh.find(key(res));
         const bool covers = fr != fresh.end() && !(plan.flags & GAAST_FLAG_NO_FUSION) && int64_t(q.n_out) == lr.row_len;
@@ -383,6 +397,67 @@ struct Lowering : LowerState {
         Step& s = emit(kind, res, std::string(label) + "[" + std::to_string(q.N) + (even ? " even" : "") + " blades, " + std::to_string(q.n_out) + " produced, n=" + std::to_string(n) + "]");
         s.a = a;
         s.b = cot;
+        s.canon_a = canon;
+        s.beta = covers ? 0 : 1;
+        s.inv = std::move(q);
+        touch(res);
+    }
+
+    // The second-order steps of the general exponential (GAAST_OP_GEXP_JVP / GAAST_OP_GEXP_ADJ2, gaast_hip.h; Step::GEXP_JVP /
+    // Step::GEXP_ADJ2, k_mv_gexp_jvp / k_mv_gexp_adj2), always launches of their own.  The forward operand (JVP: child1; ADJ2: the third
+    // child, in input_slot) is read like GEXP_ADJ's; the tangent h (JVP: child0; ADJ2: child1) and ADJ2's g (child0) are cached like
+    // product operands.  JVP: res += the wanted grades of the blade set; ADJ2: res += the operand's grades.
+    void lower_gexp2(BufRef res, int id) {
+        const gaast_node_desc& nd = node(id);
+        const bool adj2 = nd.opcode == GAAST_OP_GEXP_ADJ2;
+        const int a_id = adj2 ? nd.input_slot : nd.child1, h_id = adj2 ? nd.child1 : nd.child0, g_id = adj2 ? nd.child0 : -1;
+        const std::string op = adj2 ? "gexp second-order adjoint" : "gexp tangent";
+        const int n = d.vec_space_dim;
+        if (node(a_id).vec_space_dim != n || nd.vec_space_dim != n || node(h_id).vec_space_dim != n || (adj2 && node(g_id).vec_space_dim != n)) {
+            fail(GAAST_ERR_INVALID_PROGRAM, op + " operand lives in another vector space than the algebra");
+            return;
+        }
+        const uint64_t amask = node(a_id).minimal_grade_mask & ((uint64_t(2) << n) - 1);
+        const bool even = !(amask & 0xAAAAAAAAAAAAAAAAULL);
+        if (blade_set_unsupported(adj2 ? "the general exponential's second-order adjoint" : "the general exponential's tangent", even)) return;
+        const uint64_t smask = gs_inverse(amask, n);
+        if (node(h_id).minimal_grade_mask & ~amask) {
+            fail(GAAST_ERR_INVALID_PROGRAM, op + ": the tangent holds grades the operand does not hold");
+            return;
+        }
+        if (adj2 ? (node(g_id).minimal_grade_mask & ~smask) != 0 : (nd.minimal_grade_mask & ~smask) != 0) {
+            fail(GAAST_ERR_INVALID_PROGRAM, op + (adj2 ? ": the cotangent holds grades outside the blade set of the operand" : ": the node holds grades outside the blade set of the operand"));
+            return;
+        }
+        int canon = 0;
+        uint64_t flip = 0;
+        BufRef a = operand(a_id, &canon, &flip);
+        if (!ok()) return;
+        BufRef h = store_in_cache(h_id);
+        if (!ok()) return;
+        BufRef g;
+        if (adj2) g = store_in_cache(g_id);
+        if (!ok()) return;
+        if (key(a) == key(res) || key(h) == key(res) || (adj2 && key(g) == key(res))) {
+            fail(GAAST_ERR_MISSING_GRADE, op + " operand aliases its own result buffer");
+            return;
+        }
+        const Layout& lr = layout(res);
+        Step::Inverse q;
+        if (!blade_set_tables(q, even, a, amask, flip, res, adj2 ? nd.minimal_grade_mask & amask : nd.minimal_grade_mask)) return;
+        q.wmax = 0.0;
+        for (double w : q.weight) q.wmax = std::max(q.wmax, std::fabs(w));
+        q.h_off = blade_offsets(q, layout(h));
+        if (adj2) q.g_off = blade_offsets(q, layout(g));
+        adjoint_sign_words(q);
+        if (!q.n_out) return;
+        const auto fr = fresh.find(key(res));
+        const bool covers = fr != fresh.end() && !(plan.flags & GAAST_FLAG_NO_FUSION) && int64_t(q.n_out) == lr.row_len;
+        if (covers) removed[size_t(fr->second)] = 1;
+        Step& s = emit(adj2 ? Step::GEXP_ADJ2 : Step::GEXP_JVP, res, std::string(adj2 ? "general_exponential_adjoint2" : "general_exponential_jvp") + "[" + std::to_string(q.N) + (even ? " even" : "") + " blades, " + std::to_string(q.n_out) + " produced, n=" + std::to_string(n) + "]");
+        s.a = a;
+        s.b = g;
+        s.c = h;
         s.canon_a = canon;
         s.beta = covers ? 0 : 1;
         s.inv = std::move(q);
@@ -874,7 +949,10 @@ void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab,
         case GAAST_OP_GEXP_ADJ:
         case GAAST_OP_GSQRT_ADJ:
         case GAAST_OP_GLOG_ADJ:
+        case GAAST_OP_GEXP_JVP:
+        case GAAST_OP_GEXP_ADJ2:
             if (!child_ok(nd.child0) || !child_ok(nd.child1)) throw std::runtime_error("nodes are not in post-order");
+            if (nd.opcode == GAAST_OP_GEXP_ADJ2 && !child_ok(nd.input_slot)) throw std::runtime_error("nodes are not in post-order");   // (its third child)
             if (nd.opcode == GAAST_OP_PRODUCT && nd.product_kind >= GAAST_PROD_ADJ_LEFT) {
                 const int adj = nd.product_kind & ~7, base = nd.product_kind & 7;
                 if ((adj != GAAST_PROD_ADJ_LEFT && adj != GAAST_PROD_ADJ_RIGHT) || base > GAAST_PROD_REGRESSIVE)

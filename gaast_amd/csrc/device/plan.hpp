@@ -44,8 +44,9 @@ inline Layout make_layout(int dim, uint64_t mask) {
 // a step in place), each table and setting named after the one thing it holds.  The groups of the other kinds stay empty.  The
 // tables are host images, uploaded once at program_create.
 struct Step {
-    enum Kind { ZERO, AXPY, FLIP, SUNARY, PRODUCT_CSR, PRODUCT_DENSE, FUSED, EXPLOG, REDUCE_SCALE, ELEMENTWISE, LINMAP, EXPLOG_ADJ, DUAL, INVERSE, GEXP, GEXP_ADJ, GSQRT, GSQRT_ADJ, GLOG, GLOG_ADJ } kind = ZERO;
+    enum Kind { ZERO, AXPY, FLIP, SUNARY, PRODUCT_CSR, PRODUCT_DENSE, FUSED, EXPLOG, REDUCE_SCALE, ELEMENTWISE, LINMAP, EXPLOG_ADJ, DUAL, INVERSE, GEXP, GEXP_ADJ, GSQRT, GSQRT_ADJ, GLOG, GLOG_ADJ, GEXP_JVP, GEXP_ADJ2 } kind = ZERO;
     BufRef res, a, b;        // result; operand rows (PRODUCT_*: left, right; AXPY / EXPLOG / LINMAP / DUAL / INVERSE / GEXP / GSQRT / GLOG: a; EXPLOG_ADJ / GEXP_ADJ / GSQRT_ADJ / GLOG_ADJ: a = the forward operand, b = the cotangent; REDUCE_SCALE: the reduction's; ELEMENTWISE: b = the scalar)
+    BufRef c;                // a third operand row (GEXP_JVP: a = the forward operand, c = the tangent h; GEXP_ADJ2: a, b = g, c = h)
     std::string name;
     int canon_a = 0, canon_b = 0;   // the operand is a bound input read in place: the kernel applies the reference's 0.0 + x
     int beta = 1;                   // 0: the zero fill of a fresh result is folded in
@@ -221,6 +222,7 @@ struct Step {
         // GEXP / GEXP_ADJ / GSQRT / GSQRT_ADJ / GLOG / GLOG_ADJ only (empty for INVERSE)
         double wmax = 1.0;                  // the largest |weight|: theta = wmax * sum |A_a| bounds the largest absolute row sum of L
         std::vector<int32_t> g_off;         // GEXP_ADJ, GSQRT_ADJ, GLOG_ADJ [N] offset of blade j in the cotangent row; -1: absent (reads as 0)
+        std::vector<int32_t> h_off;         // GEXP_JVP, GEXP_ADJ2 [N] offset of blade j in the tangent row (Step::c); -1: absent (reads as 0)
         // GEXP_ADJ: the sign words of the two adjoint products of P = X Z, both with the metric factor weight[S[a] & S[b]]:
         std::vector<uint64_t> adj_neg_l;    // [N] bit b of adj_neg_l[a] = bit b of neg[a xor b]:  ADJL(g, Z)[a] = sum_b +-w Z[b] g[a xor b]
         std::vector<uint64_t> adj_neg_r;    // [N] bit a of adj_neg_r[b] = bit b of neg[a xor b]:  ADJR(g, X)[b] = sum_a +-w X[a] g[a xor b]
@@ -229,6 +231,9 @@ struct Step {
     // GEXP (GAAST_OP_GEXP, gaast_hip.h): res += exp(A) by scaling and squaring, A = row `a`; the blade set and every table are INVERSE's
     // (`inv`, built by the same function: plan.cpp: blade_set_tables).  GEXP_ADJ (GAAST_OP_GEXP_ADJ): res += the cotangent of A from
     // A = row `a` and the cotangent g = row `b` of the forward result; inv.res_off then addresses the operand's grades in res.
+    // GEXP_JVP (GAAST_OP_GEXP_JVP): res += the Frechet derivative of exp at A = row `a` in the direction h = row `c` (inv.h_off), in the
+    // wanted grades of the blade set.  GEXP_ADJ2 (GAAST_OP_GEXP_ADJ2): res += the gradient in A of <g, GEXP_JVP(h, A)>, g = row `b`
+    // (inv.g_off), h = row `c`; inv.res_off addresses the operand's grades in res.  Tables are GEXP_ADJ's; always launches of their own.
     // GSQRT (GAAST_OP_GSQRT, gaast_hip.h): res += the principal square root of A = row `a` by the Denman-Beavers product iteration, and
     // GSQRT_ADJ (GAAST_OP_GSQRT_ADJ): res += the cotangent of A, the solution of ADJL(a, X) + ADJR(a, X) = g.  Operands, blade set and
     // tables are GEXP's and GEXP_ADJ's, field for field (inv.wmax is not used; inv.adj_neg_l / adj_neg_r are the two sign words of a row of
@@ -277,7 +282,7 @@ struct Step {
 // as used input slots.  (An absent operand has idx < 0.)
 template <typename F>
 void for_each_read(const Step& s, F&& f) {
-    for (BufRef r : {s.a, s.b, s.pre.a, s.pre.b, s.reduce.x, s.cj.init_src})
+    for (BufRef r : {s.a, s.b, s.c, s.pre.a, s.pre.b, s.reduce.x, s.cj.init_src})
         if (r.idx >= 0) f(r);
     for (BufRef r : s.ew.src) f(r);
     for (const Step::FusedInput& fi : s.fused.inputs) f(BufRef{BufKind::INPUT, fi.slot});

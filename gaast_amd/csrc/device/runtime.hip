@@ -214,9 +214,9 @@ struct Launch {
         DevTable a_off, res_off, neg, weight;
         const void* kernel = nullptr;   // k_mv_inverse<T, N>
     } inv;
-    struct {   // GEXP, GEXP_ADJ
-        DevTable a_off, res_off, g_off, neg, neg_l, neg_r, weight;
-        const void* kernel = nullptr;   // k_mv_gexp<T, N> / k_mv_gexp_adj<T, N>
+    struct {   // GEXP, GEXP_ADJ, GEXP_JVP, GEXP_ADJ2
+        DevTable a_off, res_off, g_off, h_off, neg, neg_l, neg_r, weight;
+        const void* kernel = nullptr;   // k_mv_gexp<T, N> / k_mv_gexp_adj<T, N> / k_mv_gexp_jvp<T, N> / k_mv_gexp_adj2<T, N>
     } gexp;
     struct {   // GSQRT, GSQRT_ADJ
         DevTable a_off, res_off, g_off, neg, neg_l, neg_r, weight;
@@ -517,7 +517,7 @@ struct EvalRows {
 
 // ... and the operands of one launch among them (null where the step has none)
 struct Operands {
-    Bound res{nullptr, 0}, a{nullptr, 0}, b{nullptr, 0};
+    Bound res{nullptr, 0}, a{nullptr, 0}, b{nullptr, 0}, c{nullptr, 0};
     Layout lres, la, lb;
     Bound pre_a{nullptr, 0}, pre_b{nullptr, 0}, scaled_row{nullptr, 0}, init{nullptr, 0};   // Step: pre.a, pre.b, reduce.x, cj.init_src
     const EvalRows* rows = nullptr;   // FUSED, ELEMENTWISE: they read by slot and by source list
@@ -695,6 +695,60 @@ int run_gexp(const Launch& L, const Operands& o, int64_t batch) {
     p.dom = static_cast<unsigned long long*>(L.domain);
     const int64_t per_block = 256 / s.inv.N;
     launch_kernel(L.gexp.kernel, persistent_grid((batch + per_block - 1) / per_block, 8), 256, 0, p);
+    return launch_status();
+}
+
+// ---- GEXP_JVP, GEXP_ADJ2 -------------------------------------------------------------------------------------------------
+// (the second-order steps of the general exponential: one kernel per (T, N) each, the tables of GEXP_ADJ plus the tangent's offsets)
+template <typename T>
+int prepare_gexp2(Launch& L, std::string& kernel) {
+    Step& s = L.s;
+    auto& c = L.gexp;
+    const bool adj2 = s.kind == Step::GEXP_ADJ2;
+    using Kern = void (*)(Gexp2Args<T>);
+    c.kernel = kernel_address(adj2 ? static_int<2, 4, 8, 16, 32, 64>(s.inv.N, [](auto n) -> Kern { return k_mv_gexp_adj2<T, decltype(n)::value>; })
+                                   : static_int<2, 4, 8, 16, 32, 64>(s.inv.N, [](auto n) -> Kern { return k_mv_gexp_jvp<T, decltype(n)::value>; }));
+    if (!c.kernel) return set_err(GAAST_ERR_UNIMPLEMENTED, "no general-exponential kernel for " + std::to_string(s.inv.N) + " blades");
+    Upload<T> up;
+    up.idx(c.a_off, s.inv.a_off); up.idx(c.res_off, s.inv.res_off); up.idx(c.h_off, s.inv.h_off); up.idx(c.neg, s.inv.neg); up.val(c.weight, s.inv.weight);
+    if (adj2) {
+        up.idx(c.g_off, s.inv.g_off); up.idx(c.neg_l, s.inv.adj_neg_l); up.idx(c.neg_r, s.inv.adj_neg_r);
+    }
+    kernel = std::string(adj2 ? "k_mv_gexp_adj2<" : "k_mv_gexp_jvp<") + type_name<T>() + "," + std::to_string(s.inv.N) + ">";
+    return up.status;
+}
+
+template <typename T>
+int run_gexp2(const Launch& L, const Operands& o, int64_t batch) {
+    const Step& s = L.s;
+    if (batch <= 0) return GAAST_OK;
+    const bool adj2 = s.kind == Step::GEXP_ADJ2;
+    Gexp2Args<T> p;
+    p.res = static_cast<T*>(o.res.ptr);
+    p.in = static_cast<const T*>(o.a.ptr);
+    p.cot = adj2 ? static_cast<const T*>(o.b.ptr) : nullptr;
+    p.tan = static_cast<const T*>(o.c.ptr);
+    p.res_stride = o.res.stride;
+    p.in_stride = o.a.stride;
+    p.cot_stride = adj2 ? o.b.stride : 0;
+    p.tan_stride = o.c.stride;
+    p.batch = batch;
+    p.a_off = L.gexp.a_off.as<int32_t>();
+    p.res_off = L.gexp.res_off.as<int32_t>();
+    p.g_off = L.gexp.g_off.as<int32_t>();
+    p.h_off = L.gexp.h_off.as<int32_t>();
+    p.neg = L.gexp.neg.as<uint64_t>();
+    p.neg_l = L.gexp.neg_l.as<uint64_t>();
+    p.neg_r = L.gexp.neg_r.as<uint64_t>();
+    p.weight = L.gexp.weight.as<T>();
+    p.a_neg = s.inv.a_neg;
+    p.wmax = T(s.inv.wmax);
+    p.n = L.n;
+    p.even = s.inv.even;
+    p.beta = s.beta;
+    const int64_t per_block = 256 / s.inv.N;
+    const int per_cu = !adj2 ? 8 : sizeof(T) == 8 ? 2 : 4;   // (what the static LDS of k_mv_gexp_adj2 leaves resident on a CU)
+    launch_kernel(L.gexp.kernel, persistent_grid((batch + per_block - 1) / per_block, per_cu), 256, 0, p);
     return launch_status();
 }
 
@@ -1732,6 +1786,8 @@ int prepare_launch(Launch& L, const gaast_hip_program_s& prog) {
     case Step::INVERSE: st = prepare_inverse<T>(L, kernel); break;
     case Step::GEXP:
     case Step::GEXP_ADJ: st = prepare_gexp<T>(L, kernel); break;
+    case Step::GEXP_JVP:
+    case Step::GEXP_ADJ2: st = prepare_gexp2<T>(L, kernel); break;
     case Step::GSQRT:
     case Step::GSQRT_ADJ: st = prepare_gsqrt<T>(L, kernel); break;
     case Step::GLOG:
@@ -2475,6 +2531,8 @@ int run_launch(const Launch& L, const Operands& o, int64_t batch) {
     case Step::INVERSE: st = run_inverse<T>(L, o, batch); break;
     case Step::GEXP:
     case Step::GEXP_ADJ: st = run_gexp<T>(L, o, batch); break;
+    case Step::GEXP_JVP:
+    case Step::GEXP_ADJ2: st = run_gexp2<T>(L, o, batch); break;
     case Step::GSQRT:
     case Step::GSQRT_ADJ: st = run_gsqrt<T>(L, o, batch); break;
     case Step::GLOG:
@@ -2538,6 +2596,7 @@ int run_launches(gaast_hip_program_t prog, const std::vector<Bound>& in_bound, g
         o.res = rows.at(s.res, &o.lres, callers_rows);
         o.a = at(s.a, &o.la);
         o.b = at(s.b, &o.lb);
+        o.c = at(s.c, &unused);
         o.pre_a = at(s.pre.a, &unused);
         o.pre_b = at(s.pre.b, &unused);
         o.scaled_row = at(s.reduce.x, &unused);

@@ -35,7 +35,8 @@
 // nodes are forward nodes like any other; a compact GAAST_PROD_ADJ_* node is a product event whose operands' cotangents are, by the
 // trilinear form <g, a o b> of the forward kind, the forward product or the other adjoint of the same kind (product_adjoint, table
 // in gaast_expr.h); the adjoint op nodes (GAAST_OP_*_ADJ) are opaque events that are carried along off the path and refused by name
-// on it (their derivative is a Frechet derivative of a matrix function).
+// on it (their derivative is a Frechet derivative of a matrix function) -- except, under GAAST_FLAG_GEXP_GRAD2, the family of the
+// general exponential {GEXP_ADJ, GEXP_JVP, GEXP_ADJ2}, which has those kernels and is closed up to second order (gexp_family_adjoint).
 // Buffers are visited from the root down (decreasing node index: a buffer's users come after it in post-order).  The adjoint
 // program is evaluated in place as well, so every cotangent node it builds is ADDITIVE (input, product, or sums of them): adding
 // it into a buffer adds its value.  Sign changes and projections of a cotangent that cannot be folded into a list are explicit
@@ -62,8 +63,11 @@ struct VjpError {
 };
 
 bool has_two_children(int opcode) {
-    return opcode == GAAST_OP_ADD || opcode == GAAST_OP_PRODUCT || opcode == GAAST_OP_EXP_ADJ || opcode == GAAST_OP_LOG_ADJ || opcode == GAAST_OP_GEXP_ADJ || opcode == GAAST_OP_GSQRT_ADJ || opcode == GAAST_OP_GLOG_ADJ;
+    return opcode == GAAST_OP_ADD || opcode == GAAST_OP_PRODUCT || opcode == GAAST_OP_EXP_ADJ || opcode == GAAST_OP_LOG_ADJ || opcode == GAAST_OP_GEXP_ADJ || opcode == GAAST_OP_GSQRT_ADJ || opcode == GAAST_OP_GLOG_ADJ ||
+           opcode == GAAST_OP_GEXP_JVP || opcode == GAAST_OP_GEXP_ADJ2;
 }
+// GAAST_OP_GEXP_ADJ2 has a third child, the forward operand: its node index travels in input_slot (gaast_hip.h); -1 for every other node
+int third_child(const gaast_node_desc& nd) { return nd.opcode == GAAST_OP_GEXP_ADJ2 ? nd.input_slot : -1; }
 
 // the adjoint op nodes that gaast_program_vjp itself emits (child0 = a cotangent, child1 = the forward operand)
 const char* adjoint_op_name(int opcode) {
@@ -73,6 +77,7 @@ const char* adjoint_op_name(int opcode) {
     case GAAST_OP_GEXP_ADJ: return "GAAST_OP_GEXP_ADJ";
     case GAAST_OP_GSQRT_ADJ: return "GAAST_OP_GSQRT_ADJ";
     case GAAST_OP_GLOG_ADJ: return "GAAST_OP_GLOG_ADJ";
+    case GAAST_OP_GEXP_JVP: return "GAAST_OP_GEXP_JVP";
     default: return nullptr;
     }
 }
@@ -254,6 +259,32 @@ struct Builder {
         nd.child0 = g;
         nd.child1 = c;
         cot[size_t(c)].push_back(Term{add(nd), 0, ~0ULL});
+    }
+    // GAAST_FLAG_GEXP_GRAD2: the cotangents of the operands of a GEXP_ADJ / GEXP_JVP node x (table in gaast_expr.h).  Both are bilinear
+    // in (child0, the Frechet derivative at A): <k, GEXP_ADJ(g, A)> = <g, GEXP_JVP(k, A)>, whose gradient in A is GEXP_ADJ2(g, k, A)
+    void gexp_family_adjoint(int x, const std::vector<Term>& terms, std::vector<std::vector<Term>>& cot) {
+        const gaast_node_desc& xd = d.nodes[x];
+        if (xd.opcode == GAAST_OP_GEXP_ADJ2)
+            throw VjpError{GAAST_ERR_UNIMPLEMENTED, "third-order reverse mode through GAAST_OP_GEXP_ADJ2 is not implemented"};
+        const bool jvp = xd.opcode == GAAST_OP_GEXP_JVP;
+        const int c0 = xd.child0, a = xd.child1;
+        const uint64_t amask = d.nodes[a].minimal_grade_mask, c0mask = d.nodes[c0].minimal_grade_mask;
+        if (!dep[size_t(c0)] && !dep[size_t(a)]) return;
+        const int k = materialize(terms, xd.minimal_grade_mask);
+        if (k < 0 || !amask) return;
+        if (dep[size_t(c0)] && c0mask) {   // linear in child0: the transposed map at the same A
+            gaast_node_desc nd = blank(jvp ? GAAST_OP_GEXP_ADJ : GAAST_OP_GEXP_JVP, c0mask, n);
+            nd.child0 = k;
+            nd.child1 = a;
+            cot[size_t(c0)].push_back(Term{add(nd), 0, ~0ULL});
+        }
+        if (dep[size_t(a)] && c0mask) {
+            gaast_node_desc nd = blank(GAAST_OP_GEXP_ADJ2, amask, n);
+            nd.child0 = jvp ? k : c0;    // g
+            nd.child1 = jvp ? c0 : k;    // h
+            nd.input_slot = a;
+            cot[size_t(a)].push_back(Term{add(nd), 0, ~0ULL});
+        }
     }
     // gsqrt: cotangent of the operand's buffer (gaast_hip.h: GAAST_OP_GSQRT_ADJ)
     void gsqrt_adjoint(int x, const std::vector<Term>& terms, std::vector<std::vector<Term>>& cot) {
@@ -437,7 +468,8 @@ struct Builder {
         for (int i = 0; i < nf; ++i) {
             const gaast_node_desc& nd = d.nodes[i];
             if (nd.opcode == GAAST_OP_INPUT) dep[size_t(i)] = nd.input_slot == wrt;
-            else dep[size_t(i)] = dep[size_t(nd.child0)] || (nd.child1 >= 0 && has_two_children(nd.opcode) && dep[size_t(nd.child1)]);
+            else dep[size_t(i)] = dep[size_t(nd.child0)] || (nd.child1 >= 0 && has_two_children(nd.opcode) && dep[size_t(nd.child1)]) ||
+                                  (third_child(nd) >= 0 && dep[size_t(third_child(nd))]);
         }
         std::vector<std::vector<Term>> cot(static_cast<size_t>(nf));
         std::vector<int> outs;
@@ -484,7 +516,11 @@ struct Builder {
                 }
                 case EV_SCALAR: scalar_adjoint(s, e, terms); break;
                 case EV_OPAQUE:   // a node whose operand has a buffer of its own
-                    if (const char* name = adjoint_op_name(x.opcode)) {   // its second derivative needs a Frechet-derivative kernel
+                    if ((d.flags & GAAST_FLAG_GEXP_GRAD2) && (x.opcode == GAAST_OP_GEXP_ADJ || x.opcode == GAAST_OP_GEXP_JVP)) {
+                        gexp_family_adjoint(e.node, terms, cot);   // (the family is closed up to second order)
+                    } else if (x.opcode == GAAST_OP_GEXP_ADJ2) {
+                        if (dep[size_t(e.node)]) gexp_family_adjoint(e.node, terms, cot);   // (refused, with or without the flag)
+                    } else if (const char* name = adjoint_op_name(x.opcode)) {   // its second derivative needs a Frechet-derivative kernel
                         if (dep[size_t(e.node)])
                             throw VjpError{GAAST_ERR_UNIMPLEMENTED, std::string("second-order reverse mode through ") + name + " is not implemented"};
                     } else if (x.opcode == GAAST_OP_DUAL || x.opcode == GAAST_OP_UNDUAL) dual_adjoint(e.node, terms, cot);
@@ -546,9 +582,10 @@ extern "C" int gaast_program_vjp(const gaast_program_desc* desc, int32_t wrt_slo
         const gaast_node_desc& nd = d.nodes[i];
         const bool two = has_two_children(nd.opcode);
         const bool ok = nd.opcode == GAAST_OP_INPUT ? (nd.input_slot >= 0 && nd.input_slot < d.n_inputs)
-                        : (nd.opcode > GAAST_OP_INPUT && nd.opcode <= GAAST_OP_GLOG_ADJ &&
+                        : (nd.opcode > GAAST_OP_INPUT && nd.opcode <= GAAST_OP_GEXP_ADJ2 &&
                            nd.child0 >= 0 && nd.child0 < i &&
-                           (!two || (nd.child1 >= 0 && nd.child1 < i)));
+                           (!two || (nd.child1 >= 0 && nd.child1 < i)) &&
+                           (nd.opcode != GAAST_OP_GEXP_ADJ2 || (nd.input_slot >= 0 && nd.input_slot < i)));
         // a compact adjoint product (a VJP program differentiates again): GAAST_PROD_ADJ_LEFT or GAAST_PROD_ADJ_RIGHT over a kind 0..5
         const int adj = nd.product_kind & ~7, base = nd.product_kind & 7;
         const bool kind_ok = nd.opcode != GAAST_OP_PRODUCT || nd.product_kind < GAAST_PROD_ADJ_LEFT ||
@@ -573,6 +610,7 @@ extern "C" int gaast_program_vjp(const gaast_program_desc* desc, int32_t wrt_slo
             const gaast_node_desc& nd = b.nodes[i];
             if (nd.child0 >= 0) keep[size_t(nd.child0)] = 1;
             if (nd.child1 >= 0 && has_two_children(nd.opcode)) keep[size_t(nd.child1)] = 1;
+            if (third_child(nd) >= 0) keep[size_t(third_child(nd))] = 1;
         }
         std::vector<gaast_node_desc> nodes;
         for (size_t i = 0; i < b.nodes.size(); ++i) {
@@ -580,6 +618,7 @@ extern "C" int gaast_program_vjp(const gaast_program_desc* desc, int32_t wrt_slo
             gaast_node_desc nd = b.nodes[i];
             if (nd.child0 >= 0) nd.child0 = remap[size_t(nd.child0)];
             if (nd.child1 >= 0) nd.child1 = has_two_children(nd.opcode) ? remap[size_t(nd.child1)] : -1;
+            if (third_child(nd) >= 0) nd.input_slot = remap[size_t(nd.input_slot)];
             if (nd.opcode == GAAST_OP_PRODUCT && i >= size_t(d.n_nodes) && !b.lists[i].empty())   // (explicit; a regressive one names its kind)
                 nd.comp_muls = b.lists[i].data();
             remap[i] = int(nodes.size());

@@ -200,10 +200,25 @@ void gaast_program_image_free(gaast_program_image_t img);
  * orientation sign once per node), and an explicit list stays explicit.  GAAST_OP_INV needs nothing else: its adjoint is a
  * GAAST_OP_NEG, one more GAAST_OP_INV and two geometric adjoint products.
  * The adjoint op nodes GAAST_OP_EXP_ADJ, GAAST_OP_LOG_ADJ, GAAST_OP_GEXP_ADJ, GAAST_OP_GSQRT_ADJ and GAAST_OP_GLOG_ADJ are valid nodes
- * with two children; off the path to wrt_slot they are carried along untouched.
+ * with two children; off the path to wrt_slot they are carried along untouched.  So are GAAST_OP_GEXP_JVP (two children) and
+ * GAAST_OP_GEXP_ADJ2 (three: the third, the forward operand, is the node index in input_slot, which the renumbering of the image
+ * follows like child0 and child1).
+ * Second order through the general exponential (OPT-IN: GAAST_FLAG_GEXP_GRAD2 in desc->flags; only this function reads the flag, the
+ * image inherits it).  With k the cotangent of the node's buffer restricted to the node's grades:
+ *     node on the path          through   its operand's cotangent
+ *     GEXP_ADJ(g, A)            g         GEXP_JVP(k, A), mask of g
+ *     GEXP_ADJ(g, A)            A         GEXP_ADJ2(g, k, A), mask of A
+ *     GEXP_JVP(t, A)            t         GEXP_ADJ(k, A), mask of t
+ *     GEXP_JVP(t, A)            A         GEXP_ADJ2(k, t, A), mask of A
+ *     GEXP_ADJ2                 any       GAAST_ERR_UNIMPLEMENTED ("third-order reverse mode through GAAST_OP_GEXP_ADJ2 ...")
+ * so the family {GEXP_ADJ, GEXP_JVP, GEXP_ADJ2} is closed up to second order: Hessian-vector products, forward mode (the VJP of the
+ * VJP with respect to its cotangent holds GEXP_JVP and never reads the first cotangent) and the transpose of forward mode all work
+ * through gexp.  Without the flag GEXP_ADJ on the path is refused as before and GEXP_JVP in the same words; a forward image is the
+ * same with and without the flag, a first-order image differs in its flags word only.
  * Errors: GAAST_ERR_INVALID_ARGUMENT for a wrt_slot out of range or const, or n_inputs + 1 > GAAST_MAX_INPUTS;
  * GAAST_ERR_UNIMPLEMENTED for one of the five adjoint op nodes on the path to wrt_slot, through either child (the message names the
- * op: the second derivative of these matrix functions needs Frechet-derivative kernels the library does not have);
+ * op: the second derivative of these matrix functions needs Frechet-derivative kernels, which the library has for gexp alone and
+ * uses under GAAST_FLAG_GEXP_GRAD2), and for GAAST_OP_GEXP_ADJ2 on the path (third order);
  * GAAST_ERR_UNIMPLEMENTED for GAAST_FLAG_SPINOR_GEMM, and for exp / log on the path to wrt_slot unless desc->flags holds both
  * GAAST_FLAG_EXP_LOG and GAAST_FLAG_EXP_LOG_GRAD: then the operand's cotangent is a GAAST_OP_EXP_ADJ / GAAST_OP_LOG_ADJ node
  * (gaast_hip.h) over the cotangent of the exp / log node's buffer and the forward operand (exp of a bare scalar, grade set {0},

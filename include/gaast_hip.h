@@ -242,7 +242,40 @@ typedef enum gaast_opcode {
      * Every solve is GAAST_OP_INV's elimination, the pivot test against N eps max_i |M_i| of the multivector whose matrix it is.  A
      * failed pivot test, or a domain error of the recomputed forward, makes every component of the item's cotangent NaN; it is not
      * counted.  Accuracy: 4 GRAD_SCALE in the units GAAST_OP_GLOG states (tests/glog_numpy.py). */
-    GAAST_OP_GLOG_ADJ = 21
+    GAAST_OP_GLOG_ADJ = 21,
+    /* The Frechet derivative L_A(h) of GAAST_OP_GEXP at A in direction h: the tangent of the recurrences above, s held fixed.
+     * Emitted by gaast_program_vjp under GAAST_FLAG_GEXP_GRAD2 when it differentiates a GAAST_OP_GEXP_ADJ node with respect to its
+     * cotangent; evaluating the node needs no flag.  child0 = the tangent h, which may hold only grades the operand holds (anything
+     * else: GAAST_ERR_INVALID_PROGRAM); child1 = the forward operand A.  The node's own minimal grade mask lies within the maximal
+     * grade set of GAAST_OP_GEXP over A (the grades it produces); it ADDS into its buffer.  Notation is GAAST_OP_GEXP's and
+     * GAAST_OP_GEXP_ADJ's: S, N, coeff, ADJL, ADJR, wmax, the degree m, and s, which is computed from A alone.  With A_s, q_k, Y_i
+     * the forward's and h_s = 2^-s h (exact):
+     *   qd_m = 0;   qd_(k-1) = (h_s q_k + A_s qd_k) / k  for k = m ... 1   (two products, their sum, one division);
+     *   Yd_0 = qd_0;   Yd_(i+1) = Yd_i Y_i + Y_i Yd_i  for i < s;   the result is Yd_s.
+     * Every product is the forward's P[r] = sum_j L_X[r][j] Z[j], j ascending.  It is the transpose of GAAST_OP_GEXP_ADJ's sweep:
+     * <g, GEXP_JVP(h, A)> = <GEXP_ADJ(g, A), h>.  No domain check and no count: a domain-error item of the forward takes its
+     * scaling factor as NaN and every component of it comes back NaN by arithmetic.  Supported sizes are GAAST_OP_GEXP's. */
+    GAAST_OP_GEXP_JVP = 22,
+    /* The gradient with respect to A of <g, GEXP_JVP(h, A)>: the adjoint of the second Frechet derivative of GAAST_OP_GEXP, s held
+     * fixed.  Emitted by gaast_program_vjp under GAAST_FLAG_GEXP_GRAD2; evaluating the node needs no flag.  child0 = g (any grades
+     * within S), child1 = h (within the operand's grades, else GAAST_ERR_INVALID_PROGRAM), and a THIRD child, the forward operand A,
+     * whose node index is carried in input_slot (a field no other opcode than GAAST_OP_INPUT uses: the node record and the wire
+     * format keep their bytes).  The node's own minimal grade mask is the operand's; it ADDS into its buffer.
+     * The pair (Y_i, Yd_i), (q_k, qd_k) of GAAST_OP_GEXP_JVP is recomputed.  Then, with Gd the cotangent of the tangent values and
+     * G the cotangent of the values, both members of a pair computed from the old values:
+     *   Gd = g, G = 0;
+     *   for i = s-1 ... 0:  G  <- ((ADJL(G, Y_i) + ADJR(G, Y_i)) + ADJR(Gd, Yd_i)) + ADJL(Gd, Yd_i);
+     *                       Gd <- ADJL(Gd, Y_i) + ADJR(Gd, Y_i);
+     *   dA_s = 0;
+     *   for k = 1 ... m:    w = G / k;  wd = Gd / k;
+     *                       dA_s <- dA_s + (ADJL(w, q_k) + ADJL(wd, qd_k));
+     *                       G  <- ADJR(w, A_s) + ADJR(wd, h_s);   Gd <- ADJR(wd, A_s);
+     *   dA = 2^-s dA_s, restricted to the grades the operand holds.
+     * No domain check and no count, as GAAST_OP_GEXP_JVP.  Supported sizes are GAAST_OP_GEXP's.
+     * Accuracy of both, per item that is no domain error, against these recurrences in extended precision: 4 JVP_SCALE in units
+     * of N eps max(1, theta) ||h||_inf ||exp A||_inf, and 4 ADJ2_SCALE in units of N eps max(1, theta) ||g||_inf ||h||_inf
+     * ||exp A||_inf (tests/gexp2_numpy.py records the scales: the worst error of a numpy restatement in the program's dtype). */
+    GAAST_OP_GEXP_ADJ2 = 23
 } gaast_opcode;
 
 /* the five products of src/ast/expr.rs:180-197 (and the regressive product), for compact PRODUCT descriptors */
@@ -338,6 +371,13 @@ typedef struct gaast_input_desc {
  * on the path to the differentiated input stays GAAST_ERR_UNIMPLEMENTED, and every status, plan, launch name and bit of a
  * program is what it was before the flag existed.  The flag changes nothing in a forward program. */
 #define GAAST_FLAG_EXP_LOG_GRAD 0x2000u
+/* OPT-IN: gaast_program_vjp differentiates THROUGH the adjoint family of the general exponential -- a GAAST_OP_GEXP_ADJ or
+ * GAAST_OP_GEXP_JVP node on the path to the differentiated input gets GAAST_OP_GEXP_JVP / GAAST_OP_GEXP_ADJ / GAAST_OP_GEXP_ADJ2
+ * nodes (table in gaast_expr.h): second-order reverse mode and forward mode through gexp.  Only gaast_program_vjp reads the flag;
+ * the adjoint program inherits it like every flag.  Without it such a node stays GAAST_ERR_UNIMPLEMENTED, and every status, message,
+ * plan, launch name and bit is what it was before the flag existed.  The flag changes nothing in a forward program, and in a
+ * first-order VJP image only the flags word. */
+#define GAAST_FLAG_GEXP_GRAD2 0x4000u
 #define GAAST_FLAG_DEBUG_LDS_12K 0x400u /* hiprtc-specialised kernels: 12 KiB instead of 10 KiB of LDS per wave for the row transposition (A/B testing) */
 #define GAAST_FLAG_DEBUG_NO_CHAIN 0x800u /* a sparse product that only feeds a dense product stays a launch of its own (default: evaluated in the dense kernel's LDS staging; A/B testing) */
 /* (bits 30 and 31 are reserved and ignored) */
@@ -584,7 +624,9 @@ int gaast_hip_eval_gather(gaast_hip_program_t prog, const gaast_hip_mv_t *inputs
  * desc may itself be a VJP program (read from the image of gaast_program_vjp): gaast_program_vjp is closed under itself, so this
  * creates second- and higher-order programs, the cotangent of desc being one of its slots and wrt_slot any non-const one.  Adjoint
  * products of dense geometric products run on the forward's dense kernels at every order.  One of the adjoint op nodes
- * (GAAST_OP_EXP_ADJ, LOG_ADJ, GEXP_ADJ, GSQRT_ADJ, GLOG_ADJ) on the path to wrt_slot: GAAST_ERR_UNIMPLEMENTED. */
+ * (GAAST_OP_EXP_ADJ, LOG_ADJ, GEXP_ADJ, GSQRT_ADJ, GLOG_ADJ) on the path to wrt_slot: GAAST_ERR_UNIMPLEMENTED -- except GEXP_ADJ (and
+ * GEXP_JVP) when desc->flags holds GAAST_FLAG_GEXP_GRAD2: second order and forward mode through gexp (gaast_expr.h has the table);
+ * a GAAST_OP_GEXP_ADJ2 node on the path, third order, is GAAST_ERR_UNIMPLEMENTED. */
 int gaast_hip_program_create_vjp(const gaast_program_desc *desc, int32_t wrt_slot, gaast_hip_program_t *out);
 /* gaast_program_vjp followed by gaast_hip_program_create_in_basis: the VJP of a program in a non-diagonal metric.  With the orthogonal
  * Q of the basis change, y_e = C(Q) F(C(Q^T) x_e) and every C_k(Q) is orthogonal, so the VJP of the in-basis program is the in-basis

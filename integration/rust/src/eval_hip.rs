@@ -209,7 +209,8 @@ impl<T: GradedData + std::fmt::Debug> SpecializedAst<T> {
                 //     N::Inverse(e) => { d.opcode = OP_INV; d.child0 = index[e]; }
                 // with the node's grade set the even grades for an even child and every grade otherwise, and the child wanted
                 // in all of its grades (a scalar child: ScalarUnaryOp::Inversion, as above).
-                // The general exponential (OP_GEXP) flattens the same way, with the same grade set; its adjoint node OP_GEXP_ADJ is only ever emitted by gaast_program_vjp.
+                // The general exponential (OP_GEXP) flattens the same way, with the same grade set; its adjoint node OP_GEXP_ADJ is only ever emitted by gaast_program_vjp,
+                // and so are OP_GEXP_JVP / OP_GEXP_ADJ2 (second order through gexp, under FLAG_GEXP_GRAD2; ADJ2's third child is the node index in input_slot).
                 // The general square root (OP_GSQRT / OP_GSQRT_ADJ) likewise; of a scalar child it is ScalarUnaryOp::Sqrt.
                 // The general logarithm (OP_GLOG / OP_GLOG_ADJ) likewise, with no scalar lowering.
             }
