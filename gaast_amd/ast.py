@@ -390,7 +390,7 @@ class SpecializedAst:
     def jvp(self, slot):
         """Forward mode with respect to input `slot` (the double-VJP trick: the VJP program differentiated with respect to its
         cotangent), built once per slot: an object with eval_batch(inputs, tangent, batch, out=None) -> J v.  Through gexp it needs
-        specialize(..., flags=FLAG_GEXP_GRAD2)."""
+        specialize(..., flags=FLAG_GEXP_GRAD2); through gsqrt / glog it needs FLAG_GSQRT_GLOG_JVP."""
         cache = self.__dict__.setdefault("_jvps", {})
         if slot not in cache:
             cache[slot] = Jvp(self, int(slot))
@@ -413,8 +413,9 @@ class Vjp:
     and the cotangent (slot = that program's number of slots), and whose output is the gradient in the layout of input `slot`.
     The program differentiated (`parent`) is a SpecializedAst or another Vjp: gaast_program_vjp is closed under itself, except
     through the adjoint nodes of exp / log / gexp / gsqrt / glog (GAAST_ERR_UNIMPLEMENTED).  With specialize(..., flags=FLAG_GEXP_GRAD2)
-    gexp's adjoint nodes differentiate too (second order and forward mode through gexp; third order is refused); gsqrt / glog / exp /
-    log are unchanged."""
+    gexp's adjoint nodes differentiate too (second order and forward mode through gexp; third order is refused).  With
+    FLAG_GSQRT_GLOG_JVP gsqrt's adjoint nodes differentiate to any order, and glog's with respect to the cotangent path (forward mode;
+    with respect to glog's operand they stay refused).  exp / log are unchanged."""
 
     def __init__(self, parent, slot):
         L = _lib.lib()

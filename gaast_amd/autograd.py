@@ -9,7 +9,8 @@ Backward is differentiable to any order (create_graph=True: Hessian-vector produ
 autograd.Function over the Vjp object, whose own backward evaluates Vjp.vjp(slot), built when first asked for.  Programs that hold
 exp / log / gexp / gsqrt / glog on the path differentiate once; asking for their second derivative raises GaastError UNIMPLEMENTED --
 except through gexp on a spec built with specialize(..., flags=FLAG_GEXP_GRAD2): there second order (and forward mode, spec.jvp)
-works, and it is the third order that is refused.  gsqrt / glog / exp / log are unchanged by that flag.
+works, and it is the third order that is refused.  With FLAG_GSQRT_GLOG_JVP every order works through gsqrt, and forward mode
+(spec.jvp) through glog; a second derivative with respect to an input under glog stays refused.  exp / log are unchanged.
 """
 from __future__ import annotations
 

@@ -3,6 +3,7 @@
 //
 //   k_mv_glog<T, N>       res += the principal logarithm of A over a blade set S of N = 2, 4, ... 64 blades (every blade, or the even ones)
 //   k_mv_glog_adj<T, N>   res += the cotangent of A, from A and the cotangent g of glog(A)
+//   k_mv_jvp_glog<T, N>   res += the tangent of glog at A in direction h (GAAST_OP_GLOG_JVP; Step::GLOG_JVP)
 //
 // Inverse scaling and squaring in multivector space, on the left-multiplication matrix of k_mv_inverse (plan.hpp: Step::Inverse, the
 // same blade order and tables).  Per item, as gaast_hip.h states it:
@@ -19,6 +20,12 @@
 //                  (pass 2 j: R_(M_j)^T v = 2^s g with ADJL's sign word, pass 2 j + 1: L_(M_j)^T u = v with ADJR's; a += alpha_j u), and
 //                  one loop over the chain i = s ... 1, k_mv_gsqrt_adj's system at X_i.  A failed pivot or a domain error of the
 //                  forward gives NaNs; no count.
+//   k_mv_jvp_glog  the adjoint read backwards: the forward again with the chain in LDS; one loop up the chain i = 1 ... s,
+//                  k_mv_gsqrt_jvp's system (L + R at X_i) on the tangent, an item with fewer roots keeping its value by a select;
+//                  then one loop over the 14 solves (pass 2 j: L_(M_j) p = t_s with L's sign word, pass 2 j + 1: R_(M_j) q = p with
+//                  the right-multiplication word; acc += alpha_j q), the result scaled by 2^s at the store.  It takes GlogArgs as
+//                  they are: cot / cot_stride / g_off are the tangent's rows and offsets, neg_r the sign words of R (neg_l is not read).
+//                  (Its name does not begin with k_mv_glog: tests/test_kernel_resources_glog.py counts the kernels whose names do.)
 // Offsets in int64_t; any row stride (0: one operand shared by every item), padding or alignment takes the same scalar accesses.
 #pragma once
 #include "../common/glog_pade.hpp"
@@ -311,6 +318,110 @@ __global__ __launch_bounds__(256, 2) void k_mv_glog_adj(const GlogArgs<T> p) {
         if (live && res_off >= 0) {
             T* d = p.res + item * p.res_stride + res_off;
             *d = (p.beta ? *d : T(0)) + (pbad ? qnan(T(0)) : a);
+        }
+    }
+}
+
+template <typename T, int N>
+__global__ __launch_bounds__(256, 2) void k_mv_jvp_glog(const GlogArgs<T> p) {
+    using namespace glog_detail;
+    static_assert(N == 2 || N == 4 || N == 8 || N == 16 || N == 32 || N == 64, "one item per N lanes of a wave");
+    constexpr int IPB = 256 / N;
+    __shared__ Shared<T> sh;
+    __shared__ ExtraAdj<T> ex;
+    const int tid = int(threadIdx.x);
+    const int r = tid & (N - 1), g = tid / N, it0 = tid & ~(N - 1);
+    const int lane0 = (tid & 63) & ~(N - 1);
+    if (tid < (1 << p.n)) sh.weight[tid] = p.weight[tid];
+    load_pade<T>(ex, tid);
+    const int32_t a_off = p.a_off[r], res_off = p.res_off[r], h_off = p.g_off[r];
+    const bool a_neg = ((p.a_neg >> r) & 1ULL) != 0;
+    const uint64_t neg = p.neg[r], neg_m = p.neg_r[r];   // row r of L's signs and of R's
+    const uint32_t e = uint32_t(p.even);
+    const T e0 = r == 0 ? T(1) : T(0);
+    const T n_eps = T(N) * eps_of(T(0));
+    for (int64_t base = int64_t(blockIdx.x) * IPB; base < p.batch; base += int64_t(gridDim.x) * IPB) {
+        const int64_t item = base + g;
+        const bool live = item < p.batch;
+        T v = T(0), hv = T(0);
+        if (live && a_off >= 0) v = p.in[item * p.in_stride + a_off];
+        if (live && h_off >= 0) hv = p.cot[item * p.cot_stride + h_off];
+        if (a_neg) v = -v;
+        T x;
+        int s;
+        bool bad;
+        const int smax = take_roots<T, N, true>(sh, ex, v, live, tid, neg, e, p.wmax, &x, &s, &bad);
+        const T E = x - e0;
+        T t = hv;
+        uint32_t pbad = uint32_t(bad);
+        __syncthreads();                                     // (the chain is written: after 16 roots no barrier follows the last store)
+#pragma unroll 1
+        for (int i = 1; i <= smax; ++i) {                    // t <- the solution of (L + R at X_i) t = t, for i <= s
+            const T* const X = ex.chain[i - 1] + it0;
+            const T amax = item_amax<T, N>(ex.chain[i - 1][tid]);
+            uint32_t nr = ~uint32_t(r);
+            uint32_t l_lo = uint32_t(neg), l_hi = uint32_t(neg >> 32), m_lo = uint32_t(neg_m), m_hi = uint32_t(neg_m >> 32);
+            asm volatile("" : "+v"(nr), "+v"(l_lo), "+v"(l_hi), "+v"(m_lo), "+v"(m_hi));
+            const uint32_t npar = e & ~uint32_t(__builtin_popcount(~nr)) & 1u;   // e & ~parity(r)
+            T row[N];
+#pragma unroll
+            for (int c = 0; c < N; ++c) {
+                const uint32_t idx = ((uint32_t(c) & nr) << e) | ((uint32_t(__builtin_popcount(uint32_t(c))) & 1u) ? npar : 0u);
+                const T wx = sh.weight[idx] * X[(~nr & uint32_t(N - 1)) ^ uint32_t(c)];
+                row[c] = flip_sign(wx, ((c < 32 ? l_lo : l_hi) >> (c & 31)) & 1u) + flip_sign(wx, ((c < 32 ? m_lo : m_hi) >> (c & 31)) & 1u);
+                if ((c & 7) == 7) __builtin_amdgcn_sched_barrier(0);
+            }
+            int col;
+            bool sing;
+            T oc;
+            GAAST_GSQRT_ELIMINATE(row, t, n_eps * amax, r, lane0, col, oc, sing)
+            __syncthreads();                                 // (sh.w: the pass before has been read)
+            sh.w[it0 + col] = oc;
+            __syncthreads();
+            const bool mine = i <= s;
+            t = mine ? sh.w[tid] : t;
+            pbad |= uint32_t(mine && sing);
+            asm volatile("" : "+v"(pbad));
+        }
+        T acc = T(0), rhs = t;
+#pragma unroll 1
+        for (int ps = 0; ps < 2 * kGlogPadeTerms; ++ps) {    // pass 2 j: L_(M_j) p = t_s;  pass 2 j + 1: R_(M_j) q = p,  acc += alpha_j q
+            const int j = ps >> 1;
+            const bool second = (ps & 1) != 0;
+            __syncthreads();                                 // (the pass before has read sh.m and sh.w; the first: the chain is over, `node` is written)
+            const T mj = e0 + ex.node[j] * E;
+            sh.m[tid] = mj;
+            const T amax = item_amax<T, N>(mj);
+            __syncthreads();
+            // my row of L_(M_j) or of R_(M_j), as principal_root builds its row: +-w M[r xor c] with L's sign word or R's
+            uint32_t nr = ~uint32_t(r);
+            uint32_t s_lo = second ? uint32_t(neg_m) : uint32_t(neg), s_hi = second ? uint32_t(neg_m >> 32) : uint32_t(neg >> 32);
+            asm volatile("" : "+v"(nr), "+v"(s_lo), "+v"(s_hi));
+            const uint32_t npar = e & ~uint32_t(__builtin_popcount(~nr)) & 1u;   // e & ~parity(r)
+            const T* const M = sh.m + it0;
+            T row[N];
+#pragma unroll
+            for (int c = 0; c < N; ++c) {
+                const uint32_t idx = ((uint32_t(c) & nr) << e) | ((uint32_t(__builtin_popcount(uint32_t(c))) & 1u) ? npar : 0u);
+                const T w = sh.weight[idx] * M[(~nr & uint32_t(N - 1)) ^ uint32_t(c)];
+                row[c] = flip_sign(w, ((c < 32 ? s_lo : s_hi) >> (c & 31)) & 1u);
+                if ((c & 7) == 7) __builtin_amdgcn_sched_barrier(0);
+            }
+            int col;
+            bool sing;
+            T oc;
+            GAAST_GSQRT_ELIMINATE(row, rhs, n_eps * amax, r, lane0, col, oc, sing)
+            sh.w[it0 + col] = oc;
+            __syncthreads();
+            const T sol = sh.w[tid];
+            acc = second ? fma_m(ex.wgt[j], sol, acc) : acc;
+            rhs = second ? t : sol;
+            pbad |= uint32_t(sing);
+            asm volatile("" : "+v"(pbad));
+        }
+        if (live && res_off >= 0) {
+            T* d = p.res + item * p.res_stride + res_off;
+            *d = (p.beta ? *d : T(0)) + (pbad ? qnan(T(0)) : ldexp_m(acc, s));
         }
     }
 }

@@ -3,6 +3,7 @@
 //
 //   k_mv_gsqrt<T, N>       res += the principal X with X X = A over a blade set S of N = 2, 4, ... 64 blades (every blade, or the even ones)
 //   k_mv_gsqrt_adj<T, N>   res += the cotangent of A, from A and the cotangent g of gsqrt(A)
+//   k_mv_gsqrt_jvp<T, N>   res += the tangent of gsqrt at A in direction h (GAAST_OP_GSQRT_JVP; Step::GSQRT_JVP)
 //
 // The product form of the Denman-Beavers iteration in multivector space, on the left-multiplication matrix L[r][j] = coeff(r, j) A[r xor j]
 // of k_mv_inverse (plan.hpp: Step::Inverse, the same blade order and tables).  Per item, as gaast_hip.h states it:
@@ -24,6 +25,11 @@
 //                   T[c][c xor t] = +-w X[t] +- w X[t] with ADJL's and ADJR's sign bits (w = weight[S[c] & S[t]]; exactly 0 where the two
 //                   blades anticommute), the same elimination with right-hand side g_c, and the result on the operand's grades.  A
 //                   failed pivot (tested against N eps max |X_i|) or a domain error of the forward (X = NaN) gives NaNs; no count.
+//   k_mv_gsqrt_jvp  the adjoint's mirror: the forward again, then row r of L_X + R_X itself in the N registers, built as the forward
+//                   builds its row of L_M -- column j holds w X[r xor j], once with L's sign bit and once with the bit of the
+//                   right-multiplication matrix R_X[r][j] = coeff(S[j], S[r] xor S[j]) X[r xor j] (same metric factor) -- the same
+//                   elimination with right-hand side h_r, and the result on the wanted blades of S.  It takes GsqrtArgs as they are:
+//                   cot / cot_stride / g_off are the tangent's rows and offsets, neg_r the sign words of R (neg_l is not read).
 // Offsets in int64_t; any row stride (0: one operand shared by every item), padding or alignment takes the same scalar accesses.
 #pragma once
 #include "kernels_gexp.hip.hpp"
@@ -283,6 +289,68 @@ __global__ __launch_bounds__(256, 2) void k_mv_gsqrt_adj(const GsqrtArgs<T> p) {
             T* d = p.res + item * p.res_stride + res_off;
             const T a = sing ? qnan(T(0)) : sh.w[tid];
             *d = (p.beta ? *d : T(0)) + a;
+        }
+    }
+}
+
+template <typename T, int N>
+__global__ __launch_bounds__(256, 2) void k_mv_gsqrt_jvp(const GsqrtArgs<T> p) {
+    using namespace gsqrt_detail;
+    static_assert(N == 2 || N == 4 || N == 8 || N == 16 || N == 32 || N == 64, "one item per N lanes of a wave");
+    constexpr int IPB = 256 / N;
+    __shared__ Shared<T> sh;
+    const int tid = int(threadIdx.x);
+    const int r = tid & (N - 1), g = tid / N, it0 = tid & ~(N - 1);
+    const int lane0 = (tid & 63) & ~(N - 1);
+    if (tid < (1 << p.n)) sh.weight[tid] = p.weight[tid];
+    const int32_t a_off = p.a_off[r], res_off = p.res_off[r], h_off = p.g_off[r];
+    const bool a_neg = ((p.a_neg >> r) & 1ULL) != 0;
+    const uint64_t neg = p.neg[r], neg_m = p.neg_r[r];   // row r of L's signs and of R's
+    const uint32_t e = uint32_t(p.even);
+    const T tol_scale = T(N) * eps_of(T(0));
+    for (int64_t base = int64_t(blockIdx.x) * IPB; base < p.batch; base += int64_t(gridDim.x) * IPB) {
+        const int64_t item = base + g;
+        const bool live = item < p.batch;
+        T v = T(0), hv = T(0);
+        if (live && a_off >= 0) v = p.in[item * p.in_stride + a_off];
+        if (live && h_off >= 0) hv = p.cot[item * p.cot_stride + h_off];
+        if (a_neg) v = -v;
+        bool bad;
+        T x = principal_root<T, N>(sh, v, live, tid, neg, e, &bad);
+        x = bad ? qnan(T(0)) : x;                // (a domain error of the forward: every component of the tangent is NaN by arithmetic)
+        __syncthreads();                         // (the last step's product has read sh.y)
+        sh.y[tid] = x;
+        T amax = abs_m(x);
+#pragma unroll
+        for (int s = N / 2; s >= 1; s >>= 1) {
+            const T o = __shfl_xor(amax, s);
+            amax = (int(o > amax) | int(o != o)) ? o : amax;
+        }
+        __syncthreads();
+        // my row of L_X + R_X, as principal_root builds its row of L_M: (L + R)[r][j] = +-w X[r xor j] (L's sign) +- w X[r xor j] (R's)
+        uint32_t nr = ~uint32_t(r);
+        uint32_t l_lo = uint32_t(neg), l_hi = uint32_t(neg >> 32), m_lo = uint32_t(neg_m), m_hi = uint32_t(neg_m >> 32);
+        asm volatile("" : "+v"(nr), "+v"(l_lo), "+v"(l_hi), "+v"(m_lo), "+v"(m_hi));
+        const uint32_t npar = e & ~uint32_t(__builtin_popcount(~nr)) & 1u;   // e & ~parity(r)
+        const T* const X = sh.y + it0;
+        T row[N];
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const uint32_t idx = ((uint32_t(j) & nr) << e) | ((uint32_t(__builtin_popcount(uint32_t(j))) & 1u) ? npar : 0u);
+            const T wx = sh.weight[idx] * X[(~nr & uint32_t(N - 1)) ^ uint32_t(j)];
+            row[j] = flip_sign(wx, ((j < 32 ? l_lo : l_hi) >> (j & 31)) & 1u) + flip_sign(wx, ((j < 32 ? m_lo : m_hi) >> (j & 31)) & 1u);
+            if ((j & 7) == 7) __builtin_amdgcn_sched_barrier(0);
+        }
+        int col;
+        bool sing;
+        T uc;
+        GAAST_GSQRT_ELIMINATE(row, hv, tol_scale * amax, r, lane0, col, uc, sing)
+        sh.w[it0 + col] = uc;                    // (sh.w: last read before the forward's final barrier or the one above)
+        __syncthreads();
+        if (live && res_off >= 0) {
+            T* d = p.res + item * p.res_stride + res_off;
+            const T u = sing ? qnan(T(0)) : sh.w[tid];
+            *d = (p.beta ? *d : T(0)) + u;
         }
     }
 }

@@ -182,6 +182,8 @@ struct Lowering : LowerState {
         case GAAST_OP_GSQRT_ADJ: lower_gexp_adj(res, id, Step::GSQRT_ADJ, "gsqrt", "the general square root's adjoint", "general_sqrt_adjoint"); return;
         case GAAST_OP_GLOG: lower_gexp(res, id, Step::GLOG, "glog", "the general logarithm", "general_log"); return;
         case GAAST_OP_GLOG_ADJ: lower_gexp_adj(res, id, Step::GLOG_ADJ, "glog", "the general logarithm's adjoint", "general_log_adjoint"); return;
+        case GAAST_OP_GSQRT_JVP: lower_root_log_jvp(res, id, Step::GSQRT_JVP, "gsqrt", "the general square root's tangent", "general_sqrt_jvp"); return;
+        case GAAST_OP_GLOG_JVP: lower_root_log_jvp(res, id, Step::GLOG_JVP, "glog", "the general logarithm's tangent", "general_log_jvp"); return;
         case GAAST_OP_PRODUCT: lower_product(res, id); return;
         default: throw std::runtime_error("unknown opcode");
         }
@@ -240,7 +242,7 @@ struct Lowering : LowerState {
         touch(res);
     }
 
-    // The tables of a step over the blade set S (Step::Inverse: INVERSE, GEXP, GEXP_ADJ, GEXP_JVP, GEXP_ADJ2, GSQRT, GSQRT_ADJ, GLOG, GLOG_ADJ): S itself, where operand row `a` (grades
+    // The tables of a step over the blade set S (Step::Inverse: INVERSE, GEXP, GEXP_ADJ, GEXP_JVP, GEXP_ADJ2, GSQRT, GSQRT_ADJ, GSQRT_JVP, GLOG, GLOG_ADJ, GLOG_JVP): S itself, where operand row `a` (grades
     // `amask`, those of `flip` negated) and result row `res` (grades `produce`) hold its blades, the reordering signs and the metric
     // factors of the left-multiplication matrix.  false: failed (a produced grade is absent from res)
     bool blade_set_tables(Step::Inverse& q, bool even, BufRef a, uint64_t amask, uint64_t flip, BufRef res, uint64_t produce) {
@@ -357,6 +359,8 @@ struct Lowering : LowerState {
     // Reverse mode of the general square root (GAAST_OP_GSQRT_ADJ; Step::GSQRT_ADJ, k_mv_gsqrt_adj) has the same operands and the same
     // tables -- the two transposed sign words are the rows of the transposed L_X + R_X -- and is lowered by the same lines.  So is
     // reverse mode of the general logarithm (GAAST_OP_GLOG_ADJ; Step::GLOG_ADJ, k_mv_glog_adj), which uses the two words one at a time too.
+    // GSQRT_ADJ alone produces its node's grades within the blade set, not only within the operand's grades (gaast_hip.h: the
+    // second-order rule of gsqrt needs every component of the transposed solve); a node with the operand's mask lowers as it always did.
     void lower_gexp_adj(BufRef res, int id, Step::Kind kind, const std::string& op, const char* what, const char* label) {
         const gaast_node_desc& nd = node(id);
         const gaast_node_desc& ch = node(nd.child1);
@@ -385,7 +389,7 @@ struct Lowering : LowerState {
         }
         const Layout &lg = layout(cot), &lr = layout(res);
         Step::Inverse q;
-        if (!blade_set_tables(q, even, a, amask, flip, res, nd.minimal_grade_mask & amask)) return;
+        if (!blade_set_tables(q, even, a, amask, flip, res, nd.minimal_grade_mask & (kind == Step::GSQRT_ADJ ? smask : amask))) return;
         q.wmax = 0.0;
         for (double w : q.weight) q.wmax = std::max(q.wmax, std::fabs(w));
         q.g_off = blade_offsets(q, lg);
@@ -457,6 +461,59 @@ struct Lowering : LowerState {
         Step& s = emit(adj2 ? Step::GEXP_ADJ2 : Step::GEXP_JVP, res, std::string(adj2 ? "general_exponential_adjoint2" : "general_exponential_jvp") + "[" + std::to_string(q.N) + (even ? " even" : "") + " blades, " + std::to_string(q.n_out) + " produced, n=" + std::to_string(n) + "]");
         s.a = a;
         s.b = g;
+        s.c = h;
+        s.canon_a = canon;
+        s.beta = covers ? 0 : 1;
+        s.inv = std::move(q);
+        touch(res);
+    }
+
+    // The tangents of the general square root and logarithm (GAAST_OP_GSQRT_JVP / GAAST_OP_GLOG_JVP, gaast_hip.h; Step::GSQRT_JVP /
+    // Step::GLOG_JVP, k_mv_gsqrt_jvp / k_mv_jvp_glog), always launches of their own.  child1, the forward operand, is read like the
+    // adjoints'; child0, the tangent h (any grades of the blade set), is cached like a product operand.  res += the wanted grades of the
+    // blade set.
+    void lower_root_log_jvp(BufRef res, int id, Step::Kind kind, const std::string& op, const char* what, const char* label) {
+        const gaast_node_desc& nd = node(id);
+        const gaast_node_desc& ch = node(nd.child1);
+        const int n = d.vec_space_dim;
+        if (ch.vec_space_dim != n || nd.vec_space_dim != n || node(nd.child0).vec_space_dim != n) {
+            fail(GAAST_ERR_INVALID_PROGRAM, op + " tangent operand lives in another vector space than the algebra");
+            return;
+        }
+        const uint64_t amask = ch.minimal_grade_mask & ((uint64_t(2) << n) - 1);
+        const bool even = !(amask & 0xAAAAAAAAAAAAAAAAULL);
+        if (blade_set_unsupported(what, even)) return;
+        const uint64_t smask = gs_inverse(amask, n);
+        if (node(nd.child0).minimal_grade_mask & ~smask) {
+            fail(GAAST_ERR_INVALID_PROGRAM, op + " tangent: the tangent holds grades outside the blade set of the operand");
+            return;
+        }
+        int canon = 0;
+        uint64_t flip = 0;
+        BufRef a = operand(nd.child1, &canon, &flip);
+        if (!ok()) return;
+        BufRef h = store_in_cache(nd.child0);
+        if (!ok()) return;
+        if (key(a) == key(res) || key(h) == key(res)) {
+            fail(GAAST_ERR_MISSING_GRADE, op + " tangent operand aliases its own result buffer");
+            return;
+        }
+        const Layout& lr = layout(res);
+        Step::Inverse q;
+        if (!blade_set_tables(q, even, a, amask, flip, res, nd.minimal_grade_mask & smask)) return;
+        q.wmax = 0.0;
+        for (double w : q.weight) q.wmax = std::max(q.wmax, std::fabs(w));
+        q.h_off = blade_offsets(q, layout(h));
+        q.rmul_neg.assign(size_t(q.N), 0);
+        for (int r = 0; r < q.N; ++r)
+            for (int j = 0; j < q.N; ++j)
+                if (reorder_parity(q.blade[size_t(j)], q.blade[size_t(r)] ^ q.blade[size_t(j)])) q.rmul_neg[size_t(r)] |= uint64_t(1) << j;
+        if (!q.n_out) return;
+        const auto fr = fresh.find(key(res));
+        const bool covers = fr != fresh.end() && !(plan.flags & GAAST_FLAG_NO_FUSION) && int64_t(q.n_out) == lr.row_len;
+        if (covers) removed[size_t(fr->second)] = 1;
+        Step& s = emit(kind, res, std::string(label) + "[" + std::to_string(q.N) + (even ? " even" : "") + " blades, " + std::to_string(q.n_out) + " produced, n=" + std::to_string(n) + "]");
+        s.a = a;
         s.c = h;
         s.canon_a = canon;
         s.beta = covers ? 0 : 1;
@@ -951,6 +1008,8 @@ void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab,
         case GAAST_OP_GLOG_ADJ:
         case GAAST_OP_GEXP_JVP:
         case GAAST_OP_GEXP_ADJ2:
+        case GAAST_OP_GSQRT_JVP:
+        case GAAST_OP_GLOG_JVP:
             if (!child_ok(nd.child0) || !child_ok(nd.child1)) throw std::runtime_error("nodes are not in post-order");
             if (nd.opcode == GAAST_OP_GEXP_ADJ2 && !child_ok(nd.input_slot)) throw std::runtime_error("nodes are not in post-order");   // (its third child)
             if (nd.opcode == GAAST_OP_PRODUCT && nd.product_kind >= GAAST_PROD_ADJ_LEFT) {

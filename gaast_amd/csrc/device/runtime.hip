@@ -218,13 +218,13 @@ struct Launch {
         DevTable a_off, res_off, g_off, h_off, neg, neg_l, neg_r, weight;
         const void* kernel = nullptr;   // k_mv_gexp<T, N> / k_mv_gexp_adj<T, N> / k_mv_gexp_jvp<T, N> / k_mv_gexp_adj2<T, N>
     } gexp;
-    struct {   // GSQRT, GSQRT_ADJ
+    struct {   // GSQRT, GSQRT_ADJ, GSQRT_JVP (g_off: the tangent's offsets, neg_r: the sign words of the right-multiplication matrix)
         DevTable a_off, res_off, g_off, neg, neg_l, neg_r, weight;
-        const void* kernel = nullptr;   // k_mv_gsqrt<T, N> / k_mv_gsqrt_adj<T, N>
+        const void* kernel = nullptr;   // k_mv_gsqrt<T, N> / k_mv_gsqrt_adj<T, N> / k_mv_gsqrt_jvp<T, N>
     } gsqrt;
-    struct {   // GLOG, GLOG_ADJ
+    struct {   // GLOG, GLOG_ADJ, GLOG_JVP (as GSQRT_JVP)
         DevTable a_off, res_off, g_off, neg, neg_l, neg_r, weight;
-        const void* kernel = nullptr;   // k_mv_glog<T, N> / k_mv_glog_adj<T, N>
+        const void* kernel = nullptr;   // k_mv_glog<T, N> / k_mv_glog_adj<T, N> / k_mv_jvp_glog<T, N>
     } glog;
     struct {   // PRODUCT_CSR: k_product_csr, k_product_ell, k_product_ell_chain or the specialised gaast_chain
         DevTable row_start, row_out, entries, coeff;
@@ -758,17 +758,21 @@ template <typename T>
 int prepare_gsqrt(Launch& L, std::string& kernel) {
     Step& s = L.s;
     auto& c = L.gsqrt;
-    const bool adj = s.kind == Step::GSQRT_ADJ;
+    const bool adj = s.kind == Step::GSQRT_ADJ, jvp = s.kind == Step::GSQRT_JVP;
     using Kern = void (*)(GsqrtArgs<T>);
-    c.kernel = kernel_address(adj ? static_int<2, 4, 8, 16, 32, 64>(s.inv.N, [](auto n) -> Kern { return k_mv_gsqrt_adj<T, decltype(n)::value>; })
-                                  : static_int<2, 4, 8, 16, 32, 64>(s.inv.N, [](auto n) -> Kern { return k_mv_gsqrt<T, decltype(n)::value>; }));
+    c.kernel = kernel_address(jvp   ? static_int<2, 4, 8, 16, 32, 64>(s.inv.N, [](auto n) -> Kern { return k_mv_gsqrt_jvp<T, decltype(n)::value>; })
+                              : adj ? static_int<2, 4, 8, 16, 32, 64>(s.inv.N, [](auto n) -> Kern { return k_mv_gsqrt_adj<T, decltype(n)::value>; })
+                                    : static_int<2, 4, 8, 16, 32, 64>(s.inv.N, [](auto n) -> Kern { return k_mv_gsqrt<T, decltype(n)::value>; }));
     if (!c.kernel) return set_err(GAAST_ERR_UNIMPLEMENTED, "no general-square-root kernel for " + std::to_string(s.inv.N) + " blades");
     Upload<T> up;
     up.idx(c.a_off, s.inv.a_off); up.idx(c.res_off, s.inv.res_off); up.idx(c.neg, s.inv.neg); up.val(c.weight, s.inv.weight);
     if (adj) {
         up.idx(c.g_off, s.inv.g_off); up.idx(c.neg_l, s.inv.adj_neg_l); up.idx(c.neg_r, s.inv.adj_neg_r);
     }
-    kernel = std::string(adj ? "k_mv_gsqrt_adj<" : "k_mv_gsqrt<") + type_name<T>() + "," + std::to_string(s.inv.N) + ">";
+    if (jvp) {   // (the tangent's offsets and the right-multiplication words travel in the cotangent's and ADJR's places)
+        up.idx(c.g_off, s.inv.h_off); up.idx(c.neg_r, s.inv.rmul_neg);
+    }
+    kernel = std::string(jvp ? "k_mv_gsqrt_jvp<" : adj ? "k_mv_gsqrt_adj<" : "k_mv_gsqrt<") + type_name<T>() + "," + std::to_string(s.inv.N) + ">";
     return up.status;
 }
 
@@ -776,14 +780,14 @@ template <typename T>
 int run_gsqrt(const Launch& L, const Operands& o, int64_t batch) {
     const Step& s = L.s;
     if (batch <= 0) return GAAST_OK;
-    const bool adj = s.kind == Step::GSQRT_ADJ;
+    const bool adj = s.kind == Step::GSQRT_ADJ, jvp = s.kind == Step::GSQRT_JVP;
     GsqrtArgs<T> p;
     p.res = static_cast<T*>(o.res.ptr);
     p.in = static_cast<const T*>(o.a.ptr);
-    p.cot = adj ? static_cast<const T*>(o.b.ptr) : nullptr;
+    p.cot = adj ? static_cast<const T*>(o.b.ptr) : jvp ? static_cast<const T*>(o.c.ptr) : nullptr;
     p.res_stride = o.res.stride;
     p.in_stride = o.a.stride;
-    p.cot_stride = adj ? o.b.stride : 0;
+    p.cot_stride = adj ? o.b.stride : jvp ? o.c.stride : 0;
     p.batch = batch;
     p.a_off = L.gsqrt.a_off.as<int32_t>();
     p.res_off = L.gsqrt.res_off.as<int32_t>();
@@ -808,17 +812,21 @@ template <typename T>
 int prepare_glog(Launch& L, std::string& kernel) {
     Step& s = L.s;
     auto& c = L.glog;
-    const bool adj = s.kind == Step::GLOG_ADJ;
+    const bool adj = s.kind == Step::GLOG_ADJ, jvp = s.kind == Step::GLOG_JVP;
     using Kern = void (*)(GlogArgs<T>);
-    c.kernel = kernel_address(adj ? static_int<2, 4, 8, 16, 32, 64>(s.inv.N, [](auto n) -> Kern { return k_mv_glog_adj<T, decltype(n)::value>; })
-                                  : static_int<2, 4, 8, 16, 32, 64>(s.inv.N, [](auto n) -> Kern { return k_mv_glog<T, decltype(n)::value>; }));
+    c.kernel = kernel_address(jvp   ? static_int<2, 4, 8, 16, 32, 64>(s.inv.N, [](auto n) -> Kern { return k_mv_jvp_glog<T, decltype(n)::value>; })
+                              : adj ? static_int<2, 4, 8, 16, 32, 64>(s.inv.N, [](auto n) -> Kern { return k_mv_glog_adj<T, decltype(n)::value>; })
+                                    : static_int<2, 4, 8, 16, 32, 64>(s.inv.N, [](auto n) -> Kern { return k_mv_glog<T, decltype(n)::value>; }));
     if (!c.kernel) return set_err(GAAST_ERR_UNIMPLEMENTED, "no general-logarithm kernel for " + std::to_string(s.inv.N) + " blades");
     Upload<T> up;
     up.idx(c.a_off, s.inv.a_off); up.idx(c.res_off, s.inv.res_off); up.idx(c.neg, s.inv.neg); up.val(c.weight, s.inv.weight);
     if (adj) {
         up.idx(c.g_off, s.inv.g_off); up.idx(c.neg_l, s.inv.adj_neg_l); up.idx(c.neg_r, s.inv.adj_neg_r);
     }
-    kernel = std::string(adj ? "k_mv_glog_adj<" : "k_mv_glog<") + type_name<T>() + "," + std::to_string(s.inv.N) + ">";
+    if (jvp) {   // (as prepare_gsqrt)
+        up.idx(c.g_off, s.inv.h_off); up.idx(c.neg_r, s.inv.rmul_neg);
+    }
+    kernel = std::string(jvp ? "k_mv_jvp_glog<" : adj ? "k_mv_glog_adj<" : "k_mv_glog<") + type_name<T>() + "," + std::to_string(s.inv.N) + ">";
     return up.status;
 }
 
@@ -826,14 +834,14 @@ template <typename T>
 int run_glog(const Launch& L, const Operands& o, int64_t batch) {
     const Step& s = L.s;
     if (batch <= 0) return GAAST_OK;
-    const bool adj = s.kind == Step::GLOG_ADJ;
+    const bool adj = s.kind == Step::GLOG_ADJ, jvp = s.kind == Step::GLOG_JVP;
     GlogArgs<T> p;
     p.res = static_cast<T*>(o.res.ptr);
     p.in = static_cast<const T*>(o.a.ptr);
-    p.cot = adj ? static_cast<const T*>(o.b.ptr) : nullptr;
+    p.cot = adj ? static_cast<const T*>(o.b.ptr) : jvp ? static_cast<const T*>(o.c.ptr) : nullptr;
     p.res_stride = o.res.stride;
     p.in_stride = o.a.stride;
-    p.cot_stride = adj ? o.b.stride : 0;
+    p.cot_stride = adj ? o.b.stride : jvp ? o.c.stride : 0;
     p.batch = batch;
     p.a_off = L.glog.a_off.as<int32_t>();
     p.res_off = L.glog.res_off.as<int32_t>();
@@ -1789,9 +1797,11 @@ int prepare_launch(Launch& L, const gaast_hip_program_s& prog) {
     case Step::GEXP_JVP:
     case Step::GEXP_ADJ2: st = prepare_gexp2<T>(L, kernel); break;
     case Step::GSQRT:
-    case Step::GSQRT_ADJ: st = prepare_gsqrt<T>(L, kernel); break;
+    case Step::GSQRT_ADJ:
+    case Step::GSQRT_JVP: st = prepare_gsqrt<T>(L, kernel); break;
     case Step::GLOG:
-    case Step::GLOG_ADJ: st = prepare_glog<T>(L, kernel); break;
+    case Step::GLOG_ADJ:
+    case Step::GLOG_JVP: st = prepare_glog<T>(L, kernel); break;
     }
     if (st) return st;
     L.label = kernel.empty() ? s.name : s.name + " :: " + kernel;
@@ -2534,9 +2544,11 @@ int run_launch(const Launch& L, const Operands& o, int64_t batch) {
     case Step::GEXP_JVP:
     case Step::GEXP_ADJ2: st = run_gexp2<T>(L, o, batch); break;
     case Step::GSQRT:
-    case Step::GSQRT_ADJ: st = run_gsqrt<T>(L, o, batch); break;
+    case Step::GSQRT_ADJ:
+    case Step::GSQRT_JVP: st = run_gsqrt<T>(L, o, batch); break;
     case Step::GLOG:
-    case Step::GLOG_ADJ: st = run_glog<T>(L, o, batch); break;
+    case Step::GLOG_ADJ:
+    case Step::GLOG_JVP: st = run_glog<T>(L, o, batch); break;
     }
     L.variant = variant;
     return st;

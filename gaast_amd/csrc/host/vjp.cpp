@@ -36,7 +36,9 @@
 // trilinear form <g, a o b> of the forward kind, the forward product or the other adjoint of the same kind (product_adjoint, table
 // in gaast_expr.h); the adjoint op nodes (GAAST_OP_*_ADJ) are opaque events that are carried along off the path and refused by name
 // on it (their derivative is a Frechet derivative of a matrix function) -- except, under GAAST_FLAG_GEXP_GRAD2, the family of the
-// general exponential {GEXP_ADJ, GEXP_JVP, GEXP_ADJ2}, which has those kernels and is closed up to second order (gexp_family_adjoint).
+// general exponential {GEXP_ADJ, GEXP_JVP, GEXP_ADJ2}, which has those kernels and is closed up to second order (gexp_family_adjoint),
+// and, under GAAST_FLAG_GSQRT_GLOG_JVP, the families {GSQRT_ADJ, GSQRT_JVP}, closed at every order, and {GLOG_ADJ, GLOG_JVP}, closed with
+// respect to child0 alone (root_log_family_adjoint).
 // Buffers are visited from the root down (decreasing node index: a buffer's users come after it in post-order).  The adjoint
 // program is evaluated in place as well, so every cotangent node it builds is ADDITIVE (input, product, or sums of them): adding
 // it into a buffer adds its value.  Sign changes and projections of a cotangent that cannot be folded into a list are explicit
@@ -64,7 +66,7 @@ struct VjpError {
 
 bool has_two_children(int opcode) {
     return opcode == GAAST_OP_ADD || opcode == GAAST_OP_PRODUCT || opcode == GAAST_OP_EXP_ADJ || opcode == GAAST_OP_LOG_ADJ || opcode == GAAST_OP_GEXP_ADJ || opcode == GAAST_OP_GSQRT_ADJ || opcode == GAAST_OP_GLOG_ADJ ||
-           opcode == GAAST_OP_GEXP_JVP || opcode == GAAST_OP_GEXP_ADJ2;
+           opcode == GAAST_OP_GEXP_JVP || opcode == GAAST_OP_GEXP_ADJ2 || opcode == GAAST_OP_GSQRT_JVP || opcode == GAAST_OP_GLOG_JVP;
 }
 // GAAST_OP_GEXP_ADJ2 has a third child, the forward operand: its node index travels in input_slot (gaast_hip.h); -1 for every other node
 int third_child(const gaast_node_desc& nd) { return nd.opcode == GAAST_OP_GEXP_ADJ2 ? nd.input_slot : -1; }
@@ -78,6 +80,8 @@ const char* adjoint_op_name(int opcode) {
     case GAAST_OP_GSQRT_ADJ: return "GAAST_OP_GSQRT_ADJ";
     case GAAST_OP_GLOG_ADJ: return "GAAST_OP_GLOG_ADJ";
     case GAAST_OP_GEXP_JVP: return "GAAST_OP_GEXP_JVP";
+    case GAAST_OP_GSQRT_JVP: return "GAAST_OP_GSQRT_JVP";
+    case GAAST_OP_GLOG_JVP: return "GAAST_OP_GLOG_JVP";
     default: return nullptr;
     }
 }
@@ -312,6 +316,58 @@ struct Builder {
         nd.child1 = c;
         cot[size_t(c)].push_back(Term{add(nd), 0, ~0ULL});
     }
+    // GAAST_FLAG_GSQRT_GLOG_JVP: the cotangents of the operands of a GSQRT_ADJ / GSQRT_JVP / GLOG_ADJ / GLOG_JVP node x (table in
+    // gaast_expr.h).  Each is linear in child0, the tangent map at A or its transpose, so child0's cotangent is the other node of the pair
+    // over (k, A).  For gsqrt the map is S^-1 with S = L_X + R_X, X the root of A:  d(S^-1) = -S^-1 (L_dX + R_dX) S^-1 and dX = S^-1 dA
+    // give the gradient in A of <g, S^-1 h> as -GSQRT_ADJ(ADJ_LEFT(w, u) + ADJ_RIGHT(w, u), A) over geometric products, with
+    // w = GSQRT_ADJ(g, A) and u = GSQRT_JVP(h, A) on every grade of the blade set.  The sign is a Negation of k, the innermost child,
+    // as inv_adjoint places it and for its reason.  For glog the gradient in A is not implemented.
+    void root_log_family_adjoint(int x, const std::vector<Term>& terms, std::vector<std::vector<Term>>& cot) {
+        const gaast_node_desc& xd = d.nodes[x];
+        const bool log = xd.opcode == GAAST_OP_GLOG_ADJ || xd.opcode == GAAST_OP_GLOG_JVP;
+        const bool jvp = xd.opcode == GAAST_OP_GSQRT_JVP || xd.opcode == GAAST_OP_GLOG_JVP;
+        const int op_adj = log ? GAAST_OP_GLOG_ADJ : GAAST_OP_GSQRT_ADJ, op_jvp = log ? GAAST_OP_GLOG_JVP : GAAST_OP_GSQRT_JVP;
+        const int c0 = xd.child0, a = xd.child1;
+        if (log && dep[size_t(a)])
+            throw VjpError{GAAST_ERR_UNIMPLEMENTED, std::string("reverse mode through ") + adjoint_op_name(xd.opcode) + " with respect to its operand is not implemented"};
+        const uint64_t amask = d.nodes[a].minimal_grade_mask, c0mask = d.nodes[c0].minimal_grade_mask;
+        if (!dep[size_t(c0)] && !dep[size_t(a)]) return;
+        const int k = materialize(terms, xd.minimal_grade_mask);
+        if (k < 0 || !amask || !c0mask) return;
+        if (dep[size_t(c0)]) {   // linear in child0: the transposed map at the same A
+            gaast_node_desc nd = blank(jvp ? op_adj : op_jvp, c0mask, n);
+            nd.child0 = k;
+            nd.child1 = a;
+            cot[size_t(c0)].push_back(Term{add(nd), 0, ~0ULL});
+        }
+        if (dep[size_t(a)]) {
+            const uint64_t smask = gs_inverse(amask, n);
+            gaast_node_desc neg = blank(GAAST_OP_NEG, mask_of(k), n);
+            neg.child0 = k;
+            const int nk = add(neg);
+            gaast_node_desc w = blank(GAAST_OP_GSQRT_ADJ, smask, n);   // w = S^-T g
+            w.child0 = jvp ? nk : c0;
+            w.child1 = a;
+            const int wn = add(w);
+            gaast_node_desc u = blank(GAAST_OP_GSQRT_JVP, smask, n);   // u = S^-1 h
+            u.child0 = jvp ? c0 : nk;
+            u.child1 = a;
+            const int un = add(u);
+            const Selection sel{GAAST_PROD_GEOMETRIC, nullptr, nullptr, n};
+            gaast_node_desc l = blank(GAAST_OP_PRODUCT, smask, n);    // cotangent of dX in dX u
+            l.child0 = wn;
+            l.child1 = un;
+            l.product_kind = GAAST_PROD_GEOMETRIC + GAAST_PROD_ADJ_LEFT;
+            l.n_comp_muls = comp_mul_count(n, iter_contribs(smask, sel, smask, smask));
+            gaast_node_desc r = l;                                    // cotangent of dX in u dX
+            r.product_kind = GAAST_PROD_GEOMETRIC + GAAST_PROD_ADJ_RIGHT;
+            const int ln = add(l), rn = add(r);
+            gaast_node_desc out = blank(GAAST_OP_GSQRT_ADJ, amask, n);
+            out.child0 = sum({ln, rn}, smask, n);
+            out.child1 = a;
+            cot[size_t(a)].push_back(Term{add(out), 0, ~0ULL});
+        }
+    }
     // dual / undual: cotangent of the operand's buffer
     void dual_adjoint(int x, const std::vector<Term>& terms, std::vector<std::vector<Term>>& cot) {
         const gaast_node_desc& xd = d.nodes[x];
@@ -518,6 +574,9 @@ struct Builder {
                 case EV_OPAQUE:   // a node whose operand has a buffer of its own
                     if ((d.flags & GAAST_FLAG_GEXP_GRAD2) && (x.opcode == GAAST_OP_GEXP_ADJ || x.opcode == GAAST_OP_GEXP_JVP)) {
                         gexp_family_adjoint(e.node, terms, cot);   // (the family is closed up to second order)
+                    } else if ((d.flags & GAAST_FLAG_GSQRT_GLOG_JVP) && (x.opcode == GAAST_OP_GSQRT_ADJ || x.opcode == GAAST_OP_GSQRT_JVP ||
+                                                                          x.opcode == GAAST_OP_GLOG_ADJ || x.opcode == GAAST_OP_GLOG_JVP)) {
+                        root_log_family_adjoint(e.node, terms, cot);   // (gsqrt: closed at every order; glog: with respect to child0)
                     } else if (x.opcode == GAAST_OP_GEXP_ADJ2) {
                         if (dep[size_t(e.node)]) gexp_family_adjoint(e.node, terms, cot);   // (refused, with or without the flag)
                     } else if (const char* name = adjoint_op_name(x.opcode)) {   // its second derivative needs a Frechet-derivative kernel
@@ -582,7 +641,7 @@ extern "C" int gaast_program_vjp(const gaast_program_desc* desc, int32_t wrt_slo
         const gaast_node_desc& nd = d.nodes[i];
         const bool two = has_two_children(nd.opcode);
         const bool ok = nd.opcode == GAAST_OP_INPUT ? (nd.input_slot >= 0 && nd.input_slot < d.n_inputs)
-                        : (nd.opcode > GAAST_OP_INPUT && nd.opcode <= GAAST_OP_GEXP_ADJ2 &&
+                        : (nd.opcode > GAAST_OP_INPUT && nd.opcode <= GAAST_OP_GLOG_JVP &&
                            nd.child0 >= 0 && nd.child0 < i &&
                            (!two || (nd.child1 >= 0 && nd.child1 < i)) &&
                            (nd.opcode != GAAST_OP_GEXP_ADJ2 || (nd.input_slot >= 0 && nd.input_slot < i)));

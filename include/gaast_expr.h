@@ -215,10 +215,28 @@ void gaast_program_image_free(gaast_program_image_t img);
  * VJP with respect to its cotangent holds GEXP_JVP and never reads the first cotangent) and the transpose of forward mode all work
  * through gexp.  Without the flag GEXP_ADJ on the path is refused as before and GEXP_JVP in the same words; a forward image is the
  * same with and without the flag, a first-order image differs in its flags word only.
+ * Forward mode through the general square root and logarithm, any order through the root (OPT-IN: GAAST_FLAG_GSQRT_GLOG_JVP, read and
+ * inherited like GAAST_FLAG_GEXP_GRAD2; GAAST_OP_GSQRT_JVP and GAAST_OP_GLOG_JVP are two-child nodes like GAAST_OP_GEXP_JVP, no third
+ * child).  Both adjoint nodes are linear in their cotangent, so its derivative is the transposed map, the tangent of the forward at
+ * the same operand.  With k as above, S = L_X + R_X at the root X of A, w and u on every grade of the blade set:
+ *     node on the path          through   its operand's cotangent
+ *     GSQRT_ADJ(g, A)           g         GSQRT_JVP(k, A), mask of g
+ *     GSQRT_ADJ(g, A)           A         -GSQRT_ADJ(ADJ_LEFT(w, u) + ADJ_RIGHT(w, u), A), w = GSQRT_ADJ(g, A), u = GSQRT_JVP(k, A)
+ *     GSQRT_JVP(h, A)           h         GSQRT_ADJ(k, A), mask of h
+ *     GSQRT_JVP(h, A)           A         the same expression with w = GSQRT_ADJ(k, A), u = GSQRT_JVP(h, A)
+ *     GLOG_ADJ(g, A)            g         GLOG_JVP(k, A), mask of g
+ *     GLOG_JVP(h, A)            h         GLOG_ADJ(k, A), mask of h
+ *     GLOG_ADJ / GLOG_JVP       A         GAAST_ERR_UNIMPLEMENTED ("reverse mode through GAAST_OP_GLOG_ADJ with respect to its operand ...")
+ * The operand rule is the gradient in A of <g, S^-1 h>: d(S^-1) = -S^-1 (L_dX + R_dX) S^-1 and dX = S^-1 dA.  ADJ_LEFT / ADJ_RIGHT are
+ * compact geometric adjoint products, the sign one GAAST_OP_NEG on k (the innermost child, as for GAAST_OP_INV); every node is one
+ * the function emits elsewhere, so the family of gsqrt is closed at EVERY order.  A GLOG node is refused only when its operand
+ * depends on wrt_slot; reached through child0 alone (forward mode) it is accepted.  Without the flag all four nodes on the path are
+ * refused in the words of the five adjoint op nodes below, and images are what they were.
  * Errors: GAAST_ERR_INVALID_ARGUMENT for a wrt_slot out of range or const, or n_inputs + 1 > GAAST_MAX_INPUTS;
  * GAAST_ERR_UNIMPLEMENTED for one of the five adjoint op nodes on the path to wrt_slot, through either child (the message names the
  * op: the second derivative of these matrix functions needs Frechet-derivative kernels, which the library has for gexp alone and
- * uses under GAAST_FLAG_GEXP_GRAD2), and for GAAST_OP_GEXP_ADJ2 on the path (third order);
+ * uses under GAAST_FLAG_GEXP_GRAD2; under GAAST_FLAG_GSQRT_GLOG_JVP gsqrt's node is differentiated by composition and glog's with
+ * respect to its cotangent), and for GAAST_OP_GEXP_ADJ2 on the path (third order);
  * GAAST_ERR_UNIMPLEMENTED for GAAST_FLAG_SPINOR_GEMM, and for exp / log on the path to wrt_slot unless desc->flags holds both
  * GAAST_FLAG_EXP_LOG and GAAST_FLAG_EXP_LOG_GRAD: then the operand's cotangent is a GAAST_OP_EXP_ADJ / GAAST_OP_LOG_ADJ node
  * (gaast_hip.h) over the cotangent of the exp / log node's buffer and the forward operand (exp of a bare scalar, grade set {0},

@@ -192,7 +192,9 @@ typedef enum gaast_opcode {
      * two blades anticommute); it is nonsingular whenever X is a principal root, no two eigenvalues of L_X summing to zero.  The
      * forward is recomputed, the system solved by GAAST_OP_INV's elimination.  A failed pivot test of this solve makes every
      * component of the item's cotangent NaN; it is not counted, and neither is a domain-error item of the recomputed forward, whose
-     * cotangent is NaN likewise. */
+     * cotangent is NaN likewise.  (A node whose own mask holds grades of S beyond the operand's produces those too -- the solution is
+     * then restricted to the node's mask within S, not to the operand's grades: see GAAST_OP_GSQRT_JVP below, whose second-order rule
+     * emits such nodes.  A node with the operand's mask, the only kind first-order reverse mode emits, is restricted as stated.) */
     GAAST_OP_GSQRT_ADJ = 19,
     /* General multivector logarithm (no reference counterpart): glog(A) is the PRINCIPAL logarithm, the Y with gexp(Y) = A whose
      * left-multiplication matrix L_Y has every eigenvalue in the strip |Im| < pi.  It exists and is unique when L_A is nonsingular
@@ -275,7 +277,37 @@ typedef enum gaast_opcode {
      * Accuracy of both, per item that is no domain error, against these recurrences in extended precision: 4 JVP_SCALE in units
      * of N eps max(1, theta) ||h||_inf ||exp A||_inf, and 4 ADJ2_SCALE in units of N eps max(1, theta) ||g||_inf ||h||_inf
      * ||exp A||_inf (tests/gexp2_numpy.py records the scales: the worst error of a numpy restatement in the program's dtype). */
-    GAAST_OP_GEXP_ADJ2 = 23
+    GAAST_OP_GEXP_ADJ2 = 23,
+    /* The tangent of GAAST_OP_GSQRT at A in direction h, the transpose of GAAST_OP_GSQRT_ADJ's map.  Emitted by gaast_program_vjp under
+     * GAAST_FLAG_GSQRT_GLOG_JVP; evaluating the node needs no flag.  child0 = the tangent h, which may hold any grades of the blade
+     * set S of the operand (absent blades read as 0; grades outside S: GAAST_ERR_INVALID_PROGRAM); child1 = the forward operand A.
+     * The node produces its own minimal grade mask within the grades of S; it ADDS into its buffer.  No third child.
+     * With X the principal root of A, recomputed exactly as GAAST_OP_GSQRT_ADJ recomputes it (the same iteration, the same domain
+     * rule), the result is the u with  (L_X + R_X) u = h,  that is  X u + u X = h:  row r of the system has at column j the value
+     * w X[r xor j], w the metric factor of GAAST_OP_INV's L[r][j], once with the sign of L[r][j] = coeff(S[r] xor S[j], S[j]) and once
+     * with the sign of the right-multiplication matrix R_X[r][j] = coeff(S[j], S[r] xor S[j]) X[r xor j].  One run of GAAST_OP_INV's
+     * elimination, the pivot test !(|p| > N eps max_i |X_i|) of GAAST_OP_GSQRT_ADJ.  <g, GSQRT_JVP(h, A)> = <GSQRT_ADJ(g, A), h>.
+     * No domain check and no count: a domain-error item of the recomputed forward, or a failed pivot, gives NaN in every produced
+     * component.  Supported sizes are GAAST_OP_GSQRT's.  Accuracy, per item that is no domain error, against the same solve in
+     * extended precision: 4 SQRT_JVP_SCALE in units of N eps kappa_inf(L_X + R_X) ||u||_inf (tests/root_log_jvp_numpy.py records
+     * the scales: the worst error of a numpy restatement in the program's dtype).
+     * A GAAST_OP_GSQRT_ADJ node whose own mask holds grades of S that the operand does not hold produces those too (its mask within
+     * the grades of S, not within the operand's): the second-order rule of gaast_expr.h needs every component of the transposed
+     * solve.  Every such node gaast_program_vjp emitted before that rule has the operand's mask, so nothing changes for those.
+     * GAAST_OP_GEXP_ADJ and GAAST_OP_GLOG_ADJ keep the restriction to the operand's grades. */
+    GAAST_OP_GSQRT_JVP = 24,
+    /* The tangent of GAAST_OP_GLOG at A in direction h, the transpose of GAAST_OP_GLOG_ADJ's map; children, masks, flag and sizes as
+     * GAAST_OP_GSQRT_JVP states them (sizes: GAAST_OP_GLOG's).  The roots X_1 ... X_s and s are taken from A alone, exactly as
+     * GAAST_OP_GLOG_ADJ takes them, and held fixed.  Then
+     *   t_0 = h;   (L_(X_i) + R_(X_i)) t_i = t_(i-1)  for i = 1 ... s, GAAST_OP_GSQRT_JVP's system at X_i;
+     *   with E = X_s - e_0 and M_j = e_0 + beta_j E:  L_(M_j) p_j = t_s, then R_(M_j) q_j = p_j, for j = 1 ... 7
+     *     (q_j = M_j^-1 t_s M_j^-1, the derivative of M_j^-1 E, since E commutes with M_j);
+     *   the result is 2^s sum_j alpha_j q_j (j ascending; the factor is exact).
+     * 14 non-transposed solves and s Sylvester solves: GAAST_OP_GLOG_ADJ read backwards.  Every solve is GAAST_OP_INV's elimination
+     * with GAAST_OP_GLOG_ADJ's pivot tests.  <g, GLOG_JVP(h, A)> = <GLOG_ADJ(g, A), h>.  No domain check and no count: a domain-error
+     * item of the recomputed forward, or a failed pivot, gives NaN in every produced component.  Accuracy: 4 LOG_JVP_SCALE in units
+     * of N eps max(1, sum_i |(log A)_i|) ||J||_inf ||h||_inf (tests/root_log_jvp_numpy.py). */
+    GAAST_OP_GLOG_JVP = 25
 } gaast_opcode;
 
 /* the five products of src/ast/expr.rs:180-197 (and the regressive product), for compact PRODUCT descriptors */
@@ -378,6 +410,15 @@ typedef struct gaast_input_desc {
  * plan, launch name and bit is what it was before the flag existed.  The flag changes nothing in a forward program, and in a
  * first-order VJP image only the flags word. */
 #define GAAST_FLAG_GEXP_GRAD2 0x4000u
+/* OPT-IN: gaast_program_vjp differentiates THROUGH the adjoint nodes of the general square root and logarithm.  A GAAST_OP_GSQRT_ADJ
+ * or GAAST_OP_GSQRT_JVP node on the path to the differentiated input gets GAAST_OP_GSQRT_JVP / GAAST_OP_GSQRT_ADJ nodes and adjoint
+ * products (table in gaast_expr.h): forward mode and reverse mode of any order through gsqrt.  A GAAST_OP_GLOG_ADJ or
+ * GAAST_OP_GLOG_JVP node reached through child0 alone gets GAAST_OP_GLOG_JVP / GAAST_OP_GLOG_ADJ: forward mode through glog; one
+ * whose operand depends on the differentiated input stays GAAST_ERR_UNIMPLEMENTED.  Only gaast_program_vjp reads the flag; the
+ * adjoint program inherits it like every flag.  Without it such a node stays GAAST_ERR_UNIMPLEMENTED, and every status, message,
+ * plan, launch name and bit is what it was before the flag existed.  The flag changes nothing in a forward program, and in a
+ * first-order VJP image only the flags word. */
+#define GAAST_FLAG_GSQRT_GLOG_JVP 0x8000u
 #define GAAST_FLAG_DEBUG_LDS_12K 0x400u /* hiprtc-specialised kernels: 12 KiB instead of 10 KiB of LDS per wave for the row transposition (A/B testing) */
 #define GAAST_FLAG_DEBUG_NO_CHAIN 0x800u /* a sparse product that only feeds a dense product stays a launch of its own (default: evaluated in the dense kernel's LDS staging; A/B testing) */
 /* (bits 30 and 31 are reserved and ignored) */
@@ -626,7 +667,8 @@ int gaast_hip_eval_gather(gaast_hip_program_t prog, const gaast_hip_mv_t *inputs
  * products of dense geometric products run on the forward's dense kernels at every order.  One of the adjoint op nodes
  * (GAAST_OP_EXP_ADJ, LOG_ADJ, GEXP_ADJ, GSQRT_ADJ, GLOG_ADJ) on the path to wrt_slot: GAAST_ERR_UNIMPLEMENTED -- except GEXP_ADJ (and
  * GEXP_JVP) when desc->flags holds GAAST_FLAG_GEXP_GRAD2: second order and forward mode through gexp (gaast_expr.h has the table);
- * a GAAST_OP_GEXP_ADJ2 node on the path, third order, is GAAST_ERR_UNIMPLEMENTED. */
+ * a GAAST_OP_GEXP_ADJ2 node on the path, third order, is GAAST_ERR_UNIMPLEMENTED.  GSQRT_ADJ / GSQRT_JVP (any order) and GLOG_ADJ /
+ * GLOG_JVP (through child0: forward mode) differentiate when desc->flags holds GAAST_FLAG_GSQRT_GLOG_JVP. */
 int gaast_hip_program_create_vjp(const gaast_program_desc *desc, int32_t wrt_slot, gaast_hip_program_t *out);
 /* gaast_program_vjp followed by gaast_hip_program_create_in_basis: the VJP of a program in a non-diagonal metric.  With the orthogonal
  * Q of the basis change, y_e = C(Q) F(C(Q^T) x_e) and every C_k(Q) is orthogonal, so the VJP of the in-basis program is the in-basis
