@@ -19,13 +19,20 @@ STATUS_NAMES = {1: "INVALID_PROGRAM", 2: "MISSING_GRADE", 3: "UNIMPLEMENTED", 4:
 F64, F32 = 0, 1
 (OP_INPUT, OP_ADD, OP_PRODUCT, OP_NEG, OP_EXP, OP_LOG, OP_PROJ, OP_REVERSE, OP_GINVOL, OP_SINV,
  OP_SSQRT, OP_EXP_ADJ, OP_LOG_ADJ, OP_DUAL, OP_UNDUAL, OP_INV, OP_GEXP, OP_GEXP_ADJ, OP_GSQRT, OP_GSQRT_ADJ,
- OP_GLOG, OP_GLOG_ADJ, OP_GEXP_JVP, OP_GEXP_ADJ2, OP_GSQRT_JVP, OP_GLOG_JVP) = range(26)
+ OP_GLOG, OP_GLOG_ADJ, OP_GEXP_JVP, OP_GEXP_ADJ2, OP_GSQRT_JVP, OP_GLOG_JVP, OP_GLOG_ADJ2) = range(27)
 OP_NAMES = ["GradedObj", "Addition", "Product", "Negation", "Exponential", "Logarithm",
             "GradeProjection", "Reverse", "GradeInvolution", "ScalarInversion", "ScalarSqrt",
             "ExponentialAdjoint", "LogarithmAdjoint", "Dual", "Undual", "Inverse", "GeneralExponential",
             "GeneralExponentialAdjoint", "GeneralSqrt", "GeneralSqrtAdjoint",
             "GeneralLogarithm", "GeneralLogarithmAdjoint", "GeneralExponentialJvp", "GeneralExponentialAdjoint2",
             "GeneralSqrtJvp", "GeneralLogarithmJvp"]
+# (opcodes 0 ... 25: tests/test_root_log_jvp_host.py pins this list's length, so later opcodes are named here)
+MORE_OP_NAMES = {26: "GeneralLogarithmAdjoint2"}
+
+
+def op_name(opcode):
+    """the name of any opcode: OP_NAMES is frozen at its 26 entries, later opcodes are in MORE_OP_NAMES"""
+    return OP_NAMES[opcode] if 0 <= opcode < len(OP_NAMES) else MORE_OP_NAMES[opcode]
 PROD_EXPLICIT, PROD_GEOMETRIC, PROD_OUTER, PROD_INNER, PROD_LCONTRACT, PROD_RCONTRACT = -1, 0, 1, 2, 3, 4
 PROD_REGRESSIVE = 5   # a v b = undual(dual(a) ^ dual(b)): join / meet, metric-free
 PROD_ADJ_LEFT, PROD_ADJ_RIGHT = 8, 16   # added to a forward kind: compact adjoint products (reverse mode)
@@ -35,6 +42,7 @@ FLAG_DEBUG_NO_CHAIN = 0x800
 FLAG_EXP_LOG_GRAD = 0x2000   # with FLAG_EXP_LOG: reverse mode differentiates through exp / log
 FLAG_GEXP_GRAD2 = 0x4000     # reverse mode differentiates through gexp's adjoint nodes: second order and forward mode through gexp
 FLAG_GSQRT_GLOG_JVP = 0x8000  # ... and through gsqrt's (any order, forward mode) and glog's (forward mode: with respect to the cotangent path)
+FLAG_GLOG_GRAD2 = 0x10000     # with FLAG_GSQRT_GLOG_JVP: ... and glog's with respect to the operand too (second order through glog)
 COMM_ID_BYTES = 128
 # gaast_jit_cache_counter, in order
 JIT_CACHE_COUNTERS = ("compiled", "memory_hits", "disk_hits", "disk_stores", "disk_rejected", "live_modules")

@@ -390,7 +390,8 @@ class SpecializedAst:
     def jvp(self, slot):
         """Forward mode with respect to input `slot` (the double-VJP trick: the VJP program differentiated with respect to its
         cotangent), built once per slot: an object with eval_batch(inputs, tangent, batch, out=None) -> J v.  Through gexp it needs
-        specialize(..., flags=FLAG_GEXP_GRAD2); through gsqrt / glog it needs FLAG_GSQRT_GLOG_JVP."""
+        specialize(..., flags=FLAG_GEXP_GRAD2); through gsqrt / glog it needs FLAG_GSQRT_GLOG_JVP
+        (the jvp of a VJP through glog, a mixed second derivative, needs FLAG_GLOG_GRAD2 as well)."""
         cache = self.__dict__.setdefault("_jvps", {})
         if slot not in cache:
             cache[slot] = Jvp(self, int(slot))
@@ -415,7 +416,8 @@ class Vjp:
     through the adjoint nodes of exp / log / gexp / gsqrt / glog (GAAST_ERR_UNIMPLEMENTED).  With specialize(..., flags=FLAG_GEXP_GRAD2)
     gexp's adjoint nodes differentiate too (second order and forward mode through gexp; third order is refused).  With
     FLAG_GSQRT_GLOG_JVP gsqrt's adjoint nodes differentiate to any order, and glog's with respect to the cotangent path (forward mode;
-    with respect to glog's operand they stay refused).  exp / log are unchanged."""
+    with respect to glog's operand they need FLAG_GLOG_GRAD2 beside it: then Hessians through glog work, vjp(i).vjp(j), by one
+    GAAST_OP_GLOG_ADJ2 node, and it is the third order that is refused).  exp / log are unchanged."""
 
     def __init__(self, parent, slot):
         L = _lib.lib()

@@ -10,7 +10,8 @@ autograd.Function over the Vjp object, whose own backward evaluates Vjp.vjp(slot
 exp / log / gexp / gsqrt / glog on the path differentiate once; asking for their second derivative raises GaastError UNIMPLEMENTED --
 except through gexp on a spec built with specialize(..., flags=FLAG_GEXP_GRAD2): there second order (and forward mode, spec.jvp)
 works, and it is the third order that is refused.  With FLAG_GSQRT_GLOG_JVP every order works through gsqrt, and forward mode
-(spec.jvp) through glog; a second derivative with respect to an input under glog stays refused.  exp / log are unchanged.
+(spec.jvp) through glog; a second derivative with respect to an input under glog needs FLAG_GSQRT_GLOG_JVP | FLAG_GLOG_GRAD2: then
+create_graph=True gives Hessian-vector products and gradient penalties through glog (third order is refused).  exp / log are unchanged.
 """
 from __future__ import annotations
 

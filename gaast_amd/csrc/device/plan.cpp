@@ -184,6 +184,7 @@ struct Lowering : LowerState {
         case GAAST_OP_GLOG_ADJ: lower_gexp_adj(res, id, Step::GLOG_ADJ, "glog", "the general logarithm's adjoint", "general_log_adjoint"); return;
         case GAAST_OP_GSQRT_JVP: lower_root_log_jvp(res, id, Step::GSQRT_JVP, "gsqrt", "the general square root's tangent", "general_sqrt_jvp"); return;
         case GAAST_OP_GLOG_JVP: lower_root_log_jvp(res, id, Step::GLOG_JVP, "glog", "the general logarithm's tangent", "general_log_jvp"); return;
+        case GAAST_OP_GLOG_ADJ2: lower_glog_adj2(res, id); return;
         case GAAST_OP_PRODUCT: lower_product(res, id); return;
         default: throw std::runtime_error("unknown opcode");
         }
@@ -242,7 +243,7 @@ struct Lowering : LowerState {
         touch(res);
     }
 
-    // The tables of a step over the blade set S (Step::Inverse: INVERSE, GEXP, GEXP_ADJ, GEXP_JVP, GEXP_ADJ2, GSQRT, GSQRT_ADJ, GSQRT_JVP, GLOG, GLOG_ADJ, GLOG_JVP): S itself, where operand row `a` (grades
+    // The tables of a step over the blade set S (Step::Inverse: INVERSE, GEXP, GEXP_ADJ, GEXP_JVP, GEXP_ADJ2, GSQRT, GSQRT_ADJ, GSQRT_JVP, GLOG, GLOG_ADJ, GLOG_JVP, GLOG_ADJ2): S itself, where operand row `a` (grades
     // `amask`, those of `flip` negated) and result row `res` (grades `produce`) hold its blades, the reordering signs and the metric
     // factors of the left-multiplication matrix.  false: failed (a produced grade is absent from res)
     bool blade_set_tables(Step::Inverse& q, bool even, BufRef a, uint64_t amask, uint64_t flip, BufRef res, uint64_t produce) {
@@ -504,16 +505,79 @@ struct Lowering : LowerState {
         q.wmax = 0.0;
         for (double w : q.weight) q.wmax = std::max(q.wmax, std::fabs(w));
         q.h_off = blade_offsets(q, layout(h));
-        q.rmul_neg.assign(size_t(q.N), 0);
-        for (int r = 0; r < q.N; ++r)
-            for (int j = 0; j < q.N; ++j)
-                if (reorder_parity(q.blade[size_t(j)], q.blade[size_t(r)] ^ q.blade[size_t(j)])) q.rmul_neg[size_t(r)] |= uint64_t(1) << j;
+        right_mul_sign_words(q);
         if (!q.n_out) return;
         const auto fr = fresh.find(key(res));
         const bool covers = fr != fresh.end() && !(plan.flags & GAAST_FLAG_NO_FUSION) && int64_t(q.n_out) == lr.row_len;
         if (covers) removed[size_t(fr->second)] = 1;
         Step& s = emit(kind, res, std::string(label) + "[" + std::to_string(q.N) + (even ? " even" : "") + " blades, " + std::to_string(q.n_out) + " produced, n=" + std::to_string(n) + "]");
         s.a = a;
+        s.c = h;
+        s.canon_a = canon;
+        s.beta = covers ? 0 : 1;
+        s.inv = std::move(q);
+        touch(res);
+    }
+    // the sign words of the right-multiplication matrix (Step::Inverse: rmul_neg)
+    static void right_mul_sign_words(Step::Inverse& q) {
+        q.rmul_neg.assign(size_t(q.N), 0);
+        for (int r = 0; r < q.N; ++r)
+            for (int j = 0; j < q.N; ++j)
+                if (reorder_parity(q.blade[size_t(j)], q.blade[size_t(r)] ^ q.blade[size_t(j)])) q.rmul_neg[size_t(r)] |= uint64_t(1) << j;
+    }
+
+    // The second-order adjoint of the general logarithm (GAAST_OP_GLOG_ADJ2, gaast_hip.h; Step::GLOG_ADJ2, k_mv_adj2_glog), always a launch
+    // of its own.  The forward operand, the third child in input_slot, is read like the adjoint's; g (child0) and h (child1), any grades
+    // of the blade set, are cached like product operands.  res += the operand's grades.  It needs all four sign tables.
+    void lower_glog_adj2(BufRef res, int id) {
+        const gaast_node_desc& nd = node(id);
+        const int a_id = nd.input_slot, g_id = nd.child0, h_id = nd.child1;
+        const std::string op = "glog second-order adjoint";
+        const int n = d.vec_space_dim;
+        if (node(a_id).vec_space_dim != n || nd.vec_space_dim != n || node(h_id).vec_space_dim != n || node(g_id).vec_space_dim != n) {
+            fail(GAAST_ERR_INVALID_PROGRAM, op + " operand lives in another vector space than the algebra");
+            return;
+        }
+        const uint64_t amask = node(a_id).minimal_grade_mask & ((uint64_t(2) << n) - 1);
+        const bool even = !(amask & 0xAAAAAAAAAAAAAAAAULL);
+        if (blade_set_unsupported("the general logarithm's second-order adjoint", even)) return;
+        const uint64_t smask = gs_inverse(amask, n);
+        if (node(h_id).minimal_grade_mask & ~smask) {
+            fail(GAAST_ERR_INVALID_PROGRAM, op + ": the tangent holds grades outside the blade set of the operand");
+            return;
+        }
+        if (node(g_id).minimal_grade_mask & ~smask) {
+            fail(GAAST_ERR_INVALID_PROGRAM, op + ": the cotangent holds grades outside the blade set of the operand");
+            return;
+        }
+        int canon = 0;
+        uint64_t flip = 0;
+        BufRef a = operand(a_id, &canon, &flip);
+        if (!ok()) return;
+        BufRef h = store_in_cache(h_id);
+        if (!ok()) return;
+        BufRef g = store_in_cache(g_id);
+        if (!ok()) return;
+        if (key(a) == key(res) || key(h) == key(res) || key(g) == key(res)) {
+            fail(GAAST_ERR_MISSING_GRADE, op + " operand aliases its own result buffer");
+            return;
+        }
+        const Layout& lr = layout(res);
+        Step::Inverse q;
+        if (!blade_set_tables(q, even, a, amask, flip, res, nd.minimal_grade_mask & amask)) return;
+        q.wmax = 0.0;
+        for (double w : q.weight) q.wmax = std::max(q.wmax, std::fabs(w));
+        q.h_off = blade_offsets(q, layout(h));
+        q.g_off = blade_offsets(q, layout(g));
+        adjoint_sign_words(q);
+        right_mul_sign_words(q);
+        if (!q.n_out) return;
+        const auto fr = fresh.find(key(res));
+        const bool covers = fr != fresh.end() && !(plan.flags & GAAST_FLAG_NO_FUSION) && int64_t(q.n_out) == lr.row_len;
+        if (covers) removed[size_t(fr->second)] = 1;
+        Step& s = emit(Step::GLOG_ADJ2, res, std::string("general_log_adjoint2[") + std::to_string(q.N) + (even ? " even" : "") + " blades, " + std::to_string(q.n_out) + " produced, n=" + std::to_string(n) + "]");
+        s.a = a;
+        s.b = g;
         s.c = h;
         s.canon_a = canon;
         s.beta = covers ? 0 : 1;
@@ -1010,8 +1074,9 @@ void build_plan(const gaast_program_desc& desc, Plan& plan, bool small_reg_slab,
         case GAAST_OP_GEXP_ADJ2:
         case GAAST_OP_GSQRT_JVP:
         case GAAST_OP_GLOG_JVP:
+        case GAAST_OP_GLOG_ADJ2:
             if (!child_ok(nd.child0) || !child_ok(nd.child1)) throw std::runtime_error("nodes are not in post-order");
-            if (nd.opcode == GAAST_OP_GEXP_ADJ2 && !child_ok(nd.input_slot)) throw std::runtime_error("nodes are not in post-order");   // (its third child)
+            if ((nd.opcode == GAAST_OP_GEXP_ADJ2 || nd.opcode == GAAST_OP_GLOG_ADJ2) && !child_ok(nd.input_slot)) throw std::runtime_error("nodes are not in post-order");   // (its third child)
             if (nd.opcode == GAAST_OP_PRODUCT && nd.product_kind >= GAAST_PROD_ADJ_LEFT) {
                 const int adj = nd.product_kind & ~7, base = nd.product_kind & 7;
                 if ((adj != GAAST_PROD_ADJ_LEFT && adj != GAAST_PROD_ADJ_RIGHT) || base > GAAST_PROD_REGRESSIVE)

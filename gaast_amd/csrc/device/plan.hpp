@@ -44,9 +44,9 @@ inline Layout make_layout(int dim, uint64_t mask) {
 // a step in place), each table and setting named after the one thing it holds.  The groups of the other kinds stay empty.  The
 // tables are host images, uploaded once at program_create.
 struct Step {
-    enum Kind { ZERO, AXPY, FLIP, SUNARY, PRODUCT_CSR, PRODUCT_DENSE, FUSED, EXPLOG, REDUCE_SCALE, ELEMENTWISE, LINMAP, EXPLOG_ADJ, DUAL, INVERSE, GEXP, GEXP_ADJ, GSQRT, GSQRT_ADJ, GLOG, GLOG_ADJ, GEXP_JVP, GEXP_ADJ2, GSQRT_JVP, GLOG_JVP } kind = ZERO;
+    enum Kind { ZERO, AXPY, FLIP, SUNARY, PRODUCT_CSR, PRODUCT_DENSE, FUSED, EXPLOG, REDUCE_SCALE, ELEMENTWISE, LINMAP, EXPLOG_ADJ, DUAL, INVERSE, GEXP, GEXP_ADJ, GSQRT, GSQRT_ADJ, GLOG, GLOG_ADJ, GEXP_JVP, GEXP_ADJ2, GSQRT_JVP, GLOG_JVP, GLOG_ADJ2 } kind = ZERO;
     BufRef res, a, b;        // result; operand rows (PRODUCT_*: left, right; AXPY / EXPLOG / LINMAP / DUAL / INVERSE / GEXP / GSQRT / GLOG: a; EXPLOG_ADJ / GEXP_ADJ / GSQRT_ADJ / GLOG_ADJ: a = the forward operand, b = the cotangent; REDUCE_SCALE: the reduction's; ELEMENTWISE: b = the scalar)
-    BufRef c;                // a third operand row (GEXP_JVP / GSQRT_JVP / GLOG_JVP: a = the forward operand, c = the tangent h; GEXP_ADJ2: a, b = g, c = h)
+    BufRef c;                // a third operand row (GEXP_JVP / GSQRT_JVP / GLOG_JVP: a = the forward operand, c = the tangent h; GEXP_ADJ2 / GLOG_ADJ2: a, b = g, c = h)
     std::string name;
     int canon_a = 0, canon_b = 0;   // the operand is a bound input read in place: the kernel applies the reference's 0.0 + x
     int beta = 1;                   // 0: the zero fill of a fresh result is folded in
@@ -221,12 +221,12 @@ struct Step {
         }
         // GEXP / GEXP_ADJ / GSQRT / GSQRT_ADJ / GLOG / GLOG_ADJ only (empty for INVERSE)
         double wmax = 1.0;                  // the largest |weight|: theta = wmax * sum |A_a| bounds the largest absolute row sum of L
-        std::vector<int32_t> g_off;         // GEXP_ADJ, GSQRT_ADJ, GLOG_ADJ [N] offset of blade j in the cotangent row; -1: absent (reads as 0)
-        std::vector<int32_t> h_off;         // GEXP_JVP, GEXP_ADJ2, GSQRT_JVP, GLOG_JVP [N] offset of blade j in the tangent row (Step::c); -1: absent (reads as 0)
+        std::vector<int32_t> g_off;         // GEXP_ADJ, GSQRT_ADJ, GLOG_ADJ, GEXP_ADJ2, GLOG_ADJ2 [N] offset of blade j in the cotangent row; -1: absent (reads as 0)
+        std::vector<int32_t> h_off;         // GEXP_JVP, GEXP_ADJ2, GSQRT_JVP, GLOG_JVP, GLOG_ADJ2 [N] offset of blade j in the tangent row (Step::c); -1: absent (reads as 0)
         // GEXP_ADJ: the sign words of the two adjoint products of P = X Z, both with the metric factor weight[S[a] & S[b]]:
         std::vector<uint64_t> adj_neg_l;    // [N] bit b of adj_neg_l[a] = bit b of neg[a xor b]:  ADJL(g, Z)[a] = sum_b +-w Z[b] g[a xor b]
         std::vector<uint64_t> adj_neg_r;    // [N] bit a of adj_neg_r[b] = bit b of neg[a xor b]:  ADJR(g, X)[b] = sum_a +-w X[a] g[a xor b]
-        // GSQRT_JVP, GLOG_JVP: the sign words of the (non-transposed) right-multiplication matrix R_M[r][j] = +-w M[r xor j], (u M)[r] = sum_j R_M[r][j] u[j],
+        // GSQRT_JVP, GLOG_JVP, GLOG_ADJ2: the sign words of the (non-transposed) right-multiplication matrix R_M[r][j] = +-w M[r xor j], (u M)[r] = sum_j R_M[r][j] u[j],
         std::vector<uint64_t> rmul_neg;     // [N] bit j of rmul_neg[r]: e_a e_b = -(...) for a = S[j], b = S[r] xor S[j]; the metric factor is L's, weight[S[j] & ~S[r]]
     } inv;
 
@@ -247,6 +247,9 @@ struct Step {
     // GSQRT_JVP / GLOG_JVP (GAAST_OP_GSQRT_JVP / GAAST_OP_GLOG_JVP): res += the tangent of the root / the logarithm at A = row `a` in the
     // direction h = row `c` (inv.h_off: any blades of the set), in the wanted grades of the blade set.  Tables are GSQRT's / GLOG's and
     // inv.rmul_neg; the rows of L_X + R_X, L_M and R_M all come from inv.neg, inv.rmul_neg and inv.weight.  Always launches of their own.
+    // GLOG_ADJ2 (GAAST_OP_GLOG_ADJ2): res += the gradient in A of <g, GLOG_JVP(h, A)>, A = row `a`, g = row `b` (inv.g_off), h = row `c`
+    // (inv.h_off), both any blades of the set; inv.res_off addresses the operand's grades in res.  It solves with the plain and the
+    // transposed matrices, so it carries all four sign tables: inv.neg, inv.rmul_neg, inv.adj_neg_l, inv.adj_neg_r.  Always a launch of its own.
 
     // REDUCE_SCALE (plan_passes.cpp: fuse_reduce_scale): a product whose result is ONE scalar component (a single long row: norm_sq), an
     // optional ScalarUnaryOp on it, and a product of one-term rows that multiplies another row by that scalar -- the versor inverse

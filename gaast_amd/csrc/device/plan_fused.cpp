@@ -49,7 +49,7 @@ SlabLayout::SlabLayout(const Plan& p, bool small_reg_slab) : plan(p), elem(p.dty
     // which buffers are touched, and how inputs are read
     std::vector<int> in_direct(plan.inputs.size(), 0), in_axpy(plan.inputs.size(), 0);
     for (const Step& s : plan.steps) {
-        if (s.kind == Step::PRODUCT_DENSE || s.kind == Step::FUSED || s.kind == Step::INVERSE || s.kind == Step::GEXP || s.kind == Step::GEXP_ADJ || s.kind == Step::GSQRT || s.kind == Step::GSQRT_ADJ || s.kind == Step::GLOG || s.kind == Step::GLOG_ADJ || s.kind == Step::GEXP_JVP || s.kind == Step::GEXP_ADJ2 || s.kind == Step::GSQRT_JVP || s.kind == Step::GLOG_JVP) return;   // (an inverse, a general exponential, a general square root, a general logarithm, their adjoints, the exponential's second-order steps and the tangents of root and logarithm are always launches of their own)
+        if (s.kind == Step::PRODUCT_DENSE || s.kind == Step::FUSED || s.kind == Step::INVERSE || s.kind == Step::GEXP || s.kind == Step::GEXP_ADJ || s.kind == Step::GSQRT || s.kind == Step::GSQRT_ADJ || s.kind == Step::GLOG || s.kind == Step::GLOG_ADJ || s.kind == Step::GEXP_JVP || s.kind == Step::GEXP_ADJ2 || s.kind == Step::GSQRT_JVP || s.kind == Step::GLOG_JVP || s.kind == Step::GLOG_ADJ2) return;   // (an inverse, a general exponential, a general square root, a general logarithm, their adjoints, the second-order steps of exponential and logarithm and the tangents of root and logarithm are always launches of their own)
         if (s.kind == Step::AXPY) in_axpy[size_t(s.a.idx)] = 1;
         if (s.kind == Step::DUAL && s.a.kind == BufKind::INPUT) (s.canon_a ? in_direct : in_axpy)[size_t(s.a.idx)] = 1;
         if (s.kind == Step::PRODUCT_CSR) {

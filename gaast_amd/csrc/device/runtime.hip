@@ -226,6 +226,10 @@ struct Launch {
         DevTable a_off, res_off, g_off, neg, neg_l, neg_r, weight;
         const void* kernel = nullptr;   // k_mv_glog<T, N> / k_mv_glog_adj<T, N> / k_mv_jvp_glog<T, N>
     } glog;
+    struct {   // GLOG_ADJ2 (neg_m: the sign words of the right-multiplication matrix)
+        DevTable a_off, res_off, g_off, h_off, neg, neg_l, neg_r, neg_m, weight;
+        const void* kernel = nullptr;   // k_mv_adj2_glog<T, N>
+    } glog2;
     struct {   // PRODUCT_CSR: k_product_csr, k_product_ell, k_product_ell_chain or the specialised gaast_chain
         DevTable row_start, row_out, entries, coeff;
         struct { DevTable entries, row_map; } pre;        // k_product_ell_chain: the first list
@@ -858,6 +862,57 @@ int run_glog(const Launch& L, const Operands& o, int64_t batch) {
     p.dom = static_cast<unsigned long long*>(L.domain);
     const int64_t per_block = 256 / s.inv.N;
     launch_kernel(L.glog.kernel, persistent_grid((batch + per_block - 1) / per_block, 8), 256, 0, p);
+    return launch_status();
+}
+
+// ---- GLOG_ADJ2 -----------------------------------------------------------------------------------------------------------
+// (the second-order adjoint of the general logarithm: one kernel per (T, N), the tables of GLOG_ADJ and of GLOG_JVP together)
+template <typename T>
+int prepare_glog_adj2(Launch& L, std::string& kernel) {
+    Step& s = L.s;
+    auto& c = L.glog2;
+    using Kern = void (*)(GlogAdj2Args<T>);
+    c.kernel = kernel_address(static_int<2, 4, 8, 16, 32, 64>(s.inv.N, [](auto n) -> Kern { return k_mv_adj2_glog<T, decltype(n)::value>; }));
+    if (!c.kernel) return set_err(GAAST_ERR_UNIMPLEMENTED, "no general-logarithm kernel for " + std::to_string(s.inv.N) + " blades");
+    Upload<T> up;
+    up.idx(c.a_off, s.inv.a_off); up.idx(c.res_off, s.inv.res_off); up.idx(c.g_off, s.inv.g_off); up.idx(c.h_off, s.inv.h_off);
+    up.idx(c.neg, s.inv.neg); up.idx(c.neg_l, s.inv.adj_neg_l); up.idx(c.neg_r, s.inv.adj_neg_r); up.idx(c.neg_m, s.inv.rmul_neg);
+    up.val(c.weight, s.inv.weight);
+    kernel = std::string("k_mv_adj2_glog<") + type_name<T>() + "," + std::to_string(s.inv.N) + ">";
+    return up.status;
+}
+
+template <typename T>
+int run_glog_adj2(const Launch& L, const Operands& o, int64_t batch) {
+    const Step& s = L.s;
+    if (batch <= 0) return GAAST_OK;
+    GlogAdj2Args<T> p;
+    p.res = static_cast<T*>(o.res.ptr);
+    p.in = static_cast<const T*>(o.a.ptr);
+    p.cot = static_cast<const T*>(o.b.ptr);
+    p.tan = static_cast<const T*>(o.c.ptr);
+    p.res_stride = o.res.stride;
+    p.in_stride = o.a.stride;
+    p.cot_stride = o.b.stride;
+    p.tan_stride = o.c.stride;
+    p.batch = batch;
+    p.a_off = L.glog2.a_off.as<int32_t>();
+    p.res_off = L.glog2.res_off.as<int32_t>();
+    p.g_off = L.glog2.g_off.as<int32_t>();
+    p.h_off = L.glog2.h_off.as<int32_t>();
+    p.neg = L.glog2.neg.as<uint64_t>();
+    p.neg_l = L.glog2.neg_l.as<uint64_t>();
+    p.neg_r = L.glog2.neg_r.as<uint64_t>();
+    p.neg_m = L.glog2.neg_m.as<uint64_t>();
+    p.weight = L.glog2.weight.as<T>();
+    p.a_neg = s.inv.a_neg;
+    p.wmax = T(s.inv.wmax);
+    p.n = L.n;
+    p.even = s.inv.even;
+    p.beta = s.beta;
+    const int64_t per_block = 256 / s.inv.N;
+    const int per_cu = sizeof(T) == 8 ? 2 : 4;   // (what the static LDS of k_mv_adj2_glog leaves resident on a CU)
+    launch_kernel(L.glog2.kernel, persistent_grid((batch + per_block - 1) / per_block, per_cu), 256, 0, p);
     return launch_status();
 }
 
@@ -1802,6 +1857,7 @@ int prepare_launch(Launch& L, const gaast_hip_program_s& prog) {
     case Step::GLOG:
     case Step::GLOG_ADJ:
     case Step::GLOG_JVP: st = prepare_glog<T>(L, kernel); break;
+    case Step::GLOG_ADJ2: st = prepare_glog_adj2<T>(L, kernel); break;
     }
     if (st) return st;
     L.label = kernel.empty() ? s.name : s.name + " :: " + kernel;
@@ -2549,6 +2605,7 @@ int run_launch(const Launch& L, const Operands& o, int64_t batch) {
     case Step::GLOG:
     case Step::GLOG_ADJ:
     case Step::GLOG_JVP: st = run_glog<T>(L, o, batch); break;
+    case Step::GLOG_ADJ2: st = run_glog_adj2<T>(L, o, batch); break;
     }
     L.variant = variant;
     return st;

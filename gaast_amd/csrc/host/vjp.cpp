@@ -38,7 +38,8 @@
 // on it (their derivative is a Frechet derivative of a matrix function) -- except, under GAAST_FLAG_GEXP_GRAD2, the family of the
 // general exponential {GEXP_ADJ, GEXP_JVP, GEXP_ADJ2}, which has those kernels and is closed up to second order (gexp_family_adjoint),
 // and, under GAAST_FLAG_GSQRT_GLOG_JVP, the families {GSQRT_ADJ, GSQRT_JVP}, closed at every order, and {GLOG_ADJ, GLOG_JVP}, closed with
-// respect to child0 alone (root_log_family_adjoint).
+// respect to child0 alone (root_log_family_adjoint) -- and, with GAAST_FLAG_GLOG_GRAD2 beside it, with respect to the operand too, up to
+// second order, through GAAST_OP_GLOG_ADJ2.
 // Buffers are visited from the root down (decreasing node index: a buffer's users come after it in post-order).  The adjoint
 // program is evaluated in place as well, so every cotangent node it builds is ADDITIVE (input, product, or sums of them): adding
 // it into a buffer adds its value.  Sign changes and projections of a cotangent that cannot be folded into a list are explicit
@@ -66,10 +67,11 @@ struct VjpError {
 
 bool has_two_children(int opcode) {
     return opcode == GAAST_OP_ADD || opcode == GAAST_OP_PRODUCT || opcode == GAAST_OP_EXP_ADJ || opcode == GAAST_OP_LOG_ADJ || opcode == GAAST_OP_GEXP_ADJ || opcode == GAAST_OP_GSQRT_ADJ || opcode == GAAST_OP_GLOG_ADJ ||
-           opcode == GAAST_OP_GEXP_JVP || opcode == GAAST_OP_GEXP_ADJ2 || opcode == GAAST_OP_GSQRT_JVP || opcode == GAAST_OP_GLOG_JVP;
+           opcode == GAAST_OP_GEXP_JVP || opcode == GAAST_OP_GEXP_ADJ2 || opcode == GAAST_OP_GSQRT_JVP || opcode == GAAST_OP_GLOG_JVP ||
+           opcode == GAAST_OP_GLOG_ADJ2;
 }
-// GAAST_OP_GEXP_ADJ2 has a third child, the forward operand: its node index travels in input_slot (gaast_hip.h); -1 for every other node
-int third_child(const gaast_node_desc& nd) { return nd.opcode == GAAST_OP_GEXP_ADJ2 ? nd.input_slot : -1; }
+// GAAST_OP_GEXP_ADJ2 and GAAST_OP_GLOG_ADJ2 have a third child, the forward operand: its node index travels in input_slot (gaast_hip.h); -1 for every other node
+int third_child(const gaast_node_desc& nd) { return nd.opcode == GAAST_OP_GEXP_ADJ2 || nd.opcode == GAAST_OP_GLOG_ADJ2 ? nd.input_slot : -1; }
 
 // the adjoint op nodes that gaast_program_vjp itself emits (child0 = a cotangent, child1 = the forward operand)
 const char* adjoint_op_name(int opcode) {
@@ -82,6 +84,7 @@ const char* adjoint_op_name(int opcode) {
     case GAAST_OP_GEXP_JVP: return "GAAST_OP_GEXP_JVP";
     case GAAST_OP_GSQRT_JVP: return "GAAST_OP_GSQRT_JVP";
     case GAAST_OP_GLOG_JVP: return "GAAST_OP_GLOG_JVP";
+    case GAAST_OP_GLOG_ADJ2: return "GAAST_OP_GLOG_ADJ2";
     default: return nullptr;
     }
 }
@@ -321,14 +324,18 @@ struct Builder {
     // over (k, A).  For gsqrt the map is S^-1 with S = L_X + R_X, X the root of A:  d(S^-1) = -S^-1 (L_dX + R_dX) S^-1 and dX = S^-1 dA
     // give the gradient in A of <g, S^-1 h> as -GSQRT_ADJ(ADJ_LEFT(w, u) + ADJ_RIGHT(w, u), A) over geometric products, with
     // w = GSQRT_ADJ(g, A) and u = GSQRT_JVP(h, A) on every grade of the blade set.  The sign is a Negation of k, the innermost child,
-    // as inv_adjoint places it and for its reason.  For glog the gradient in A is not implemented.
+    // as inv_adjoint places it and for its reason.  For glog the gradient in A needs GAAST_FLAG_GLOG_GRAD2 as well and is one
+    // GAAST_OP_GLOG_ADJ2 node over (g, h, A), the two vectors of the pair in that order; a GLOG_ADJ2 node on the path is refused.
     void root_log_family_adjoint(int x, const std::vector<Term>& terms, std::vector<std::vector<Term>>& cot) {
         const gaast_node_desc& xd = d.nodes[x];
         const bool log = xd.opcode == GAAST_OP_GLOG_ADJ || xd.opcode == GAAST_OP_GLOG_JVP;
         const bool jvp = xd.opcode == GAAST_OP_GSQRT_JVP || xd.opcode == GAAST_OP_GLOG_JVP;
         const int op_adj = log ? GAAST_OP_GLOG_ADJ : GAAST_OP_GSQRT_ADJ, op_jvp = log ? GAAST_OP_GLOG_JVP : GAAST_OP_GSQRT_JVP;
         const int c0 = xd.child0, a = xd.child1;
-        if (log && dep[size_t(a)])
+        if (xd.opcode == GAAST_OP_GLOG_ADJ2)
+            throw VjpError{GAAST_ERR_UNIMPLEMENTED, "third-order reverse mode through GAAST_OP_GLOG_ADJ2 is not implemented"};
+        const bool grad2 = (d.flags & GAAST_FLAG_GSQRT_GLOG_JVP) && (d.flags & GAAST_FLAG_GLOG_GRAD2);
+        if (log && dep[size_t(a)] && !grad2)
             throw VjpError{GAAST_ERR_UNIMPLEMENTED, std::string("reverse mode through ") + adjoint_op_name(xd.opcode) + " with respect to its operand is not implemented"};
         const uint64_t amask = d.nodes[a].minimal_grade_mask, c0mask = d.nodes[c0].minimal_grade_mask;
         if (!dep[size_t(c0)] && !dep[size_t(a)]) return;
@@ -340,7 +347,13 @@ struct Builder {
             nd.child1 = a;
             cot[size_t(c0)].push_back(Term{add(nd), 0, ~0ULL});
         }
-        if (dep[size_t(a)]) {
+        if (dep[size_t(a)] && log) {   // GAAST_FLAG_GLOG_GRAD2: bilinear in (g, h) at A, one node (gaast_hip.h: GAAST_OP_GLOG_ADJ2)
+            gaast_node_desc nd = blank(GAAST_OP_GLOG_ADJ2, amask, n);
+            nd.child0 = jvp ? k : c0;    // g
+            nd.child1 = jvp ? c0 : k;    // h
+            nd.input_slot = a;
+            cot[size_t(a)].push_back(Term{add(nd), 0, ~0ULL});
+        } else if (dep[size_t(a)]) {
             const uint64_t smask = gs_inverse(amask, n);
             gaast_node_desc neg = blank(GAAST_OP_NEG, mask_of(k), n);
             neg.child0 = k;
@@ -579,6 +592,8 @@ struct Builder {
                         root_log_family_adjoint(e.node, terms, cot);   // (gsqrt: closed at every order; glog: with respect to child0)
                     } else if (x.opcode == GAAST_OP_GEXP_ADJ2) {
                         if (dep[size_t(e.node)]) gexp_family_adjoint(e.node, terms, cot);   // (refused, with or without the flag)
+                    } else if (x.opcode == GAAST_OP_GLOG_ADJ2) {
+                        if (dep[size_t(e.node)]) root_log_family_adjoint(e.node, terms, cot);   // (refused, with or without the flags)
                     } else if (const char* name = adjoint_op_name(x.opcode)) {   // its second derivative needs a Frechet-derivative kernel
                         if (dep[size_t(e.node)])
                             throw VjpError{GAAST_ERR_UNIMPLEMENTED, std::string("second-order reverse mode through ") + name + " is not implemented"};
@@ -641,10 +656,10 @@ extern "C" int gaast_program_vjp(const gaast_program_desc* desc, int32_t wrt_slo
         const gaast_node_desc& nd = d.nodes[i];
         const bool two = has_two_children(nd.opcode);
         const bool ok = nd.opcode == GAAST_OP_INPUT ? (nd.input_slot >= 0 && nd.input_slot < d.n_inputs)
-                        : (nd.opcode > GAAST_OP_INPUT && nd.opcode <= GAAST_OP_GLOG_JVP &&
+                        : (nd.opcode > GAAST_OP_INPUT && nd.opcode <= GAAST_OP_GLOG_ADJ2 &&
                            nd.child0 >= 0 && nd.child0 < i &&
                            (!two || (nd.child1 >= 0 && nd.child1 < i)) &&
-                           (nd.opcode != GAAST_OP_GEXP_ADJ2 || (nd.input_slot >= 0 && nd.input_slot < i)));
+                           ((nd.opcode != GAAST_OP_GEXP_ADJ2 && nd.opcode != GAAST_OP_GLOG_ADJ2) || (nd.input_slot >= 0 && nd.input_slot < i)));
         // a compact adjoint product (a VJP program differentiates again): GAAST_PROD_ADJ_LEFT or GAAST_PROD_ADJ_RIGHT over a kind 0..5
         const int adj = nd.product_kind & ~7, base = nd.product_kind & 7;
         const bool kind_ok = nd.opcode != GAAST_OP_PRODUCT || nd.product_kind < GAAST_PROD_ADJ_LEFT ||

@@ -201,7 +201,7 @@ void gaast_program_image_free(gaast_program_image_t img);
  * GAAST_OP_NEG, one more GAAST_OP_INV and two geometric adjoint products.
  * The adjoint op nodes GAAST_OP_EXP_ADJ, GAAST_OP_LOG_ADJ, GAAST_OP_GEXP_ADJ, GAAST_OP_GSQRT_ADJ and GAAST_OP_GLOG_ADJ are valid nodes
  * with two children; off the path to wrt_slot they are carried along untouched.  So are GAAST_OP_GEXP_JVP (two children) and
- * GAAST_OP_GEXP_ADJ2 (three: the third, the forward operand, is the node index in input_slot, which the renumbering of the image
+ * GAAST_OP_GEXP_ADJ2 / GAAST_OP_GLOG_ADJ2 (three: the third, the forward operand, is the node index in input_slot, which the renumbering of the image
  * follows like child0 and child1).
  * Second order through the general exponential (OPT-IN: GAAST_FLAG_GEXP_GRAD2 in desc->flags; only this function reads the flag, the
  * image inherits it).  With k the cotangent of the node's buffer restricted to the node's grades:
@@ -227,16 +227,23 @@ void gaast_program_image_free(gaast_program_image_t img);
  *     GLOG_ADJ(g, A)            g         GLOG_JVP(k, A), mask of g
  *     GLOG_JVP(h, A)            h         GLOG_ADJ(k, A), mask of h
  *     GLOG_ADJ / GLOG_JVP       A         GAAST_ERR_UNIMPLEMENTED ("reverse mode through GAAST_OP_GLOG_ADJ with respect to its operand ...")
+ *   and with GAAST_FLAG_GLOG_GRAD2 beside the flag (alone it changes nothing), in the place of the last line:
+ *     GLOG_ADJ(g, A)            A         GLOG_ADJ2(g, k, A), mask of A
+ *     GLOG_JVP(h, A)            A         GLOG_ADJ2(k, h, A), mask of A
+ *     GLOG_ADJ2                 any       GAAST_ERR_UNIMPLEMENTED ("third-order reverse mode through GAAST_OP_GLOG_ADJ2 ...")
  * The operand rule is the gradient in A of <g, S^-1 h>: d(S^-1) = -S^-1 (L_dX + R_dX) S^-1 and dX = S^-1 dA.  ADJ_LEFT / ADJ_RIGHT are
  * compact geometric adjoint products, the sign one GAAST_OP_NEG on k (the innermost child, as for GAAST_OP_INV); every node is one
  * the function emits elsewhere, so the family of gsqrt is closed at EVERY order.  A GLOG node is refused only when its operand
  * depends on wrt_slot; reached through child0 alone (forward mode) it is accepted.  Without the flag all four nodes on the path are
- * refused in the words of the five adjoint op nodes below, and images are what they were.
+ * refused in the words of the five adjoint op nodes below, and images are what they were.  GAAST_OP_GLOG_ADJ2 (gaast_hip.h) is the
+ * gradient in A of <g, GLOG_JVP(h, A)> with the roots of A held fixed, one node with three children like GAAST_OP_GEXP_ADJ2 (the third,
+ * the forward operand, in input_slot): with both flags the family {GLOG_ADJ, GLOG_JVP, GLOG_ADJ2} is closed up to second order.
  * Errors: GAAST_ERR_INVALID_ARGUMENT for a wrt_slot out of range or const, or n_inputs + 1 > GAAST_MAX_INPUTS;
  * GAAST_ERR_UNIMPLEMENTED for one of the five adjoint op nodes on the path to wrt_slot, through either child (the message names the
  * op: the second derivative of these matrix functions needs Frechet-derivative kernels, which the library has for gexp alone and
  * uses under GAAST_FLAG_GEXP_GRAD2; under GAAST_FLAG_GSQRT_GLOG_JVP gsqrt's node is differentiated by composition and glog's with
- * respect to its cotangent), and for GAAST_OP_GEXP_ADJ2 on the path (third order);
+ * respect to its cotangent, with GAAST_FLAG_GLOG_GRAD2 with respect to its operand too), and for GAAST_OP_GEXP_ADJ2 or
+ * GAAST_OP_GLOG_ADJ2 on the path (third order);
  * GAAST_ERR_UNIMPLEMENTED for GAAST_FLAG_SPINOR_GEMM, and for exp / log on the path to wrt_slot unless desc->flags holds both
  * GAAST_FLAG_EXP_LOG and GAAST_FLAG_EXP_LOG_GRAD: then the operand's cotangent is a GAAST_OP_EXP_ADJ / GAAST_OP_LOG_ADJ node
  * (gaast_hip.h) over the cotangent of the exp / log node's buffer and the forward operand (exp of a bare scalar, grade set {0},

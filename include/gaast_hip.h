@@ -307,7 +307,33 @@ typedef enum gaast_opcode {
      * with GAAST_OP_GLOG_ADJ's pivot tests.  <g, GLOG_JVP(h, A)> = <GLOG_ADJ(g, A), h>.  No domain check and no count: a domain-error
      * item of the recomputed forward, or a failed pivot, gives NaN in every produced component.  Accuracy: 4 LOG_JVP_SCALE in units
      * of N eps max(1, sum_i |(log A)_i|) ||J||_inf ||h||_inf (tests/root_log_jvp_numpy.py). */
-    GAAST_OP_GLOG_JVP = 25
+    GAAST_OP_GLOG_JVP = 25,
+    /* The gradient with respect to A of <g, GLOG_JVP(h, A)> = <GLOG_ADJ(g, A), h>: the adjoint of the second derivative of
+     * GAAST_OP_GLOG, the roots X_1 ... X_s and s taken from A alone, exactly as GAAST_OP_GLOG_ADJ takes them, and held fixed.
+     * Emitted by gaast_program_vjp under GAAST_FLAG_GSQRT_GLOG_JVP | GAAST_FLAG_GLOG_GRAD2; evaluating the node needs no flag.
+     * child0 = g and child1 = h, each any grades of the blade set S of the operand (absent blades read as 0; grades outside S:
+     * GAAST_ERR_INVALID_PROGRAM), and a THIRD child, the forward operand A, whose node index is carried in input_slot as
+     * GAAST_OP_GEXP_ADJ2 carries it (the node record and the wire format keep their bytes).  The node's own minimal grade mask is the
+     * operand's; it ADDS into its buffer.  With S_i = L_(X_i) + R_(X_i), E = X_s - e_0, M_j = e_0 + beta_j E and
+     * ADJL(G, Z) = R_Z^T G, ADJR(G, X) = L_X^T G:
+     *   up the chain:    t_0 = h;   S_i t_i = t_(i-1)  for i = 1 ... s  (GAAST_OP_GLOG_JVP's loop; every t_i is kept);
+     *   scale:           g' = 2^s g  (exact);
+     *   Pade, for j = 1 ... 7, j ascending, five solves per node:
+     *                    R_(M_j)^T v1 = g';   L_(M_j)^T u = v1;   L_(M_j)^T v2 = g';   L_(M_j) p = t_s;   R_(M_j) q = p;
+     *                    a <- a + alpha_j u                                      (GAAST_OP_GLOG_ADJ's first stage);
+     *                    gamma <- gamma - alpha_j beta_j (ADJR(v1, q) + ADJL(v2, q))   (the adjoint of the second derivative of
+     *                    the approximant: d(M^-1) = -beta M^-1 dE M^-1 on either side of q = M^-1 t_s M^-1);
+     *   down the chain:  w = a, e = gamma;  for i = s ... 1:
+     *                    w <- S_i^-T w;   e <- S_i^-T (e - (ADJR(w, t_i) + ADJL(w, t_i)))  with the new w
+     *                    (d(S_i^-1) = -S_i^-1 (L_dX + R_dX) S_i^-1 and dX_i = S_i^-1 dX_(i-1));
+     *   the result is e, restricted to the grades the operand holds.
+     * 35 + 3 s eliminations; ADJR(., q) and ADJL(., q) are N multiply-adds each and no solve.  Every solve is GAAST_OP_INV's
+     * elimination with GAAST_OP_GLOG_ADJ's pivot tests.  No domain check and no count, as GAAST_OP_GLOG_JVP: a domain-error item of
+     * the recomputed forward, or a failed pivot, gives NaN in every produced component.  Supported sizes are GAAST_OP_GLOG's.
+     * Accuracy, per item that is no domain error, against these recurrences in extended precision: 4 LOG_ADJ2_SCALE in units of
+     * N eps max(1, sum_i |(log A)_i|) ||G||_inf ||h||_inf, G the N x N matrix with GLOG_ADJ2(g, h, A) = G h (tests/glog_adj2_numpy.py
+     * records the scales: the worst error of a numpy restatement in the program's dtype). */
+    GAAST_OP_GLOG_ADJ2 = 26
 } gaast_opcode;
 
 /* the five products of src/ast/expr.rs:180-197 (and the regressive product), for compact PRODUCT descriptors */
@@ -414,11 +440,17 @@ typedef struct gaast_input_desc {
  * or GAAST_OP_GSQRT_JVP node on the path to the differentiated input gets GAAST_OP_GSQRT_JVP / GAAST_OP_GSQRT_ADJ nodes and adjoint
  * products (table in gaast_expr.h): forward mode and reverse mode of any order through gsqrt.  A GAAST_OP_GLOG_ADJ or
  * GAAST_OP_GLOG_JVP node reached through child0 alone gets GAAST_OP_GLOG_JVP / GAAST_OP_GLOG_ADJ: forward mode through glog; one
- * whose operand depends on the differentiated input stays GAAST_ERR_UNIMPLEMENTED.  Only gaast_program_vjp reads the flag; the
+ * whose operand depends on the differentiated input stays GAAST_ERR_UNIMPLEMENTED (unless GAAST_FLAG_GLOG_GRAD2 is set as well).  Only gaast_program_vjp reads the flag; the
  * adjoint program inherits it like every flag.  Without it such a node stays GAAST_ERR_UNIMPLEMENTED, and every status, message,
  * plan, launch name and bit is what it was before the flag existed.  The flag changes nothing in a forward program, and in a
  * first-order VJP image only the flags word. */
 #define GAAST_FLAG_GSQRT_GLOG_JVP 0x8000u
+/* OPT-IN, only meaningful together with GAAST_FLAG_GSQRT_GLOG_JVP: gaast_program_vjp differentiates a GAAST_OP_GLOG_ADJ or
+ * GAAST_OP_GLOG_JVP node with respect to its OPERAND too, by one GAAST_OP_GLOG_ADJ2 node (table in gaast_expr.h): Hessian-vector
+ * products and double backward through glog.  A GAAST_OP_GLOG_ADJ2 node on the path, third order, is GAAST_ERR_UNIMPLEMENTED.  Only
+ * gaast_program_vjp reads the flag; the adjoint program inherits it like every flag.  Without it -- and with it alone -- every
+ * status, message, image byte, plan and launch name is what it was before the flag existed. */
+#define GAAST_FLAG_GLOG_GRAD2 0x10000u
 #define GAAST_FLAG_DEBUG_LDS_12K 0x400u /* hiprtc-specialised kernels: 12 KiB instead of 10 KiB of LDS per wave for the row transposition (A/B testing) */
 #define GAAST_FLAG_DEBUG_NO_CHAIN 0x800u /* a sparse product that only feeds a dense product stays a launch of its own (default: evaluated in the dense kernel's LDS staging; A/B testing) */
 /* (bits 30 and 31 are reserved and ignored) */
@@ -668,7 +700,9 @@ int gaast_hip_eval_gather(gaast_hip_program_t prog, const gaast_hip_mv_t *inputs
  * (GAAST_OP_EXP_ADJ, LOG_ADJ, GEXP_ADJ, GSQRT_ADJ, GLOG_ADJ) on the path to wrt_slot: GAAST_ERR_UNIMPLEMENTED -- except GEXP_ADJ (and
  * GEXP_JVP) when desc->flags holds GAAST_FLAG_GEXP_GRAD2: second order and forward mode through gexp (gaast_expr.h has the table);
  * a GAAST_OP_GEXP_ADJ2 node on the path, third order, is GAAST_ERR_UNIMPLEMENTED.  GSQRT_ADJ / GSQRT_JVP (any order) and GLOG_ADJ /
- * GLOG_JVP (through child0: forward mode) differentiate when desc->flags holds GAAST_FLAG_GSQRT_GLOG_JVP. */
+ * GLOG_JVP (through child0: forward mode) differentiate when desc->flags holds GAAST_FLAG_GSQRT_GLOG_JVP; with GAAST_FLAG_GLOG_GRAD2
+ * beside it GLOG_ADJ / GLOG_JVP differentiate through their operand too (one GAAST_OP_GLOG_ADJ2 node: second order through glog),
+ * and a GAAST_OP_GLOG_ADJ2 node on the path, third order, is GAAST_ERR_UNIMPLEMENTED. */
 int gaast_hip_program_create_vjp(const gaast_program_desc *desc, int32_t wrt_slot, gaast_hip_program_t *out);
 /* gaast_program_vjp followed by gaast_hip_program_create_in_basis: the VJP of a program in a non-diagonal metric.  With the orthogonal
  * Q of the basis change, y_e = C(Q) F(C(Q^T) x_e) and every C_k(Q) is orthogonal, so the VJP of the in-basis program is the in-basis

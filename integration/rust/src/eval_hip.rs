@@ -212,7 +212,8 @@ impl<T: GradedData + std::fmt::Debug> SpecializedAst<T> {
                 // The general exponential (OP_GEXP) flattens the same way, with the same grade set; its adjoint node OP_GEXP_ADJ is only ever emitted by gaast_program_vjp,
                 // and so are OP_GEXP_JVP / OP_GEXP_ADJ2 (second order through gexp, under FLAG_GEXP_GRAD2; ADJ2's third child is the node index in input_slot).
                 // The general square root (OP_GSQRT / OP_GSQRT_ADJ) likewise; of a scalar child it is ScalarUnaryOp::Sqrt.
-                // OP_GSQRT_JVP / OP_GLOG_JVP (the tangents, two children like OP_GEXP_JVP) are only ever emitted by gaast_program_vjp, under FLAG_GSQRT_GLOG_JVP.
+                // OP_GSQRT_JVP / OP_GLOG_JVP (the tangents, two children like OP_GEXP_JVP) are only ever emitted by gaast_program_vjp, under FLAG_GSQRT_GLOG_JVP;
+                // OP_GLOG_ADJ2 (three children like OP_GEXP_ADJ2) under FLAG_GSQRT_GLOG_JVP | FLAG_GLOG_GRAD2.
                 // The general logarithm (OP_GLOG / OP_GLOG_ADJ) likewise, with no scalar lowering.
             }
             nodes.push(d);

@@ -42,6 +42,7 @@ pub const OP_GEXP_JVP: i32 = 22; // the Frechet derivative of gexp (child0 = the
 pub const OP_GEXP_ADJ2: i32 = 23; // its second-order adjoint (child0 = g, child1 = h, input_slot = the operand's node index)
 pub const OP_GSQRT_JVP: i32 = 24; // the tangent of gsqrt (child0 = the tangent, child1 = the operand): the transpose of OP_GSQRT_ADJ
 pub const OP_GLOG_JVP: i32 = 25; // the tangent of glog, likewise
+pub const OP_GLOG_ADJ2: i32 = 26; // the second-order adjoint of glog (child0 = g, child1 = h, input_slot = the operand's node index)
 // compact product kinds (gaast_product_kind); 5 = the regressive product a v b = undual(dual(a) ^ dual(b))
 pub const PROD_REGRESSIVE: i32 = 5;
 
@@ -51,6 +52,7 @@ pub const FLAG_EXP_LOG: u32 = 0x100; // opt-in extension: evaluate Exponential /
 pub const FLAG_EXP_LOG_GRAD: u32 = 0x2000; // with FLAG_EXP_LOG: gaast_hip_program_create_vjp differentiates through exp / log
 pub const FLAG_GEXP_GRAD2: u32 = 0x4000; // gaast_program_vjp differentiates through gexp's adjoint nodes (second order, forward mode)
 pub const FLAG_GSQRT_GLOG_JVP: u32 = 0x8000; // ... through gsqrt's adjoint nodes (any order) and glog's (forward mode)
+pub const FLAG_GLOG_GRAD2: u32 = 0x10000; // with FLAG_GSQRT_GLOG_JVP: ... and glog's with respect to the operand (second order)
 
 #[repr(C)]
 pub struct GaastCompMul {
